@@ -57,7 +57,32 @@ def parse():
                          "builds; probe builds: python -m primia_amd.build --probe)")
     ap.add_argument("--engine-opt", action="append", default=[], metavar="NAME=VALUE",
                     help="ResNet18Engine(options={NAME: VALUE}) (schedule switches of the engine)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (logits, loss, weights) as DIR/<name>.npy "
+                         "(rank 0): two builds run with the same arguments can then be compared output for output")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  When the total would exceed DUMP_LIMIT_BYTES, the largest
+    array is replaced by a fixed, seeded sample of its elements (<name>.npy) plus their flat indices (<name>_index.npy)."""
+    import numpy as np
+
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        big = max(host, key=lambda k: host[k].nbytes)
+        flat = host[big].reshape(-1)
+        # 4 bytes of value + 4 bytes of index per element; 4 KB left for the .npy headers
+        keep = (DUMP_LIMIT_BYTES - 4096 - (total - flat.nbytes)) // 8
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, size=keep, replace=False)).astype(np.int32)
+        host[big], host[big + "_index"] = flat[idx], idx
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def host_cpu():
@@ -281,6 +306,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, fedavg_ms = t[0].item(), round(t[1].item(), 3)
     loss = eng.loss.item()
+    if a.dump_outputs and rank == 0:
+        # the last timed step's results, before the legs below run more steps on the same engine.  Inputs are seeded
+        # (weights: torch.manual_seed(42); batches: generator 1000 + rank), so equal arguments mean equal inputs.
+        dump_outputs(a.dump_outputs, {"logits": eng.logits, "loss": eng.loss, "weights": eng.flat})
     # A second figure over >= 5 s of back-to-back steps: the 100-step region above lasts ~0.6 s, short enough for the
     # chip to ride its boost clock; this one shows what it sustains (same run() calls, own barriers).
     sustained = None
