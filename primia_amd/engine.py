@@ -38,8 +38,8 @@ class ResNet18Engine:
         """norm="batch": the reference model.  norm="group": GroupNorm(groups, C) in place of every
         BatchNorm (ResNet's `norm_layer` hook, torchlib/models.py:355) — the BN-free network the
         DP-SGD configuration needs (train.py:308).
-        `options`: {name: value} overriding the schedule switches below (class attributes such as wgrad_group,
-        wgrad_overlap, masked_acc, stem_bwd_fused, dp_keep ...) for THIS engine before its buffers are sized.  Nothing here
+        `options`: {name: value} overriding the schedule switches below (class attributes such as fwd_pair,
+        wgrad_overlap, wgrad_flush_last, fuse_stem, dp_keep ...) for THIS engine before its buffers are sized.  Nothing here
         reads the environment; the kernel library's own switches are `_lib.set_option` (primia_set_option).
         `share`: another engine of the same network whose PARAMETERS this one uses (see `sibling`)."""
         self._root = self if share is None else share._root
@@ -169,7 +169,7 @@ class ResNet18Engine:
         self._wg_count = {}        # shape key -> layers of that shape in the network
         self._wg_seen = {}         # shape key -> layers of that shape this backward pass has reached
         group_ws = [0]
-        if dtype == torch.bfloat16 and self.wgrad_group:
+        if dtype == torch.bfloat16:
             shapes = {}
             for c in self.spec.convs:
                 d = self.convs[c.name].desc
@@ -227,16 +227,14 @@ class ResNet18Engine:
                 t[key] = act(d1.Ho, blk.conv1.cout)
             din = t[key] if blk.down is None else act(d1.H, blk.conv1.cin)
             t[(blocks[i - 1].prefix + ".dout") if i > 0 else "pool.dout"] = din
-        # Fused BN statistics: the conv epilogue can accumulate the batch sums (primia_conv2d_fwd_stats).
-        # Measured on MI355X at batch 256 it is a wash — the epilogue reduction costs the forward kernels
-        # +0.38 ms/step, the separate statistics pass it removes costs 0.39 ms/step — so it stays off.
-        self.fuse_stats = False
         # stem tail bn1 -> relu -> maxpool as ONE fused op in training (z = relu(bn(y)) is never written)
         self.fuse_stem = True
         self._stem_fused = False
-        self.use_relu_masks = True   # residual layers: 1-bit ReLU masks for the backward passes (see _bn)
-        self.relu_masks = {}
-        self._stem_padded = False
+        self.relu_masks = {}         # residual layers: 1-bit ReLU masks for the backward passes (see _bn)
+        # the stem convolutions read the padded input copy; the unpadded one is written only where the halo kernels on the
+        # padded one do not serve the shape
+        self._stem_padded = self.x0p is not None
+        self._x0_valid = not self._stem_padded or (norm == "group" and self._stem_ws_bytes <= 0)
         self.stat_slots = query("primia_conv_stat_slots")
         for c in self.spec.convs:   # slots the kernel serving this conv writes (per-block partials for layer1's)
             self.convs[c.name].stat_slots = (query("primia_conv_stat_slots_for", self.convs[c.name].desc, self.dt)
@@ -248,8 +246,7 @@ class ResNet18Engine:
             self.convs[c.name].sums = self.stat_sums[off:off + per(c)]
             off += per(c)
         # Layers whose conv kernel emits the BatchNorm partial sums for free (deterministic per-block partials out
-        # of the write-back phase): the statistics pass over their output is dropped.  Decided per layer,
-        # independent of the global `fuse_stats` experiment above.
+        # of the write-back phase): the statistics pass over their output is dropped.
         self.free_stats = {c.name for c in self.spec.convs
                            if dtype == torch.bfloat16 and norm == "batch" and c.name != "conv1"
                            and query("primia_conv_stats_per_tile", self.convs[c.name].desc, self.dt) == 1}
@@ -257,12 +254,9 @@ class ResNet18Engine:
         # batch sums for the late stages, and BatchNorm-backward sums emitted by the data-gradient kernels' write-backs —
         # 6.375 -> 6.449 ms per step.)
         # identity blocks: can conv1's accumulating data gradient apply bn2's ReLU mask to the old values itself?
-        self.masked_acc_ok = {}
-        if self.masked_acc:
-            for blk in self.spec.blocks:
-                if blk.down is None:
-                    self.masked_acc_ok[blk.conv1.name] = query("primia_conv_dgrad_masked_acc_ok",
-                                                               self.convs[blk.conv1.name].desc, self.dt) == 1
+        self.masked_acc_ok = {blk.conv1.name: query("primia_conv_dgrad_masked_acc_ok", self.convs[blk.conv1.name].desc,
+                                                    self.dt) == 1
+                              for blk in self.spec.blocks if blk.down is None}
         self.save = {}
         for c in self.spec.convs:
             b = bn_name(c.name)
@@ -280,9 +274,6 @@ class ResNet18Engine:
                               for c in self.spec.convs}
             self.ones_n = torch.ones(N, dtype=torch.float32, device=dev)
         self.bn_ws = torch.zeros(self.bn_ws_bytes, dtype=torch.uint8, device=dev)  # holds a completion counter
-        # bn_inline: one flag word per 4 channels and BatchNorm layer (primia_bn_fwd_train_apply_inline), cleared once per step
-        self.bn_flags = torch.zeros(len(self.spec.convs) * 128, dtype=torch.int32, device=dev)
-        self._bn_flag_of = {bn_name(c.name): i * 128 for i, c in enumerate(self.spec.convs)}
         self.dp = None  # set by dp_backward: {"wgrads": [...]} defers the weight gradients
         self.feat = torch.empty(N, 512, dtype=torch.float32, device=dev)
         self.dfeat = torch.empty(N, 512, dtype=torch.float32, device=dev)
@@ -427,7 +418,7 @@ class ResNet18Engine:
         g, be = self.views[b + ".weight"], self.views[b + ".bias"]
         if self.norm == "group":  # identical in train and eval mode: no running statistics
             sm, si = self.save[b]
-            if self.training and residual is not None and relu and self.use_relu_masks and self.gn_relu_masks:
+            if self.training and residual is not None and relu and self.gn_relu_masks:
                 # residual layer: also write the 1-bit ReLU mask the backward passes read instead of z
                 if b not in self.relu_masks:
                     self.relu_masks[b] = torch.empty(y.numel() * y.element_size() // 16, dtype=torch.uint8, device=y.device)
@@ -438,30 +429,19 @@ class ResNet18Engine:
                  self.bn_ws, self.bn_ws_bytes, self.dt)
             return
         rm, rv = self.views[b + ".running_mean"], self.views[b + ".running_var"]
-        if self.training and residual is not None and relu and self.use_relu_masks:
+        if self.training and residual is not None and relu:
             # residual layer: also write the 1-bit ReLU mask the backward passes read instead of z
             sm, si = self.save[b]
             if b not in self.relu_masks:
                 self.relu_masks[b] = torch.empty(y.numel() * y.element_size() // 16, dtype=torch.uint8, device=y.device)
-            have_sums = self.fuse_stats or conv_name in self.free_stats
-            if have_sums and self.bn_inline:
-                fl = self.bn_flags[self._bn_flag_of[b]:self._bn_flag_of[b] + 128]
-                call("primia_bn_fwd_train_apply_inline", y, residual, z, self.relu_masks[b], g, be, rm, rv, sm, si,
-                     self.convs[conv_name].sums, self.convs[conv_name].stat_slots, M, C, BN_EPS, BN_MOMENTUM, 1, fl, self.dt)
-                self.num_batches_tracked[b] += 1
-                return
+            have_sums = conv_name in self.free_stats
             call("primia_bn_fwd_train_mask", y, residual, z, self.relu_masks[b], g, be, rm, rv, sm, si,
                  self.convs[conv_name].sums if have_sums else None, self.convs[conv_name].stat_slots if have_sums else 0,
                  M, C, BN_EPS, BN_MOMENTUM, self.bn_ws, self.bn_ws_bytes, self.dt)
             self.num_batches_tracked[b] += 1
         elif self.training:
             sm, si = self.save[b]
-            if (self.fuse_stats or conv_name in self.free_stats) and self.bn_inline:
-                fl = self.bn_flags[self._bn_flag_of[b]:self._bn_flag_of[b] + 128]
-                call("primia_bn_fwd_train_apply_inline", y, residual, z, None, g, be, rm, rv, sm, si,
-                     self.convs[conv_name].sums, self.convs[conv_name].stat_slots, M, C, BN_EPS, BN_MOMENTUM, int(relu), fl,
-                     self.dt)
-            elif self.fuse_stats or conv_name in self.free_stats:
+            if conv_name in self.free_stats:
                 call("primia_bn_fwd_train_from_sums", y, residual, z, g, be, rm, rv, sm, si,
                      self.convs[conv_name].sums, self.convs[conv_name].stat_slots, M, C, BN_EPS, BN_MOMENTUM,
                      int(relu), self.dt)
@@ -480,35 +460,6 @@ class ResNet18Engine:
     # accumulating data gradient turns the same buffer into the gradient of the block in front.
     taps = None
 
-    # the BatchNorm finalize launch folded into the apply kernel (primia_bn_fwd_train_apply_inline): bit-identical, and
-    # SLOWER — 4.745 -> 4.79 ms per step, same box: 2,048 apply blocks each fetching 2C constants through agent-scope loads
-    # contend at the coherence point the way the producers' atomics did (profiles/r05_bn_finalize_atomics.txt).  Off.
-    bn_inline = False
-    # conv2's data gradient also forms the backward sums of bn1 (primia_conv2d_dgrad_bnsums + primia_bn_relu_bwd_from_sums):
-    # the reduction pass over (y1, da1) is dropped where the linear-halo kernels serve conv2
-    dgrad_bnsums = True
-    # ... and the transition block's paired data gradient the sums of the residual BatchNorm in front of the block
-    # (primia_conv2d_dgrad_pair_bnsums: conv_s2lh_kernel for 64-channel dx, conv_igemm_kernel's parity-class walk for layer3.0 /
-    # layer4.0).  The 64-channel one alone measured neutral (4.770 vs 4.770 ms); with the two igemm launches, whose LDS
-    # write-back loop already walks 16-byte chunks of whole pixel rows, 4.882 -> 4.862 ms (8 alternating rounds, one box).
-    pair_bnsums = True
-    # ... and the ACCUMULATING data gradient of a 64 -> 64 identity block's conv1 the sums of the BatchNorm whose output gradient
-    # it completes: layer1.0's bn2 (layer1.1.conv1) and the stem's bn1 through the max-pool (layer1.0.conv1) —
-    # primia_conv2d_dgrad_masked_acc_bnsums; the two most expensive reduction passes of the step (43 + 48 us)
-    acc_bnsums = True
-    # ... and the head's backward pass the sums of the last block's bn2 (primia_head_bwd_bnsums)
-    head_bnsums = True
-    # conv1 + downsample data gradients of a transition block in one pass (primia_conv2d_dgrad_pair)
-    pair_dgrad = True
-    # identity blocks: conv1's accumulating data gradient applies bn2's ReLU mask to the old values itself
-    masked_acc = True
-    # transition blocks: bn2's and the downsample BatchNorm's backward passes as one (primia_bn_bwd_pair)
-    bn_pair = True
-    # order of a layer's two gradient kernels: weight gradient first, so that the BatchNorm backward pass that follows
-    # the data gradient reads it while it is still in the Infinity Cache (6.42 -> 6.39 ms per step; wgrad_first = False
-    # restores the other order)
-    wgrad_first = True
-
     @staticmethod
     def _macs(c):
         d = c.desc
@@ -525,7 +476,7 @@ class ResNet18Engine:
 
     def _conv_fwd(self, name, x, y):
         c = self.convs[name]
-        if self.training and (self.fuse_stats or name in self.free_stats):
+        if self.training and name in self.free_stats:
             self._timed("fwd", c, lambda: call("primia_conv2d_fwd_stats", c.desc, x, c.w_fwd, y, c.sums, self.dt))
         else:
             self._timed("fwd", c, lambda: call("primia_conv2d_fwd", c.desc, x, c.w_fwd, y, self.dt))
@@ -551,8 +502,8 @@ class ResNet18Engine:
         if not c1.pair_ok:
             return False
         stats = self.training and self.norm == "batch"
-        s1 = c1.sums if stats and (self.fuse_stats or blk.conv1.name in self.free_stats) else None
-        sd = cd.sums if stats and (self.fuse_stats or blk.down.name in self.free_stats) else None
+        s1 = c1.sums if stats and blk.conv1.name in self.free_stats else None
+        sd = cd.sums if stats and blk.down.name in self.free_stats else None
         if stats and (s1 is None or sd is None):
             return False        # (a layer whose statistics come from a separate pass: keep the single launches)
         self._timed("fwd", c1, lambda: call("primia_conv2d_fwd_stats_pair", c1.desc, x, c1.w_fwd, y1, s1, cd.desc, cd.w_fwd,
@@ -568,13 +519,6 @@ class ResNet18Engine:
         if query("primia_options_epoch") != self._options_epoch:
             raise _lib.PrimiaError("library options changed (primia_set_option) after this engine sized its buffers: "
                                    "set options first, then construct the engine")
-        if self.training and self.fuse_stats:
-            self.stat_sums.zero_()
-        if self.training and self.bn_inline and self.norm == "batch":
-            self.bn_flags.zero_()
-        self._stem_padded = self.x0p is not None and not (self.training and self.fuse_stats)
-        # (the unpadded copy is read only where the halo kernels on the padded one do not serve the shape)
-        self._x0_valid = not self._stem_padded or (self.norm == "group" and self._stem_ws_bytes <= 0)
         if self._x0_valid:
             call("primia_nchw_to_nhwc", x_nchw, self.x0, N, self.spec.in_channels, S, S, 4, self.dt)
         stem_done = False
@@ -588,29 +532,25 @@ class ResNet18Engine:
                     self._stem_sums = torch.zeros(self._stem_slots, 2, 64, dtype=torch.float32, device=self.device)
                 self._timed("fwd", c, lambda: call("primia_stem_conv_fwd_stats", self.x0p, c.w_fwd, t["stem.y"],
                                                    self._stem_sums, N, S, S, self.dt))
-                self._stem_has_sums = True
             elif self._stem_eval_one_pass():
                 # eval mode: conv1 -> bn1 -> relu -> maxpool as one pass over the input (neither stem tensor is written)
                 call("primia_stem_conv_pool_eval", self.x0p, c.w_fwd, t["pool.out"], self.pool_argmax,
                      self.views["bn1.weight"], self.views["bn1.bias"], self.views["bn1.running_mean"],
                      self.views["bn1.running_var"], BN_EPS, N, S, S, self.dt)
-                self._stem_has_sums = False
                 stem_done = True
             else:
                 self._timed("fwd", c, lambda: call("primia_stem_conv_fwd", self.x0p, c.w_fwd, t["stem.y"], N, S, S,
                                                    self.dt))
-                self._stem_has_sums = False
         else:
             self._conv_fwd("conv1", self.x0, t["stem.y"])
         hw = self.stem_hw
-        self._stem_fused = (self.fuse_stem and self.training and self.norm == "batch" and self.spec.pooling == "max"
-                            and not self.fuse_stats)
+        self._stem_fused = self.fuse_stem and self.training and self.norm == "batch" and self.spec.pooling == "max"
         # GroupNorm: gn1 -> relu -> maxpool as one op each way (primia_gn_relu_maxpool_fwd / _bwd; _bwd wants even sizes)
         self._stem_fused_gn = (self.fuse_stem and self.gn_stem_fused and self.norm == "group"
                                and self.spec.pooling == "max" and hw % 2 == 0)
         if stem_done:
             pass
-        elif self._stem_fused and getattr(self, "_stem_has_sums", False) and self._stem_padded:
+        elif self._stem_fused and self._stem_padded:     # (bn1's sums came with the padded-input stem conv above)
             sm, si = self.save["bn1"]
             call("primia_bn_relu_maxpool_fwd_from_sums", t["stem.y"], t["pool.out"], self.pool_argmax,
                  self.views["bn1.weight"], self.views["bn1.bias"], self.views["bn1.running_mean"],
@@ -645,7 +585,7 @@ class ResNet18Engine:
             self._bn(blk.conv1.name, t[p + ".y1"], t[p + ".a1"], None, True)
             self._conv_fwd(blk.conv2.name, t[p + ".a1"], t[p + ".y2"])
             idn = x
-            if blk.down is not None and self.training and self.norm == "batch" and self.use_relu_masks and self.bn_pair:
+            if blk.down is not None and self.training and self.norm == "batch":
                 # transition block: both BatchNorms in one apply pass (the downsample branch's output is never stored)
                 if not down_done:
                     self._conv_fwd(blk.down.name, x, t[p + ".yd"])
@@ -655,9 +595,9 @@ class ResNet18Engine:
                     self.relu_masks[b2] = torch.empty(y2.numel() * y2.element_size() // 16, dtype=torch.uint8,
                                                       device=y2.device)
                 c2 = self.convs[blk.conv2.name]
-                have = self.fuse_stats or blk.conv2.name in self.free_stats
+                have = blk.conv2.name in self.free_stats
                 cd = self.convs[blk.down.name]
-                have_d = self.fuse_stats or blk.down.name in self.free_stats
+                have_d = blk.down.name in self.free_stats
                 (sm2, si2), (smd, sid) = self.save[b2], self.save[bd]
                 call("primia_bn_fwd_train_pair", y2, t[p + ".yd"], t[p + ".out"], self.relu_masks[b2],
                      self.views[b2 + ".weight"], self.views[b2 + ".bias"], self.views[b2 + ".running_mean"],
@@ -712,7 +652,7 @@ class ResNet18Engine:
         if self.norm == "group":
             psg, psb = self.ps_affine[b]
             C = y.shape[1]
-            if relu and g_out is None and self.gn_relu_recompute:
+            if relu and g_out is None:
                 # z = relu(gn(y)), no residual: the mask is recomputed from y, z is not read
                 call("primia_gn_relu_bwd", y, dz, dy, self.views[b + ".weight"], self.views[b + ".bias"], sm, si, psg, psb,
                      self.N, y.shape[0] // self.N, C, self.groups, self.bn_ws, self.bn_ws_bytes, self.dt)
@@ -748,25 +688,21 @@ class ResNet18Engine:
         call("primia_bn_bwd", y, z, dz, dy, g_out, self.views[b + ".weight"], sm, si, self._gviews[b + ".weight"],
              self._gviews[b + ".bias"], y.shape[0], y.shape[1], int(relu), self.bn_ws, self.bn_ws_bytes, self.dt)
 
-    wgrad_pair = True
     # a stage's LAST same-shape layer does not wait for a group that can no longer fill (layer4 at batch 256: groups of 2 for 3
     # layers): its weight gradient runs as soon as its dy exists instead of at the end of the backward pass (round 6)
     wgrad_flush_last = True
-    gn_relu_recompute = True
     # GroupNorm residual layers with the BatchNorm path's 1-bit ReLU masks (and its mask-applying accumulate dgrad)
     gn_relu_masks = True
-    gn_ds_mask = True
     gn_stem_fused = True
-    wgrad_group = True
-    # (all 13 layers in ONE launch at the end of the backward pass was built and measured no better than the per-stage
-    # groups — 5.16 vs 5.14 ms: by then every operand comes from HBM, while a stage's group still finds its newest dy in
-    # the Infinity Cache — and is not kept: profiles/r03_negative_results.txt)
+    # (bf16: a stage's same-shape 3x3 weight gradients run as one launch, primia_conv2d_wgrad_group_ws.  All 13 layers in ONE
+    # launch at the end of the backward pass was built and measured no better than the per-stage groups — 5.16 vs 5.14 ms:
+    # by then every operand comes from HBM, while a stage's group still finds its newest dy in the Infinity Cache — and is
+    # not kept: profiles/r03_negative_results.txt)
 
     def _wgrad_transition(self, blk, x, dy1, dyd):
         """conv1 and the downsample of a transition block: one launch where the library serves the pair."""
         c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
-        if (self.wgrad_pair and self.dp is None and self.wgrad_ws is not None
-                and self._pair_ws.get(blk.conv1.name, 0) > 0):
+        if self.dp is None and self.wgrad_ws is not None and self._pair_ws.get(blk.conv1.name, 0) > 0:
             self._on_wgrad_stream(lambda: self._timed(
                 "wgrad", c1, lambda: call("primia_conv2d_wgrad_pair_ws", c1.desc, x, dy1, c1.acc, cd.desc, dyd, cd.acc,
                                           self.wgrad_ws, self.wgrad_ws_bytes, self.dt), extra_macs=self._macs(cd)), transition=True)
@@ -806,7 +742,6 @@ class ResNet18Engine:
     # Re-measured in round 3 with the workspace kernels (wgrad_overlap = 1: the schedule above; = 2: the weight
     # gradients free-running on the second stream until the finalize): see profiles/r03_negative_results.txt.
     wgrad_overlap = 0
-    stem_bwd_fused = True
 
     def _on_wgrad_stream(self, fn, transition=False):
         if self.wgrad_overlap == 3 and not transition and self.prof is None:
@@ -840,7 +775,7 @@ class ResNet18Engine:
         if getattr(self, "_stem_bwd_fused_ok", None) is None:     # asked once: the library's own gate for this shape
             S0 = self.spec.input_size
             self._stem_bwd_fused_ok = query("primia_stem_bwd_fused_ok", self.N, S0, S0, self.dt) == 1
-        return bool(self._stem_fused and self._stem_padded and self.dp is None and self.stem_bwd_fused
+        return bool(self._stem_fused and self._stem_padded and self.dp is None
                     and self.wgrad_ws is not None and self._stem_bwd_fused_ok)
 
     def _dgrad_bnsums_slots(self, name):
@@ -856,14 +791,140 @@ class ResNet18Engine:
             tab[name] = torch.empty(slots * 2 * channels, dtype=torch.float32, device=self.device)
         return tab[name]
 
-    def _dgrad(self, name, dy, dx, accumulate, consumer=None, consumer_y=None):
-        """Data gradient of conv `name` into dx (`consumer`, `consumer_y`: the conv whose BatchNorm backward reads dx
-        next — kept in the signature for the callers; the kernels no longer form that BatchNorm's sums, see __init__)."""
+    def _dgrad(self, name, dy, dx, accumulate):
+        """Data gradient of conv `name` into dx (accumulate: added to what dx holds)."""
         c = self.convs[name]
         if self.wgrad_overlap == 1:
             self._join_wgrad_stream()   # (narrow overlap) two MFMA-bound kernels never run side by side
         self._timed("dgrad", c,
                     lambda: call("primia_conv2d_dgrad", c.desc, dy, c.w_dgrad, dx, int(accumulate), self.dt))
+
+    def _backward_conv2(self, blk):
+        """conv2's weight and data gradients, then bn1's backward pass.  The weight gradient goes first, so that the
+        BatchNorm backward pass finds the data gradient it reads still in the Infinity Cache."""
+        t, p = self.t, blk.prefix
+        self._wgrad(blk.conv2.name, t[p + ".a1"], t[p + ".dy2"])
+        # where the linear-halo kernels serve conv2, its data gradient also forms bn1's backward sums
+        # (primia_conv2d_dgrad_bnsums): the reduction pass over (y1, da1) is dropped
+        slots = self._dgrad_bnsums_slots(blk.conv2.name) if self.norm == "batch" else 0
+        if not slots:
+            self._dgrad(blk.conv2.name, t[p + ".dy2"], t[p + ".da1"], False)
+            self._bn_bwd(blk.conv1.name, t[p + ".y1"], t[p + ".a1"], t[p + ".da1"], t[p + ".dy1"], None, True)
+            return
+        c2, b1 = self.convs[blk.conv2.name], bn_name(blk.conv1.name)
+        sm1, si1 = self.save[b1]
+        if self.wgrad_overlap == 1:
+            self._join_wgrad_stream()   # (as _dgrad does: two MFMA-bound kernels never run side by side)
+        sums = self._bwd_sums(blk.conv2.name, slots, blk.conv1.cout)
+        self._timed("dgrad", c2, lambda: call(
+            "primia_conv2d_dgrad_bnsums", c2.desc, t[p + ".dy2"], c2.w_dgrad, t[p + ".da1"], t[p + ".y1"], sm1, si1,
+            self.views[b1 + ".weight"], self.views[b1 + ".bias"], sums, self.dt))
+        y1 = t[p + ".y1"]
+        call("primia_bn_relu_bwd_from_sums", y1, t[p + ".da1"], t[p + ".dy1"], self.views[b1 + ".weight"],
+             self.views[b1 + ".bias"], sm1, si1, self._gviews[b1 + ".weight"], self._gviews[b1 + ".bias"], sums, slots,
+             y1.shape[0], y1.shape[1], self.dt)
+
+    def _backward_identity(self, blk, prev, x_in, dx_in):
+        """Identity block: dx_in aliases dout, which conv1's accumulating data gradient completes in place."""
+        t, p = self.t, blk.prefix
+        dout, dy1 = t[p + ".dout"], t[p + ".dy1"]
+        b2 = bn_name(blk.conv2.name)
+        # bn2 (+residual, relu): dy2, and the masked gradient g written back over dout — unless conv1's accumulating data
+        # gradient can apply bn2's ReLU mask to the old values itself (one tensor write less)
+        masked_acc = self.masked_acc_ok[blk.conv1.name] and b2 in self.relu_masks
+        self._bn_bwd(blk.conv2.name, t[p + ".y2"], t[p + ".out"], dout, t[p + ".dy2"], dout, True, keep_g=not masked_acc,
+                     from_sums=self._dout_sums.pop(p, None))
+        self._backward_conv2(blk)
+        self._wgrad(blk.conv1.name, x_in, dy1)
+        if not masked_acc:
+            self._dgrad(blk.conv1.name, dy1, dx_in, True)
+            return
+        c1 = self.convs[blk.conv1.name]
+        if self.wgrad_overlap == 1:
+            self._join_wgrad_stream()
+        # ... whose write-back also forms the backward sums of the BatchNorm whose output gradient it completes
+        # (primia_conv2d_dgrad_masked_acc_bnsums; 64 -> 64 layers): the previous block's bn2 (mode 2), or the stem's bn1
+        # through the max-pool (mode 3) — the two most expensive reduction passes of the step (43 + 48 us)
+        mode = 0
+        if self.norm == "batch" and self.dp is None and self.dtype == torch.bfloat16:
+            if prev is not None and prev.down is None and bn_name(prev.conv2.name) in self.relu_masks:
+                mode = 2
+            elif prev is None and self._stem_bwd_fused_wanted():
+                mode = 3
+        if mode and getattr(c1, "acc_bnsums_slots", None) is None:
+            c1.acc_bnsums_slots = query("primia_conv_dgrad_masked_acc_bnsums_slots", c1.desc, self.dt)
+        slots = c1.acc_bnsums_slots if mode else 0
+        if slots > 0 and mode == 2:
+            sums = self._bwd_sums(blk.conv1.name + ".acc", slots, prev.conv2.cout)
+            pb2 = bn_name(prev.conv2.name)
+            smp, sip = self.save[pb2]
+            self._timed("dgrad", c1, lambda: call(
+                "primia_conv2d_dgrad_masked_acc_bnsums", c1.desc, dy1, c1.w_dgrad, dx_in, self.relu_masks[b2], 2,
+                t[prev.prefix + ".y2"], self.relu_masks[pb2], smp, sip, sums, self.dt))
+            self._dout_sums[prev.prefix] = (sums, slots)
+        elif slots > 0:
+            sums = self._bwd_sums(blk.conv1.name + ".acc", slots, 64)
+            self._timed("dgrad", c1, lambda: call(
+                "primia_conv2d_dgrad_masked_acc_bnsums", c1.desc, dy1, c1.w_dgrad, dx_in, self.relu_masks[b2], 3,
+                t["pool.out"], None, self.views["bn1.bias"], self.views["bn1.weight"], sums, self.dt))
+            self._pool_sums = (sums, slots)
+        else:
+            self._timed("dgrad", c1, lambda: call("primia_conv2d_dgrad_masked_acc", c1.desc, dy1, c1.w_dgrad, dx_in,
+                                                  self.relu_masks[b2], self.dt))
+
+    def _backward_transition(self, blk, prev, x_in, dx_in):
+        """Transition block: both BatchNorm backward passes, then ONE weight-gradient and ONE data-gradient launch for
+        conv1 + downsample (primia_conv2d_dgrad_pair)."""
+        t, p = self.t, blk.prefix
+        dout, dy1, dyd = t[p + ".dout"], t[p + ".dy1"], t[p + ".dyd"]
+        b2, bd = bn_name(blk.conv2.name), bn_name(blk.down.name)
+        masked = b2 in self.relu_masks
+        if masked and self.norm == "batch":
+            # bn2 and the downsample BatchNorm share the incoming gradient -> ONE fused backward pass (primia_bn_bwd_pair)
+            (sm2, si2), (smd, sid) = self.save[b2], self.save[bd]
+            call("primia_bn_bwd_pair", t[p + ".y2"], t[p + ".yd"], dout, self.relu_masks[b2], t[p + ".dy2"], dyd,
+                 self.views[b2 + ".weight"], sm2, si2, self.views[bd + ".weight"], smd, sid, self._gviews[b2 + ".weight"],
+                 self._gviews[b2 + ".bias"], self._gviews[bd + ".weight"], self._gviews[bd + ".bias"],
+                 t[p + ".y2"].shape[0], t[p + ".y2"].shape[1], self.bn_ws, self.bn_ws_bytes, self.dt)
+        else:
+            # GroupNorm: the downsample's backward pass applies bn2's ReLU mask to dout itself (primia_gn_bwd_mask on yd,
+            # below), so the masked gradient is not written here
+            self._bn_bwd(blk.conv2.name, t[p + ".y2"], t[p + ".out"], dout, t[p + ".dy2"], dout, True, keep_g=not masked)
+        self._backward_conv2(blk)
+        if masked and self.norm == "group":
+            (smd, sid), (psg, psb) = self.save[bd], self.ps_affine[bd]
+            yd = t[p + ".yd"]
+            call("primia_gn_bwd_mask", yd, self.relu_masks[b2], dout, dyd, None, self.views[bd + ".weight"], smd, sid, psg,
+                 psb, self.N, yd.shape[0] // self.N, yd.shape[1], self.groups, self.bn_ws, self.bn_ws_bytes, self.dt)
+            if self.dp is None:
+                call("primia_weighted_colsum", psg, self.ones_n, self._gviews[bd + ".weight"], self.N, yd.shape[1])
+                call("primia_weighted_colsum", psb, self.ones_n, self._gviews[bd + ".bias"], self.N, yd.shape[1])
+        elif not masked:
+            self._bn_bwd(blk.down.name, t[p + ".yd"], None, dout, dyd, None, False)
+        c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
+        if self.wgrad_overlap == 1:
+            self._join_wgrad_stream()
+        self._wgrad_transition(blk, x_in, dy1, dyd)
+        # the paired data gradient also forms the backward sums of the residual BatchNorm in front of the block
+        # (primia_conv2d_dgrad_pair_bnsums: conv_s2lh_kernel for 64-channel dx, conv_igemm_kernel's parity-class walk for
+        # layer3.0 / layer4.0)
+        pslots = 0
+        pb2 = bn_name(prev.conv2.name) if prev is not None else None
+        if (self.norm == "batch" and self.dp is None and prev is not None and prev.down is None and pb2 in self.relu_masks
+                and self.dtype == torch.bfloat16):
+            if getattr(c1, "pair_bnsums_slots", None) is None:
+                c1.pair_bnsums_slots = query("primia_conv_dgrad_pair_bnsums_slots", c1.desc, self.dt)
+            pslots = c1.pair_bnsums_slots
+        if pslots > 0:
+            sums = self._bwd_sums(blk.conv1.name + ".pair", pslots, prev.conv2.cout)
+            smp, sip = self.save[pb2]
+            self._timed("dgrad", c1, lambda: call(
+                "primia_conv2d_dgrad_pair_bnsums", c1.desc, dy1, c1.w_dgrad, cd.desc, dyd, cd.w_dgrad, dx_in,
+                t[prev.prefix + ".y2"], self.relu_masks[pb2], smp, sip, sums, self.dt), extra_macs=self._macs(cd))
+            self._dout_sums[prev.prefix] = (sums, pslots)
+        else:
+            self._timed("dgrad", c1, lambda: call("primia_conv2d_dgrad_pair", c1.desc, dy1, c1.w_dgrad, cd.desc, dyd,
+                                                  cd.w_dgrad, dx_in, self.dt), extra_macs=self._macs(cd))
 
     def backward(self):
         N, t = self.N, self.t
@@ -889,7 +950,7 @@ class ResNet18Engine:
         hw = self.final_hw
         blocks = self.spec.blocks
         lb2 = bn_name(blocks[-1].conv2.name)
-        if (self.head_bnsums and self.norm == "batch" and self.dp is None and blocks[-1].down is None and lb2 in self.relu_masks
+        if (self.norm == "batch" and self.dp is None and blocks[-1].down is None and lb2 in self.relu_masks
                 and self._head_bnsums_ok()):
             # ... forming the backward sums of the last block's bn2 on the way (one value per image and channel)
             sums = self._bwd_sums("head", N, 512)
@@ -900,154 +961,15 @@ class ResNet18Engine:
         else:
             call("primia_head_bwd", self.views["fc.weight"], self.dlogits, t[last + ".dout"], N, hw * hw, 512, nc, self.dt)
         for i in range(len(blocks) - 1, -1, -1):
-            blk = blocks[i]
-            p = blk.prefix
-            x_in = t[blocks[i - 1].prefix + ".out"] if i > 0 else t["pool.out"]
-            dx_in = t[blocks[i - 1].prefix + ".dout"] if i > 0 else t["pool.dout"]
-            dout = t[p + ".dout"]
+            blk, prev = blocks[i], (blocks[i - 1] if i > 0 else None)
+            x_in = t[prev.prefix + ".out"] if prev is not None else t["pool.out"]
+            dx_in = t[prev.prefix + ".dout"] if prev is not None else t["pool.dout"]
             if self.taps is not None:
-                self.taps[p + ".dout_in"] = dout.clone()
-            # bn2 (+residual, relu): dy2, and the masked gradient g written back over dout — unless this is an identity
-            # block whose conv1 data gradient can mask the old values itself (one tensor write less)
-            b2 = bn_name(blk.conv2.name)
-            masked_acc = (blk.down is None and self.masked_acc_ok.get(blk.conv1.name, False)
-                          and b2 in self.relu_masks)
-            # transition block: bn2 and the downsample BatchNorm share the incoming gradient -> ONE fused backward
-            bn_pair = (blk.down is not None and self.pair_dgrad and self.bn_pair and self.norm == "batch"
-                       and b2 in self.relu_masks)
-            if bn_pair:
-                bd = bn_name(blk.down.name)
-                (sm2, si2), (smd, sid) = self.save[b2], self.save[bd]
-                call("primia_bn_bwd_pair", t[p + ".y2"], t[p + ".yd"], dout, self.relu_masks[b2], t[p + ".dy2"],
-                     t[p + ".dyd"], self.views[b2 + ".weight"], sm2, si2, self.views[bd + ".weight"], smd, sid,
-                     self._gviews[b2 + ".weight"], self._gviews[b2 + ".bias"], self._gviews[bd + ".weight"],
-                     self._gviews[bd + ".bias"], t[p + ".y2"].shape[0], t[p + ".y2"].shape[1], self.bn_ws,
-                     self.bn_ws_bytes, self.dt)
+                self.taps[blk.prefix + ".dout_in"] = t[blk.prefix + ".dout"].clone()
+            if blk.down is None:
+                self._backward_identity(blk, prev, x_in, dx_in)
             else:
-                # GroupNorm transition block: the downsample's backward pass applies bn2's ReLU mask to dout itself
-                # (primia_gn_bwd_mask on yd), so the masked gradient is not written here either
-                gn_ds_mask = (blk.down is not None and self.norm == "group" and self.pair_dgrad and self.gn_ds_mask
-                              and b2 in self.relu_masks)
-                self._bn_bwd(blk.conv2.name, t[p + ".y2"], t[p + ".out"], dout, t[p + ".dy2"], dout, True,
-                             keep_g=not (masked_acc or gn_ds_mask), from_sums=self._dout_sums.pop(p, None))
-            # data gradient first: the weight gradient (a leaf) then runs beside the BatchNorm chain that follows
-            fused_sums = self._dgrad_bnsums_slots(blk.conv2.name) if (self.dgrad_bnsums and self.norm == "batch") else 0
-            if self.wgrad_first:   # weight gradient, then data gradient, so that the BatchNorm backward pass which
-                # follows finds the data gradient it reads still in the Infinity Cache
-                self._wgrad(blk.conv2.name, t[p + ".a1"], t[p + ".dy2"])
-            if fused_sums:
-                c2, b1 = self.convs[blk.conv2.name], bn_name(blk.conv1.name)
-                sm1, si1 = self.save[b1]
-                if self.wgrad_overlap == 1:
-                    self._join_wgrad_stream()   # (as _dgrad does: two MFMA-bound kernels never run side by side)
-                sums = self._bwd_sums(blk.conv2.name, fused_sums, blk.conv1.cout)
-                self._timed("dgrad", c2, lambda: call(
-                    "primia_conv2d_dgrad_bnsums", c2.desc, t[p + ".dy2"], c2.w_dgrad, t[p + ".da1"], t[p + ".y1"], sm1, si1,
-                    self.views[b1 + ".weight"], self.views[b1 + ".bias"], sums, self.dt))
-            else:
-                self._dgrad(blk.conv2.name, t[p + ".dy2"], t[p + ".da1"], False, blk.conv1.name, t[p + ".y1"])
-            if not self.wgrad_first:
-                self._wgrad(blk.conv2.name, t[p + ".a1"], t[p + ".dy2"])
-            if fused_sums:
-                y1 = t[p + ".y1"]
-                call("primia_bn_relu_bwd_from_sums", y1, t[p + ".da1"], t[p + ".dy1"], self.views[b1 + ".weight"],
-                     self.views[b1 + ".bias"], sm1, si1, self._gviews[b1 + ".weight"], self._gviews[b1 + ".bias"], sums,
-                     fused_sums, y1.shape[0], y1.shape[1], self.dt)
-            else:
-                self._bn_bwd(blk.conv1.name, t[p + ".y1"], t[p + ".a1"], t[p + ".da1"], t[p + ".dy1"], None, True)
-            if blk.down is not None and self.pair_dgrad:
-                # both BatchNorm backward passes first, then ONE data-gradient pass for conv1 + downsample
-                if not bn_pair and gn_ds_mask:
-                    bd = bn_name(blk.down.name)
-                    (smd, sid), (psg, psb) = self.save[bd], self.ps_affine[bd]
-                    yd = t[p + ".yd"]
-                    call("primia_gn_bwd_mask", yd, self.relu_masks[b2], dout, t[p + ".dyd"], None, self.views[bd + ".weight"],
-                         smd, sid, psg, psb, self.N, yd.shape[0] // self.N, yd.shape[1], self.groups, self.bn_ws,
-                         self.bn_ws_bytes, self.dt)
-                    if self.dp is None:
-                        call("primia_weighted_colsum", psg, self.ones_n, self._gviews[bd + ".weight"], self.N, yd.shape[1])
-                        call("primia_weighted_colsum", psb, self.ones_n, self._gviews[bd + ".bias"], self.N, yd.shape[1])
-                elif not bn_pair:
-                    self._bn_bwd(blk.down.name, t[p + ".yd"], None, dout, t[p + ".dyd"], None, False)
-                c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
-                if self.wgrad_overlap == 1:
-                    self._join_wgrad_stream()
-                if self.wgrad_first:
-                    self._wgrad_transition(blk, x_in, t[p + ".dy1"], t[p + ".dyd"])
-                prev = blocks[i - 1] if i > 0 else None
-                pb2 = bn_name(prev.conv2.name) if prev is not None else None
-                pslots = 0
-                if (self.pair_bnsums and self.norm == "batch" and self.dp is None and prev is not None and prev.down is None
-                        and pb2 in self.relu_masks and self.dtype == torch.bfloat16):
-                    if getattr(c1, "pair_bnsums_slots", None) is None:
-                        c1.pair_bnsums_slots = query("primia_conv_dgrad_pair_bnsums_slots", c1.desc, self.dt)
-                    pslots = c1.pair_bnsums_slots
-                if pslots > 0:
-                    # ... and the backward sums of the previous block's bn2 out of the same write-back
-                    sums = self._bwd_sums(blk.conv1.name + ".pair", pslots, prev.conv2.cout)
-                    smp, sip = self.save[pb2]
-                    self._timed("dgrad", c1, lambda: call(
-                        "primia_conv2d_dgrad_pair_bnsums", c1.desc, t[p + ".dy1"], c1.w_dgrad, cd.desc, t[p + ".dyd"], cd.w_dgrad,
-                        dx_in, t[prev.prefix + ".y2"], self.relu_masks[pb2], smp, sip, sums, self.dt), extra_macs=self._macs(cd))
-                    self._dout_sums[prev.prefix] = (sums, pslots)
-                else:
-                    self._timed("dgrad", c1, lambda: call("primia_conv2d_dgrad_pair", c1.desc, t[p + ".dy1"], c1.w_dgrad,
-                                                          cd.desc, t[p + ".dyd"], cd.w_dgrad, dx_in, self.dt),
-                                extra_macs=self._macs(cd))
-                if not self.wgrad_first:
-                    self._wgrad_transition(blk, x_in, t[p + ".dy1"], t[p + ".dyd"])
-            elif blk.down is not None:
-                self._dgrad(blk.conv1.name, t[p + ".dy1"], dx_in, False)
-                self._wgrad(blk.conv1.name, x_in, t[p + ".dy1"])
-                self._bn_bwd(blk.down.name, t[p + ".yd"], None, dout, t[p + ".dyd"], None, False)
-                self._dgrad(blk.down.name, t[p + ".dyd"], dx_in, True)
-                self._wgrad(blk.down.name, x_in, t[p + ".dyd"])
-            else:
-                # identity skip: dx_in aliases dout, which now holds the masked gradient g
-                if self.wgrad_first:
-                    self._wgrad(blk.conv1.name, x_in, t[p + ".dy1"])
-                if masked_acc:
-                    c1 = self.convs[blk.conv1.name]
-                    if self.wgrad_overlap == 1:
-                        self._join_wgrad_stream()
-                    # ... whose write-back also forms the backward sums of the BatchNorm whose output gradient it completes:
-                    # the previous block's bn2 (mode 2), or the stem's bn1 through the max-pool (mode 3)
-                    aslots, amode = 0, 0
-                    if self.acc_bnsums and self.norm == "batch" and self.dp is None and self.dtype == torch.bfloat16:
-                        prev = blocks[i - 1] if i > 0 else None
-                        pb2 = bn_name(prev.conv2.name) if prev is not None else None
-                        if prev is not None and prev.down is None and pb2 in self.relu_masks:
-                            amode = 2
-                        elif prev is None and self._stem_bwd_fused_wanted():
-                            amode = 3
-                        if amode:
-                            if getattr(c1, "acc_bnsums_slots", None) is None:
-                                c1.acc_bnsums_slots = query("primia_conv_dgrad_masked_acc_bnsums_slots", c1.desc, self.dt)
-                            aslots = c1.acc_bnsums_slots
-                    if aslots > 0 and amode == 2:
-                        sums = self._bwd_sums(blk.conv1.name + ".acc", aslots, prev.conv2.cout)
-                        smp, sip = self.save[pb2]
-                        self._timed("dgrad", c1, lambda: call(
-                            "primia_conv2d_dgrad_masked_acc_bnsums", c1.desc, t[p + ".dy1"], c1.w_dgrad, dx_in,
-                            self.relu_masks[b2], 2, t[prev.prefix + ".y2"], self.relu_masks[pb2], smp, sip, sums, self.dt))
-                        self._dout_sums[prev.prefix] = (sums, aslots)
-                    elif aslots > 0 and amode == 3:
-                        sums = self._bwd_sums(blk.conv1.name + ".acc", aslots, 64)
-                        self._timed("dgrad", c1, lambda: call(
-                            "primia_conv2d_dgrad_masked_acc_bnsums", c1.desc, t[p + ".dy1"], c1.w_dgrad, dx_in,
-                            self.relu_masks[b2], 3, t["pool.out"], None, self.views["bn1.bias"], self.views["bn1.weight"],
-                            sums, self.dt))
-                        self._pool_sums = (sums, aslots)
-                    else:
-                        self._timed("dgrad", c1, lambda: call("primia_conv2d_dgrad_masked_acc", c1.desc, t[p + ".dy1"],
-                                                              c1.w_dgrad, dx_in, self.relu_masks[b2], self.dt))
-                elif i > 0:
-                    self._dgrad(blk.conv1.name, t[p + ".dy1"], dx_in, True, blocks[i - 1].conv2.name,
-                                t[blocks[i - 1].prefix + ".y2"])
-                else:
-                    self._dgrad(blk.conv1.name, t[p + ".dy1"], dx_in, True)
-                if not self.wgrad_first:
-                    self._wgrad(blk.conv1.name, x_in, t[p + ".dy1"])
+                self._backward_transition(blk, prev, x_in, dx_in)
         hw = self.stem_hw
         # the stem's tail in two launches less and without the dy tensor (411 MB at batch 256): bn1's backward sums at
         # pooled resolution, then conv1's weight gradient forming its dy tiles on the fly (primia_stem_bwd_fused)
@@ -1297,14 +1219,14 @@ class ResNet18Engine:
             # clipped sums
             # (a transition block's conv1 + downsample: ONE launch as in plain training, once both dy are scaled)
             pair_of, pair_wait = {}, {}
-            if self.wgrad_pair and self.wgrad_ws is not None:
+            if self.wgrad_ws is not None:
                 for blk in self.spec.blocks:
                     if (blk.down is not None and self._pair_ws.get(blk.conv1.name, 0) > 0
                             and blk.conv1.name not in kept and blk.down.name not in kept):
                         pair_of[blk.conv1.name] = pair_of[blk.down.name] = blk
             # every dy of a layer whose tiles are not kept, scaled by the clip factors in ONE launch (a dozen tensors)
             to_scale = [dy for name, _, dy in self.dp["wgrads"] if name not in kept]
-            many = self.dp_scale_many and 0 < len(to_scale) <= 16
+            many = 0 < len(to_scale) <= 16
             if many:
                 key = tuple(tt.data_ptr() for tt in to_scale)
                 if getattr(self, "_scale_many", (None,))[0] != key:
@@ -1378,7 +1300,6 @@ class ResNet18Engine:
         return self.loss
 
     dp_keep = True
-    dp_scale_many = True
 
     def _dp_keep_buffers(self):
         """{conv name: fp32 buffer} for the layers whose per-sample tiles the DP-SGD norm pass keeps (built once)."""
@@ -1393,8 +1314,6 @@ class ResNet18Engine:
                         n = query("primia_conv_wgrad_persample_slab_bytes", self.convs[c.name].desc, self.dt)
                     if n > 0:
                         self._dp_keep[c.name] = torch.empty(n // 4, dtype=torch.float32, device=self.device)
-        if "conv1" in self._dp_keep and not self._stem_padded:
-            return {k: v for k, v in self._dp_keep.items() if k != "conv1"}
         return self._dp_keep
 
     # ------------------------------------------------------------------------------------------

@@ -357,8 +357,14 @@ def test_bf16_full_size_step_against_oracle(cuda):
     eng.taps = {}
     logits = eng.forward(x.to(cuda)).float().cpu()
     loss = eng.loss_backward(y.to(cuda)).item()
-    # the fused reductions are the paths taken
-    assert eng.dgrad_bnsums and eng.pair_bnsums and eng.acc_bnsums and eng.head_bnsums
+    # the fused reductions are the paths taken: every conv2's data gradient forms bn1's sums (the linear-halo kernels serve
+    # all eight), the transition pairs' and layer1's accumulating data gradients those of the bn2 in front of them
+    conv2s = {blk.conv2.name for blk in eng.spec.blocks}
+    assert all(eng._dgrad_bnsums_slots(n) > 0 for n in conv2s)
+    assert all(getattr(eng.convs[blk.conv1.name], "pair_bnsums_slots", 0) > 0
+               for blk in eng.spec.blocks if blk.down is not None)
+    assert all(getattr(eng.convs[n], "acc_bnsums_slots", 0) > 0 for n in ("layer1.0.conv1", "layer1.1.conv1"))
+    assert set(eng._bwd_sum_bufs) >= conv2s
     assert set(eng._bwd_sum_bufs) >= {"head", "layer1.0.conv1.acc", "layer1.1.conv1.acc", "layer2.0.conv1.pair",
                                       "layer3.0.conv1.pair", "layer4.0.conv1.pair"}
     ologits, oloss, ograds = O.train_step(sd, x, y, 0.0, 0.0)

@@ -63,9 +63,9 @@ for k in keys:
 # ---- finer: snapshot the gradient entering each block (dz of bn2's backward) -------------------
 snaps = {}
 orig = eng._bn_bwd
-def hooked(conv_name, y, z, dz, dy, g_out, relu):
+def hooked(conv_name, y, z, dz, dy, g_out, relu, **kw):
     snaps[conv_name + ".dz_in"] = dz.clone()
-    orig(conv_name, y, z, dz, dy, g_out, relu)
+    orig(conv_name, y, z, dz, dy, g_out, relu, **kw)
     snaps[conv_name + ".dy_out"] = dy.clone()
     if g_out is not None:
         snaps[conv_name + ".g_out"] = g_out.clone()
