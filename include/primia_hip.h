@@ -125,6 +125,13 @@ int primia_conv_sgd_step_many(const primia_conv_desc* descs_host, const int* c_r
                               const float* const* dw_acc_host, float* const* dw_oihw_host,
                               float* const* w_oihw_host, void* const* w_fwd_host, void* const* w_dgrad_host,
                               int n, float lr, float weight_decay, int dtype, primia_stream_t stream);
+/* The same pass with lr / weight_decay read on the device from `hyper` (layout below, primia_opt_hyper_set): what a
+ * captured hipGraph of the training step launches, so that the scheduler's rate reaches every replay.  Bit-identical to
+ * primia_conv_sgd_step_many with the same values. */
+int primia_conv_sgd_step_many_dev(const primia_conv_desc* descs_host, const int* c_real_host,
+                                  const float* const* dw_acc_host, float* const* dw_oihw_host,
+                                  float* const* w_oihw_host, void* const* w_fwd_host, void* const* w_dgrad_host,
+                                  int n, const float* hyper, int dtype, primia_stream_t stream);
 
 /* A transition block's two forward convolutions of the same x — conv1 (3x3, stride 2) and the downsample (1x1, stride 2;
  * torchlib/models.py:236-247 `identity = self.downsample(x)` beside `out = self.conv1(x)`) — in ONE launch, each with its
@@ -717,6 +724,23 @@ int primia_sgd_step_ranges(float* p, const float* g, const int64_t* begin_host, 
 int primia_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t n,
                      float lr, float beta1, float beta2, float eps, float weight_decay,
                      int64_t step, primia_stream_t stream);
+
+/* Device-scalar forms of the three optimizer steps above — the same optimizer.step() of train.py:280-303 with the
+ * scheduler-written rate (torchlib/utils.py:84-88) and Adam's per-step bias corrections taken from a device array, so
+ * that a captured hipGraph of the step (train.py --hip_graph) picks up new values at every replay.  `hyper` holds 8
+ * fp32 words: {lr, weight_decay, beta1, beta2, eps, lr / bc1, 1 / sqrt(bc2), 0}, bc_i = 1 - beta_i^step.  Each kernel
+ * reads the words it needs once; the arithmetic is that of the host-scalar entry point, results are bit-identical. */
+int primia_sgd_step_dev(float* p, const float* g, int64_t n, const float* hyper, primia_stream_t stream);
+int primia_sgd_step_ranges_dev(float* p, const float* g, const int64_t* begin_host, const int64_t* len_host, int n,
+                               const float* hyper, primia_stream_t stream);
+int primia_adam_step_dev(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t n,
+                         const float* hyper, primia_stream_t stream);
+/* Writes `hyper` on `stream` (one single-thread launch, no copy from the host, no synchronisation): Adam's bias
+ * corrections of `step` are computed on the host in double with primia_adam_step's expressions; step 0 (SGD) writes
+ * 0 in their two words.  The optimizer.step() hyperparameters of train.py:280-303 as the reference's param_groups hold
+ * them before each step. */
+int primia_opt_hyper_set(float* hyper, float lr, float weight_decay, float beta1, float beta2, float eps,
+                         int64_t step, primia_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * FedAvg helpers — the arithmetic of aggregation() (torchlib/utils.py:1000-1092) on the flat

@@ -133,6 +133,10 @@ __host__ __device__ __forceinline__ bool pool_xhat_recoverable(float gamma, floa
 // (optim.hip) and the fused gradient-finalize + step + weight-refresh tiles (layout.hip): the two must agree bit for bit.
 __device__ __forceinline__ float sgd_update(float p, float g, float lr, float wd) { return p - lr * (g + wd * p); }
 
+// Word offsets of an optimizer's device scalars (the `hyper` array of the *_dev entry points, primia_opt_hyper_set):
+// {lr, weight_decay, beta1, beta2, eps, lr / bc1, 1 / sqrt(bc2), 0}
+enum { kHyperLr = 0, kHyperWd, kHyperBeta1, kHyperBeta2, kHyperEps, kHyperStepSize, kHyperInvSqrtBc2, kHyperWords = 8 };
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Post-launch error check -> C-ABI code.

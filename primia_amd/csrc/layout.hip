@@ -354,7 +354,9 @@ struct SgdTileArgs {
 // KT out-channels per tile: 16 for the 3x3 layers (37 KB of LDS: four blocks per CU instead of two, 1,200 tiles instead of
 // 600 — the pass is a chain of memory round trips per block and lives on blocks in flight), 32 for the 1x1 layers.
 // Both loads of a tile (accumulator rows, master weights) are requested before the first barrier.
-template <typename T, int RS, int KT>
+// kDev: lr / wd came from the device scalars (conv_sgd_tiled_dev_kernel) — the same code, instantiated apart so that the
+// host-scalar kernel's code does not depend on the device-scalar one's
+template <typename T, int RS, int KT, bool kDev = false>
 __device__ __forceinline__ void sgd_tile(const SgdTileEntry& en, int tile, float* lds, float lr, float wd) {
     constexpr int ROW = 64 * RS, PITCH = ROW + 1;
     constexpr int NV = KT * ROW / 4;                 // float4 pieces of the tile
@@ -423,6 +425,21 @@ __global__ __launch_bounds__(256) void conv_sgd_tiled_kernel(SgdTileArgs a) {
         sgd_tile<T, 1, 32>(en, tile, lds, a.lr, a.wd);
 }
 
+// the same pass with lr / weight_decay read from the device scalars (primia_opt_hyper_set) at the start
+template <typename T>
+__global__ __launch_bounds__(256) void conv_sgd_tiled_dev_kernel(SgdTileArgs a, const float* __restrict__ hyper) {
+    __shared__ float lds[kTileK9 * (64 * 9 + 1)];
+    const float lr = hyper[kHyperLr], wd = hyper[kHyperWd];
+    int c = 0;
+    while (c + 1 < a.n && (int)blockIdx.x >= a.tile_begin[c + 1]) ++c;
+    const SgdTileEntry& en = a.e[c];
+    const int tile = blockIdx.x - a.tile_begin[c];
+    if (en.RS == 9)
+        sgd_tile<T, 9, kTileK9, true>(en, tile, lds, lr, wd);
+    else
+        sgd_tile<T, 1, 32, true>(en, tile, lds, lr, wd);
+}
+
 // SGD over up to 32 element ranges of a flat arena in one launch (what the fused tiles leave over: BatchNorm / fc
 // parameters, the stem filter) — scalar accesses, the ranges are a few thousand elements each
 constexpr int kMaxRanges = 32;
@@ -431,8 +448,8 @@ struct SgdRanges {
     int n;
     long total;
 };
-__global__ __launch_bounds__(256) void sgd_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, SgdRanges r,
-                                                         float lr, float wd) {
+__device__ __forceinline__ void sgd_ranges_body(float* __restrict__ p, const float* __restrict__ g, const SgdRanges& r,
+                                                float lr, float wd) {
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < r.total; i += stride) {
         long j = i;
@@ -441,6 +458,15 @@ __global__ __launch_bounds__(256) void sgd_ranges_kernel(float* __restrict__ p, 
         const long o = r.begin[k] + j;
         p[o] = sgd_update(p[o], g[o], lr, wd);
     }
+}
+__global__ __launch_bounds__(256) void sgd_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, SgdRanges r,
+                                                         float lr, float wd) {
+    sgd_ranges_body(p, g, r, lr, wd);
+}
+__global__ __launch_bounds__(256) void sgd_ranges_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                             SgdRanges r, const float* __restrict__ hyper) {
+    const float lr = hyper[kHyperLr], wd = hyper[kHyperWd];
+    sgd_ranges_body(p, g, r, lr, wd);
 }
 
 // regular conv that the tiled kernels cover
@@ -681,16 +707,16 @@ int primia_conv_sgd_fusable(const primia_conv_desc* d, int c_real) {
     return tiled_ok(g, c_real) ? 1 : 0;
 }
 
-int primia_conv_sgd_step_many(const primia_conv_desc* descs, const int* c_real, const float* const* dw_acc,
-                              float* const* dw_oihw, float* const* w_oihw, void* const* w_fwd, void* const* w_dgrad,
-                              int n, float lr, float weight_decay, int dtype, primia_stream_t stream) {
+// argument block of primia_conv_sgd_step_many[_dev]: PRIMIA_OK, or the error code to return
+static int conv_sgd_args(const primia_conv_desc* descs, const int* c_real, const float* const* dw_acc,
+                         float* const* dw_oihw, float* const* w_oihw, void* const* w_fwd, void* const* w_dgrad, int n,
+                         float lr, float weight_decay, int dtype, SgdTileArgs& ta, int& tiles) {
     PRIMIA_REQUIRE(descs && c_real && dw_acc && dw_oihw && w_oihw && w_fwd && w_dgrad && n > 0 && n <= kMaxConvs);
     PRIMIA_REQUIRE(dtype == PRIMIA_F32 || dtype == PRIMIA_BF16);
-    SgdTileArgs ta;
     ta.n = 0;
     ta.lr = lr;
     ta.wd = weight_decay;
-    int tiles = 0;
+    tiles = 0;
     for (int i = 0; i < n; ++i) {
         ConvGeom g;
         PRIMIA_REQUIRE(g.init(descs[i]) && dw_acc[i] && dw_oihw[i] && w_oihw[i] && w_fwd[i]);
@@ -704,6 +730,17 @@ int primia_conv_sgd_step_many(const primia_conv_desc* descs, const int* c_real, 
         tiles += tiles_of(g.K, g.C, en.RS);
     }
     ta.tile_begin[ta.n] = tiles;
+    return PRIMIA_OK;
+}
+
+int primia_conv_sgd_step_many(const primia_conv_desc* descs, const int* c_real, const float* const* dw_acc,
+                              float* const* dw_oihw, float* const* w_oihw, void* const* w_fwd, void* const* w_dgrad,
+                              int n, float lr, float weight_decay, int dtype, primia_stream_t stream) {
+    SgdTileArgs ta;
+    int tiles;
+    const int rc = conv_sgd_args(descs, c_real, dw_acc, dw_oihw, w_oihw, w_fwd, w_dgrad, n, lr, weight_decay, dtype, ta,
+                                 tiles);
+    if (rc != PRIMIA_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == PRIMIA_F32)
         conv_sgd_tiled_kernel<float><<<tiles, 256, 0, st>>>(ta);
@@ -712,11 +749,25 @@ int primia_conv_sgd_step_many(const primia_conv_desc* descs, const int* c_real, 
     return launch_status();
 }
 
-int primia_sgd_step_ranges(float* p, const float* g, const int64_t* begin_host, const int64_t* len_host, int n, float lr,
-                           float weight_decay, primia_stream_t stream) {
-    if (n == 0) return PRIMIA_OK;
+int primia_conv_sgd_step_many_dev(const primia_conv_desc* descs, const int* c_real, const float* const* dw_acc,
+                                  float* const* dw_oihw, float* const* w_oihw, void* const* w_fwd,
+                                  void* const* w_dgrad, int n, const float* hyper, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(hyper);
+    SgdTileArgs ta;
+    int tiles;
+    const int rc = conv_sgd_args(descs, c_real, dw_acc, dw_oihw, w_oihw, w_fwd, w_dgrad, n, 0.f, 0.f, dtype, ta, tiles);
+    if (rc != PRIMIA_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PRIMIA_F32)
+        conv_sgd_tiled_dev_kernel<float><<<tiles, 256, 0, st>>>(ta, hyper);
+    else
+        conv_sgd_tiled_dev_kernel<bf16><<<tiles, 256, 0, st>>>(ta, hyper);
+    return launch_status();
+}
+
+static int sgd_ranges_args(const float* p, const float* g, const int64_t* begin_host, const int64_t* len_host, int n,
+                           SgdRanges& r) {
     PRIMIA_REQUIRE(p && g && begin_host && len_host && n > 0 && n <= kMaxRanges);
-    SgdRanges r;
     r.n = n;
     r.total = 0;
     for (int i = 0; i < n; ++i) {
@@ -725,8 +776,30 @@ int primia_sgd_step_ranges(float* p, const float* g, const int64_t* begin_host, 
         r.len[i] = len_host[i];
         r.total += len_host[i];
     }
-    const int blocks = (int)((r.total + 255) / 256 < 1024 ? (r.total + 255) / 256 : 1024);
-    sgd_ranges_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(p, g, r, lr, weight_decay);
+    return PRIMIA_OK;
+}
+static inline int sgd_ranges_blocks(const SgdRanges& r) {
+    return (int)((r.total + 255) / 256 < 1024 ? (r.total + 255) / 256 : 1024);
+}
+
+int primia_sgd_step_ranges(float* p, const float* g, const int64_t* begin_host, const int64_t* len_host, int n, float lr,
+                           float weight_decay, primia_stream_t stream) {
+    if (n == 0) return PRIMIA_OK;
+    SgdRanges r;
+    const int rc = sgd_ranges_args(p, g, begin_host, len_host, n, r);
+    if (rc != PRIMIA_OK) return rc;
+    sgd_ranges_kernel<<<sgd_ranges_blocks(r), 256, 0, (hipStream_t)stream>>>(p, g, r, lr, weight_decay);
+    return launch_status();
+}
+
+int primia_sgd_step_ranges_dev(float* p, const float* g, const int64_t* begin_host, const int64_t* len_host, int n,
+                               const float* hyper, primia_stream_t stream) {
+    if (n == 0) return PRIMIA_OK;
+    PRIMIA_REQUIRE(hyper);
+    SgdRanges r;
+    const int rc = sgd_ranges_args(p, g, begin_host, len_host, n, r);
+    if (rc != PRIMIA_OK) return rc;
+    sgd_ranges_dev_kernel<<<sgd_ranges_blocks(r), 256, 0, (hipStream_t)stream>>>(p, g, r, hyper);
     return launch_status();
 }
 

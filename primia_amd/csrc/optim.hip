@@ -13,11 +13,24 @@ __global__ __launch_bounds__(256) void flat_kernel(F f, long n) {
     if (t < n) f.one(t);
 }
 
+// The same pass with the functor's scalars read from the device array `hyper` (layout: primia_opt_hyper_set), once, before
+// the loop: a captured hipGraph replays it with the values written before each replay.
+template <typename F>
+__global__ __launch_bounds__(256) void flat_dev_kernel(F f, const float* __restrict__ hyper, long n) {
+    f.load(hyper);
+    const long nv = n >> 2;
+    const long stride = (long)gridDim.x * 256;
+    for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nv; q += stride) f.vec(q);
+    const long t = (nv << 2) + (long)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) f.one(t);
+}
+
 struct SgdFn {
     float* p;
     const float* g;
     float lr, wd;
     // torch.optim.SGD without momentum: d_p = g + wd*p ; p = p - lr*d_p
+    __device__ __forceinline__ void load(const float* h) { lr = h[kHyperLr]; wd = h[kHyperWd]; }
     __device__ __forceinline__ float upd(float p_, float g_) const { return sgd_update(p_, g_, lr, wd); }
     __device__ __forceinline__ void vec(long q) const {
         f32x4 a = ((f32x4*)p)[q];
@@ -35,6 +48,10 @@ struct AdamFn {
     float* m;
     float* v;
     float beta1, beta2, eps, wd, step_size, inv_sqrt_bc2;
+    __device__ __forceinline__ void load(const float* h) {
+        beta1 = h[kHyperBeta1]; beta2 = h[kHyperBeta2]; eps = h[kHyperEps]; wd = h[kHyperWd];
+        step_size = h[kHyperStepSize]; inv_sqrt_bc2 = h[kHyperInvSqrtBc2];
+    }
     // torch-1.4 torch.optim.Adam (L2-coupled weight decay)
     __device__ __forceinline__ void upd(float& p_, float g_, float& m_, float& v_) const {
         g_ = g_ + wd * p_;
@@ -112,6 +129,19 @@ __global__ __launch_bounds__(256) void fx_decode_kernel(const int64_t* __restric
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) x[i] = (float)q[i] / scale;
 }
 
+// writes the eight words of an optimizer's device scalars (one thread, plain stores)
+__global__ void opt_hyper_set_kernel(float* __restrict__ h, float lr, float wd, float beta1, float beta2, float eps,
+                                     float step_size, float inv_sqrt_bc2) {
+    h[kHyperLr] = lr;
+    h[kHyperWd] = wd;
+    h[kHyperBeta1] = beta1;
+    h[kHyperBeta2] = beta2;
+    h[kHyperEps] = eps;
+    h[kHyperStepSize] = step_size;
+    h[kHyperInvSqrtBc2] = inv_sqrt_bc2;
+    h[7] = 0.f;
+}
+
 static inline int flat_blocks(long n) {
     long b = ((n >> 2) + 255) / 256;
     if (b < 1) b = 1;
@@ -147,6 +177,41 @@ int primia_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq
     AdamFn f{p, g, exp_avg, exp_avg_sq, beta1, beta2, eps, weight_decay, (float)((double)lr / bc1),
              (float)(1.0 / sqrt(bc2))};
     flat_kernel<<<flat_blocks(n), 256, 0, (hipStream_t)stream>>>(f, n);
+    return launch_status();
+}
+
+int primia_sgd_step_dev(float* p, const float* g, int64_t n, const float* hyper, primia_stream_t stream) {
+    if (n == 0) return PRIMIA_OK;  // empty input: no-op, pointers may be null
+    PRIMIA_REQUIRE(p && g && hyper && n >= 0 && aligned16(p) && aligned16(g));
+    SgdFn f{p, g, 0.f, 0.f};
+    flat_dev_kernel<<<flat_blocks(n), 256, 0, (hipStream_t)stream>>>(f, hyper, n);
+    return launch_status();
+}
+
+int primia_adam_step_dev(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
+                         primia_stream_t stream) {
+    if (n == 0) return PRIMIA_OK;  // empty input: no-op, pointers may be null
+    PRIMIA_REQUIRE(p && g && exp_avg && exp_avg_sq && hyper && n >= 0);
+    PRIMIA_REQUIRE(aligned16(p) && aligned16(g) && aligned16(exp_avg) && aligned16(exp_avg_sq));
+    AdamFn f{p, g, exp_avg, exp_avg_sq, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    flat_dev_kernel<<<flat_blocks(n), 256, 0, (hipStream_t)stream>>>(f, hyper, n);
+    return launch_status();
+}
+
+int primia_opt_hyper_set(float* hyper, float lr, float weight_decay, float beta1, float beta2, float eps, int64_t step,
+                         primia_stream_t stream) {
+    PRIMIA_REQUIRE(hyper && aligned16(hyper) && step >= 0);
+    // Adam's bias corrections on the host, in double, with primia_adam_step's expressions (a device pow need not agree
+    // with the host's in the last bit); step 0 (no Adam step yet, or SGD) leaves them 0
+    float step_size = 0.f, inv_sqrt_bc2 = 0.f;
+    if (step >= 1) {
+        const double bc1 = 1.0 - pow((double)beta1, (double)step);
+        const double bc2 = 1.0 - pow((double)beta2, (double)step);
+        step_size = (float)((double)lr / bc1);
+        inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    opt_hyper_set_kernel<<<1, 1, 0, (hipStream_t)stream>>>(hyper, lr, weight_decay, beta1, beta2, eps, step_size,
+                                                          inv_sqrt_bc2);
     return launch_status();
 }
 

@@ -1335,31 +1335,49 @@ class ResNet18Engine:
         self.opt_state = None
         self.opt_steps = 0
 
-    def sgd_step(self, lr, weight_decay=0.0):
+    def sgd_step(self, lr, weight_decay=0.0, hyper=None):
+        """`hyper`: an fp32 [8] device tensor written by primia_opt_hyper_set — the step then reads lr / weight_decay
+        from it on the device (the *_dev entry points: what a captured graph of the step replays) and ignores the two
+        arguments."""
         if self._grads_pending:
             fus, rest, rb, rl, nr = self._sgd_tail_plan()
             self._grads_pending = False
-            call("primia_conv_sgd_step_many", fus["descs"], fus["creal"], fus["acc"], fus["gw"], fus["w"], fus["wf"],
-                 fus["wd"], fus["n"], float(lr), float(weight_decay), self.dt)
+            if hyper is None:
+                call("primia_conv_sgd_step_many", fus["descs"], fus["creal"], fus["acc"], fus["gw"], fus["w"], fus["wf"],
+                     fus["wd"], fus["n"], float(lr), float(weight_decay), self.dt)
+            else:
+                call("primia_conv_sgd_step_many_dev", fus["descs"], fus["creal"], fus["acc"], fus["gw"], fus["w"],
+                     fus["wf"], fus["wd"], fus["n"], hyper, self.dt)
             if rest is not None:
                 call("primia_conv_wgrad_finalize_many", rest["descs"], rest["creal"], rest["acc"], rest["gw"], rest["n"])
-            call("primia_sgd_step_ranges", self.flat, self._grads, rb, rl, nr, float(lr), float(weight_decay))
+            if hyper is None:
+                call("primia_sgd_step_ranges", self.flat, self._grads, rb, rl, nr, float(lr), float(weight_decay))
+            else:
+                call("primia_sgd_step_ranges_dev", self.flat, self._grads, rb, rl, nr, hyper)
             if rest is not None:
                 call("primia_conv_weight_prepare_many", rest["descs"], rest["creal"], rest["w"], rest["wf"], rest["wd"],
                      rest["n"], self.dt)
             return
-        call("primia_sgd_step", self.flat, self.grads, self.P, float(lr), float(weight_decay))
+        if hyper is None:
+            call("primia_sgd_step", self.flat, self.grads, self.P, float(lr), float(weight_decay))
+        else:
+            call("primia_sgd_step_dev", self.flat, self.grads, self.P, hyper)
         self.refresh_weights()
 
-    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, hyper=None):
+        """`hyper`: as in sgd_step; it must hold this step's bias corrections (primia_opt_hyper_set with step =
+        opt_steps + 1, the count this call advances to)."""
         self.materialize_grads()
         if self.opt_state is None:
             self.opt_state = (torch.zeros_like(self.grads), torch.zeros_like(self.grads))
             self.opt_steps = 0
         self.opt_steps += 1
         m, v = self.opt_state
-        call("primia_adam_step", self.flat, self.grads, m, v, self.P, float(lr), float(betas[0]), float(betas[1]),
-             float(eps), float(weight_decay), self.opt_steps)
+        if hyper is None:
+            call("primia_adam_step", self.flat, self.grads, m, v, self.P, float(lr), float(betas[0]), float(betas[1]),
+                 float(eps), float(weight_decay), self.opt_steps)
+        else:
+            call("primia_adam_step_dev", self.flat, self.grads, m, v, self.P, hyper)
         self.refresh_weights()
 
     def train_step(self, x_nchw, target, lr, weight_decay=0.0, soft=False):

@@ -285,6 +285,9 @@ def federated_epoch(engine, loader, args, optimizer=None, group=None, ops=None, 
         optimizer = EngineOptimizer.from_args(engine, args)
     losses = []
     it = iter(loader)
+    hip_graph = getattr(args, "hip_graph", False)
+    if hip_graph:
+        from .graphed_train import graphed_step
 
     def sync(final, batch_idx):
         fedavg_allreduce(engine.flat, local_flat, weight, secure, pf, 10, group, ops, scratch, masks)
@@ -298,12 +301,15 @@ def federated_epoch(engine, loader, args, optimizer=None, group=None, ops=None, 
     for batch_idx in range(sched.max_batches):
         if sched.trains(rank, batch_idx):
             data, target = next(it)
-            optimizer.zero_grad()
-            sib = getattr(engine, "sibling", None)       # (the ragged final batch of a client's loader)
-            eng = engine if sib is None else sib(data.shape[0])
-            eng.forward(data)
-            losses.append(eng.loss_backward(target, soft=soft_targets).clone())
-            optimizer.step() if eng is engine else optimizer.step(eng)
+            if hip_graph:
+                losses.append(graphed_step(engine, optimizer, data, target, soft=soft_targets).clone())
+            else:
+                optimizer.zero_grad()
+                sib = getattr(engine, "sibling", None)       # (the ragged final batch of a client's loader)
+                eng = engine if sib is None else sib(data.shape[0])
+                eng.forward(data)
+                losses.append(eng.loss_backward(target, soft=soft_targets).clone())
+                optimizer.step() if eng is engine else optimizer.step(eng)
         if sched.sync_after(batch_idx):
             sync(False, batch_idx)
             if not args.keep_optim_dict:

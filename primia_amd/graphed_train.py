@@ -1,0 +1,202 @@
+"""One training step of the host loops (forward + loss + backward + optimizer.step(), torchlib/utils.py:1016-1030 /
+:1236-1292) replayed as a captured hipGraph: `train.py --hip_graph`.
+
+The eager step launches ~130 kernels from Python; replaying the captured step removes that launch cost (bench.py measures
+the same capture on its fixed inputs).  What a training loop needs beyond bench.py's capture:
+
+  * the scheduler's learning rate and Adam's bias corrections change between steps: the graph launches the optimizer's
+    device-scalar entry points (primia_*_dev) and primia_opt_hyper_set writes the scalars before every replay, on the
+    replay's stream (no host-to-device copy, no synchronisation);
+  * the batch is copied into the graph's static input buffers (skipped when the caller already wrote them);
+  * Adam's moments belong to the graphs of the root engine: the optimizer objects the loops re-create at every FedAvg
+    sync (engine.reset_optimizer), `keep_optim_dict` and checkpoint loads all leave `engine.opt_state` pointing at
+    other tensors (or None); before a replay the graph's pair takes their values (zeros for None) and is bound again;
+  * the host counters a replay does not advance (num_batches_tracked, opt_steps) are advanced by what one captured
+    step advanced them by, so eager and graphed steps mix freely on one model;
+  * a replay must never read memory the allocator has freed: the data pointers of every buffer the step touches are
+    compared with those seen at capture, and a mismatch captures again.
+
+Graphs live on the engine they replay (the root engine or a `sibling()`, so that sibling eviction drops them with their
+buffers), keyed by batch size, soft targets, optimizer kind, fuse_sgd_tail and class-weight presence.  Only the root's
+batch size and MixUp's half batch are captured; other sizes (a loader's ragged last batch) and DP-SGD run eagerly.  The
+first step of a key runs eagerly (real training that also allocates the engine's lazy buffers), the second is captured
+and replayed.
+"""
+import gc
+import warnings
+
+import torch
+
+from . import _lib
+from ._lib import call, query
+
+_dp_warned = False
+
+
+def eager_reason(engine, optimizer, batch_size):
+    """Why a step of `batch_size` samples on `engine` runs eagerly under graphed_step, or None when it is graphed."""
+    root = getattr(engine, "_root", engine)
+    if getattr(root, "dp_params", None) is not None:
+        return "DP-SGD runs eagerly: its noise draws have not been shown bit-identical between eager and graphed steps"
+    if getattr(optimizer, "kind", None) not in ("SGD", "Adam"):
+        return "not an EngineOptimizer"
+    if batch_size not in (root.N, root.N // 2):
+        return f"batch size {batch_size} is neither the engine's ({root.N}) nor its half (MixUp)"
+    if not root.training:
+        return "engine in eval mode"
+    return None
+
+
+def _eager(engine, eng, optimizer, data, target, soft):
+    """The loops' step as it is without --hip_graph."""
+    optimizer.zero_grad()
+    eng.forward(data)
+    loss = eng.loss_backward(target, soft=soft)
+    optimizer.step() if eng is engine else optimizer.step(eng)
+    return loss
+
+
+def _key(eng, optimizer, soft):
+    return (eng.N, bool(soft), optimizer.kind, bool(eng.fuse_sgd_tail), eng.class_weight is not None)
+
+
+def _sync_moments(root):
+    """Bind the graphs' Adam moments to the optimizer state the host currently holds (see the module docstring)."""
+    own, st = getattr(root, "_graph_moments", None), root._opt_state
+    if own is None:
+        if st is None:
+            st = (torch.zeros_like(root._grads), torch.zeros_like(root._grads))
+            root._opt_steps = 0
+        root._graph_moments = root._opt_state = st
+        return
+    if st is None:          # a fresh optimizer (reset_optimizer): adam_step would start from zeros and step 0
+        own[0].zero_()
+        own[1].zero_()
+        root._opt_steps = 0
+    elif st[0] is not own[0] or st[1] is not own[1]:      # load_state_dict / another object's moments
+        own[0].copy_(st[0])
+        own[1].copy_(st[1])
+    root._opt_state = own
+
+
+def _fingerprint(eng, g):
+    """Data pointers of every buffer the captured step reads or writes that may be (re)allocated after construction."""
+    ts = [eng.flat, eng._grads, eng.dw_acc, eng.wgrad_ws, eng.x0, eng.x0p, eng.pool_argmax, eng.stat_sums, eng.bn_ws,
+          eng.feat, eng.dfeat, eng.logits, eng.dlogits, eng.loss, eng.class_weight, getattr(eng, "_stem_sums", None),
+          g.x, g.target, g.hyper]
+    ts += list(eng.t.values()) + list(eng.relu_masks.values())
+    for sm, si in eng.save.values():
+        ts += [sm, si]
+    for c in eng.convs.values():
+        ts += [c.w_fwd, c.w_dgrad]
+    if eng.opt_state is not None:
+        ts += list(eng.opt_state)
+    return tuple(t.data_ptr() if t is not None else 0 for t in ts) + (len(eng.relu_masks),)
+
+
+class _StepGraph:
+    """One captured training step of one engine and key."""
+
+    def __init__(self, eng, optimizer, soft, data, target):
+        root = eng._root
+        self.kind, self.soft = optimizer.kind, bool(soft)      # (no reference to the engine: it owns this object)
+        self.x = torch.empty_like(data, memory_format=torch.contiguous_format)
+        self.target = torch.empty_like(target, memory_format=torch.contiguous_format)
+        self.hyper = torch.zeros(8, dtype=torch.float32, device=eng.device)
+        if self.kind == "Adam":
+            _sync_moments(root)
+        # capture runs the step's Python (forward / optimizer.step advance the host counters) without executing a kernel:
+        # keep what one step advances them by, and put them back
+        nbt = dict(eng.num_batches_tracked)
+        steps = root._opt_steps
+        self.graph = torch.cuda.CUDAGraph()
+        # No garbage collection inside the capture: a collected engine (every engine is a reference cycle through
+        # `_root`) would destroy its own graphs and release their memory pools in the middle of this capture, which the
+        # runtime refuses by aborting the process.  Dead engines go now, outside it.
+        gc.collect()
+        gc_on = gc.isenabled()
+        gc.disable()
+        try:
+            # thread_local: another thread of the process (a process group's watchdog) may touch the runtime meanwhile
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                eng.forward(self.x)
+                eng.loss_backward(self.target, soft=self.soft)
+                optimizer.step(eng, hyper=self.hyper)
+        finally:
+            if gc_on:
+                gc.enable()
+        self.nbt_delta = {k: v - nbt[k] for k, v in eng.num_batches_tracked.items() if v != nbt[k]}
+        self.steps_delta = root._opt_steps - steps
+        eng.num_batches_tracked.update(nbt)
+        root._opt_steps = steps
+        self.fingerprint = _fingerprint(eng, self)
+        self.captures = 1
+
+    def replay(self, eng, optimizer, data, target):
+        root = eng._root
+        for src, dst in ((data, self.x), (target, self.target)):
+            if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+                raise ValueError(f"graphed step captured for {dst.dtype} {tuple(dst.shape)}, got {src.dtype} "
+                                 f"{tuple(src.shape)}")
+            if src.data_ptr() != dst.data_ptr():
+                dst.copy_(src)
+        g = optimizer.param_groups[0]
+        if self.kind == "Adam":
+            call("primia_opt_hyper_set", self.hyper, float(g["lr"]), float(g["weight_decay"]), float(g["betas"][0]),
+                 float(g["betas"][1]), float(g["eps"]), root._opt_steps + 1)
+        else:
+            call("primia_opt_hyper_set", self.hyper, float(g["lr"]), float(g["weight_decay"]), 0.0, 0.0, 0.0, 0)
+        self.graph.replay()
+        for k, d in self.nbt_delta.items():
+            eng.num_batches_tracked[k] += d
+        root._opt_steps += self.steps_delta
+        return eng.loss
+
+
+def graphed_step(engine, optimizer, data, target, soft=False):
+    """One training step of `engine` (the loop's model: its sibling of data's batch size runs it) with `optimizer`
+    (primia_amd.optim.EngineOptimizer), as a replayed hipGraph where it can be (see the module docstring), eagerly
+    otherwise.  Returns the engine's device loss scalar; the next step overwrites it, so keep a `.clone()`."""
+    global _dp_warned
+    n = int(data.shape[0])
+    eng = engine if n == engine.N else engine.sibling(n)
+    reason = eager_reason(engine, optimizer, n)
+    if reason is not None:
+        if getattr(engine._root, "dp_params", None) is not None and not _dp_warned:
+            _dp_warned = True
+            warnings.warn("hip_graph: " + reason, RuntimeWarning, stacklevel=2)
+        return _eager(engine, eng, optimizer, data, target, soft)
+    key = _key(eng, optimizer, soft)
+    graphs = eng.__dict__.setdefault("_step_graphs", {})
+    g = graphs.get(key)
+    if g is None:
+        warm = eng.__dict__.setdefault("_step_graphs_warm", set())
+        if key not in warm:
+            warm.add(key)
+            return _eager(engine, eng, optimizer, data, target, soft)
+    if query("primia_options_epoch") != eng._options_epoch:
+        raise _lib.PrimiaError("library options changed (primia_set_option) after this engine sized its buffers: "
+                               "set options first, then construct the engine")
+    optimizer.zero_grad()
+    earlier = 0
+    if g is not None:
+        if g.kind == "Adam":
+            _sync_moments(eng._root)
+        if _fingerprint(eng, g) != g.fingerprint:       # a buffer of the step was reallocated: capture again
+            earlier = g.captures
+            del graphs[key]
+            g = None
+    if g is None:
+        g = graphs[key] = _StepGraph(eng, optimizer, soft, data, target)
+        g.captures += earlier
+    return g.replay(eng, optimizer, data, target)
+
+
+def captures(engine):
+    """{key: number of captures} of the graphs held by `engine`'s root and its siblings (tests, tools)."""
+    root = engine._root
+    out = {}
+    for e in [root] + list(root.__dict__.get("_siblings", {}).values()):
+        for k, g in e.__dict__.get("_step_graphs", {}).items():
+            out[k] = g.captures
+    return out

@@ -46,17 +46,19 @@ class EngineOptimizer:
     def zero_grad(self):
         pass   # every backward pass of the engine overwrites the gradient arena
 
-    def step(self, engine=None):
+    def step(self, engine=None, hyper=None):
         """`engine`: the engine whose backward pass produced the gradients, when it is a sibling of the one this optimizer
-        was built on (ResNet18Engine.sibling: same parameters and optimizer state, another batch size)."""
+        was built on (ResNet18Engine.sibling: same parameters and optimizer state, another batch size).  `hyper`: the
+        device scalars of primia_opt_hyper_set, read by the step instead of param_groups (primia_amd.graphed_train)."""
         eng = self.engine if engine is None else engine
         if eng is not self.engine and getattr(eng, "_root", eng) is not getattr(self.engine, "_root", self.engine):
             raise ValueError("optimizer.step(engine): not a sibling of the optimizer's engine")
         g = self.param_groups[0]
+        kw = {} if hyper is None else {"hyper": hyper}
         if self.kind == "SGD":
-            eng.sgd_step(g["lr"], g["weight_decay"])
+            eng.sgd_step(g["lr"], g["weight_decay"], **kw)
         else:
-            eng.adam_step(g["lr"], g["betas"], g["eps"], g["weight_decay"])
+            eng.adam_step(g["lr"], g["betas"], g["eps"], g["weight_decay"], **kw)
 
     # ---- torch's checkpoint format --------------------------------------------------------------------------------
     def _slices(self):

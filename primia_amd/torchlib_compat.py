@@ -288,6 +288,9 @@ def secure_aggregation_epoch(args, models, device, train_loaders, optimizers, ep
     for w in list(optimizers):
         optimizers[w] = (EngineOptimizer.from_args(models[w], args) if not args.keep_optim_dict
                          else _as_optimizer(models[w], optimizers[w], args))
+    hip_graph = getattr(args, "hip_graph", False)
+    if hip_graph:
+        from .graphed_train import graphed_step
     avg_loss = []
     num_batches = {wid(w): len(tl) for w, tl in train_loaders.items()}
     loaders = {w: iter(tl) for w, tl in train_loaders.items()}
@@ -299,10 +302,15 @@ def secure_aggregation_epoch(args, models, device, train_loaders, optimizers, ep
                 continue
             optimizers[i].zero_grad()
             data, target = next(it)
+            soft = getattr(loss_fns.get(i), "soft", False) if loss_fns else False
+            if hip_graph:
+                # the device loss stays on the device until the epoch ends (no wait on the GPU per step)
+                avg_loss.append(graphed_step(models[i], optimizers[i], data, target, soft=soft).clone())
+                continue
             sib = getattr(models[i], "sibling", None)    # (the ragged final batch of a client's loader)
             eng = models[i] if sib is None else sib(data.shape[0])
             eng.forward(data)
-            loss = eng.loss_backward(target, soft=getattr(loss_fns.get(i), "soft", False) if loss_fns else False)
+            loss = eng.loss_backward(target, soft=soft)
             optimizers[i].step() if eng is models[i] else optimizers[i].step(eng)
             avg_loss.append(loss.item())
         if batch_idx > 0 and batch_idx % args.sync_every_n_batch == 0:
@@ -316,6 +324,10 @@ def secure_aggregation_epoch(args, models, device, train_loaders, optimizers, ep
     models["local_model"] = aggregation(models["local_model"], models, train_loaders.keys(), crypto_provider, args,
                                         test_params, weights=weights, secure=secure)
     models = send_new_models(models["local_model"], models)
+    if hip_graph and avg_loss:
+        import torch
+
+        avg_loss = torch.cat(avg_loss).cpu().tolist()        # the same float32 values loss.item() reads
     return models, float(np.mean(avg_loss))
 
 
@@ -351,11 +363,16 @@ def train(args, model, device, train_loader, optimizer, epoch, loss_fn, num_clas
             soft = True
         # MixUp mixes the two halves of a batch with probability mixup_prob and passes it on whole otherwise: consecutive
         # steps see B or B / 2 samples (:1262-1267).  A sibling engine serves the other size on the same parameters.
-        eng = model if data.shape[0] == getattr(model, "N", data.shape[0]) else model.sibling(data.shape[0])
-        optimizer.zero_grad()
-        eng.forward(data)
-        loss = eng.loss_backward(target, soft=soft)
-        optimizer.step() if eng is model else optimizer.step(eng)
+        if getattr(args, "hip_graph", False):
+            from .graphed_train import graphed_step
+
+            loss = graphed_step(model, optimizer, data, target, soft=soft)
+        else:
+            eng = model if data.shape[0] == getattr(model, "N", data.shape[0]) else model.sibling(data.shape[0])
+            optimizer.zero_grad()
+            eng.forward(data)
+            loss = eng.loss_backward(target, soft=soft)
+            optimizer.step() if eng is model else optimizer.step(eng)
         if batch_idx % args.log_interval == 0:
             losses.append(loss.item())
             if verbose:

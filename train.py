@@ -5,7 +5,7 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
 
     python train.py --config configs/torch/pneumonia-resnet-pretrained.ini --train_federated \
         [--unencrypted_aggregation] [--data_dir DIR|synthetic] [--cuda] [--resume_checkpoint P] \
-        [--save_file F] [--training_name N]
+        [--save_file F] [--training_name N] [--hip_graph]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -435,12 +435,16 @@ if __name__ == "__main__":
     parser.add_argument("--verbose", action="store_true")
     parser.add_argument("--save_file", type=str, default="model_weights/completed_trainings.csv")
     parser.add_argument("--training_name", default=None, type=str)
+    parser.add_argument("--hip_graph", action="store_true",
+                        help="training: capture each training step once as a hipGraph and replay it per batch (the "
+                             "learning rate and Adam's step reach the replay on the device; FedAvg runs between replays)")
     cmd_args = parser.parse_args()
     config = configparser.ConfigParser()
     assert path.isfile(cmd_args.config), "Configuration file not found"
     config.read(cmd_args.config)
     cmd_args.websockets = False  # in-process / RCCL clients replace the websocket transport
     args = Arguments(cmd_args, config, mode="train", verbose=int(os.environ.get("RANK", 0)) == 0)
+    args.hip_graph = cmd_args.hip_graph
     if args.train_federated and (args.mixup or args.weight_classes):
         if args.mixup and args.mixup_lambda == 0.5:
             args.mixup_lambda = 0.499
