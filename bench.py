@@ -1,19 +1,24 @@
 #!/usr/bin/env python3
 """Headline benchmark: ResNet-18 federated-client training throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one pass of the hot path over one synthetic batch on every client: forward, loss,
 backward, SGD (lr 1e-4, wd 5e-4 — the reference's pneumonia-resnet-pretrained.ini), plus, for
 N > 1, the FedAvg exchange every `sync_every_n_batch` = 3 steps (BASELINE.json configs[2]).
 N = 1 is BASELINE.json configs[1]: bf16, batch 256, 3x224x224 synthetic, inputs resident in HBM.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the contract fields with what the timed steps give beside them.
+Everything else the benchmark measures runs only under --full, whose line also carries
+  sustained    : the same steps over >= --sustain-s seconds (N = 1)
   roofline     : MFMA roofline of the dominant convolution kernel, measured live with HIP events
                  on the launch stream; algorithmic FLOPs = 2*MACs of the layers it ran
                  (10.881 GFLOP / image over fwd + dgrad + wgrad)
   cpu_baseline : the oracle (torch-CPU fp32 restatement of the reference step) timed on the host
-                 cores on a bounded sample, rank 0 at N = 1 only.
+                 cores on a bounded sample, rank 0 at N = 1 only
+  encrypted_inference, dp_sgd : the other BASELINE metrics, each from a child process (N = 1)
+  collective, cpu_baseline_b2 : which collective ran on which GPUs, and BASELINE.md B2 (N > 1)
 """
 import argparse
 import json
@@ -37,6 +42,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)      # >= 20 warm-up + >= 100 timed steps
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: sustained clock, roofline, CPU baseline, encrypted "
+                         "inference, DP-SGD, collective identification (the --no-* switches and --sustain-s trim them)")
     ap.add_argument("--sustain-s", type=float, default=5.0, help="length of the extra sustained-clock run at N = 1 (0: skip)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--size", type=int, default=224)
@@ -145,6 +153,128 @@ def cpu_baseline(batch, size, budget_s=30.0):
             "sample": f"{n} fp32 train steps of batch {batch} at {size}x{size} on {best} threads, the best of "
                       f"{counts} (oracle/train_oracle.py, torch-CPU; BASELINE.md B1)",
             "thread_probe": {str(c): r for c, r in probe.items()}}
+
+
+def roofline(eng, a, dtype, local_step):
+    """The `roofline` field of a --full line."""
+    # ---- roofline leg: per-launch HIP events around every convolution kernel ----------------------
+    # One untimed eager step first (the timed region replays graphs), then `nprof` profiled steps.  A launch's
+    # duration is the MEDIAN over the profiled steps: the events bracket the host-side call too, so a host hiccup
+    # between the two records (GC, a page fault) would otherwise be booked as kernel time.
+    local_step(0)
+    torch.cuda.synchronize()
+    eng.prof = []
+    nprof = 5
+    for i in range(nprof):
+        local_step(i)
+    torch.cuda.synchronize()
+    # Launches are grouped by the kernel that serves them (the library's dispatch rules: conv_igemm.hip,
+    # conv_wgrad.hip) so that every group's average duration can be checked against the rocprofv3
+    # per-kernel averages under profiles/.
+    # The library itself says which kernel its dispatch rules pick for a layer (primia_conv_kernel_id, include/primia_hip.h),
+    # so runs under PRIMIA_LH2=0 / PRIMIA_WGP32=0 / ... are labelled with what ran.  Forward and data gradient of the
+    # wide 3x3 layers are ONE kernel (same code, flipped taps) and therefore one family.
+    from primia_amd import _lib
+    from primia_amd._lib import query
+
+    KNAME = {1: "conv_igemm_kernel", 5: "conv_s2lh_kernel (stride-2 3x3 + 1x1, fwd + dgrad)", 2: "conv3x3_c64_kernel (fwd + dgrad)", 4: "conv3x3_lh2_kernel (fwd + dgrad)",
+             6: "conv3x3_lh4_kernel (fwd + dgrad)",
+             13: "conv_wgrad_dma_kernel (per-tap, stride 2 / 1x1)", 14: "conv_wgrad_kernel (per-tap, stride 2 / 1x1)",
+             16: "conv_wgrad_patch33_kernel + wgrad_patch32_reduce_kernel",
+             18: "conv_wgrad_patch33lw_kernel + wgrad_patch32_reduce_kernel",
+             17: "conv_wgrad_tap_kernel + wgrad_tile_reduce_kernel (per-tap, stride 2 / 1x1)"}
+    dtc = _lib.dtype_code(dtype)
+
+    def family(kind, name):     # (also used as family_of below)
+        sp = eng.convs[name].spec
+        if sp.k == 7:
+            if kind != "wgrad":
+                return "stem_conv_fwd_kernel"
+            # (fused: the kernel also forms its dy tiles from y / dpooled / argmax — bn1, relu and maxpool backward)
+            return "stem_conv_wgrad_kernel<fused>" if getattr(eng, "stem_bwd_fused_active", False) else "stem_conv_wgrad_kernel"
+        d = eng.convs[name].desc
+        if kind == "wgrad":
+            return KNAME[query("primia_conv_wgrad_kernel_id", d, dtc)]
+        kid = query("primia_conv_kernel_id", d, 0 if kind == "fwd" else 1, dtc)
+        return KNAME.get(kid, "kernel id %d" % kid) + ("<%s>" % kind if kid == 1 else "")
+
+    family_of = family
+    per_launch = {}
+    for kind, name, flops, e0, e1 in eng.prof:
+        per_launch.setdefault((kind, name), (flops, []))[1].append(e0.elapsed_time(e1))
+    launch_table = per_launch
+    agg, fam, layers = {}, {}, {}
+    for (kind, name), (flops, samples) in per_launch.items():
+        samples.sort()
+        layers[f"{kind}:{name}"] = round(samples[len(samples) // 2] * 1e3, 1)     # median launch, us
+        ms = samples[len(samples) // 2] * nprof   # median launch, scaled so the tables below stay per-nprof sums
+        for table, key in ((agg, kind), (fam, family(kind, name))):
+            d = table.setdefault(key, {"ms": 0.0, "flops": 0.0, "launches": 0})
+            d["ms"] += ms
+            d["flops"] += flops * nprof
+            d["launches"] += nprof
+    eng.prof = None
+    peak = MFMA_PEAK_TFLOPS[a.dtype]
+
+    def summarise(table):
+        return {k: {"tflops": round(d["flops"] / (d["ms"] * 1e-3) / 1e12, 2), "ms_per_step": round(d["ms"] / nprof, 4),
+                    "avg_launch_us": round(d["ms"] * 1e3 / d["launches"], 2),
+                    "launches_per_step": d["launches"] // nprof} for k, d in table.items()}
+
+    kernels, by_pass = summarise(fam), summarise(agg)
+    dom = max(fam, key=lambda k: fam[k]["ms"])
+    conv_ms = sum(d["ms"] for d in agg.values()) / nprof
+    conv_fl = sum(d["flops"] for d in agg.values()) / nprof
+    # `traffic` needs PMC counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, tools/profile_round.sh),
+    # which cannot be collected from inside the timed process.  The committed passes over this same command carry the
+    # sha256 of the library sources they ran (primia_amd.build.source_digest): `traffic` is their per-launch figure when
+    # that digest equals the one of the code running NOW, null otherwise (then `traffic_offline` still names the file,
+    # marked stale).
+    traffic = None
+    traffic_offline = None
+    tpath = os.path.join(ROOT, "profiles", TRAFFIC_FILE)
+    if os.path.exists(tpath) and a.batch == 256 and a.size == 224 and a.dtype == "bf16":
+        from primia_amd.build import source_digest
+        rec = json.load(open(tpath))
+        key = dom.split(" ")[0].split("<")[0]     # the kernel that ran; no record for it -> traffic_offline stays null
+        if key in rec:
+            same = rec.get("_source_sha256") == source_digest()
+            per_launch = rec[key].get("hbm_bytes_per_launch")
+            traffic_offline = {"hbm_bytes_per_launch": per_launch, "kernel": key,
+                               "source": "profiles/" + TRAFFIC_FILE, "same_sources_as_this_run": same}
+            if same:
+                traffic = per_launch
+    # the wide 3x3 / stride-1 layers (layer2-4 forward + data gradient) are ONE algorithm on two kernels — conv3x3_lh2_kernel
+    # (392-pixel tiles) and conv3x3_lh4_kernel (196-pixel tiles, loader waves): reported together beside the dominant kernel
+    wide = [k for k in fam if k.startswith("conv3x3_lh2_kernel") or k.startswith("conv3x3_lh4_kernel")]
+    family = None
+    if wide:
+        f_ms, f_fl, f_n = (sum(fam[k][q] for k in wide) for q in ("ms", "flops", "launches"))
+        family = {"kernels": wide, "tflops": round(f_fl / (f_ms * 1e-3) / 1e12, 2), "frac": round(f_fl / (f_ms * 1e-3) / 1e12 / peak, 4),
+                  "ms_per_step": round(f_ms / nprof, 4), "avg_launch_us": round(f_ms * 1e3 / f_n, 2), "launches_per_step": f_n // nprof}
+        # the family's FORWARD launches alone: since round 5 six of its data-gradient launches also form the BatchNorm backward
+        # sums of the layer in front of them in their write-back (engine.dgrad_bnsums: the reduction passes they replace are
+        # gone from the step), so the family's own time per FLOP went UP while the step's went down
+        fw = [(fl_, sm_) for (kind_, name_), (fl_, sm_) in launch_table.items() if kind_ == "fwd" and family_of(kind_, name_) in wide]
+        if fw:
+            w_ms = sum(sorted(sm_)[len(sm_) // 2] for _, sm_ in fw)
+            w_fl = sum(fl_ for fl_, _ in fw)
+            family["forward_only"] = {"launches_per_step": len(fw), "tflops": round(w_fl / (w_ms * 1e-3) / 1e12, 2),
+                                      "frac": round(w_fl / (w_ms * 1e-3) / 1e12 / peak, 4)}
+            family["note"] = ("data-gradient launches with engine.dgrad_bnsums include the BatchNorm backward sums of the layer "
+                              "in front of them")
+    roof = {"bound": "mfma", "kernel": dom,
+            "kernel_is": "the kernel (one C-ABI call; a weight-gradient call = the kernel + its ordered reduce) with the most time per step",
+            "launch": "median over %d steps of the HIP-event bracket around one C-ABI call" % nprof,
+            "achieved": kernels[dom]["tflops"], "peak": peak, "unit": "TFLOP/s",
+            "frac": round(kernels[dom]["tflops"] / peak, 4), "traffic": traffic, "traffic_offline": traffic_offline,
+            # (`frac` is priced at the nominal 2.4 GHz dense-bf16 peak; what the part sustains under matrix load is measured in
+            # profiles/r04_mfma_ceilings.txt and discussed in DESIGN.md — no constants from there are repeated here)
+            "wide3x3_family": family,
+            "all_conv": {"tflops": round(conv_fl / (conv_ms * 1e-3) / 1e12, 2), "ms_per_step": round(conv_ms, 3),
+                         "frac": round(conv_fl / (conv_ms * 1e-3) / 1e12 / peak, 4)},
+            "kernels": kernels, "by_pass": by_pass, "layers_us": layers}
+    return roof
 
 
 def main():
@@ -310,140 +440,9 @@ def main():
         # the last timed step's results, before the legs below run more steps on the same engine.  Inputs are seeded
         # (weights: torch.manual_seed(42); batches: generator 1000 + rank), so equal arguments mean equal inputs.
         dump_outputs(a.dump_outputs, {"logits": eng.logits, "loss": eng.loss, "weights": eng.flat})
-    # A second figure over >= 5 s of back-to-back steps: the 100-step region above lasts ~0.6 s, short enough for the
-    # chip to ride its boost clock; this one shows what it sustains (same run() calls, own barriers).
-    sustained = None
-    if world == 1 and a.sustain_s > 0:
-        n_sus = max(a.steps, int(a.sustain_s / (dt / a.steps)) + 1)
-        barrier()
-        t1 = time.perf_counter()
-        for i in range(n_sus):
-            run(i)
-        barrier()
-        dts = time.perf_counter() - t1
-        sustained = {"steps": n_sus, "seconds": round(dts, 3), "images_per_sec": round(a.batch * n_sus / dts, 1),
-                     "ms_per_step": round(dts / n_sus * 1e3, 3)}
-
-    # ---- roofline leg: per-launch HIP events around every convolution kernel ----------------------
-    # One untimed eager step first (the timed region replays graphs), then `nprof` profiled steps.  A launch's
-    # duration is the MEDIAN over the profiled steps: the events bracket the host-side call too, so a host hiccup
-    # between the two records (GC, a page fault) would otherwise be booked as kernel time.
-    local_step(0)
-    torch.cuda.synchronize()
-    eng.prof = []
-    nprof = 5
-    for i in range(nprof):
-        local_step(i)
-    torch.cuda.synchronize()
-    # Launches are grouped by the kernel that serves them (the library's dispatch rules: conv_igemm.hip,
-    # conv_wgrad.hip) so that every group's average duration can be checked against the rocprofv3
-    # per-kernel averages under profiles/.
-    # The library itself says which kernel its dispatch rules pick for a layer (primia_conv_kernel_id, include/primia_hip.h),
-    # so runs under PRIMIA_LH2=0 / PRIMIA_WGP32=0 / ... are labelled with what ran.  Forward and data gradient of the
-    # wide 3x3 layers are ONE kernel (same code, flipped taps) and therefore one family.
-    from primia_amd import _lib
-    from primia_amd._lib import query
-
-    KNAME = {1: "conv_igemm_kernel", 5: "conv_s2lh_kernel (stride-2 3x3 + 1x1, fwd + dgrad)", 2: "conv3x3_c64_kernel (fwd + dgrad)", 4: "conv3x3_lh2_kernel (fwd + dgrad)",
-             6: "conv3x3_lh4_kernel (fwd + dgrad)",
-             13: "conv_wgrad_dma_kernel (per-tap, stride 2 / 1x1)", 14: "conv_wgrad_kernel (per-tap, stride 2 / 1x1)",
-             16: "conv_wgrad_patch33_kernel + wgrad_patch32_reduce_kernel",
-             18: "conv_wgrad_patch33lw_kernel + wgrad_patch32_reduce_kernel",
-             17: "conv_wgrad_tap_kernel + wgrad_tile_reduce_kernel (per-tap, stride 2 / 1x1)"}
-    dtc = _lib.dtype_code(dtype)
-
-    def family(kind, name):     # (also used as family_of below)
-        sp = eng.convs[name].spec
-        if sp.k == 7:
-            if kind != "wgrad":
-                return "stem_conv_fwd_kernel"
-            # (fused: the kernel also forms its dy tiles from y / dpooled / argmax — bn1, relu and maxpool backward)
-            return "stem_conv_wgrad_kernel<fused>" if getattr(eng, "stem_bwd_fused_active", False) else "stem_conv_wgrad_kernel"
-        d = eng.convs[name].desc
-        if kind == "wgrad":
-            return KNAME[query("primia_conv_wgrad_kernel_id", d, dtc)]
-        kid = query("primia_conv_kernel_id", d, 0 if kind == "fwd" else 1, dtc)
-        return KNAME.get(kid, "kernel id %d" % kid) + ("<%s>" % kind if kid == 1 else "")
-
-    family_of = family
-    per_launch = {}
-    for kind, name, flops, e0, e1 in eng.prof:
-        per_launch.setdefault((kind, name), (flops, []))[1].append(e0.elapsed_time(e1))
-    launch_table = per_launch
-    agg, fam, layers = {}, {}, {}
-    for (kind, name), (flops, samples) in per_launch.items():
-        samples.sort()
-        layers[f"{kind}:{name}"] = round(samples[len(samples) // 2] * 1e3, 1)     # median launch, us
-        ms = samples[len(samples) // 2] * nprof   # median launch, scaled so the tables below stay per-nprof sums
-        for table, key in ((agg, kind), (fam, family(kind, name))):
-            d = table.setdefault(key, {"ms": 0.0, "flops": 0.0, "launches": 0})
-            d["ms"] += ms
-            d["flops"] += flops * nprof
-            d["launches"] += nprof
-    eng.prof = None
-    peak = MFMA_PEAK_TFLOPS[a.dtype]
-
-    def summarise(table):
-        return {k: {"tflops": round(d["flops"] / (d["ms"] * 1e-3) / 1e12, 2), "ms_per_step": round(d["ms"] / nprof, 4),
-                    "avg_launch_us": round(d["ms"] * 1e3 / d["launches"], 2),
-                    "launches_per_step": d["launches"] // nprof} for k, d in table.items()}
-
-    kernels, by_pass = summarise(fam), summarise(agg)
-    dom = max(fam, key=lambda k: fam[k]["ms"])
-    conv_ms = sum(d["ms"] for d in agg.values()) / nprof
-    conv_fl = sum(d["flops"] for d in agg.values()) / nprof
-    # `traffic` needs PMC counters (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, tools/profile_round.sh),
-    # which cannot be collected from inside the timed process.  The committed passes over this same command carry the
-    # sha256 of the library sources they ran (primia_amd.build.source_digest): `traffic` is their per-launch figure when
-    # that digest equals the one of the code running NOW, null otherwise (then `traffic_offline` still names the file,
-    # marked stale).
-    traffic = None
-    traffic_offline = None
-    tpath = os.path.join(ROOT, "profiles", TRAFFIC_FILE)
-    if os.path.exists(tpath) and a.batch == 256 and a.size == 224 and a.dtype == "bf16":
-        from primia_amd.build import source_digest
-        rec = json.load(open(tpath))
-        key = dom.split(" ")[0].split("<")[0]     # the kernel that ran; no record for it -> traffic_offline stays null
-        if key in rec:
-            same = rec.get("_source_sha256") == source_digest()
-            per_launch = rec[key].get("hbm_bytes_per_launch")
-            traffic_offline = {"hbm_bytes_per_launch": per_launch, "kernel": key,
-                               "source": "profiles/" + TRAFFIC_FILE, "same_sources_as_this_run": same}
-            if same:
-                traffic = per_launch
-    # the wide 3x3 / stride-1 layers (layer2-4 forward + data gradient) are ONE algorithm on two kernels — conv3x3_lh2_kernel
-    # (392-pixel tiles) and conv3x3_lh4_kernel (196-pixel tiles, loader waves): reported together beside the dominant kernel
-    wide = [k for k in fam if k.startswith("conv3x3_lh2_kernel") or k.startswith("conv3x3_lh4_kernel")]
-    family = None
-    if wide:
-        f_ms, f_fl, f_n = (sum(fam[k][q] for k in wide) for q in ("ms", "flops", "launches"))
-        family = {"kernels": wide, "tflops": round(f_fl / (f_ms * 1e-3) / 1e12, 2), "frac": round(f_fl / (f_ms * 1e-3) / 1e12 / peak, 4),
-                  "ms_per_step": round(f_ms / nprof, 4), "avg_launch_us": round(f_ms * 1e3 / f_n, 2), "launches_per_step": f_n // nprof}
-        # the family's FORWARD launches alone: since round 5 six of its data-gradient launches also form the BatchNorm backward
-        # sums of the layer in front of them in their write-back (engine.dgrad_bnsums: the reduction passes they replace are
-        # gone from the step), so the family's own time per FLOP went UP while the step's went down
-        fw = [(fl_, sm_) for (kind_, name_), (fl_, sm_) in launch_table.items() if kind_ == "fwd" and family_of(kind_, name_) in wide]
-        if fw:
-            w_ms = sum(sorted(sm_)[len(sm_) // 2] for _, sm_ in fw)
-            w_fl = sum(fl_ for fl_, _ in fw)
-            family["forward_only"] = {"launches_per_step": len(fw), "tflops": round(w_fl / (w_ms * 1e-3) / 1e12, 2),
-                                      "frac": round(w_fl / (w_ms * 1e-3) / 1e12 / peak, 4)}
-            family["note"] = ("data-gradient launches with engine.dgrad_bnsums include the BatchNorm backward sums of the layer "
-                              "in front of them")
-    roof = {"bound": "mfma", "kernel": dom,
-            "kernel_is": "the kernel (one C-ABI call; a weight-gradient call = the kernel + its ordered reduce) with the most time per step",
-            "launch": "median over %d steps of the HIP-event bracket around one C-ABI call" % nprof,
-            "achieved": kernels[dom]["tflops"], "peak": peak, "unit": "TFLOP/s",
-            "frac": round(kernels[dom]["tflops"] / peak, 4), "traffic": traffic, "traffic_offline": traffic_offline,
-            # (`frac` is priced at the nominal 2.4 GHz dense-bf16 peak; what the part sustains under matrix load is measured in
-            # profiles/r04_mfma_ceilings.txt and discussed in DESIGN.md — no constants from there are repeated here)
-            "wide3x3_family": family,
-            "all_conv": {"tflops": round(conv_fl / (conv_ms * 1e-3) / 1e12, 2), "ms_per_step": round(conv_ms, 3),
-                         "frac": round(conv_fl / (conv_ms * 1e-3) / 1e12 / peak, 4)},
-            "kernels": kernels, "by_pass": by_pass, "layers_us": layers}
-
     ms_per_step = dt / a.steps * 1e3
     total_ips = a.batch * world * a.steps / dt
+    peak = MFMA_PEAK_TFLOPS[a.dtype]
     out = {
         "metric": "images_per_sec", "value": round(total_ips, 1), "unit": "images/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -456,11 +455,27 @@ def main():
         "images_per_sec_per_client": round(total_ips / world, 1),
         "step_tflops": round(GFLOP_PER_IMAGE * 1e9 * a.batch / (dt / a.steps) / 1e12, 2),
         "step_mfma_frac": round(GFLOP_PER_IMAGE * 1e9 * a.batch / (dt / a.steps) / 1e12 / peak, 4),
-        "final_loss": round(loss, 5), "hip_graph": graphs is not None, "sustained": sustained,
+        "final_loss": round(loss, 5), "hip_graph": graphs is not None,
         "fedavg_ms_per_sync": fedavg_ms,
-        "roofline": roof,
     }
-    if world > 1:
+    # ---- --full: the legs that measure something besides the headline; a plain run prints the line above ----
+    if a.full:
+        # A second figure over >= 5 s of back-to-back steps: the 100-step region above lasts ~0.6 s, short enough for the
+        # chip to ride its boost clock; this one shows what it sustains (same run() calls, own barriers).
+        sustained = None
+        if world == 1 and a.sustain_s > 0:
+            n_sus = max(a.steps, int(a.sustain_s / (dt / a.steps)) + 1)
+            barrier()
+            t1 = time.perf_counter()
+            for i in range(n_sus):
+                run(i)
+            barrier()
+            dts = time.perf_counter() - t1
+            sustained = {"steps": n_sus, "seconds": round(dts, 3), "images_per_sec": round(a.batch * n_sus / dts, 1),
+                         "ms_per_step": round(dts / n_sus * 1e3, 3)}
+        out["sustained"] = sustained
+        out["roofline"] = roofline(eng, a, dtype, local_step)
+    if a.full and world > 1:
         # proof that the exchange ran on RCCL with `world` ranks, and BASELINE.md B2 beside it
         ver = None
         try:
@@ -483,9 +498,9 @@ def main():
                           "host cores (torchlib/utils.py:1159-1174), so its per-client rate is B1 / K and its aggregate rate is B1",
             "K": world, "value_per_client": "cpu_baseline.value of the N = 1 line / %d" % world,
             "note": "cpu_baseline is timed on rank 0 at N = 1 only (bench contract); B1 does not depend on N"}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.cpu_baseline_batch, a.size)
-    if rank == 0 and world == 1 and not a.no_secure:
+    if a.full and rank == 0 and world == 1 and not a.no_secure:
         # second BASELINE.json metric: encrypted-inference ms/image (3 roles on this GPU), as a child
         # process so that its allocations never share the training engine's pool
         import subprocess
@@ -500,14 +515,14 @@ def main():
             out["encrypted_inference"] = json.loads(r.stdout.strip().splitlines()[-1])
         except Exception:  # noqa: BLE001 - the primary metric must still be reported
             out["encrypted_inference"] = {"error": (r.stderr or r.stdout)[-300:]}
-    if rank == 0 and world == 1 and not a.dp and not a.no_dp_leg and not a.no_secure and a.dtype == "bf16":
+    if a.full and rank == 0 and world == 1 and not a.dp and not a.no_dp_leg and not a.no_secure and a.dtype == "bf16":
         # BASELINE configs[3] beside the headline: the DP-SGD step (GroupNorm network, per-sample clip 1.0 + Gaussian noise 1.3) at
         # the same batch, as a child process with its own engine — so that the driver's line carries a DP figure, not only
         # profiles/ (VERDICT r05 weak #14).  Same contract: hipGraph replay, 30 timed steps, inputs resident.
         import subprocess
 
-        cmd = [sys.executable, os.path.abspath(__file__), "--dp", "--steps", "30", "--warmup", "5", "--no-secure",
-               "--no-cpu-baseline", "--sustain-s", "0", "--batch", str(a.batch), "--size", str(a.size)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--dp", "--steps", "30", "--warmup", "5", "--batch", str(a.batch),
+               "--size", str(a.size)]
         if a.lib:
             cmd += ["--lib", a.lib]
         try:

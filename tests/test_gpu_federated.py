@@ -183,11 +183,12 @@ def test_bench_two_ranks_control_flow(tmp_path, secure):
 
 def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no WORLD_SIZE in the environment: the parent (which never touches the GPU) starts
-    the two ranks as a child under torch.distributed.run, relays rank 0's JSON line and the exit code."""
+    the two ranks as a child under torch.distributed.run, relays rank 0's JSON line and the exit code.  With --full, the
+    line also carries the collective's identification and the roofline."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(PRIMIA_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "1", "--batch", "8", "--size", "64",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

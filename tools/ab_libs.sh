@@ -3,7 +3,7 @@
 # library); alternating runs, 200 timed steps each, prints images/s, ms per step and the layer1 / stem launches per run.
 # The libraries are loaded with bench.py --lib: the shipped one is never overwritten.
 rounds=$1; shift
-B="python bench.py --no-secure --no-cpu-baseline --sustain-s 0 --steps 200"
+B="python bench.py --full --no-secure --no-cpu-baseline --sustain-s 0 --steps 200"
 for i in $(seq $rounds); do
   for lib in "$@"; do
     if [ "$lib" = base ]; then L=""; else L="--lib $lib"; fi

@@ -16,5 +16,6 @@ bash tools/pmc_secure.sh > gpurun_out/${R}_pmc_secure.log 2>&1
 rm -rf gpurun_out/prof_$R gpurun_out/prof_secure_$R gpurun_out/pmc_secure
 python3 -m pytest tests -m gpu -q > gpurun_out/${R}_gpu_tests.log 2>&1
 tail -3 gpurun_out/${R}_gpu_tests.log | cut -c1-200
-python3 bench.py > gpurun_out/${R}_bench_final.json 2> gpurun_out/${R}_bench_final.err
-tail -c 400 gpurun_out/${R}_bench_final.json
+D=$(dirname "$O")      # (where every file above lands)
+python3 bench.py --full > "$D/${R}_bench_final.json" 2> "$D/${R}_bench_final.err"
+tail -c 400 "$D/${R}_bench_final.json"
