@@ -46,10 +46,10 @@ typedef void* primia_stream_t; /* hipStream_t */
 int primia_abi_version(void);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
- * The library never reads the environment.  Every switch that selects between kernels or sizes a launch (the A/B knobs
- * of the measurements under profiles/) is an entry of ONE process-wide table with the defaults the benchmarks run on:
- * primia_set_option("lh2", 0) keeps the wide 3x3 layers on the implicit GEMM, ("wgp_group", 0) launches every weight
- * gradient on its own, ("dp_ghost", 0) takes the DP-SGD norms from the weight-gradient kernels, ...  The names, defaults
+ * The library never reads the environment.  The switches that select between kernels or size a launch, and that a
+ * test or a tool still sets, are the eight entries of ONE process-wide table with the defaults the benchmarks run on:
+ * primia_set_option("lh2", 0) keeps the wide 3x3 layers on the implicit GEMM, ("s2lh", 7) puts every pass of the
+ * transition blocks on conv_s2lh_kernel, ("c64_stages", 3) shortens conv3x3_c64_kernel's ring, ...  The names, defaults
  * and meanings are listed in primia_amd/csrc/options.h; unknown names return PRIMIA_ERR_ARG.  Options are read when a
  * call dispatches (and by the *_bytes / *_ok / *_kernel_id queries, which therefore must be asked again after a
  * change).  Each entry is read and written atomically (no torn values, callable from any thread), but a SEQUENCE of
@@ -198,7 +198,7 @@ int primia_stem_conv_wgrad_ws(const void* x_padded, const void* dy, float* dw_ac
  * BatchNorm that follows — are accumulated into stat_sums, laid out [slots][2][K] with
  * slots = primia_conv_stat_slots() partial sums (spread to keep atomics uncontended); caller zeroes it. */
 /* Which kernel the library's dispatch rules select for a convolution (measurement tooling: bench.py names its
- * roofline families with it, so a run under primia_set_option("lh2", 0) / ("wgrad_kernel", 2) / ... reports the kernel that
+ * roofline families with it, so a run under primia_set_option("lh2", 0) / ("s2lh", 7) / ... reports the kernel that
  * actually ran).  pass 0 = forward, 1 = data gradient:
  *   1 conv_igemm_kernel   2 conv3x3_c64_kernel   4 conv3x3_lh2_kernel   (3: conv3x3_lh_kernel, removed in round 4)
  *   5 conv_s2lh_kernel (the stride-2 3x3 / 1x1 layers of the transition blocks on parity planes, round 5)

@@ -959,10 +959,10 @@ __global__ __launch_bounds__(256) void bn_relu_pool_bwd_apply_kernel(
 }
 
 static inline void reduce_geometry(long M, int C, int& nblk, long& rows_per_block) {
-    // <= 1024 blocks; at least `min_rows` rows per block (option bn_minrows, default 32: the small late
-    // layers are latency-bound with few blocks — 256 rows per block left layer4 with 49 blocks; measured
-    // 6.518 / 6.492 / 6.508 ms per step at 64 / 32 / 16).
-    const long min_rows = PRIMIA_OPT(bn_minrows) > 0 ? PRIMIA_OPT(bn_minrows) : 32;
+    // <= 1024 blocks; at least `min_rows` rows per block (the small late layers are latency-bound with few
+    // blocks — 256 rows per block left layer4 with 49 blocks; measured 6.518 / 6.492 / 6.508 ms per step at
+    // 64 / 32 / 16).
+    constexpr long min_rows = 32;
     long nb = (M + min_rows - 1) / min_rows;
     if (nb > kMaxPartialBlocks) nb = kMaxPartialBlocks;
     if (nb < 1) nb = 1;
@@ -1011,8 +1011,7 @@ static int bn_bwd_impl(const void* y, const void* z, const void* dz, void* dy, v
     colreduce2_kernel<T, BwdFn<T>><<<nblk, 256, 0, st>>>(f, M, C, rpb, partials);
     bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partials, nblk, C, M, 1, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr);
     const long nchunks = M * C / Chunk<T>::N;
-    const int unroll = PRIMIA_OPT(bn_unroll);
-    if (unroll == 2 && nchunks >= 4L * 2048 * 256)
+    if (nchunks >= 4L * 2048 * 256)     // two chunks per thread and trip on the large tensors
         bn_bwd_apply_kernel<T, 2><<<stream_blocks(nchunks), 256, 0, st>>>(
             (const T*)y, relu ? (const T*)z : nullptr, (const T*)dz, (T*)dy, (T*)g_out, gamma, save_mean,
             save_invstd, dbeta, dgamma, (float)(1.0 / (double)M), nchunks, C, beta, mask);
@@ -1751,7 +1750,7 @@ int primia_bn_relu_bwd_from_sums(const void* y, const void* dz, void* dy, const 
                                                                            inv_m, nchunks, C, beta, nullptr);
     } else if (dtype == PRIMIA_BF16) {
         const long nchunks = M * C / 8;
-        if (PRIMIA_OPT(bn_unroll) == 2 && nchunks >= 4L * 2048 * 256)
+        if (nchunks >= 4L * 2048 * 256)
             bn_bwd_apply_kernel<bf16, 2><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, nullptr, (const bf16*)dz, (bf16*)dy,
                                                                                  nullptr, gamma, save_mean, save_invstd, dbeta,
                                                                                  dgamma, inv_m, nchunks, C, beta, nullptr);
@@ -1782,7 +1781,7 @@ int primia_bn_bwd_mask_from_sums(const void* y, const uint8_t* relu_mask, const 
                                                                            dgamma, inv_m, nchunks, C, nullptr, relu_mask);
     } else if (dtype == PRIMIA_BF16) {
         const long nchunks = M * C / 8;
-        if (PRIMIA_OPT(bn_unroll) == 2 && nchunks >= 4L * 2048 * 256)
+        if (nchunks >= 4L * 2048 * 256)
             bn_bwd_apply_kernel<bf16, 2><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, nullptr, (const bf16*)dz, (bf16*)dy,
                                                                                  (bf16*)g_out, gamma, save_mean, save_invstd, dbeta,
                                                                                  dgamma, inv_m, nchunks, C, nullptr, relu_mask);

@@ -41,7 +41,7 @@ struct IgemmParams {
     float* stat_sums;  // optional [slots][2][Nd]: per-channel sum and sum of squares of the stored output
     int stat_tiles;    // 1: stat_sums holds one deterministic partial per pixel tile (written); 0: kStatSlots atomic slots
     int s2_classes;    // data-gradient of a stride-2 conv: dst pixels are processed in 4 parity classes
-    int cls_inner;     // ... the class index is the fastest tile coordinate (option dgrad_cls_inner)
+    int cls_inner;     // ... the class index is the fastest tile coordinate (the host always sets 1)
     int ntm_class;     // pixel tiles per class
     // Transition block (3x3/2 conv1 beside a 1x1/2 downsample, both reading the same x): the downsample's data
     // gradient lands on the even/even pixels only, where conv1's only tap is the centre one and reads the SAME dy
@@ -134,7 +134,7 @@ __device__ __forceinline__ void conv_igemm_body(const IgemmParams& p, int bid, i
     int cls_ph = 0, cls_pw = 0;
     int slot_id = tm;
     if (DGRAD && p.s2_classes) {
-        // class-major (all tiles of class 0, then class 1, ...) or, option dgrad_cls_inner, position-major: the four classes of
+        // class-major (all tiles of class 0, then class 1, ...) or, cls_inner (what the host sets), position-major: the four classes of
         // a pixel tile are dispatched back to back, so that the dy rows they share are fetched into the XCD's L2 once
         slot_id = tm;          // unique per (pixel tile, class): the row of a BatchNorm-sums partial table
         int cls;
@@ -817,12 +817,10 @@ static int launch_igemm(const IgemmParams& p, hipStream_t st) {
     return launch_status();
 }
 
-// Tile choice.  Default 'e': 128-pixel tile, 8 waves (4 x 2), double-buffered LDS-DMA, 2 blocks/CU —
-// measured fastest on the ResNet-18 shapes (profiles/r01_conv_layers_*.txt): the kernel is bound by
-// the L2 -> LDS fill rate per CU, so waves in flight beat pipeline depth (the 3-stage variants lose
-// the second resident block).  option conv_cfg = 0..5 (a..f) selects an alternative for A/B runs:
-//   a 128 px 2x2 waves 2 stages | b 128 px 2x2 3 stages | c 256 px 4x2 2 stages | d 256 px 4x2 3 stages
-//   e 128 px 4x2 waves 2 stages | f 128 px 4x2 3 stages
+// Tile choice: 128-pixel tile, 8 waves (4 x 2), double-buffered LDS-DMA, 2 blocks/CU — measured fastest on the
+// ResNet-18 shapes (profiles/r01_conv_layers_*.txt): the kernel is bound by the L2 -> LDS fill rate per CU, so waves in
+// flight beat pipeline depth (the 3-stage variants lose the second resident block; DESIGN.md §7 lists the five
+// configurations that were retired).  The per-tile statistics and the BatchNorm-backward write-back assume this tile.
 template <typename T, bool DGRAD>
 static int dispatch_igemm(const IgemmParams& p, bool stem, hipStream_t st) {
     if (stem) {
@@ -830,26 +828,8 @@ static int dispatch_igemm(const IgemmParams& p, bool stem, hipStream_t st) {
         return launch_igemm<T, 128, 64, 2, 2, 2, false, true>(p, st);
     }
     if ((long)p.Nb * p.Hs * p.Ws * p.Cs >= (1L << 31)) return PRIMIA_ERR_ARG;  // 32-bit element offsets
-    const char cfg_env = (char)('a' + PRIMIA_OPT(conv_cfg));      // option conv_cfg 0..5 = a..f
-    const char cfg = (p.stat_tiles || p.bnb_y) ? 'e' : cfg_env;   // per-tile statistics assume the 128-pixel tile
-    const bool wide = p.Nd % 128 == 0;
-#define PRIMIA_IGEMM_CASE(L, BM, WM_, WN_, ST)                                                   \
-    case L:                                                                                      \
-        return wide ? launch_igemm<T, BM, 128, WM_, WN_, ST, DGRAD, false>(p, st)                \
-                    : launch_igemm<T, BM, 64, WM_, WN_, ST, DGRAD, false>(p, st);
-    switch (cfg) {
-        PRIMIA_IGEMM_CASE('a', 128, 2, 2, 2)
-        PRIMIA_IGEMM_CASE('b', 128, 2, 2, 3)
-        PRIMIA_IGEMM_CASE('c', 256, 4, 2, 2)
-        PRIMIA_IGEMM_CASE('d', 256, 4, 2, 3)
-        PRIMIA_IGEMM_CASE('e', 128, 4, 2, 2)
-        PRIMIA_IGEMM_CASE('f', 128, 4, 2, 3)
-        default:
-            break;
-    }
-#undef PRIMIA_IGEMM_CASE
-    return wide ? launch_igemm<T, 128, 128, 4, 2, 2, DGRAD, false>(p, st)
-                : launch_igemm<T, 128, 64, 4, 2, 2, DGRAD, false>(p, st);
+    return p.Nd % 128 == 0 ? launch_igemm<T, 128, 128, 4, 2, 2, DGRAD, false>(p, st)
+                           : launch_igemm<T, 128, 64, 4, 2, 2, DGRAD, false>(p, st);
 }
 
 }  // namespace primia
@@ -864,27 +844,25 @@ int conv3x3_c64_grid(int N, int H, int W);
 }
 
 // wide 3x3 / stride-1 layers (layer2-4): linear-halo kernel (conv3x3_lh2.hip); option lh2 = 0 keeps the implicit GEMM
-static int lh_fwd_maxw() {   // forward only: widest image the linear-halo kernel takes (option lh_fwd_maxw)
-    return PRIMIA_OPT(lh_fwd_maxw);
-}
+constexpr int kLhFwdMaxW = 30;   // forward only: widest image the linear-halo kernel takes
 static bool lh_shape(const ConvGeom& g) {
     return !g.stem && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1;
 }
 
-// layer1 shape (3x3, stride 1, pad 1, 64 -> 64 channels, bf16): weight-stationary halo kernel (conv3x3_c64.hip);
-// option c64 = 0 keeps the implicit GEMM (A/B measurements)
+// layer1 shape (3x3, stride 1, pad 1, 64 -> 64 channels, bf16): weight-stationary halo kernel (conv3x3_c64.hip)
 static bool use_c64(const ConvGeom& g) {
-    return PRIMIA_OPT(c64) && !g.stem && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.C == 64 && g.K == 64;
+    return !g.stem && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.C == 64 && g.K == 64;
 }
 
 // transition-block shapes served by conv_s2lh_kernel (bf16): 3x3 / 2 / pad 1 or 1x1 / 2 / pad 0 on an even-sized input
-// option s2lh (bits): 1 data gradient where it wins in the training step (dx with <= s2lh_dx_max = 64 channels: layer2.0 —
+// option s2lh (bits): 1 data gradient where it wins in the training step (dx with <= kS2DxMax = 64 channels: layer2.0 —
 // in-step medians at batch 256: 100 / 74 / 69 us on the implicit GEMM, 84 / 70 / 72 on conv_s2lh_kernel), 2 forward too
 // (74 / 58 / 47 vs 85 / 85 / 95 us: off by default), 4 data gradient at every width.  Default 1.
+constexpr int kS2DxMax = 64;
 static bool s2_pass_on(int pass, int dx_channels = 0) {
     const int o = PRIMIA_OPT(s2lh);
     if (pass == 0) return (o & 2) != 0;
-    return (o & 4) != 0 || ((o & 1) != 0 && dx_channels <= PRIMIA_OPT(s2lh_dx_max));
+    return (o & 4) != 0 || ((o & 1) != 0 && dx_channels <= kS2DxMax);
 }
 static bool s2_conv1_shape(const ConvGeom& g) {
     return !g.stem && g.R == 3 && g.S == 3 && g.stride == 2 && g.pad == 1 && conv_s2lh_ok(g.N, g.H, g.W, g.C, g.K);
@@ -924,7 +902,7 @@ static int conv2d_fwd_impl(const primia_conv_desc* d, const void* x, const void*
             const int rc = conv3x3_c64_dispatch((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, g.N, g.H, g.W, 0, 0, st,
                                                 stat_sums);
             if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
-        } else if (lh_shape(g) && g.W <= lh_fwd_maxw()) {   // (statistics: per-block partials as well)
+        } else if (lh_shape(g) && g.W <= kLhFwdMaxW) {   // (statistics: per-block partials as well)
             const int rc2 = conv3x3_lh2_dispatch((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, g.N, g.H, g.W, g.C, g.K, 0,
                                                  0, st, stat_sums);
             if (rc2 != PRIMIA_ERR_UNSUPPORTED) return rc2;
@@ -951,7 +929,7 @@ int primia_conv2d_fwd(const primia_conv_desc* d, const void* x, const void* w_fw
 // a transition block's conv1 (3x3 / 2) and downsample (1x1 / 2) forward in one launch: both on the bf16 implicit GEMM,
 // same input, output channels a multiple of 128
 static bool fwd_pair_shape(const ConvGeom& g, const ConvGeom& gd, int dtype) {
-    if (!PRIMIA_OPT(fwd_pair) || dtype != PRIMIA_BF16 || g.stem || gd.stem) return false;
+    if (dtype != PRIMIA_BF16 || g.stem || gd.stem) return false;
     if (gd.N != g.N || gd.H != g.H || gd.W != g.W || gd.C != g.C || gd.Ho != g.Ho || gd.Wo != g.Wo) return false;
     if (g.stride != 2 || gd.stride != 2 || g.R != 3 || g.S != 3 || gd.R != 1 || gd.S != 1 || gd.pad != 0) return false;
     if (g.K % 128 || gd.K % 128) return false;
@@ -1005,7 +983,7 @@ int primia_conv_kernel_id(const primia_conv_desc* d, int pass, int dtype) {
     if (dtype != PRIMIA_BF16) return 1;
     if (g.stem) return 1;     // (the engine's bf16 stem runs primia_stem_conv_fwd on the padded input: stem_conv_fwd_kernel)
     if (use_c64(g) && (long)g.N * g.H * g.W * 64 < (1L << 31)) return 2;
-    if (lh_shape(g) && (pass == 1 || g.W <= lh_fwd_maxw())) {
+    if (lh_shape(g) && (pass == 1 || g.W <= kLhFwdMaxW)) {
         const int cs = pass == 0 ? g.C : g.K, nd = pass == 0 ? g.K : g.C;
         const int lk = conv3x3_lh_kernel_of(g.N, g.H, g.W, cs, nd);
         if (lk) return lk;
@@ -1024,7 +1002,7 @@ static int conv_stat_slots_impl(const primia_conv_desc* d, int dtype, int* per_t
     if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
     *per_tile = 1;
     if (dtype == PRIMIA_BF16 && use_c64(g) && (long)g.N * g.H * g.W * 64 < (1L << 31)) return conv3x3_c64_grid(g.N, g.H, g.W);
-    if (dtype == PRIMIA_BF16 && !use_c64(g) && lh_shape(g) && g.W <= lh_fwd_maxw()) {
+    if (dtype == PRIMIA_BF16 && !use_c64(g) && lh_shape(g) && g.W <= kLhFwdMaxW) {
         const int t2 = conv3x3_lh2_tiles_m(g.N, g.H, g.W, g.C, g.K);
         if (t2 > 0) return t2;
     }
@@ -1074,9 +1052,8 @@ static int conv2d_dgrad_impl(const primia_conv_desc* d, const void* dy, const vo
     p.stat_sums = nullptr;
     p.stat_tiles = 0;
     p.bnb_y = nullptr; p.bnb_mask = nullptr; p.bnb_mean = nullptr; p.bnb_invstd = nullptr;
-    const bool no_classes = !PRIMIA_OPT(dgrad_classes);
-    p.s2_classes = (g.stride == 2 && g.H % 2 == 0 && g.W % 2 == 0 && !no_classes) ? 1 : 0;
-    p.cls_inner = PRIMIA_OPT(dgrad_cls_inner) ? 1 : 0;
+    p.s2_classes = (g.stride == 2 && g.H % 2 == 0 && g.W % 2 == 0) ? 1 : 0;
+    p.cls_inner = 1;
     p.ntm_class = 0;
     if (p.src2 && !p.s2_classes) return PRIMIA_ERR_UNSUPPORTED;   // the pairing lives in the parity-class walk
     hipStream_t st = (hipStream_t)stream;
@@ -1119,7 +1096,7 @@ int primia_conv_dgrad_bnsums_slots(const primia_conv_desc* d, int dtype) {
     ConvGeom g;
     if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
     if (dtype != PRIMIA_BF16 || !lh_shape(g)) return 0;
-    if (use_c64(g)) return (PRIMIA_OPT(c64_bnsums) && (long)g.N * g.H * g.W * 64 < (1L << 31)) ? conv3x3_c64_grid(g.N, g.H, g.W) : 0;
+    if (use_c64(g)) return (long)g.N * g.H * g.W * 64 < (1L << 31) ? conv3x3_c64_grid(g.N, g.H, g.W) : 0;
     const int t = conv3x3_lh2_tiles_m(g.N, g.H, g.W, g.K, g.C);
     return t > 0 ? t : 0;
 }
@@ -1169,7 +1146,7 @@ int primia_conv_dgrad_masked_acc_bnsums_slots(const primia_conv_desc* d, int dty
     ConvGeom g;
     if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
     if (dtype != PRIMIA_BF16 || !use_c64(g) || (long)g.N * g.H * g.W * 64 >= (1L << 31)) return 0;
-    return PRIMIA_OPT(c64_bnsums) ? conv3x3_c64_grid(g.N, g.H, g.W) : 0;
+    return conv3x3_c64_grid(g.N, g.H, g.W);
 }
 
 int primia_conv2d_dgrad_masked_acc_bnsums(const primia_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
@@ -1192,7 +1169,7 @@ int primia_conv_dgrad_pair_bnsums_slots(const primia_conv_desc* d, int dtype) {
     if (dtype != PRIMIA_BF16 || !s2_conv1_shape(g)) return 0;
     if (s2_pass_on(1, g.C)) return g.C == 64 ? 2 * conv_s2lh_tiles_m(g.N, g.H, g.W) : 0;
     // conv_igemm_kernel's parity-class walk: one partial per (128-pixel tile, class)
-    if (!PRIMIA_OPT(dgrad_classes) || g.C % 8) return 0;
+    if (g.C % 8) return 0;
     return 4 * ceil_div((long)g.N * (g.H / 2) * (g.W / 2), 128);
 }
 

@@ -713,9 +713,7 @@ static int s2_launch(S2Params& p, hipStream_t st) {
     p.magicHo = (unsigned)(((1ULL << 32) + p.Ho - 1) / p.Ho);
     const int ncu = s2_num_cus();
     // a block needs at least one tile; with fewer row groups than CUs the cost split still spreads the columns
-    int grid = p.ntiles < ncu ? p.ntiles : ncu;
-    const int opt = PRIMIA_OPT(s2lh_blocks);
-    if (opt > 0 && opt < grid) grid = opt;
+    const int grid = p.ntiles < ncu ? p.ntiles : ncu;
     static bool attr_set = false;
     if (!attr_set) {
         if (hipFuncSetAttribute((const void*)conv_s2lh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kS2Lds) != hipSuccess)

@@ -18,11 +18,9 @@
 
 namespace primia {
 
-// option wgrad_kernel: 0 = by shape, else the per-tap kernel named: 'o' register-staged, 'd' LDS-DMA, 't' either by shape
-static inline char wgrad_force() {
-    const int v = PRIMIA_OPT(wgrad_kernel);
-    return v == 1 ? 'o' : v == 2 ? 'd' : v == 3 ? 't' : 0;
-}
+// of the two per-tap kernels (for the shapes the patch and tap kernels refuse): the LDS-DMA one on the wide, few-pixel
+// layers (layer3/4), the register-staged one elsewhere
+static inline bool wgrad_dma_shape(const ConvGeom& g) { return g.C >= 256 || (g.K >= 256 && g.C >= 128); }
 
 
 template <typename T, int BMK, int BNC, bool STEM>
@@ -361,7 +359,7 @@ static void wgrad_geometry(WgradParams& p) {
     p.nct = STEM ? 1 : p.C / BNC;
     const int combos = p.ntaps * p.nkt * p.nct;
     // enough blocks to fill 256 CUs a few times over, but at least 8 steps per block
-    const int target_blocks = PRIMIA_OPT(wgt_blocks) > 0 ? PRIMIA_OPT(wgt_blocks) : 4 * 256;
+    constexpr int target_blocks = 4 * 256;
     long want = (target_blocks + combos - 1) / combos;
     long max_split = (p.Md + 8 * KP - 1) / (8 * KP);
     if (want > max_split) want = max_split;
@@ -495,16 +493,12 @@ extern "C" int64_t primia_conv_wgrad_ws_bytes(const primia_conv_desc* d, int dty
         return (int64_t)wgrad_ws_need<float, 64, 64, false>(p);
     }
     if (dtype != PRIMIA_BF16) return PRIMIA_ERR_ARG;
-    const char force = wgrad_force();
-    const bool dma = force == 'd' || (force != 'o' && (g.C >= 256 || (g.K >= 256 && g.C >= 128)));
-    if (!force && !g.stem) {
-        const size_t n = wgrad_patch_ws_bytes(p);
-        if (n > 0) return (int64_t)n;
-        const size_t nt = wgrad_tap_ws_bytes(p);
-        if (nt > 0) return (int64_t)nt;
-    }
-    if (!g.stem && dma) return (int64_t)wgrad_dma_ws_bytes(p);
     if (g.stem) return (int64_t)wgrad_ws_need<bf16, 64, 32, true>(p);
+    const size_t n = wgrad_patch_ws_bytes(p);
+    if (n > 0) return (int64_t)n;
+    const size_t nt = wgrad_tap_ws_bytes(p);
+    if (nt > 0) return (int64_t)nt;
+    if (wgrad_dma_shape(g)) return (int64_t)wgrad_dma_ws_bytes(p);
     if (g.K % 128 == 0 && g.C % 128 == 0) return (int64_t)wgrad_ws_need<bf16, 128, 128, false>(p);
     return (int64_t)wgrad_ws_need<bf16, 64, 64, false>(p);
 }
@@ -518,7 +512,7 @@ extern "C" int64_t primia_conv_wgrad_pair_ws_bytes(const primia_conv_desc* d, co
     WgradParams p, p2;
     ConvGeom g, g2;
     if (!fill_wgrad_params(d, p, g) || !fill_wgrad_params(d2, p2, g2)) return PRIMIA_ERR_ARG;
-    if (dtype != PRIMIA_BF16 || wgrad_force()) return 0;
+    if (dtype != PRIMIA_BF16) return 0;
     return (int64_t)wgrad_tap_pair_ws_bytes(p, p2);
 }
 
@@ -529,7 +523,7 @@ extern "C" int primia_conv2d_wgrad_pair_ws(const primia_conv_desc* d, const void
     WgradParams p, p2;
     ConvGeom g, g2;
     PRIMIA_REQUIRE(fill_wgrad_params(d, p, g) && fill_wgrad_params(d2, p2, g2));
-    if (dtype != PRIMIA_BF16 || wgrad_force()) return PRIMIA_ERR_UNSUPPORTED;
+    if (dtype != PRIMIA_BF16) return PRIMIA_ERR_UNSUPPORTED;
     p.x = x; p.dy = dy; p.dw = dw; p.ws = (float*)ws; p.ws_bytes = ws && ws_bytes > 0 ? (size_t)ws_bytes : 0;
     p2.x = x; p2.dy = dy2; p2.dw = dw2;
     return wgrad_tap_pair_dispatch(p, p2, (hipStream_t)stream);
@@ -541,8 +535,7 @@ extern "C" int primia_conv_wgrad_group_size(const primia_conv_desc* d, int count
     ConvGeom g;
     WgradParams p;
     if (!d || count < 1 || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
-    const char force = wgrad_force();
-    if (dtype != PRIMIA_BF16 || g.stem || force) return 0;
+    if (dtype != PRIMIA_BF16 || g.stem) return 0;
     p.persample = 0;
     return wgrad_patch_group_size(p, count);
 }
@@ -608,8 +601,7 @@ extern "C" int64_t primia_conv_wgrad_persample_slab_bytes(const primia_conv_desc
     ConvGeom g;
     WgradParams p;
     if (!d || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
-    const char force = wgrad_force();
-    if (dtype != PRIMIA_BF16 || g.stem || force) return 0;
+    if (dtype != PRIMIA_BF16 || g.stem) return 0;
     p.persample = 1;
     return (int64_t)wgrad_patch_keep_bytes(p);
 }
@@ -672,15 +664,11 @@ extern "C" int primia_conv_wgrad_persample_kernel_id(const primia_conv_desc* d, 
     if (dtype != PRIMIA_BF16) return 14;
     const int gh = dp_ghost_kernel_id(d->H, d->W, d->C, d->K, d->R, d->S, d->stride, d->pad);
     if (gh) return gh;
-    const char force = wgrad_force();
-    if (!force) {
-        const int id = wgrad_patch_persample_kernel_id(p);
-        if (id) return id;
-        const int idt = wgrad_tap_persample_kernel_id(p);
-        if (idt) return idt;
-    }
-    const bool dma = force == 'd' || (force != 'o' && (g.C >= 256 || (g.K >= 256 && g.C >= 128)));
-    return dma ? 13 : 14;
+    const int id = wgrad_patch_persample_kernel_id(p);
+    if (id) return id;
+    const int idt = wgrad_tap_persample_kernel_id(p);
+    if (idt) return idt;
+    return wgrad_dma_shape(g) ? 13 : 14;
 }
 
 extern "C" int primia_conv_wgrad_kernel_id(const primia_conv_desc* d, int dtype) {
@@ -689,15 +677,11 @@ extern "C" int primia_conv_wgrad_kernel_id(const primia_conv_desc* d, int dtype)
     if (!d || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
     if (g.stem) return 15;
     if (dtype != PRIMIA_BF16) return 14;
-    const char force = wgrad_force();
-    if (!force) {
-        const int id = wgrad_patch_kernel_id(p);
-        if (id) return id;
-        const int idt = wgrad_tap_kernel_id(p);
-        if (idt) return idt;
-    }
-    const bool dma = force == 'd' || (force != 'o' && (g.C >= 256 || (g.K >= 256 && g.C >= 128)));
-    return dma ? 13 : 14;
+    const int id = wgrad_patch_kernel_id(p);
+    if (id) return id;
+    const int idt = wgrad_tap_kernel_id(p);
+    if (idt) return idt;
+    return wgrad_dma_shape(g) ? 13 : 14;
 }
 
 static int conv2d_wgrad_impl(const primia_conv_desc* d, const void* x, const void* dy, float* dw_acc, int persample,
@@ -718,20 +702,15 @@ static int conv2d_wgrad_impl(const primia_conv_desc* d, const void* x, const voi
     } else if (dtype == PRIMIA_BF16) {
         // Measured per layer (profiles/r01_conv_layers_*): the halo-patch kernel (conv_wgrad_patch.hip) wins
         // on every 3x3 / stride-1 layer; of the per-tap kernels the LDS-DMA one wins on the wide, few-pixel
-        // layers (layer3/4) and the register-staged one elsewhere.  option wgrad_kernel = 1 (old) | 2 (dma) | 3 (tap) forces one
-        // (tap = per-tap kernels with the default old/dma choice).
-        const char force = wgrad_force();
-        const bool dma = force == 'd' || (force != 'o' && (g.C >= 256 || (g.K >= 256 && g.C >= 128)));
-        if (!force && !g.stem) {
-            const int rc = wgrad_patch_dispatch(p, st);
-            if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
-            const int rt = wgrad_tap_dispatch(p, st);     // stride-2 / 1x1 layers with a workspace
-            if (rt != PRIMIA_ERR_UNSUPPORTED) return rt;
-            const int rp = wgrad_tap_persample_dispatch(p, st);   // ... and their DP-SGD norm pass
-            if (rp != PRIMIA_ERR_UNSUPPORTED) return rp;
-        }
-        if (!g.stem && dma) return wgrad_dma_dispatch(p, st);
+        // layers (layer3/4) and the register-staged one elsewhere.
         if (g.stem) return launch_wgrad<bf16, 64, 32, true>(p, st);
+        const int rc = wgrad_patch_dispatch(p, st);
+        if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
+        const int rt = wgrad_tap_dispatch(p, st);     // stride-2 / 1x1 layers with a workspace
+        if (rt != PRIMIA_ERR_UNSUPPORTED) return rt;
+        const int rp = wgrad_tap_persample_dispatch(p, st);   // ... and their DP-SGD norm pass
+        if (rp != PRIMIA_ERR_UNSUPPORTED) return rp;
+        if (wgrad_dma_shape(g)) return wgrad_dma_dispatch(p, st);
         if (g.K % 128 == 0 && g.C % 128 == 0) return launch_wgrad<bf16, 128, 128, false>(p, st);
         return launch_wgrad<bf16, 64, 64, false>(p, st);
     }
@@ -932,7 +911,7 @@ static bool wgrad_dma_geometry(WgradParams& p) {
     const int combos = p.ntaps * p.nkt * p.nct;
     // Blocks of one launch: ONE round at two resident blocks per CU.  Every block ends with a BMK x BNC fp32 flush, so
     // fewer, longer blocks halve that traffic too (1024 -> 504: layer3.0.conv1 100 -> 84 us, layer4.0.conv1 97 -> 83).
-    const int target_blocks = PRIMIA_OPT(wg_blocks) > 0 ? PRIMIA_OPT(wg_blocks) : 504;
+    constexpr int target_blocks = 504;
     long want = (target_blocks + combos - 1) / combos;
     long max_split = (p.Md + 8 * KP - 1) / (8 * KP);
     if (want > max_split) want = max_split;

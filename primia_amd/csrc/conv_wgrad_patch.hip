@@ -669,7 +669,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_patch33_kernel(PatchParams p) 
     patch33_body<SW, SH, STAGES>(p, xcd_remap(blockIdx.x, gridDim.x));
 }
 
-// the loader-wave form (option wgp_lw; the batched gradient only)
+// the loader-wave form (the batched gradient only)
 template <int SW, int SH, int STAGES>
 __global__ __launch_bounds__(512) void conv_wgrad_patch33lw_kernel(PatchParams p) {
     patch33_body<SW, SH, STAGES, true>(p, xcd_remap(blockIdx.x, gridDim.x));
@@ -683,7 +683,7 @@ struct PatchGeom {
 
 // DP-SGD norm pass with whole images per half: needs at least two images per block for every slab
 static bool pairimg_mode(const WgradParams& w, const PatchGeom& g) {
-    return w.persample && w.sqnorm && PRIMIA_OPT(wgp_pairimg) && w.N >= 2 && (long)g.combos * ((w.N + 1) / 2) >= 256;   // (else: one block per image, as before)
+    return w.persample && w.sqnorm && w.N >= 2 && (long)g.combos * ((w.N + 1) / 2) >= 256;   // (else: one block per image, as before)
 }
 // ngroup > 1: geometry of ONE layer of a grouped launch (the layers share the 256 CUs)
 static PatchGeom patch_geom(const WgradParams& w, int ngroup = 1) {
@@ -700,18 +700,13 @@ static PatchGeom patch_geom(const WgradParams& w, int ngroup = 1) {
         // +14 %) 75 | 83 (16 x 2) — a stage of 64 pixels per half with one barrier beats 32 pixels without padding
         // (7-row bands of 16-column strips for H = 28 / 14 were measured: no gain, 9 spilled registers — not kept)
         static const int cand[3][2] = {{8, 8}, {8, 4}, {16, 2}};
-        const int force = PRIMIA_OPT(wgp_shape);       // 0 .. 2, -1: by image size
         long slots[3], best = -1;
         for (int i = 0; i < 3; ++i) {
             slots[i] = (long)((w.W + cand[i][0] - 1) / cand[i][0] * cand[i][0]) * ((w.H + cand[i][1] - 1) / cand[i][1] * cand[i][1]);
             if (best < 0 || slots[i] < best) best = slots[i];
         }
         int pick = 0;
-        if (force >= 0 && force < 3) {
-            pick = force;
-        } else if (slots[0] * 100 > best * 135) {
-            pick = slots[1] <= slots[2] ? 1 : 2;
-        }
+        if (slots[0] * 100 > best * 135) pick = slots[1] <= slots[2] ? 1 : 2;
         SW = cand[pick][0]; SH = cand[pick][1];
         g.wide = SW == 16;
     }
@@ -720,8 +715,7 @@ static PatchGeom patch_geom(const WgradParams& w, int ngroup = 1) {
     g.total = w.N * g.PPI;
     g.combos = (w.C / 64) * (w.K / 64);
     // one 8-wave block per CU
-    const int target_blocks = PRIMIA_OPT(wgp_blocks);
-    const int target = target_blocks ? target_blocks : 256;
+    constexpr int target = 256;
     long want = (target + g.combos - 1) / g.combos;
     if (ngroup > 1) want = target / ((long)ngroup * g.combos);      // all layers' blocks in ONE round
     if (want < 1) want = 1;
@@ -756,7 +750,7 @@ static void fill_patch_params(PatchParams& p, const WgradParams& w, const PatchG
     p.total = g.total;
     p.per_block = g.per_block;
     p.nsplit = g.nsplit;
-    p.split_fastest = PRIMIA_OPT(wgp_order);
+    p.split_fastest = 0;      // block id order: slab fastest (the slabs of a pixel range share x, dy in one L2)
     p.split_stride = w.persample ? (long)w.K * w.klen : 0;
     p.sqnorm = w.persample ? w.sqnorm : nullptr;
     const bool store = !w.persample && w.ws && w.ws_bytes >= (size_t)g.combos * g.nsplit * kSlab * sizeof(float);
@@ -767,16 +761,15 @@ static void fill_patch_params(PatchParams& p, const WgradParams& w, const PatchG
     p.group_blocks = 0;
 }
 
-template <int SW, int SH, int STAGES = 3>
+template <int SW, int SH>
 static int launch_patch33(const WgradParams& w, const PatchGeom& g, hipStream_t st) {
     PatchParams p;
     fill_patch_params(p, w, g);
-    // the stage ring (at most 144 KiB; 160 KiB for four 8 x 8 stages), or the 144 KiB the two halves need to meet in
-    // after the main loop
-    size_t lds = (size_t)kSlab * 4;
-    if (SW == 8 && SH == 8 && STAGES == 4) lds = 163840;
-    const bool lw = PRIMIA_OPT(wgp_lw) && !p.pairimg && !p.sqnorm;
-    void (*kern)(PatchParams) = lw ? conv_wgrad_patch33lw_kernel<SW, SH, STAGES> : conv_wgrad_patch33_kernel<SW, SH, STAGES>;
+    // the three-stage ring (at most 144 KiB), or the 144 KiB the two halves need to meet in after the main loop
+    const size_t lds = (size_t)kSlab * 4;
+    // the batched gradient: four matrix waves (one per SIMD) + four loader waves; the DP-SGD norm passes: the two halves
+    const bool lw = !p.pairimg && !p.sqnorm;
+    void (*kern)(PatchParams) = lw ? conv_wgrad_patch33lw_kernel<SW, SH, 3> : conv_wgrad_patch33_kernel<SW, SH, 3>;
     static bool attr_set[2] = {false, false};
     if (!attr_set[lw]) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -796,7 +789,7 @@ static int launch_patch33(const WgradParams& w, const PatchGeom& g, hipStream_t 
     return launch_status();
 }
 
-// ---- grouped launch: up to four layers of ONE shape in one launch of conv_wgrad_patch33_kernel<8, 8> -------------------
+// ---- grouped launch: up to four layers of ONE shape in one launch of conv_wgrad_patch33lw_kernel<8, 8> -----------------
 // A call of this kernel carries ~25-29 us that do not shrink with the work (launch, lane constants, first DMA round trip,
 // the halves' meeting + slab store, the reduce launch: profiles/r03_wgp33_phase_profile.txt) next to 45-55 us of main
 // loop; with n layers the blocks split n ways — each block walks n times as many sub-patches behind ONE such cost, and
@@ -805,14 +798,13 @@ static int launch_patch33(const WgradParams& w, const PatchGeom& g, hipStream_t 
 // Preferred group size for `count` layers of this shape: the largest n <= min(count, 4) whose blocks fill >= 90 % of the
 // CUs in one round (0: shape not served).
 int wgrad_patch_group_size(const WgradParams& w, int count) {
-    if (!PRIMIA_OPT(wgp_group) || w.persample) return 0;
+    if (w.persample) return 0;
     const PatchGeom g1 = patch_geom(w);
     if (!g1.ok || g1.SW != 8 || g1.SH != 8) return 0;
     for (int n = count < 4 ? count : 4; n >= 2; --n) {
         const PatchGeom g = patch_geom(w, n);
         const long blocks = (long)n * g.combos * g.nsplit;
-        const int minfill = PRIMIA_OPT(wgp_group_minfill);
-        if (blocks <= 256 && blocks * 100 >= 256 * minfill) return n;
+        if (blocks <= 256 && blocks * 100 >= 256 * 90) return n;
     }
     return 1;
 }
@@ -849,13 +841,12 @@ int wgrad_patch_group_dispatch(const WgradParams* ws_, int n, hipStream_t st) {
         rg.dwg[i - 1] = ws_[i].dw;
     }
     const size_t lds = (size_t)kSlab * 4;
-    const bool lw = PRIMIA_OPT(wgp_lw) != 0;
-    void (*kern)(PatchParams) = lw ? conv_wgrad_patch33lw_kernel<8, 8, 3> : conv_wgrad_patch33_kernel<8, 8, 3>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[lw]) {
+    void (*kern)(PatchParams) = conv_wgrad_patch33lw_kernel<8, 8, 3>;
+    static bool attr_set = false;
+    if (!attr_set) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return PRIMIA_ERR_LAUNCH;
-        attr_set[lw] = true;
+        attr_set = true;
     }
     kern<<<(unsigned)(n * p.group_blocks), 512, lds, st>>>(p);
     const int ns = g.nsplit, all = n * g.combos;
@@ -870,7 +861,7 @@ int wgrad_patch_group_dispatch(const WgradParams* ws_, int n, hipStream_t st) {
 
 // ---- DP-SGD: norm pass that KEEPS every sample's tiles, clipped sum as a weighted reduce (see conv_wgrad.hip) ----------
 size_t wgrad_patch_keep_bytes(const WgradParams& w) {
-    const long budget = (long)PRIMIA_OPT(dp_keep_mb) << 20;   // (layer1: 38 MB per layer, layer2: 151; layer3 would be 604 MB written and read back: a loss)
+    constexpr long budget = 160L << 20;   // per-sample tiles of a layer are kept up to 160 MiB (layer1: 38 MB per layer, layer2: 151; layer3 would be 604 MB written and read back: a loss)
     WgradParams q = w;
     q.persample = 1;
     double dummy;
@@ -909,11 +900,9 @@ int wgrad_patch_clipped_sum(const WgradParams& w, const float* slabs, const floa
     return launch_status();
 }
 
-// 16 = conv_wgrad_patch33_kernel, 18 = conv_wgrad_patch33lw_kernel, 11 = conv_wgrad_patch32_kernel, 12 = conv_wgrad_patch_kernel (round 1), 0 = shape not served
-int wgrad_patch_kernel_id(const WgradParams& w) {
-    if (!patch_geom(w).ok) return 0;
-    return PRIMIA_OPT(wgp_lw) ? 18 : 16;       // 18 = conv_wgrad_patch33lw_kernel (loader waves; the batched gradient)
-}
+// 18 = conv_wgrad_patch33lw_kernel (loader waves; the batched gradient), 0 = shape not served.  (16, 11 and 12 named its
+// predecessors conv_wgrad_patch33_kernel, conv_wgrad_patch32_kernel and conv_wgrad_patch_kernel: the numbers stay theirs.)
+int wgrad_patch_kernel_id(const WgradParams& w) { return patch_geom(w).ok ? 18 : 0; }
 
 // DP-SGD norm pass on this kernel: 0 shape not served, 24 one block per (image, slab), 25 whole images per half-block
 int wgrad_patch_persample_kernel_id(const WgradParams& w) {
@@ -930,8 +919,6 @@ int wgrad_patch_dispatch(const WgradParams& w, hipStream_t st) {
     const PatchGeom g = patch_geom(w);
     if (!g.ok) return PRIMIA_ERR_UNSUPPORTED;
     if (g.SW == 16) return launch_patch33<16, 2>(w, g, st);
-    // (8 x 8: four stages of 40 KiB are exactly the CU's 160 KiB of LDS)
-    if (g.SH == 8 && PRIMIA_OPT(wgp_stages88) == 4) return launch_patch33<8, 8, 4>(w, g, st);
     return g.SH == 8 ? launch_patch33<8, 8>(w, g, st) : launch_patch33<8, 4>(w, g, st);
 }
 

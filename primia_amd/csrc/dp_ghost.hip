@@ -242,7 +242,7 @@ static size_t ghost7_lds_bytes(int C, int K) {
 // which Gram-matrix kernel serves the norm pass of this layer: 0 none, 21 dp_ghost_sqnorm7_kernel (7x7, stride 1),
 // 22 dp_ghost_sqnorm7s2_kernel (14x14 -> 7x7, stride 2)
 int dp_ghost_kernel_id(int H, int W, int C, int K, int R, int S, int stride, int pad) {
-    if (!PRIMIA_OPT(dp_ghost) || R != 3 || S != 3 || pad != 1 || C % 32 || K % 32 || C < 32 || K < 32) return 0;
+    if (R != 3 || S != 3 || pad != 1 || C % 32 || K % 32 || C < 32 || K < 32) return 0;
     if (H == 14 && W == 14 && stride == 2) {
         size_t a = (size_t)226 * (C * 2 + 16), b = (size_t)(kGhPix + 1) * (K * 2 + 16);
         return (a > b ? a : b) > 160 * 1024 ? 0 : 22;
