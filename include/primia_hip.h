@@ -444,6 +444,56 @@ int primia_image_add_noise_u8(const uint8_t* in, const float* noise, int64_t n, 
 int primia_image_finish(const uint8_t* in, int S, int C, const float* mean, const float* std, float* out,
                         primia_stream_t stream);
 
+/* The same chain a BATCH at a time (csrc/augment_batch.hip): one call per stage covers the n images of the batch on which
+ * the stage fired (n = 0: nothing to do).  Record j of every table belongs to the j-th such image.  `ptrs` is a DEVICE
+ * array of int64 addresses (as primia_newton_reciprocal_local's `prim`), k per record: the image's current S x S x C uint8
+ * slice and the slice the stage writes; the other tables are device arrays of the stage's parameters.  The host uploads all
+ * tables of a batch in one copy (primia_amd/augment.py TrainTransform.batch).  Every stage computes, per image, bit for bit
+ * what the per-image call it replaces computes (shared arithmetic: csrc/augment_px.h).  src != dst unless stated.
+ *   primia_image_affine_resize_crop_batch_u8  primia_image_affine_u8 + primia_image_resize_crop_u8 (flip_v = 0) without the
+ *                                full-size warped image: each bilinear tap is read through the affine gather.  ptrs (src,
+ *                                dst); ip (H, W, has_affine, oy, ox): images differ in size; fp (a, b, c, d, e, f).
+ *   primia_clahe_batch_u8        primia_clahe_u8 on H x W images; ptrs (img, out), in place allowed; workspace >= n x
+ *                                primia_clahe_workspace_bytes(H, W, C).
+ *   primia_image_flip_lut_batch_u8  a.VerticalFlip (torch.flip on axis 0) and / or primia_image_lut_u8.  ptrs (src, dst); ip
+ *                                (flip, index of the image's table in luts[.][256] or -1).  RandomGamma and RandomBrightness
+ *                                of one image are one composed table; InvertImg and Solarize are tables without a flip.
+ *   primia_image_box_blur_batch_u8  primia_image_box_blur_u8 with k = ks[j] (a.Blur; RandomFog's trailing blur).  ptrs (src, dst).
+ *   primia_image_warp_batch_u8   primia_warp_map_* + primia_image_remap_u8 with the map value computed in the kernel.  ptrs
+ *                                (src, dst, aux0, aux1); kinds[j]: 0 affine (dp[j][0..5] = the inverse matrix), 1 optical
+ *                                (dp[j][0..6] = k, fx, fy, cx, cy, new_cx, new_cy), 2 grid (aux0 = xx[S], aux1 = yy[S], float32),
+ *                                3 index + displacement (aux0 = dx, aux1 = dy, float32 [S][S]: primia_warp_map_elastic's maps).
+ *   primia_warp_elastic_disp_batch  the displacements of primia_warp_map_elastic for n images: fields [n][2][H][W] float64
+ *                                (x field, y field) -> disp [n][2][H][W] float32; the Gaussian taps are evaluated once per
+ *                                call.  workspace >= primia_warp_elastic_disp_workspace_bytes(n, H, W, sigma).
+ *   primia_image_fog_batch_u8    primia_image_fog_u8.  ptrs (src, dst); ip (hw, first point, points) into haze_xy[.][2];
+ *                                alphas[j].
+ *   primia_image_fill_rects_batch_u8  primia_image_fill_rects_u8, in place.  ptrs (img); ip (first rectangle, rectangles)
+ *                                into rects[.][4].
+ *   primia_image_add_noise_batch_u8  primia_image_add_noise_u8 in place with noise = normal[j][per_image] * sigmas[j] (one
+ *                                float32 product, as torch.randn(...) * sigma).  ptrs (img).
+ *   primia_image_finish_batch    primia_image_finish.  ptrs (src uint8 [S][S][C], dst fp32 [C][S][S]). */
+int primia_image_affine_resize_crop_batch_u8(const int64_t* ptrs, const int32_t* ip, const float* fp, int n, int C, int R,
+                                             int S, primia_stream_t stream);
+int primia_clahe_batch_u8(const int64_t* ptrs, int n, int H, int W, int C, float clip_limit, void* workspace,
+                          int64_t workspace_bytes, primia_stream_t stream);
+int primia_image_flip_lut_batch_u8(const int64_t* ptrs, const int32_t* ip, const uint8_t* luts, int n, int S, int C,
+                                   primia_stream_t stream);
+int primia_image_box_blur_batch_u8(const int64_t* ptrs, const int32_t* ks, int n, int S, int C, primia_stream_t stream);
+int primia_image_warp_batch_u8(const int64_t* ptrs, const int32_t* kinds, const double* dp, int n, int S, int C,
+                               primia_stream_t stream);
+int64_t primia_warp_elastic_disp_workspace_bytes(int n, int H, int W, double sigma);
+int primia_warp_elastic_disp_batch(const double* fields, int n, int H, int W, double sigma, double alpha, void* workspace,
+                                   int64_t workspace_bytes, float* disp, primia_stream_t stream);
+int primia_image_fog_batch_u8(const int64_t* ptrs, const int32_t* ip, const float* alphas, const int32_t* haze_xy, int n, int S,
+                              int C, primia_stream_t stream);
+int primia_image_fill_rects_batch_u8(const int64_t* ptrs, const int32_t* ip, const int32_t* rects, int n, int S, int C,
+                                     int fill, primia_stream_t stream);
+int primia_image_add_noise_batch_u8(const int64_t* ptrs, const float* noise, const float* sigmas, int n, int64_t per_image,
+                                    primia_stream_t stream);
+int primia_image_finish_batch(const int64_t* ptrs, int n, int S, int C, const float* mean, const float* std,
+                              primia_stream_t stream);
+
 /* out[i] = lam * x[i] + one_minus_lam * x[L/2 + i] for i < L/2 over rows of `per_sample` floats (three
  * roundings, like the reference's expression); an odd trailing sample is copied to out[L/2].  The same call
  * mixes the one-hot targets (per_sample = classes).  out has ceil(L/2) rows. */

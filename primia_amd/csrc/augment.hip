@@ -8,8 +8,10 @@
 // cv2 / albumentations are not in this image, so these kernels follow the published algorithms (OpenCV's clahe.cpp,
 // box filter with BORDER_REFLECT_101, cv2.LUT tables as albumentations builds them) and are held bit-exact to
 // oracle/augment_oracle.py, which restates them in NumPy; parity with cv2's own binaries is unpinned.
-// Registration-time work, a few hundred kilobytes per image: nowhere near a roofline, written for clarity.
-#include "common.h"
+// Written for clarity, one launch per stage per image: a single image (`tf(img, rng)`) goes through these.  The
+// loaders, which transform a batch every training step or a whole dataset at registration, go through
+// augment_batch.hip, whose kernels run one launch per stage per BATCH over the same per-pixel functions (augment_px.h).
+#include "augment_px.h"
 
 // every product below is rounded on its own, as the NumPy / OpenCV float arithmetic these kernels follow does: no
 // fused multiply-add contraction in this file
@@ -24,10 +26,8 @@ __global__ __launch_bounds__(256) void affine_u8_kernel(const uint8_t* __restric
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
     const int y = idx / W, x = idx - y * W;
-    const double xs = (double)a * (x + 0.5) + (double)b * (y + 0.5) + (double)c;
-    const double ys = (double)d * (x + 0.5) + (double)e * (y + 0.5) + (double)f;
-    const int xi = (int)floor(xs), yi = (int)floor(ys);
-    const bool in = xi >= 0 && xi < W && yi >= 0 && yi < H;
+    int xi, yi;
+    const bool in = affine_source(H, W, a, b, c, d, e, f, y, x, yi, xi);
     for (int ch = 0; ch < C; ++ch) out[(long)idx * C + ch] = in ? src[((long)yi * W + xi) * C + ch] : (uint8_t)0;
 }
 
@@ -39,80 +39,21 @@ __global__ __launch_bounds__(256) void resize_crop_u8_kernel(const uint8_t* __re
     if (idx >= S * S) return;
     const int y = idx / S, x = idx - y * S;
     const int ry = (flip_v ? S - 1 - y : y) + oy, rx = x + ox;
-    const float sy = ((float)ry + 0.5f) * ((float)Hin / (float)R) - 0.5f;
-    const float sx = ((float)rx + 0.5f) * ((float)Win / (float)R) - 0.5f;
-    int y0 = (int)floorf(sy), x0 = (int)floorf(sx);
-    float fy = sy - (float)y0, fx = sx - (float)x0;
-    if (y0 < 0) { y0 = 0; fy = 0.f; }
-    if (x0 < 0) { x0 = 0; fx = 0.f; }
-    int y1 = y0 + 1, x1 = x0 + 1;
-    if (y1 >= Hin) { y1 = Hin - 1; if (y0 >= Hin - 1) { y0 = Hin - 1; fy = 0.f; } }
-    if (x1 >= Win) { x1 = Win - 1; if (x0 >= Win - 1) { x0 = Win - 1; fx = 0.f; } }
+    const ResizeTaps t = resize_taps(Hin, Win, R, ry, rx);
     for (int c = 0; c < C; ++c) {
-        const float p00 = src[((long)y0 * Win + x0) * C + c], p01 = src[((long)y0 * Win + x1) * C + c];
-        const float p10 = src[((long)y1 * Win + x0) * C + c], p11 = src[((long)y1 * Win + x1) * C + c];
-        const float top = p00 + (p01 - p00) * fx, bot = p10 + (p11 - p10) * fx;
-        const float v = fminf(fmaxf(floorf(top + (bot - top) * fy + 0.5f), 0.f), 255.f);
-        out[(long)idx * C + c] = (uint8_t)v;
+        const float p00 = src[((long)t.y0 * Win + t.x0) * C + c], p01 = src[((long)t.y0 * Win + t.x1) * C + c];
+        const float p10 = src[((long)t.y1 * Win + t.x0) * C + c], p11 = src[((long)t.y1 * Win + t.x1) * C + c];
+        out[(long)idx * C + c] = resize_blend(p00, p01, p10, p11, t.fx, t.fy);
     }
 }
 
 // ---- CLAHE (OpenCV clahe.cpp), 8 x 8 tiles, on one uint8 plane with pixel stride `ps` ---------------------------
-__device__ __forceinline__ int reflect101(int p, int n) {   // BORDER_REFLECT_101: gfedcb|abcdefgh|gfedcba
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p : 2 * (n - 1) - p;
-    return p;
-}
-
 // one block per tile: histogram of the (reflect-padded) tile, clip, redistribute, cumulative LUT
 __global__ __launch_bounds__(256) void clahe_lut_kernel(const uint8_t* __restrict__ img, int H, int W, int ps, int tw,
                                                         int th, int clip, uint8_t* __restrict__ lut) {
     __shared__ int hist[256];
     __shared__ int scan[256];
-    const int tx = blockIdx.x, ty = blockIdx.y, t = threadIdx.x;
-    hist[t] = 0;
-    __syncthreads();
-    for (int i = t; i < tw * th; i += 256) {
-        const int y = reflect101(ty * th + i / tw, H), x = reflect101(tx * tw + i % tw, W);
-        atomicAdd(&hist[img[((long)y * W + x) * ps]], 1);
-    }
-    __syncthreads();
-    if (clip > 0) {
-        // clipped = sum of the excesses; every bin gets clipped / 256, the residual goes to bins 0, step, 2 step, ...
-        int v = hist[t];
-        const int ex = v > clip ? v - clip : 0;
-        scan[t] = ex;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (t < o) scan[t] += scan[t + o];
-            __syncthreads();
-        }
-        const int clipped = scan[0];
-        __syncthreads();
-        const int batch = clipped / 256;
-        int residual = clipped - batch * 256;
-        v = (v > clip ? clip : v) + batch;
-        if (residual != 0) {
-            int step = 256 / residual;
-            if (step < 1) step = 1;
-            if (t % step == 0 && t / step < residual) ++v;
-        }
-        hist[t] = v;
-        __syncthreads();
-    }
-    // inclusive prefix sum (Hillis-Steele), then lut = saturate(round_half_even(sum * 255 / tile_area))
-    scan[t] = hist[t];
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int add = t >= o ? scan[t - o] : 0;
-        __syncthreads();
-        scan[t] += add;
-        __syncthreads();
-    }
-    const float scale = 255.0f / (float)(tw * th);
-    float r = rintf((float)scan[t] * scale);
-    r = fminf(fmaxf(r, 0.f), 255.f);
-    lut[((long)(ty * gridDim.x + tx)) * 256 + t] = (uint8_t)r;
+    clahe_lut_tile(img, H, W, ps, tw, th, clip, blockIdx.x, blockIdx.y, gridDim.x, hist, scan, lut);
 }
 
 __global__ __launch_bounds__(256) void clahe_apply_kernel(const uint8_t* __restrict__ img, int H, int W, int ps, int tw,
@@ -120,55 +61,15 @@ __global__ __launch_bounds__(256) void clahe_apply_kernel(const uint8_t* __restr
                                                           uint8_t* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
-    const int y = idx / W, x = idx - y * W;
-    const float txf = (float)x * (1.0f / (float)tw) - 0.5f, tyf = (float)y * (1.0f / (float)th) - 0.5f;
-    int tx1 = (int)floorf(txf), ty1 = (int)floorf(tyf);
-    const float xa = txf - (float)tx1, ya = tyf - (float)ty1;
-    int tx2 = tx1 + 1, ty2 = ty1 + 1;
-    tx1 = tx1 < 0 ? 0 : tx1;
-    ty1 = ty1 < 0 ? 0 : ty1;
-    tx2 = tx2 > tiles - 1 ? tiles - 1 : tx2;
-    ty2 = ty2 > tiles - 1 ? tiles - 1 : ty2;
-    const int v = img[(long)idx * ps];
-    const float l11 = lut[(ty1 * tiles + tx1) * 256 + v], l12 = lut[(ty1 * tiles + tx2) * 256 + v];
-    const float l21 = lut[(ty2 * tiles + tx1) * 256 + v], l22 = lut[(ty2 * tiles + tx2) * 256 + v];
-    const float res = (l11 * (1.0f - xa) + l12 * xa) * (1.0f - ya) + (l21 * (1.0f - xa) + l22 * xa) * ya;
-    out[(long)idx * ps] = (uint8_t)fminf(fmaxf(rintf(res), 0.f), 255.f);
+    clahe_apply_px(img, W, ps, tw, th, tiles, lut, out, idx);
 }
 
 // ---- RGB <-> CIE L*a*b* (D65, sRGB transfer), 8 bit: L * 255 / 100, a + 128, b + 128 ---------------------------
-__device__ __forceinline__ float srgb_to_linear(float c) { return c <= 0.04045f ? c / 12.92f : powf((c + 0.055f) / 1.055f, 2.4f); }
-__device__ __forceinline__ float linear_to_srgb(float c) { return c <= 0.0031308f ? 12.92f * c : 1.055f * powf(c, 1.0f / 2.4f) - 0.055f; }
-__device__ __forceinline__ float lab_f(float t) { return t > 0.008856f ? cbrtf(t) : 7.787f * t + 16.0f / 116.0f; }
-__device__ __forceinline__ uint8_t sat_u8(float v) { return (uint8_t)fminf(fmaxf(rintf(v), 0.f), 255.f); }
-
 __global__ __launch_bounds__(256) void rgb_lab_kernel(const uint8_t* __restrict__ in, long n, int inverse,
                                                       uint8_t* __restrict__ out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float p0 = in[3 * i], p1 = in[3 * i + 1], p2 = in[3 * i + 2];
-    if (!inverse) {
-        const float r = srgb_to_linear(p0 / 255.f), g = srgb_to_linear(p1 / 255.f), b = srgb_to_linear(p2 / 255.f);
-        const float X = (0.412453f * r + 0.357580f * g + 0.180423f * b) / 0.950456f;
-        const float Y = 0.212671f * r + 0.715160f * g + 0.072169f * b;
-        const float Z = (0.019334f * r + 0.119193f * g + 0.950227f * b) / 1.088754f;
-        const float fx = lab_f(X), fy = lab_f(Y), fz = lab_f(Z);
-        const float L = Y > 0.008856f ? 116.f * fy - 16.f : 903.3f * Y;
-        out[3 * i] = sat_u8(L * 255.f / 100.f);
-        out[3 * i + 1] = sat_u8(500.f * (fx - fy) + 128.f);
-        out[3 * i + 2] = sat_u8(200.f * (fy - fz) + 128.f);
-    } else {
-        const float L = p0 * 100.f / 255.f, a = p1 - 128.f, b = p2 - 128.f;
-        const float fy = (L + 16.f) / 116.f, fx = fy + a / 500.f, fz = fy - b / 200.f;
-        auto inv = [](float t) { return t > 0.206893f ? t * t * t : (t - 16.f / 116.f) / 7.787f; };
-        const float X = inv(fx) * 0.950456f, Y = L > 7.9996f ? inv(fy) : L / 903.3f, Z = inv(fz) * 1.088754f;
-        const float r = 3.240479f * X - 1.537150f * Y - 0.498535f * Z;
-        const float g = -0.969256f * X + 1.875991f * Y + 0.041556f * Z;
-        const float bl = 0.055648f * X - 0.204043f * Y + 1.057311f * Z;
-        out[3 * i] = sat_u8(linear_to_srgb(fminf(fmaxf(r, 0.f), 1.f)) * 255.f);
-        out[3 * i + 1] = sat_u8(linear_to_srgb(fminf(fmaxf(g, 0.f), 1.f)) * 255.f);
-        out[3 * i + 2] = sat_u8(linear_to_srgb(fminf(fmaxf(bl, 0.f), 1.f)) * 255.f);
-    }
+    rgb_lab_px(in, inverse, out, i);
 }
 
 // ---- cv2.LUT with a 256-entry table (RandomGamma, RandomBrightness) -------------------------------------------------
@@ -183,59 +84,31 @@ __global__ __launch_bounds__(256) void box_blur_u8_kernel(const uint8_t* __restr
                                                           uint8_t* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
-    const int y = idx / W, x = idx - y * W, a = k / 2;      // window [p - k / 2, p - k / 2 + k - 1]: cv2's default anchor
-    for (int c = 0; c < C; ++c) {
-        int s = 0;
-        for (int dy = -a; dy < k - a; ++dy)
-            for (int dx = -a; dx < k - a; ++dx)
-                s += in[((long)reflect101(y + dy, H) * W + reflect101(x + dx, W)) * C + c];
-        out[(long)idx * C + c] = sat_u8((float)s / (float)(k * k));
-    }
+    box_blur_px(in, H, W, C, k, out, idx);
 }
 
 // ---- the warping transforms of albumentations 0.4.6 (ElasticTransform, OpticalDistortion, GridDistortion) ----------
 // All three are cv2.remap(img, map_x, map_y, INTER_LINEAR, BORDER_REFLECT_101) with a generated coordinate field
 // (torchlib/dataloader.py:167-172): the maps are formed on the device from the few parameters the host draws, one remap
-// kernel samples them.  Bilinear weights in fp32, result rounded to nearest even (cv2's 8-bit path uses 5-bit fixed-point
-// coordinates: unpinned, see oracle/augment_oracle.py).
+// kernel samples them (remap_px).
 __global__ __launch_bounds__(256) void remap_u8_kernel(const uint8_t* __restrict__ src, int H, int W, int C,
                                                        const float* __restrict__ mx, const float* __restrict__ my,
                                                        uint8_t* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
-    const float x = mx[idx], y = my[idx];
-    const float x0f = floorf(x), y0f = floorf(y);
-    const float fx = x - x0f, fy = y - y0f;
-    // (coordinates far outside the image — a degenerate affine draw — are clamped before the integer conversion; the
-    // reflection below is periodic, so the clamp only has to keep the value representable)
-    const int x0 = (int)fminf(fmaxf(x0f, -1.0e6f), 1.0e6f), y0 = (int)fminf(fmaxf(y0f, -1.0e6f), 1.0e6f);
-    const int xa = reflect101(x0, W), xb = reflect101(x0 + 1, W), ya = reflect101(y0, H), yb = reflect101(y0 + 1, H);
-    for (int c = 0; c < C; ++c) {
-        const float p00 = src[((long)ya * W + xa) * C + c], p01 = src[((long)ya * W + xb) * C + c];
-        const float p10 = src[((long)yb * W + xa) * C + c], p11 = src[((long)yb * W + xb) * C + c];
-        const float top = p00 * (1.f - fx) + p01 * fx, bot = p10 * (1.f - fx) + p11 * fx;
-        out[(long)idx * C + c] = sat_u8(top * (1.f - fy) + bot * fy);
-    }
+    remap_px(src, H, W, C, mx[idx], my[idx], out, idx);
 }
 
-// kind 0: affine  (p = inverse matrix a b c d e f: source = (a x + b y + c, d x + e y + f)), cv2.warpAffine
-// kind 1: optical (p = k, fx, fy, cx, cy, ncx, ncy): cv2.initUndistortRectifyMap with distortion (k, k, 0, 0, 0)
+// kind 0: affine, kind 1: optical (warp_coord)
 __global__ __launch_bounds__(256) void warp_map_kernel(int H, int W, int kind, double p0, double p1, double p2, double p3,
                                                        double p4, double p5, double p6, float* __restrict__ mx,
                                                        float* __restrict__ my) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
-    const double y = idx / W, x = idx - (idx / W) * W;
-    if (kind == 0) {
-        mx[idx] = (float)(p0 * x + p1 * y + p2);
-        my[idx] = (float)(p3 * x + p4 * y + p5);
-    } else {
-        const double u = (x - p5) / p1, v = (y - p6) / p2;
-        const double r2 = u * u + v * v;
-        const double kr = 1.0 + p0 * r2 + p0 * r2 * r2;
-        mx[idx] = (float)(p1 * (u * kr) + p3);
-        my[idx] = (float)(p2 * (v * kr) + p4);
-    }
+    float x, y;
+    warp_coord(W, kind, p0, p1, p2, p3, p4, p5, p6, idx, x, y);
+    mx[idx] = x;
+    my[idx] = y;
 }
 
 // GridDistortion: map_x, map_y = meshgrid(xx, yy)  |  ElasticTransform: map = float32(index + displacement)
@@ -244,63 +117,38 @@ __global__ __launch_bounds__(256) void grid_map_kernel(int H, int W, const float
                                                        float* __restrict__ mx, float* __restrict__ my) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
-    const int y = idx / W, x = idx - y * W;
-    mx[idx] = xx ? xx[x] : (float)x + dx[idx];
-    my[idx] = yy ? yy[y] : (float)y + dy[idx];
+    float x, y;
+    grid_coord(W, xx, yy, dx, dy, idx, x, y);
+    mx[idx] = x;
+    my[idx] = y;
 }
 
-// scipy.ndimage.gaussian_filter's 1-D pass (correlate1d, mode "reflect": d c b a | a b c d | d c b a), float64, on
-// u = 2 r - 1 of a uniform field r (first pass) or on the first pass's output; `scale`: factor applied to the result
-// (alpha after the second pass), which is stored as float32 when `out32` is given.
+// scipy.ndimage.gaussian_filter's 1-D pass (gauss1d_px); `scale`: factor applied to the result (alpha after the second
+// pass), which is stored as float32 when `out32` is given.
 __global__ __launch_bounds__(256) void gauss1d_kernel(const double* __restrict__ in, int H, int W, int axis, double sigma,
                                                       int radius, int affine_in, double scale, double* __restrict__ out,
                                                       float* __restrict__ out32) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
-    const int y = idx / W, x = idx - y * W;
-    const int n = axis == 0 ? H : W, p = axis == 0 ? y : x;
-    double wsum = 0.0;
-    for (int t = -radius; t <= radius; ++t) wsum += exp(-0.5 / (sigma * sigma) * (double)t * (double)t);
-    double acc = 0.0;
-    for (int t = -radius; t <= radius; ++t) {
-        int q = p + t;
-        const int period = 2 * n;                      // half-sample symmetric reflection
-        q %= period;
-        if (q < 0) q += period;
-        if (q >= n) q = period - 1 - q;
-        double v = in[axis == 0 ? (long)q * W + x : (long)y * W + q];
-        if (affine_in) v = v * 2.0 - 1.0;
-        acc += v * (exp(-0.5 / (sigma * sigma) * (double)t * (double)t) / wsum);
-    }
-    acc *= scale;
+    const double acc = gauss1d_px(in, H, W, axis, sigma, radius, affine_in, scale, nullptr, idx);
     if (out32) out32[idx] = (float)acc;
     else out[idx] = acc;
 }
 
-// ---- RandomFog (F.add_fog): per haze point a white disc of radius hw / 2 blended in with cv2.addWeighted(alpha) ---------
-// sequentially (a pixel covered by m discs is blended m times, in list order); the cv2.blur(hw / 10) that follows is
-// primia_image_box_blur_u8.
+// ---- RandomFog (F.add_fog): the haze discs (fog_px); the cv2.blur(hw / 10) that follows is primia_image_box_blur_u8.
 __global__ __launch_bounds__(256) void fog_u8_kernel(const uint8_t* __restrict__ in, int H, int W, int C,
                                                      const int* __restrict__ haze, int n, int hw, float alpha, float beta,
                                                      uint8_t* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
-    const int y = idx / W, x = idx - y * W, rad = hw / 2;
-    float v[3];
-    for (int c = 0; c < C; ++c) v[c] = in[(long)idx * C + c];
-    for (int i = 0; i < n; ++i) {
-        const int dx = x - (haze[2 * i] + hw / 2), dy = y - (haze[2 * i + 1] + hw / 2);
-        if (dx * dx + dy * dy <= rad * rad)
-            for (int c = 0; c < C; ++c) v[c] = fminf(fmaxf(rintf(255.f * alpha + v[c] * beta), 0.f), 255.f);
-    }
-    for (int c = 0; c < C; ++c) out[(long)idx * C + c] = (uint8_t)v[c];
+    fog_px(in, W, C, haze, n, hw, alpha, beta, out, idx);
 }
 
 // ---- GaussNoise: image + noise (fp32, given), clipped to [0, 255], cast to uint8 (truncation, as ndarray.astype) -----
 __global__ __launch_bounds__(256) void add_noise_u8_kernel(const uint8_t* __restrict__ in, const float* __restrict__ noise,
                                                            long n, uint8_t* __restrict__ out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (uint8_t)fminf(fmaxf((float)in[i] + noise[i], 0.f), 255.f);
+    if (i < n) out[i] = add_noise_px(in[i], noise[i]);
 }
 
 // ---- ToFloat(255) + Normalize(mean, std, max_pixel_value = 1): uint8 HWC -> fp32 CHW ------------------------------
@@ -309,11 +157,7 @@ __global__ __launch_bounds__(256) void finish_u8_kernel(const uint8_t* __restric
                                                         float* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= S * S) return;
-    for (int c = 0; c < C; ++c) {
-        float v = (float)in[(long)idx * C + c] / 255.0f;
-        if (mean) v = (v - mean[c]) / stdv[c];
-        out[(long)c * S * S + idx] = v;
-    }
+    finish_px(in, S, C, mean, stdv, out, idx);
 }
 
 // ---- round 4, second batch: RandomGridShuffle, HueSaturationValue, Cutout / GridDropout, RandomShadow, RandomSunFlare,
@@ -364,9 +208,7 @@ __global__ __launch_bounds__(256) void fill_rects_u8_kernel(uint8_t* __restrict_
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= H * W) return;
     const int y = idx / W, x = idx - y * W;
-    bool hit = false;
-    for (int k = 0; k < n && !hit; ++k) hit = x >= rects[4 * k] && x < rects[4 * k + 2] && y >= rects[4 * k + 1] && y < rects[4 * k + 3];
-    if (hit)
+    if (rects_hit(rects, n, y, x))
         for (int c = 0; c < C; ++c) img[(long)idx * C + c] = (uint8_t)fill;
 }
 

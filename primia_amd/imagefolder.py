@@ -9,7 +9,9 @@ through create_albu_transform (torchlib/dataloader.py:138-217) with that mean / 
 Here the decode (PIL, host) produces uint8 HWC arrays; everything after it runs on the GPU: `primia_image_prepare`
 (resize, crop, to-float, normalise — one launch per image into the client's device-resident dataset tensor) and
 `primia_mean_std`.  The transform chain is primia_amd.augment.TrainTransform: every member of the reference's
-create_albu_transform on the GPU (both shipped presets run as written).
+create_albu_transform on the GPU (both shipped presets run as written).  Loaders send images through it a batch at a
+time (`TrainTransform.batch`: one launch per stage per batch, one parameter upload per batch), which yields bit for bit
+the tensors of the per-image chain `tf(image, rng)` with the same consumption of the random streams.
 
 Loaders yield the ragged final batch as the reference's do (DataLoader / FederatedDataLoader, drop_last = False):
 `len(loader)` = ceil(n / batch_size); such a batch — and the batches MixUp halves in the local training loop — run on a
@@ -25,6 +27,7 @@ import torch
 from ._lib import call
 
 EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
+REGISTRATION_CHUNK = 256      # images per TrainTransform.batch call in the federated registration walks
 
 def scan(root):
     """torchvision.datasets.ImageFolder's listing: classes = sorted sub-directory names, samples sorted per class."""
@@ -102,7 +105,8 @@ class AugmentingLoader:
         order = torch.randperm(len(self.images), generator=self.gen).tolist()
         for b in range(len(self)):
             idx = order[b * self.batch_size:(b + 1) * self.batch_size]
-            yield torch.stack([self.tf(self.images[i], self.rng) for i in idx]), self.targets[torch.tensor(idx, device=self.targets.device)]
+            # one launch per stage per batch (TrainTransform.batch), bit-identical to stacking self.tf(image, rng) per image
+            yield self.tf.batch([self.images[i] for i in idx], self.rng), self.targets[torch.tensor(idx, device=self.targets.device)]
 
 
 def register(data_per_rep, targets, args, num_classes, seed):
@@ -148,7 +152,9 @@ def client_loader(root, args, device, channels, seed):
         # vanilla training draws fresh augmentations every epoch (a DataLoader over the transforming dataset)
         return AugmentingLoader(images, targets, tf, rng, args.batch_size, seed), (mean, std)
     reps = int(getattr(args, "repetitions_dataset", 1) or 1)
-    walks = [torch.stack([tf(img, rng) for img in images]) for _ in range(reps)]   # utils.py:704-717: one pass per walk
+    # utils.py:704-717: one pass per walk, the chain a chunk of images at a time (equal to tf(img, rng) image by image)
+    walks = [torch.cat([tf.batch(images[k:k + REGISTRATION_CHUNK], rng) for k in range(0, len(images), REGISTRATION_CHUNK)])
+             for _ in range(reps)]
     data, targets = register(walks, targets, args, len(classes), seed)
     return DeviceLoader(data, targets, args.batch_size, True, seed, drop_last=False), (mean, std)
 
