@@ -889,6 +889,12 @@ int primia_im2col_syft(const int64_t* x, int64_t* im, int B, int C, int H, int W
 /* _post_conv (nn/functional.py:169-201): res [B, Ho*Wo, O] (+ bias[O]) -> [B, O, Ho, Wo]. */
 int primia_col2out_syft(const int64_t* res, const int64_t* bias, int64_t* out, int B, int HoWo,
                         int O, primia_stream_t stream);
+/* The re-layouts around eval-mode batch_norm's rows form for a batch (nn/functional.py:44-75), one share each:
+ *   primia_nchw_to_rows   x.permute(1,0,2,3).reshape(C,-1).t():           x [B,C,HW] -> rows [B*HW, C], row b*HW + p
+ *   primia_rows_to_nchw   result.t().reshape(C,B,H,W).permute(1,0,2,3):   rows [B*HW, C] -> out [B,C,HW]
+ * (for B = 1 the plain transposes that primia_col2out_syft(.., 1, C, HW) / (.., 1, HW, C) perform).  Out of place. */
+int primia_nchw_to_rows(const int64_t* x, int64_t* rows, int B, int C, int HW, primia_stream_t stream);
+int primia_rows_to_nchw(const int64_t* rows, int64_t* out, int B, int C, int HW, primia_stream_t stream);
 /* _pre_pool (nn/functional.py:311-393): x [B,C,H,W] -> [B, C, Ho*Wo, k*k], zero padding. */
 int primia_pool_unroll_syft(const int64_t* x, int64_t* out, int B, int C, int H, int W, int k,
                             int stride, int pad, primia_stream_t stream);
@@ -918,6 +924,8 @@ int primia_newton_reciprocal_local(const int64_t* v0, const int64_t* v1, const i
  *   primia_bn_eval_local         batch_norm in eval mode (nn/functional.py:44-75) of one image: NCHW in, NCHW out, both
  *                                FPT products and the row / column re-layouts inside; t1 / t2: HOST arrays of the two
  *                                triples' six pointers (t1: a ~ inv [C], b, c ~ rows [HW, C]; t2: a, c ~ rows, b ~ weight)
+ *   primia_bn_eval_local_batch   the same for a batch (the reference's batch_norm on [B,C,H,W]): x / out [B][C][HW], the
+ *                                triples' rows side [B*HW, C] with row b*HW + p, i.e. x.permute(1,0,2,3).reshape(C,-1).t()
  *   primia_im2col_syft_2p, primia_pool_unroll_syft_2p   the PySyft layouts of both shares
  *   primia_beaver_matmul_local   spdz_mul "matmul": both opens, then z_j = c_j + delta @ (b_j [+ eps]) + a_j @ eps for
  *                                both parties in one grid; scratch = primia_beaver_matmul_local_scratch_elems int64
@@ -942,6 +950,11 @@ int primia_bn_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* me
                          const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
                          const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,
                          int64_t* out0, int64_t* out1, int C, int HW, int64_t div, primia_stream_t stream);
+int primia_bn_eval_local_batch(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
+                               const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
+                               const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1,
+                               const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW, int64_t div,
+                               primia_stream_t stream);
 int primia_im2col_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* im0, int64_t* im1, int B, int C, int H, int W, int R,
                           int S, int stride, int pad, primia_stream_t stream);
 int64_t primia_beaver_matmul_local_scratch_elems(int M, int K, int N);

@@ -7,7 +7,7 @@
 Plain inference runs the HIP engine in eval mode.  `--encrypted_inference` shares the model and
 each image between model_owner and data_owner (fixed precision 10^16, protocol "fss", a dealer as
 crypto provider) and runs the secret-shared forward of primia_amd.secure, image by image like the
-reference's loop.  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
+reference's loop, or `--batch_size N` images per protocol pass.  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
 """
 import argparse
 import json
@@ -73,6 +73,12 @@ if __name__ == "__main__":
     parser.add_argument("--cuda", action="store_true", help="Use GPU acceleration (always on here).")
     parser.add_argument("--http_protocol", action="store_true", help="accepted for compatibility")
     parser.add_argument("--num_images", type=int, default=4)
+    parser.add_argument("--batch_size", type=int, default=1,
+                        help="encrypted inference: images per protocol pass (default 1, the reference's loop); the last "
+                             "pass of --hip_graph / --three_role is padded with all-zero images whose rows are dropped")
+    parser.add_argument("--precision_fractional", type=int, default=16,
+                        help="encrypted inference: fractional decimal digits of the fixed-point encoding (default 16, the "
+                             "reference's literal, at which products wrap in the 2^64 ring; 3 keeps logits meaningful)")
     parser.add_argument("--hip_graph", action="store_true",
                         help="encrypted inference: capture the online phase once as a hipGraph and replay it per image "
                              "(the dealer refills the primitive buffers between images)")
@@ -104,6 +110,9 @@ if __name__ == "__main__":
     images = load_images(cmd_args.data_dir, cmd_args.num_images, size, channels, device, mean, std,
                          clahe=bool(getattr(args, "clahe", False)))
     total_pred = []
+    bs = cmd_args.batch_size
+    if bs < 1:
+        raise SystemExit("--batch_size must be at least 1")
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
         if cmd_args.three_role:
@@ -122,27 +131,29 @@ if __name__ == "__main__":
             logits = run_three_role(link, architecture_of(sd), size, images.shape[0],
                                     state_dict=sd if link.role == 0 else None,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
-                                    seed=cmd_args.debug_dealer_seed)
+                                    seed=cmd_args.debug_dealer_seed, batch=bs,
+                                    precision_fractional=cmd_args.precision_fractional)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
                 sys.exit(0)
-            total_pred = [int(o.argmax(dim=1).item()) for o in logits]
+            total_pred = [int(c) for o in logits for c in o.argmax(dim=1).tolist()]
             if os.environ.get("PRIMIA_DUMP_LOGITS"):
                 torch.save(torch.cat(logits).cpu(), os.environ["PRIMIA_DUMP_LOGITS"])
         elif cmd_args.hip_graph:
             from primia_amd.secure import GraphedSecureInference
 
-            model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=16,
-                                           seed=cmd_args.debug_dealer_seed)
+            model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
+                                           seed=cmd_args.debug_dealer_seed, batch=bs)
         else:
-            ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed), base=10, precision_fractional=16)
+            ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed), base=10,
+                                precision_fractional=cmd_args.precision_fractional)
             model = SecureResNet18(ctx, sd, input_size=size)
         logits = []
-        for i in range(0 if cmd_args.three_role else images.shape[0]):
-            out = model(images[i:i + 1]).clone()      # (the graphed form returns its static output buffer: keep a copy)
+        for i in range(0, 0 if cmd_args.three_role else images.shape[0], bs):
+            out = model(images[i:i + bs]).clone()     # (the graphed form returns its static output buffer: keep a copy)
             logits.append(out)
-            total_pred.append(int(out.argmax(dim=1).item()))
+            total_pred += [int(c) for c in out.argmax(dim=1).tolist()]
         if logits and os.environ.get("PRIMIA_DUMP_LOGITS"):
             torch.save(torch.cat(logits).cpu(), os.environ["PRIMIA_DUMP_LOGITS"])
     else:

@@ -29,6 +29,11 @@ __global__ __launch_bounds__(256) void ring_scale_kernel(const u64* __restrict__
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = a[i] * k;
 }
 
+__global__ __launch_bounds__(256) void ring_fill_kernel(u64* __restrict__ out, u64 v, long n) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = v;
+}
+
 __global__ __launch_bounds__(256) void trunc_div_kernel(const int64_t* __restrict__ x, int64_t d,
                                                         int64_t* __restrict__ out, long n) {
     const long stride = (long)gridDim.x * 256;
@@ -91,6 +96,30 @@ __global__ __launch_bounds__(256) void col2out_syft_kernel(const u64* __restrict
     const int o = (int)(t % O);
     const int b = (int)(t / O);
     out[i] = res[((long)b * P + p) * O + o] + (bias ? bias[o] : (u64)0);
+}
+
+// dst[b][j][i] = src[b][i][j] for src [B][R][Cn]: the two re-layouts around batch_norm's rows form (nn/functional.py:44-75),
+//   x.permute(1,0,2,3).reshape(C,-1).t()          [B][C][HW] -> [B*HW][C]  (row b*HW + p: R = C, Cn = HW)
+//   result.t().reshape(C,B,H,W).permute(1,0,2,3)  [B*HW][C] -> [B][C][HW]  (R = HW, Cn = C)
+// of one share.  A 32 x 32 tile through LDS, whole lines on both sides; grid (j-tile, i-tile, b), so a tile lies inside one
+// image.  Rows of 33 u64: the transposed read is at dword 66 tx + const, 2 tx mod 64 over a 32-lane group of ds_read_b64 --
+// every bank once (unpadded: 32 lanes on one bank); see bn_eval_local_kernel, secure_local.hip.
+__global__ __launch_bounds__(256) void batch_transpose_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int R, int Cn) {
+    __shared__ u64 tile[32][33];
+    const int j0 = blockIdx.x * 32, i0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
+    const long img = (long)blockIdx.z * R * Cn;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = i0 + ty + 8 * k, j = j0 + tx;
+        if (i < R && j < Cn) tile[ty + 8 * k][tx] = src[img + (long)i * Cn + j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int j = j0 + ty + 8 * k, i = i0 + tx;
+        if (i < R && j < Cn) dst[img + (long)j * R + i] = tile[tx][ty + 8 * k];
+    }
 }
 
 // out[b][c][ho*Wo + wo][r*k + s] = xpad[b][c][ho*stride + r][wo*stride + s]
@@ -310,7 +339,9 @@ static inline int ew_blocks(long n) {
 
 static int launch_gemm(GemmPair p1, GemmPair p2, const u64* C0, u64* C, int M, int K, int N, hipStream_t st) {
     const int tiles = ((N + 63) / 64) * ((M + 63) / 64);
-    // few output tiles (the N = 1 image has M = 49..784 rows in layer3/4): split K to fill the chip
+    // few output tiles (the N = 1 image has M = 49..784 rows in layer3/4): split K to fill the chip.  M enters through the
+    // tile count only: a batch's [B*L, K] operand has B times the tiles and a proportionally smaller split, down to 1 once
+    // there are 256 tiles (the table for the 224 x 224 shapes is at primia_beaver_matmul_local, secure_local.hip)
     int ksplit = 1;
     if (tiles < 256) {
         ksplit = (512 + tiles - 1) / tiles;
@@ -319,13 +350,16 @@ static int launch_gemm(GemmPair p1, GemmPair p2, const u64* C0, u64* C, int M, i
         if (ksplit < 1) ksplit = 1;
     }
     if (ksplit > 1) {
-        const size_t bytes = (size_t)M * N * sizeof(u64);
-        hipError_t e = hipSuccess;
+        // C = C0 (or zero) before the slices add to it -- by kernels of this library, not hipMemsetAsync / hipMemcpyAsync: as
+        // memset NODES of a captured refill graph (GraphedSecureInference) the zeroing of c1 was seen to be lost on replays
+        // once a second serving instance had been constructed (its triples then no longer multiplied out:
+        // tests/test_gpu_secure_batch.py, the pipelined test); a kernel node has no such dependence on the runtime's state
+        const long mn = (long)M * N;
         if (!C0)
-            e = hipMemsetAsync(C, 0, bytes, st);
+            ring_fill_kernel<<<ew_blocks(mn), 256, 0, st>>>(C, (u64)0, mn);
         else if (C0 != C)
-            e = hipMemcpyAsync(C, C0, bytes, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return PRIMIA_ERR_LAUNCH;
+            ring_scale_kernel<<<ew_blocks(mn), 256, 0, st>>>(C0, (u64)1, C, mn);
+        if (launch_status() != PRIMIA_OK) return PRIMIA_ERR_LAUNCH;
     }
     dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
     ring_gemm_kernel<<<grid, 256, 0, st>>>(p1, p2, C0, C, M, K, N, ksplit);
@@ -406,6 +440,21 @@ int primia_col2out_syft(const int64_t* res, const int64_t* bias, int64_t* out, i
     col2out_syft_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)st>>>((const u64*)res, (const u64*)bias,
                                                                             (u64*)out, B, HoWo, O);
     return launch_status();
+}
+
+static int launch_batch_transpose(const int64_t* src, int64_t* dst, int B, int R, int Cn, primia_stream_t st) {
+    PRIMIA_REQUIRE(src && dst && src != dst && B > 0 && B <= 65535 && R > 0 && Cn > 0 && (R + 31) / 32 <= 65535);
+    const dim3 grid((Cn + 31) / 32, (R + 31) / 32, B);
+    batch_transpose_kernel<<<grid, 256, 0, (hipStream_t)st>>>((const u64*)src, (u64*)dst, R, Cn);
+    return launch_status();
+}
+
+int primia_nchw_to_rows(const int64_t* x, int64_t* rows, int B, int C, int HW, primia_stream_t st) {
+    return launch_batch_transpose(x, rows, B, C, HW, st);
+}
+
+int primia_rows_to_nchw(const int64_t* rows, int64_t* out, int B, int C, int HW, primia_stream_t st) {
+    return launch_batch_transpose(rows, out, B, HW, C, st);
 }
 
 int primia_pool_unroll_syft(const int64_t* x, int64_t* out, int B, int C, int H, int W, int k, int stride,

@@ -102,13 +102,22 @@ __global__ __launch_bounds__(256) void max_combine_local_kernel(Pair bit, ColOpe
     }
 }
 
-// ---- batch_norm in eval mode (nn/functional.py:44-75) on one image, both parties -------------------------------------
-//   rows = x.permute(1,0,2,3).reshape(C,-1).t()                         [HW, C]
+// ---- batch_norm in eval mode (nn/functional.py:44-75), both parties ---------------------------------------------------
+//   rows = x.permute(1,0,2,3).reshape(C,-1).t()                         [B*HW, C], row b*HW + p
 //   normalized = inv * (rows - mean)     (FPT mul: Beaver + truncation; triple t1: a ~ inv [C], b ~ rows, c ~ rows)
 //   result = normalized * weight + bias  (triple t2: a ~ rows, b ~ weight [C], c ~ rows)
-//   out = result.t().reshape(C, 1, H, W).permute(1,0,2,3)               [1, C, H, W]
-// x / out are NCHW ([C][HW]), the triples are in the ROWS layout: a 32 x 32 tile goes through LDS so that both sides
-// are read and written in whole lines.
+//   out = result.t().reshape(C, B, H, W).permute(1,0,2,3)               [B, C, H, W]
+// x / out are NCHW ([B][C][HW]), the triples are in the ROWS layout: a 32 x 32 tile goes through LDS so that both sides
+// are read and written in whole lines.  The grid is (p-tile, c-tile, b): a tile lies inside ONE image, so its 32 rows are
+// consecutive rows b*HW + p of the triples (one image, primia_bn_eval_local, is the grid with a single z plane).
+//
+// LDS padding, 8-byte elements (rows of 33 u64 = 66 dwords).  A wave is tx = 0..31 at two values of ty:
+//   row access   tile[ty + 8k][tx]   16 (store) / 32 (load) consecutive u64: every bank once;
+//   transposed   tile[tx][ty + 8k]   dword address 66 tx + const.  ds_read_b64 banks over 64 dwords in 32-lane groups:
+//                66 tx mod 64 = 2 tx, 32 distinct even banks, each lane also taking the odd one after it -> all 64 banks
+//                once.  ds_write_b64 banks over 32 dwords in 16-lane groups: 2 tx mod 32 for 16 consecutive tx -> all 32
+//                banks once.  Unpadded ([32][32], 64 dwords a row) every lane of a group would sit on ONE bank: 32-way and
+//                16-way.  A pad of one element is the smallest that clears both; 2 / 4 / 8 elements leave 2 / 4 / 8-way.
 struct BnVec {
     const u64 *mean0, *mean1, *inv0, *inv1, *w0, *w1, *bias0, *bias1;
 };
@@ -117,13 +126,15 @@ __global__ __launch_bounds__(256) void bn_eval_local_kernel(Pair x, BnVec v, Tri
     __shared__ u64 tile[2][32][33];
     const int p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
+    const long img = (long)blockIdx.z * C * HW;                   // this image's [C][HW] plane of x / out
+    const long row0 = (long)blockIdx.z * HW;                      // ... and its first row of the triples
     // load x[c][p] (coalesced along p)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int c = c0 + ty + 8 * k, p = p0 + tx;
         if (c < C && p < HW) {
-            tile[0][ty + 8 * k][tx] = x.p0[(long)c * HW + p];
-            tile[1][ty + 8 * k][tx] = x.p1[(long)c * HW + p];
+            tile[0][ty + 8 * k][tx] = x.p0[img + (long)c * HW + p];
+            tile[1][ty + 8 * k][tx] = x.p1[img + (long)c * HW + p];
         }
     }
     __syncthreads();
@@ -134,7 +145,7 @@ __global__ __launch_bounds__(256) void bn_eval_local_kernel(Pair x, BnVec v, Tri
         const int p = p0 + ty + 8 * k, c = c0 + tx;
         r0[k] = r1[k] = 0;
         if (c < C && p < HW) {
-            const long i = (long)p * C + c;
+            const long i = (row0 + p) * C + c;
             const u64 y0 = tile[0][tx][ty + 8 * k] - v.mean0[c], y1 = tile[1][tx][ty + 8 * k] - v.mean1[c];
             u64 n0, n1;
             // fpt_mul(inv, rows - mean): the small operand (inv) is the FIRST one -> its triple side is `a`
@@ -161,8 +172,8 @@ __global__ __launch_bounds__(256) void bn_eval_local_kernel(Pair x, BnVec v, Tri
     for (int k = 0; k < 4; ++k) {
         const int c = c0 + ty + 8 * k, p = p0 + tx;
         if (c < C && p < HW) {
-            out.p0[(long)c * HW + p] = tile[0][ty + 8 * k][tx];
-            out.p1[(long)c * HW + p] = tile[1][ty + 8 * k][tx];
+            out.p0[img + (long)c * HW + p] = tile[0][ty + 8 * k][tx];
+            out.p1[img + (long)c * HW + p] = tile[1][ty + 8 * k][tx];
         }
     }
 }
@@ -371,19 +382,34 @@ int primia_max_combine_local(const int64_t* bit0, const int64_t* bit1, const int
     return launch_status();
 }
 
-int primia_bn_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
-                         const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
-                         const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,
-                         int64_t* out0, int64_t* out1, int C, int HW, int64_t div, primia_stream_t st) {
+static int bn_eval_local_launch(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
+                                const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
+                                const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,
+                                int64_t* out0, int64_t* out1, int B, int C, int HW, int64_t div, primia_stream_t st) {
     PRIMIA_REQUIRE(x0 && x1 && mean0 && mean1 && inv0 && inv1 && w0 && w1 && bias0 && bias1 && t1 && t2 && out0 && out1 &&
-                   C > 0 && HW > 0 && div > 0);
+                   B > 0 && B <= 65535 && C > 0 && HW > 0 && div > 0);
     for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(t1[k] && t2[k]);
-    const dim3 grid((HW + 31) / 32, (C + 31) / 32);
+    const dim3 grid((HW + 31) / 32, (C + 31) / 32, B);
     bn_eval_local_kernel<<<grid, 256, 0, (hipStream_t)st>>>(
         Pair{U(x0), U(x1)}, BnVec{U(mean0), U(mean1), U(inv0), U(inv1), U(w0), U(w1), U(bias0), U(bias1)},
         Triple{U(t1[0]), U(t1[1]), U(t1[2]), U(t1[3]), U(t1[4]), U(t1[5])},
         Triple{U(t2[0]), U(t2[1]), U(t2[2]), U(t2[3]), U(t2[4]), U(t2[5])}, OutPair{(u64*)out0, (u64*)out1}, C, HW, (u64)div);
     return launch_status();
+}
+
+int primia_bn_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
+                         const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
+                         const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,
+                         int64_t* out0, int64_t* out1, int C, int HW, int64_t div, primia_stream_t st) {
+    return bn_eval_local_launch(x0, x1, mean0, mean1, inv0, inv1, w0, w1, bias0, bias1, t1, t2, out0, out1, 1, C, HW, div, st);
+}
+
+int primia_bn_eval_local_batch(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
+                               const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
+                               const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1,
+                               const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW, int64_t div,
+                               primia_stream_t st) {
+    return bn_eval_local_launch(x0, x1, mean0, mean1, inv0, inv1, w0, w1, bias0, bias1, t1, t2, out0, out1, B, C, HW, div, st);
 }
 
 int primia_im2col_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* im0, int64_t* im1, int B, int C, int H, int W, int R,
@@ -417,6 +443,11 @@ int primia_beaver_matmul_local(const int64_t* x0, const int64_t* x1, const int64
                                                                      b0e, z, mk, kn, mn);
     const int tiles = ((N + 63) / 64) * ((M + 63) / 64);
     int ksplit = 1;
+    // The split depends on M through the tile count only.  A batch of B images is the [B*L, K] matrix: at 224 x 224 the five
+    // shapes (L = 12544, 3136, 784, 196, 49 with N = 64, 64, 128, 256, 512 and K = 147, 576, 1152, 2304, 4608) give, as
+    // (tiles per party, ksplit):  B = 1: (196,1) (49,6) (26,10) (16,16) (8,32);  B = 2: (392,1) (98,3) (50,6) (28,10) (16,16);
+    // B = 4: (784,1) (196,1) (98,3) (52,5) (32,8);  B = 8: (1568,1) (392,1) (196,1) (100,3) (56,5) -- always 2 * tiles * ksplit
+    // >= 512 blocks for the 256 CUs until the tiles alone provide them, and never fewer than 64 k per slice.
     if (2 * tiles < 256) {       // few output tiles (one image: M = 49 .. 784 rows in layer3 / 4): split K to fill the chip
         ksplit = (512 + 2 * tiles - 1) / (2 * tiles);
         const int kmax = (K + 63) / 64;

@@ -102,7 +102,9 @@ class Dealer:
             else:
                 call("primia_triple_mul_c1", b0, b1, a0, a1, c0, c1, b0.numel(), a0.numel())
         else:
-            M, K, N = xshape[-2], xshape[-1], yshape[-1]
+            # a [B, L, K] operand (conv2d of a batch) is the [B*L, K] matrix: the leading dimensions are rows
+            K, N = xshape[-1], yshape[-1]
+            M = int(torch.Size(xshape).numel()) // K
             if scratch is None:
                 scratch = torch.empty(M * K + K * N, dtype=I64, device=self.device)
             call("primia_triple_matmul_c1", a0, a1, b0, b1, c0, c1, scratch, M, K, N)
@@ -371,9 +373,11 @@ class SecureContext:
         return self.trunc(out, trunc) if (trunc is not None and not fused_trunc) else out
 
     def beaver_matmul(self, x, y):
+        """x [..., K] @ y [K, N]: the leading dimensions of x are rows of ONE product (a batch's [B, L, K] im2col operand is
+        the [B*L, K] matrix); the triple is requested with the operand's own shape, as the reference's batched call does."""
         xr, yr = self._ref(x), self._ref(y)
-        M, K = xr.shape[-2], xr.shape[-1]
-        N = yr.shape[-1]
+        K, N = xr.shape[-1], yr.shape[-1]
+        M = xr.numel() // K
         t = self.dealer.triple("matmul", tuple(xr.shape), tuple(yr.shape))
         if self._local:
             out = [torch.empty(*xr.shape[:-1], N, dtype=I64, device=xr.device) for _ in range(2)]
@@ -486,7 +490,7 @@ class SecureContext:
     # ---- layers (nn/functional.py) ------------------------------------------------------------------
     def conv2d(self, x, w, stride, padding):
         """conv2d (nn/functional.py:204-308): per-share im2col, Beaver matmul + truncation,
-        per-share reshape.  x shares [1,C,H,W]; w shares [O,C,R,S]; no bias in ResNet convs."""
+        per-share reshape.  x shares [B,C,H,W]; w shares [O,C,R,S]; no bias in ResNet convs."""
         B, C, H, W = self._ref(x).shape
         O, _, R, S = self._ref(w).shape
         Ho, Wo = (H + 2 * padding - R) // stride + 1, (W + 2 * padding - S) // stride + 1
@@ -615,12 +619,13 @@ class SecureContext:
         "newton" iteration converges to var^-1/2).  `inv` may carry shares of newton(var) computed
         earlier (see SecureResNet18.precompute_inv)."""
         B, C, H, W = self._ref(x).shape
-        if B != 1:
-            raise ValueError("encrypted inference runs one image at a time (inference.py:292)")
 
-        def to_rows(j):  # permute(1,0,2,3).reshape(C,-1).t()  -> [B*H*W, C]  (B == 1)
+        def to_rows(j):  # permute(1,0,2,3).reshape(C,-1).t()  -> [B*H*W, C], row b*H*W + p
             o = torch.empty(B * H * W, C, dtype=I64, device=x[j].device)
-            call("primia_col2out_syft", x[j], None, o, 1, C, B * H * W)
+            if B == 1:
+                call("primia_col2out_syft", x[j], None, o, 1, C, H * W)
+            else:
+                call("primia_nchw_to_rows", x[j], o, B, C, H * W)
             return o
 
         if self._local:
@@ -634,8 +639,12 @@ class SecureContext:
             arr = lambda t: (ctypes.c_void_p * 6)(*[q.data_ptr() for q in (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])])
             dev = x[0].device
             out = [torch.empty(B, C, H, W, dtype=I64, device=dev), torch.empty(B, C, H, W, dtype=I64, device=dev)]
-            call("primia_bn_eval_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0], bias[1],
-                 arr(t1), arr(t2), out[0], out[1], C, HW, int(self.scale))
+            if B == 1:
+                call("primia_bn_eval_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
+                     bias[1], arr(t1), arr(t2), out[0], out[1], C, HW, int(self.scale))
+            else:
+                call("primia_bn_eval_local_batch", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
+                     bias[1], arr(t1), arr(t2), out[0], out[1], B, C, H * W, int(self.scale))
             self.stats["beaver_mul"] += 2
             return out
         rows = self._each(to_rows)
@@ -646,7 +655,10 @@ class SecureContext:
 
         def back(j):
             o = torch.empty(B, C, H, W, dtype=I64, device=result[j].device)
-            call("primia_col2out_syft", result[j], None, o, 1, B * H * W, C)
+            if B == 1:
+                call("primia_col2out_syft", result[j], None, o, 1, H * W, C)
+            else:
+                call("primia_rows_to_nchw", result[j], o, B, C, H * W)
             return o
 
         return self._each(back)
@@ -816,20 +828,134 @@ class SecureResNet18:
             x = c.relu(c.add(out, identity))
         k = c._ref(x).shape[-1]
         x = c.avg_pool2d(x, k)
-        x = [None if t is None else t.reshape(1, -1) for t in x]
+        B = c._ref(x).shape[0]
+        x = [None if t is None else t.reshape(B, -1) for t in x]
         return c.linear(x, p["fc.weight"], p["fc.bias"])
 
-    def __call__(self, image):
-        """image: fp32 [1, C, S, S] on the GPU -> decoded fp32 logits [1, classes].  The data owner is
-        party 1 (inference.py:292-300); in a distributed run party 0 passes image = None."""
+    def __call__(self, image, batch=1):
+        """image: fp32 [B, C, S, S] on the GPU -> decoded fp32 logits [B, classes]: the B images go through ONE protocol
+        pass.  The data owner is party 1 (inference.py:292-300); in a distributed run party 0 passes image = None and
+        `batch`, the number of images it is to expect (it receives shares, never an image)."""
         c = self.ctx
         if c.party in (None, 1):
             xs = c.share(c.encode(image), owner=1)
         else:
             cin = c._ref(self.p["conv1.weight"]).shape[1]        # 3 (pretrained) or 1 (train.py:262)
-            xs = c.share(None, owner=1, shape=(1, cin, self.input_size, self.input_size))
+            xs = c.share(None, owner=1, shape=(int(batch), cin, self.input_size, self.input_size))
         out = self.forward_shares(xs)
         return c.decode(c.reconstruct(out))
+
+
+def _default_blocks():
+    return [(f"layer{li}.{bi}", (2 if (li > 1 and bi == 0) else 1)) for li in range(1, 5) for bi in range(2)]
+
+
+def image_requests(arch, input_size, batch=1, blocks=None):
+    """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
+    `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
+    what `SecureResNet18.__call__` asks for (tests hold the two equal), so that the memory a serving form needs is known
+    BEFORE anything is allocated.  Per batch, not per image: the 80-step Newton reciprocal (237 triples over all BatchNorm
+    channels) and the weight side of every matmul triple; per image: everything with a row of its own."""
+    B, req = int(batch), []
+    blocks = _default_blocks() if blocks is None else blocks
+    triple = lambda op, xs, ys: req.append(("triple", (op, tuple(xs), tuple(ys)), {}))
+    mask = lambda shape, owner: req.append(("const_mask", tuple(shape), {"owner": owner}))
+    out_hw = lambda h, k, stride, pad: (h + 2 * pad - k) // stride + 1
+    cin = arch["conv1.weight"][1]
+    mask((B, cin, input_size, input_size), 1)                                  # the images, shared by the data owner
+    names = ["bn1"]
+    for prefix, _ in blocks:
+        names += [prefix + ".bn1", prefix + ".bn2"]
+        if (prefix + ".downsample.0.weight") in arch:
+            names.append(prefix + ".downsample.1")
+    total = sum(arch[n + ".running_var"][0] for n in names)
+    mask((1,), None)                                                           # reciprocal_newton of all layers at once
+    for _ in range(79):
+        triple("mul", (total,), (total,))
+        triple("mul", (total,), (total,))
+        mask((1,), None)
+        triple("mul", (total,), (total,))
+
+    def conv(name, h, stride, pad):
+        o, c, r, _ = arch[name + ".weight"]
+        ho = out_hw(h, r, stride, pad)
+        triple("matmul", (B, ho * ho, c * r * r), (c * r * r, o))
+        return o, ho
+
+    def bn(c, h):
+        triple("mul", (c,), (B * h * h, c))
+        triple("mul", (B * h * h, c), (c,))
+
+    def relu(c, h):
+        req.append(("dif_keys", (B * c * h * h,), {}))
+        triple("mul", (B, c, h, h), (B, c, h, h))
+
+    c, h = conv("conv1", input_size, 2, 3)
+    bn(c, h)
+    h = out_hw(h, 3, 2, 1)
+    rows = B * c * h * h
+    for length in (4, 2, 1, 1):                                                # the 9-window max tree
+        req.append(("dif_keys", (rows * length,), {}))
+        triple("mul", (rows, length), (rows, length))
+    relu(c, h)
+    for prefix, stride in blocks:
+        o, ho = conv(prefix + ".conv1", h, stride, 1)
+        bn(o, ho)
+        relu(o, ho)
+        conv(prefix + ".conv2", ho, 1, 1)
+        bn(o, ho)
+        if (prefix + ".downsample.0.weight") in arch:
+            conv(prefix + ".downsample.0", h, stride, 0)
+            bn(o, ho)
+        relu(o, ho)
+        c, h = o, ho
+    classes, feat = arch["fc.weight"]
+    triple("matmul", (B, feat), (feat, classes))
+    return req
+
+
+# bytes of one comparison's DIF key as Dealer.dif_keys lays it out: raw alpha, its mask and party 0's share (3 x 8), both
+# parties' seeds (2 x 2 x 8), the packed control bits (32), cw_sigma and cw_s (32 x 2 x 8 each), the leaf words (33 x 4)
+DIF_KEY_BYTES = 3 * 8 + 32 + 32 + 2 * 32 * 2 * 8 + 33 * 4
+
+
+def primitive_bytes(requests):
+    """Device bytes of the primitives a request list stands for (both parties' halves)."""
+    numel = lambda shape: int(torch.Size(shape).numel())
+    total = 0
+    for kind, args, _ in requests:
+        if kind == "const_mask":
+            total += 8 * numel(args)
+        elif kind == "dif_keys":
+            total += DIF_KEY_BYTES * args[0]
+        else:
+            op, xs, ys = args
+            total += 16 * (numel(xs) + numel(ys) + numel(_triple_c_shape(op, xs, ys)))
+    return total
+
+
+def serving_bytes(arch, input_size, batch, blocks=None):
+    """What GraphedSecureInference(batch=...) holds in static buffers: every primitive of one pass (dominated by the DIF
+    keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image) plus one eighth on top for the arena copy of
+    their random words while both exist (5/6 of a triple, 48 of a key's 1,244 bytes) and the captured graph's activations
+    (im2col and pool-unroll operands: under 2 % of the keys at every layer)."""
+    b = primitive_bytes(image_requests(arch, input_size, batch, blocks))
+    return b + b // 8
+
+
+def largest_batch_that_fits(arch, input_size, budget, blocks=None):
+    """The largest batch whose static buffers fit in `budget` bytes (0: not even one image).  serving_bytes is affine in the
+    batch (a per-batch part, Newton and the weight masks, plus a per-image part) up to its rounding, so two evaluations
+    give the answer and the neighbours settle the rounding."""
+    need = lambda k: serving_bytes(arch, input_size, k, blocks)
+    one, two = need(1), need(2)
+    per_image, fixed = two - one, 2 * one - two
+    k = max(0, (int(budget) - fixed) // per_image)
+    while need(k + 1) <= budget:
+        k += 1
+    while k > 0 and need(k) > budget:
+        k -= 1
+    return k
 
 
 class GraphedSecureInference:
@@ -846,14 +972,33 @@ class GraphedSecureInference:
     image would get the same masks), then one launch per triple forms c1 = a o b - c0 and two per comparison batch form
     the key (alpha split, DIF keygen).  ~3,000 eager launches per image became ~450 graph nodes; `refill_graph = False`
     launches the same calls eagerly (same bits).  The constructor ends with one refill: no image is ever served on the
-    primitives the all-zero warm-up image consumed (opened values on a known input reveal the masks)."""
+    primitives the all-zero warm-up image consumed (opened values on a known input reveal the masks).
+
+    `batch` images per protocol pass: the static input buffer, the arena and both captured graphs are for that ONE batch
+    size; fewer images (the last ones of a stream) are padded with all-zero images whose rows consume their own primitives
+    and are dropped.  The static buffers are sized on the host first (`serving_bytes`) and a batch that does not fit in
+    `memory_budget` bytes (default: the device's free memory plus what torch's allocator holds unused) is refused with the
+    largest batch that would."""
 
     refill_graph = True
 
-    def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None):
+    def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
+                 memory_budget=None):
         self.device = torch.device(device)
-        # (an all-zero warm-up image, uploaded: no fill kernel of torch's on the path)
-        self.image = torch.zeros(1, state_dict["conv1.weight"].shape[1], input_size, input_size, dtype=torch.float32).to(self.device)
+        self.batch = int(batch)
+        if self.batch < 1:
+            raise ValueError("batch must be at least 1")
+        arch = architecture_of(state_dict)
+        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks)
+        if memory_budget is None:
+            free, _ = torch.cuda.mem_get_info(self.device)
+            memory_budget = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
+        if self.static_bytes > memory_budget:
+            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks)
+            raise ValueError(f"a batch of {self.batch} images at {input_size}x{input_size} needs {self.static_bytes} bytes of static "
+                             f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
+        # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
+        self.image = torch.zeros(self.batch, state_dict["conv1.weight"].shape[1], input_size, input_size, dtype=torch.float32).to(self.device)
         self.dealer = Dealer(self.device, seed)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
@@ -938,8 +1083,8 @@ class GraphedSecureInference:
                 a0, a1, b0, b1, c0 = (view(o, t) for o, t in zip(offs, (a0, a1, b0, b1, c0)))
                 self.tape[i] = [(a0, b0, c0), (a1, b1, c1)]
                 self._ops.append(("triple", op, xshape, yshape, a0, a1, b0, b1, c0, c1))
-                if op != "mul":
-                    max_kn = max(max_kn, xshape[-2] * xshape[-1] + xshape[-1] * yshape[-1])
+                if op != "mul":      # triple_c1's scratch: a = a0 + a1 [B*L, K] and b = b0 + b1 [K, N]
+                    max_kn = max(max_kn, a0.numel() + b0.numel())
             else:
                 (n,) = args
                 k0, k1 = e
@@ -974,14 +1119,32 @@ class GraphedSecureInference:
             self._refill_launches()
         self.refills += 1
 
+    def load(self, image):
+        """Copy [n <= batch, C, S, S] images into the static input buffer, the rest of it zero; returns n."""
+        if self.batch == 1:
+            self.image.copy_(image)
+            return 1
+        n = image.shape[0]
+        if not 1 <= n <= self.batch:
+            raise ValueError(f"this form serves 1 to {self.batch} images per pass, got {n}")
+        self.image[:n].copy_(image)
+        if n < self.batch:
+            self.image[n:].zero_()
+        return n
+
+    def rows(self, n):
+        """The first n rows of the static output (all of it, the very buffer, for a full batch)."""
+        return self.out if n == self.batch else self.out[:n]
+
     def __call__(self, image, refill=True):
-        """refill=False replays on the primitives the buffers hold (bit-identity checks against an eager forward on the
+        """image [n <= batch, C, S, S] -> logits [n, classes] (a view of the static output buffer).
+        refill=False replays on the primitives the buffers hold (bit-identity checks against an eager forward on the
         same tape; a deployment never serves two images on one set of primitives)."""
         if refill:
             self.refill()
-        self.image.copy_(image)
+        n = self.load(image)
         self.graph.replay()
-        return self.out
+        return self.rows(n)
 
 
 class PipelinedSecureInference:
@@ -996,10 +1159,11 @@ class PipelinedSecureInference:
     bit-identical to it, tests/test_gpu_secure.py); nothing about the protocol changes, only who waits for whom.
     In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU."""
 
-    def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2):
+    def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
+                 batch=1):
         self.device = torch.device(device)
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
-                                             None if seed is None else seed + 7919 * k, blocks) for k in range(slots)]
+                                             None if seed is None else seed + 7919 * k, blocks, batch) for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
         # event: slot k's primitives are fresh.  None = fresh since construction: GraphedSecureInference ends its constructor
@@ -1009,15 +1173,16 @@ class PipelinedSecureInference:
         self._n = 0
 
     def __call__(self, image):
-        """One encrypted inference; returns what SecureResNet18 returns (a copy: the slot's buffers are reused)."""
+        """One encrypted pass over [n <= batch] images; returns what SecureResNet18 returns (a copy: the slot's buffers are
+        reused)."""
         k = self._n % len(self.slots)
         slot = self.slots[k]
         main = torch.cuda.current_stream()
         if self._ready[k] is not None:
             main.wait_event(self._ready[k])
-        slot.image.copy_(image)
+        n = slot.load(image)
         slot.graph.replay()
-        out = slot.out.clone()
+        out = slot.rows(n).clone()
         consumed = torch.cuda.Event()
         consumed.record(main)
         # the dealer regenerates this slot's primitives for image n + len(slots) while the next image runs on another slot
@@ -1122,17 +1287,17 @@ def architecture_of(state_dict):
     return {k: tuple(v.shape) for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
 
 
-def request_schedule(arch, input_size, device, blocks=None, precision_fractional=16, base=10):
-    """The (public) sequence of primitives one model sharing + one encrypted forward consumes, as
-    (model_requests, image_requests): it depends on the architecture and the input size only, so the crypto
-    provider derives it from a dry run on a dummy model of that architecture."""
+def request_schedule(arch, input_size, device, blocks=None, precision_fractional=16, base=10, batch=1):
+    """The (public) sequence of primitives one model sharing + one encrypted forward of `batch` images consumes, as
+    (model_requests, image_requests): it depends on the architecture, the input size and the batch size only, so the
+    crypto provider derives it from a dry run on a dummy model of that architecture."""
     d = Dealer(device, seed=0)
     d.requests = []
     ctx = SecureContext(d, base, precision_fractional)
     dummy = {k: torch.ones(shape, dtype=torch.float32) for k, shape in arch.items()}
     model = SecureResNet18(ctx, dummy, input_size, blocks)
     n_model = len(d.requests)
-    model(torch.zeros(1, arch["conv1.weight"][1], input_size, input_size, dtype=torch.float32, device=device))
+    model(torch.zeros(batch, arch["conv1.weight"][1], input_size, input_size, dtype=torch.float32, device=device))
     return d.requests[:n_model], d.requests[n_model:]
 
 
@@ -1168,16 +1333,19 @@ def party_context(link: PartyLink, precision_fractional=16, base=10):
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10):
+                   precision_fractional=16, base=10, batch=1):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
-    all know the architecture, the input size and how many images will be classified.  Parties return the
-    list of decoded logits (the reference `.get()`s the prediction to the orchestrator), the dealer None."""
+    all know the architecture, the input size, how many images will be classified and how many go through one
+    protocol pass (`batch`; the last pass is padded with all-zero images, whose rows are dropped).  Parties return the
+    list of decoded logits, one [<= batch, classes] tensor per pass (the reference `.get()`s the prediction to the
+    orchestrator), the dealer None."""
+    passes = (n_images + batch - 1) // batch
     if link.role == "dealer":
-        model_req, image_req = request_schedule(arch, input_size, link.device, blocks, precision_fractional, base)
+        model_req, image_req = request_schedule(arch, input_size, link.device, blocks, precision_fractional, base, batch)
         svc = DealerService(Dealer(link.device, seed), link)
         svc.serve(model_req)
-        for _ in range(n_images):
+        for _ in range(passes):
             svc.serve(image_req)
         return None
     ctx = party_context(link, precision_fractional, base)
@@ -1191,6 +1359,13 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         shapes = {k: torch.empty(shape, device="meta") for k, shape in arch.items()}
     model = SecureResNet18(ctx, shapes, input_size, blocks)
     out = []
-    for i in range(n_images):
-        out.append(model(images[i:i + 1] if link.role == 1 else None))
+    for i in range(0, n_images, batch):
+        n = min(batch, n_images - i)
+        chunk = None
+        if link.role == 1:
+            chunk = images[i:i + n]
+            if n < batch:
+                chunk = torch.cat([chunk, chunk.new_zeros((batch - n,) + tuple(chunk.shape[1:]))])
+        res = model(chunk, batch=batch)
+        out.append(res if n == batch else res[:n])
     return out

@@ -1,6 +1,7 @@
 """Encrypted-inference timing (BASELINE.json configs[4], all three roles on one GPU):
 ms/image for the online phase (primitives pre-provisioned) and for the dealer (triples + FSS keys).
-    python tools/bench_secure.py [--size 224] [--pf 16] [--images 2]"""
+    python tools/bench_secure.py [--size 224] [--pf 16] [--images 2]
+    python tools/bench_secure.py --batch N [--size 224] [--pf 16] [--images 3]     the serving form on N images per pass only"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -12,6 +13,9 @@ def main():
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--pf", type=int, default=16)
     ap.add_argument("--images", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=0,
+                    help="time ONLY GraphedSecureInference(batch=N): ms per image online and with the dealer's refill included "
+                         "(--images passes each), the static primitive bytes and the largest batch the card admits")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
     ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph replay of the online phase")
     ap.add_argument("--only-fss-roofline", action="store_true",
@@ -137,6 +141,35 @@ def main():
         rec["valu_pmc"] = pmc
         return rec
 
+
+    if a.batch:
+        from primia_amd.secure import GraphedSecureInference, architecture_of, largest_batch_that_fits
+
+        B, reps = a.batch, max(a.images, 3)
+        imgs = torch.randn(B, 3, a.size, a.size, generator=g).to(dev)
+        free = torch.cuda.mem_get_info(dev)[0]
+        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B)
+        gi(imgs, refill=False); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            gi(imgs, refill=False)
+        torch.cuda.synchronize()
+        online = (time.perf_counter() - t0) / reps * 1e3
+        gi(imgs); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            gi(imgs)                    # the dealer's refill graph, then the online graph, on one stream
+        torch.cuda.synchronize()
+        both = (time.perf_counter() - t0) / reps * 1e3
+        print(json.dumps({"metric": "encrypted_inference_batch", "batch": B, "size": a.size, "precision_fractional": a.pf,
+                          "online_ms_per_image": round(online / B, 2), "with_refill_ms_per_image": round(both / B, 2),
+                          "online_ms_per_pass": round(online, 2), "with_refill_ms_per_pass": round(both, 2),
+                          "static_primitive_bytes": gi.static_bytes, "arena_mb": round(gi._arena.numel() * 8 / 1e6, 1),
+                          "device_free_bytes_before": free,
+                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free),
+                          "dif_evals": gi.stats["dif_evals"], "beaver_matmul": gi.stats["beaver_matmul"],
+                          "beaver_mul": gi.stats["beaver_mul"]}))
+        return
 
     if a.only_fss_roofline:
         d = Dealer(dev, seed=3)
