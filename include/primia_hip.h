@@ -898,6 +898,13 @@ int primia_rows_to_nchw(const int64_t* rows, int64_t* out, int B, int C, int HW,
 /* _pre_pool (nn/functional.py:311-393): x [B,C,H,W] -> [B, C, Ho*Wo, k*k], zero padding. */
 int primia_pool_unroll_syft(const int64_t* x, int64_t* out, int B, int C, int H, int W, int k,
                             int stride, int pad, primia_stream_t stream);
+/* _pool2d(mode="avg") of ONE party's share (nn/functional.py:460-525: _pre_pool, the window sum and the per-share
+ * truncating division of AST.mean, additive_shared.py:719-729), read in place: x [B,C,H,W] -> out [B,C,Ho,Wo],
+ * out = primia_trunc_div(wrapping int64 sum of the k*k window, k*k) with zero padding -- the divisor is k*k for border
+ * windows too (count_include_pad).  Bit-identical to primia_pool_unroll_syft -> primia_ring_rowsum -> primia_trunc_div
+ * without the [rows, k*k] intermediate.  pad < k, Ho = (H + 2 pad - k) / stride + 1 >= 1 (Wo alike); out of place. */
+int primia_avg_pool_syft(const int64_t* x, int64_t* out, int B, int C, int H, int W, int k, int stride, int pad,
+                         primia_stream_t stream);
 
 /* FixedPrecisionTensor.reciprocal(method="newton") (precision.py:507-518: C = 20, 80 steps — what eval-mode
  * batch_norm calls on running_var, nn/functional.py:62) when BOTH parties' shares live in this process: the whole
@@ -927,6 +934,7 @@ int primia_newton_reciprocal_local(const int64_t* v0, const int64_t* v1, const i
  *   primia_bn_eval_local_batch   the same for a batch (the reference's batch_norm on [B,C,H,W]): x / out [B][C][HW], the
  *                                triples' rows side [B*HW, C] with row b*HW + p, i.e. x.permute(1,0,2,3).reshape(C,-1).t()
  *   primia_im2col_syft_2p, primia_pool_unroll_syft_2p   the PySyft layouts of both shares
+ *   primia_avg_pool_syft_2p      primia_avg_pool_syft on both parties' shares (nothing is opened: a party-local step)
  *   primia_beaver_matmul_local   spdz_mul "matmul": both opens, then z_j = c_j + delta @ (b_j [+ eps]) + a_j @ eps for
  *                                both parties in one grid; scratch = primia_beaver_matmul_local_scratch_elems int64
  *   primia_trunc_col2out_2p      each party's truncation of its product share + conv2d's output re-layout (+ bias) */
@@ -965,6 +973,8 @@ int primia_trunc_col2out_2p(const int64_t* res0, const int64_t* res1, const int6
                             int64_t* out0, int64_t* out1, int B, int HoWo, int O, int64_t div, primia_stream_t stream);
 int primia_pool_unroll_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* out0, int64_t* out1, int B, int C, int H, int W,
                                int k, int stride, int pad, primia_stream_t stream);
+int primia_avg_pool_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* out0, int64_t* out1, int B, int C, int H, int W,
+                            int k, int stride, int pad, primia_stream_t stream);
 /* spdz_compute (mpc/spdz.py:63-122), party j in {0,1}:
  *   mul   : z = delta*b + a*eps + c (+ delta*eps if j == 0), element-wise; b / eps hold nb
  *           elements and broadcast over the leading dims when nb < n;

@@ -7,7 +7,8 @@
 Plain inference runs the HIP engine in eval mode.  `--encrypted_inference` shares the model and
 each image between model_owner and data_owner (fixed precision 10^16, protocol "fss", a dealer as
 crypto provider) and runs the secret-shared forward of primia_amd.secure, image by image like the
-reference's loop, or `--batch_size N` images per protocol pass.  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
+reference's loop, or `--batch_size N` images per protocol pass; the checkpoint's `pooling_type` (max | avg) decides the stem pool
+of the plain and of every encrypted form.  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
 """
 import argparse
 import json
@@ -113,6 +114,7 @@ if __name__ == "__main__":
     bs = cmd_args.batch_size
     if bs < 1:
         raise SystemExit("--batch_size must be at least 1")
+    pooling = getattr(args, "pooling_type", "max")
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
         if cmd_args.three_role:
@@ -132,7 +134,7 @@ if __name__ == "__main__":
                                     state_dict=sd if link.role == 0 else None,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
-                                    precision_fractional=cmd_args.precision_fractional)
+                                    precision_fractional=cmd_args.precision_fractional, pooling=pooling)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
@@ -144,11 +146,11 @@ if __name__ == "__main__":
             from primia_amd.secure import GraphedSecureInference
 
             model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
-                                           seed=cmd_args.debug_dealer_seed, batch=bs)
+                                           seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling)
         else:
             ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed), base=10,
                                 precision_fractional=cmd_args.precision_fractional)
-            model = SecureResNet18(ctx, sd, input_size=size)
+            model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling)
         logits = []
         for i in range(0, 0 if cmd_args.three_role else images.shape[0], bs):
             out = model(images[i:i + bs]).clone()     # (the graphed form returns its static output buffer: keep a copy)
@@ -158,7 +160,7 @@ if __name__ == "__main__":
             torch.save(torch.cat(logits).cpu(), os.environ["PRIMIA_DUMP_LOGITS"])
     else:
         eng = ResNet18Engine(1, sd["fc.weight"].shape[0], sd["conv1.weight"].shape[1], size,
-                             getattr(args, "pooling_type", "max"), dtype=torch.float32, device=device)
+                             pooling, dtype=torch.float32, device=device)
         eng.load_state_dict(sd)
         eng.eval()
         for i in range(images.shape[0]):

@@ -205,6 +205,28 @@ __device__ __forceinline__ int64_t trunc_div1(int64_t v, u64 d) {
     return v < 0 ? (int64_t)((u64)0 - q) : (int64_t)q;
 }
 
+// _pool2d(mode="avg") of one share without the [rows, k*k] unrolled intermediate (pool_unroll_kernel -> ring_rowsum_kernel ->
+// trunc_div_kernel): out[t][ho][wo] = trunc(sum_{r,s < k} xpad[t][ho*stride + r][wo*stride + s], k*k), t = b*C + c.  The sum
+// wraps mod 2^64 (its order is immaterial), padding contributes zero and the divisor is k*k for every window.  One thread
+// per output element: neighbouring lanes read neighbouring (overlapping) windows of the same input rows.
+__global__ __launch_bounds__(256) void avg_pool_kernel(const u64* __restrict__ x, u64* __restrict__ out, long total, int H,
+                                                       int W, int k, int stride, int pad, int Ho, int Wo) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int wo = (int)(i % Wo);
+    long t = i / Wo;
+    const int ho = (int)(t % Ho);
+    t /= Ho;  // t = b*C + c
+    const int h0 = ho * stride - pad, w0 = wo * stride - pad;
+    const int r0 = h0 < 0 ? -h0 : 0, r1 = h0 + k > H ? H - h0 : k;
+    const int s0 = w0 < 0 ? -w0 : 0, s1 = w0 + k > W ? W - w0 : k;
+    const u64* plane = x + t * H * W;
+    u64 sum = 0;
+    for (int r = r0; r < r1; ++r)
+        for (int s = s0; s < s1; ++s) sum += plane[(long)(h0 + r) * W + (w0 + s)];
+    out[i] = (u64)trunc_div1((int64_t)sum, (u64)k * k);
+}
+
 __global__ __launch_bounds__(64) void newton_local_kernel(const u64* __restrict__ v0, const u64* __restrict__ v1,
                                                           const u64* const* __restrict__ prim, u64 scale,
                                                           u64* __restrict__ x0o, u64* __restrict__ x1o, long n) {
@@ -465,6 +487,18 @@ int primia_pool_unroll_syft(const int64_t* x, int64_t* out, int B, int C, int H,
     const long total = (long)B * C * Ho * Wo * k * k;
     pool_unroll_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)st>>>((const u64*)x, (u64*)out, B, C, H, W, k,
                                                                            stride, pad, Ho, Wo);
+    return launch_status();
+}
+
+int primia_avg_pool_syft(const int64_t* x, int64_t* out, int B, int C, int H, int W, int k, int stride, int pad,
+                         primia_stream_t st) {
+    PRIMIA_REQUIRE(x && out && x != out && B > 0 && C > 0 && H > 0 && W > 0 && k > 0 && stride > 0 && pad >= 0 && pad < k);
+    PRIMIA_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    const long total = (long)B * C * Ho * Wo;
+    PRIMIA_REQUIRE(total <= 256L * 0x7fffffffL);
+    avg_pool_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)st>>>((const u64*)x, (u64*)out, total, H, W, k, stride,
+                                                                        pad, Ho, Wo);
     return launch_status();
 }
 

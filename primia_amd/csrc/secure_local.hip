@@ -330,6 +330,31 @@ __global__ __launch_bounds__(256) void pool_unroll_2p_kernel(Pair x, OutPair out
     out.p1[i] = v1;
 }
 
+// _pool2d(mode="avg") of both parties' shares, read in place (avg_pool_kernel, ring.hip): each party's wrapping window sum
+// with zero padding and ITS truncating division by k*k (AST.mean) -- no comparison, no Beaver product, nothing opened
+__global__ __launch_bounds__(256) void avg_pool_2p_kernel(Pair x, OutPair out, long total, int H, int W, int k, int stride,
+                                                          int pad, int Ho, int Wo) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int wo = (int)(i % Wo);
+    long t = i / Wo;
+    const int ho = (int)(t % Ho);
+    t /= Ho;  // t = b*C + c
+    const int h0 = ho * stride - pad, w0 = wo * stride - pad;
+    const int r0 = h0 < 0 ? -h0 : 0, r1 = h0 + k > H ? H - h0 : k;
+    const int s0 = w0 < 0 ? -w0 : 0, s1 = w0 + k > W ? W - w0 : k;
+    const long plane = t * H * W;
+    u64 sum0 = 0, sum1 = 0;
+    for (int r = r0; r < r1; ++r)
+        for (int s = s0; s < s1; ++s) {
+            const long src = plane + (long)(h0 + r) * W + (w0 + s);
+            sum0 += x.p0[src];
+            sum1 += x.p1[src];
+        }
+    out.p0[i] = sl_trunc(sum0, (u64)k * k);
+    out.p1[i] = sl_trunc(sum1, (u64)k * k);
+}
+
 static inline int sl_blocks(long n) {
     long b = (n + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -477,6 +502,20 @@ int primia_pool_unroll_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* ou
     const long total = (long)B * C * Ho * Wo * k * k;
     pool_unroll_2p_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)st>>>(Pair{U(x0), U(x1)}, OutPair{(u64*)out0, (u64*)out1},
                                                                               B, C, H, W, k, stride, pad, Ho, Wo);
+    return launch_status();
+}
+
+int primia_avg_pool_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* out0, int64_t* out1, int B, int C, int H, int W, int k,
+                            int stride, int pad, primia_stream_t st) {
+    PRIMIA_REQUIRE(x0 && x1 && out0 && out1 && out0 != out1 && B > 0 && C > 0 && H > 0 && W > 0 && k > 0 && stride > 0 &&
+                   pad >= 0 && pad < k);
+    PRIMIA_REQUIRE(x0 != out0 && x0 != out1 && x1 != out0 && x1 != out1);
+    PRIMIA_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k);
+    const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+    const long total = (long)B * C * Ho * Wo;
+    PRIMIA_REQUIRE(total <= 256L * 0x7fffffffL);
+    avg_pool_2p_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)st>>>(Pair{U(x0), U(x1)}, OutPair{(u64*)out0, (u64*)out1},
+                                                                           total, H, W, k, stride, pad, Ho, Wo);
     return launch_status();
 }
 

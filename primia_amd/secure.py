@@ -709,6 +709,27 @@ class SecureContext:
 
         return self._each(one)
 
+    def avg_pool2d_3x3s2(self, x):
+        """_pool2d(mode="avg") for AvgPool2d(3, 2, 1), the stem pool of a network trained with pooling_type = avg
+        (nn/functional.py:460-525): zero padding of the shares, per-share window sum, then the per-share truncating
+        division of AST.mean by 9 for every window, border windows included (count_include_pad, torch's default).  Party
+        local -- no comparison, no Beaver product, nothing from the dealer -- and read in place: one launch, no
+        [rows, 9] intermediate; bit-identical to the unroll / rowsum / trunc_div chain of `avg_pool2d`."""
+        B, C, H, W = self._ref(x).shape
+        Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+        if self._local:
+            dev = x[0].device
+            out = [torch.empty(B, C, Ho, Wo, dtype=I64, device=dev), torch.empty(B, C, Ho, Wo, dtype=I64, device=dev)]
+            call("primia_avg_pool_syft_2p", x[0], x[1], out[0], out[1], B, C, H, W, 3, 2, 1)
+            return out
+
+        def one(j):
+            o = torch.empty(B, C, Ho, Wo, dtype=I64, device=x[j].device)
+            call("primia_avg_pool_syft", x[j], o, B, C, H, W, 3, 2, 1)
+            return o
+
+        return self._each(one)
+
     def linear(self, x, w, b):
         """F.linear -> torch.addmm(bias, input, weight.t()) -> FPT.addmm (nn/functional.py:10-14,
         precision.py:822-827): matmul + truncation, then + bias."""
@@ -724,6 +745,16 @@ class SecureContext:
         return self.add(self.fpt_matmul(x, self._each(tr)), b)
 
 
+POOLINGS = ("max", "avg")
+
+
+def _check_pooling(pooling):
+    """The stem pool a checkpoint was trained with (train.py's pooling_type)."""
+    if pooling not in POOLINGS:
+        raise ValueError(f"pooling must be one of {POOLINGS}, got {pooling!r}")
+    return pooling
+
+
 def share_order(keys):
     """model.fix_precision().share() walks `parameters()` and then `buffers()` (hook.py:624-632,738-765)."""
     keys = [k for k in keys if not k.endswith("num_batches_tracked")]
@@ -734,15 +765,22 @@ def share_order(keys):
 class SecureResNet18:
     """ResNet-18 forward on secret shares — `model.fix_precision().share()` followed by
     `model(data)` in inference.py:279-321, including the stem swap `model.pool, model.relu =
-    model.relu, model.pool` (:289): conv1 -> bn1 -> MAXPOOL -> RELU."""
+    model.relu, model.pool` (:289): conv1 -> bn1 -> MAXPOOL -> RELU.
 
-    def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True):
+    pooling="avg" serves a checkpoint trained with pooling_type = avg.  The reference's swap is an identity for a max pool
+    only (relu(avg(x)) != avg(relu(x))), so the avg stem keeps the order the network was trained with,
+    conv1 -> bn1 -> RELU -> AvgPool2d(3, 2, 1), with zero padding and the divisor 9 for every window: it decodes to the
+    model the checkpoint holds.  This stem is NOT pinned against the reference (whose behaviour for this case has not been
+    checked); it follows the plaintext model."""
+
+    def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max"):
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
         default hoists the image-independent iterations of all BatchNorm layers into one batched vector."""
         self.ctx = ctx
         self.input_size = input_size
         self.batched_newton = batched_newton
+        self.pooling = _check_pooling(pooling)
         dev = ctx.dealer.device
         self.p = {}
         ctx.invalidate_weight_cache()      # (a model shared on this context before: its transposed shares go with it)
@@ -814,8 +852,11 @@ class SecureResNet18:
         self._inv = self.precompute_inv() if self.batched_newton else {n: None for n in self.bn_prefixes()}
         x = c.conv2d(x, p["conv1.weight"], 2, 3)
         x = self._bn(x, "bn1")
-        x = c.max_pool2d_3x3s2(x)      # swapped stem (inference.py:289)
-        x = c.relu(x)
+        if self.pooling == "max":
+            x = c.max_pool2d_3x3s2(x)      # swapped stem (inference.py:289)
+            x = c.relu(x)
+        else:
+            x = c.avg_pool2d_3x3s2(c.relu(x))      # the plaintext order: the swap is an identity for a max pool only
         for prefix, stride in self.blocks:
             identity = x
             out = c.conv2d(x, p[prefix + ".conv1.weight"], stride, 1)
@@ -850,12 +891,15 @@ def _default_blocks():
     return [(f"layer{li}.{bi}", (2 if (li > 1 and bi == 0) else 1)) for li in range(1, 5) for bi in range(2)]
 
 
-def image_requests(arch, input_size, batch=1, blocks=None):
+def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
     """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
     `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
     what `SecureResNet18.__call__` asks for (tests hold the two equal), so that the memory a serving form needs is known
     BEFORE anything is allocated.  Per batch, not per image: the 80-step Newton reciprocal (237 triples over all BatchNorm
-    channels) and the weight side of every matmul triple; per image: everything with a row of its own."""
+    channels) and the weight side of every matmul triple; per image: everything with a row of its own.
+    pooling="avg": the stem is one ReLU at conv1's output resolution and a party-local average pool that requests nothing
+    (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree)."""
+    _check_pooling(pooling)
     B, req = int(batch), []
     blocks = _default_blocks() if blocks is None else blocks
     triple = lambda op, xs, ys: req.append(("triple", (op, tuple(xs), tuple(ys)), {}))
@@ -892,12 +936,16 @@ def image_requests(arch, input_size, batch=1, blocks=None):
 
     c, h = conv("conv1", input_size, 2, 3)
     bn(c, h)
-    h = out_hw(h, 3, 2, 1)
-    rows = B * c * h * h
-    for length in (4, 2, 1, 1):                                                # the 9-window max tree
-        req.append(("dif_keys", (rows * length,), {}))
-        triple("mul", (rows, length), (rows, length))
-    relu(c, h)
+    if pooling == "avg":
+        relu(c, h)                                                             # ReLU first, then the pool: no primitives
+        h = out_hw(h, 3, 2, 1)
+    else:
+        h = out_hw(h, 3, 2, 1)
+        rows = B * c * h * h
+        for length in (4, 2, 1, 1):                                            # the 9-window max tree
+            req.append(("dif_keys", (rows * length,), {}))
+            triple("mul", (rows, length), (rows, length))
+        relu(c, h)
     for prefix, stride in blocks:
         o, ho = conv(prefix + ".conv1", h, stride, 1)
         bn(o, ho)
@@ -934,20 +982,20 @@ def primitive_bytes(requests):
     return total
 
 
-def serving_bytes(arch, input_size, batch, blocks=None):
+def serving_bytes(arch, input_size, batch, blocks=None, pooling="max"):
     """What GraphedSecureInference(batch=...) holds in static buffers: every primitive of one pass (dominated by the DIF
-    keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image) plus one eighth on top for the arena copy of
+    keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image, 2,308,096 with pooling="avg") plus one eighth on top for the arena copy of
     their random words while both exist (5/6 of a triple, 48 of a key's 1,244 bytes) and the captured graph's activations
     (im2col and pool-unroll operands: under 2 % of the keys at every layer)."""
-    b = primitive_bytes(image_requests(arch, input_size, batch, blocks))
+    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling))
     return b + b // 8
 
 
-def largest_batch_that_fits(arch, input_size, budget, blocks=None):
+def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max"):
     """The largest batch whose static buffers fit in `budget` bytes (0: not even one image).  serving_bytes is affine in the
     batch (a per-batch part, Newton and the weight masks, plus a per-image part) up to its rounding, so two evaluations
     give the answer and the neighbours settle the rounding."""
-    need = lambda k: serving_bytes(arch, input_size, k, blocks)
+    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling)
     one, two = need(1), need(2)
     per_image, fixed = two - one, 2 * one - two
     k = max(0, (int(budget) - fixed) // per_image)
@@ -983,18 +1031,19 @@ class GraphedSecureInference:
     refill_graph = True
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
-                 memory_budget=None):
+                 memory_budget=None, pooling="max"):
         self.device = torch.device(device)
         self.batch = int(batch)
+        self.pooling = _check_pooling(pooling)
         if self.batch < 1:
             raise ValueError("batch must be at least 1")
         arch = architecture_of(state_dict)
-        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks)
+        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling)
         if memory_budget is None:
             free, _ = torch.cuda.mem_get_info(self.device)
             memory_budget = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if self.static_bytes > memory_budget:
-            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks)
+            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling)
             raise ValueError(f"a batch of {self.batch} images at {input_size}x{input_size} needs {self.static_bytes} bytes of static "
                              f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
@@ -1002,7 +1051,7 @@ class GraphedSecureInference:
         self.dealer = Dealer(self.device, seed)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
-        model = SecureResNet18(ctx, state_dict, input_size, blocks)
+        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling)
         self._n_model = len(self.dealer.tape)          # primitives consumed by sharing the model (kept)
         model(self.image)                              # offline pass: fills the tape, warms every kernel
         self.tape, self.requests = self.dealer.tape, self.dealer.requests
@@ -1011,7 +1060,7 @@ class GraphedSecureInference:
         self._rehome_tape()                            # per-image random words -> one arena (before any pointer is captured)
         pre = PreloadedDealer(self.tape, self.device)
         self._ctx = SecureContext(pre, base, precision_fractional)
-        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks)   # re-shares with the same masks
+        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling)   # re-shares with the same masks
         self._model(self.image)                        # eager pass over the static buffers: builds the pointer tables
         pre.pos, self._ctx._newton_calls = self._n_model, 0
         side = torch.cuda.Stream(device=self.device)
@@ -1160,10 +1209,11 @@ class PipelinedSecureInference:
     In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU."""
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
-                 batch=1):
+                 batch=1, pooling="max"):
         self.device = torch.device(device)
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
-                                             None if seed is None else seed + 7919 * k, blocks, batch) for k in range(slots)]
+                                             None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling)
+                      for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
         # event: slot k's primitives are fresh.  None = fresh since construction: GraphedSecureInference ends its constructor
@@ -1287,15 +1337,15 @@ def architecture_of(state_dict):
     return {k: tuple(v.shape) for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
 
 
-def request_schedule(arch, input_size, device, blocks=None, precision_fractional=16, base=10, batch=1):
+def request_schedule(arch, input_size, device, blocks=None, precision_fractional=16, base=10, batch=1, pooling="max"):
     """The (public) sequence of primitives one model sharing + one encrypted forward of `batch` images consumes, as
-    (model_requests, image_requests): it depends on the architecture, the input size and the batch size only, so the
+    (model_requests, image_requests): it depends on the architecture, the input size, the batch size and the stem pool only, so the
     crypto provider derives it from a dry run on a dummy model of that architecture."""
     d = Dealer(device, seed=0)
     d.requests = []
     ctx = SecureContext(d, base, precision_fractional)
     dummy = {k: torch.ones(shape, dtype=torch.float32) for k, shape in arch.items()}
-    model = SecureResNet18(ctx, dummy, input_size, blocks)
+    model = SecureResNet18(ctx, dummy, input_size, blocks, pooling=pooling)
     n_model = len(d.requests)
     model(torch.zeros(batch, arch["conv1.weight"][1], input_size, input_size, dtype=torch.float32, device=device))
     return d.requests[:n_model], d.requests[n_model:]
@@ -1333,16 +1383,18 @@ def party_context(link: PartyLink, precision_fractional=16, base=10):
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10, batch=1):
+                   precision_fractional=16, base=10, batch=1, pooling="max"):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
-    all know the architecture, the input size, how many images will be classified and how many go through one
-    protocol pass (`batch`; the last pass is padded with all-zero images, whose rows are dropped).  Parties return the
+    all know the architecture, the input size, the stem pool (`pooling`), how many images will be classified and how many go
+    through one protocol pass (`batch`; the last pass is padded with all-zero images, whose rows are dropped).  Parties return the
     list of decoded logits, one [<= batch, classes] tensor per pass (the reference `.get()`s the prediction to the
     orchestrator), the dealer None."""
+    _check_pooling(pooling)
     passes = (n_images + batch - 1) // batch
     if link.role == "dealer":
-        model_req, image_req = request_schedule(arch, input_size, link.device, blocks, precision_fractional, base, batch)
+        model_req, image_req = request_schedule(arch, input_size, link.device, blocks, precision_fractional, base, batch,
+                                                pooling)
         svc = DealerService(Dealer(link.device, seed), link)
         svc.serve(model_req)
         for _ in range(passes):
@@ -1357,7 +1409,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         if images is None:
             raise ValueError("party 1 is the data owner: it needs the images")
         shapes = {k: torch.empty(shape, device="meta") for k, shape in arch.items()}
-    model = SecureResNet18(ctx, shapes, input_size, blocks)
+    model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling)
     out = []
     for i in range(0, n_images, batch):
         n = min(batch, n_images - i)

@@ -1,7 +1,8 @@
 """Encrypted-inference timing (BASELINE.json configs[4], all three roles on one GPU):
 ms/image for the online phase (primitives pre-provisioned) and for the dealer (triples + FSS keys).
     python tools/bench_secure.py [--size 224] [--pf 16] [--images 2]
-    python tools/bench_secure.py --batch N [--size 224] [--pf 16] [--images 3]     the serving form on N images per pass only"""
+    python tools/bench_secure.py --batch N [--size 224] [--pf 16] [--images 3]     the serving form on N images per pass only
+    --pooling avg: the stem of a checkpoint trained with pooling_type = avg (ReLU, then a party-local average pool)"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,6 +17,8 @@ def main():
     ap.add_argument("--batch", type=int, default=0,
                     help="time ONLY GraphedSecureInference(batch=N): ms per image online and with the dealer's refill included "
                          "(--images passes each), the static primitive bytes and the largest batch the card admits")
+    ap.add_argument("--pooling", choices=("max", "avg"), default="max",
+                    help="the stem pool of the served network (a checkpoint's pooling_type); the report names it when it is avg")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
     ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph replay of the online phase")
     ap.add_argument("--only-fss-roofline", action="store_true",
@@ -68,13 +71,15 @@ def main():
     cpu_t = cpu_sample_timings() if (a.cpu_sample and not a.only_fss_roofline) else None   # before the first GPU call
     dev = torch.device("cuda:0")
     torch.manual_seed(42)
-    sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, "max"))
+    sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, a.pooling))
+    # (the report of the default keeps its keys: "pooling" appears for avg only)
+    pool_kw = {} if a.pooling == "max" else {"pooling": a.pooling}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
     def run(dealer, share_model=True):
         ctx = SecureContext(dealer, 10, a.pf)
-        model = SecureResNet18(ctx, sd, input_size=a.size)
+        model = SecureResNet18(ctx, sd, input_size=a.size, **pool_kw)
         torch.cuda.synchronize(); t0 = time.perf_counter()
         out = model(img)
         torch.cuda.synchronize()
@@ -148,7 +153,7 @@ def main():
         B, reps = a.batch, max(a.images, 3)
         imgs = torch.randn(B, 3, a.size, a.size, generator=g).to(dev)
         free = torch.cuda.mem_get_info(dev)[0]
-        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B)
+        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw)
         gi(imgs, refill=False); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(reps):
@@ -161,12 +166,12 @@ def main():
             gi(imgs)                    # the dealer's refill graph, then the online graph, on one stream
         torch.cuda.synchronize()
         both = (time.perf_counter() - t0) / reps * 1e3
-        print(json.dumps({"metric": "encrypted_inference_batch", "batch": B, "size": a.size, "precision_fractional": a.pf,
+        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
                           "online_ms_per_image": round(online / B, 2), "with_refill_ms_per_image": round(both / B, 2),
                           "online_ms_per_pass": round(online, 2), "with_refill_ms_per_pass": round(both, 2),
                           "static_primitive_bytes": gi.static_bytes, "arena_mb": round(gi._arena.numel() * 8 / 1e6, 1),
                           "device_free_bytes_before": free,
-                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free),
+                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw),
                           "dif_evals": gi.stats["dif_evals"], "beaver_matmul": gi.stats["beaver_matmul"],
                           "beaver_mul": gi.stats["beaver_mul"]}))
         return
@@ -198,9 +203,9 @@ def main():
         try:
             from primia_amd.secure import GraphedSecureInference
 
-            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999)
+            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, **pool_kw)
             ctx_e = SecureContext(PreloadedDealer(gi.tape, dev), 10, a.pf)
-            out_ref = SecureResNet18(ctx_e, sd, input_size=a.size)(img)
+            out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, **pool_kw)(img)
             assert torch.equal(gi(img, refill=False).cpu(), out_ref.cpu()), "graph replay must be bit-identical"
             torch.cuda.synchronize(); t0 = time.perf_counter()
             for _ in range(3):
@@ -221,7 +226,7 @@ def main():
             # on its own stream while the other replays): wall time per image, every image on fresh primitives
             from primia_amd.secure import PipelinedSecureInference
 
-            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555)
+            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, **pool_kw)
             for _ in range(2):
                 pi(img)
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -249,7 +254,7 @@ def main():
 
     extra = {"cpu_baseline": cpu_sample_report(cpu_t, ctx.stats["dif_evals"])} if cpu_t else {}
     extra["roofline"] = fss_roofline()
-    print(json.dumps({"metric": "encrypted_inference_ms_per_image", "online_ms": round(to * 1e3, 1),
+    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, "online_ms": round(to * 1e3, 1),
                       "online_graph_ms": None if graph_ms is None else round(graph_ms, 1),
                       "dealer_refill_ms": None if refill_ms is None else round(refill_ms, 1),
                       "dealer_refill_launches": refill_nodes, "dealer_keystream_mb_per_image": None if arena_mb is None else round(arena_mb, 1),
