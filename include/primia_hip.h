@@ -712,6 +712,22 @@ int primia_fc_persample_grads(const float* x, const float* dy, float* ps, int N,
 /* g = (g + noise * sigma) * inv_batch — the Gaussian mechanism on the summed clipped gradient. */
 int primia_dp_add_noise(float* g, const float* noise, int64_t n, float sigma, float inv_batch,
                         primia_stream_t stream);
+/* The same update with the noise drawn in registers from the ChaCha20 keystream of primia_chacha20_fill (key, nonce and
+ * state layout are that kernel's): g[i] = (g[i] + sigma * z[i]) * inv_batch, z never written to memory.  Replaces
+ * torch.randn, a Philox generator seeded from the command line: the Gaussian mechanism's guarantee rests on z being
+ * unpredictable.  The noise is defined by this arithmetic: element i lives in block B = (counter ? *counter : 0) +
+ * block_offset + i / 16 with output words x[0..15]; for p = (i % 16) / 2, a = x[2p], c = x[2p + 1] (the low and high half of
+ * keystream word 8B + p as primia_chacha20_fill lays it out), u1 = ((a >> 8) + 1) * 2^-24 in (0, 1], u2 = (c >> 8) * 2^-24
+ * in [0, 1), r = sqrtf(-2 logf(u1)); the even i of the pair gets r * cos(2 pi u2), the odd i r * sin(2 pi u2), in precise
+ * float32.  24-bit uniforms truncate the tail at sqrt(48 ln 2) = 5.77 standard deviations: the same class as the float
+ * generator this replaces, and no claim about floating-point attacks on the Gaussian mechanism.
+ * `counter` (a device word, may be NULL: block_offset is then the absolute block) is read, not advanced: the caller follows
+ * with primia_u64_add(counter, primia_dp_noise_blocks(n)), so a captured step draws fresh noise at every replay.  Two calls
+ * must never cover the same blocks under one key and nonce.  n == 0 is a no-op; PRIMIA_ERR_ARG for n < 0, a NULL g or a
+ * g that is not 16-byte aligned (n itself may be ragged: a partial last block uses its first n % 16 values). */
+int primia_dp_noise_add(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce, const uint64_t* counter,
+                        uint64_t block_offset, float* g, int64_t n, float sigma, float inv_batch, primia_stream_t stream);
+int64_t primia_dp_noise_blocks(int64_t n);     /* ceil(n / 16): the blocks a call on n elements draws */
 
 /* ------------------------------------------------------------------------------------------
  * Pooling — replaces F.max_pool2d(3,2,1) / F.avg_pool2d(3,2,1) (torchlib/models.py:384-389)

@@ -1,0 +1,82 @@
+// DP-SGD's Gaussian mechanism drawn from the ChaCha20 keystream and applied to the gradient in one pass:
+//     g[i] = (g[i] + sigma * z[i]) * inv_batch,   z ~ N(0, 1), never written to memory.
+//
+// The pair it replaces (torch.randn + primia_dp_add_noise) draws z from a Philox generator seeded by the command line;
+// the privacy guarantee of the Gaussian mechanism rests on z being unpredictable, exactly as additive sharing rests on
+// the provider's masks (chacha.hip), so z comes from the same cipher under a key from the operating system's entropy pool.
+//
+// The noise is DEFINED by this arithmetic (tests/dp_noise_ref.py is its float64 form):
+//   element i lives in ChaCha20 block B = (counter ? *counter : 0) + block_offset + i / 16, output words x[0..15];
+//   for p = (i % 16) / 2:  a = x[2p], c = x[2p + 1]   (low / high half of 64-bit keystream word 8B + p)
+//     u1 = ((a >> 8) + 1) * 2^-24 in (0, 1],   u2 = (c >> 8) * 2^-24 in [0, 1),   r = sqrtf(-2 logf(u1))
+//     even i: r * cos(2 pi u2),   odd i: r * sin(2 pi u2)      (precise float32 functions; sincospif(2 u2) is exact
+//                                                               in its argument)
+// 24-bit uniforms truncate the tail at sqrt(-2 ln 2^-24) = sqrt(48 ln 2) = 5.77 standard deviations — the same class as the
+// float generator it replaces; not a statement about floating-point attacks on the Gaussian mechanism.
+//
+// One thread = one 64-byte block = 16 gradient elements, read and written as four 16-byte accesses; a workgroup covers
+// 4096 elements.  (The other mapping measured — four lanes per block, 16 bytes each, every lane computing the block —
+// is tools/micro/dp_noise_mapping.hip; profiles/dp_noise.txt has both.)
+#include "chacha_block.h"
+
+namespace primia {
+
+// Box-Muller on one 64-bit keystream word (a = low half, c = high half)
+__device__ __forceinline__ void dp_noise_pair(uint32_t a, uint32_t c, float& z_even, float& z_odd) {
+    const float u1 = (float)((a >> 8) + 1u) * 0x1p-24f;      // integers <= 2^24: both conversions are exact
+    const float u2 = (float)(c >> 8) * 0x1p-24f;
+    const float r = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincospif(2.0f * u2, &sn, &cs);
+    z_even = r * cs;
+    z_odd = r * sn;
+}
+
+__global__ __launch_bounds__(256) void dp_noise_add_kernel(ChaChaKey key, uint64_t block0, const uint64_t* __restrict__ counter,
+                                                           float* __restrict__ g, int64_t n, float sigma, float inv_b) {
+    const int64_t blk = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (blk * 16 >= n) return;
+    float* o = g + blk * 16;
+    const bool full = blk * 16 + 16 <= n;
+    f32x4 v[4];
+    if (full) {     // issued before the 20 rounds: their latency hides behind the integer work
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = *(const f32x4*)(o + 4 * i);
+    }
+    const uint64_t ctr = block0 + (counter ? *counter : 0) + (uint64_t)blk;
+    uint32_t x[16];
+    chacha20_block(key, ctr, x);
+    float z[16];
+#pragma unroll
+    for (int p = 0; p < 8; ++p) dp_noise_pair(x[2 * p], x[2 * p + 1], z[2 * p], z[2 * p + 1]);
+    if (full) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] + z[4 * i + j] * sigma) * inv_b;
+            *(f32x4*)(o + 4 * i) = v[i];
+        }
+    } else {        // the partial last block: its first n % 16 values
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (blk * 16 + i < n) o[i] = (o[i] + z[i] * sigma) * inv_b;
+    }
+}
+
+}  // namespace primia
+
+using namespace primia;
+
+extern "C" int64_t primia_dp_noise_blocks(int64_t n) { return n <= 0 ? 0 : (n + 15) / 16; }
+
+extern "C" int primia_dp_noise_add(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce,
+                                   const uint64_t* counter, uint64_t block_offset, float* g, int64_t n, float sigma,
+                                   float inv_batch, primia_stream_t st) {
+    if (n == 0) return PRIMIA_OK;  // empty input: no-op, pointers may be null
+    PRIMIA_REQUIRE(g && n > 0 && ((uintptr_t)g & 15) == 0);
+    const ChaChaKey key = chacha_key(k0, k1, k2, k3, nonce);
+    const int64_t blocks = primia_dp_noise_blocks(n);
+    dp_noise_add_kernel<<<ceil_div(blocks, 256), 256, 0, (hipStream_t)st>>>(key, block_offset, counter, g, n, sigma,
+                                                                            inv_batch);
+    return launch_status();
+}

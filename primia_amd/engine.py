@@ -391,7 +391,7 @@ class ResNet18Engine:
                                     groups=self.groups, options=self._root._options, share=self._root)
         # what the host sets on the root after construction travels with every call: the optimizer's fused tail and —
         # above all — the DP-SGD parameters (a halved or ragged batch must be clipped and noised like every other)
-        for attr in ("fuse_sgd_tail", "dp_params", "class_weight"):
+        for attr in ("fuse_sgd_tail", "dp_params", "dp_noise", "class_weight"):
             setattr(sib[n], attr, getattr(self._root, attr))
         sib[n].train(self.training)
         return sib[n]
@@ -627,6 +627,7 @@ class ResNet18Engine:
     # loss + backward
     # ------------------------------------------------------------------------------------------
     dp_params = None  # e.g. {"max_grad_norm": 1.0, "noise_multiplier": 1.3}: loss_backward() becomes DP-SGD
+    dp_noise = None   # a primia_amd.dp_noise.DeviceNoise: the DP-SGD noise is its ChaCha20 stream instead of torch.randn
 
     def loss_backward(self, target, soft=False):
         """Cross entropy (hard int64 labels, or soft [N, classes] fp32 targets as in
@@ -1144,7 +1145,8 @@ class ResNet18Engine:
         """Per-sample gradient clipping + Gaussian noise, pytorch-dp semantics:
             g = (1/B) * ( sum_n min(1, C / (||g_n|| + 1e-6)) * g_n  +  N(0, (noise_multiplier*C)^2 I) )
         with g_n the gradient of sample n's OWN loss over all 62 parameter tensors (flat L2 norm).
-        Needs norm="group".  `noise` (fp32 [P], standard normal) may be given for reproducibility.
+        Needs norm="group".  `noise` (fp32 [P], standard normal) may be given for reproducibility; without it (and without
+        a `generator`) the root engine's `dp_noise` stream is used when set, torch.randn otherwise.
 
         How: one ordinary backward pass yields every layer's activation gradient dy (samples are
         independent under GroupNorm).  Pass 1 runs the weight-gradient kernels with one pixel split per image
@@ -1293,9 +1295,14 @@ class ResNet18Engine:
             if getattr(self, "dp_keep_operands", False):      # tests: the (layer, x, dy) triples the norm pass walked
                 self.dp_operands = list(self.dp["wgrads"])
             self.dp = None
-        if noise is None:
-            noise = torch.randn(self.P, dtype=torch.float32, device=dev, generator=generator)
-        call("primia_dp_add_noise", self.grads, noise, self.P, float(noise_multiplier * max_grad_norm), 1.0 / N)
+        sigma = float(noise_multiplier * max_grad_norm)
+        if noise is None and generator is None and self._root.dp_noise is not None:
+            # the ROOT's stream, whichever sibling runs the step: a halved or ragged batch advances the one counter
+            self._root.dp_noise.add_to(self.grads, self.P, sigma, 1.0 / N)
+        else:
+            if noise is None:
+                noise = torch.randn(self.P, dtype=torch.float32, device=dev, generator=generator)
+            call("primia_dp_add_noise", self.grads, noise, self.P, sigma, 1.0 / N)
         self.dp_stats = {"sq_norms": sq, "clip": clip}
         return self.loss
 

@@ -18,7 +18,9 @@ the same capture on its fixed inputs).  What a training loop needs beyond bench.
 
 Graphs live on the engine they replay (the root engine or a `sibling()`, so that sibling eviction drops them with their
 buffers), keyed by batch size, soft targets, optimizer kind, fuse_sgd_tail and class-weight presence.  Only the root's
-batch size and MixUp's half batch are captured; other sizes (a loader's ragged last batch) and DP-SGD run eagerly.  The
+batch size and MixUp's half batch are captured; other sizes (a loader's ragged last batch) run eagerly, and so does DP-SGD
+unless its noise comes from a device stream (engine.dp_noise, primia_amd.dp_noise.DeviceNoise: the noise node reads the
+stream's device counter and the next node advances it, so every replay draws fresh noise).  The
 first step of a key runs eagerly (real training that also allocates the engine's lazy buffers), the second is captured
 and replayed.
 """
@@ -36,7 +38,8 @@ _dp_warned = False
 def eager_reason(engine, optimizer, batch_size):
     """Why a step of `batch_size` samples on `engine` runs eagerly under graphed_step, or None when it is graphed."""
     root = getattr(engine, "_root", engine)
-    if getattr(root, "dp_params", None) is not None:
+    if getattr(root, "dp_params", None) is not None and getattr(root, "dp_noise", None) is None:
+        # torch.randn's generator state is host-side; a DeviceNoise (engine.dp_noise) keeps its counter on the device
         return "DP-SGD runs eagerly: its noise draws have not been shown bit-identical between eager and graphed steps"
     if getattr(optimizer, "kind", None) not in ("SGD", "Adam"):
         return "not an EngineOptimizer"
@@ -57,7 +60,14 @@ def _eager(engine, eng, optimizer, data, target, soft):
 
 
 def _key(eng, optimizer, soft):
-    return (eng.N, bool(soft), optimizer.kind, bool(eng.fuse_sgd_tail), eng.class_weight is not None)
+    key = (eng.N, bool(soft), optimizer.kind, bool(eng.fuse_sgd_tail), eng.class_weight is not None)
+    root = eng._root
+    if getattr(root, "dp_params", None) is not None:
+        # the DP-SGD parameters are frozen into the graph as kernel arguments, and so is the noise stream's key
+        dp = root.dp_params
+        key += ("DP with device noise", float(dp.get("max_grad_norm", 1.0)), float(dp.get("noise_multiplier", 1.3)),
+                root.dp_noise.key_words + (root.dp_noise.nonce,))
+    return key
 
 
 def _sync_moments(root):
@@ -91,6 +101,8 @@ def _fingerprint(eng, g):
         ts += [c.w_fwd, c.w_dgrad]
     if eng.opt_state is not None:
         ts += list(eng.opt_state)
+    if getattr(eng._root, "dp_params", None) is not None:       # (the per-step DP buffers are the graph pool's own)
+        ts += [eng._root.dp_noise.counter] + list(eng._dp_keep_buffers().values())
     return tuple(t.data_ptr() if t is not None else 0 for t in ts) + (len(eng.relu_masks),)
 
 
@@ -105,6 +117,8 @@ class _StepGraph:
         self.hyper = torch.zeros(8, dtype=torch.float32, device=eng.device)
         if self.kind == "Adam":
             _sync_moments(root)
+        if getattr(root, "dp_noise", None) is not None:
+            root.dp_noise.counter       # exists BEFORE the capture: allocated inside, every replay would zero it again
         # capture runs the step's Python (forward / optimizer.step advance the host counters) without executing a kernel:
         # keep what one step advances them by, and put them back
         nbt = dict(eng.num_batches_tracked)
@@ -162,7 +176,7 @@ def graphed_step(engine, optimizer, data, target, soft=False):
     eng = engine if n == engine.N else engine.sibling(n)
     reason = eager_reason(engine, optimizer, n)
     if reason is not None:
-        if getattr(engine._root, "dp_params", None) is not None and not _dp_warned:
+        if reason.startswith("DP-SGD") and not _dp_warned:
             _dp_warned = True
             warnings.warn("hip_graph: " + reason, RuntimeWarning, stacklevel=2)
         return _eager(engine, eng, optimizer, data, target, soft)

@@ -6,7 +6,9 @@ lr 1e-4, weight decay 5e-4) on device-resident synthetic batches like train.py's
 The two modes run on two engines built from the same weights, alternating (eager, graph, eager, graph, ...), each run
 a train() call over `--steps` batches bracketed by device synchronisations; one untimed train() call per mode first
 (the graphed mode captures its step there).  Prints one JSON line: per mode the median and every run's ms per step and
-images per second.  Needs a GPU (there is no CPU path)."""
+images per second.  --dp times the DP-SGD loop (GroupNorm network, clip 1.0, noise multiplier 1.3: train.py with
+differentially_private = yes) with --dp_noise torch (torch.randn; --hip_graph leaves its steps eager) or chacha (the
+device ChaCha20 stream of primia_amd.dp_noise; --hip_graph replays the steps).  Needs a GPU (there is no CPU path)."""
 import argparse
 import json
 import os
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--buffers", type=int, default=4, help="distinct device batches the loader cycles through")
     ap.add_argument("--modes", default="eager,graph")
+    ap.add_argument("--dp", action="store_true", help="the DP-SGD loop (differentially_private = yes)")
+    ap.add_argument("--dp_noise", choices=("torch", "chacha"), default="torch", help="with --dp: train.py's --dp_noise")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_loop_bench needs a GPU")
@@ -47,8 +51,15 @@ def main():
     runs = {}
     for m in modes:
         torch.manual_seed(42)
-        eng = ResNet18Engine(a.batch, 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev)
+        eng = ResNet18Engine(a.batch, 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
+                             norm="group" if a.dp else "batch")
         eng.init_weights()
+        if a.dp:
+            eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": 1.3}
+            if a.dp_noise == "chacha":
+                from primia_amd.dp_noise import DeviceNoise
+
+                eng.dp_noise = DeviceNoise(dev)
         args = SimpleNamespace(optimizer="SGD", lr=1e-4, weight_decay=5e-4, log_interval=10 ** 9, mixup=False,
                                hip_graph=m == "graph")
         opt = EngineOptimizer.from_args(eng, args)
@@ -65,6 +76,11 @@ def main():
             ts.append((time.perf_counter() - t0) / a.steps * 1e3)
     out = {"metric": "train_loop", "batch": a.batch, "size": a.size, "dtype": "bf16", "optimizer": "SGD",
            "steps": a.steps, "runs": a.runs}
+    if a.dp:
+        from primia_amd.graphed_train import captures
+
+        out["dp_noise"] = a.dp_noise
+        out["graphed_keys"] = {m: len(captures(runs[m][0])) for m in modes}
     for m in modes:
         ts = runs[m][3]
         med = statistics.median(ts)

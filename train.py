@@ -5,7 +5,7 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
 
     python train.py --config configs/torch/pneumonia-resnet-pretrained.ini --train_federated \
         [--unencrypted_aggregation] [--data_dir DIR|synthetic] [--cuda] [--resume_checkpoint P] \
-        [--save_file F] [--training_name N] [--hip_graph]
+        [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -30,6 +30,7 @@ import configparser
 import os
 import random
 import shutil
+import sys
 from os import path
 from warnings import warn
 
@@ -229,13 +230,27 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                 args.data_dir))
         from primia_amd import imagefolder
 
-    def make_engine():
+    dp_noise_kind = getattr(cmd_args, "dp_noise", "torch") if cmd_args is not None else "torch"
+    dp_noise_seed = getattr(cmd_args, "debug_dp_noise_seed", None) if cmd_args is not None else None
+
+    if dp_noise_kind == "chacha" and not args.differentially_private:
+        warn("--dp_noise chacha has no effect: the config has differentially_private = no, no noise is applied")
+
+    def make_engine(client=None):
         # differentially_private = yes (train.py:304-334 of the reference): BatchNorm is rejected by the
         # PrivacyEngine, so the network is built with GroupNorm and every step clips / noises per sample
         eng = ResNet18Engine(args.batch_size, num_classes, channels, size, args.pooling_type,
                              dtype=dtype, device=device, norm="group" if args.differentially_private else "batch")
         if args.differentially_private:
             eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": 1.3}
+            if dp_noise_kind == "chacha":
+                # a key of its own from the OS entropy pool per engine; the nonce is the client index (the model that
+                # holds a federated run's aggregate never takes a step: it gets the last nonce; a vanilla run's one model
+                # has nonce 0 like federated client 0 — independent under OS keys, the SAME stream under a debug seed)
+                from primia_amd.dp_noise import DeviceNoise
+
+                nonce = client if client is not None else (2 ** 64 - 1 if args.train_federated else 0)
+                eng.dp_noise = DeviceNoise(device, nonce=nonce, debug_seed=dp_noise_seed)
         return eng
 
     local = make_engine()
@@ -262,7 +277,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             mine = list(workers)
         model = {"local_model": local}
         for w in mine:
-            model[w] = make_engine()
+            model[w] = make_engine(client=workers.index(w))
             model[w].load_state_dict(local.state_dict())
         train_loader, stats = {}, {}
         for w in mine:
@@ -414,6 +429,12 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         if verbose:
             print("Highest matthews coefficient was {:.1f}% in epoch {:d}".format(
                 best_score, (best + 1) * args.test_interval * (reps if args.train_federated else 1)))
+    if args.hip_graph and args.differentially_private and dp_noise_kind == "chacha" and rank == 0:
+        from primia_amd.graphed_train import captures
+
+        engines = [m for m in (model.values() if isinstance(model, dict) else [model]) if hasattr(m, "_root")]
+        n = sum(1 for e in engines for k in captures(e) if "DP with device noise" in k)
+        print("hip_graph: {:d} DP-SGD step graph(s) captured and replayed".format(n), file=sys.stderr)
     if world > 1:
         import torch.distributed as dist
 
@@ -438,7 +459,22 @@ if __name__ == "__main__":
     parser.add_argument("--hip_graph", action="store_true",
                         help="training: capture each training step once as a hipGraph and replay it per batch (the "
                              "learning rate and Adam's step reach the replay on the device; FedAvg runs between replays)")
+    parser.add_argument("--dp_noise", choices=("torch", "chacha"), default="torch",
+                        help="differentially_private = yes: where the Gaussian noise comes from.  torch: torch.randn, seeded "
+                             "by the config's seed (steps run eagerly under --hip_graph).  chacha: a ChaCha20 keystream on "
+                             "the device under a key from the OS entropy pool, applied to the gradient in one kernel; "
+                             "--hip_graph then replays the DP steps too.  The stream's counter is not checkpointed: a "
+                             "resumed run draws a new key.")
+    parser.add_argument("--debug_dp_noise_seed", type=int, default=None,
+                        help="derive the --dp_noise chacha key from this seed: a reproducible, PREDICTABLE noise stream "
+                             "that restarts from its beginning when a run is resumed, and is shared by a vanilla run and "
+                             "federated client 0 (tests only: no privacy)")
     cmd_args = parser.parse_args()
+    if cmd_args.debug_dp_noise_seed is not None:
+        if cmd_args.dp_noise != "chacha":
+            parser.error("--debug_dp_noise_seed needs --dp_noise chacha")
+        print("WARNING: --debug_dp_noise_seed makes the DP-SGD noise predictable: no differential privacy",
+              file=sys.stderr)
     config = configparser.ConfigParser()
     assert path.isfile(cmd_args.config), "Configuration file not found"
     config.read(cmd_args.config)
