@@ -991,6 +991,36 @@ int primia_pool_unroll_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* ou
                                int k, int stride, int pad, primia_stream_t stream);
 int primia_avg_pool_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* out0, int64_t* out1, int B, int C, int H, int W,
                             int k, int stride, int pad, primia_stream_t stream);
+/* GroupNorm(groups, C) on shares, both parties here (csrc/secure_gn.hip) -- the norm of the BatchNorm-free network of
+ * differentially private training.  The reference has NO secret-shared GroupNorm: the layer is defined from the
+ * reference's building blocks (AST.mean's per-share sum and truncating division, additive_shared.py:719-729; FPT mul,
+ * precision.py:309-316; reciprocal(method="newton"), precision.py:507-518; batch_norm's affine part,
+ * nn/functional.py:70-75) and held to a CPU composition of the oracle's methods, not to the reference.
+ * x [B, C, HW] is [R, m] with R = B * groups and m = (C / groups) * HW: a group is m contiguous elements.
+ *   primia_gn_moments_local   mean_j = trunc_div(row sum of x_j, m); Sq = FPT mul of (x - mean) with itself on the triple
+ *                             ("mul", (R, m), (R, m)), opens inside, each party truncating by `div`; var_j =
+ *                             trunc_div(row sum of Sq_j, m).  Bit-identical to the chain primia_ring_rowsum ->
+ *                             primia_trunc_div -> primia_ring_sub -> primia_fpt_mul_local -> primia_ring_rowsum ->
+ *                             primia_trunc_div (ring sums are exact in any order: a group of more than 1,024 elements is
+ *                             summed by several workgroups through `scratch`, int64
+ *                             [primia_gn_moments_local_scratch_elems(R, m)], which may be NULL when that is 0).
+ *   primia_gn_apply_local     out = FPT mul(rows(FPT mul(inv, (x - mean).T).T), weight) + bias, NCHW in, NCHW out, both
+ *                             transposes by indexing; mean / inv [R]; t1 / t2: HOST arrays of the two triples' six
+ *                             pointers (t1 = ("mul", (R,), (m, R)): a ~ inv, b, c ~ [m, R]; t2 = ("mul", (B*HW, C), (C,)):
+ *                             a, c ~ rows with row b*HW + p as in primia_bn_eval_local_batch, b ~ weight).  Bit-identical
+ *                             to primia_ring_sub -> primia_col2out_syft -> primia_fpt_mul_local -> primia_col2out_syft
+ *                             -> primia_nchw_to_rows -> primia_fpt_mul_local -> primia_ring_add -> primia_rows_to_nchw.
+ *                             C % groups != 0: PRIMIA_ERR_UNSUPPORTED.
+ * Between the two: var + eps (a re-shared constant) and primia_newton_reciprocal_local on the R variances. */
+int64_t primia_gn_moments_local_scratch_elems(int64_t R, int64_t m);
+int primia_gn_moments_local(const int64_t* x0, const int64_t* x1, const int64_t* a0, const int64_t* b0, const int64_t* c0,
+                            const int64_t* a1, const int64_t* b1, const int64_t* c1, int64_t* mean0, int64_t* mean1,
+                            int64_t* var0, int64_t* var1, int64_t* scratch, int64_t R, int64_t m, int64_t div,
+                            primia_stream_t stream);
+int primia_gn_apply_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1, const int64_t* inv0,
+                          const int64_t* inv1, const int64_t* w0, const int64_t* w1, const int64_t* bias0, const int64_t* bias1,
+                          const int64_t* const* t1, const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW,
+                          int groups, int64_t div, primia_stream_t stream);
 /* spdz_compute (mpc/spdz.py:63-122), party j in {0,1}:
  *   mul   : z = delta*b + a*eps + c (+ delta*eps if j == 0), element-wise; b / eps hold nb
  *           elements and broadcast over the leading dims when nb < n;

@@ -663,6 +663,97 @@ class SecureContext:
 
         return self._each(back)
 
+    def group_norm(self, x, weight, bias, groups=32):
+        """GroupNorm(groups, C) on shares [B, C, H, W] -- the norm of the BatchNorm-free network that differentially private
+        training builds.  The reference has no secret-shared GroupNorm: this layer is DEFINED here from the reference's
+        building blocks and is not pinned against the reference.  With X_j = x_j.reshape(R, m), R = B * groups
+        and m = (C / groups) * H * W (a group is m contiguous elements of NCHW):
+          mean = trunc_div(row sum of X_j, m)          per share, as AST.mean (additive_shared.py:719-729)
+          Xc   = X - mean[:, None]                     party local
+          var  = trunc_div(row sum of fpt_mul(Xc, Xc)_j, m)         triple ("mul", (R, m), (R, m))
+          inv  = reciprocal_newton(var + eps)          eps = fix_encode(1e-5), a re-shared constant; per layer: it depends
+                                                       on the image (batch_norm's does not and is hoisted)
+          N    = fpt_mul(inv, Xc.T).T                  triple ("mul", (R,), (m, R))
+          out  = fpt_mul(rows(N), weight) + bias       rows [B*H*W, C], exactly batch_norm_eval's affine part
+        The Newton iteration approximates v^-1/2 to under 1 % for v in about [0.05, 16]: group variances outside that range
+        are normalised wrongly (1.6 % at 0.01, 15 % at 0.001).
+        Both parties here: two fused launches around the Newton launch (primia_gn_moments_local, primia_gn_apply_local);
+        otherwise the step-by-step chain, which a three-role run executes -- same dealer requests, same bits."""
+        B, C, H, W = self._ref(x).shape
+        groups = int(groups)
+        if groups < 1 or C % groups != 0:
+            raise ValueError(f"group_norm: {C} channels do not divide into {groups} groups")
+        R, m, HW = B * groups, (C // groups) * H * W, H * W
+        eps_q = _eps_q(self.base, self.pf)
+        if self._local:
+            import ctypes
+
+            dev = x[0].device
+            x = [x[0].contiguous(), x[1].contiguous()]
+            ts = self.dealer.triple("mul", (R, m), (R, m))           # fpt_mul(Xc, Xc)
+            mean = [torch.empty(R, dtype=I64, device=dev) for _ in range(2)]
+            var = [torch.empty(R, dtype=I64, device=dev) for _ in range(2)]
+            n_scratch = _lib.query("primia_gn_moments_local_scratch_elems", R, m)
+            scratch = torch.empty(n_scratch, dtype=I64, device=dev) if n_scratch > 0 else None
+            call("primia_gn_moments_local", x[0], x[1], ts[0][0], ts[0][1], ts[0][2], ts[1][0], ts[1][1], ts[1][2], mean[0],
+                 mean[1], var[0], var[1], scratch, R, m, int(self.scale))
+            self.stats["beaver_mul"] += 1
+            inv = self.reciprocal_newton(self.sub_public_scalar(var, -eps_q))
+            t1 = self.dealer.triple("mul", (R,), (m, R))             # fpt_mul(inv, Xc.T)
+            t2 = self.dealer.triple("mul", (B * HW, C), (C,))        # fpt_mul(rows, weight)
+            arr = lambda t: (ctypes.c_void_p * 6)(*[q.data_ptr() for q in (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])])
+            out = [torch.empty(B, C, H, W, dtype=I64, device=dev), torch.empty(B, C, H, W, dtype=I64, device=dev)]
+            call("primia_gn_apply_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0], bias[1],
+                 arr(t1), arr(t2), out[0], out[1], B, C, HW, groups, int(self.scale))
+            self.stats["beaver_mul"] += 2
+            return out
+
+        def transpose(t, rows, cols):      # [rows, cols] -> [cols, rows]
+            def one(j):
+                o = torch.empty(cols, rows, dtype=I64, device=t[j].device)
+                call("primia_col2out_syft", t[j].contiguous(), None, o, 1, rows, cols)
+                return o
+
+            return self._each(one)
+
+        def row_mean(t):                   # [R, m] -> trunc_div(row sum, m)  [R]
+            def one(j):
+                s = torch.empty(R, dtype=I64, device=t[j].device)
+                call("primia_ring_rowsum", t[j].contiguous(), s, R, m)
+                o = _empty_like(s)
+                call("primia_trunc_div", s, m, o, R)
+                return o
+
+            return self._each(one)
+
+        mean = row_mean(x)
+        xct = self.sub(transpose(x, R, m), mean)                     # Xc.T [m, R]: the mean broadcasts over the leading dim
+        xc = transpose(xct, m, R)                                    # Xc [R, m]
+        var = row_mean(self.fpt_mul(xc, xc))
+        inv = self.reciprocal_newton(self.sub_public_scalar(var, -eps_q))
+        nt = self.fpt_mul(inv, xct)                                  # [m, R]
+        n = [None if t is None else t.view(B, C, H, W) for t in transpose(nt, m, R)]
+
+        def to_rows(j):  # permute(1,0,2,3).reshape(C,-1).t()  -> [B*H*W, C], row b*H*W + p
+            o = torch.empty(B * HW, C, dtype=I64, device=n[j].device)
+            if B == 1:
+                call("primia_col2out_syft", n[j], None, o, 1, C, HW)
+            else:
+                call("primia_nchw_to_rows", n[j], o, B, C, HW)
+            return o
+
+        result = self.add(self.fpt_mul(self._each(to_rows), weight), bias)
+
+        def back(j):
+            o = torch.empty(B, C, H, W, dtype=I64, device=result[j].device)
+            if B == 1:
+                call("primia_col2out_syft", result[j], None, o, 1, HW, C)
+            else:
+                call("primia_rows_to_nchw", result[j], o, B, C, HW)
+            return o
+
+        return self._each(back)
+
     def max_pool2d_3x3s2(self, x):
         """_pool2d(mode="max") for a 3x3 window (nn/functional.py:460-508): unroll to 9 columns,
         binary tree on the first 8, then against the 9th."""
@@ -755,6 +846,40 @@ def _check_pooling(pooling):
     return pooling
 
 
+NORMS = ("batch", "group")
+GN_GROUPS = 32      # GroupNorm(32, C) at every norm site: the network train.py builds for differentially_private = yes
+
+
+def norm_of(keys, norm=None):
+    """The normalisation a state dict / architecture holds: "group" when it has no running statistics (the BatchNorm-free
+    network of differentially private training), else "batch".  An explicit `norm` is checked against the keys."""
+    found = "batch" if "bn1.running_mean" in keys else "group"
+    if norm is None:
+        return found
+    if norm not in NORMS:
+        raise ValueError(f"norm must be one of {NORMS} or None, got {norm!r}")
+    if norm != found:
+        raise ValueError(f"norm={norm!r}, but the state dict holds a {found}-norm network (bn1.running_mean is "
+                         f"{'present' if found == 'batch' else 'absent'})")
+    return norm
+
+
+def _eps_q(base, pf):
+    """GroupNorm's eps = 1e-5 in fixed point, as fix_precision encodes it (precision.py:117-132: a float32 product,
+    truncated): 0 below five fractional digits."""
+    up = torch.tensor(1e-5, dtype=torch.float32) * torch.tensor(float(base ** pf), dtype=torch.float32)
+    return int(up.double().trunc().item())
+
+
+def _norm_prefixes(keys, blocks):
+    out = ["bn1"]
+    for prefix, _ in blocks:
+        out += [prefix + ".bn1", prefix + ".bn2"]
+        if (prefix + ".downsample.0.weight") in keys:
+            out.append(prefix + ".downsample.1")
+    return out
+
+
 def share_order(keys):
     """model.fix_precision().share() walks `parameters()` and then `buffers()` (hook.py:624-632,738-765)."""
     keys = [k for k in keys if not k.endswith("num_batches_tracked")]
@@ -771,16 +896,31 @@ class SecureResNet18:
     only (relu(avg(x)) != avg(relu(x))), so the avg stem keeps the order the network was trained with,
     conv1 -> bn1 -> RELU -> AvgPool2d(3, 2, 1), with zero padding and the divisor 9 for every window: it decodes to the
     model the checkpoint holds.  This stem is NOT pinned against the reference (whose behaviour for this case has not been
-    checked); it follows the plaintext model."""
+    checked); it follows the plaintext model.
 
-    def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max"):
+    norm="group" serves the BatchNorm-free network of differentially private training (GroupNorm(32, C) at every norm
+    site, no running statistics in the state dict): every norm site is `SecureContext.group_norm`, whose statistics depend
+    on the image -- one Beaver square and one 80-step Newton iteration on B * 32 values per layer, online.  Like the avg
+    stem it is NOT pinned against the reference, which has no such layer; it follows the plaintext model."""
+
+    def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max",
+                 norm=None):
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
-        default hoists the image-independent iterations of all BatchNorm layers into one batched vector."""
+        default hoists the image-independent iterations of all BatchNorm layers into one batched vector.  (Ignored with
+        GroupNorm: nothing there is image independent.)
+        norm=None: "group" when the state dict has no bn1.running_mean, else "batch"; an explicit value must agree."""
         self.ctx = ctx
         self.input_size = input_size
         self.batched_newton = batched_newton
         self.pooling = _check_pooling(pooling)
+        self.norm = norm_of(state_dict.keys(), norm)
+        self.blocks = blocks if blocks is not None else _default_blocks()
+        if self.norm == "group":
+            for n in _norm_prefixes(state_dict.keys(), self.blocks):
+                c = int(state_dict[n + ".weight"].shape[0])
+                if c % GN_GROUPS != 0:
+                    raise ValueError(f"{n}: {c} channels do not divide into {GN_GROUPS} groups")
         dev = ctx.dealer.device
         self.p = {}
         ctx.invalidate_weight_cache()      # (a model shared on this context before: its transposed shares go with it)
@@ -793,16 +933,9 @@ class SecureResNet18:
                 self.p[k] = ctx.share(ctx.encode(v.to(dev)), owner=0)
             else:
                 self.p[k] = ctx.share(None, owner=0, shape=v.shape)
-        self.blocks = blocks if blocks is not None else [
-            (f"layer{li}.{bi}", (2 if (li > 1 and bi == 0) else 1)) for li in range(1, 5) for bi in range(2)]
 
     def bn_prefixes(self):
-        out = ["bn1"]
-        for prefix, _ in self.blocks:
-            out += [prefix + ".bn1", prefix + ".bn2"]
-            if (prefix + ".downsample.0.weight") in self.p:
-                out.append(prefix + ".downsample.1")
-        return out
+        return _norm_prefixes(self.p, self.blocks)
 
     def precompute_inv(self):
         """newton(running_var) of every BatchNorm layer in ONE batched 80-step iteration.
@@ -844,12 +977,15 @@ class SecureResNet18:
 
     def _bn(self, x, prefix):
         p = self.p
+        if self.norm == "group":
+            return self.ctx.group_norm(x, p[prefix + ".weight"], p[prefix + ".bias"], GN_GROUPS)
         return self.ctx.batch_norm_eval(x, p[prefix + ".running_mean"], p[prefix + ".running_var"],
                                         p[prefix + ".weight"], p[prefix + ".bias"], inv=self._inv[prefix])
 
     def forward_shares(self, x):
         c, p = self.ctx, self.p
-        self._inv = self.precompute_inv() if self.batched_newton else {n: None for n in self.bn_prefixes()}
+        if self.norm == "batch":
+            self._inv = self.precompute_inv() if self.batched_newton else {n: None for n in self.bn_prefixes()}
         x = c.conv2d(x, p["conv1.weight"], 2, 3)
         x = self._bn(x, "bn1")
         if self.pooling == "max":
@@ -898,7 +1034,9 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
     BEFORE anything is allocated.  Per batch, not per image: the 80-step Newton reciprocal (237 triples over all BatchNorm
     channels) and the weight side of every matmul triple; per image: everything with a row of its own.
     pooling="avg": the stem is one ReLU at conv1's output resolution and a party-local average pool that requests nothing
-    (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree)."""
+    (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree).
+    An architecture without running statistics is the GroupNorm network: no hoisted Newton; every norm site requests its
+    square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples."""
     _check_pooling(pooling)
     B, req = int(batch), []
     blocks = _default_blocks() if blocks is None else blocks
@@ -907,18 +1045,19 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
     out_hw = lambda h, k, stride, pad: (h + 2 * pad - k) // stride + 1
     cin = arch["conv1.weight"][1]
     mask((B, cin, input_size, input_size), 1)                                  # the images, shared by the data owner
-    names = ["bn1"]
-    for prefix, _ in blocks:
-        names += [prefix + ".bn1", prefix + ".bn2"]
-        if (prefix + ".downsample.0.weight") in arch:
-            names.append(prefix + ".downsample.1")
-    total = sum(arch[n + ".running_var"][0] for n in names)
-    mask((1,), None)                                                           # reciprocal_newton of all layers at once
-    for _ in range(79):
-        triple("mul", (total,), (total,))
-        triple("mul", (total,), (total,))
+    group = norm_of(arch) == "group"
+    names = _norm_prefixes(arch, blocks)
+
+    def newton(n):
         mask((1,), None)
-        triple("mul", (total,), (total,))
+        for _ in range(79):
+            triple("mul", (n,), (n,))
+            triple("mul", (n,), (n,))
+            mask((1,), None)
+            triple("mul", (n,), (n,))
+
+    if not group:
+        newton(sum(arch[n + ".running_var"][0] for n in names))                # reciprocal_newton of all layers at once
 
     def conv(name, h, stride, pad):
         o, c, r, _ = arch[name + ".weight"]
@@ -927,7 +1066,16 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
         return o, ho
 
     def bn(c, h):
-        triple("mul", (c,), (B * h * h, c))
+        if group:                                                              # SecureContext.group_norm, per layer
+            if c % GN_GROUPS != 0:
+                raise ValueError(f"{c} channels do not divide into {GN_GROUPS} groups")
+            R, m = B * GN_GROUPS, (c // GN_GROUPS) * h * h
+            triple("mul", (R, m), (R, m))
+            mask((1,), None)                                                   # + eps
+            newton(R)
+            triple("mul", (R,), (m, R))
+        else:
+            triple("mul", (c,), (B * h * h, c))
         triple("mul", (B * h * h, c), (c,))
 
     def relu(c, h):

@@ -2,7 +2,9 @@
 ms/image for the online phase (primitives pre-provisioned) and for the dealer (triples + FSS keys).
     python tools/bench_secure.py [--size 224] [--pf 16] [--images 2]
     python tools/bench_secure.py --batch N [--size 224] [--pf 16] [--images 3]     the serving form on N images per pass only
-    --pooling avg: the stem of a checkpoint trained with pooling_type = avg (ReLU, then a party-local average pool)"""
+    --pooling avg: the stem of a checkpoint trained with pooling_type = avg (ReLU, then a party-local average pool)
+    --norm group:  a GroupNorm state dict (the network of differentially private training): every norm site computes its
+                   statistics online -- a Beaver square and an 80-step Newton iteration on batch * 32 values per layer"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,6 +21,8 @@ def main():
                          "(--images passes each), the static primitive bytes and the largest batch the card admits")
     ap.add_argument("--pooling", choices=("max", "avg"), default="max",
                     help="the stem pool of the served network (a checkpoint's pooling_type); the report names it when it is avg")
+    ap.add_argument("--norm", choices=("batch", "group"), default="batch",
+                    help="group: a synthetic GroupNorm(32, C) state dict, no running statistics (the report names it)")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
     ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph replay of the online phase")
     ap.add_argument("--only-fss-roofline", action="store_true",
@@ -71,9 +75,10 @@ def main():
     cpu_t = cpu_sample_timings() if (a.cpu_sample and not a.only_fss_roofline) else None   # before the first GPU call
     dev = torch.device("cuda:0")
     torch.manual_seed(42)
-    sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, a.pooling))
-    # (the report of the default keeps its keys: "pooling" appears for avg only)
+    sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, a.pooling), a.norm)
+    # (the report of the default keeps its keys: "pooling" appears for avg only, "norm" for group only)
     pool_kw = {} if a.pooling == "max" else {"pooling": a.pooling}
+    norm_kw = {} if a.norm == "batch" else {"norm": a.norm}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
@@ -166,7 +171,7 @@ def main():
             gi(imgs)                    # the dealer's refill graph, then the online graph, on one stream
         torch.cuda.synchronize()
         both = (time.perf_counter() - t0) / reps * 1e3
-        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
+        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
                           "online_ms_per_image": round(online / B, 2), "with_refill_ms_per_image": round(both / B, 2),
                           "online_ms_per_pass": round(online, 2), "with_refill_ms_per_pass": round(both, 2),
                           "static_primitive_bytes": gi.static_bytes, "arena_mb": round(gi._arena.numel() * 8 / 1e6, 1),
@@ -254,7 +259,7 @@ def main():
 
     extra = {"cpu_baseline": cpu_sample_report(cpu_t, ctx.stats["dif_evals"])} if cpu_t else {}
     extra["roofline"] = fss_roofline()
-    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, "online_ms": round(to * 1e3, 1),
+    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, **norm_kw, "online_ms": round(to * 1e3, 1),
                       "online_graph_ms": None if graph_ms is None else round(graph_ms, 1),
                       "dealer_refill_ms": None if refill_ms is None else round(refill_ms, 1),
                       "dealer_refill_launches": refill_nodes, "dealer_keystream_mb_per_image": None if arena_mb is None else round(arena_mb, 1),
