@@ -60,8 +60,9 @@ def forward(sd, x, training=True, pooling="max", input_size=224, taps=None, relu
     """ResNet._forward_impl (models.py:466-482).  `sd` maps reference state-dict keys to tensors
     (parameters may require grad).  `taps`, if a dict, receives named intermediates.
     `bf16_storage` (tests only): model the bf16 engine's storage format — the input, every convolution output, every
-    block activation and the compute copies of the conv weights are rounded to bf16 where the engine keeps them in
-    bf16 buffers (fp32 accumulation, BatchNorm statistics and the master weights stay fp32).
+    block activation (with pooling="avg" also the stem activation in front of the pool) and the compute copies of the
+    conv weights are rounded to bf16 where the engine keeps them in bf16 buffers (fp32 accumulation, BatchNorm
+    statistics and the master weights stay fp32).
     `relu_masks` (tests only): {site: bool NCHW mask} — at the named ReLU sites ("stem.z", "<block>.a1",
     "<block>.out") the activation is `pre * mask` instead of relu(pre).  With the masks another implementation
     produced, the backward pass follows that implementation's branch at pre-activations that are zero up to
@@ -85,7 +86,9 @@ def forward(sd, x, training=True, pooling="max", input_size=224, taps=None, relu
     if pooling == "max":
         x = F.max_pool2d(x, 3, 2, 1)
     else:
-        x = F.avg_pool2d(x, 3, 2, 1)
+        # the avg stem is the unfused chain norm -> relu | pool: the engine stores z (and, on the way back, dz) between
+        # the two, where the fused max stem writes neither
+        x = F.avg_pool2d(q(x), 3, 2, 1)
     x = tap("pool.out", q(x))
     for lname, planes, stride in BLOCKS:
         for bi in range(2):
@@ -244,10 +247,18 @@ def dp_gradients(sd, x, target, max_grad_norm=1.0, noise_multiplier=1.3, noise=N
     (norm_layer=GroupNorm) differentiated by torch.func.vmap(grad) — tests/golden/dp_ref.npz.
     `noise`: dict key -> standard-normal tensor (explicit randomness).  Returns (grads, norms, clip).
     `bf16_storage` (tests only): the forward pass rounds to bf16 where the bf16 engine stores (see forward())."""
+    per = per_sample_gradients(sd, x, target, pooling, bf16_storage)
+    out, norms, clip = dp_clip_and_average(per, max_grad_norm, noise_multiplier, noise)
+    if return_per_sample:
+        return out, norms, clip, per
+    return out, norms, clip
+
+
+def per_sample_gradients(sd, x, target, pooling="max", bf16_storage=False):
+    """[{key: gradient of sample n's own loss}] — the expensive half of dp_gradients (one batch-of-1 pass per sample)."""
     keys = param_keys(sd)
-    B = x.shape[0]
     per = []
-    for n in range(B):
+    for n in range(x.shape[0]):
         for k in keys:
             sd[k].requires_grad_(True)
             sd[k].grad = None
@@ -256,6 +267,13 @@ def dp_gradients(sd, x, target, max_grad_norm=1.0, noise_multiplier=1.3, noise=N
         per.append(OrderedDict((k, sd[k].grad.detach().clone()) for k in keys))
     for k in keys:
         sd[k].requires_grad_(False)
+    return per
+
+
+def dp_clip_and_average(per, max_grad_norm=1.0, noise_multiplier=1.3, noise=None):
+    """The clip / noise rule of dp_gradients on given per-sample gradients (a test that derives its clipping norm from
+    the per-sample norms applies it without a second pass).  Returns (grads, norms, clip)."""
+    keys, B = list(per[0]), len(per)
     norms = torch.stack([torch.sqrt(sum((g[k].double() ** 2).sum() for k in keys)) for g in per])
     clip = torch.clamp(max_grad_norm / (norms + 1e-6), max=1.0)
     out = OrderedDict()
@@ -264,6 +282,4 @@ def dp_gradients(sd, x, target, max_grad_norm=1.0, noise_multiplier=1.3, noise=N
         if noise is not None:
             s = s + noise[k] * (noise_multiplier * max_grad_norm)
         out[k] = s / B
-    if return_per_sample:
-        return out, norms, clip, per
     return out, norms, clip
