@@ -22,6 +22,7 @@ Reference map (paths under syft/frameworks/torch/):
   conv2d / pools / bn / lin  nn/functional.py:10-14, 44-75, 204-308, 460-525
   public add / sub / rsub    additive_shared.py:440-527 (constants are RE-SHARED with fresh randomness)
 """
+import ctypes
 import os
 
 import torch
@@ -34,6 +35,28 @@ I64 = torch.int64
 
 def _empty_like(t):
     return torch.empty_like(t)
+
+
+def _pair(shape, device):
+    """Two empty int64 tensors: the outputs of a launch that writes both parties' shares."""
+    return [torch.empty(tuple(shape), dtype=I64, device=device) for _ in range(2)]
+
+
+def _six(t):
+    """A triple's shares as the two-party kernels take them: a, b, c of party 0, then of party 1."""
+    return (*t[0], *t[1])
+
+
+def _ptr_table(t):
+    """The host pointer table of a triple's six shares."""
+    return (ctypes.c_void_p * 6)(*[q.data_ptr() for q in _six(t)])
+
+
+def _transposed(t, rows, cols):
+    """One share [rows, cols] -> [cols, rows] (weight.reshape(O, -1).t() of a conv / linear weight)."""
+    o = torch.empty(cols, rows, dtype=I64, device=t.device)
+    call("primia_col2out_syft", t.contiguous(), None, o, 1, rows, cols)
+    return o
 
 
 class Dealer:
@@ -220,8 +243,12 @@ class SecureContext:
     local_fused = True
 
     @property
+    def _in_process(self):
+        return self.party is None and isinstance(self.opener, LocalOpener)
+
+    @property
     def _local(self):
-        return self.party is None and isinstance(self.opener, LocalOpener) and self.local_fused
+        return self._in_process and self.local_fused
 
     # ---- encode / share / reconstruct -----------------------------------------------------------
     def encode(self, x):
@@ -330,8 +357,6 @@ class SecureContext:
         return cache[key]
 
     # ---- Beaver -----------------------------------------------------------------------------------
-    fuse_beaver = True
-
     def beaver_mul(self, x, y, trunc=None):
         """Element-wise private product; trunc = d: followed by each party's truncation of its share by d (fpt_mul).
         One operand may be a vector broadcast over the other's leading dims; the ring product is symmetric so the
@@ -345,32 +370,26 @@ class SecureContext:
         n, nb = xr.numel(), yr.numel()
         if self._local:
             out = [_empty_like(xr), _empty_like(xr)]
-            call("primia_fpt_mul_local", x[0], x[1], y[0], y[1], t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2],
-                 None, None, out[0], out[1], n, nb, 0 if trunc is None else int(trunc))
+            call("primia_fpt_mul_local", x[0], x[1], y[0], y[1], *_six(t), None, None, out[0], out[1], n, nb,
+                 0 if trunc is None else int(trunc))
             self.stats["beaver_mul"] += 1
             return out
         d, e = [None, None], [None, None]
         for j in self.parties:  # spdz_mask
             d[j], e[j] = _empty_like(xr), _empty_like(yr)
-            if self.fuse_beaver:
-                call("primia_beaver_mask", x[j], t[j][0], d[j], n, y[j], t[j][1], e[j], nb)
-            else:
-                call("primia_ring_sub", x[j], t[j][0], d[j], n, n)
-                call("primia_ring_sub", y[j], t[j][1], e[j], nb, nb)
+            call("primia_beaver_mask", x[j], t[j][0], d[j], n, y[j], t[j][1], e[j], nb)
         delta, eps = self.opener.open(d), self.opener.open(e)
-        fused_trunc = trunc is not None and self.fuse_beaver
 
         def one(j):  # spdz_compute
             o = _empty_like(xr)
-            if fused_trunc:
-                call("primia_beaver_combine_mul_trunc", j, delta, eps, t[j][0], t[j][1], t[j][2], o, n, nb, int(trunc))
+            if trunc is not None:
+                call("primia_beaver_combine_mul_trunc", j, delta, eps, *t[j], o, n, nb, int(trunc))
             else:
-                call("primia_beaver_combine_mul", j, delta, eps, t[j][0], t[j][1], t[j][2], o, n, nb)
+                call("primia_beaver_combine_mul", j, delta, eps, *t[j], o, n, nb)
             return o
 
         self.stats["beaver_mul"] += 1
-        out = self._each(one)
-        return self.trunc(out, trunc) if (trunc is not None and not fused_trunc) else out
+        return self._each(one)
 
     def beaver_matmul(self, x, y):
         """x [..., K] @ y [K, N]: the leading dimensions of x are rows of ONE product (a batch's [B, L, K] im2col operand is
@@ -380,26 +399,21 @@ class SecureContext:
         M = xr.numel() // K
         t = self.dealer.triple("matmul", tuple(xr.shape), tuple(yr.shape))
         if self._local:
-            out = [torch.empty(*xr.shape[:-1], N, dtype=I64, device=xr.device) for _ in range(2)]
+            out = _pair((*xr.shape[:-1], N), xr.device)
             scratch = torch.empty(M * K + 2 * K * N, dtype=I64, device=xr.device)
-            call("primia_beaver_matmul_local", x[0], x[1], y[0], y[1], t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2],
-                 out[0], out[1], scratch, M, K, N)
+            call("primia_beaver_matmul_local", x[0], x[1], y[0], y[1], *_six(t), out[0], out[1], scratch, M, K, N)
             self.stats["beaver_matmul"] += 1
             return out
         d, e = [None, None], [None, None]
         for j in self.parties:
             d[j], e[j] = _empty_like(xr), _empty_like(yr)
-            if self.fuse_beaver:
-                call("primia_beaver_mask", x[j], t[j][0], d[j], xr.numel(), y[j], t[j][1], e[j], yr.numel())
-            else:
-                call("primia_ring_sub", x[j], t[j][0], d[j], xr.numel(), xr.numel())
-                call("primia_ring_sub", y[j], t[j][1], e[j], yr.numel(), yr.numel())
+            call("primia_beaver_mask", x[j], t[j][0], d[j], xr.numel(), y[j], t[j][1], e[j], yr.numel())
         delta, eps = self.opener.open(d), self.opener.open(e)
         scratch = torch.empty(K * N, dtype=I64, device=xr.device)
 
         def one(j):
             o = torch.empty(*xr.shape[:-1], N, dtype=I64, device=xr.device)
-            call("primia_beaver_combine_matmul", j, delta, eps, t[j][0], t[j][1], t[j][2], o, scratch, M, K, N)
+            call("primia_beaver_combine_matmul", j, delta, eps, *t[j], o, scratch, M, K, N)
             return o
 
         self.stats["beaver_matmul"] += 1
@@ -418,8 +432,7 @@ class SecureContext:
         """fss.le with both parties here: mask_builder, the open and both DIF evaluations in one launch.  x1 = None stands
         for shares of zero; colsK = (row width, first column) when operand K is a column range of a matrix."""
         keys = self.dealer.dif_keys(n)
-        dev = x2[0].device
-        out = [torch.empty(shape, dtype=I64, device=dev), torch.empty(shape, dtype=I64, device=dev)]
+        out = _pair(shape, x2[0].device)
         k0, k1 = keys
         call("primia_dif_eval_local", None if x1 is None else x1[0], None if x1 is None else x1[1], cols1[0], cols1[1],
              x2[0], x2[1], cols2[0], cols2[1], length, k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"],
@@ -472,10 +485,9 @@ class SecureContext:
         n = rows * length
         bit = self._le_local(left, right, n, (rows, length), (wl, sl), (wr, sr), length)
         t = self.dealer.triple("mul", (rows, length), (rows, length))
-        dev = left[0].device
-        out = [torch.empty(rows, length, dtype=I64, device=dev), torch.empty(rows, length, dtype=I64, device=dev)]
-        call("primia_max_combine_local", bit[0], bit[1], left[0], left[1], wl, sl, right[0], right[1], wr, sr, t[0][0],
-             t[0][1], t[0][2], t[1][0], t[1][1], t[1][2], out[0], out[1], rows, length)
+        out = _pair((rows, length), left[0].device)
+        call("primia_max_combine_local", bit[0], bit[1], left[0], left[1], wl, sl, right[0], right[1], wr, sr, *_six(t),
+             out[0], out[1], rows, length)
         self.stats["beaver_mul"] += 1
         return out
 
@@ -497,11 +509,11 @@ class SecureContext:
         K = C * R * S
         if self._local:
             dev = x[0].device
-            im = [torch.empty(B, Ho * Wo, K, dtype=I64, device=dev), torch.empty(B, Ho * Wo, K, dtype=I64, device=dev)]
+            im = _pair((B, Ho * Wo, K), dev)
             call("primia_im2col_syft_2p", x[0], x[1], im[0], im[1], B, C, H, W, R, S, stride, padding)
             wt = self._weight_t(w, O, K)
             res = self.beaver_matmul(im, wt)
-            out = [torch.empty(B, O, Ho, Wo, dtype=I64, device=dev), torch.empty(B, O, Ho, Wo, dtype=I64, device=dev)]
+            out = _pair((B, O, Ho, Wo), dev)
             call("primia_trunc_col2out_2p", res[0], res[1], None, None, out[0], out[1], B, Ho * Wo, O, int(self.scale))
             return out
         im, wt = [None, None], [None, None]
@@ -509,10 +521,7 @@ class SecureContext:
             a = torch.empty(B, Ho * Wo, K, dtype=I64, device=x[j].device)
             call("primia_im2col_syft", x[j], a, B, C, H, W, R, S, stride, padding)
             im[j] = a
-            # weight.reshape(O, -1).t(): [K, O]
-            t = torch.empty(K, O, dtype=I64, device=x[j].device)
-            call("primia_col2out_syft", w[j], None, t, 1, O, K)
-            wt[j] = t
+            wt[j] = _transposed(w[j], O, K)
         res = self.fpt_matmul(im, wt)
 
         def one(j):
@@ -541,11 +550,7 @@ class SecureContext:
                 self._wt_cache[key] = self._wt_cache.pop(key)      # most recently used: to the back
                 return wt
             del self._wt_cache[key]
-        wt = []
-        for j in (0, 1):
-            t = torch.empty(K, O, dtype=I64, device=w[j].device)
-            call("primia_col2out_syft", w[j], None, t, 1, O, K)
-            wt.append(t)
+        wt = [_transposed(w[j], O, K) for j in (0, 1)]
         while len(self._wt_cache) >= self._wt_cache_max:
             del self._wt_cache[next(iter(self._wt_cache))]
         self._wt_cache[key] = (w[0], w[1], w[0]._version, w[1]._version, wt)
@@ -563,7 +568,7 @@ class SecureContext:
         step-by-step chain below consumes them and handed to the kernel as a pointer table, so the two forms are
         bit-identical — the chain is what a three-role run (opens = messages) executes, and `fuse_newton = False`
         selects it here too."""
-        if self.party is None and isinstance(self.opener, LocalOpener) and self.fuse_newton:
+        if self._in_process and self.fuse_newton:
             return self._reciprocal_newton_fused(v)
         C = 20
         # x0 = (C + 1 - v) / C
@@ -587,7 +592,7 @@ class SecureContext:
                     m = self.dealer.const_mask(1, owner=None)
                     prims.append(m)
                 t = self.dealer.triple("mul", shape, shape)
-                prims += [t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2]]
+                prims += _six(t)
         ptrs = [p.data_ptr() for p in prims]
         if isinstance(self.dealer, PreloadedDealer):
             # static primitive buffers (pre-provisioned store, GraphedSecureInference): the device pointer table is
@@ -608,50 +613,26 @@ class SecureContext:
             # is on the current stream and torch's allocator is stream-ordered, so the 237 triples may be recycled
             # as soon as this function returns (round 2 pinned all of them per image: ~55 MB leaked per forward).
             table = torch.tensor(ptrs, dtype=I64).to(dev)
-        out = [torch.empty(shape, dtype=I64, device=dev), torch.empty(shape, dtype=I64, device=dev)]
+        out = _pair(shape, dev)
         call("primia_newton_reciprocal_local", v[0].contiguous(), v[1].contiguous(), table, int(self.scale), out[0], out[1], n)
         self.stats["beaver_mul"] += 3 * 79
         return out
 
-    def batch_norm_eval(self, x, mean, var, weight, bias, inv=None):
-        """batch_norm in eval mode (nn/functional.py:44-75): ((x - mean) * newton(var)) * w + b on
-        [H*W, C] rows — no explicit sqrt and no eps, exactly as the reference computes it (its
-        "newton" iteration converges to var^-1/2).  `inv` may carry shares of newton(var) computed
-        earlier (see SecureResNet18.precompute_inv)."""
-        B, C, H, W = self._ref(x).shape
-
-        def to_rows(j):  # permute(1,0,2,3).reshape(C,-1).t()  -> [B*H*W, C], row b*H*W + p
-            o = torch.empty(B * H * W, C, dtype=I64, device=x[j].device)
+    def _to_rows(self, x, B, C, HW):
+        """NCHW shares -> [B*HW, C] rows (row b*HW + p): permute(1,0,2,3).reshape(C,-1).t()."""
+        def one(j):
+            o = torch.empty(B * HW, C, dtype=I64, device=x[j].device)
             if B == 1:
-                call("primia_col2out_syft", x[j], None, o, 1, C, H * W)
+                call("primia_col2out_syft", x[j], None, o, 1, C, HW)
             else:
-                call("primia_nchw_to_rows", x[j], o, B, C, H * W)
+                call("primia_nchw_to_rows", x[j], o, B, C, HW)
             return o
 
-        if self._local:
-            if inv is None:
-                inv = self.reciprocal_newton(var)
-            import ctypes
+        return self._each(one)
 
-            HW = B * H * W
-            t1 = self.dealer.triple("mul", (C,), (HW, C))           # fpt_mul(inv, rows - mean)
-            t2 = self.dealer.triple("mul", (HW, C), (C,))           # fpt_mul(normalized, weight)
-            arr = lambda t: (ctypes.c_void_p * 6)(*[q.data_ptr() for q in (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])])
-            dev = x[0].device
-            out = [torch.empty(B, C, H, W, dtype=I64, device=dev), torch.empty(B, C, H, W, dtype=I64, device=dev)]
-            if B == 1:
-                call("primia_bn_eval_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
-                     bias[1], arr(t1), arr(t2), out[0], out[1], C, HW, int(self.scale))
-            else:
-                call("primia_bn_eval_local_batch", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
-                     bias[1], arr(t1), arr(t2), out[0], out[1], B, C, H * W, int(self.scale))
-            self.stats["beaver_mul"] += 2
-            return out
-        rows = self._each(to_rows)
-        if inv is None:
-            inv = self.reciprocal_newton(var)
-        normalized = self.fpt_mul(inv, self.sub(rows, mean))
-        result = self.add(self.fpt_mul(normalized, weight), bias)
+    def _affine_to_nchw(self, rows, weight, bias, B, C, H, W):
+        """fpt_mul(rows, weight) + bias on [B*H*W, C] rows, back to NCHW: the affine tail of both norms' step-by-step paths."""
+        result = self.add(self.fpt_mul(rows, weight), bias)
 
         def back(j):
             o = torch.empty(B, C, H, W, dtype=I64, device=result[j].device)
@@ -662,6 +643,33 @@ class SecureContext:
             return o
 
         return self._each(back)
+
+    def batch_norm_eval(self, x, mean, var, weight, bias, inv=None):
+        """batch_norm in eval mode (nn/functional.py:44-75): ((x - mean) * newton(var)) * w + b on
+        [H*W, C] rows — no explicit sqrt and no eps, exactly as the reference computes it (its
+        "newton" iteration converges to var^-1/2).  `inv` may carry shares of newton(var) computed
+        earlier (see SecureResNet18.precompute_inv)."""
+        B, C, H, W = self._ref(x).shape
+        if self._local:
+            if inv is None:
+                inv = self.reciprocal_newton(var)
+            HW = B * H * W
+            t1 = self.dealer.triple("mul", (C,), (HW, C))           # fpt_mul(inv, rows - mean)
+            t2 = self.dealer.triple("mul", (HW, C), (C,))           # fpt_mul(normalized, weight)
+            out = _pair((B, C, H, W), x[0].device)
+            if B == 1:
+                call("primia_bn_eval_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
+                     bias[1], _ptr_table(t1), _ptr_table(t2), out[0], out[1], C, HW, int(self.scale))
+            else:
+                call("primia_bn_eval_local_batch", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
+                     bias[1], _ptr_table(t1), _ptr_table(t2), out[0], out[1], B, C, H * W, int(self.scale))
+            self.stats["beaver_mul"] += 2
+            return out
+        rows = self._to_rows(x, B, C, H * W)
+        if inv is None:
+            inv = self.reciprocal_newton(var)
+        normalized = self.fpt_mul(inv, self.sub(rows, mean))
+        return self._affine_to_nchw(normalized, weight, bias, B, C, H, W)
 
     def group_norm(self, x, weight, bias, groups=32):
         """GroupNorm(groups, C) on shares [B, C, H, W] -- the norm of the BatchNorm-free network that differentially private
@@ -686,35 +694,26 @@ class SecureContext:
         R, m, HW = B * groups, (C // groups) * H * W, H * W
         eps_q = _eps_q(self.base, self.pf)
         if self._local:
-            import ctypes
-
             dev = x[0].device
             x = [x[0].contiguous(), x[1].contiguous()]
             ts = self.dealer.triple("mul", (R, m), (R, m))           # fpt_mul(Xc, Xc)
-            mean = [torch.empty(R, dtype=I64, device=dev) for _ in range(2)]
-            var = [torch.empty(R, dtype=I64, device=dev) for _ in range(2)]
+            mean, var = _pair((R,), dev), _pair((R,), dev)
             n_scratch = _lib.query("primia_gn_moments_local_scratch_elems", R, m)
             scratch = torch.empty(n_scratch, dtype=I64, device=dev) if n_scratch > 0 else None
-            call("primia_gn_moments_local", x[0], x[1], ts[0][0], ts[0][1], ts[0][2], ts[1][0], ts[1][1], ts[1][2], mean[0],
-                 mean[1], var[0], var[1], scratch, R, m, int(self.scale))
+            call("primia_gn_moments_local", x[0], x[1], *_six(ts), mean[0], mean[1], var[0], var[1], scratch, R, m,
+                 int(self.scale))
             self.stats["beaver_mul"] += 1
             inv = self.reciprocal_newton(self.sub_public_scalar(var, -eps_q))
             t1 = self.dealer.triple("mul", (R,), (m, R))             # fpt_mul(inv, Xc.T)
             t2 = self.dealer.triple("mul", (B * HW, C), (C,))        # fpt_mul(rows, weight)
-            arr = lambda t: (ctypes.c_void_p * 6)(*[q.data_ptr() for q in (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])])
-            out = [torch.empty(B, C, H, W, dtype=I64, device=dev), torch.empty(B, C, H, W, dtype=I64, device=dev)]
+            out = _pair((B, C, H, W), dev)
             call("primia_gn_apply_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0], bias[1],
-                 arr(t1), arr(t2), out[0], out[1], B, C, HW, groups, int(self.scale))
+                 _ptr_table(t1), _ptr_table(t2), out[0], out[1], B, C, HW, groups, int(self.scale))
             self.stats["beaver_mul"] += 2
             return out
 
         def transpose(t, rows, cols):      # [rows, cols] -> [cols, rows]
-            def one(j):
-                o = torch.empty(cols, rows, dtype=I64, device=t[j].device)
-                call("primia_col2out_syft", t[j].contiguous(), None, o, 1, rows, cols)
-                return o
-
-            return self._each(one)
+            return self._each(lambda j: _transposed(t[j], rows, cols))
 
         def row_mean(t):                   # [R, m] -> trunc_div(row sum, m)  [R]
             def one(j):
@@ -733,26 +732,7 @@ class SecureContext:
         inv = self.reciprocal_newton(self.sub_public_scalar(var, -eps_q))
         nt = self.fpt_mul(inv, xct)                                  # [m, R]
         n = [None if t is None else t.view(B, C, H, W) for t in transpose(nt, m, R)]
-
-        def to_rows(j):  # permute(1,0,2,3).reshape(C,-1).t()  -> [B*H*W, C], row b*H*W + p
-            o = torch.empty(B * HW, C, dtype=I64, device=n[j].device)
-            if B == 1:
-                call("primia_col2out_syft", n[j], None, o, 1, C, HW)
-            else:
-                call("primia_nchw_to_rows", n[j], o, B, C, HW)
-            return o
-
-        result = self.add(self.fpt_mul(self._each(to_rows), weight), bias)
-
-        def back(j):
-            o = torch.empty(B, C, H, W, dtype=I64, device=result[j].device)
-            if B == 1:
-                call("primia_col2out_syft", result[j], None, o, 1, HW, C)
-            else:
-                call("primia_rows_to_nchw", result[j], o, B, C, HW)
-            return o
-
-        return self._each(back)
+        return self._affine_to_nchw(self._to_rows(n, B, C, HW), weight, bias, B, C, H, W)
 
     def max_pool2d_3x3s2(self, x):
         """_pool2d(mode="max") for a 3x3 window (nn/functional.py:460-508): unroll to 9 columns,
@@ -767,8 +747,7 @@ class SecureContext:
             return o
 
         if self._local:
-            dev = x[0].device
-            im = [torch.empty(rows, 9, dtype=I64, device=dev), torch.empty(rows, 9, dtype=I64, device=dev)]
+            im = _pair((rows, 9), x[0].device)
             call("primia_pool_unroll_syft_2p", x[0], x[1], im[0], im[1], B, C, H, W, 3, 2, 1)
             res = self._max_pair_cols(im, 9, 0, im, 9, 4, rows, 4)
             res = self._max_pair_cols(res, 4, 0, res, 4, 2, rows, 2)
@@ -809,8 +788,7 @@ class SecureContext:
         B, C, H, W = self._ref(x).shape
         Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
         if self._local:
-            dev = x[0].device
-            out = [torch.empty(B, C, Ho, Wo, dtype=I64, device=dev), torch.empty(B, C, Ho, Wo, dtype=I64, device=dev)]
+            out = _pair((B, C, Ho, Wo), x[0].device)
             call("primia_avg_pool_syft_2p", x[0], x[1], out[0], out[1], B, C, H, W, 3, 2, 1)
             return out
 
@@ -825,15 +803,8 @@ class SecureContext:
         """F.linear -> torch.addmm(bias, input, weight.t()) -> FPT.addmm (nn/functional.py:10-14,
         precision.py:822-827): matmul + truncation, then + bias."""
         O, I = self._ref(w).shape
-
-        def tr(j):
-            t = torch.empty(I, O, dtype=I64, device=w[j].device)
-            call("primia_col2out_syft", w[j], None, t, 1, O, I)
-            return t
-
-        if self._local:
-            return self.add(self.fpt_matmul(x, self._weight_t(w, O, I)), b)
-        return self.add(self.fpt_matmul(x, self._each(tr)), b)
+        wt = self._weight_t(w, O, I) if self._local else self._each(lambda j: _transposed(w[j], O, I))
+        return self.add(self.fpt_matmul(x, wt), b)
 
 
 POOLINGS = ("max", "avg")
@@ -1025,6 +996,12 @@ class SecureResNet18:
 
 def _default_blocks():
     return [(f"layer{li}.{bi}", (2 if (li > 1 and bi == 0) else 1)) for li in range(1, 5) for bi in range(2)]
+
+
+def model_requests(arch):
+    """The masks sharing a model of architecture `arch` (name -> shape) requests, one per shared tensor in share_order, in the
+    form `Dealer.requests` records them: what constructing a SecureResNet18 asks for (tests hold the two equal)."""
+    return [("const_mask", tuple(arch[k]), {"owner": 0}) for k in share_order(arch)]
 
 
 def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
@@ -1452,7 +1429,7 @@ def _triple_c_shape(op, xshape, yshape):
 class PartyDealer:
     """What party j sees of the crypto provider: it receives ITS half of each primitive, in protocol order
     (mpc/primitives.py:161-235 keeps the same per-worker store; here nothing is requested — the provider
-    follows the public request schedule of the network, see request_schedule)."""
+    follows the public request schedule of the network, see model_requests and image_requests)."""
 
     def __init__(self, link: PartyLink):
         self.link, self.device, self.j = link, link.device, link.role
@@ -1483,20 +1460,6 @@ class PartyDealer:
 def architecture_of(state_dict):
     """name -> shape of every shared tensor: all a non-owner needs to know about the model."""
     return {k: tuple(v.shape) for k, v in state_dict.items() if not k.endswith("num_batches_tracked")}
-
-
-def request_schedule(arch, input_size, device, blocks=None, precision_fractional=16, base=10, batch=1, pooling="max"):
-    """The (public) sequence of primitives one model sharing + one encrypted forward of `batch` images consumes, as
-    (model_requests, image_requests): it depends on the architecture, the input size, the batch size and the stem pool only, so the
-    crypto provider derives it from a dry run on a dummy model of that architecture."""
-    d = Dealer(device, seed=0)
-    d.requests = []
-    ctx = SecureContext(d, base, precision_fractional)
-    dummy = {k: torch.ones(shape, dtype=torch.float32) for k, shape in arch.items()}
-    model = SecureResNet18(ctx, dummy, input_size, blocks, pooling=pooling)
-    n_model = len(d.requests)
-    model(torch.zeros(batch, arch["conv1.weight"][1], input_size, input_size, dtype=torch.float32, device=device))
-    return d.requests[:n_model], d.requests[n_model:]
 
 
 class DealerService:
@@ -1540,11 +1503,10 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     orchestrator), the dealer None."""
     _check_pooling(pooling)
     passes = (n_images + batch - 1) // batch
-    if link.role == "dealer":
-        model_req, image_req = request_schedule(arch, input_size, link.device, blocks, precision_fractional, base, batch,
-                                                pooling)
+    if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
+        image_req = image_requests(arch, input_size, batch, blocks, pooling)
         svc = DealerService(Dealer(link.device, seed), link)
-        svc.serve(model_req)
+        svc.serve(model_requests(arch))
         for _ in range(passes):
             svc.serve(image_req)
         return None

@@ -1,10 +1,12 @@
-"""Networks, images and the composed oracle forward shared by tests/test_gpu_secure_batch.py and its three-role worker
-(tests/party_worker_batch.py): a module of helpers, not of tests."""
+"""Networks and the composed oracle forward (every stem pool, every norm) shared by the tests of encrypted inference: a module
+of helpers, not of tests."""
 import numpy as np
 import torch
 
 from oracle import secure_oracle as S
 from primia_amd import resnet_spec
+from tests.secure_avgpool_nets import oracle_avg_pool
+from tests.secure_groupnorm_nets import oracle_group_norm
 
 
 def draw_bn(sd, name, c, gen):
@@ -55,47 +57,48 @@ def mini_resnet(gen):
     return sd
 
 
-def three_role_case():
-    """(state dict, three 32 x 32 images, blocks) of the three-role batch test, identical in every process."""
-    gen = torch.Generator().manual_seed(61)
-    sd = mini_resnet(gen)
-    return sd, torch.randn(3, 3, 32, 32, generator=gen), MINI_BLOCKS
-
-
 def numpy_sd(sd):
     return {k: v.numpy() for k, v in sd.items()}
 
 
-def oracle_batch_forward(ctx, state_dict, images, blocks=None):
-    """oracle.secure_oracle.secure_resnet_forward for images [B, C, S, S], composed from OracleContext's own methods
-    (which are batch-general): that function flattens the pooled features with reshape(1, -1), this one with
-    reshape(B, -1) -- nothing else differs.  state_dict values / images are float32 numpy arrays."""
+def oracle_forward(ctx, state_dict, images, blocks=None, pooling="max", norm="batch"):
+    """The secure forward of images [B, C, S, S], composed from OracleContext's own methods (which are batch-general),
+    oracle_avg_pool and oracle_group_norm -- nothing of primia_amd.secure, so that it stays an independent reference.
+    oracle.secure_oracle.secure_resnet_forward flattens the pooled features with reshape(1, -1), this one with reshape(B, -1).
+    pooling="avg": the stem in the order a pooling_type = avg network was trained with, conv1 -> norm -> ReLU ->
+    AvgPool2d(3, 2, 1); "max": the swapped stem, max pool before ReLU.  norm="batch": the Newton reciprocal of every layer's
+    running_var hoisted into one call; "group": oracle_group_norm at every norm site, nothing hoisted.
+    state_dict values / images are float32 numpy arrays."""
     p = {}
     for k in S.share_order(list(state_dict.keys())):
         p[k] = ctx.share(S.fix_encode(state_dict[k], ctx.base, ctx.pf))
     if blocks is None:
         blocks = [(f"layer{li}.{bi}", (2 if (li > 1 and bi == 0) else 1)) for li in range(1, 5) for bi in range(2)]
     x = ctx.share(S.fix_encode(images, ctx.base, ctx.pf))
-    names = ["bn1"]
-    for prefix, _ in blocks:
-        names += [prefix + ".bn1", prefix + ".bn2"]
-        if (prefix + ".downsample.0.weight") in p:
-            names.append(prefix + ".downsample.1")
-    inv_all = ctx.reciprocal_newton([np.concatenate([p[n + ".running_var"][j] for n in names]) for j in range(2)])
-    inv, off = {}, 0
-    for n in names:
-        k = p[n + ".running_var"][0].size
-        inv[n] = [inv_all[j][off:off + k] for j in range(2)]
-        off += k
+    if norm == "batch":
+        names = ["bn1"]
+        for prefix, _ in blocks:
+            names += [prefix + ".bn1", prefix + ".bn2"]
+            if (prefix + ".downsample.0.weight") in p:
+                names.append(prefix + ".downsample.1")
+        inv_all = ctx.reciprocal_newton([np.concatenate([p[n + ".running_var"][j] for n in names]) for j in range(2)])
+        inv, off = {}, 0
+        for n in names:
+            k = p[n + ".running_var"][0].size
+            inv[n] = [inv_all[j][off:off + k] for j in range(2)]
+            off += k
 
     def bn(t, prefix):
+        if norm == "group":
+            return oracle_group_norm(ctx, t, p[prefix + ".weight"], p[prefix + ".bias"])
         return ctx.batch_norm_eval(t, p[prefix + ".running_mean"], p[prefix + ".running_var"], p[prefix + ".weight"],
                                    p[prefix + ".bias"], inv=inv[prefix])
 
-    x = ctx.conv2d(x, p["conv1.weight"], 2, 3)
-    x = bn(x, "bn1")
-    x = ctx.max_pool2d_3x3s2(x)
-    x = ctx.relu(x)
+    x = bn(ctx.conv2d(x, p["conv1.weight"], 2, 3), "bn1")
+    if pooling == "max":
+        x = ctx.relu(ctx.max_pool2d_3x3s2(x))
+    else:
+        x = oracle_avg_pool(ctx.relu(x), 3, 2, 1)
     for prefix, stride in blocks:
         identity = x
         out = ctx.conv2d(x, p[prefix + ".conv1.weight"], stride, 1)

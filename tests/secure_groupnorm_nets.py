@@ -1,7 +1,7 @@
-"""The definition of the secret-shared GroupNorm (the reference has none), the composed oracle forward of a GroupNorm
-network, its float64 plaintext reference, CPU dealers and networks shared by tests/test_secure_groupnorm_host.py,
-tests/test_gpu_secure_groupnorm.py and the three-role worker tests/party_worker_groupnorm.py: a module of helpers, not of
-tests.  Everything is composed from oracle.secure_oracle's own functions; nothing under oracle/ knows about GroupNorm."""
+"""The definition of the secret-shared GroupNorm (the reference has none; tests/secure_batch_nets.py's oracle_forward places it
+at every norm site for norm="group"), the float64 plaintext reference of a GroupNorm network, CPU dealers and networks shared
+by tests/test_secure_groupnorm_host.py and tests/test_gpu_secure_groupnorm.py: a module of helpers, not of tests.
+Everything is composed from oracle.secure_oracle's own functions; nothing under oracle/ knows about GroupNorm."""
 import hashlib
 
 import numpy as np
@@ -11,8 +11,6 @@ from oracle import secure_oracle as S
 from oracle import train_oracle as O
 from primia_amd import resnet_spec
 from tests.cpu_standins import chacha20_words
-from tests.secure_avgpool_nets import oracle_avg_pool
-from tests.secure_batch_nets import MINI_BLOCKS
 
 I64, U64 = np.int64, np.uint64
 GROUPS = 32
@@ -22,7 +20,7 @@ VAR_DOMAIN = (0.05, 16.0)      # where the reference's Newton iteration approxim
 # held bit-identical to that composition, so the CPU figure is the measurement):
 #   LAYER_TOL   oracle_group_norm at pf = 6 on the [2, 64, 6, 6] input of tests/test_secure_groupnorm_host.py (group
 #               variances 0.41 to 3.57) against F.group_norm: max |error| 4.98e-4, 5.00e-4, 4.99e-4 under three dealer seeds.
-#   GROUP_TOL   oracle_group_forward at pf = 3 of group_resnet18(32, 520) on three N(0, 1) images (seed 521) on
+#   GROUP_TOL   oracle_forward(norm="group") at pf = 3 of group_resnet18(32, 520) on three N(0, 1) images (seed 521) on
 #               ChaChaDealer(53) -- the host twin of Dealer(seed=53) -- against plaintext_group_logits: max |error| per image
 #               0.00619, 0.00398, 0.00379 (group variances of the float64 forward: 0.063 to 13.02).
 LAYER_TOL = 2 * 5.0e-4
@@ -58,41 +56,6 @@ def oracle_group_norm(ctx, x, weight, bias, groups=GROUPS):
 
 def default_blocks():
     return [(f"layer{li}.{bi}", (2 if (li > 1 and bi == 0) else 1)) for li in range(1, 5) for bi in range(2)]
-
-
-def oracle_group_forward(ctx, state_dict, images, blocks=None, pooling="max"):
-    """The secure forward of images [B, C, S, S] through a GroupNorm network, composed as
-    tests/secure_avgpool_nets.py's oracle_avg_forward with oracle_group_norm at every norm site: no hoisted Newton, the
-    parameters shared in share_order (no buffers here), the stem in the order SecureResNet18 runs it for `pooling`.
-    state_dict values / images are float32 numpy arrays."""
-    p = {}
-    for k in S.share_order(list(state_dict.keys())):
-        p[k] = ctx.share(S.fix_encode(state_dict[k], ctx.base, ctx.pf))
-    blocks = default_blocks() if blocks is None else blocks
-    x = ctx.share(S.fix_encode(images, ctx.base, ctx.pf))
-
-    def gn(t, prefix):
-        return oracle_group_norm(ctx, t, p[prefix + ".weight"], p[prefix + ".bias"])
-
-    x = gn(ctx.conv2d(x, p["conv1.weight"], 2, 3), "bn1")
-    if pooling == "max":
-        x = ctx.relu(ctx.max_pool2d_3x3s2(x))
-    else:
-        x = oracle_avg_pool(ctx.relu(x), 3, 2, 1)
-    for prefix, stride in blocks:
-        identity = x
-        out = ctx.conv2d(x, p[prefix + ".conv1.weight"], stride, 1)
-        out = ctx.relu(gn(out, prefix + ".bn1"))
-        out = ctx.conv2d(out, p[prefix + ".conv2.weight"], 1, 1)
-        out = gn(out, prefix + ".bn2")
-        if (prefix + ".downsample.0.weight") in p:
-            identity = ctx.conv2d(x, p[prefix + ".downsample.0.weight"], stride, 0)
-            identity = gn(identity, prefix + ".downsample.1")
-        x = ctx.relu(ctx.add(out, identity))
-    x = ctx.avg_pool2d(x, x[0].shape[-1])
-    B = x[0].shape[0]
-    x = [t.reshape(B, -1) for t in x]
-    return ctx.linear(x, p["fc.weight"], p["fc.bias"])
 
 
 def quantise(v, pf):
@@ -179,13 +142,6 @@ def group_mini(gen):
     return sd
 
 
-def three_role_group_case():
-    """(state dict, three 32 x 32 images, blocks) of the three-role GroupNorm test, identical in every process."""
-    gen = torch.Generator().manual_seed(71)
-    sd = group_mini(gen)
-    return sd, torch.randn(3, 3, 32, 32, generator=gen), MINI_BLOCKS
-
-
 # ---- CPU dealers ----------------------------------------------------------------------------------------------------------
 class RecordingDealer:
     """A crypto provider on the host for OracleContext: uniform int64 primitives from a seeded numpy generator, every request
@@ -258,11 +214,3 @@ class ScheduleContext(S.OracleContext):
     def le(self, x1, x2):
         self.dealer.requests.append(("dif_keys", (x1[0].size,)))
         return [np.zeros(x1[0].shape, I64), np.zeros(x1[0].shape, I64)]
-
-
-def walk_requests(state_dict, images, blocks=None, pooling="max", pf=3):
-    """(model requests, image requests) of oracle_group_forward as (kind, args) pairs."""
-    d = RecordingDealer(0)
-    oracle_group_forward(ScheduleContext(d, 10, pf), state_dict, images, blocks, pooling)
-    n_model = len(S.share_order(list(state_dict.keys())))
-    return d.requests[:n_model], d.requests[n_model:]

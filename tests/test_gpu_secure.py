@@ -13,8 +13,8 @@ pytestmark = pytest.mark.gpu
 from oracle import secure_oracle as S  # noqa: E402
 from primia_amd._lib import call  # noqa: E402
 from primia_amd.secure import Dealer, SecureContext, SecureResNet18  # noqa: E402
-
-I64 = torch.int64
+from tests.secure_batch_nets import mini_resnet as mini_state_dict  # noqa: E402
+from tests.secure_common import I64, host, in_process_logits, shares_equal, three_role_logits  # noqa: E402
 
 
 def dev(a, cuda):
@@ -24,10 +24,6 @@ def dev(a, cuda):
     if a.dtype == np.uint32:
         a = a.view(np.int32)
     return torch.from_numpy(a).to(cuda)
-
-
-def host(t):
-    return t.cpu().numpy()
 
 
 def test_layout_kernels_golden(cuda, golden_dir):
@@ -187,10 +183,6 @@ def test_fss_kernels_golden(cuda, golden_dir, kind):
         assert np.array_equal(host(out), g[f"{kind}.out{b}"]), (kind, b)
 
 
-def shares_equal(gpu, ora):
-    return all(np.array_equal(host(gpu[j]), ora[j]) for j in range(2))
-
-
 @pytest.mark.parametrize("pf", [3, 16])
 def test_protocol_ops_bit_exact_vs_oracle(cuda, pf):
     """relu, 9-window max tree, conv2d, Newton BN, avgpool, linear: GPU shares == oracle shares when
@@ -232,36 +224,6 @@ def test_protocol_ops_bit_exact_vs_oracle(cuda, pf):
     if pf == 3:  # sane precision: the decoded values mean something
         dec = ctx.decode(ctx.reconstruct(gout["relu"])).cpu()
         assert torch.allclose(dec, torch.relu((x * 1000).long().float() / 1000), atol=1e-6)
-
-
-def mini_state_dict(gen):
-    sd = {}
-
-    def conv(name, o, i, k):
-        sd[name + ".weight"] = torch.randn(o, i, k, k, generator=gen) * (1.0 / (i * k * k) ** 0.5)
-
-    def bn(name, c):
-        sd[name + ".weight"] = torch.rand(c, generator=gen) + 0.5
-        sd[name + ".bias"] = torch.randn(c, generator=gen) * 0.1
-        sd[name + ".running_mean"] = torch.randn(c, generator=gen) * 0.1
-        sd[name + ".running_var"] = torch.rand(c, generator=gen) + 0.5
-        sd[name + ".num_batches_tracked"] = torch.tensor(1)
-
-    conv("conv1", 64, 3, 7)
-    bn("bn1", 64)
-    conv("layer1.0.conv1", 64, 64, 3)
-    bn("layer1.0.bn1", 64)
-    conv("layer1.0.conv2", 64, 64, 3)
-    bn("layer1.0.bn2", 64)
-    conv("layer2.0.conv1", 128, 64, 3)
-    bn("layer2.0.bn1", 128)
-    conv("layer2.0.conv2", 128, 128, 3)
-    bn("layer2.0.bn2", 128)
-    conv("layer2.0.downsample.0", 128, 64, 1)
-    bn("layer2.0.downsample.1", 128)
-    sd["fc.weight"] = torch.randn(3, 128, generator=gen) * 0.1
-    sd["fc.bias"] = torch.randn(3, generator=gen) * 0.1
-    return sd
 
 
 @pytest.mark.parametrize("pf", [3, 16])
@@ -356,29 +318,9 @@ def test_three_role_deployment_bit_identical_to_in_process(cuda, tmp_path, pf):
     """model_owner / data_owner / crypto_provider as three ranks: party j holds only share j, the
     dealer ships each half of every primitive to its party, opens are 2-party all_reduces.  With the same
     dealer seed the decoded logits equal the in-process run bit for bit, on both parties."""
-    import subprocess
-    import sys
-
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    gen = torch.Generator().manual_seed(21)
-    sd = mini_state_dict(gen)
-    images = torch.randn(2, 3, 16, 16, generator=gen)
-    blocks = [("layer1.0", 1), ("layer2.0", 2)]
-    ctx = SecureContext(Dealer(cuda, seed=5), 10, pf)
-    model = SecureResNet18(ctx, sd, input_size=16, blocks=blocks)
-    want = torch.cat([model(images[i:i + 1].to(cuda)) for i in range(2)]).cpu()
-    out = str(tmp_path / "logits")
-    from tests.conftest import free_port
-
-    port = free_port()
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "tests", "party_worker.py"),
-           out, str(pf)]
-    r = subprocess.run(cmd, cwd=root, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    for j in range(2):
-        assert torch.equal(torch.load(f"{out}.{j}"), want), j
+    want = in_process_logits(cuda, "mini", pf, 5)
+    for j, got in enumerate(three_role_logits("mini", pf, 5, tmp_path)):
+        assert torch.equal(got, want), j
 
 
 def test_eager_forwards_do_not_retain_newton_primitives(cuda):

@@ -4,11 +4,8 @@ only); the pool is a party-local window sum and truncating division by 9, read i
 Kernels and whole networks are held BIT-EXACT to the CPU oracle, the decoded logits to the float64 plaintext forward of the
 avg model, in the eager, graphed, pipelined, three-role and CLI forms."""
 import argparse
-import contextlib
 import json
-import multiprocessing as mp
 import os
-import signal
 import subprocess
 import sys
 
@@ -22,87 +19,14 @@ from oracle import secure_oracle as S  # noqa: E402
 from primia_amd import resnet_spec  # noqa: E402
 from primia_amd._lib import PrimiaError, call  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PipelinedSecureInference, PreloadedDealer,  # noqa: E402
-                               SecureContext, SecureResNet18, architecture_of, image_requests)
-from tests.secure_avgpool_nets import oracle_avg_forward, oracle_avg_pool, plaintext_logits  # noqa: E402
-from tests.secure_batch_nets import MINI_BLOCKS, draw_bn, mini_resnet, numpy_sd, resnet18, three_role_case  # noqa: E402
-from tests.test_gpu_secure_batch import PLAIN_TOL  # noqa: E402  (0.05: the project's bound on pf = 3 logits)
-
-I64 = torch.int64
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 0x5A5A5A5A
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def shares_equal(gpu, ora):
-    return all(np.array_equal(host(gpu[j]), ora[j]) for j in range(2))
-
-
-def context(cuda, seed, pf, fused=True):
-    dealer = Dealer(cuda, seed=seed)
-    dealer.log = []
-    ctx = SecureContext(dealer, 10, pf)
-    ctx.local_fused = fused
-    ctx.fuse_newton = fused
-    return dealer, ctx
-
-
-@contextlib.contextmanager
-def time_limit(seconds):
-    """A test's own time limit: SIGALRM raises in the main thread (a pool.map of the oracle's fan-out wakes up for it)."""
-    def expired(signum, frame):
-        raise TimeoutError(f"test exceeded its own limit of {seconds} s")
-
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-@pytest.fixture(scope="module")
-def oracle_pool():
-    """Worker processes for the oracle's FSS fan-out (spawned: this process holds a HIP context).  Each worker evaluates
-    whole elements of a slice, so the size changes no bit of a result."""
-    try:
-        n = len(os.sched_getaffinity(0))
-    except AttributeError:
-        n = os.cpu_count() or 8
-    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
-    if omp.isdigit() and int(omp) > 0:
-        n = min(n, int(omp))
-    n = max(4, min(64, n))
-    with mp.get_context("spawn").Pool(n) as pool:
-        S.use_pool(pool, n_slices=2 * n)
-        yield pool
-        S.use_pool(None)
+                               SecureContext, SecureResNet18, architecture_of, image_requests, model_requests)
+from tests.secure_avgpool_nets import oracle_avg_pool, plaintext_logits  # noqa: E402
+from tests.secure_batch_nets import MINI_BLOCKS, draw_bn, mini_resnet, numpy_sd, oracle_forward, resnet18  # noqa: E402
+from tests.secure_common import (I64, PLAIN_TOL, ROOT, context, guarded, guards_intact, host, in_process_logits,  # noqa: E402,F401
+                                 oracle_pool, shares_equal, three_role_logits, time_limit, wrapping_shares)
 
 
 # ---- 1. the kernels -----------------------------------------------------------------------------------------------------
-def wrapping_shares(rng, shape):
-    """Uniform int64 with every fifth value within 16 of +-2^63 (the two extremes among them): window sums wrap, and
-    truncation meets the most negative value."""
-    x = rng.integers(-2 ** 63, 2 ** 63 - 1, size=shape, dtype=np.int64, endpoint=True)
-    flat = x.reshape(-1)
-    near = rng.integers(0, 16, size=flat[::5].size, dtype=np.int64)
-    flat[::5] = np.where(rng.integers(0, 2, size=near.size) == 1, np.int64(2 ** 63 - 1) - near, np.int64(-2 ** 63) + near)
-    flat[0], flat[-1] = np.int64(-2 ** 63), np.int64(2 ** 63 - 1)
-    return x
-
-
-def guarded(n, cuda):
-    buf = torch.full((n + 128,), GUARD, dtype=I64, device=cuda)
-    return buf, buf[64:64 + n]
-
-
-def guards_intact(buf, n):
-    return bool((buf[:64] == GUARD).all()) and bool((buf[64 + n:] == GUARD).all())
-
-
 @pytest.mark.parametrize("k,stride,pad", [(3, 2, 1), (7, 7, 0)])
 @pytest.mark.parametrize("shape", [(1, 64, 112, 112), (3, 5, 33, 33), (2, 130, 7, 7)])
 def test_avg_pool_kernels_equal_the_chain_and_the_oracle(cuda, shape, k, stride, pad):
@@ -197,10 +121,10 @@ def test_resnet18_avg_bit_exact(cuda, oracle_pool, B, pf):
     n_model = len(dealer.requests)
     out = model.forward_shares(ctx.share(ctx.encode(images.to(cuda)), owner=1))
     want = image_requests(architecture_of(sd), 32, B, pooling="avg")
-    assert dealer.requests[n_model:] == want
+    assert dealer.requests[n_model:] == want and dealer.requests[:n_model] == model_requests(architecture_of(sd))
     assert dealer.requests[n_model:] != image_requests(architecture_of(sd), 32, B)
     octx = S.OracleContext(S.ReplayDealer(dealer.log), 10, pf)
-    oout = oracle_avg_forward(octx, numpy_sd(sd), images.numpy())
+    oout = oracle_forward(octx, numpy_sd(sd), images.numpy(), pooling="avg")
     assert octx.dealer.pos == len(dealer.log)
     assert tuple(out[0].shape) == (B, 3)
     assert shares_equal(out, oout)
@@ -250,6 +174,7 @@ def test_graphed_avg_matches_eager_and_refills(cuda):
     g = GraphedSecureInference(sd, cuda, input_size=32, precision_fractional=pf, seed=5, blocks=MINI_BLOCKS, batch=2,
                                pooling="avg")
     assert g.requests[g._n_model:] == image_requests(architecture_of(sd), 32, 2, MINI_BLOCKS, pooling="avg")
+    assert g.requests[:g._n_model] == model_requests(architecture_of(sd))
     out_g = g(imgs[:2], refill=False).clone()
     ctx = SecureContext(PreloadedDealer(g.tape, cuda), 10, pf)
     out_e = SecureResNet18(ctx, sd, 32, MINI_BLOCKS, pooling="avg")(imgs[:2])
@@ -323,23 +248,10 @@ def test_three_role_avg_bit_identical_to_in_process(cuda, tmp_path):
     the single-share kernel, the dealer derives the avg schedule): both parties' decoded logits equal the in-process run's
     under the same debug seed."""
     pf, seed = 3, 5
-    sd, images, blocks = three_role_case()
-    ctx = SecureContext(Dealer(cuda, seed=seed), 10, pf)
-    model = SecureResNet18(ctx, sd, input_size=32, blocks=blocks, pooling="avg")
-    dv = images.to(cuda)
-    want = torch.cat([model(dv[:2]), model(torch.cat([dv[2:3], torch.zeros_like(dv[:1])]))[:1]]).cpu()
+    want = in_process_logits(cuda, "avg", pf, seed)
     assert not torch.allclose(want[0], want[1], atol=1e-2)
-    out = str(tmp_path / "logits")
-    from tests.conftest import free_port
-
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
-           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "tests", "party_worker_avgpool.py"),
-           out, str(pf), str(seed)]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    for j in range(2):
-        assert torch.equal(torch.load(f"{out}.{j}"), want), j
+    for j, got in enumerate(three_role_logits("avg", pf, seed, tmp_path)):
+        assert torch.equal(got, want), j
 
 
 # ---- 6. CLI -------------------------------------------------------------------------------------------------------------
@@ -408,7 +320,7 @@ def test_224_resnet18_avg_bit_exact_and_close_to_plaintext(cuda, oracle_pool):
         out = model.forward_shares(ctx.share(ctx.encode(images.to(cuda)), owner=1))
         assert ctx.stats == {"dif_evals": 2_308_096, "beaver_matmul": 21, "beaver_mul": 294}
         octx = S.OracleContext(S.ReplayDealer(dealer.log), 10, pf)
-        oout = oracle_avg_forward(octx, numpy_sd(sd), images.numpy())
+        oout = oracle_forward(octx, numpy_sd(sd), images.numpy(), pooling="avg")
         assert octx.dealer.pos == len(dealer.log)
         assert shares_equal(out, oout)
         dec = host(ctx.decode(ctx.reconstruct(out))).astype(np.float64)

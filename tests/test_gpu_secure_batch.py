@@ -3,7 +3,6 @@ replaying the GPU dealer's stream (oracle/secure_oracle.py's OracleContext is wr
 composed from its methods in tests/secure_batch_nets.py because secure_resnet_forward ends in reshape(1, -1)), on the fused
 in-process path and on the step-by-step path a three-role run executes; B = 1 stays what it was."""
 import json
-import multiprocessing as mp
 import os
 import subprocess
 import sys
@@ -18,50 +17,10 @@ from oracle import secure_oracle as S  # noqa: E402
 from oracle import train_oracle as O  # noqa: E402
 from primia_amd._lib import call  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PipelinedSecureInference, PreloadedDealer,  # noqa: E402
-                               SecureContext, SecureResNet18, architecture_of, image_requests)
-from tests.secure_batch_nets import (MINI_BLOCKS, mini_resnet, numpy_sd, oracle_batch_forward, plain_forward,  # noqa: E402
-                                     resnet18, three_role_case)
-
-I64 = torch.int64
-# max |secure - float64 plaintext| of pf = 3 logits: the bound tests/test_gpu_secure_fullsize.py established for the 224 network
-# (a maximum of 0.047 over 300 dealer draws, 99th percentile 0.030)
-PLAIN_TOL = 0.05
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def shares_equal(gpu, ora):
-    return all(np.array_equal(host(gpu[j]), ora[j]) for j in range(2))
-
-
-def context(cuda, seed, pf, fused):
-    dealer = Dealer(cuda, seed=seed)
-    dealer.log = []
-    ctx = SecureContext(dealer, 10, pf)
-    ctx.local_fused = fused
-    ctx.fuse_newton = fused
-    return dealer, ctx
-
-
-@pytest.fixture(scope="module")
-def oracle_pool():
-    """Worker processes for the oracle's FSS fan-out (spawned: this process holds a HIP context).  Each worker evaluates
-    whole elements of a slice, so the size changes no bit of a result."""
-    try:
-        n = len(os.sched_getaffinity(0))
-    except AttributeError:
-        n = os.cpu_count() or 8
-    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
-    if omp.isdigit() and int(omp) > 0:
-        n = min(n, int(omp))
-    n = max(4, min(64, n))
-    with mp.get_context("spawn").Pool(n) as pool:
-        S.use_pool(pool, n_slices=2 * n)
-        yield pool
-        S.use_pool(None)
+                               SecureContext, SecureResNet18, architecture_of, image_requests, model_requests)
+from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet, numpy_sd, oracle_forward, plain_forward, resnet18  # noqa: E402
+from tests.secure_common import (I64, PLAIN_TOL, ROOT, context, host, in_process_logits, oracle_pool,  # noqa: E402,F401
+                                 shares_equal, three_role_logits)
 
 
 # ---- 0. the layout kernels on their own ---------------------------------------------------------------------------------
@@ -167,8 +126,9 @@ def test_resnet18_batch_of_three_bit_exact(cuda, oracle_pool, pf):
     n_model = len(dealer.requests)
     out = model.forward_shares(ctx.share(ctx.encode(images.to(cuda)), owner=1))
     assert dealer.requests[n_model:] == image_requests(architecture_of(sd), 32, B)
+    assert dealer.requests[:n_model] == model_requests(architecture_of(sd))
     octx = S.OracleContext(S.ReplayDealer(dealer.log), 10, pf)
-    oout = oracle_batch_forward(octx, numpy_sd(sd), images.numpy())
+    oout = oracle_forward(octx, numpy_sd(sd), images.numpy())
     assert octx.dealer.pos == len(dealer.log)
     assert tuple(out[0].shape) == (B, 3)
     assert shares_equal(out, oout)
@@ -190,7 +150,7 @@ def test_one_image_keeps_its_schedule_and_its_bits(cuda):
     n_model = len(dealer.requests)
     model(img)
     want = image_requests(architecture_of(sd), 32, 1)
-    assert dealer.requests[n_model:] == want
+    assert dealer.requests[n_model:] == want and dealer.requests[:n_model] == model_requests(architecture_of(sd))
     assert ("triple", ("matmul", (1, 256, 147), (147, 64)), {}) == want[1 + 1 + 79 * 4]
     g = GraphedSecureInference(sd, cuda, input_size=32, precision_fractional=3, seed=77)
     assert g.batch == 1 and g.requests[g._n_model:] == want and g._n_model == n_model
@@ -209,6 +169,7 @@ def test_graphed_batch_of_two_matches_eager_refills_and_pads(cuda):
     pf = 3
     g = GraphedSecureInference(sd, cuda, input_size=32, precision_fractional=pf, seed=5, blocks=MINI_BLOCKS, batch=2)
     assert g.requests[g._n_model:] == image_requests(architecture_of(sd), 32, 2, MINI_BLOCKS)
+    assert g.requests[:g._n_model] == model_requests(architecture_of(sd))
     out_g = g(imgs[:2], refill=False).clone()
     ctx = SecureContext(PreloadedDealer(g.tape, cuda), 10, pf)
     out_e = SecureResNet18(ctx, sd, 32, MINI_BLOCKS)(imgs[:2])
@@ -331,7 +292,7 @@ def test_224_resnet18_batch_of_two_bit_exact_and_close_to_plaintext(cuda, oracle
     model = SecureResNet18(ctx, sd, 224)
     out = model.forward_shares(ctx.share(ctx.encode(images.to(cuda)), owner=1))
     octx = S.OracleContext(S.ReplayDealer(dealer.log), 10, pf)
-    oout = oracle_batch_forward(octx, numpy_sd(sd), images.numpy())
+    oout = oracle_forward(octx, numpy_sd(sd), images.numpy())
     assert octx.dealer.pos == len(dealer.log)
     assert shares_equal(out, oout)
     assert ctx.stats == {"dif_evals": 2 * 3_311_616, "beaver_matmul": 21, "beaver_mul": 298}
@@ -349,23 +310,10 @@ def test_three_role_batch_bit_identical_to_in_process(cuda, tmp_path):
     """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo, two images per protocol pass and a
     padded second pass (three images): both parties' decoded logits equal the in-process run's under the same debug seed."""
     pf, seed = 3, 5
-    sd, images, blocks = three_role_case()
-    ctx = SecureContext(Dealer(cuda, seed=seed), 10, pf)
-    model = SecureResNet18(ctx, sd, input_size=32, blocks=blocks)
-    dv = images.to(cuda)
-    want = torch.cat([model(dv[:2]), model(torch.cat([dv[2:3], torch.zeros_like(dv[:1])]))[:1]]).cpu()
+    want = in_process_logits(cuda, "batch", pf, seed)
     assert not torch.allclose(want[0], want[1], atol=1e-2)
-    out = str(tmp_path / "logits")
-    from tests.conftest import free_port
-
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
-           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "tests", "party_worker_batch.py"),
-           out, str(pf), str(seed)]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    for j in range(2):
-        assert torch.equal(torch.load(f"{out}.{j}"), want), j
+    for j, got in enumerate(three_role_logits("batch", pf, seed, tmp_path)):
+        assert torch.equal(got, want), j
 
 
 # ---- 7. CLI -------------------------------------------------------------------------------------------------------------

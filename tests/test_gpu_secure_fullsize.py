@@ -7,9 +7,6 @@ end-to-end segment stem -> pool -> relu -> layer1.0 -> head, and the whole ResNe
 and in the graphed serving form, all BIT-EXACT against the CPU oracle replaying the GPU dealer's stream.  The oracle
 fans FSS work out over processes the way the reference does above MULTI_LIMIT (mpc/fss.py:43-44,214-266); the workers are spawned (fresh interpreters, numpy only), never forked from this
 process, which holds a HIP context."""
-import multiprocessing as mp
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -22,31 +19,8 @@ from primia_amd import resnet_spec  # noqa: E402
 from primia_amd._lib import call  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PreloadedDealer, SecureContext,  # noqa: E402
                                SecureResNet18)
-
-I64 = torch.int64
-
-
-def pool_size():
-    """Worker processes for the oracle's FSS fan-out: the CPUs this process may run on (not the host's count), capped by
-    OMP_NUM_THREADS when it is set, with the reference's floor of 4.  Each worker evaluates whole elements of a slice,
-    so the size changes no bit of a result."""
-    try:
-        n = len(os.sched_getaffinity(0))
-    except AttributeError:
-        n = os.cpu_count() or 8
-    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
-    if omp.isdigit() and int(omp) > 0:
-        n = min(n, int(omp))
-    return max(4, min(64, n))
-
-
-@pytest.fixture(scope="module")
-def oracle_pool():
-    n = pool_size()
-    with mp.get_context("spawn").Pool(n) as pool:
-        S.use_pool(pool, n_slices=2 * n)
-        yield pool
-        S.use_pool(None)
+from tests.secure_batch_nets import draw_bn, numpy_sd  # noqa: E402
+from tests.secure_common import I64, PLAIN_TOL, host, oracle_pool, shares_equal  # noqa: E402,F401
 
 
 def dev(a, cuda):
@@ -54,10 +28,6 @@ def dev(a, cuda):
     if a.dtype == np.uint64:
         a = a.view(np.int64)
     return torch.from_numpy(a).to(cuda)
-
-
-def host(t):
-    return t.cpu().numpy()
 
 
 FULL_GEMMS = [(12544, 147, 64), (3136, 576, 64), (784, 1152, 128), (196, 2304, 256), (49, 4608, 512)]
@@ -151,10 +121,6 @@ def test_im2col_of_the_224_stem_and_layer_shapes(cuda):
     assert np.array_equal(host(out), want)
 
 
-def shares_equal(gpu, ora):
-    return all(np.array_equal(host(gpu[j]), ora[j]) for j in range(2))
-
-
 @pytest.mark.parametrize("pf", [16])
 def test_max_pool_tree_and_relu_on_112x112(cuda, oracle_pool, pf):
     """The stem's swapped tail at full size (inference.py:289): the 9-window max tree on [1,64,112,112] — 802,816 +
@@ -177,14 +143,6 @@ def test_max_pool_tree_and_relu_on_112x112(cuda, oracle_pool, pf):
     assert ctx.stats["dif_evals"] == 802_816 + 401_408 + 200_704 + 200_704 + 200_704
     for k in gout:
         assert shares_equal(gout[k], oout[k]), k
-
-
-def draw_bn(sd, name, c, gen):
-    """A BatchNorm that is not the identity: weight U[0.5, 1.5), bias and mean N(0, 0.1), var U[0.5, 1.5)."""
-    sd[name + ".weight"] = torch.rand(c, generator=gen) + 0.5
-    sd[name + ".bias"] = torch.randn(c, generator=gen) * 0.1
-    sd[name + ".running_mean"] = torch.randn(c, generator=gen) * 0.1
-    sd[name + ".running_var"] = torch.rand(c, generator=gen) + 0.5
 
 
 def segment_state_dict(gen):
@@ -246,10 +204,6 @@ def resnet18_224():
     return sd, images
 
 
-def numpy_sd(sd):
-    return {k: v.numpy() for k, v in sd.items()}
-
-
 def test_224_resnet18_eager_bit_exact_against_the_oracle(cuda, oracle_pool, resnet18_224):
     """The whole 224 network on the product's default in-process path (fused local ops) at the reference's literal
     precision_fractional = 16: stem, pool, layer1 on 56x56, layer2-4 on 28x28 / 14x14 / 7x7 with their stride-2 3x3 and
@@ -308,10 +262,6 @@ def plaintext_logits(sd, image, pf):
             sd64[k] = sd64[k] - 1e-5
     with torch.no_grad():
         return O.forward(sd64, q(image), training=False, pooling="max", input_size=224).numpy()
-
-
-# max |secure - float64 plaintext| of the pf = 3 logits at 224 (see the test below for how it was set)
-PLAIN_TOL = 0.05
 
 
 def test_224_graphed_serving_form_bit_exact_against_the_oracle(cuda, oracle_pool, resnet18_224):

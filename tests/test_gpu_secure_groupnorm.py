@@ -5,11 +5,8 @@ float64 plaintext forward, in the eager, graphed, pipelined, three-role and CLI 
 (The bounds come from the CPU composition, tests/secure_groupnorm_nets.py; no MI355X run of this file has been made yet, and
 the kernels' index arithmetic has so far been checked against the oracle in a host model only.)"""
 import argparse
-import contextlib
 import json
-import multiprocessing as mp
 import os
-import signal
 import subprocess
 import sys
 
@@ -23,83 +20,12 @@ from oracle import secure_oracle as S  # noqa: E402
 from primia_amd._lib import PrimiaError, call, query  # noqa: E402
 from primia_amd.engine import ResNet18Engine  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PipelinedSecureInference, PreloadedDealer,  # noqa: E402
-                               SecureContext, SecureResNet18, architecture_of, image_requests)
-from tests.secure_batch_nets import MINI_BLOCKS, numpy_sd, resnet18  # noqa: E402
+                               SecureContext, SecureResNet18, architecture_of, image_requests, model_requests)
+from tests.secure_batch_nets import MINI_BLOCKS, numpy_sd, oracle_forward, resnet18  # noqa: E402
+from tests.secure_common import (I64, ROOT, context, guarded, guards_intact, host, in_process_logits,  # noqa: E402,F401
+                                 oracle_pool, shares_equal, three_role_logits, time_limit, wrapping_shares)
 from tests.secure_groupnorm_nets import (GROUP_TOL, VAR_DOMAIN, ChaChaDealer, default_blocks, group_mini,  # noqa: E402
-                                         group_resnet18, oracle_group_forward, oracle_group_norm, plain_group_forward,
-                                         plaintext_group_logits, three_role_group_case)
-
-I64 = torch.int64
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GUARD = 0x5A5A5A5A
-
-
-def host(t):
-    return t.cpu().numpy()
-
-
-def shares_equal(gpu, ora):
-    return all(np.array_equal(host(gpu[j]), ora[j]) for j in range(2))
-
-
-def context(cuda, seed, pf, fused=True):
-    dealer = Dealer(cuda, seed=seed)
-    dealer.log = []
-    ctx = SecureContext(dealer, 10, pf)
-    ctx.local_fused = fused
-    ctx.fuse_newton = fused
-    return dealer, ctx
-
-
-@contextlib.contextmanager
-def time_limit(seconds):
-    """A test's own time limit: SIGALRM raises in the main thread."""
-    def expired(signum, frame):
-        raise TimeoutError(f"test exceeded its own limit of {seconds} s")
-
-    old = signal.signal(signal.SIGALRM, expired)
-    signal.alarm(seconds)
-    try:
-        yield
-    finally:
-        signal.alarm(0)
-        signal.signal(signal.SIGALRM, old)
-
-
-@pytest.fixture(scope="module")
-def oracle_pool():
-    """Worker processes for the oracle's FSS fan-out (spawned: this process holds a HIP context)."""
-    try:
-        n = len(os.sched_getaffinity(0))
-    except AttributeError:
-        n = os.cpu_count() or 8
-    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
-    if omp.isdigit() and int(omp) > 0:
-        n = min(n, int(omp))
-    n = max(4, min(64, n))
-    with mp.get_context("spawn").Pool(n) as pool:
-        S.use_pool(pool, n_slices=2 * n)
-        yield pool
-        S.use_pool(None)
-
-
-def wrapping_shares(rng, shape):
-    """Uniform int64 with every fifth value within 16 of +-2^63 (the two extremes among them)."""
-    x = rng.integers(-2 ** 63, 2 ** 63 - 1, size=shape, dtype=np.int64, endpoint=True)
-    flat = x.reshape(-1)
-    near = rng.integers(0, 16, size=flat[::5].size, dtype=np.int64)
-    flat[::5] = np.where(rng.integers(0, 2, size=near.size) == 1, np.int64(2 ** 63 - 1) - near, np.int64(-2 ** 63) + near)
-    flat[0], flat[-1] = np.int64(-2 ** 63), np.int64(2 ** 63 - 1)
-    return x
-
-
-def guarded(n, cuda):
-    buf = torch.full((n + 128,), GUARD, dtype=I64, device=cuda)
-    return buf, buf[64:64 + n]
-
-
-def guards_intact(buf, n):
-    return bool((buf[:64] == GUARD).all()) and bool((buf[64 + n:] == GUARD).all())
+                                         group_resnet18, oracle_group_norm, plain_group_forward, plaintext_group_logits)
 
 
 def six(t):
@@ -311,7 +237,7 @@ def test_context_group_norm_fused_equals_steps(cuda, shape):
 @pytest.mark.parametrize("pf", [3, 16])
 @pytest.mark.parametrize("B", [1, 3])
 def test_resnet18_group_bit_exact(cuda, oracle_pool, B, pf):
-    """The 8-block GroupNorm ResNet-18 at 32 x 32: both logit shares equal oracle_group_forward on the replayed dealer log,
+    """The 8-block GroupNorm ResNet-18 at 32 x 32: both logit shares equal oracle_forward(norm="group") on the replayed dealer log,
     which is consumed exactly; the dealer was asked for what image_requests lists; the counters are those of the list."""
     sd = group_resnet18(32, 520)
     images = torch.randn(B, 3, 32, 32, generator=torch.Generator().manual_seed(521))
@@ -322,10 +248,10 @@ def test_resnet18_group_bit_exact(cuda, oracle_pool, B, pf):
     n_model = len(dealer.requests)
     out = model.forward_shares(ctx.share(ctx.encode(images.to(cuda)), owner=1))
     want = image_requests(architecture_of(sd), 32, B)
-    assert dealer.requests[n_model:] == want
+    assert dealer.requests[n_model:] == want and dealer.requests[:n_model] == model_requests(architecture_of(sd))
     assert want != image_requests(architecture_of(resnet18(32, 320)), 32, B)
     octx = S.OracleContext(S.ReplayDealer(dealer.log), 10, pf)
-    oout = oracle_group_forward(octx, numpy_sd(sd), images.numpy())
+    oout = oracle_forward(octx, numpy_sd(sd), images.numpy(), norm="group")
     assert octx.dealer.pos == len(dealer.log)
     assert tuple(out[0].shape) == (B, 3)
     assert shares_equal(out, oout)
@@ -357,7 +283,7 @@ def test_group_logits_follow_the_plaintext_group_model(cuda):
     """pf = 3, the 8-block GroupNorm network at 32 x 32 (seed 520) on three images (seed 521), dealer seed 53: every group
     variance of the float64 forward lies in the Newton domain [0.05, 16] (asserted here on the reference alone), and the
     decoded logits are within GROUP_TOL of plaintext_group_logits.  GROUP_TOL is twice the largest error the CPU composition
-    (oracle_group_forward on ChaChaDealer, the host twin of the device dealer) measured against the same float64 forward:
+    (oracle_forward(norm="group") on ChaChaDealer, the host twin of the device dealer) measured against the same float64 forward:
     see tests/secure_groupnorm_nets.py for the figures."""
     sd = group_resnet18(32, 520)
     images = torch.randn(3, 3, 32, 32, generator=torch.Generator().manual_seed(521))
@@ -386,7 +312,7 @@ def test_graphed_group_matches_eager_across_refills(cuda, B):
     pf = 3
     g = GraphedSecureInference(sd, cuda, input_size=32, precision_fractional=pf, seed=5, blocks=MINI_BLOCKS, batch=B)
     want = image_requests(architecture_of(sd), 32, B, MINI_BLOCKS)
-    assert g.requests[g._n_model:] == want
+    assert g.requests[g._n_model:] == want and g.requests[:g._n_model] == model_requests(architecture_of(sd))
     assert sum(1 for k, a, _ in want if k == "const_mask" and a == (1,)) == 6 * 81
     plain = plain_group_forward(sd, imgs.cpu(), MINI_BLOCKS, pf)
     seen = []
@@ -429,23 +355,10 @@ def test_three_role_group_bit_identical_to_in_process(cuda, tmp_path):
     run the step-by-step chain, the dealer derives the schedule from the architecture, which has no running statistics):
     both parties' decoded logits equal the in-process run's under the same debug seed."""
     pf, seed = 3, 5
-    sd, images, blocks = three_role_group_case()
-    ctx = SecureContext(Dealer(cuda, seed=seed), 10, pf)
-    model = SecureResNet18(ctx, sd, input_size=32, blocks=blocks)
-    dv = images.to(cuda)
-    want = torch.cat([model(dv[:2]), model(torch.cat([dv[2:3], torch.zeros_like(dv[:1])]))[:1]]).cpu()
+    want = in_process_logits(cuda, "group", pf, seed)
     assert not torch.allclose(want[0], want[1], atol=1e-2)
-    out = str(tmp_path / "logits")
-    from tests.conftest import free_port
-
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
-           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "tests", "party_worker_groupnorm.py"),
-           out, str(pf), str(seed)]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    for j in range(2):
-        assert torch.equal(torch.load(f"{out}.{j}"), want), j
+    for j, got in enumerate(three_role_logits("group", pf, seed, tmp_path)):
+        assert torch.equal(got, want), j
 
 
 # ---- 7. CLI ---------------------------------------------------------------------------------------------------------------------
@@ -508,6 +421,7 @@ def test_224_group_graphed_equals_eager(cuda):
         img = torch.randn(1, 3, 224, 224, generator=torch.Generator().manual_seed(225)).to(cuda)
         g = GraphedSecureInference(sd, cuda, input_size=224, precision_fractional=3, seed=9)
         assert g.requests[g._n_model:] == image_requests(architecture_of(sd), 224, 1)
+        assert g.requests[:g._n_model] == model_requests(architecture_of(sd))
         first = g(img, refill=False).clone()
         again = g(img, refill=False).clone()
         ctx = SecureContext(PreloadedDealer(g.tape, cuda), 10, 3)

@@ -5,10 +5,10 @@ import pytest
 import torch
 
 from oracle import secure_oracle as S
-from primia_amd.secure import architecture_of, image_requests, norm_of, primitive_bytes, serving_bytes
-from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet, numpy_sd
-from tests.secure_groupnorm_nets import (LAYER_TOL, VAR_DOMAIN, RecordingDealer, group_mini, group_resnet18,
-                                         oracle_group_norm, walk_requests)
+from primia_amd.secure import architecture_of, image_requests, model_requests, norm_of, primitive_bytes, serving_bytes
+from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet, numpy_sd, oracle_forward, resnet18
+from tests.secure_groupnorm_nets import (LAYER_TOL, VAR_DOMAIN, RecordingDealer, ScheduleContext, group_mini, group_resnet18,
+                                         oracle_group_norm)
 
 
 def test_oracle_group_norm_is_a_group_norm():
@@ -51,20 +51,33 @@ def flat(req):
     return req
 
 
+def walk_requests(state_dict, images, blocks, pooling, norm, pf=3):
+    """(model requests, image requests) of oracle_forward as (kind, args) pairs."""
+    d = RecordingDealer(0)
+    oracle_forward(ScheduleContext(d, 10, pf), state_dict, images, blocks, pooling, norm)
+    n_model = len(S.share_order(list(state_dict.keys())))
+    return d.requests[:n_model], d.requests[n_model:]
+
+
 @pytest.mark.parametrize("pooling", ["max", "avg"])
 @pytest.mark.parametrize("B", [1, 3])
 def test_image_requests_of_a_groupnorm_pass(B, pooling):
-    """image_requests for a GroupNorm architecture equals what a walk of oracle_group_forward asks its dealer for (the mini
-    network and the 8-block ResNet-18 at 32 x 32), has the data owner's mask first and public masks after it, and differs
-    from the BatchNorm list of the same convolutions."""
+    """image_requests equals what a walk of oracle_forward asks its dealer for -- the GroupNorm and the BatchNorm form of the
+    mini network and of the 8-block ResNet-18 at 32 x 32 -- has the data owner's mask first and public masks after it, and
+    the GroupNorm list differs from the BatchNorm list of the same convolutions.  The walk's model part is model_requests
+    (an OracleContext passes no owner on)."""
     images = np.zeros((B, 3, 32, 32), np.float32)
-    for sd, blocks in ((group_mini(torch.Generator().manual_seed(31)), MINI_BLOCKS), (group_resnet18(32, 520), None)):
+    for sd, blocks, norm in ((group_mini(torch.Generator().manual_seed(31)), MINI_BLOCKS, "group"),
+                             (group_resnet18(32, 520), None, "group"),
+                             (mini_resnet(torch.Generator().manual_seed(21)), MINI_BLOCKS, "batch"),
+                             (resnet18(32, 320), None, "batch")):
         arch = architecture_of(sd)
-        assert norm_of(arch) == "group"
+        assert norm_of(arch) == norm
         got = image_requests(arch, 32, B, blocks, pooling)
-        model_req, image_req = walk_requests(numpy_sd(sd), images, blocks, pooling)
+        model_req, image_req = walk_requests(numpy_sd(sd), images, blocks, pooling, norm)
         assert [flat((k, a)) for k, a, _ in got] == [flat(r) for r in image_req]
         assert len(model_req) == len(arch)
+        assert model_req == [(k, a) for k, a, _ in model_requests(arch)]
         assert got[0][2] == {"owner": 1} and all(kw == {"owner": None} for k, _, kw in got[1:] if k == "const_mask")
         assert serving_bytes(arch, 32, B, blocks, pooling) == primitive_bytes(got) + primitive_bytes(got) // 8
     bn = mini_resnet(torch.Generator().manual_seed(21))
