@@ -944,6 +944,12 @@ int primia_newton_reciprocal_local(const int64_t* v0, const int64_t* v1, const i
  *                                DIF evaluations; x1 / x2 may be column ranges [start, start + len) of a [rows][w]
  *                                matrix; x1 == NULL: shares of zero (AST.relu, additive_shared.py:922-925)
  *   primia_max_combine_local     left + (right >= left) * (right - left) (nn/functional.py:494) on column ranges
+ *   primia_argmax_combine_local  one step of the secret-shared argmax walk, visiting class k = `start` of the
+ *                                [B][w] logits with bit = shares of [L_k >= V] from primia_dif_eval_local:
+ *                                D = [L_k - V, K - I] [B, 2], R = bit2 * D (Beaver product on the triple
+ *                                ("mul", (B, 2), (B, 2)), both opens inside, no truncation), V += R[:, 0], I += R[:, 1].
+ *                                k0 / k1: shares of the re-shared constant k [B]; v / i: the running maximum and its index
+ *                                [B], updated IN PLACE (four distinct buffers, none of them an input)
  *   primia_bn_eval_local         batch_norm in eval mode (nn/functional.py:44-75) of one image: NCHW in, NCHW out, both
  *                                FPT products and the row / column re-layouts inside; t1 / t2: HOST arrays of the two
  *                                triples' six pointers (t1: a ~ inv [C], b, c ~ rows [HW, C]; t2: a, c ~ rows, b ~ weight)
@@ -970,6 +976,10 @@ int primia_max_combine_local(const int64_t* bit0, const int64_t* bit1, const int
                              const int64_t* a0, const int64_t* b0, const int64_t* c0, const int64_t* a1, const int64_t* b1,
                              const int64_t* c1, int64_t* out0, int64_t* out1, int64_t rows, int len,
                              primia_stream_t stream);
+int primia_argmax_combine_local(const int64_t* bit0, const int64_t* bit1, const int64_t* logits0, const int64_t* logits1, int w,
+                                int start, const int64_t* k0, const int64_t* k1, const int64_t* a0, const int64_t* b0,
+                                const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1, int64_t* v0,
+                                int64_t* v1, int64_t* i0, int64_t* i1, int64_t B, primia_stream_t stream);
 int primia_bn_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
                          const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
                          const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,

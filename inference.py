@@ -11,7 +11,8 @@ reference's loop, or `--batch_size N` images per protocol pass; the checkpoint's
 of the plain and of every encrypted form, and a checkpoint without BatchNorm running statistics (train.py with
 differentially_private = yes: GroupNorm(32, C) at every norm site) is served as the GroupNorm network, plain and encrypted.
 The encrypted GroupNorm takes its inverse square root from the reference's Newton iteration, which is accurate to under 1 %
-for group variances in about [0.05, 16] (1.6 % off at 0.01, 15 % at 0.001).  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
+for group variances in about [0.05, 16] (1.6 % off at 0.01, 15 % at 0.001).  `--reveal class` ends every encrypted pass with
+a secret-shared argmax and opens the predicted class alone: the logits, the model owner's asset, are never reconstructed.  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
 """
 import argparse
 import json
@@ -93,6 +94,11 @@ if __name__ == "__main__":
                         help="encrypted inference with model_owner, data_owner and crypto_provider as three ranks "
                              "(launch with `python -m torch.distributed.run --nproc-per-node 3 inference.py ...`): "
                              "one GPU each over RCCL when three are visible, else all on GPU 0 over gloo")
+    parser.add_argument("--reveal", choices=("logits", "class"), default="logits",
+                        help="encrypted inference: what a pass opens.  logits (default, the reference): the full score "
+                             "vector, whose argmax is taken in the clear; class: the predicted class alone, through a "
+                             "secret-shared argmax of classes - 1 comparison rounds (the logits are never reconstructed, so "
+                             "PRIMIA_DUMP_LOGITS is refused)")
     parser.add_argument("--debug_dealer_seed", type=int, default=None,
                         help="DEBUG ONLY: derive the crypto provider's key from this number (reproducible, hence "
                              "NOT private); by default the key comes from the OS entropy pool and never leaves the "
@@ -101,6 +107,9 @@ if __name__ == "__main__":
     if cmd_args.debug_dealer_seed is not None:
         print("WARNING: --debug_dealer_seed makes every mask, triple and FSS key predictable: no confidentiality",
               file=sys.stderr)
+    reveal = cmd_args.reveal
+    if reveal == "class" and os.environ.get("PRIMIA_DUMP_LOGITS"):
+        raise SystemExit("--reveal class: the logits are never opened, there is nothing for PRIMIA_DUMP_LOGITS to write")
     if not torch.cuda.is_available():
         raise SystemExit("primia_amd runs inference on the GPU only (HIP kernels); no GPU visible")
     device = torch.device("cuda:0")
@@ -140,26 +149,30 @@ if __name__ == "__main__":
                                     state_dict=sd if link.role == 0 else None,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
-                                    precision_fractional=cmd_args.precision_fractional, pooling=pooling)
+                                    precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
                 sys.exit(0)
-            total_pred = [int(c) for o in logits for c in o.argmax(dim=1).tolist()]
+            # (reveal = class: party 1 holds the class indices themselves)
+            total_pred = [int(c) for o in logits for c in (o if reveal == "class" else o.argmax(dim=1)).tolist()]
             if os.environ.get("PRIMIA_DUMP_LOGITS"):
                 torch.save(torch.cat(logits).cpu(), os.environ["PRIMIA_DUMP_LOGITS"])
         elif cmd_args.hip_graph:
             from primia_amd.secure import GraphedSecureInference
 
             model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
-                                           seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling)
+                                           seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal)
         else:
             ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed), base=10,
                                 precision_fractional=cmd_args.precision_fractional)
-            model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling)
+            model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling, reveal=reveal)
         logits = []
         for i in range(0, 0 if cmd_args.three_role else images.shape[0], bs):
             out = model(images[i:i + bs]).clone()     # (the graphed form returns its static output buffer: keep a copy)
+            if reveal == "class":      # int64 class indices: all the pass opened
+                total_pred += [int(c) for c in out.tolist()]
+                continue
             logits.append(out)
             total_pred += [int(c) for c in out.argmax(dim=1).tolist()]
         if logits and os.environ.get("PRIMIA_DUMP_LOGITS"):

@@ -102,6 +102,31 @@ __global__ __launch_bounds__(256) void max_combine_local_kernel(Pair bit, ColOpe
     }
 }
 
+// ---- one step of the secret-shared argmax walk (defined in tests/secure_argmax_nets.py) --------------------
+// The walk keeps shares of the running maximum V [B] and of its index I [B] and visits class k with bit = [L_k >= V]:
+//   D = stack([L[:, k] - V, K - I], axis=1)   [B, 2]     K: shares of the re-shared public constant k
+//   R = beaver_mul(bit2, D)                              bit2: the bit in both columns; triple ("mul", (B, 2), (B, 2)),
+//   V += R[:, 0]    I += R[:, 1]                         a masks bit2, b masks D; no truncation (the bit is unscaled)
+// Thread i = 2 b + col is element [b][col] of the triple: it forms its element of D, both opens, each party's combine in that
+// party's own arithmetic and updates ITS word of V (col 0) or I (col 1) in place -- no other thread reads or writes that word.
+__global__ __launch_bounds__(256) void argmax_combine_local_kernel(Pair bit, ColOperand logits, Pair kidx, Triple t, OutPair v,
+                                                                   OutPair idx, long B) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < 2 * B; i += stride) {
+        const long b = i >> 1;
+        const bool col = i & 1;
+        u64* const cur0 = (col ? idx.p0 : v.p0) + b;
+        u64* const cur1 = (col ? idx.p1 : v.p1) + b;
+        const long il = b * logits.w + logits.start;
+        const u64 s0 = *cur0, s1 = *cur1;
+        const u64 d0 = (col ? kidx.p0[b] : logits.p0[il]) - s0, d1 = (col ? kidx.p1[b] : logits.p1[il]) - s1;
+        u64 z0, z1;
+        sl_beaver(bit.p0[b], bit.p1[b], d0, d1, t.a0[i], t.b0[i], t.c0[i], t.a1[i], t.b1[i], t.c1[i], z0, z1);
+        *cur0 = s0 + z0;
+        *cur1 = s1 + z1;
+    }
+}
+
 // ---- batch_norm in eval mode (nn/functional.py:44-75), both parties ---------------------------------------------------
 //   rows = x.permute(1,0,2,3).reshape(C,-1).t()                         [B*HW, C], row b*HW + p
 //   normalized = inv * (rows - mean)     (FPT mul: Beaver + truncation; triple t1: a ~ inv [C], b ~ rows, c ~ rows)
@@ -404,6 +429,22 @@ int primia_max_combine_local(const int64_t* bit0, const int64_t* bit1, const int
     max_combine_local_kernel<<<sl_blocks(rows * len), 256, 0, (hipStream_t)st>>>(
         Pair{U(bit0), U(bit1)}, ColOperand{U(left0), U(left1), wl, start_left}, ColOperand{U(right0), U(right1), wr, start_right},
         Triple{U(a0), U(b0), U(c0), U(a1), U(b1), U(c1)}, OutPair{(u64*)out0, (u64*)out1}, rows, len);
+    return launch_status();
+}
+
+int primia_argmax_combine_local(const int64_t* bit0, const int64_t* bit1, const int64_t* logits0, const int64_t* logits1, int w,
+                                int start, const int64_t* k0, const int64_t* k1, const int64_t* a0, const int64_t* b0,
+                                const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1, int64_t* v0,
+                                int64_t* v1, int64_t* i0, int64_t* i1, int64_t B, primia_stream_t st) {
+    PRIMIA_REQUIRE(bit0 && bit1 && logits0 && logits1 && k0 && k1 && a0 && b0 && c0 && a1 && b1 && c1 && v0 && v1 && i0 && i1 &&
+                   B > 0 && w > 0 && start >= 0 && start < w);
+    // V and I are updated in place, one word per thread: the four must be four buffers, and none of them an input
+    PRIMIA_REQUIRE(v0 != v1 && i0 != i1 && v0 != i0 && v0 != i1 && v1 != i0 && v1 != i1);
+    const int64_t* const in[] = {bit0, bit1, logits0, logits1, k0, k1, a0, b0, c0, a1, b1, c1};
+    for (const int64_t* q : in) PRIMIA_REQUIRE(q != v0 && q != v1 && q != i0 && q != i1);
+    argmax_combine_local_kernel<<<sl_blocks(2 * B), 256, 0, (hipStream_t)st>>>(
+        Pair{U(bit0), U(bit1)}, ColOperand{U(logits0), U(logits1), w, start}, Pair{U(k0), U(k1)},
+        Triple{U(a0), U(b0), U(c0), U(a1), U(b1), U(c1)}, OutPair{(u64*)v0, (u64*)v1}, OutPair{(u64*)i0, (u64*)i1}, B);
     return launch_status();
 }
 

@@ -499,6 +499,83 @@ class SecureContext:
 
         return self._each(one)
 
+    # ---- argmax: the tail that opens the predicted class only --------------------------------------------------
+    def argmax(self, x, values=False):
+        """Shares of the first-index argmax over the classes of the logits x [B, C] -- raw, unscaled int64 [B] -- so that a
+        pass can open the predicted class and nothing else.  The reference has no such layer: it is DEFINED here from the
+        reference's operations (tests/secure_argmax_nets.py's oracle_argmax) and is not pinned against the
+        reference.  V = x[:, C-1], I = share(C-1); then for k = C-2 .. 0:
+          bit = le(V, x[:, k])                       dif_keys(B)
+          K   = share(full([B], k))                  const_mask(B): a public constant, re-shared like every other
+          R   = beaver_mul(bit2, [x[:, k] - V, K - I])       triple ("mul", (B, 2), (B, 2)); the bit is unscaled: no truncation
+          V  += R[:, 0];  I += R[:, 1]
+        Walking down with [x_k >= V] sends a tie to the lower index, torch.argmax's rule.  The comparison sees the low 32 bits
+        of the masked difference: the result is the true argmax while all pairwise differences of the encoded logits stay
+        below 2^31, and a deterministic function of the wrapped values otherwise.  (Like every comparison of the reference,
+        one on a difference d errs with probability |d| / 2^32 over the dealer's mask: 2e-7 for two pf = 3 logits 1.0 apart.)
+        Both parties here: two launches per class (primia_dif_eval_local, primia_argmax_combine_local); otherwise the
+        step-by-step chain, which a three-role run executes -- same dealer requests, same bits.
+        values=True: (I, V), with the shares of the maximum as well (tests; a deployment opens I alone)."""
+        xr = self._ref(x)
+        if xr.dim() != 2 or xr.shape[1] < 1:
+            raise ValueError(f"argmax takes logits [B, classes], got {tuple(xr.shape)}")
+        B, C = xr.shape
+        dev = xr.device
+        x = self._each(lambda j: x[j].contiguous())
+        flat = lambda t: [None if q is None else q.view(B) for q in t]
+        V = flat(self._cols(x, B, C, C - 1, 1))
+
+        first = self.share(self._const(C - 1, dev, B))
+
+        def own(j):      # (party 0's share of a fresh sharing IS the dealer's mask: I is updated in place, so it gets buffers of its own)
+            o = _empty_like(first[j])
+            call("primia_ring_scale", first[j], 1, o, B)
+            return o
+
+        I = self._each(own)
+        for k in range(C - 2, -1, -1):
+            if self._local:
+                bit = self._le_local(V, x, B, (B,), (1, 0), (C, k), 1)
+                K = self.share(self._const(k, dev, B))
+                t = self.dealer.triple("mul", (B, 2), (B, 2))
+                call("primia_argmax_combine_local", bit[0], bit[1], x[0], x[1], C, k, K[0], K[1], *_six(t), V[0], V[1], I[0],
+                     I[1], B)
+                self.stats["beaver_mul"] += 1
+                continue
+            Lk = flat(self._cols(x, B, C, k, 1))
+            bit = self.le(V, Lk)
+            K = self.share(self._const(k, dev, B))
+            R = self.beaver_mul(self._stack2(bit, bit, B), self._stack2(self.sub(Lk, V), self.sub(K, I), B))
+            Rt = self._each(lambda j: _transposed(R[j], B, 2))
+            V = self.add(V, self._each(lambda j: Rt[j][0]))
+            I = self.add(I, self._each(lambda j: Rt[j][1]))
+        return (I, V) if values else I
+
+    def _stack2(self, a, b, n):
+        """stack([a, b], axis=1) of two [n] vectors, per share: [n, 2]."""
+        def one(j):
+            rows = torch.empty(2, n, dtype=I64, device=a[j].device)
+            call("primia_ring_scale", a[j], 1, rows[0], n)
+            call("primia_ring_scale", b[j], 1, rows[1], n)
+            return _transposed(rows, 2, n)
+
+        return self._each(one)
+
+    def open_to(self, x, to=1):
+        """Open x towards party `to` alone: the other party sends its share and learns nothing (the reference `.get()`s a
+        prediction to one worker).  With both parties in this process that is `reconstruct`; in a distributed run the
+        receiving party returns the value, the sending party None."""
+        if self.party is None:
+            return self.reconstruct(x)
+        mine = x[self.party]
+        if self.party != to:
+            self.link.send_to_peer(mine)
+            return None
+        theirs = self.link.recv_from_peer(tuple(mine.shape))
+        out = _empty_like(mine)
+        call("primia_ring_add", mine, theirs, out, mine.numel(), mine.numel())
+        return out
+
     # ---- layers (nn/functional.py) ------------------------------------------------------------------
     def conv2d(self, x, w, stride, padding):
         """conv2d (nn/functional.py:204-308): per-share im2col, Beaver matmul + truncation,
@@ -817,6 +894,16 @@ def _check_pooling(pooling):
     return pooling
 
 
+REVEALS = ("logits", "class")
+
+
+def _check_reveal(reveal):
+    """What a pass opens: "logits", the full score vector (the reference's behaviour), or "class", the argmax alone."""
+    if reveal not in REVEALS:
+        raise ValueError(f"reveal must be one of {REVEALS}, got {reveal!r}")
+    return reveal
+
+
 NORMS = ("batch", "group")
 GN_GROUPS = 32      # GroupNorm(32, C) at every norm site: the network train.py builds for differentially_private = yes
 
@@ -872,10 +959,14 @@ class SecureResNet18:
     norm="group" serves the BatchNorm-free network of differentially private training (GroupNorm(32, C) at every norm
     site, no running statistics in the state dict): every norm site is `SecureContext.group_norm`, whose statistics depend
     on the image -- one Beaver square and one 80-step Newton iteration on B * 32 values per layer, online.  Like the avg
-    stem it is NOT pinned against the reference, which has no such layer; it follows the plaintext model."""
+    stem it is NOT pinned against the reference, which has no such layer; it follows the plaintext model.
+
+    reveal="class" ends the pass with `SecureContext.argmax` on the logit shares and opens the class indices alone (to the
+    data owner): the logits, the model owner's asset, are never reconstructed.  "logits" (the default) is the reference's
+    behaviour, unchanged down to the dealer's request list, which is a strict prefix of the class form's."""
 
     def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max",
-                 norm=None):
+                 norm=None, reveal="logits"):
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
         default hoists the image-independent iterations of all BatchNorm layers into one batched vector.  (Ignored with
@@ -885,6 +976,7 @@ class SecureResNet18:
         self.input_size = input_size
         self.batched_newton = batched_newton
         self.pooling = _check_pooling(pooling)
+        self.reveal = _check_reveal(reveal)
         self.norm = norm_of(state_dict.keys(), norm)
         self.blocks = blocks if blocks is not None else _default_blocks()
         if self.norm == "group":
@@ -983,7 +1075,9 @@ class SecureResNet18:
     def __call__(self, image, batch=1):
         """image: fp32 [B, C, S, S] on the GPU -> decoded fp32 logits [B, classes]: the B images go through ONE protocol
         pass.  The data owner is party 1 (inference.py:292-300); in a distributed run party 0 passes image = None and
-        `batch`, the number of images it is to expect (it receives shares, never an image)."""
+        `batch`, the number of images it is to expect (it receives shares, never an image).
+        reveal="class": -> int64 [B] class indices, the only value the pass reconstructs; in a distributed run party 0 sends
+        its share of them to party 1, which returns the classes, and returns None itself."""
         c = self.ctx
         if c.party in (None, 1):
             xs = c.share(c.encode(image), owner=1)
@@ -991,6 +1085,8 @@ class SecureResNet18:
             cin = c._ref(self.p["conv1.weight"]).shape[1]        # 3 (pretrained) or 1 (train.py:262)
             xs = c.share(None, owner=1, shape=(int(batch), cin, self.input_size, self.input_size))
         out = self.forward_shares(xs)
+        if self.reveal == "class":
+            return c.open_to(c.argmax(out), to=1)
         return c.decode(c.reconstruct(out))
 
 
@@ -1004,7 +1100,15 @@ def model_requests(arch):
     return [("const_mask", tuple(arch[k]), {"owner": 0}) for k in share_order(arch)]
 
 
-def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
+def argmax_requests(batch, classes):
+    """What `SecureContext.argmax` on [batch, classes] logits requests: the mask of the first index, then per class walked
+    the comparison keys, the mask of the class's index and the ("mul", (B, 2), (B, 2)) triple of the select."""
+    B = int(batch)
+    mask = ("const_mask", (B,), {"owner": None})
+    return [mask] + (int(classes) - 1) * [("dif_keys", (B,), {}), mask, ("triple", ("mul", (B, 2), (B, 2)), {})]
+
+
+def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits"):
     """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
     `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
     what `SecureResNet18.__call__` asks for (tests hold the two equal), so that the memory a serving form needs is known
@@ -1013,8 +1117,10 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
     pooling="avg": the stem is one ReLU at conv1's output resolution and a party-local average pool that requests nothing
     (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree).
     An architecture without running statistics is the GroupNorm network: no hoisted Newton; every norm site requests its
-    square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples."""
+    square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples.
+    reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix)."""
     _check_pooling(pooling)
+    _check_reveal(reveal)
     B, req = int(batch), []
     blocks = _default_blocks() if blocks is None else blocks
     triple = lambda op, xs, ys: req.append(("triple", (op, tuple(xs), tuple(ys)), {}))
@@ -1084,6 +1190,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max"):
         c, h = o, ho
     classes, feat = arch["fc.weight"]
     triple("matmul", (B, feat), (feat, classes))
+    if reveal == "class":
+        req += argmax_requests(B, classes)
     return req
 
 
@@ -1107,20 +1215,20 @@ def primitive_bytes(requests):
     return total
 
 
-def serving_bytes(arch, input_size, batch, blocks=None, pooling="max"):
+def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits"):
     """What GraphedSecureInference(batch=...) holds in static buffers: every primitive of one pass (dominated by the DIF
     keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image, 2,308,096 with pooling="avg") plus one eighth on top for the arena copy of
     their random words while both exist (5/6 of a triple, 48 of a key's 1,244 bytes) and the captured graph's activations
     (im2col and pool-unroll operands: under 2 % of the keys at every layer)."""
-    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling))
+    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal))
     return b + b // 8
 
 
-def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max"):
+def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max", reveal="logits"):
     """The largest batch whose static buffers fit in `budget` bytes (0: not even one image).  serving_bytes is affine in the
     batch (a per-batch part, Newton and the weight masks, plus a per-image part) up to its rounding, so two evaluations
     give the answer and the neighbours settle the rounding."""
-    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling)
+    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal)
     one, two = need(1), need(2)
     per_image, fixed = two - one, 2 * one - two
     k = max(0, (int(budget) - fixed) // per_image)
@@ -1151,24 +1259,28 @@ class GraphedSecureInference:
     size; fewer images (the last ones of a stream) are padded with all-zero images whose rows consume their own primitives
     and are dropped.  The static buffers are sized on the host first (`serving_bytes`) and a batch that does not fit in
     `memory_budget` bytes (default: the device's free memory plus what torch's allocator holds unused) is refused with the
-    largest batch that would."""
+    largest batch that would.
+
+    reveal="class": the argmax tail is part of the captured graph and the static output is the int64 [batch] buffer of class
+    indices; nothing else is reconstructed."""
 
     refill_graph = True
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
-                 memory_budget=None, pooling="max"):
+                 memory_budget=None, pooling="max", reveal="logits"):
         self.device = torch.device(device)
         self.batch = int(batch)
         self.pooling = _check_pooling(pooling)
+        self.reveal = _check_reveal(reveal)
         if self.batch < 1:
             raise ValueError("batch must be at least 1")
         arch = architecture_of(state_dict)
-        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling)
+        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal)
         if memory_budget is None:
             free, _ = torch.cuda.mem_get_info(self.device)
             memory_budget = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if self.static_bytes > memory_budget:
-            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling)
+            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal)
             raise ValueError(f"a batch of {self.batch} images at {input_size}x{input_size} needs {self.static_bytes} bytes of static "
                              f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
@@ -1176,7 +1288,7 @@ class GraphedSecureInference:
         self.dealer = Dealer(self.device, seed)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
-        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling)
+        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)
         self._n_model = len(self.dealer.tape)          # primitives consumed by sharing the model (kept)
         model(self.image)                              # offline pass: fills the tape, warms every kernel
         self.tape, self.requests = self.dealer.tape, self.dealer.requests
@@ -1185,7 +1297,7 @@ class GraphedSecureInference:
         self._rehome_tape()                            # per-image random words -> one arena (before any pointer is captured)
         pre = PreloadedDealer(self.tape, self.device)
         self._ctx = SecureContext(pre, base, precision_fractional)
-        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling)   # re-shares with the same masks
+        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)   # re-shares with the same masks
         self._model(self.image)                        # eager pass over the static buffers: builds the pointer tables
         pre.pos, self._ctx._newton_calls = self._n_model, 0
         side = torch.cuda.Stream(device=self.device)
@@ -1311,7 +1423,8 @@ class GraphedSecureInference:
         return self.out if n == self.batch else self.out[:n]
 
     def __call__(self, image, refill=True):
-        """image [n <= batch, C, S, S] -> logits [n, classes] (a view of the static output buffer).
+        """image [n <= batch, C, S, S] -> logits [n, classes], or with reveal="class" int64 class indices [n] (a view of the
+        static output buffer).
         refill=False replays on the primitives the buffers hold (bit-identity checks against an eager forward on the
         same tape; a deployment never serves two images on one set of primitives)."""
         if refill:
@@ -1334,10 +1447,11 @@ class PipelinedSecureInference:
     In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU."""
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
-                 batch=1, pooling="max"):
+                 batch=1, pooling="max", reveal="logits"):
         self.device = torch.device(device)
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
-                                             None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling)
+                                             None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling,
+                                             reveal=reveal)
                       for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
@@ -1494,17 +1608,21 @@ def party_context(link: PartyLink, precision_fractional=16, base=10):
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10, batch=1, pooling="max"):
+                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits"):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
     all know the architecture, the input size, the stem pool (`pooling`), how many images will be classified and how many go
     through one protocol pass (`batch`; the last pass is padded with all-zero images, whose rows are dropped).  Parties return the
     list of decoded logits, one [<= batch, classes] tensor per pass (the reference `.get()`s the prediction to the
-    orchestrator), the dealer None."""
+    orchestrator), the dealer None.
+    reveal="class": every pass ends with the argmax tail and party 0 sends its share of the class indices to party 1, which
+    returns one int64 [<= batch] tensor per pass; party 0 learns nothing and returns None, like the dealer, which follows
+    the extended schedule."""
     _check_pooling(pooling)
+    _check_reveal(reveal)
     passes = (n_images + batch - 1) // batch
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
-        image_req = image_requests(arch, input_size, batch, blocks, pooling)
+        image_req = image_requests(arch, input_size, batch, blocks, pooling, reveal)
         svc = DealerService(Dealer(link.device, seed), link)
         svc.serve(model_requests(arch))
         for _ in range(passes):
@@ -1519,7 +1637,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         if images is None:
             raise ValueError("party 1 is the data owner: it needs the images")
         shapes = {k: torch.empty(shape, device="meta") for k, shape in arch.items()}
-    model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling)
+    model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling, reveal=reveal)
     out = []
     for i in range(0, n_images, batch):
         n = min(batch, n_images - i)
@@ -1529,5 +1647,6 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
             if n < batch:
                 chunk = torch.cat([chunk, chunk.new_zeros((batch - n,) + tuple(chunk.shape[1:]))])
         res = model(chunk, batch=batch)
-        out.append(res if n == batch else res[:n])
-    return out
+        if res is not None:
+            out.append(res if n == batch else res[:n])
+    return None if reveal == "class" and link.role == 0 else out
