@@ -494,6 +494,17 @@ int primia_image_add_noise_batch_u8(const int64_t* ptrs, const float* noise, con
 int primia_image_finish_batch(const int64_t* ptrs, int n, int S, int C, const float* mean, const float* std,
                               primia_stream_t stream);
 
+/* NumPy's legacy uniform stream on the device (csrc/mt19937.hip) — replaces the `random_state.rand(h, w)` draws of
+ * albumentations 0.4.6's F.elastic_transform, which made ElasticTransform's two fields on the host.  For every j < n,
+ * out[j * count .. (j + 1) * count) receives, bit for bit, what `rs = np.random.RandomState(seeds[j]);
+ * rs.random_sample(skip)` is positioned to return from `rs.random_sample(count)`: MT19937 seeded by init_genrand, two
+ * 32-bit outputs a, b per double, ((a >> 5) * 2^26 + (b >> 6)) / 2^53.  seeds: DEVICE array of n words, read as unsigned
+ * (a non-negative int32 column of the batch's parameter table serves); out: n x count float64.  With skip = 6 (the
+ * six uniform draws of the transform's random affine) and count = 2 * H * W the rows are primia_warp_elastic_disp_batch's
+ * `fields`.  One generator per seed, its state in LDS; n = 0: nothing to do; 2 * n <= 65535. */
+int primia_mt19937_fields_batch(const uint32_t* seeds, int n, int64_t skip, int64_t count, double* out,
+                                primia_stream_t stream);
+
 /* out[i] = lam * x[i] + one_minus_lam * x[L/2 + i] for i < L/2 over rows of `per_sample` floats (three
  * roundings, like the reference's expression); an odd trailing sample is copied to out[L/2].  The same call
  * mixes the one-hot targets (per_sample = classes).  out has ceil(L/2) rows. */

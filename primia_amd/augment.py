@@ -14,8 +14,9 @@ one of them on) run as written.  `UNBUILT` is empty; `check(args)` stays as the 
 
 The three warping transforms are `cv2.remap` with a generated coordinate field (albumentations 0.4.6, the release the
 reference pins: functional.py elastic_transform / optical_distortion / grid_distortion): the host draws their few
-parameters (ElasticTransform: a seed for numpy's RandomState, whose two uniform fields are the only bulk data that
-crosses to the device), the maps are formed and sampled on the GPU (primia_warp_map_*, primia_image_remap_u8).
+parameters (ElasticTransform: a seed for numpy's RandomState; the per-image path draws its two uniform fields on the host
+and copies them, the batch path generates the same stream on the device, primia_mt19937_fields_batch), the maps are formed
+and sampled on the GPU (primia_warp_map_*, primia_image_remap_u8).
 
 Draw order (Python's `random`, as torchvision's RandomAffine.get_params and albumentations' BasicTransform.__call__ use
 it): affine angle, [translate x, y], scale, shear; crop h, w; Compose coin; then per enabled transform its own coin and,
@@ -27,7 +28,7 @@ Draw and apply are separate.  `draw_plan` (TrainTransform.plan) makes all draws 
 depends on pixel values — and returns them as a plan.  `TrainTransform.__call__` applies a plan to ONE image with the
 per-image entry points (4 to 15 calls and as many small uploads).  `TrainTransform.batch` plans image 0, image 1, ... (the
 `random` stream is consumed exactly as that many `__call__`s consume it), packs every parameter of the batch into one
-table (`pack_plans`; one host-to-device copy, plus one for the elastic fields when ElasticTransform fired) and applies the
+table (`pack_plans`; the batch's one host-to-device copy) and applies the
 chain stage by stage: one C-ABI call per stage (TrainTransform.STAGES) covers every image on which the stage fired
 (csrc/augment_batch.hip, the same per-pixel functions as the per-image kernels: csrc/augment_px.h).  GaussNoise's values
 are requested from torch's generator with the same calls in the same image order.  The tensors equal the per-image chain's
@@ -615,9 +616,9 @@ class TrainTransform:
 
     # the stage kinds of `batch`, in chain order: each is at most ONE C-ABI call per batch (the five members that only the
     # -fast preset switches on — grid_shuffle, hsv, shadow, sun_flare, equalize — go image by image instead)
-    STAGES = ("affine_resize_crop", "clahe", "flip_lut", "blur", "elastic_affine", "elastic_displacements", "elastic_warp",
-              "optical", "grid", "grid_shuffle", "hsv", "invert", "cutout", "shadow", "fog", "fog_blur", "sun_flare",
-              "solarize", "equalize", "grid_dropout", "noise", "finish")
+    STAGES = ("affine_resize_crop", "clahe", "flip_lut", "blur", "elastic_fields", "elastic_affine", "elastic_displacements",
+              "elastic_warp", "optical", "grid", "grid_shuffle", "hsv", "invert", "cutout", "shadow", "fog", "fog_blur",
+              "sun_flare", "solarize", "equalize", "grid_dropout", "noise", "finish")
     # plan key of every member that fires on its own coin -> the configuration switches that enable it
     MEMBERS = {"flip": (), "lut": ("randomgamma", "randombrightness"), "blur": ("blur",), "elastic": ("elastic",),
                "optical": ("optical_distortion",), "grid": ("grid_distortion",), "grid_shuffle": ("grid_shuffle",),
@@ -811,7 +812,7 @@ class TrainTransform:
 
     # ---- a batch: a launch per stage ---------------------------------------------------------------------------------
     def _upload(self, dst, src):
-        """THE host-to-device copy of `batch` (the parameter table; the elastic fields when ElasticTransform fired)."""
+        """THE host-to-device copy of `batch`: the parameter table."""
         dst.copy_(src, non_blocking=True)
 
     def _grow(self, name, nbytes, pinned=False):
@@ -875,14 +876,9 @@ class TrainTransform:
         if n_of("blur.idx"):
             call("primia_image_box_blur_batch_u8", at("blur.ptrs"), at("blur.k"), n_of("blur.idx"), S, C)
         if n_el:
-            # the uniform fields of numpy's RandomState stay a host draw: all firing images' fields in one more copy
-            fields_host = self._grow("fields_host", n_el * 2 * S * S * 8, pinned=True)
-            fh = fields_host.numpy()[:n_el * 2 * S * S * 8].view(np.float64).reshape(n_el, 2, S, S)
-            for j, i in enumerate(tab.view("el.idx")):
-                rs = elastic_affine(S, plans[i]["elastic"])[1]
-                fh[j, 0], fh[j, 1] = rs.rand(S, S), rs.rand(S, S)
+            # the uniform fields of numpy's RandomState(seed), after elastic_affine's six draws, made on the device
             fields = self._grow("fields", n_el * 2 * S * S * 8)
-            self._upload(fields[:fh.nbytes], fields_host[:fh.nbytes])
+            call("primia_mt19937_fields_batch", at("el.seed"), n_el, 6, 2 * S * S, fields)
             wsb = query("primia_warp_elastic_disp_workspace_bytes", n_el, S, S, 50.0)
             gws = self._grow("gauss", wsb)
             call("primia_image_warp_batch_u8", at("ela.ptrs"), at("ela.kind"), at("ela.dp"), n_el, S, C)

@@ -189,9 +189,6 @@ __global__ __launch_bounds__(256) void finish_batch_kernel(const int64_t* __rest
 
 using namespace primia;
 
-// (gridDim.y / gridDim.z carry the image index)
-#define PRIMIA_BATCH_MAX 65535
-
 extern "C" {
 
 int primia_image_affine_resize_crop_batch_u8(const int64_t* ptrs, const int32_t* ip, const float* fp, int n, int C, int R,

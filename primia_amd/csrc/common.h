@@ -150,6 +150,9 @@ static inline int launch_status() {
         if (!(cond)) return PRIMIA_ERR_ARG;  \
     } while (0)
 
+// Most images (or planes) one batched entry point takes: gridDim.y / gridDim.z carry the image index
+#define PRIMIA_BATCH_MAX 65535
+
 // XCD-aware, bijective remap of a 1-D block id: blocks b, b+8, b+16, ... share an XCD (observed
 // placement; speed only), so give each XCD a contiguous range of tiles.
 __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
