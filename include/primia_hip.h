@@ -37,6 +37,7 @@ extern "C" {
 #define PRIMIA_ERR_LAUNCH (-2)      /* HIP launch or runtime error */
 #define PRIMIA_ERR_UNSUPPORTED (-3) /* valid request this build does not implement */
 #define PRIMIA_ERR_WORKSPACE (-4)   /* workspace too small */
+#define PRIMIA_ERR_INTERNAL (-5)    /* a dispatcher was handed a shape its kernel does not serve: a bug in the library */
 
 #define PRIMIA_F32 0
 #define PRIMIA_BF16 1
@@ -197,13 +198,18 @@ int primia_stem_conv_wgrad_ws(const void* x_padded, const void* dy, float* dw_ac
 /* Same, and the per-channel sum / sum of squares of y (values as stored) — the batch statistics of the
  * BatchNorm that follows — are accumulated into stat_sums, laid out [slots][2][K] with
  * slots = primia_conv_stat_slots() partial sums (spread to keep atomics uncontended); caller zeroes it. */
-/* Which kernel the library's dispatch rules select for a convolution (measurement tooling: bench.py names its
- * roofline families with it, so a run under primia_set_option("lh2", 0) / ("s2lh", 7) / ... reports the kernel that
- * actually ran).  pass 0 = forward, 1 = data gradient:
+/* Which kernel the library's dispatch selects for a convolution (measurement tooling: bench.py names its roofline
+ * families with it, so a run under primia_set_option("lh2", 0) / ("s2lh", 7) / ... reports the kernel that actually
+ * ran; the tests assert their routes with it).  Not a copy of the dispatch rules: each pass has ONE route decision
+ * (primia_amd/csrc/conv_route.h: conv_route, wgrad_route — the ids below are the values of its enums), which the entry
+ * points switch on and which these queries, the *_slots / *_ok / *_ws_bytes queries and the engine's buffer sizes all read.
+ * primia_conv_kernel_id answers for the plain call (primia_conv2d_fwd / primia_conv2d_dgrad with accumulate = 0), pass 0 =
+ * forward, 1 = data gradient:
  *   1 conv_igemm_kernel   2 conv3x3_c64_kernel   4 conv3x3_lh2_kernel   (3: conv3x3_lh_kernel, removed in round 4)
  *   5 conv_s2lh_kernel (the stride-2 3x3 / 1x1 layers of the transition blocks on parity planes, round 5)
  *   6 conv3x3_lh4_kernel (the linear-halo layers that take 196-pixel tiles: loader-wave form, round 4)
- * weight gradient:
+ * primia_conv_wgrad_kernel_id answers for the WORKSPACE form (primia_conv2d_wgrad_ws with the workspace of
+ * primia_conv_wgrad_ws_bytes; without one, primia_conv2d_wgrad, the shapes named 17 run on 13 where wide, else 14):
  *   13 conv_wgrad_dma_kernel   14 conv_wgrad_kernel   (11 / 12: the first two patch kernels, removed in round 4)
  *   16 conv_wgrad_patch33_kernel (3 + 3 fragments per k-step, two alternating halves)   17 conv_wgrad_tap_kernel
  *   18 conv_wgrad_patch33lw_kernel (the same scheme on four matrix + four loader waves: the default since round 5)

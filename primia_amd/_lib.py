@@ -15,7 +15,8 @@ LIB_PATH = os.path.join(HERE, "libprimia_hip.so")
 PRIMIA_F32 = 0
 PRIMIA_BF16 = 1
 
-_ERR = {-1: "PRIMIA_ERR_ARG", -2: "PRIMIA_ERR_LAUNCH", -3: "PRIMIA_ERR_UNSUPPORTED", -4: "PRIMIA_ERR_WORKSPACE"}
+_ERR = {-1: "PRIMIA_ERR_ARG", -2: "PRIMIA_ERR_LAUNCH", -3: "PRIMIA_ERR_UNSUPPORTED", -4: "PRIMIA_ERR_WORKSPACE",
+        -5: "PRIMIA_ERR_INTERNAL"}
 
 
 class PrimiaError(RuntimeError):

@@ -771,7 +771,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-// returns PRIMIA_ERR_UNSUPPORTED when the shape is not covered (caller falls back to the implicit GEMM)
+static bool c64_offsets_ok(int N, int H, int W) { return (long)N * H * W * 64 < (1L << 31); }   // 32-bit element offsets
+
+// layer1's shape: 3x3, stride 1, pad 1, 64 -> 64 channels
+bool conv3x3_c64_ok(const ConvGeom& g) {
+    return !g.stem && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.C == 64 && g.K == 64 &&
+           c64_offsets_ok(g.N, g.H, g.W);
+}
+
 int conv3x3_c64_grid(int N, int H, int W) {
     const long total = (long)N * ((H + 7) / 8) * ((W + 7) / 8);
     const int target = PRIMIA_OPT(c64_blocks) > 0 ? PRIMIA_OPT(c64_blocks) : 512;
@@ -783,7 +790,7 @@ int conv3x3_c64_grid(int N, int H, int W) {
 int conv3x3_c64_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int flip, int accumulate,
                          hipStream_t st, float* stat_partials, const uint8_t* acc_mask, const LhBnBwd* bnb,
                          const C64AccBnb* abnb) {
-    if ((long)N * H * W * 64 >= (1L << 31)) return PRIMIA_ERR_UNSUPPORTED;
+    if (!c64_offsets_ok(N, H, W)) return PRIMIA_ERR_INTERNAL;
     const bool with_bnb = bnb && bnb->y;
     const int amode = (abnb && abnb->aux) ? abnb->mode : 0;
     if (with_bnb && (!flip || accumulate || !stat_partials || amode)) return PRIMIA_ERR_ARG;

@@ -1,11 +1,13 @@
-// Interface of the linear-halo 3x3 kernel (conv3x3_lh2.hip) towards the dispatch code in conv_igemm.hip.
+// Interface of the halo convolution kernels towards the dispatch (conv_route.h, conv_igemm.hip): the linear-halo 3x3 /
+// stride-1 kernels (conv3x3_lh2.hip, conv3x3_lh4.hip), the 64 -> 64 kernel (conv3x3_c64.hip) and the transition-block kernel on
+// parity planes (conv_s2lh.hip) — and the device write-back the linear-halo kernels share.
+// Each kernel's shape limits are written ONCE, in its *_ok() / geometry function below; conv_route() calls them, and a
+// dispatcher handed a shape its *_ok() refuses returns PRIMIA_ERR_INTERNAL (the route makes that unreachable).
 #pragma once
 #include "conv_common.h"
 
 namespace primia {
 
-// Linear-halo 3x3 / stride-1 kernel (conv3x3_lh2.hip): persistent 392- / 196-pixel tiles.  (Its first generation,
-// conv3x3_lh.hip — one tile per block, 74.8 us per launch against 55.6 — was superseded in round 3 and removed.)
 // the BatchNorm whose backward sums a plain data-gradient launch forms in its write-back (lh_tile_writeback below)
 struct LhBnBwd {
     const bf16* y;          // [M][Nd], the BatchNorm's input (null: forward statistics)
@@ -26,15 +28,28 @@ struct C64AccBnb {
     const float* c1;
 };
 
-// pixel tiles (= partial slots) if the shape is served by the kernel, else PRIMIA_ERR_UNSUPPORTED
-int conv3x3_lh2_tiles_m(int N, int H, int W, int Cs, int Nd);
+// Linear-halo 3x3 / stride-1 / pad-1 kernels: persistent 392- / 196-pixel tiles x 128 output channels.  Cs / Nd = channels of the
+// tensor read / written (forward C, K; data gradient K, C).
+bool conv3x3_lh_ok(int N, int H, int W, int Cs, int Nd);         // the kernels' shape limits
+int conv3x3_lh_bm(int N, int H, int W, int Cs, int Nd);          // tile height under the options lh2 / lh2_bm, 0: not served
+int conv3x3_lh2_tiles_m(int N, int H, int W, int Cs, int Nd);    // pixel tiles (= partial slots), 0: not served
 int conv3x3_lh_kernel_of(int N, int H, int W, int Cs, int Nd);   // 4 conv3x3_lh2_kernel | 6 conv3x3_lh4_kernel | 0 neither
+// launches the kernel conv3x3_lh_kernel_of() names (the 196-pixel tiles under option lh4 go on to conv3x3_lh4_dispatch)
 int conv3x3_lh2_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int Cs, int Nd, int flip,
                          int accumulate, hipStream_t st, float* stat_partials = nullptr,
                          const uint8_t* acc_mask = nullptr, const LhBnBwd* bnb = nullptr);
+int conv3x3_lh4_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int Cs, int Nd, int flip,
+                         int accumulate, hipStream_t st, float* stat_partials, const uint8_t* acc_mask, const LhBnBwd* bnb);
+
+// 64 -> 64 weight-stationary halo kernel (conv3x3_c64.hip): 3x3 / stride 1 / pad 1; grid = rows of its per-block partial tables
+bool conv3x3_c64_ok(const ConvGeom& g);
+int conv3x3_c64_grid(int N, int H, int W);
+int conv3x3_c64_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int flip, int accumulate,
+                         hipStream_t st, float* stat_partials = nullptr, const uint8_t* acc_mask = nullptr,
+                         const LhBnBwd* bnb = nullptr, const C64AccBnb* abnb = nullptr);
 
 // Transition blocks on the parity planes (conv_s2lh.hip): 3x3 / stride 2 / pad 1 and 1x1 / stride 2 forward (one launch, either
-// filter may be null) and data gradient (the downsample's optional).  PRIMIA_ERR_UNSUPPORTED where conv_s2lh_ok() is false.
+// filter may be null) and data gradient (the downsample's optional), where conv_s2lh_ok().
 bool conv_s2lh_ok(int N, int H, int W, int C, int K);
 int conv_s2lh_tiles_m(int N, int H, int W);
 int conv_s2lh_fwd(const bf16* x, const bf16* w, bf16* y, float* stat, const bf16* w_ds, bf16* y_ds, float* stat_ds, int N,

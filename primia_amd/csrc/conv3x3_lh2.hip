@@ -543,41 +543,41 @@ static int lh2_num_cus() {
     return n;
 }
 
+// what both linear-halo kernels take: the halo buffers hold images up to 28 wide, 64-channel slices in, 128-channel tiles out
+bool conv3x3_lh_ok(int N, int H, int W, int Cs, int Nd) {
+    if (W > 28 || W < 2 || H < 2 || Cs % 64 || Nd % 128) return false;
+    return (long)N * H * W * (Cs > Nd ? Cs : Nd) < (1L << 30);     // byte offsets stay below 2^31
+}
+
 // tile height in pixels for a shape (0: not served).  392 when that gives every CU at least one tile, else 196.
-static int lh2_bm(int N, int H, int W, int Cs, int Nd) {
-    const int off = !PRIMIA_OPT(lh2), force = PRIMIA_OPT(lh2_bm);
-    if (off || W > 28 || W < 2 || H < 2 || Cs % 64 || Nd % 128) return 0;
-    const long M = (long)N * H * W;
-    if (M * (Cs > Nd ? Cs : Nd) >= (1L << 30)) return 0;     // byte offsets stay below 2^31
+int conv3x3_lh_bm(int N, int H, int W, int Cs, int Nd) {
+    const int force = PRIMIA_OPT(lh2_bm);
+    if (!PRIMIA_OPT(lh2) || !conv3x3_lh_ok(N, H, W, Cs, Nd)) return 0;
     if (force == 392 || force == 196) return force;
-    const long t392 = (M + 391) / 392 * (Nd / 128);
+    const long t392 = ((long)N * H * W + 391) / 392 * (Nd / 128);
     return t392 >= lh2_num_cus() ? 392 : 196;
 }
 
-int conv3x3_lh4_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int Cs, int Nd, int flip,
-                         int accumulate, hipStream_t st, float* stat_partials, const uint8_t* acc_mask, const LhBnBwd* bnb);
-
 int conv3x3_lh2_tiles_m(int N, int H, int W, int Cs, int Nd) {
-    const int bm = lh2_bm(N, H, W, Cs, Nd);
-    if (!bm) return PRIMIA_ERR_UNSUPPORTED;
-    return (int)(((long)N * H * W + bm - 1) / bm);
+    const int bm = conv3x3_lh_bm(N, H, W, Cs, Nd);
+    return bm ? (int)(((long)N * H * W + bm - 1) / bm) : 0;
 }
 
 // 4: conv3x3_lh2_kernel serves the shape, 6: conv3x3_lh4_kernel does (196-pixel tiles, option lh4), 0: neither
 int conv3x3_lh_kernel_of(int N, int H, int W, int Cs, int Nd) {
-    const int bm = lh2_bm(N, H, W, Cs, Nd);
+    const int bm = conv3x3_lh_bm(N, H, W, Cs, Nd);
     if (!bm) return 0;
     return bm == 196 && PRIMIA_OPT(lh4) ? 6 : 4;
 }
 
 int conv3x3_lh2_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int Cs, int Nd, int flip,
                          int accumulate, hipStream_t st, float* stat_partials, const uint8_t* acc_mask, const LhBnBwd* bnb) {
-    const int bm = lh2_bm(N, H, W, Cs, Nd);
-    if (!bm) return PRIMIA_ERR_UNSUPPORTED;
+    const int bm = conv3x3_lh_bm(N, H, W, Cs, Nd);
+    if (!bm) return PRIMIA_ERR_INTERNAL;
     // partial sums: forward statistics (plain forward launch), or a BatchNorm's backward sums (plain data-gradient launch + bnb)
     if (stat_partials && (accumulate || (flip != 0) != (bnb != nullptr && bnb->y != nullptr))) return PRIMIA_ERR_ARG;
     if (bnb && bnb->y && !stat_partials) return PRIMIA_ERR_ARG;
-    if (accumulate && !flip) return PRIMIA_ERR_UNSUPPORTED;
+    if (accumulate && !flip) return PRIMIA_ERR_ARG;
     const long M = (long)N * H * W;
     Lh2Params p;
     p.src = src; p.wt = wt; p.dst = dst;
@@ -594,7 +594,7 @@ int conv3x3_lh2_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int 
 #else
     p.prof = nullptr;
 #endif
-    if (bm == 196 && PRIMIA_OPT(lh4))
+    if (conv3x3_lh_kernel_of(N, H, W, Cs, Nd) == 6)
         return conv3x3_lh4_dispatch(src, wt, dst, N, H, W, Cs, Nd, flip, accumulate, st, stat_partials, acc_mask, bnb);
     const int ncu = lh2_num_cus();
     const int grid = p.ntiles < ncu ? p.ntiles : ncu;

@@ -405,11 +405,10 @@ static int lh4_num_cus() {
 int conv3x3_lh4_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int Cs, int Nd, int flip,
                          int accumulate, hipStream_t st, float* stat_partials, const uint8_t* acc_mask, const LhBnBwd* bnb) {
     const int bm = 196;
-    if (W > 28 || W < 2 || H < 2 || Cs % 64 || Nd % 128) return PRIMIA_ERR_UNSUPPORTED;
+    if (!conv3x3_lh_ok(N, H, W, Cs, Nd)) return PRIMIA_ERR_INTERNAL;
     if (stat_partials && (accumulate || (flip != 0) != (bnb != nullptr && bnb->y != nullptr))) return PRIMIA_ERR_ARG;
-    if (accumulate && !flip) return PRIMIA_ERR_UNSUPPORTED;
+    if (accumulate && !flip) return PRIMIA_ERR_ARG;
     const long M = (long)N * H * W;
-    if (M * (Cs > Nd ? Cs : Nd) >= (1L << 30)) return PRIMIA_ERR_UNSUPPORTED;     // byte offsets stay below 2^31
     Lh4Params p;
     p.src = src; p.wt = wt; p.dst = dst;
     p.H = H; p.W = W; p.Cs = Cs; p.Nd = Nd; p.M = (int)M;

@@ -19,7 +19,7 @@
 // v_mfma_f32_16x16x32_bf16 with fp32 accumulation — the throughput path.
 #include <stdlib.h>
 
-#include "conv3x3_lh.h"
+#include "conv_route.h"
 
 namespace primia {
 
@@ -784,9 +784,7 @@ static int igemm_finish_params(IgemmParams& q) {
 
 template <typename T, int BM, int BN, int WM, int WN, int STAGES>
 static int launch_igemm_pair(const IgemmParams& pa, const IgemmParams& pb, hipStream_t st) {
-    IgemmPair pp;
-    pp.a = pa;
-    pp.b = pb;
+    IgemmPair pp = {pa, pb, 0};
     pp.na = igemm_finish_params<BM, BN, false>(pp.a);
     const int nb = igemm_finish_params<BM, BN, false>(pp.b);
     const size_t lds = (size_t)STAGES * (BM + BN) * 128;
@@ -817,41 +815,63 @@ static int launch_igemm(const IgemmParams& p, hipStream_t st) {
     return launch_status();
 }
 
+// 32-bit element offsets into the tensor the tiles are staged from
+static bool igemm_ok(const IgemmParams& p) { return (long)p.Nb * p.Hs * p.Ws * p.Cs < (1L << 31); }
+
 // Tile choice: 128-pixel tile, 8 waves (4 x 2), double-buffered LDS-DMA, 2 blocks/CU — measured fastest on the
 // ResNet-18 shapes (profiles/r01_conv_layers_*.txt): the kernel is bound by the L2 -> LDS fill rate per CU, so waves in
 // flight beat pipeline depth (the 3-stage variants lose the second resident block; DESIGN.md §7 lists the five
 // configurations that were retired).  The per-tile statistics and the BatchNorm-backward write-back assume this tile.
+constexpr int kIgemmBM = 128;
 template <typename T, bool DGRAD>
 static int dispatch_igemm(const IgemmParams& p, bool stem, hipStream_t st) {
     if (stem) {
         if (DGRAD) return PRIMIA_ERR_UNSUPPORTED;
-        return launch_igemm<T, 128, 64, 2, 2, 2, false, true>(p, st);
+        return launch_igemm<T, kIgemmBM, 64, 2, 2, 2, false, true>(p, st);
     }
-    if ((long)p.Nb * p.Hs * p.Ws * p.Cs >= (1L << 31)) return PRIMIA_ERR_ARG;  // 32-bit element offsets
-    return p.Nd % 128 == 0 ? launch_igemm<T, 128, 128, 4, 2, 2, DGRAD, false>(p, st)
-                           : launch_igemm<T, 128, 64, 4, 2, 2, DGRAD, false>(p, st);
+    if (!igemm_ok(p)) return PRIMIA_ERR_ARG;
+    return p.Nd % 128 == 0 ? launch_igemm<T, kIgemmBM, 128, 4, 2, 2, DGRAD, false>(p, st)
+                           : launch_igemm<T, kIgemmBM, 64, 4, 2, 2, DGRAD, false>(p, st);
+}
+
+// The shape fields of a launch (pass 0: forward, dst = y; 1: data gradient, dst = dx, parity classes where the stride-2 input
+// is even-sized); operands, accumulate and the statistics / BatchNorm tables are the caller's
+static IgemmParams igemm_params(const ConvGeom& g, int pass, int dtype) {
+    IgemmParams p = {};
+    p.Nb = g.N; p.R = g.R; p.S = g.S; p.stride = g.stride; p.pad = g.pad;
+    if (pass == 0) {
+        p.Hd = g.Ho; p.Wd = g.Wo; p.Nd = g.K;
+        p.Hs = g.H; p.Ws = g.W; p.Cs = g.C;
+        p.klen = g.klen;
+    } else {
+        p.Hd = g.H; p.Wd = g.W; p.Nd = g.C;
+        p.Hs = g.Ho; p.Ws = g.Wo; p.Cs = g.K;
+        p.klen = g.R * g.S * g.K;
+        p.s2_classes = (g.stride == 2 && g.H % 2 == 0 && g.W % 2 == 0) ? 1 : 0;
+        p.cls_inner = 1;
+    }
+    p.Md = (long)p.Nb * p.Hd * p.Wd;
+    p.nsteps = dtype == PRIMIA_F32 ? (g.stem ? 7 : p.klen / 32) : p.klen / 64;
+    return p;
+}
+
+template <bool DGRAD>
+static int dispatch_igemm_dtype(const IgemmParams& p, bool stem, int dtype, hipStream_t st) {
+    if (dtype == PRIMIA_F32) return dispatch_igemm<float, DGRAD>(p, stem, st);
+    if (dtype == PRIMIA_BF16) return dispatch_igemm<bf16, DGRAD>(p, stem, st);
+    return PRIMIA_ERR_ARG;
 }
 
 }  // namespace primia
 
 using namespace primia;
 
-namespace primia {
-int conv3x3_c64_dispatch(const bf16* src, const bf16* wt, bf16* dst, int N, int H, int W, int flip, int accumulate,
-                         hipStream_t st, float* stat_partials = nullptr, const uint8_t* acc_mask = nullptr,
-                         const LhBnBwd* bnb = nullptr, const C64AccBnb* abnb = nullptr);
-int conv3x3_c64_grid(int N, int H, int W);
-}
-
-// wide 3x3 / stride-1 layers (layer2-4): linear-halo kernel (conv3x3_lh2.hip); option lh2 = 0 keeps the implicit GEMM
-constexpr int kLhFwdMaxW = 30;   // forward only: widest image the linear-halo kernel takes
-static bool lh_shape(const ConvGeom& g) {
-    return !g.stem && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1;
-}
-
-// layer1 shape (3x3, stride 1, pad 1, 64 -> 64 channels, bf16): weight-stationary halo kernel (conv3x3_c64.hip)
-static bool use_c64(const ConvGeom& g) {
-    return !g.stem && g.R == 3 && g.S == 3 && g.stride == 1 && g.pad == 1 && g.C == 64 && g.K == 64;
+// ---- the route ------------------------------------------------------------------------------------------------------------
+// wide 3x3 / stride-1 layers (layer2-4): the linear-halo kernels; option lh2 = 0 keeps the implicit GEMM
+constexpr int kLhFwdMaxW = 30;   // forward only: widest image the dispatch offers them
+static int lh_kernel(const ConvGeom& g, int pass) {    // 4, 6 or 0; Cs, Nd = (C, K) forward, (K, C) data gradient
+    if (g.stem || g.R != 3 || g.S != 3 || g.stride != 1 || g.pad != 1 || (pass == 0 && g.W > kLhFwdMaxW)) return 0;
+    return pass == 0 ? conv3x3_lh_kernel_of(g.N, g.H, g.W, g.C, g.K) : conv3x3_lh_kernel_of(g.N, g.H, g.W, g.K, g.C);
 }
 
 // transition-block shapes served by conv_s2lh_kernel (bf16): 3x3 / 2 / pad 1 or 1x1 / 2 / pad 0 on an even-sized input
@@ -864,11 +884,66 @@ static bool s2_pass_on(int pass, int dx_channels = 0) {
     if (pass == 0) return (o & 2) != 0;
     return (o & 4) != 0 || ((o & 1) != 0 && dx_channels <= kS2DxMax);
 }
-static bool s2_conv1_shape(const ConvGeom& g) {
-    return !g.stem && g.R == 3 && g.S == 3 && g.stride == 2 && g.pad == 1 && conv_s2lh_ok(g.N, g.H, g.W, g.C, g.K);
+static bool s2_shape(const ConvGeom& g, int r) {     // r = 3: conv1 (pad 1), r = 1: the downsample (pad 0)
+    return !g.stem && g.R == r && g.S == r && g.stride == 2 && g.pad == r / 2 && conv_s2lh_ok(g.N, g.H, g.W, g.C, g.K);
 }
-static bool s2_ds_shape(const ConvGeom& g) {
-    return !g.stem && g.R == 1 && g.S == 1 && g.stride == 2 && g.pad == 0 && conv_s2lh_ok(g.N, g.H, g.W, g.C, g.K);
+
+ConvRoute primia::conv_route(const ConvGeom& g, int dtype, ConvForm form) {
+    const ConvRoute none = {PRIMIA_ERR_UNSUPPORTED, 0};
+    const bool bf = dtype == PRIMIA_BF16;
+    if (form == kFwd || form == kFwdStats || form == kFwdPair) {
+        // the pair: both convolutions on 128-channel tiles of one launch
+        if (form == kFwdPair && !(bf && !g.stem && g.R == 3 && g.S == 3 && g.stride == 2 && g.K % 128 == 0 &&
+                                  igemm_ok(igemm_params(g, 0, dtype))))
+            return none;
+        int kernel = kConvIgemm;
+        if (bf && conv3x3_c64_ok(g)) kernel = kConvC64;
+        else if (bf && lh_kernel(g, 0)) kernel = lh_kernel(g, 0);
+        else if (bf && s2_pass_on(0) && (s2_shape(g, 3) || s2_shape(g, 1))) kernel = kConvS2lh;
+        // statistics: one deterministic partial per block / pixel tile out of the write-back; the fp32 and stem launches of
+        // the implicit GEMM add into the primia_conv_stat_slots() atomic slots instead
+        int slots = 0;
+        if (form != kFwd) {
+            if (kernel == kConvC64) slots = conv3x3_c64_grid(g.N, g.H, g.W);
+            else if (kernel == kConvLh2 || kernel == kConvLh4) slots = conv3x3_lh2_tiles_m(g.N, g.H, g.W, g.C, g.K);
+            else if (kernel == kConvS2lh) slots = conv_s2lh_tiles_m(g.N, g.H, g.W);
+            else if (bf && !g.stem) slots = ceil_div((long)g.N * g.Ho * g.Wo, kIgemmBM);
+        }
+        return {kernel, slots};
+    }
+    const bool pair = form == kDgradPair || form == kDgradPairBnSums;
+    const bool acc = form == kDgradAcc || form == kDgradMaskedAcc || form == kDgradMaskedAccBnSums;
+    const bool masked = form == kDgradMaskedAcc || form == kDgradMaskedAccBnSums;
+    const bool sums = form == kDgradBnSums || form == kDgradMaskedAccBnSums || form == kDgradPairBnSums;
+    if (pair && !igemm_params(g, 1, dtype).s2_classes) return none;   // the pairing lives in the parity-class walk
+    if (!bf) return (masked || sums) ? none : ConvRoute{kConvIgemm, 0};
+    if (form == kDgradPairBnSums) {
+        // (asked of the transition-block shapes conv_s2lh_ok() takes, whichever kernel then serves them)
+        if (!s2_shape(g, 3)) return none;
+        if (s2_pass_on(1, g.C)) return g.C == 64 ? ConvRoute{kConvS2lh, 2 * conv_s2lh_tiles_m(g.N, g.H, g.W)} : none;
+        // conv_igemm_kernel's parity-class walk: one partial per (pixel tile, class)
+        return {kConvIgemm, 4 * ceil_div((long)g.N * (g.H / 2) * (g.W / 2), kIgemmBM)};
+    }
+    if (conv3x3_c64_ok(g)) return {kConvC64, sums ? conv3x3_c64_grid(g.N, g.H, g.W) : 0};
+    if (form == kDgradMaskedAccBnSums) return none;     // only the 64 -> 64 accumulate form carries these sums
+    if (!pair && lh_kernel(g, 1))
+        return {lh_kernel(g, 1), sums ? conv3x3_lh2_tiles_m(g.N, g.H, g.W, g.K, g.C) : 0};
+    if (form == kDgradBnSums) return none;
+    if (!acc && s2_pass_on(1, g.C) && s2_shape(g, 3)) return {kConvS2lh, 0};     // conv1 (+ the downsample) on the parity planes
+    if (masked) return none;     // only the 64 -> 64 and linear-halo write-backs mask the old values
+    return {kConvIgemm, 0};
+}
+
+// a valid descriptor's route; the kernel is PRIMIA_ERR_ARG for a bad one
+static ConvRoute route_of(const primia_conv_desc* d, int dtype, ConvForm form) {
+    ConvGeom g;
+    if (!d || !g.init(*d)) return {PRIMIA_ERR_ARG, 0};
+    return conv_route(g, dtype, form);
+}
+// ... as a query's answer: the rows of the form's partial table, 0 where no kernel has the form
+static int route_slots(const primia_conv_desc* d, int dtype, ConvForm form) {
+    const ConvRoute r = route_of(d, dtype, form);
+    return r.kernel == PRIMIA_ERR_ARG ? PRIMIA_ERR_ARG : (r.kernel < 0 ? 0 : r.slots);
 }
 
 extern "C" {
@@ -878,47 +953,28 @@ static int conv2d_fwd_impl(const primia_conv_desc* d, const void* x, const void*
     PRIMIA_REQUIRE(d && x && w_fwd && y);
     ConvGeom g;
     PRIMIA_REQUIRE(g.init(*d));
-    IgemmParams p;
-    p.src = x; p.wt = w_fwd; p.dst = y;
-    p.Nb = g.N; p.Hd = g.Ho; p.Wd = g.Wo; p.Nd = g.K;
-    p.Hs = g.H; p.Ws = g.W; p.Cs = g.C;
-    p.R = g.R; p.S = g.S; p.stride = g.stride; p.pad = g.pad;
-    p.klen = g.klen;
-    p.Md = (long)g.N * g.Ho * g.Wo;
-    p.accumulate = 0;
-    p.stat_sums = stat_sums;
-    p.stat_tiles = (stat_sums && dtype == PRIMIA_BF16 && !g.stem) ? 1 : 0;
-    p.s2_classes = 0;
-    p.bnb_y = nullptr; p.bnb_mask = nullptr; p.bnb_mean = nullptr; p.bnb_invstd = nullptr;
-    p.cls_inner = 0;
-    p.ntm_class = 0;
-    p.src2 = nullptr; p.wt2 = nullptr;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32) {
-        p.nsteps = g.stem ? 7 : g.klen / 32;
-        return dispatch_igemm<float, false>(p, g.stem, st);
-    } else if (dtype == PRIMIA_BF16) {
-        if (use_c64(g)) {  // (its statistics are per-block partials, see primia_conv_stat_slots_for)
-            const int rc = conv3x3_c64_dispatch((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, g.N, g.H, g.W, 0, 0, st,
-                                                stat_sums);
-            if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
-        } else if (lh_shape(g) && g.W <= kLhFwdMaxW) {   // (statistics: per-block partials as well)
-            const int rc2 = conv3x3_lh2_dispatch((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, g.N, g.H, g.W, g.C, g.K, 0,
-                                                 0, st, stat_sums);
-            if (rc2 != PRIMIA_ERR_UNSUPPORTED) return rc2;
-        } else if (s2_pass_on(0) && s2_conv1_shape(g)) {
-            const int rc3 = conv_s2lh_fwd((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, stat_sums, nullptr, nullptr, nullptr, g.N,
-                                          g.H, g.W, g.C, g.K, st);
-            if (rc3 != PRIMIA_ERR_UNSUPPORTED) return rc3;
-        } else if (s2_pass_on(0) && s2_ds_shape(g)) {
-            const int rc3 = conv_s2lh_fwd((const bf16*)x, nullptr, nullptr, nullptr, (const bf16*)w_fwd, (bf16*)y, stat_sums, g.N,
-                                          g.H, g.W, g.C, g.K, st);
-            if (rc3 != PRIMIA_ERR_UNSUPPORTED) return rc3;
-        }
-        p.nsteps = g.klen / 64;
-        return dispatch_igemm<bf16, false>(p, g.stem, st);
+    const ConvRoute r = conv_route(g, dtype, stat_sums ? kFwdStats : kFwd);
+    switch (r.kernel) {
+    case kConvC64:
+        return conv3x3_c64_dispatch((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, g.N, g.H, g.W, 0, 0, st, stat_sums);
+    case kConvLh2:
+    case kConvLh4:
+        return conv3x3_lh2_dispatch((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, g.N, g.H, g.W, g.C, g.K, 0, 0, st, stat_sums);
+    case kConvS2lh: {
+        const bf16 *w1 = g.R == 3 ? (const bf16*)w_fwd : nullptr, *wd = g.R == 3 ? nullptr : (const bf16*)w_fwd;    // conv1 | downsample
+        return conv_s2lh_fwd((const bf16*)x, w1, w1 ? (bf16*)y : nullptr, w1 ? stat_sums : nullptr, wd, wd ? (bf16*)y : nullptr,
+                             wd ? stat_sums : nullptr, g.N, g.H, g.W, g.C, g.K, st);
     }
-    return PRIMIA_ERR_ARG;
+    case kConvIgemm: {
+        IgemmParams p = igemm_params(g, 0, dtype);
+        p.src = x; p.wt = w_fwd; p.dst = y;
+        p.stat_sums = stat_sums;
+        p.stat_tiles = r.slots > 0;       // else the primia_conv_stat_slots() atomic slots
+        return dispatch_igemm_dtype<false>(p, g.stem, dtype, st);
+    }
+    }
+    return PRIMIA_ERR_INTERNAL;
 }
 
 int primia_conv2d_fwd(const primia_conv_desc* d, const void* x, const void* w_fwd, void* y, int dtype,
@@ -926,20 +982,17 @@ int primia_conv2d_fwd(const primia_conv_desc* d, const void* x, const void* w_fw
     return conv2d_fwd_impl(d, x, w_fwd, y, nullptr, dtype, stream);
 }
 
-// a transition block's conv1 (3x3 / 2) and downsample (1x1 / 2) forward in one launch: both on the bf16 implicit GEMM,
-// same input, output channels a multiple of 128
-static bool fwd_pair_shape(const ConvGeom& g, const ConvGeom& gd, int dtype) {
-    if (dtype != PRIMIA_BF16 || g.stem || gd.stem) return false;
-    if (gd.N != g.N || gd.H != g.H || gd.W != g.W || gd.C != g.C || gd.Ho != g.Ho || gd.Wo != g.Wo) return false;
-    if (g.stride != 2 || gd.stride != 2 || g.R != 3 || g.S != 3 || gd.R != 1 || gd.S != 1 || gd.pad != 0) return false;
-    if (g.K % 128 || gd.K % 128) return false;
-    return (long)g.N * g.H * g.W * g.C < (1L << 31);
+// a transition block's conv1 (3x3 / 2) and downsample (1x1 / 2) forward in one launch: the downsample of the same input,
+// output channels a multiple of 128 as well
+static bool fwd_pair_partner(const ConvGeom& g, const ConvGeom& gd) {
+    return !gd.stem && gd.N == g.N && gd.H == g.H && gd.W == g.W && gd.C == g.C && gd.Ho == g.Ho && gd.Wo == g.Wo &&
+           gd.stride == 2 && gd.R == 1 && gd.S == 1 && gd.pad == 0 && gd.K % 128 == 0;
 }
 
 int primia_conv_fwd_pair_ok(const primia_conv_desc* d, const primia_conv_desc* d_ds, int dtype) {
     ConvGeom g, gd;
     if (!d || !d_ds || !g.init(*d) || !gd.init(*d_ds)) return PRIMIA_ERR_ARG;
-    return fwd_pair_shape(g, gd, dtype) ? 1 : 0;
+    return fwd_pair_partner(g, gd) && conv_route(g, dtype, kFwdPair).kernel > 0 ? 1 : 0;
 }
 
 int primia_conv2d_fwd_stats_pair(const primia_conv_desc* d, const void* x, const void* w_fwd, void* y, float* stat_sums,
@@ -948,82 +1001,47 @@ int primia_conv2d_fwd_stats_pair(const primia_conv_desc* d, const void* x, const
     PRIMIA_REQUIRE(d && d_ds && x && w_fwd && y && w_fwd_ds && y_ds);
     ConvGeom g, gd;
     PRIMIA_REQUIRE(g.init(*d) && gd.init(*d_ds));
-    if (!fwd_pair_shape(g, gd, dtype)) return PRIMIA_ERR_UNSUPPORTED;
-    if (s2_pass_on(0) && s2_conv1_shape(g) && s2_ds_shape(gd) && g.pad == 1 && (stat_sums == nullptr) == (stat_sums_ds == nullptr)) {
-        const int rc = conv_s2lh_fwd((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, stat_sums, (const bf16*)w_fwd_ds,
-                                     (bf16*)y_ds, stat_sums_ds, g.N, g.H, g.W, g.C, g.K, (hipStream_t)stream);
-        if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
+    ConvRoute r = conv_route(g, dtype, kFwdPair);
+    if (!fwd_pair_partner(g, gd) || r.kernel < 0) return PRIMIA_ERR_UNSUPPORTED;
+    // conv_s2lh_kernel takes ONE output width and writes both statistics tables or neither
+    if (r.kernel == kConvS2lh && (gd.K != g.K || (stat_sums == nullptr) != (stat_sums_ds == nullptr))) r.kernel = kConvIgemm;
+    switch (r.kernel) {
+    case kConvS2lh:
+        return conv_s2lh_fwd((const bf16*)x, (const bf16*)w_fwd, (bf16*)y, stat_sums, (const bf16*)w_fwd_ds, (bf16*)y_ds,
+                             stat_sums_ds, g.N, g.H, g.W, g.C, g.K, (hipStream_t)stream);
+    case kConvIgemm: {
+        IgemmParams pa = igemm_params(g, 0, dtype), pb = igemm_params(gd, 0, dtype);
+        pa.src = x; pa.wt = w_fwd; pa.dst = y;
+        pa.stat_sums = stat_sums; pa.stat_tiles = stat_sums ? 1 : 0;
+        pb.src = x; pb.wt = w_fwd_ds; pb.dst = y_ds;
+        pb.stat_sums = stat_sums_ds; pb.stat_tiles = stat_sums_ds ? 1 : 0;
+        return launch_igemm_pair<bf16, kIgemmBM, 128, 4, 2, 2>(pa, pb, (hipStream_t)stream);
     }
-    auto fill = [&](IgemmParams& p, const ConvGeom& c, const void* w, void* out, float* sums) {
-        p.src = x; p.wt = w; p.dst = out;
-        p.Nb = c.N; p.Hd = c.Ho; p.Wd = c.Wo; p.Nd = c.K;
-        p.Hs = c.H; p.Ws = c.W; p.Cs = c.C;
-        p.R = c.R; p.S = c.S; p.stride = c.stride; p.pad = c.pad;
-        p.klen = c.klen;
-        p.nsteps = c.klen / 64;
-        p.Md = (long)c.N * c.Ho * c.Wo;
-        p.accumulate = 0;
-        p.stat_sums = sums;
-        p.stat_tiles = sums ? 1 : 0;
-        p.s2_classes = 0;
-        p.bnb_y = nullptr; p.bnb_mask = nullptr; p.bnb_mean = nullptr; p.bnb_invstd = nullptr;
-        p.cls_inner = 0;
-        p.ntm_class = 0;
-        p.src2 = nullptr; p.wt2 = nullptr;
-    };
-    IgemmParams pa, pb;
-    fill(pa, g, w_fwd, y, stat_sums);
-    fill(pb, gd, w_fwd_ds, y_ds, stat_sums_ds);
-    return launch_igemm_pair<bf16, 128, 128, 4, 2, 2>(pa, pb, (hipStream_t)stream);
+    }
+    return PRIMIA_ERR_INTERNAL;
 }
 
+// What the dispatch runs for the plain forward (pass 0) or the plain data gradient (pass 1) of `d`.  (The engine's bf16 stem
+// runs primia_stem_conv_fwd on the padded input, stem_conv_fwd_kernel: this names the generic call's kernel.)
 int primia_conv_kernel_id(const primia_conv_desc* d, int pass, int dtype) {
-    ConvGeom g;
-    if (!d || !g.init(*d) || (pass != 0 && pass != 1)) return PRIMIA_ERR_ARG;
-    if (dtype != PRIMIA_BF16) return 1;
-    if (g.stem) return 1;     // (the engine's bf16 stem runs primia_stem_conv_fwd on the padded input: stem_conv_fwd_kernel)
-    if (use_c64(g) && (long)g.N * g.H * g.W * 64 < (1L << 31)) return 2;
-    if (lh_shape(g) && (pass == 1 || g.W <= kLhFwdMaxW)) {
-        const int cs = pass == 0 ? g.C : g.K, nd = pass == 0 ? g.K : g.C;
-        const int lk = conv3x3_lh_kernel_of(g.N, g.H, g.W, cs, nd);
-        if (lk) return lk;
-    }
-    if (s2_pass_on(pass, g.C) && (s2_conv1_shape(g) || (pass == 0 && s2_ds_shape(g)))) return 5;
-    return 1;
+    if (pass != 0 && pass != 1) return PRIMIA_ERR_ARG;
+    return route_of(d, dtype, pass == 0 ? kFwd : kDgrad).kernel;
 }
 
 int primia_conv_stat_slots(void) { return kStatSlots; }
 
-// slots of the kernel serving this conv; *per_tile: 1 = deterministic per-tile partials WRITTEN by its write-back (nothing
-// to zero, no extra pass), 0 = the kStatSlots atomic slots
-static int conv_stat_slots_impl(const primia_conv_desc* d, int dtype, int* per_tile) {
-    ConvGeom g;
-    *per_tile = 0;
-    if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
-    *per_tile = 1;
-    if (dtype == PRIMIA_BF16 && use_c64(g) && (long)g.N * g.H * g.W * 64 < (1L << 31)) return conv3x3_c64_grid(g.N, g.H, g.W);
-    if (dtype == PRIMIA_BF16 && !use_c64(g) && lh_shape(g) && g.W <= kLhFwdMaxW) {
-        const int t2 = conv3x3_lh2_tiles_m(g.N, g.H, g.W, g.C, g.K);
-        if (t2 > 0) return t2;
-    }
-    if (dtype == PRIMIA_BF16 && s2_pass_on(0) && (s2_conv1_shape(g) || s2_ds_shape(g))) return conv_s2lh_tiles_m(g.N, g.H, g.W);
-    // bf16 implicit GEMM: one partial per 128-pixel tile out of its write-back (every tile config in use has BM = 128)
-    if (dtype == PRIMIA_BF16 && !g.stem && g.K % 8 == 0) return (int)(((long)g.N * g.Ho * g.Wo + 127) / 128);
-    *per_tile = 0;
-    return kStatSlots;
-}
-
+// slots of the kernel serving this conv: its per-tile partials where it WRITES them (nothing to zero, no extra pass), else
+// the kStatSlots atomic slots
 int primia_conv_stat_slots_for(const primia_conv_desc* d, int dtype) {
-    int per_tile;
-    return conv_stat_slots_impl(d, dtype, &per_tile);
+    const int slots = route_slots(d, dtype, kFwdStats);
+    return slots == 0 ? kStatSlots : slots;
 }
 
 // 1: this conv's forward kernel writes the BatchNorm partial sums for free (per-tile, deterministic); 0: atomic slots.
 // (The slot COUNT does not tell: layer4's 3x3 convs at batch 256 have 64 tiles, which is also kStatSlots.)
 int primia_conv_stats_per_tile(const primia_conv_desc* d, int dtype) {
-    int per_tile;
-    const int rc = conv_stat_slots_impl(d, dtype, &per_tile);
-    return rc < 0 ? rc : per_tile;
+    const int slots = route_slots(d, dtype, kFwdStats);
+    return slots < 0 ? slots : (slots > 0 ? 1 : 0);
 }
 
 int primia_conv2d_fwd_stats(const primia_conv_desc* d, const void* x, const void* w_fwd, void* y, float* stat_sums,
@@ -1032,122 +1050,88 @@ int primia_conv2d_fwd_stats(const primia_conv_desc* d, const void* x, const void
     return conv2d_fwd_impl(d, x, w_fwd, y, stat_sums, dtype, stream);
 }
 
-static int conv2d_dgrad_impl(const primia_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
-                             int accumulate, const void* dy2, const void* w_dgrad2, int dtype, primia_stream_t stream,
-                             const uint8_t* acc_mask = nullptr, const S2BnBwd* pair_bnb = nullptr,
-                             const C64AccBnb* acc_bnb = nullptr, float* acc_sums = nullptr) {
+// what the forms beyond the plain data gradient carry
+struct DgradExtra {
+    const void *dy2 = nullptr, *w_dgrad2 = nullptr;     // pair: the downsample's dy and filter
+    const uint8_t* acc_mask = nullptr;       // masked accumulate: ReLU bits applied to the old dx
+    const LhBnBwd* bnb = nullptr;            // the BatchNorm whose backward sums the write-back forms, per form
+    const C64AccBnb* acc_bnb = nullptr;
+    const S2BnBwd* pair_bnb = nullptr;
+    float* sums = nullptr;                   // ... their partial table (S2BnBwd carries its own)
+};
+
+static int conv2d_dgrad_impl(const primia_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, ConvForm form,
+                             int dtype, primia_stream_t stream, const DgradExtra& e = DgradExtra()) {
     PRIMIA_REQUIRE(d && dy && w_dgrad && dx);
     ConvGeom g;
-    PRIMIA_REQUIRE(g.init(*d));
-    PRIMIA_REQUIRE(!g.stem && (g.stride == 1 || g.stride == 2));
-    IgemmParams p;
-    p.src2 = dy2; p.wt2 = w_dgrad2;
-    p.src = dy; p.wt = w_dgrad; p.dst = dx;
-    p.Nb = g.N; p.Hd = g.H; p.Wd = g.W; p.Nd = g.C;
-    p.Hs = g.Ho; p.Ws = g.Wo; p.Cs = g.K;
-    p.R = g.R; p.S = g.S; p.stride = g.stride; p.pad = g.pad;
-    p.klen = g.R * g.S * g.K;
-    p.Md = (long)g.N * g.H * g.W;
-    p.accumulate = accumulate;
-    p.stat_sums = nullptr;
-    p.stat_tiles = 0;
-    p.bnb_y = nullptr; p.bnb_mask = nullptr; p.bnb_mean = nullptr; p.bnb_invstd = nullptr;
-    p.s2_classes = (g.stride == 2 && g.H % 2 == 0 && g.W % 2 == 0) ? 1 : 0;
-    p.cls_inner = 1;
-    p.ntm_class = 0;
-    if (p.src2 && !p.s2_classes) return PRIMIA_ERR_UNSUPPORTED;   // the pairing lives in the parity-class walk
+    PRIMIA_REQUIRE(g.init(*d) && !g.stem && (g.stride == 1 || g.stride == 2));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32) {
-        p.nsteps = p.klen / 32;
-        return dispatch_igemm<float, true>(p, false, st);
-    } else if (dtype == PRIMIA_BF16) {
-        if (use_c64(g)) {
-            const int rc = conv3x3_c64_dispatch((const bf16*)dy, (const bf16*)w_dgrad, (bf16*)dx, g.N, g.H, g.W, 1,
-                                                accumulate, st, acc_sums, acc_mask, nullptr, acc_bnb);
-            if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
+    const int accumulate = form == kDgradAcc || form == kDgradMaskedAcc || form == kDgradMaskedAccBnSums;
+    const ConvRoute r = conv_route(g, dtype, form);
+    if (r.kernel < 0) return r.kernel;
+    switch (r.kernel) {
+    case kConvC64:
+        return conv3x3_c64_dispatch((const bf16*)dy, (const bf16*)w_dgrad, (bf16*)dx, g.N, g.H, g.W, 1, accumulate, st, e.sums,
+                                    e.acc_mask, e.bnb, e.acc_bnb);
+    case kConvLh2:
+    case kConvLh4:
+        return conv3x3_lh2_dispatch((const bf16*)dy, (const bf16*)w_dgrad, (bf16*)dx, g.N, g.H, g.W, g.K, g.C, 1, accumulate, st,
+                                    e.sums, e.acc_mask, e.bnb);
+    case kConvS2lh:
+        return conv_s2lh_dgrad((const bf16*)dy, (const bf16*)w_dgrad, (const bf16*)e.dy2, (const bf16*)e.w_dgrad2, (bf16*)dx, g.N,
+                               g.H, g.W, g.C, g.K, st, e.pair_bnb);
+    case kConvIgemm: {
+        IgemmParams p = igemm_params(g, 1, dtype);
+        p.src = dy; p.wt = w_dgrad; p.dst = dx;
+        p.src2 = e.dy2; p.wt2 = e.w_dgrad2;
+        p.accumulate = accumulate;
+        if (e.pair_bnb) {
+            p.bnb_y = e.pair_bnb->y; p.bnb_mask = e.pair_bnb->mask; p.bnb_mean = e.pair_bnb->mean; p.bnb_invstd = e.pair_bnb->invstd;
+            p.stat_sums = e.pair_bnb->sums;
         }
-        if (acc_bnb) return PRIMIA_ERR_UNSUPPORTED;     // only the 64 -> 64 accumulate form carries these sums
-        if (!use_c64(g) && lh_shape(g) && !p.src2) {
-            const int rc2 = conv3x3_lh2_dispatch((const bf16*)dy, (const bf16*)w_dgrad, (bf16*)dx, g.N, g.H, g.W, g.K, g.C,
-                                                 1, accumulate, st, nullptr, acc_mask);
-            if (rc2 != PRIMIA_ERR_UNSUPPORTED) return rc2;
-        }
-        if (!accumulate && !acc_mask && s2_pass_on(1, g.C) && s2_conv1_shape(g)) {     // transition block: conv1 (+ the downsample) on the parity planes
-            const int rc3 = conv_s2lh_dgrad((const bf16*)dy, (const bf16*)w_dgrad, (const bf16*)dy2, (const bf16*)w_dgrad2,
-                                            (bf16*)dx, g.N, g.H, g.W, g.C, g.K, st);
-            if (rc3 != PRIMIA_ERR_UNSUPPORTED) return rc3;
-        }
-        if (acc_mask) return PRIMIA_ERR_UNSUPPORTED;   // only the 64->64 and linear-halo write-backs mask the old values
-        if (pair_bnb) {
-            p.bnb_y = pair_bnb->y; p.bnb_mask = pair_bnb->mask; p.bnb_mean = pair_bnb->mean; p.bnb_invstd = pair_bnb->invstd;
-            p.stat_sums = pair_bnb->sums;
-        }
-        p.nsteps = p.klen / 64;
-        return dispatch_igemm<bf16, true>(p, false, st);
+        return dispatch_igemm_dtype<true>(p, false, dtype, st);
     }
-    return PRIMIA_ERR_ARG;
+    }
+    return PRIMIA_ERR_INTERNAL;
 }
 
-// The plain data gradient of a wide 3x3 / stride-1 layer that ALSO forms, in its write-back, the two sums the BatchNorm backward
-// of the layer in front of it needs (dx = dz of that layer: sum g and sum g * xhat per channel, g = dz * [bn(y) > 0]) as per-tile
-// partials — the separate reduction pass over (y, dz) is dropped (conv3x3_lh.h: LhBnBwd; primia_bn_relu_bwd_from_sums consumes
-// them).  Slots of the partial table [slots][2][C], or 0 where the linear-halo kernels do not serve the shape.
-int primia_conv_dgrad_bnsums_slots(const primia_conv_desc* d, int dtype) {
-    ConvGeom g;
-    if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
-    if (dtype != PRIMIA_BF16 || !lh_shape(g)) return 0;
-    if (use_c64(g)) return (long)g.N * g.H * g.W * 64 < (1L << 31) ? conv3x3_c64_grid(g.N, g.H, g.W) : 0;
-    const int t = conv3x3_lh2_tiles_m(g.N, g.H, g.W, g.K, g.C);
-    return t > 0 ? t : 0;
-}
+// The data gradients whose write-back also forms a BatchNorm's backward sums as per-tile partials [slots][2][C] (what each form
+// sums and who consumes it: include/primia_hip.h).  Plain, in front of a wide 3x3 / stride-1 layer (LhBnBwd): linear-halo and
+// 64 -> 64 kernels; slots = 0 elsewhere.
+int primia_conv_dgrad_bnsums_slots(const primia_conv_desc* d, int dtype) { return route_slots(d, dtype, kDgradBnSums); }
 
 int primia_conv2d_dgrad_bnsums(const primia_conv_desc* d, const void* dy, const void* w_dgrad, void* dx, const void* bn_y,
                                const float* bn_mean, const float* bn_invstd, const float* bn_gamma, const float* bn_beta,
                                float* sums, int dtype, primia_stream_t stream) {
     PRIMIA_REQUIRE(d && dy && w_dgrad && dx && bn_y && bn_mean && bn_invstd && bn_gamma && bn_beta && sums);
     if (primia_conv_dgrad_bnsums_slots(d, dtype) <= 0) return PRIMIA_ERR_UNSUPPORTED;
-    ConvGeom g;
-    PRIMIA_REQUIRE(g.init(*d));
     const LhBnBwd bnb{(const bf16*)bn_y, bn_mean, bn_invstd, bn_gamma, bn_beta};
-    if (use_c64(g))
-        return conv3x3_c64_dispatch((const bf16*)dy, (const bf16*)w_dgrad, (bf16*)dx, g.N, g.H, g.W, 1, 0, (hipStream_t)stream, sums,
-                                    nullptr, &bnb);
-    return conv3x3_lh2_dispatch((const bf16*)dy, (const bf16*)w_dgrad, (bf16*)dx, g.N, g.H, g.W, g.K, g.C, 1, 0,
-                                (hipStream_t)stream, sums, nullptr, &bnb);
+    DgradExtra e;
+    e.bnb = &bnb; e.sums = sums;
+    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, kDgradBnSums, dtype, stream, e);
 }
 
 int primia_conv2d_dgrad(const primia_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                         int accumulate, int dtype, primia_stream_t stream) {
-    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, accumulate, nullptr, nullptr, dtype, stream);
+    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, accumulate ? kDgradAcc : kDgrad, dtype, stream);
 }
 
 int primia_conv_dgrad_masked_acc_ok(const primia_conv_desc* d, int dtype) {
-    ConvGeom g;
-    if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
-    if (dtype != PRIMIA_BF16) return 0;
-    if (use_c64(g)) return (long)g.N * g.H * g.W * 64 < (1L << 31) ? 1 : 0;
-    return lh_shape(g) && conv3x3_lh2_tiles_m(g.N, g.H, g.W, g.K, g.C) > 0 ? 1 : 0;
+    const int k = route_of(d, dtype, kDgradMaskedAcc).kernel;
+    return k == PRIMIA_ERR_ARG ? k : (k > 0 ? 1 : 0);
 }
 
 int primia_conv2d_dgrad_masked_acc(const primia_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                                    const uint8_t* relu_mask, int dtype, primia_stream_t stream) {
     PRIMIA_REQUIRE(relu_mask);
     if (dtype != PRIMIA_BF16) return PRIMIA_ERR_UNSUPPORTED;
-    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, 1, nullptr, nullptr, dtype, stream, relu_mask);
+    DgradExtra e;
+    e.acc_mask = relu_mask;
+    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, kDgradMaskedAcc, dtype, stream, e);
 }
 
-// primia_conv2d_dgrad_masked_acc whose write-back also forms the backward sums of the BatchNorm whose OUTPUT gradient the call
-// completes (dx after the call = that gradient): sum g, sum g * xhat over g = dx AS STORED where the layer's ReLU passed, as
-// per-block partials [slots][2][64].  mode 2: a residual BatchNorm (aux = its input y, aux_mask = the ReLU-mask bytes of its
-// forward pass, c0 = saved mean, c1 = saved invstd) -> primia_bn_bwd_mask_from_sums; mode 3: the stem's BatchNorm seen through
-// the 3x3 / 2 max-pool (aux = the pooled activation p: ReLU = [p > 0], xhat = (p - beta) / gamma; c0 = beta, c1 = gamma)
-// -> primia_bn_relu_maxpool_bwd_from_sums.  64 -> 64 layers (conv3x3_c64_kernel<true, 3, mode>); slots = 0 elsewhere.
-int primia_conv_dgrad_masked_acc_bnsums_slots(const primia_conv_desc* d, int dtype) {
-    ConvGeom g;
-    if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
-    if (dtype != PRIMIA_BF16 || !use_c64(g) || (long)g.N * g.H * g.W * 64 >= (1L << 31)) return 0;
-    return conv3x3_c64_grid(g.N, g.H, g.W);
-}
+// ... masked-accumulating (C64AccBnb modes 2 and 3): the 64 -> 64 layers (conv3x3_c64_kernel<true, 3, mode>); slots = 0 elsewhere
+int primia_conv_dgrad_masked_acc_bnsums_slots(const primia_conv_desc* d, int dtype) { return route_slots(d, dtype, kDgradMaskedAccBnSums); }
 
 int primia_conv2d_dgrad_masked_acc_bnsums(const primia_conv_desc* d, const void* dy, const void* w_dgrad, void* dx,
                                           const uint8_t* relu_mask, int mode, const void* aux, const uint8_t* aux_mask,
@@ -1155,23 +1139,14 @@ int primia_conv2d_dgrad_masked_acc_bnsums(const primia_conv_desc* d, const void*
     PRIMIA_REQUIRE(relu_mask && aux && c0 && c1 && sums && (mode == 2 || mode == 3) && (mode == 3 || aux_mask));
     if (primia_conv_dgrad_masked_acc_bnsums_slots(d, dtype) <= 0) return PRIMIA_ERR_UNSUPPORTED;
     const C64AccBnb ab{mode, (const bf16*)aux, aux_mask, c0, c1};
-    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, 1, nullptr, nullptr, dtype, stream, relu_mask, nullptr, &ab, sums);
+    DgradExtra e;
+    e.acc_mask = relu_mask; e.acc_bnb = &ab; e.sums = sums;
+    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, kDgradMaskedAccBnSums, dtype, stream, e);
 }
 
-// primia_conv2d_dgrad_pair whose write-back also forms the backward sums of the residual BatchNorm in FRONT of the transition
-// block (dx = the gradient w.r.t. that layer's output z = relu(bn(y) + identity); its forward pass left one ReLU-mask byte per 8
-// channels): sum g, sum g * xhat with g = dx AS STORED * mask bit, as partials [slots][2][C] — primia_bn_bwd_mask_from_sums
-// consumes them.  Served by conv_s2lh_kernel for 64-channel dx (layer2.0) and by conv_igemm_kernel's LDS write-back loop (which
-// already walks whole 16-byte chunks of the scattered pixel rows) for the wider ones; slots = 0 elsewhere.
-int primia_conv_dgrad_pair_bnsums_slots(const primia_conv_desc* d, int dtype) {
-    ConvGeom g;
-    if (!d || !g.init(*d)) return PRIMIA_ERR_ARG;
-    if (dtype != PRIMIA_BF16 || !s2_conv1_shape(g)) return 0;
-    if (s2_pass_on(1, g.C)) return g.C == 64 ? 2 * conv_s2lh_tiles_m(g.N, g.H, g.W) : 0;
-    // conv_igemm_kernel's parity-class walk: one partial per (128-pixel tile, class)
-    if (g.C % 8) return 0;
-    return 4 * ceil_div((long)g.N * (g.H / 2) * (g.W / 2), 128);
-}
+// ... paired (S2BnBwd): conv_s2lh_kernel for 64-channel dx (layer2.0), conv_igemm_kernel's LDS write-back loop (which already
+// walks whole 16-byte chunks of the scattered pixel rows) for the wider ones; slots = 0 elsewhere
+int primia_conv_dgrad_pair_bnsums_slots(const primia_conv_desc* d, int dtype) { return route_slots(d, dtype, kDgradPairBnSums); }
 
 int primia_conv2d_dgrad_pair_bnsums(const primia_conv_desc* d, const void* dy, const void* w_dgrad,
                                     const primia_conv_desc* d_ds, const void* dy_ds, const void* w_dgrad_ds, void* dx,
@@ -1181,12 +1156,10 @@ int primia_conv2d_dgrad_pair_bnsums(const primia_conv_desc* d, const void* dy, c
     PRIMIA_REQUIRE(d_ds->R == 1 && d_ds->S == 1 && d_ds->stride == 2 && d_ds->pad == 0);
     PRIMIA_REQUIRE(d_ds->N == d->N && d_ds->H == d->H && d_ds->W == d->W && d_ds->C == d->C && d_ds->K == d->K);
     if (primia_conv_dgrad_pair_bnsums_slots(d, dtype) <= 0) return PRIMIA_ERR_UNSUPPORTED;
-    ConvGeom g;
-    PRIMIA_REQUIRE(g.init(*d));
     const S2BnBwd bnb{(const bf16*)bn_y, relu_mask, bn_mean, bn_invstd, sums};
-    if (!s2_pass_on(1, g.C)) return conv2d_dgrad_impl(d, dy, w_dgrad, dx, 0, dy_ds, w_dgrad_ds, dtype, stream, nullptr, &bnb);
-    return conv_s2lh_dgrad((const bf16*)dy, (const bf16*)w_dgrad, (const bf16*)dy_ds, (const bf16*)w_dgrad_ds, (bf16*)dx, g.N, g.H,
-                           g.W, g.C, g.K, (hipStream_t)stream, &bnb);
+    DgradExtra e;
+    e.dy2 = dy_ds; e.w_dgrad2 = w_dgrad_ds; e.pair_bnb = &bnb;
+    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, kDgradPairBnSums, dtype, stream, e);
 }
 
 int primia_conv2d_dgrad_pair(const primia_conv_desc* d, const void* dy, const void* w_dgrad,
@@ -1198,7 +1171,9 @@ int primia_conv2d_dgrad_pair(const primia_conv_desc* d, const void* dy, const vo
     PRIMIA_REQUIRE(d_ds->R == 1 && d_ds->S == 1 && d_ds->stride == 2 && d_ds->pad == 0);
     PRIMIA_REQUIRE(d_ds->N == d->N && d_ds->H == d->H && d_ds->W == d->W && d_ds->C == d->C && d_ds->K == d->K &&
                    d_ds->Ho == d->Ho && d_ds->Wo == d->Wo);
-    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, 0, dy_ds, w_dgrad_ds, dtype, stream);
+    DgradExtra e;
+    e.dy2 = dy_ds; e.w_dgrad2 = w_dgrad_ds;
+    return conv2d_dgrad_impl(d, dy, w_dgrad, dx, kDgradPair, dtype, stream, e);
 }
 
 }  // extern "C"

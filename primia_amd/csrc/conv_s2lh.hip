@@ -743,7 +743,7 @@ int conv_s2lh_tiles_m(int N, int H, int W) { return (int)(((long)N * (H / 2) * (
 // [N, H/2, W/2, K]; w [K][3][3][C], w_ds [K][C]; stat / stat_ds [tiles_m][2][K] or both null.
 int conv_s2lh_fwd(const bf16* x, const bf16* w, bf16* y, float* stat, const bf16* w_ds, bf16* y_ds, float* stat_ds, int N,
                   int H, int W, int C, int K, hipStream_t st) {
-    if (!conv_s2lh_ok(N, H, W, C, K)) return PRIMIA_ERR_UNSUPPORTED;
+    if (!conv_s2lh_ok(N, H, W, C, K)) return PRIMIA_ERR_INTERNAL;
     if (!w && !w_ds) return PRIMIA_ERR_ARG;
     if (w && w_ds && ((stat == nullptr) != (stat_ds == nullptr))) return PRIMIA_ERR_ARG;
     S2Params p = {};
@@ -789,9 +789,9 @@ int conv_s2lh_fwd(const bf16* x, const bf16* w, bf16* y, float* stat, const bf16
 // [N, H/2, W/2, K]; wd [C][3][3][K], wd_ds [C][K].  Every element of dx is written.
 int conv_s2lh_dgrad(const bf16* dy, const bf16* wd, const bf16* dy_ds, const bf16* wd_ds, bf16* dx, int N, int H, int W, int C,
                     int K, hipStream_t st, const S2BnBwd* bnb) {
-    if (!conv_s2lh_ok(N, H, W, C, K)) return PRIMIA_ERR_UNSUPPORTED;
+    if (!conv_s2lh_ok(N, H, W, C, K)) return PRIMIA_ERR_INTERNAL;
     if ((dy_ds == nullptr) != (wd_ds == nullptr)) return PRIMIA_ERR_ARG;
-    if (bnb && bnb->y && (C != 64 || !bnb->mask || !bnb->mean || !bnb->invstd || !bnb->sums)) return PRIMIA_ERR_UNSUPPORTED;
+    if (bnb && bnb->y && (C != 64 || !bnb->mask || !bnb->mean || !bnb->invstd || !bnb->sums)) return PRIMIA_ERR_INTERNAL;
     S2Params p = {};
     p.mode = 1;
     p.src[0] = dy; p.src[1] = dy_ds;

@@ -4,6 +4,13 @@
 
 namespace primia {
 
+// The forms of a weight-gradient call.  kWgAccumulate adds into a zeroed dw (atomics, no workspace), kWgWorkspace stores
+// per-block partial tiles and reduces them in a fixed order; the per-sample forms are DP-SGD's, one split per image: every
+// sample's tiles written to dw [N][K][klen], only their squared norms added to sqnorm, or the norms added and the tiles KEPT.
+enum WgradForm { kWgAccumulate, kWgWorkspace, kWgPersampleTiles, kWgPersampleSqnorm, kWgPersampleKeep };
+static inline bool wgrad_persample(WgradForm f) { return f >= kWgPersampleTiles; }
+static inline bool wgrad_norm_pass(WgradForm f) { return f == kWgPersampleSqnorm || f == kWgPersampleKeep; }
+
 struct WgradParams {
     const void* x;
     const void* dy;
@@ -17,8 +24,8 @@ struct WgradParams {
     long pix_per_split;
     long split_stride;  // 0: every split accumulates into dw; else split i writes dw + i*split_stride
                         // (per-sample gradients for DP-SGD: one split per image, stride K*klen)
-    int persample;
-    double* sqnorm;    // per-sample mode: if set, split i adds the squared L2 norm of ITS gradient tile to
+    WgradForm form;
+    double* sqnorm;    // the norm-pass forms: split i adds the squared L2 norm of ITS gradient tile to
                        // sqnorm[i] instead of writing the tile (the DP-SGD norm pass needs nothing else)
     float* ws;         // optional workspace of the store-and-reduce path (conv_wgrad_patch.hip); null: atomics
     size_t ws_bytes;
@@ -34,23 +41,27 @@ __device__ __forceinline__ void wave_sqnorm_add(double s, double* dst) {
 
 int wgrad_dma_dispatch(const WgradParams& p, hipStream_t st);
 size_t wgrad_dma_ws_bytes(const WgradParams& p);
-// halo-patch kernel (3x3, stride 1, bf16); returns PRIMIA_ERR_UNSUPPORTED when the shape is not covered
+// halo-patch kernel (3x3 / stride 1 / pad 1, bf16), every form: conv_wgrad_patch33lw_kernel (id 18) for the batched and
+// per-sample-tile forms, conv_wgrad_patch33_kernel for the norm pass — one block per (image, slab) (24), or whole images per
+// half-block where wgrad_patch_pairimg() (25)
+bool wgrad_patch_ok(const WgradParams& p);
+bool wgrad_patch_pairimg(const WgradParams& p, WgradForm form);
 int wgrad_patch_dispatch(const WgradParams& p, hipStream_t st);
-int wgrad_patch_kernel_id(const WgradParams& p);
-int wgrad_patch_persample_kernel_id(const WgradParams& p);
-int wgrad_tap_persample_kernel_id(const WgradParams& p);
+// DP-SGD norm pass of the 7x7-output 3x3 layers from two Gram matrices per sample (dp_ghost.hip): ids 21 / 22, 0 not served
 int dp_ghost_kernel_id(int H, int W, int C, int K, int R, int S, int stride, int pad);
+int dp_ghost_sqnorm_dispatch(const void* x, const void* dy, double* sq, int N, int H, int W, int C, int K, int R, int S,
+                             int stride, int pad, hipStream_t st);
 size_t wgrad_patch_ws_bytes(const WgradParams& p);
 // up to four layers of one shape in one launch (conv_wgrad_patch.hip): preferred group size for `count` such layers
 // (0: shape not served, 1: no gain), workspace of a group of n, and the launch (p[0].ws / ws_bytes = the group's)
 int wgrad_patch_group_size(const WgradParams& p, int count);
 size_t wgrad_patch_group_ws_bytes(const WgradParams& p, int n);
 int wgrad_patch_group_dispatch(const WgradParams* p, int n, hipStream_t st);
-// per-tap kernel of the stride-2 / 1x1 layers, second generation (conv_wgrad_tap.hip); needs the workspace
+// per-tap kernel of the stride-2 / 1x1 layers, second generation (conv_wgrad_tap.hip): the workspace form (id 17) ...
+bool wgrad_tap_ok(const WgradParams& p);
 int wgrad_tap_dispatch(const WgradParams& p, hipStream_t st);
-int wgrad_tap_kernel_id(const WgradParams& p);
 size_t wgrad_tap_ws_bytes(const WgradParams& p);
-// DP-SGD norm pass of those layers: whole images per block, squared tile norms added to p.sqnorm (no workspace)
+// ... and the DP-SGD norm pass of those layers (26): whole images per block, squared tile norms added to p.sqnorm
 int wgrad_tap_persample_dispatch(const WgradParams& p, hipStream_t st);
 // conv1 + downsample of a transition block in one launch (the downsample = a tenth tap with its own dy)
 int wgrad_tap_pair_dispatch(const WgradParams& p, const WgradParams& p2, hipStream_t st);

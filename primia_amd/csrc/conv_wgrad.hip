@@ -14,7 +14,7 @@
 // atomics into a zeroed [K][klen] buffer (fwd weight layout, see conv_common.h).
 #include <stdlib.h>
 
-#include "conv_wgrad.h"
+#include "conv_route.h"
 
 namespace primia {
 
@@ -366,10 +366,10 @@ static void wgrad_geometry(WgradParams& p) {
     if (want < 1) want = 1;
     long pps = (p.Md + want - 1) / want;
     pps = (pps + KP - 1) / KP * KP;
-    if (p.persample) pps = (long)p.Ho * p.Wo;  // one split per image
+    if (wgrad_persample(p.form)) pps = (long)p.Ho * p.Wo;  // one split per image
     p.pix_per_split = pps;
     p.nsplit = (int)((p.Md + pps - 1) / pps);
-    p.split_stride = p.persample ? (long)p.K * p.klen : 0;
+    p.split_stride = wgrad_persample(p.form) ? (long)p.K * p.klen : 0;
 }
 
 template <typename T, int BMK, int BNC, bool STEM>
@@ -383,7 +383,7 @@ static int launch_wgrad(WgradParams p, hipStream_t st) {
     constexpr int KP = (sizeof(T) == 2) ? 64 : 32;
     wgrad_geometry<sizeof(T), BMK, BNC, STEM>(p);
     const int combos = p.ntaps * p.nkt * p.nct;
-    const bool store = !p.persample && p.ws && p.ws_bytes >= (size_t)combos * p.nsplit * BMK * BNC * sizeof(float);
+    const bool store = !wgrad_persample(p.form) && p.ws && p.ws_bytes >= (size_t)combos * p.nsplit * BMK * BNC * sizeof(float);
     if (!store) p.ws = nullptr;
     const int grid = combos * p.nsplit;
     const size_t lds = 2 * KP * ((BMK + BNC) * sizeof(T) + 32);
@@ -403,12 +403,117 @@ static int launch_wgrad(WgradParams p, hipStream_t st) {
 
 using namespace primia;
 
-static int conv2d_wgrad_impl(const primia_conv_desc* d, const void* x, const void* dy, float* dw_acc, int persample,
-                             int dtype, primia_stream_t stream, double* sqnorm = nullptr, float* ws = nullptr,
-                             size_t ws_bytes = 0);
+static bool fill_wgrad_params(const primia_conv_desc* d, WgradParams& p, ConvGeom& g) {
+    if (!d || !g.init(*d)) return false;
+    p.N = g.N; p.H = g.H; p.W = g.W; p.C = g.C; p.K = g.K; p.R = g.R; p.S = g.S;
+    p.stride = g.stride; p.pad = g.pad; p.Ho = g.Ho; p.Wo = g.Wo;
+    p.klen = g.klen;
+    p.Md = (long)g.N * g.Ho * g.Wo;
+    p.ntaps = g.stem ? g.R : g.R * g.S;
+    p.form = kWgAccumulate;
+    p.split_stride = 0;
+    p.xpad = 0;
+    p.sqnorm = nullptr;
+    p.ws = nullptr; p.ws_bytes = 0;
+    return true;
+}
 
 static int stem_conv_wgrad_impl(const void* x_padded, const void* dy, float* dw_acc, float* ws, size_t ws_bytes, int N,
-                                int H, int W, int dtype, primia_stream_t stream);
+                                int H, int W, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(x_padded && dy && dw_acc && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0);
+    const primia_conv_desc d = {N, H, W, 4, 64, 7, 7, 2, 3, H / 2, W / 2};
+    WgradParams p;
+    ConvGeom g;
+    PRIMIA_REQUIRE(fill_wgrad_params(&d, p, g));      // (accumulate form: the generic kernel below runs without the workspace)
+    p.x = x_padded; p.dy = dy; p.dw = dw_acc;
+    p.xpad = 1;
+    if (dtype == PRIMIA_F32) return launch_wgrad<float, 64, 32, true>(p, (hipStream_t)stream);
+    if (dtype == PRIMIA_BF16) {
+        const int rc = stem_wgrad_halo_dispatch((const bf16*)x_padded, (const bf16*)dy, dw_acc, N, H, W, (hipStream_t)stream,
+                                                ws, ws_bytes);
+        if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
+        return launch_wgrad<bf16, 64, 32, true>(p, (hipStream_t)stream);
+    }
+    return PRIMIA_ERR_ARG;
+}
+
+// the generic kernel (ids 14 and 15): stem tile, else 128 x 128 where both channel counts allow, else 64 x 64
+template <typename T>
+static size_t wgrad_generic_ws(const WgradParams& p, const ConvGeom& g) {
+    if (g.stem) return wgrad_ws_need<T, 64, 32, true>(p);
+    return g.K % 128 == 0 && g.C % 128 == 0 ? wgrad_ws_need<T, 128, 128, false>(p) : wgrad_ws_need<T, 64, 64, false>(p);
+}
+template <typename T>
+static int launch_wgrad_generic(const WgradParams& p, const ConvGeom& g, hipStream_t st) {
+    if (g.stem) return launch_wgrad<T, 64, 32, true>(p, st);
+    return g.K % 128 == 0 && g.C % 128 == 0 ? launch_wgrad<T, 128, 128, false>(p, st) : launch_wgrad<T, 64, 64, false>(p, st);
+}
+
+// Measured per layer (profiles/r01_conv_layers_*): the halo-patch kernel (conv_wgrad_patch.hip) wins on every 3x3 /
+// stride-1 layer; of the per-tap kernels conv_wgrad_tap_kernel serves the stride-2 / 1x1 layers where it has its
+// workspace (and their norm pass), the LDS-DMA one the wide layers that are left and the register-staged one the rest.
+WgradRoute primia::wgrad_route(const WgradParams& p0, const ConvGeom& g, int dtype, WgradForm form) {
+    WgradParams p = p0;
+    p.form = form;
+    const bool ws = form == kWgWorkspace;
+    if (g.stem || dtype != PRIMIA_BF16) {
+        const size_t n = !ws ? 0 : (dtype == PRIMIA_BF16 ? wgrad_generic_ws<bf16>(p, g) : wgrad_generic_ws<float>(p, g));
+        return {g.stem ? 15 : 14, n};
+    }
+    if (form == kWgPersampleSqnorm) {
+        // 7x7 outputs, 3x3: the norms come out of two Gram matrices per sample (dp_ghost.hip), the per-sample gradients are
+        // never formed
+        const int gh = dp_ghost_kernel_id(g.H, g.W, g.C, g.K, g.R, g.S, g.stride, g.pad);
+        if (gh) return {gh, 0};
+    }
+    if (wgrad_patch_ok(p)) {
+        if (wgrad_norm_pass(form)) return {wgrad_patch_pairimg(p, form) ? 25 : 24, 0};
+        return {18, ws ? wgrad_patch_ws_bytes(p) : 0};
+    }
+    if (wgrad_tap_ok(p) && ws) return {17, wgrad_tap_ws_bytes(p)};
+    if (wgrad_tap_ok(p) && form == kWgPersampleSqnorm) return {26, 0};
+    if (wgrad_dma_shape(g)) return {13, ws ? wgrad_dma_ws_bytes(p) : 0};
+    return {14, ws ? wgrad_generic_ws<bf16>(p, g) : 0};
+}
+
+static int conv2d_wgrad_impl(const primia_conv_desc* d, const void* x, const void* dy, float* dw_acc, WgradForm form,
+                             int dtype, primia_stream_t stream, double* sqnorm = nullptr, float* ws = nullptr,
+                             size_t ws_bytes = 0) {
+    PRIMIA_REQUIRE(d && x && dy && (dw_acc || sqnorm) && (dtype == PRIMIA_F32 || dtype == PRIMIA_BF16));
+    ConvGeom g;
+    WgradParams p;
+    PRIMIA_REQUIRE(fill_wgrad_params(d, p, g));
+    WgradRoute r = wgrad_route(p, g, dtype, form);
+    if (form == kWgWorkspace && !(ws && r.ws_bytes && ws_bytes >= r.ws_bytes)) {
+        // without a (large enough) workspace the call is primia_conv2d_wgrad: accumulate into the zeroed dw
+        form = kWgAccumulate;
+        r = wgrad_route(p, g, dtype, form);
+    }
+    p.x = x; p.dy = dy; p.dw = dw_acc;
+    p.form = form;
+    p.sqnorm = sqnorm;
+    p.ws = form == kWgWorkspace ? ws : nullptr; p.ws_bytes = form == kWgWorkspace ? ws_bytes : 0;
+    hipStream_t st = (hipStream_t)stream;
+    switch (r.kernel) {
+    case 14:
+    case 15:
+        return dtype == PRIMIA_F32 ? launch_wgrad_generic<float>(p, g, st) : launch_wgrad_generic<bf16>(p, g, st);
+    case 18:
+    case 24:
+    case 25:
+        return wgrad_patch_dispatch(p, st);
+    case 17:
+        return wgrad_tap_dispatch(p, st);
+    case 26:
+        return wgrad_tap_persample_dispatch(p, st);
+    case 13:
+        return wgrad_dma_dispatch(p, st);
+    case 21:
+    case 22:
+        return dp_ghost_sqnorm_dispatch(x, dy, sqnorm, g.N, g.H, g.W, g.C, g.K, g.R, g.S, g.stride, g.pad, st);
+    }
+    return PRIMIA_ERR_INTERNAL;
+}
 
 extern "C" int primia_stem_conv_wgrad(const void* x_padded, const void* dy, float* dw_acc, int N, int H, int W, int dtype,
                                       primia_stream_t stream) {
@@ -437,75 +542,21 @@ extern "C" int primia_stem_conv_wgrad_ws(const void* x_padded, const void* dy, f
                                 stream);
 }
 
-static int stem_conv_wgrad_impl(const void* x_padded, const void* dy, float* dw_acc, float* ws, size_t ws_bytes, int N,
-                                int H, int W, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(x_padded && dy && dw_acc && N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0);
-    WgradParams p;
-    p.x = x_padded; p.dy = dy; p.dw = dw_acc;
-    p.N = N; p.H = H; p.W = W; p.C = 4; p.K = 64; p.R = 7; p.S = 7; p.stride = 2; p.pad = 3;
-    p.Ho = H / 2; p.Wo = W / 2;
-    p.klen = 256;
-    p.Md = (long)N * p.Ho * p.Wo;
-    p.ntaps = 7;
-    p.persample = 0;
-    p.split_stride = 0;
-    p.xpad = 1;
-    p.sqnorm = nullptr;
-    p.ws = nullptr; p.ws_bytes = 0;
-    if (dtype == PRIMIA_F32) return launch_wgrad<float, 64, 32, true>(p, (hipStream_t)stream);
-    if (dtype == PRIMIA_BF16) {
-        const int rc = stem_wgrad_halo_dispatch((const bf16*)x_padded, (const bf16*)dy, dw_acc, N, H, W, (hipStream_t)stream,
-                                                ws, ws_bytes);
-        if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
-        return launch_wgrad<bf16, 64, 32, true>(p, (hipStream_t)stream);
-    }
-    return PRIMIA_ERR_ARG;
-}
-
 extern "C" int primia_conv2d_wgrad(const primia_conv_desc* d, const void* x, const void* dy, float* dw_acc,
                                    int dtype, primia_stream_t stream) {
-    return conv2d_wgrad_impl(d, x, dy, dw_acc, 0, dtype, stream);
-}
-
-static bool fill_wgrad_params(const primia_conv_desc* d, WgradParams& p, ConvGeom& g) {
-    if (!d || !g.init(*d)) return false;
-    p.N = g.N; p.H = g.H; p.W = g.W; p.C = g.C; p.K = g.K; p.R = g.R; p.S = g.S;
-    p.stride = g.stride; p.pad = g.pad; p.Ho = g.Ho; p.Wo = g.Wo;
-    p.klen = g.klen;
-    p.Md = (long)g.N * g.Ho * g.Wo;
-    p.ntaps = g.stem ? g.R : g.R * g.S;
-    p.persample = 0;
-    p.split_stride = 0;
-    p.xpad = 0;
-    p.sqnorm = nullptr;
-    p.ws = nullptr; p.ws_bytes = 0;
-    return true;
+    return conv2d_wgrad_impl(d, x, dy, dw_acc, kWgAccumulate, dtype, stream);
 }
 
 extern "C" int64_t primia_conv_wgrad_ws_bytes(const primia_conv_desc* d, int dtype) {
     WgradParams p;
     ConvGeom g;
-    if (!fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
-    // mirrors the kernel choice of conv2d_wgrad_impl below
-    if (dtype == PRIMIA_F32) {
-        if (g.stem) return (int64_t)wgrad_ws_need<float, 64, 32, true>(p);
-        if (g.K % 128 == 0 && g.C % 128 == 0) return (int64_t)wgrad_ws_need<float, 128, 128, false>(p);
-        return (int64_t)wgrad_ws_need<float, 64, 64, false>(p);
-    }
-    if (dtype != PRIMIA_BF16) return PRIMIA_ERR_ARG;
-    if (g.stem) return (int64_t)wgrad_ws_need<bf16, 64, 32, true>(p);
-    const size_t n = wgrad_patch_ws_bytes(p);
-    if (n > 0) return (int64_t)n;
-    const size_t nt = wgrad_tap_ws_bytes(p);
-    if (nt > 0) return (int64_t)nt;
-    if (wgrad_dma_shape(g)) return (int64_t)wgrad_dma_ws_bytes(p);
-    if (g.K % 128 == 0 && g.C % 128 == 0) return (int64_t)wgrad_ws_need<bf16, 128, 128, false>(p);
-    return (int64_t)wgrad_ws_need<bf16, 64, 64, false>(p);
+    if (!fill_wgrad_params(d, p, g) || (dtype != PRIMIA_F32 && dtype != PRIMIA_BF16)) return PRIMIA_ERR_ARG;
+    return (int64_t)wgrad_route(p, g, dtype, kWgWorkspace).ws_bytes;
 }
 
 extern "C" int primia_conv2d_wgrad_ws(const primia_conv_desc* d, const void* x, const void* dy, float* dw,
                                       void* ws, int64_t ws_bytes, int dtype, primia_stream_t stream) {
-    return conv2d_wgrad_impl(d, x, dy, dw, 0, dtype, stream, nullptr, (float*)ws, ws_bytes > 0 ? (size_t)ws_bytes : 0);
+    return conv2d_wgrad_impl(d, x, dy, dw, kWgWorkspace, dtype, stream, nullptr, (float*)ws, ws_bytes > 0 ? (size_t)ws_bytes : 0);
 }
 
 extern "C" int64_t primia_conv_wgrad_pair_ws_bytes(const primia_conv_desc* d, const primia_conv_desc* d2, int dtype) {
@@ -536,7 +587,6 @@ extern "C" int primia_conv_wgrad_group_size(const primia_conv_desc* d, int count
     WgradParams p;
     if (!d || count < 1 || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
     if (dtype != PRIMIA_BF16 || g.stem) return 0;
-    p.persample = 0;
     return wgrad_patch_group_size(p, count);
 }
 
@@ -545,7 +595,6 @@ extern "C" int64_t primia_conv_wgrad_group_ws_bytes(const primia_conv_desc* d, i
     WgradParams p;
     if (!d || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
     if (dtype != PRIMIA_BF16 || g.stem) return 0;
-    p.persample = 0;
     return (int64_t)wgrad_patch_group_ws_bytes(p, n);
 }
 
@@ -564,7 +613,7 @@ extern "C" int primia_conv2d_wgrad_group_ws(const primia_conv_desc* d, int n, co
         PRIMIA_REQUIRE(xs[i] && dys[i] && dws[i] && fill_wgrad_params(d, ps[i], g));
         if (g.stem) return PRIMIA_ERR_UNSUPPORTED;
         ps[i].x = xs[i]; ps[i].dy = dys[i]; ps[i].dw = dws[i];
-        ps[i].persample = 0; ps[i].sqnorm = nullptr;
+        ps[i].form = kWgWorkspace;
         ps[i].ws = (float*)ws; ps[i].ws_bytes = (size_t)ws_bytes;
     }
     return wgrad_patch_group_dispatch(ps, n, (hipStream_t)stream);
@@ -602,7 +651,6 @@ extern "C" int64_t primia_conv_wgrad_persample_slab_bytes(const primia_conv_desc
     WgradParams p;
     if (!d || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
     if (dtype != PRIMIA_BF16 || g.stem) return 0;
-    p.persample = 1;
     return (int64_t)wgrad_patch_keep_bytes(p);
 }
 
@@ -616,7 +664,7 @@ extern "C" int primia_conv2d_wgrad_persample_sqnorm_keep(const primia_conv_desc*
     PRIMIA_REQUIRE(fill_wgrad_params(d, p, g));
     if (g.stem) return PRIMIA_ERR_UNSUPPORTED;
     p.x = x; p.dy = dy; p.dw = nullptr;
-    p.persample = 1; p.sqnorm = sqnorm;
+    p.form = kWgPersampleKeep; p.sqnorm = sqnorm;
     p.ws = (float*)slabs; p.ws_bytes = (size_t)slab_bytes;
     return wgrad_patch_keep_dispatch(p, (hipStream_t)stream);
 }
@@ -628,93 +676,34 @@ extern "C" int primia_conv_wgrad_clipped_sum(const primia_conv_desc* d, const vo
     ConvGeom g;
     WgradParams p;
     PRIMIA_REQUIRE(fill_wgrad_params(d, p, g));
-    p.persample = 1; p.dw = dw_acc;
+    p.form = kWgPersampleKeep; p.dw = dw_acc;
     return wgrad_patch_clipped_sum(p, (const float*)slabs, clip, (hipStream_t)stream);
 }
 
 extern "C" int primia_conv2d_wgrad_persample(const primia_conv_desc* d, const void* x, const void* dy,
                                              float* dw_ps, int dtype, primia_stream_t stream) {
-    return conv2d_wgrad_impl(d, x, dy, dw_ps, 1, dtype, stream);
-}
-
-namespace primia {
-int dp_ghost_sqnorm_dispatch(const void* x, const void* dy, double* sq, int N, int H, int W, int C, int K, int R, int S,
-                             int stride, int pad, hipStream_t st);
+    return conv2d_wgrad_impl(d, x, dy, dw_ps, kWgPersampleTiles, dtype, stream);
 }
 
 extern "C" int primia_conv2d_wgrad_persample_sqnorm(const primia_conv_desc* d, const void* x, const void* dy,
                                                     double* sqnorm, int dtype, primia_stream_t stream) {
     PRIMIA_REQUIRE(sqnorm);
-    if (d && x && dy && dtype == PRIMIA_BF16) {
-        // 7x7 images, 3x3 / stride 1: the norms come out of two Gram matrices per sample (dp_ghost.hip), the per-sample
-        // gradients are never formed
-        const int rc = dp_ghost_sqnorm_dispatch(x, dy, sqnorm, d->N, d->H, d->W, d->C, d->K, d->R, d->S, d->stride, d->pad,
-                                                (hipStream_t)stream);
-        if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
-    }
-    return conv2d_wgrad_impl(d, x, dy, nullptr, 1, dtype, stream, sqnorm);
+    return conv2d_wgrad_impl(d, x, dy, nullptr, kWgPersampleSqnorm, dtype, stream, sqnorm);
+}
+
+static int wgrad_kernel_of(const primia_conv_desc* d, int dtype, WgradForm form) {
+    ConvGeom g;
+    WgradParams p;
+    if (!fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
+    return wgrad_route(p, g, dtype, form).kernel;
 }
 
 extern "C" int primia_conv_wgrad_persample_kernel_id(const primia_conv_desc* d, int dtype) {
-    ConvGeom g;
-    WgradParams p;
-    if (!d || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
-    p.persample = 1;
-    if (g.stem) return 15;
-    if (dtype != PRIMIA_BF16) return 14;
-    const int gh = dp_ghost_kernel_id(d->H, d->W, d->C, d->K, d->R, d->S, d->stride, d->pad);
-    if (gh) return gh;
-    const int id = wgrad_patch_persample_kernel_id(p);
-    if (id) return id;
-    const int idt = wgrad_tap_persample_kernel_id(p);
-    if (idt) return idt;
-    return wgrad_dma_shape(g) ? 13 : 14;
+    return wgrad_kernel_of(d, dtype, kWgPersampleSqnorm);
 }
 
 extern "C" int primia_conv_wgrad_kernel_id(const primia_conv_desc* d, int dtype) {
-    ConvGeom g;
-    WgradParams p;
-    if (!d || !fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
-    if (g.stem) return 15;
-    if (dtype != PRIMIA_BF16) return 14;
-    const int id = wgrad_patch_kernel_id(p);
-    if (id) return id;
-    const int idt = wgrad_tap_kernel_id(p);
-    if (idt) return idt;
-    return wgrad_dma_shape(g) ? 13 : 14;
-}
-
-static int conv2d_wgrad_impl(const primia_conv_desc* d, const void* x, const void* dy, float* dw_acc, int persample,
-                             int dtype, primia_stream_t stream, double* sqnorm, float* ws, size_t ws_bytes) {
-    PRIMIA_REQUIRE(d && x && dy && (dw_acc || sqnorm));
-    ConvGeom g;
-    WgradParams p;
-    PRIMIA_REQUIRE(fill_wgrad_params(d, p, g));
-    p.x = x; p.dy = dy; p.dw = dw_acc;
-    p.persample = persample;
-    p.sqnorm = sqnorm;
-    p.ws = ws; p.ws_bytes = ws ? ws_bytes : 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32) {
-        if (g.stem) return launch_wgrad<float, 64, 32, true>(p, st);
-        if (g.K % 128 == 0 && g.C % 128 == 0) return launch_wgrad<float, 128, 128, false>(p, st);
-        return launch_wgrad<float, 64, 64, false>(p, st);
-    } else if (dtype == PRIMIA_BF16) {
-        // Measured per layer (profiles/r01_conv_layers_*): the halo-patch kernel (conv_wgrad_patch.hip) wins
-        // on every 3x3 / stride-1 layer; of the per-tap kernels the LDS-DMA one wins on the wide, few-pixel
-        // layers (layer3/4) and the register-staged one elsewhere.
-        if (g.stem) return launch_wgrad<bf16, 64, 32, true>(p, st);
-        const int rc = wgrad_patch_dispatch(p, st);
-        if (rc != PRIMIA_ERR_UNSUPPORTED) return rc;
-        const int rt = wgrad_tap_dispatch(p, st);     // stride-2 / 1x1 layers with a workspace
-        if (rt != PRIMIA_ERR_UNSUPPORTED) return rt;
-        const int rp = wgrad_tap_persample_dispatch(p, st);   // ... and their DP-SGD norm pass
-        if (rp != PRIMIA_ERR_UNSUPPORTED) return rp;
-        if (wgrad_dma_shape(g)) return wgrad_dma_dispatch(p, st);
-        if (g.K % 128 == 0 && g.C % 128 == 0) return launch_wgrad<bf16, 128, 128, false>(p, st);
-        return launch_wgrad<bf16, 64, 64, false>(p, st);
-    }
-    return PRIMIA_ERR_ARG;
+    return wgrad_kernel_of(d, dtype, kWgWorkspace);
 }
 
 // =================================================================================================
@@ -918,10 +907,10 @@ static bool wgrad_dma_geometry(WgradParams& p) {
     if (want < 1) want = 1;
     long pps = (p.Md + want - 1) / want;
     pps = (pps + KP - 1) / KP * KP;
-    if (p.persample) pps = (long)p.Ho * p.Wo;
+    if (wgrad_persample(p.form)) pps = (long)p.Ho * p.Wo;
     p.pix_per_split = pps;
     p.nsplit = (int)((p.Md + pps - 1) / pps);
-    p.split_stride = p.persample ? (long)p.K * p.klen : 0;
+    p.split_stride = wgrad_persample(p.form) ? (long)p.K * p.klen : 0;
     return true;
 }
 
@@ -930,7 +919,7 @@ static int launch_wgrad_dma(WgradParams p, hipStream_t st) {
     constexpr int KP = 64;
     if (!wgrad_dma_geometry<BMK, BNC>(p)) return PRIMIA_ERR_ARG;
     const int combos = p.ntaps * p.nkt * p.nct;
-    const bool store = !p.persample && p.ws && p.ws_bytes >= (size_t)combos * p.nsplit * BMK * BNC * sizeof(float);
+    const bool store = !wgrad_persample(p.form) && p.ws && p.ws_bytes >= (size_t)combos * p.nsplit * BMK * BNC * sizeof(float);
     if (!store) p.ws = nullptr;
     const int grid = combos * p.nsplit;
     const size_t lds = 2 * (size_t)KP * (BMK + BNC) * 2;

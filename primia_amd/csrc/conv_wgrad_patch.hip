@@ -682,16 +682,19 @@ struct PatchGeom {
 };
 
 // DP-SGD norm pass with whole images per half: needs at least two images per block for every slab
-static bool pairimg_mode(const WgradParams& w, const PatchGeom& g) {
-    return w.persample && w.sqnorm && w.N >= 2 && (long)g.combos * ((w.N + 1) / 2) >= 256;   // (else: one block per image, as before)
+static bool pairimg_mode(const WgradParams& w, WgradForm form, const PatchGeom& g) {
+    return wgrad_norm_pass(form) && w.N >= 2 && (long)g.combos * ((w.N + 1) / 2) >= 256;   // (else: one block per image, as before)
 }
-// ngroup > 1: geometry of ONE layer of a grouped launch (the layers share the 256 CUs)
-static PatchGeom patch_geom(const WgradParams& w, int ngroup = 1) {
-    PatchGeom g{};
-    // x and dy are addressed with 32-bit BYTE offsets through buffer resources (signed arithmetic, range check against
-    // num_records): elements < 2^30
-    g.ok = !(w.R != 3 || w.S != 3 || w.stride != 1 || w.pad != 1 || w.C % 64 || w.K % 64) &&
+// x and dy are addressed with 32-bit BYTE offsets through buffer resources (signed arithmetic, range check against
+// num_records): elements < 2^30
+bool wgrad_patch_ok(const WgradParams& w) {
+    return !(w.R != 3 || w.S != 3 || w.stride != 1 || w.pad != 1 || w.C % 64 || w.K % 64) &&
            (long)w.N * w.H * w.W * (w.C > w.K ? w.C : w.K) < (1L << 30);
+}
+// geometry of a launch in `form`; ngroup > 1: of ONE layer of a grouped launch (the layers share the 256 CUs)
+static PatchGeom patch_geom(const WgradParams& w, WgradForm form, int ngroup = 1) {
+    PatchGeom g{};
+    g.ok = wgrad_patch_ok(w);
     if (!g.ok) return g;
     int SW, SH;
     {
@@ -722,8 +725,8 @@ static PatchGeom patch_geom(const WgradParams& w, int ngroup = 1) {
     long per = (g.total + want - 1) / want;
     per = (per + 1) & ~1L;
     if (per < 2) per = 2;
-    if (w.persample) per = g.PPI;  // one split per image
-    if (pairimg_mode(w, g)) {
+    if (wgrad_persample(form)) per = g.PPI;  // one split per image
+    if (pairimg_mode(w, form, g)) {
         // norm pass: a block walks many images, each half whole images of its own (see the kernel); units: images
         g.total = w.N;
         per = (w.N + want - 1) / want;
@@ -735,10 +738,12 @@ static PatchGeom patch_geom(const WgradParams& w, int ngroup = 1) {
     return g;
 }
 
-// bytes of workspace the store-and-reduce path needs for this layer (0: layer not served by this kernel)
+bool wgrad_patch_pairimg(const WgradParams& w, WgradForm form) { return pairimg_mode(w, form, patch_geom(w, form)); }
+
+// bytes of workspace the store-and-reduce form needs for this layer (0: layer not served by this kernel)
 size_t wgrad_patch_ws_bytes(const WgradParams& w) {
-    const PatchGeom g = patch_geom(w);
-    if (!g.ok || w.persample) return 0;
+    const PatchGeom g = patch_geom(w, kWgWorkspace);
+    if (!g.ok) return 0;
     return (size_t)g.combos * g.nsplit * kSlab * sizeof(float);
 }
 
@@ -751,11 +756,11 @@ static void fill_patch_params(PatchParams& p, const WgradParams& w, const PatchG
     p.per_block = g.per_block;
     p.nsplit = g.nsplit;
     p.split_fastest = 0;      // block id order: slab fastest (the slabs of a pixel range share x, dy in one L2)
-    p.split_stride = w.persample ? (long)w.K * w.klen : 0;
-    p.sqnorm = w.persample ? w.sqnorm : nullptr;
-    const bool store = !w.persample && w.ws && w.ws_bytes >= (size_t)g.combos * g.nsplit * kSlab * sizeof(float);
+    p.split_stride = wgrad_persample(w.form) ? (long)w.K * w.klen : 0;
+    p.sqnorm = wgrad_norm_pass(w.form) ? w.sqnorm : nullptr;
+    const bool store = !wgrad_persample(w.form) && w.ws && w.ws_bytes >= (size_t)g.combos * g.nsplit * kSlab * sizeof(float);
     p.ws = store ? w.ws : nullptr;
-    p.pairimg = pairimg_mode(w, g) ? 1 : 0;
+    p.pairimg = pairimg_mode(w, w.form, g) ? 1 : 0;
     p.nimg = w.N;
     p.ngroups = 1;
     p.group_blocks = 0;
@@ -798,11 +803,10 @@ static int launch_patch33(const WgradParams& w, const PatchGeom& g, hipStream_t 
 // Preferred group size for `count` layers of this shape: the largest n <= min(count, 4) whose blocks fill >= 90 % of the
 // CUs in one round (0: shape not served).
 int wgrad_patch_group_size(const WgradParams& w, int count) {
-    if (w.persample) return 0;
-    const PatchGeom g1 = patch_geom(w);
+    const PatchGeom g1 = patch_geom(w, kWgWorkspace);
     if (!g1.ok || g1.SW != 8 || g1.SH != 8) return 0;
     for (int n = count < 4 ? count : 4; n >= 2; --n) {
-        const PatchGeom g = patch_geom(w, n);
+        const PatchGeom g = patch_geom(w, kWgWorkspace, n);
         const long blocks = (long)n * g.combos * g.nsplit;
         if (blocks <= 256 && blocks * 100 >= 256 * 90) return n;
     }
@@ -811,7 +815,7 @@ int wgrad_patch_group_size(const WgradParams& w, int count) {
 
 size_t wgrad_patch_group_ws_bytes(const WgradParams& w, int n) {
     if (n < 2 || n > 4 || wgrad_patch_group_size(w, n) < n) return 0;
-    const PatchGeom g = patch_geom(w, n);
+    const PatchGeom g = patch_geom(w, kWgWorkspace, n);
     return (size_t)n * g.combos * g.nsplit * kSlab * sizeof(float);
 }
 
@@ -824,9 +828,10 @@ int wgrad_patch_group_dispatch(const WgradParams* ws_, int n, hipStream_t st) {
         if (!ws_[i].x || !ws_[i].dy || !ws_[i].dw || ws_[i].N != w.N || ws_[i].H != w.H || ws_[i].W != w.W ||
             ws_[i].C != w.C || ws_[i].K != w.K || ws_[i].R != 3 || ws_[i].S != 3 || ws_[i].stride != 1 || ws_[i].pad != 1)
             return PRIMIA_ERR_ARG;
-    const PatchGeom g = patch_geom(w, n);
+    const PatchGeom g = patch_geom(w, kWgWorkspace, n);
     PatchParams p;
     WgradParams w0 = w;
+    w0.form = kWgWorkspace;
     w0.ws_bytes = (size_t)g.combos * g.nsplit * kSlab * sizeof(float);   // (fill_patch_params checks one layer's share)
     fill_patch_params(p, w0, g);
     p.ws = w.ws;
@@ -862,11 +867,7 @@ int wgrad_patch_group_dispatch(const WgradParams* ws_, int n, hipStream_t st) {
 // ---- DP-SGD: norm pass that KEEPS every sample's tiles, clipped sum as a weighted reduce (see conv_wgrad.hip) ----------
 size_t wgrad_patch_keep_bytes(const WgradParams& w) {
     constexpr long budget = 160L << 20;   // per-sample tiles of a layer are kept up to 160 MiB (layer1: 38 MB per layer, layer2: 151; layer3 would be 604 MB written and read back: a loss)
-    WgradParams q = w;
-    q.persample = 1;
-    double dummy;
-    q.sqnorm = &dummy;
-    const PatchGeom g = patch_geom(q);
+    const PatchGeom g = patch_geom(w, kWgPersampleKeep);
     if (!g.ok) return 0;       // (whole images per half, or one block per (image, slab): both keep)
     const size_t n = (size_t)g.combos * w.N * kSlab * sizeof(float);
     return (long)n <= budget ? n : 0;
@@ -874,11 +875,11 @@ size_t wgrad_patch_keep_bytes(const WgradParams& w) {
 
 int wgrad_patch_keep_dispatch(const WgradParams& w, hipStream_t st) {
     const size_t need = wgrad_patch_keep_bytes(w);
-    if (!need || !w.sqnorm || !w.ws) return PRIMIA_ERR_UNSUPPORTED;
+    if (!need || w.form != kWgPersampleKeep || !w.sqnorm || !w.ws) return PRIMIA_ERR_UNSUPPORTED;
     if (w.ws_bytes < need) return PRIMIA_ERR_WORKSPACE;
-    const PatchGeom g = patch_geom(w);
+    const PatchGeom g = patch_geom(w, w.form);
     PatchParams p;
-    fill_patch_params(p, w, g);      // (persample: p.ws = null)
+    fill_patch_params(p, w, g);      // (a per-sample form: p.ws = null)
     if (!p.pairimg && g.nsplit != w.N) return PRIMIA_ERR_UNSUPPORTED;
     p.ws = w.ws;
     const size_t lds = (size_t)kSlab * 4;
@@ -900,24 +901,9 @@ int wgrad_patch_clipped_sum(const WgradParams& w, const float* slabs, const floa
     return launch_status();
 }
 
-// 18 = conv_wgrad_patch33lw_kernel (loader waves; the batched gradient), 0 = shape not served.  (16, 11 and 12 named its
-// predecessors conv_wgrad_patch33_kernel, conv_wgrad_patch32_kernel and conv_wgrad_patch_kernel: the numbers stay theirs.)
-int wgrad_patch_kernel_id(const WgradParams& w) { return patch_geom(w).ok ? 18 : 0; }
-
-// DP-SGD norm pass on this kernel: 0 shape not served, 24 one block per (image, slab), 25 whole images per half-block
-int wgrad_patch_persample_kernel_id(const WgradParams& w) {
-    WgradParams q = w;
-    static double dummy;
-    q.persample = 1;
-    q.sqnorm = &dummy;       // (never dereferenced: the mode test only asks whether a norm pass was requested)
-    const PatchGeom g = patch_geom(q);
-    if (!g.ok) return 0;
-    return pairimg_mode(q, g) ? 25 : 24;
-}
-
 int wgrad_patch_dispatch(const WgradParams& w, hipStream_t st) {
-    const PatchGeom g = patch_geom(w);
-    if (!g.ok) return PRIMIA_ERR_UNSUPPORTED;
+    const PatchGeom g = patch_geom(w, w.form);
+    if (!g.ok || w.form == kWgPersampleKeep || (w.form == kWgPersampleSqnorm && !w.sqnorm)) return PRIMIA_ERR_INTERNAL;
     if (g.SW == 16) return launch_patch33<16, 2>(w, g, st);
     return g.SH == 8 ? launch_patch33<8, 8>(w, g, st) : launch_patch33<8, 4>(w, g, st);
 }

@@ -327,7 +327,7 @@ struct TapGeom {
 // extra_taps: taps of a paired layer that ride in the same launch (they count for the one-round block budget)
 static TapGeom tap_geom(const WgradParams& w, int extra_taps = 0) {
     TapGeom g{};
-    g.ok = !w.persample && !w.xpad && (w.stride == 2 || (w.R == 1 && w.S == 1)) && w.ntaps == w.R * w.S &&
+    g.ok = !w.xpad && (w.stride == 2 || (w.R == 1 && w.S == 1)) && w.ntaps == w.R * w.S &&
            w.Md < (1L << 24) && (long)w.N * w.H * w.W * w.C < (1L << 31) && w.Md * w.K < (1L << 31) && w.K % 128 == 0 &&
            w.C % 64 == 0;
     if (!g.ok) return g;
@@ -350,14 +350,13 @@ static TapGeom tap_geom(const WgradParams& w, int extra_taps = 0) {
     return g;
 }
 
+bool wgrad_tap_ok(const WgradParams& w) { return tap_geom(w).ok; }
+
 size_t wgrad_tap_ws_bytes(const WgradParams& w) {
     const TapGeom g = tap_geom(w);
     if (!g.ok) return 0;
     return (size_t)g.combos * g.nsplit * g.BMK * g.BNC * sizeof(float);
 }
-
-// 17 = conv_wgrad_tap_kernel; 0: shape not served
-int wgrad_tap_kernel_id(const WgradParams& w) { return tap_geom(w).ok ? 17 : 0; }
 
 template <int BMK, int BNC, int WM, int WN>
 static int launch_tap(const WgradParams& w, const TapGeom& g, hipStream_t st) {
@@ -449,27 +448,16 @@ static int launch_tap_persample(const WgradParams& w, const TapGeom& g, hipStrea
     return launch_status();
 }
 
-// 26 = conv_wgrad_tap_kernel's norm pass (whole images per block), 0 = shape not served
-int wgrad_tap_persample_kernel_id(const WgradParams& w) {
-    WgradParams b = w;
-    b.persample = 0;
-    return (!tap_geom(b).ok || w.Ho * w.Wo < 1) ? 0 : 26;
-}
-
 int wgrad_tap_persample_dispatch(const WgradParams& w, hipStream_t st) {
-    if (!w.persample || !w.sqnorm) return PRIMIA_ERR_UNSUPPORTED;
-    WgradParams b = w;
-    b.persample = 0;
-    const TapGeom g = tap_geom(b);
-    if (!g.ok || w.Ho * w.Wo < 1) return PRIMIA_ERR_UNSUPPORTED;
+    const TapGeom g = tap_geom(w);
+    if (!g.ok || w.form != kWgPersampleSqnorm || !w.sqnorm) return PRIMIA_ERR_INTERNAL;
     return g.wide ? launch_tap_persample<256, 128, 2, 4>(w, g, st) : launch_tap_persample<128, 64, 4, 2>(w, g, st);
 }
 
-// PRIMIA_ERR_UNSUPPORTED: shape not served, or no (large enough) workspace — the caller falls back to the older kernels
+// the workspace form only (without a large enough workspace these layers run on the older kernels: wgrad_route)
 int wgrad_tap_dispatch(const WgradParams& w, hipStream_t st) {
     const TapGeom g = tap_geom(w);
-    if (!g.ok || !w.ws || !w.dw || w.ws_bytes < (size_t)g.combos * g.nsplit * g.BMK * g.BNC * sizeof(float))
-        return PRIMIA_ERR_UNSUPPORTED;
+    if (!g.ok || w.form != kWgWorkspace || !w.ws || !w.dw || w.ws_bytes < wgrad_tap_ws_bytes(w)) return PRIMIA_ERR_INTERNAL;
     return g.wide ? launch_tap<256, 128, 2, 4>(w, g, st) : launch_tap<128, 64, 4, 2>(w, g, st);
 }
 

@@ -69,7 +69,7 @@ int main(int argc, char** argv) {
                sh.name, N, us, tf, (int)WGP33_DBG, dense ? "dense" : "relu-like", ng, us / ng);
 #ifdef WGP33_PROF
         {
-            const PatchGeom g = patch_geom(p);
+            const PatchGeom g = patch_geom(p, p.form);
             const int nblk = g.combos * g.nsplit;
             unsigned long long* prof;
             hipMalloc(&prof, (size_t)nblk * 8 * 6 * 8);
