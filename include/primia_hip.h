@@ -747,6 +747,43 @@ int primia_dp_noise_add(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint
 int64_t primia_dp_noise_blocks(int64_t n);     /* ceil(n / 16): the blocks a call on n elements draws */
 
 /* ------------------------------------------------------------------------------------------
+ * BatchNorm with FROZEN statistics: DP-SGD fine-tuning from pretrained (BatchNorm) weights.  Every norm layer is the
+ * per-channel affine map z = (y - running_mean) * invstd * gamma + beta with invstd = 1 / sqrtf(running_var + eps);
+ * gamma and beta train, the running statistics are never written.  A sample's gradient then depends on that sample
+ * alone, as under GroupNorm.  Forward: primia_bn_fwd_eval / primia_bn_fwd_eval_mask.  The backward pass replaces the
+ * autograd of F.batch_norm(..., training=False) (+ F.relu / the residual add) under loss.backward()
+ * (torchlib/models.py:261-264).  Tensors are [N*HW, C]; sample n owns rows n*HW .. (n+1)*HW - 1.
+ *     g         = relu ? (mask ? dz : 0) : dz
+ *     dy        = g * (gamma * invstd)                           rounded once to the storage dtype
+ *     g_out     = g                                              optional; may alias dz
+ *     ps_dgamma = sum over the sample's rows of g * ((y - running_mean) * invstd)       [N][C]
+ *     ps_dbeta  = sum over the sample's rows of g                                       [N][C]
+ * One pass over the tensors; the sums use no atomics and are bitwise reproducible.  C <= 512 and the shape rules of the
+ * other BatchNorm entry points; PRIMIA_ERR_WORKSPACE for a workspace below primia_bn_frozen_workspace_bytes.
+ * ------------------------------------------------------------------------------------------ */
+int64_t primia_bn_frozen_workspace_bytes(int N, int HW, int C);
+/* primia_bn_fwd_eval with relu = 1 that also writes one mask byte per 16-byte chunk (bit i = stored z_i > 0). */
+int primia_bn_fwd_eval_mask(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
+                            const float* beta, const float* running_mean, const float* running_var, int64_t M, int C,
+                            float eps, int dtype, primia_stream_t stream);
+/* mask = stored z > 0 (z may be NULL when relu == 0). */
+int primia_bn_frozen_bwd(const void* y, const void* z, const void* dz, void* dy, void* g_out, const float* gamma,
+                         const float* running_mean, const float* running_var, float eps, float* ps_dgamma,
+                         float* ps_dbeta, int N, int HW, int C, int relu, void* workspace, int64_t workspace_bytes,
+                         int dtype, primia_stream_t stream);
+/* mask = the bytes primia_bn_fwd_eval_mask wrote (residual layers: 1/16 of the bytes of z). */
+int primia_bn_frozen_bwd_mask(const void* y, const uint8_t* relu_mask, const void* dz, void* dy, void* g_out,
+                              const float* gamma, const float* running_mean, const float* running_var, float eps,
+                              float* ps_dgamma, float* ps_dbeta, int N, int HW, int C, void* workspace,
+                              int64_t workspace_bytes, int dtype, primia_stream_t stream);
+/* z = relu(bn(y)) WITHOUT a residual: the mask is recomputed from y with the forward pass's own expression (the sign of
+ * the value it stored), z is not read.  Same results as the two above, bit for bit. */
+int primia_bn_frozen_relu_bwd(const void* y, const void* dz, void* dy, const float* gamma, const float* beta,
+                              const float* running_mean, const float* running_var, float eps, float* ps_dgamma,
+                              float* ps_dbeta, int N, int HW, int C, void* workspace, int64_t workspace_bytes, int dtype,
+                              primia_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pooling — replaces F.max_pool2d(3,2,1) / F.avg_pool2d(3,2,1) (torchlib/models.py:384-389)
  * and nn.AvgPool2d(7) + flatten (models.py:400-404, 477-478).
  * ------------------------------------------------------------------------------------------ */

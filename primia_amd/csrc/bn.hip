@@ -15,11 +15,7 @@ namespace primia {
 
 constexpr int kMaxPartialBlocks = 1024;
 
-// z before activation: one explicit fma, so the backward pass can recompute the ReLU mask from y
-// bit-identically to what the forward pass stored (see primia_bn_relu_bwd).
-__device__ __forceinline__ float bn_affine(float y, float mean, float scale, float beta) {
-    return __builtin_fmaf(y - mean, scale, beta);
-}
+// (bn_affine, round_to and bn_shape_ok live in common.h: csrc/bn_frozen.hip shares them)
 
 // ---- generic column reduction of two per-element quantities ------------------------------------
 // Threads are laid out [rows_per_pass][C/CH]; thread (rg, cc) owns channels cc*CH..+CH-1.
@@ -346,15 +342,6 @@ __device__ __forceinline__ void bn_inline_finalize_stats(const BnInline& q, int 
         lds_mean[c] = __hip_atomic_load(q.save_mean + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         lds_invstd[c] = __hip_atomic_load(q.save_invstd + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-}
-
-template <typename T>
-__device__ __forceinline__ float round_to(float v) {
-    return v;
-}
-template <>
-__device__ __forceinline__ float round_to<bf16>(float v) {
-    return bf16_to_f32(f32_to_bf16(v));
 }
 
 // z = act((y - mean) * (invstd * gamma) + beta [+ residual]); optionally one mask byte per 16-byte chunk with
@@ -975,11 +962,6 @@ static inline int stream_blocks(long nchunks) {
     return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
 }
 
-static inline bool bn_shape_ok(long M, int C, int dtype) {
-    const int ch = dtype == PRIMIA_F32 ? 4 : 8;
-    return M > 0 && C > 0 && C <= 512 && C % ch == 0 && 256 % (C / ch) == 0;
-}
-
 template <typename T>
 static int bn_fwd_train_impl(const void* y, const void* residual, void* z, const float* gamma,
                              const float* beta, float* running_mean, float* running_var,
@@ -1495,6 +1477,29 @@ int primia_bn_fwd_eval(const void* y, const void* residual, void* z, const float
         bn_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>(
             (const bf16*)y, (const bf16*)residual, (bf16*)z, gamma, beta, running_mean, running_var, eps, 1,
             nchunks, C, relu);
+    } else {
+        return PRIMIA_ERR_ARG;
+    }
+    return launch_status();
+}
+
+// primia_bn_fwd_eval on a residual layer, plus the 1-bit ReLU mask of the stored z (the bytes primia_bn_frozen_bwd_mask reads)
+int primia_bn_fwd_eval_mask(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
+                            const float* beta, const float* running_mean, const float* running_var, int64_t M, int C,
+                            float eps, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && z && relu_mask && gamma && beta && running_mean && running_var);
+    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == PRIMIA_F32) {
+        const long nchunks = M * C / 4;
+        bn_apply_kernel<float><<<stream_blocks(nchunks), 256, 0, st>>>(
+            (const float*)y, (const float*)residual, (float*)z, gamma, beta, running_mean, running_var, eps, 1,
+            nchunks, C, 1, relu_mask);
+    } else if (dtype == PRIMIA_BF16) {
+        const long nchunks = M * C / 8;
+        bn_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>(
+            (const bf16*)y, (const bf16*)residual, (bf16*)z, gamma, beta, running_mean, running_var, eps, 1,
+            nchunks, C, 1, relu_mask);
     } else {
         return PRIMIA_ERR_ARG;
     }

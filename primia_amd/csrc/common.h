@@ -120,6 +120,29 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// BatchNorm's z before activation: one explicit fma, so a backward pass can recompute the ReLU mask from y
+// bit-identically to what the forward pass stored (primia_bn_relu_bwd, primia_bn_frozen_relu_bwd).
+__device__ __forceinline__ float bn_affine(float y, float mean, float scale, float beta) {
+    return __builtin_fmaf(y - mean, scale, beta);
+}
+
+// the value a store to a T tensor keeps
+template <typename T>
+__device__ __forceinline__ float round_to(float v) {
+    return v;
+}
+template <>
+__device__ __forceinline__ float round_to<bf16>(float v) {
+    return bf16_to_f32(f32_to_bf16(v));
+}
+
+// [M, C] tensors the BatchNorm kernels take: whole 16-byte chunks per row, a row's chunks divide the 256-thread block,
+// per-channel tables of 512 entries
+static inline bool bn_shape_ok(long M, int C, int dtype) {
+    const int ch = dtype == PRIMIA_F32 ? 4 : 8;
+    return M > 0 && C > 0 && C <= 512 && C % ch == 0 && 256 % (C / ch) == 0;
+}
+
 // The stem's BatchNorm seen through ReLU + max-pool: where ReLU was active the pooled value IS the activation, so
 // xhat = (p - beta) / gamma can be read off the pooled tensor (bn.hip PoolScatterFn, gn.hip GnPoolScatterFn,
 // conv3x3_c64.hip mode 3).  p is a STORED value: its rounding error |p| * 2^-9 (bf16) is divided by gamma, so a channel

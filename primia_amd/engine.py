@@ -37,7 +37,10 @@ class ResNet18Engine:
                  dtype=torch.bfloat16, device="cuda:0", norm="batch", groups=32, options=None, share=None):
         """norm="batch": the reference model.  norm="group": GroupNorm(groups, C) in place of every
         BatchNorm (ResNet's `norm_layer` hook, torchlib/models.py:355) — the BN-free network the
-        DP-SGD configuration needs (train.py:308).
+        DP-SGD configuration needs (train.py:308).  norm="frozen": the reference model with every BatchNorm applied
+        with its running statistics in training too (gamma / beta train, the statistics are never written) — a sample's
+        gradient depends on that sample alone, so DP-SGD can fine-tune pretrained BatchNorm weights; state dicts are
+        the BatchNorm network's.
         `options`: {name: value} overriding the schedule switches below (class attributes such as fwd_pair,
         wgrad_overlap, wgrad_flush_last, fuse_stem, dp_keep ...) for THIS engine before its buffers are sized.  Nothing here
         reads the environment; the kernel library's own switches are `_lib.set_option` (primia_set_option).
@@ -56,8 +59,8 @@ class ResNet18Engine:
         # primia_set_option("c64_blocks" | "lh2" | ...) would make kernels write more partials than were allocated)
         self._options_epoch = query("primia_options_epoch")
         self.spec: NetSpec = resnet18_spec(num_classes, in_channels, input_size, pooling)
-        if norm not in ("batch", "group"):
-            raise ValueError("norm must be 'batch' or 'group'")
+        if norm not in ("batch", "group", "frozen"):
+            raise ValueError("norm must be 'batch', 'group' or 'frozen'")
         self.norm, self.groups = norm, int(groups)
         self.N = int(batch_size)
         self.dtype = dtype
@@ -234,7 +237,7 @@ class ResNet18Engine:
         # the stem convolutions read the padded input copy; the unpadded one is written only where the halo kernels on the
         # padded one do not serve the shape
         self._stem_padded = self.x0p is not None
-        self._x0_valid = not self._stem_padded or (norm == "group" and self._stem_ws_bytes <= 0)
+        self._x0_valid = not self._stem_padded or (norm in ("group", "frozen") and self._stem_ws_bytes <= 0)
         self.stat_slots = query("primia_conv_stat_slots")
         for c in self.spec.convs:   # slots the kernel serving this conv writes (per-block partials for layer1's)
             self.convs[c.name].stat_slots = (query("primia_conv_stat_slots_for", self.convs[c.name].desc, self.dt)
@@ -269,6 +272,10 @@ class ResNet18Engine:
             self.save = {bn_name(c.name): (torch.empty(N * self.groups, dtype=torch.float32, device=dev),
                                            torch.empty(N * self.groups, dtype=torch.float32, device=dev))
                          for c in self.spec.convs}
+        if norm == "frozen":
+            self.bn_ws_bytes = max([self.bn_ws_bytes] + [
+                query("primia_bn_frozen_workspace_bytes", N, self.convs[c.name].desc.Ho ** 2, c.cout) for c in self.spec.convs])
+        if norm in ("group", "frozen"):
             self.ps_affine = {bn_name(c.name): (torch.empty(N, c.cout, dtype=torch.float32, device=dev),
                                                 torch.empty(N, c.cout, dtype=torch.float32, device=dev))
                               for c in self.spec.convs}
@@ -416,6 +423,16 @@ class ResNet18Engine:
         C = y.shape[1]
         M = y.shape[0]
         g, be = self.views[b + ".weight"], self.views[b + ".bias"]
+        if self.norm == "frozen":  # identical in train and eval mode: the running statistics are read, never written
+            rm, rv = self.views[b + ".running_mean"], self.views[b + ".running_var"]
+            if self.training and residual is not None and relu and self.gn_relu_masks:
+                # residual layer: also write the 1-bit ReLU mask the backward passes read instead of z
+                if b not in self.relu_masks:
+                    self.relu_masks[b] = torch.empty(y.numel() * y.element_size() // 16, dtype=torch.uint8, device=y.device)
+                call("primia_bn_fwd_eval_mask", y, residual, z, self.relu_masks[b], g, be, rm, rv, M, C, BN_EPS, self.dt)
+                return
+            call("primia_bn_fwd_eval", y, residual, z, g, be, rm, rv, M, C, BN_EPS, int(relu), self.dt)
+            return
         if self.norm == "group":  # identical in train and eval mode: no running statistics
             sm, si = self.save[b]
             if self.training and residual is not None and relu and self.gn_relu_masks:
@@ -650,6 +667,25 @@ class ResNet18Engine:
         the accumulating data gradient that consumes it applies the mask itself (primia_conv2d_dgrad_masked_acc)."""
         b = bn_name(conv_name)
         sm, si = self.save[b]
+        if self.norm == "frozen":
+            psg, psb = self.ps_affine[b]
+            C, HW = y.shape[1], y.shape[0] // self.N
+            gam, rm, rv = self.views[b + ".weight"], self.views[b + ".running_mean"], self.views[b + ".running_var"]
+            if relu and g_out is None:
+                # z = relu(bn(y)), no residual: the mask is recomputed from y, z is not read
+                call("primia_bn_frozen_relu_bwd", y, dz, dy, gam, self.views[b + ".bias"], rm, rv, BN_EPS, psg, psb,
+                     self.N, HW, C, self.bn_ws, self.bn_ws_bytes, self.dt)
+            elif relu and g_out is not None and b in self.relu_masks:
+                # residual layer: mask bytes instead of z; keep_g = False: the masked gradient is not written either
+                call("primia_bn_frozen_bwd_mask", y, self.relu_masks[b], dz, dy, g_out if keep_g else None, gam, rm, rv,
+                     BN_EPS, psg, psb, self.N, HW, C, self.bn_ws, self.bn_ws_bytes, self.dt)
+            else:
+                call("primia_bn_frozen_bwd", y, z, dz, dy, g_out, gam, rm, rv, BN_EPS, psg, psb, self.N, HW, C, int(relu),
+                     self.bn_ws, self.bn_ws_bytes, self.dt)
+            if self.dp is None:  # plain fine-tuning: dgamma / dbeta = sum over samples
+                call("primia_weighted_colsum", psg, self.ones_n, self._gviews[b + ".weight"], self.N, C)
+                call("primia_weighted_colsum", psb, self.ones_n, self._gviews[b + ".bias"], self.N, C)
+            return
         if self.norm == "group":
             psg, psb = self.ps_affine[b]
             C = y.shape[1]
@@ -888,8 +924,8 @@ class ResNet18Engine:
                  self._gviews[b2 + ".bias"], self._gviews[bd + ".weight"], self._gviews[bd + ".bias"],
                  t[p + ".y2"].shape[0], t[p + ".y2"].shape[1], self.bn_ws, self.bn_ws_bytes, self.dt)
         else:
-            # GroupNorm: the downsample's backward pass applies bn2's ReLU mask to dout itself (primia_gn_bwd_mask on yd,
-            # below), so the masked gradient is not written here
+            # GroupNorm / frozen BatchNorm: the downsample's backward pass applies bn2's ReLU mask to dout itself
+            # (primia_gn_bwd_mask / primia_bn_frozen_bwd_mask on yd, below), so the masked gradient is not written here
             self._bn_bwd(blk.conv2.name, t[p + ".y2"], t[p + ".out"], dout, t[p + ".dy2"], dout, True, keep_g=not masked)
         self._backward_conv2(blk)
         if masked and self.norm == "group":
@@ -897,6 +933,16 @@ class ResNet18Engine:
             yd = t[p + ".yd"]
             call("primia_gn_bwd_mask", yd, self.relu_masks[b2], dout, dyd, None, self.views[bd + ".weight"], smd, sid, psg,
                  psb, self.N, yd.shape[0] // self.N, yd.shape[1], self.groups, self.bn_ws, self.bn_ws_bytes, self.dt)
+            if self.dp is None:
+                call("primia_weighted_colsum", psg, self.ones_n, self._gviews[bd + ".weight"], self.N, yd.shape[1])
+                call("primia_weighted_colsum", psb, self.ones_n, self._gviews[bd + ".bias"], self.N, yd.shape[1])
+        elif masked and self.norm == "frozen":
+            # ... and so does the frozen downsample BatchNorm (primia_bn_frozen_bwd_mask on yd with bn2's mask bytes)
+            psg, psb = self.ps_affine[bd]
+            yd = t[p + ".yd"]
+            call("primia_bn_frozen_bwd_mask", yd, self.relu_masks[b2], dout, dyd, None, self.views[bd + ".weight"],
+                 self.views[bd + ".running_mean"], self.views[bd + ".running_var"], BN_EPS, psg, psb, self.N,
+                 yd.shape[0] // self.N, yd.shape[1], self.bn_ws, self.bn_ws_bytes, self.dt)
             if self.dp is None:
                 call("primia_weighted_colsum", psg, self.ones_n, self._gviews[bd + ".weight"], self.N, yd.shape[1])
                 call("primia_weighted_colsum", psb, self.ones_n, self._gviews[bd + ".bias"], self.N, yd.shape[1])
@@ -1145,17 +1191,18 @@ class ResNet18Engine:
         """Per-sample gradient clipping + Gaussian noise, pytorch-dp semantics:
             g = (1/B) * ( sum_n min(1, C / (||g_n|| + 1e-6)) * g_n  +  N(0, (noise_multiplier*C)^2 I) )
         with g_n the gradient of sample n's OWN loss over all 62 parameter tensors (flat L2 norm).
-        Needs norm="group".  `noise` (fp32 [P], standard normal) may be given for reproducibility; without it (and without
+        Needs norm="group" or norm="frozen".  `noise` (fp32 [P], standard normal) may be given for reproducibility; without it (and without
         a `generator`) the root engine's `dp_noise` stream is used when set, torch.randn otherwise.
 
         How: one ordinary backward pass yields every layer's activation gradient dy (samples are
-        independent under GroupNorm).  Pass 1 runs the weight-gradient kernels with one pixel split per image
+        independent under GroupNorm and under BatchNorm with frozen statistics).  Pass 1 runs the weight-gradient kernels with one pixel split per image
         and has every block add the squares of ITS (complete) per-sample tile to ||g_n||^2 — the per-sample
         gradients are never written; then each sample's rows of
         dy are scaled by its clip factor and the ordinary batched wgrad — linear in dy — produces
         sum_n clip_n * g_n directly."""
-        if self.norm != "group":
-            raise _lib.PrimiaError("DP-SGD needs the BatchNorm-free network: ResNet18Engine(norm='group')")
+        if self.norm not in ("group", "frozen"):
+            raise _lib.PrimiaError("DP-SGD needs per-sample independent norm layers: ResNet18Engine(norm='group') or "
+                                   "norm='frozen' (BatchNorm with fixed statistics)")
         N, nc, dev = self.N, self.spec.num_classes, self.device
         # per-sample loss gradients: softmax - onehot (xent gives them divided by the batch size)
         call("primia_xent_hard", self.logits, target, None, self.loss, self.dlogits, N, nc)
@@ -1332,8 +1379,9 @@ class ResNet18Engine:
 
     def note_replayed_steps(self, n):
         """Training steps that ran as hipGraph replays: advance the host-side counters forward() would have advanced."""
-        for b in self.num_batches_tracked:
-            self.num_batches_tracked[b] += int(n)
+        if self.norm != "frozen":        # (frozen statistics: no batch is ever tracked)
+            for b in self.num_batches_tracked:
+                self.num_batches_tracked[b] += int(n)
         if self.opt_state is not None:
             self.opt_steps += int(n)
 

@@ -61,6 +61,8 @@ def _eager(engine, eng, optimizer, data, target, soft):
 
 def _key(eng, optimizer, soft):
     key = (eng.N, bool(soft), optimizer.kind, bool(eng.fuse_sgd_tail), eng.class_weight is not None)
+    if eng.norm == "frozen":        # (a frozen-statistics step launches other kernels than a GroupNorm one)
+        key += ("frozen BatchNorm",)
     root = eng._root
     if getattr(root, "dp_params", None) is not None:
         # the DP-SGD parameters are frozen into the graph as kernel arguments, and so is the noise stream's key

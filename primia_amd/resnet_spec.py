@@ -107,7 +107,8 @@ def param_entries(spec: NetSpec):
 
 def buffer_entries(spec: NetSpec, norm: str = "batch"):
     """(key, shape) of the float buffers (running_mean, running_var) in reference order.
-    GroupNorm (norm="group", the DP configuration) has none."""
+    GroupNorm (norm="group", the DP configuration) has none; norm="frozen" (BatchNorm applied with fixed statistics) is a
+    BatchNorm network: the same buffers."""
     out = []
     if norm == "group":
         return out
@@ -126,7 +127,7 @@ def state_dict_keys(spec: NetSpec, norm: str = "batch"):
     def conv_bn(c: ConvSpec):
         b = bn_name(c.name)
         keys.extend([c.name + ".weight", b + ".weight", b + ".bias"])
-        if norm == "batch":
+        if norm in ("batch", "frozen"):
             keys.extend([b + ".running_mean", b + ".running_var", b + ".num_batches_tracked"])
 
     conv_bn(spec.stem)

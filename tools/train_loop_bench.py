@@ -8,7 +8,8 @@ a train() call over `--steps` batches bracketed by device synchronisations; one 
 (the graphed mode captures its step there).  Prints one JSON line: per mode the median and every run's ms per step and
 images per second.  --dp times the DP-SGD loop (GroupNorm network, clip 1.0, noise multiplier 1.3: train.py with
 differentially_private = yes) with --dp_noise torch (torch.randn; --hip_graph leaves its steps eager) or chacha (the
-device ChaCha20 stream of primia_amd.dp_noise; --hip_graph replays the steps).  Needs a GPU (there is no CPU path)."""
+device ChaCha20 stream of primia_amd.dp_noise; --hip_graph replays the steps); --dp_norm frozen times it on the BatchNorm
+network with frozen statistics (train.py's --dp_norm frozen) instead.  Needs a GPU (there is no CPU path)."""
 import argparse
 import json
 import os
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--dp", action="store_true", help="the DP-SGD loop (differentially_private = yes)")
     ap.add_argument("--dp_noise", choices=("torch", "chacha"), default="torch", help="with --dp: train.py's --dp_noise")
+    ap.add_argument("--dp_norm", choices=("group", "frozen"), default="group", help="with --dp: train.py's --dp_norm")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("train_loop_bench needs a GPU")
@@ -52,7 +54,7 @@ def main():
     for m in modes:
         torch.manual_seed(42)
         eng = ResNet18Engine(a.batch, 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
-                             norm="group" if a.dp else "batch")
+                             norm=a.dp_norm if a.dp else "batch")
         eng.init_weights()
         if a.dp:
             eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": 1.3}
@@ -80,6 +82,7 @@ def main():
         from primia_amd.graphed_train import captures
 
         out["dp_noise"] = a.dp_noise
+        out["dp_norm"] = a.dp_norm
         out["graphed_keys"] = {m: len(captures(runs[m][0])) for m in modes}
     for m in modes:
         ts = runs[m][3]

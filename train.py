@@ -5,7 +5,8 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
 
     python train.py --config configs/torch/pneumonia-resnet-pretrained.ini --train_federated \
         [--unencrypted_aggregation] [--data_dir DIR|synthetic] [--cuda] [--resume_checkpoint P] \
-        [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N]
+        [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N] \
+        [--dp_norm {group,frozen}]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -88,9 +89,10 @@ def load_pretrained(engine, num_classes, rank=0, world=1):
     reference's main preset depends on these weights; training from scratch instead would be a different experiment)
     unless PRIMIA_ALLOW_RANDOM_INIT=1 says that is what is wanted.  Under torch.distributed.run rank 0 reads the file
     and every rank takes rank 0's arena, so all clients start from the same model whatever their own caches hold."""
-    if engine.norm != "batch":
+    if engine.norm == "group":
         raise SystemExit("pretrained ImageNet weights carry BatchNorm statistics; differentially_private = yes builds "
-                         "a GroupNorm network (train.py:304-334)")
+                         "a GroupNorm network (train.py:304-334).  --dp_norm frozen keeps the BatchNorm network and "
+                         "applies it with those statistics held fixed")
     # rank 0's outcome travels to every rank BEFORE anybody raises: 1 loaded, 0 no file, 2 the file does not fit / does
     # not load (ADVICE r04: a SystemExit on rank 0 alone left the others blocked in the broadcast until the RCCL timeout)
     status, problem = 1, ""
@@ -236,11 +238,19 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
     if dp_noise_kind == "chacha" and not args.differentially_private:
         warn("--dp_noise chacha has no effect: the config has differentially_private = no, no noise is applied")
 
+    dp_norm = getattr(cmd_args, "dp_norm", "group") if cmd_args is not None else "group"
+    if dp_norm == "frozen" and not args.differentially_private:
+        warn("--dp_norm frozen has no effect: the config has differentially_private = no, BatchNorm trains as usual")
+    elif dp_norm == "frozen" and not args.pretrained:
+        warn("--dp_norm frozen without pretrained = yes: the frozen statistics are the initial mean 0 / variance 1, every "
+             "norm layer is a learned per-channel affine map")
+
     def make_engine(client=None):
         # differentially_private = yes (train.py:304-334 of the reference): BatchNorm is rejected by the
-        # PrivacyEngine, so the network is built with GroupNorm and every step clips / noises per sample
+        # PrivacyEngine, so the network is built with GroupNorm — or (--dp_norm frozen) BatchNorm is applied with its
+        # running statistics held fixed, which keeps samples independent too — and every step clips / noises per sample
         eng = ResNet18Engine(args.batch_size, num_classes, channels, size, args.pooling_type,
-                             dtype=dtype, device=device, norm="group" if args.differentially_private else "batch")
+                             dtype=dtype, device=device, norm=dp_norm if args.differentially_private else "batch")
         if args.differentially_private:
             eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": 1.3}
             if dp_noise_kind == "chacha":
@@ -443,7 +453,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
     return best_score
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--config", type=str, required=True, help="Path to the configuration file (.ini).")
     parser.add_argument("--train_federated", action="store_true", help="Train with federated learning.")
@@ -469,6 +479,16 @@ if __name__ == "__main__":
                         help="derive the --dp_noise chacha key from this seed: a reproducible, PREDICTABLE noise stream "
                              "that restarts from its beginning when a run is resumed, and is shared by a vanilla run and "
                              "federated client 0 (tests only: no privacy)")
+    parser.add_argument("--dp_norm", choices=("group", "frozen"), default="group",
+                        help="differentially_private = yes: the norm layers that keep samples independent.  group: "
+                             "GroupNorm(32, C), trained from a random initialisation (pretrained = yes is refused).  frozen: "
+                             "the BatchNorm network applied with its running statistics held fixed (gamma / beta train): "
+                             "DP-SGD fine-tuning of pretrained weights; the checkpoint is an ordinary BatchNorm state dict.")
+    return parser
+
+
+if __name__ == "__main__":
+    parser = build_parser()
     cmd_args = parser.parse_args()
     if cmd_args.debug_dp_noise_seed is not None:
         if cmd_args.dp_noise != "chacha":
