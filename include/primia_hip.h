@@ -1114,7 +1114,17 @@ int primia_beaver_combine_matmul(int j, const int64_t* delta, const int64_t* eps
  *   cw_sigma  uint64 [32][2][n]    DIF only
  *   cw_s      uint64 [32][2][n]
  *   cw_leaf   int32  [33][n]       DIF;  DPF: int64 [n]
- * = the content of the reference key tuple (alpha, s0, *_CW, CW_leaf), 1,204 B per DIF key. */
+ * = the content of the reference key tuple (alpha, s0, *_CW, CW_leaf), 1,204 B per DIF key.
+ * The DIF comparison at a width of `bits` in [32, 64] (the *_n entry points at the end of this section): the
+ * reference's level step `bits` times, on bits bits-1 .. 0 of alpha and of the masked input, most significant first:
+ *   x         uint64 [n]           the opened masked input, below 2^bits
+ *   s0        uint64 [2][n]
+ *   cw_bits   uint8  [bits][n]
+ *   cw_sigma  uint64 [bits][2][n]
+ *   cw_s      uint64 [bits][2][n]
+ *   cw_leaf   int32  [bits+1][n]
+ * 16 + 37 * bits + 4 B per DIF key (1,204 at 32, 2,388 at 64); at bits = 32 every field holds what the 32-bit entry points
+ * read and write (x apart, which they keep in uint32). */
 /* mask_builder (fss.py:189-204): r = (x1 - x2) + alpha_share. */
 int primia_fss_mask(const int64_t* x1, const int64_t* x2, const uint64_t* alpha_share, int64_t* r,
                     int64_t n, primia_stream_t stream);
@@ -1143,6 +1153,26 @@ int primia_dif_keygen(const uint64_t* alpha, const uint64_t* s0_pair, uint8_t* c
                       primia_stream_t stream);
 int primia_dpf_keygen(const uint64_t* alpha, const uint64_t* s0_pair, uint8_t* cw_bits,
                       uint64_t* cw_s, int64_t* cw_n, int64_t n, primia_stream_t stream);
+/* The DIF entry points above at a width of `bits` (key layout: the head of this section); bits outside [32, 64]:
+ * PRIMIA_ERR_ARG.  The result is party b's share of [(d + alpha) mod 2^bits <= alpha] for the difference d = x1 - x2: [d <= 0]
+ * while |d| < 2^(bits-1) and alpha + d does not leave [0, 2^bits), which fails with probability |d| / 2^bits over the draw.
+ *   primia_fss_alpha_split_n   alpha [n] &= 2^bits - 1, r [n] &= 2^bits - 1, alpha0 = (alpha - r) mod 2^bits; seeds as above
+ *   primia_fss_open_n          x = (r0 + r1) mod 2^bits, uint64
+ *   primia_dif_keygen_n        the low `bits` bits of alpha (higher ones are ignored)
+ *   primia_dif_eval_n          x uint64 [n] (bits above the width are ignored)
+ *   primia_dif_eval_local_n    primia_dif_eval_local with the open taken mod 2^bits */
+int primia_fss_alpha_split_n(uint64_t* alpha, uint64_t* s0_pair, uint64_t* r, uint64_t* alpha0, int64_t n, int bits,
+                             primia_stream_t stream);
+int primia_fss_open_n(const int64_t* r0, const int64_t* r1, uint64_t* x, int64_t n, int bits, primia_stream_t stream);
+int primia_dif_keygen_n(const uint64_t* alpha, const uint64_t* s0_pair, uint8_t* cw_bits, uint64_t* cw_sigma, uint64_t* cw_s,
+                        int32_t* cw_leaf, int64_t n, int bits, primia_stream_t stream);
+int primia_dif_eval_n(int b, const uint64_t* x, const uint64_t* s0, const uint8_t* cw_bits, const uint64_t* cw_sigma,
+                      const uint64_t* cw_s, const int32_t* cw_leaf, int64_t* out, int64_t n, int bits, primia_stream_t stream);
+int primia_dif_eval_local_n(const int64_t* x1_0, const int64_t* x1_1, int w1, int start1, const int64_t* x2_0,
+                            const int64_t* x2_1, int w2, int start2, int len, const uint64_t* alpha0, const uint64_t* alpha1,
+                            const uint64_t* s0_0, const uint64_t* s0_1, const uint8_t* cw_bits, const uint64_t* cw_sigma,
+                            const uint64_t* cw_s, const int32_t* cw_leaf, int64_t* out0, int64_t* out1, int64_t n, int bits,
+                            primia_stream_t stream);
 
 #ifdef __cplusplus
 }

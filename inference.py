@@ -86,7 +86,15 @@ if __name__ == "__main__":
                              "pass of --hip_graph / --three_role is padded with all-zero images whose rows are dropped")
     parser.add_argument("--precision_fractional", type=int, default=16,
                         help="encrypted inference: fractional decimal digits of the fixed-point encoding (default 16, the "
-                             "reference's literal, at which products wrap in the 2^64 ring; 3 keeps logits meaningful)")
+                             "reference's literal, at which products wrap in the 2^64 ring; 3 keeps logits meaningful).  "
+                             "More digits make the encoded activations larger and the 32-bit comparisons wrong more often: "
+                             "see --fss_bits")
+    parser.add_argument("--fss_bits", type=int, default=32,
+                        help="encrypted inference: the width n of the ReLU / max-pool / argmax comparisons, 32 (default, the "
+                             "reference's) to 64.  A comparison of two encoded values d apart is wrong with probability "
+                             "|d| / 2^n over the provider's mask, and always beyond 2^(n-1): at 32 bits and 6 fractional "
+                             "digits that is every activation above 2147.  Key bytes (60 + 37 n per comparison) and the "
+                             "comparison kernels' time grow linearly with n")
     parser.add_argument("--hip_graph", action="store_true",
                         help="encrypted inference: capture the online phase once as a hipGraph and replay it per image "
                              "(the dealer refills the primitive buffers between images)")
@@ -108,6 +116,9 @@ if __name__ == "__main__":
         print("WARNING: --debug_dealer_seed makes every mask, triple and FSS key predictable: no confidentiality",
               file=sys.stderr)
     reveal = cmd_args.reveal
+    fss_bits = cmd_args.fss_bits
+    if not 32 <= fss_bits <= 64:
+        raise SystemExit(f"--fss_bits must be in [32, 64], got {fss_bits}")
     if reveal == "class" and os.environ.get("PRIMIA_DUMP_LOGITS"):
         raise SystemExit("--reveal class: the logits are never opened, there is nothing for PRIMIA_DUMP_LOGITS to write")
     if not torch.cuda.is_available():
@@ -149,7 +160,8 @@ if __name__ == "__main__":
                                     state_dict=sd if link.role == 0 else None,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
-                                    precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal)
+                                    precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal,
+                                    fss_bits=fss_bits)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
@@ -162,9 +174,10 @@ if __name__ == "__main__":
             from primia_amd.secure import GraphedSecureInference
 
             model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
-                                           seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal)
+                                           seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal,
+                                           fss_bits=fss_bits)
         else:
-            ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed), base=10,
+            ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
                                 precision_fractional=cmd_args.precision_fractional)
             model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling, reveal=reveal)
         logits = []

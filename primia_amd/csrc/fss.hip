@@ -1,6 +1,8 @@
 // Function Secret Sharing kernels (2-party DIF comparison / DPF equality on 32-bit inputs,
 // lambda = 127) — the per-party evaluation and the dealer's key generation of
-// syft/frameworks/torch/mpc/fss.py, one comparison per lane.
+// syft/frameworks/torch/mpc/fss.py, one comparison per lane.  The DIF comparison also exists at a run-time
+// width of 32..64 bits (the *_n kernels): the reference's level step, `bits` times -- one walk each for
+// evaluation and key generation (DIF_EVAL_WALK, dif_keygen_walk), which the 32-bit kernels expand with the width a constant.
 //
 // The PRG is SHA-512 (DIF) / SHA-256 (DPF) of the 16-byte seed (the reference calls the `shaloop`
 // wheel on (n,16)-byte rows, fss.py:532,581).  A 16-byte message is one padded block whose words
@@ -175,6 +177,39 @@ __device__ __forceinline__ HSide h_side(const u64 buf[8], int side) {
 __device__ __forceinline__ long conv31(u64 last_word) { return (long)(last_word & 0x7fffffffULL); }
 
 // ---- DIF.eval (fss.py:400-428) ------------------------------------------------------------------------
+// The walk of comparison i down BITS levels for the party whose state is (sa, sb, t): every level's output and the leaf's are
+// added to acc.  BIT_OF_LEVEL is the bit of the masked input at level `lvl`, most significant first.  Shared by the four
+// evaluation kernels as TEXT, inside a scope that declares u64 sa, sb, t, acc, long sgn, i, n and the key pointers: as an
+// inlined function -- one level or the whole loop -- the same statements are scheduled differently, and the 32-bit local kernel
+// came out 1.1 % slower on an MI355X (6.60 against 6.53 ms on 2^20 comparisons; profiles/secure_fss_bits.txt).  Expanded with
+// BITS = 32 this is the reference's walk and compiles to the code it always did.  The loop is not unrolled across levels (one
+// level is an unrolled SHA-512), so a run-time BITS costs nothing.
+#define DIF_EVAL_WALK(BITS, BIT_OF_LEVEL)                                                                                  \
+    for (int lvl = 0; lvl < (BITS); ++lvl) {                                                                               \
+        u64 buf[8];                                                                                                        \
+        sha512_seed(sa, sb, buf);                                                                                          \
+        const int bit = (BIT_OF_LEVEL);                                                                                    \
+        HSide hs = h_side(buf, bit);                                                                                       \
+        /* t * CW_i, side `bit` of the uncompressed correction word (fss.py:456-477) */                                    \
+        const u64 m = (u64)0 - t; /* all-ones if t == 1 */                                                                 \
+        const u32 cb = cw_bits[(long)lvl * n + i];                                                                         \
+        const u64 csg1 = cw_sigma[((long)lvl * 2 + 1) * n + i];                                                            \
+        const u64 cs0 = cw_s[((long)lvl * 2 + 0) * n + i], cs1 = cw_s[((long)lvl * 2 + 1) * n + i];                        \
+        const u64 ctau = (cb >> (2 * bit)) & 1, ct = (cb >> (2 * bit + 1)) & 1;                                            \
+        const u64 sg1 = hs.sg1 ^ (csg1 & m);                                                                               \
+        const u64 tau = hs.tau ^ (ctau & m);                                                                               \
+        sa = hs.s0 ^ (cs0 & m);                                                                                            \
+        sb = hs.s1 ^ (cs1 & m);                                                                                            \
+        t = hs.t ^ (ct & m);                                                                                               \
+        const long leaf = (long)cw_leaf[(long)lvl * n + i];                                                                \
+        acc += (u64)(sgn * ((long)tau * leaf + conv31(sg1)));                                                              \
+    }                                                                                                                      \
+    const long leaf = (long)cw_leaf[(long)(BITS) * n + i];                                                                 \
+    acc += (u64)(sgn * ((long)t * leaf + conv31(sb)));
+
+// A width-n comparison works on the low n bits of alpha and of the masked input (n = 64: all of them).
+__device__ __forceinline__ u64 width_mask(int bits) { return bits == 64 ? ~0ULL : (1ULL << bits) - 1; }
+
 __global__ __launch_bounds__(256, 2) void dif_eval_kernel(int b, const u32* __restrict__ x, const u64* __restrict__ s0,
                                                        const uint8_t* __restrict__ cw_bits,
                                                        const u64* __restrict__ cw_sigma, const u64* __restrict__ cw_s,
@@ -187,28 +222,23 @@ __global__ __launch_bounds__(256, 2) void dif_eval_kernel(int b, const u32* __re
     const u32 xv = x[i];
     u64 acc = 0;
     const long sgn = b ? -1 : 1;
-    for (int lvl = 0; lvl < 32; ++lvl) {
-        u64 buf[8];
-        sha512_seed(sa, sb, buf);
-        const int bit = (xv >> (31 - lvl)) & 1;
-        HSide hs = h_side(buf, bit);
-        // t * CW_i, side `bit` of the uncompressed correction word (fss.py:456-477)
-        const u64 m = (u64)0 - t;  // all-ones if t == 1
-        const u32 cb = cw_bits[(long)lvl * n + i];
-        const u64 csg0 = cw_sigma[((long)lvl * 2 + 0) * n + i], csg1 = cw_sigma[((long)lvl * 2 + 1) * n + i];
-        const u64 cs0 = cw_s[((long)lvl * 2 + 0) * n + i], cs1 = cw_s[((long)lvl * 2 + 1) * n + i];
-        const u64 ctau = (cb >> (2 * bit)) & 1, ct = (cb >> (2 * bit + 1)) & 1;
-        const u64 sg1 = hs.sg1 ^ (csg1 & m);
-        const u64 tau = hs.tau ^ (ctau & m);
-        sa = hs.s0 ^ (cs0 & m);
-        sb = hs.s1 ^ (cs1 & m);
-        t = hs.t ^ (ct & m);
-        (void)csg0;
-        const long leaf = (long)cw_leaf[(long)lvl * n + i];
-        acc += (u64)(sgn * ((long)tau * leaf + conv31(sg1)));
-    }
-    const long leaf = (long)cw_leaf[32L * n + i];
-    acc += (u64)(sgn * ((long)t * leaf + conv31(sb)));
+    DIF_EVAL_WALK(32, (xv >> (31 - lvl)) & 1)
+    out[i] = (int64_t)acc;
+}
+// x uint64 [n] (primia_fss_open_n; bits above the width are ignored), key fields with `bits` levels
+__global__ __launch_bounds__(256, 2) void dif_eval_n_kernel(int b, int bits, const u64* __restrict__ x, const u64* __restrict__ s0,
+                                                         const uint8_t* __restrict__ cw_bits,
+                                                         const u64* __restrict__ cw_sigma, const u64* __restrict__ cw_s,
+                                                         const int32_t* __restrict__ cw_leaf, int64_t* __restrict__ out,
+                                                         long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    u64 sa = s0[i], sb = s0[n + i];
+    u64 t = (u64)b;
+    const u64 xv = x[i];
+    u64 acc = 0;
+    const long sgn = b ? -1 : 1;
+    DIF_EVAL_WALK(bits, (int)((xv >> (bits - 1 - lvl)) & 1))
     out[i] = (int64_t)acc;
 }
 
@@ -220,6 +250,19 @@ struct LeOperand {
     const u64 *p0, *p1;
     int w, start;
 };
+// the open of comparison i: the sum of both parties' masked shares in Z_2^64, before its reduction to the width
+__device__ __forceinline__ u64 le_masked_sum(const LeOperand& x1, const LeOperand& x2, int len, const u64* __restrict__ alpha0,
+                                             const u64* __restrict__ alpha1, long i) {
+    const long r = i / len, c = i - r * len;
+    const long i2 = r * x2.w + x2.start + c;
+    u64 m0 = alpha0[i] - x2.p0[i2], m1 = alpha1[i] - x2.p1[i2];
+    if (x1.p0) {
+        const long i1 = r * x1.w + x1.start + c;
+        m0 += x1.p0[i1];
+        m1 += x1.p1[i1];
+    }
+    return m0 + m1;
+}
 __global__ __launch_bounds__(256, 2) void dif_eval_local_kernel(LeOperand x1, LeOperand x2, int len, const u64* __restrict__ alpha0,
                                                                const u64* __restrict__ alpha1, const u64* __restrict__ s0_0,
                                                                const u64* __restrict__ s0_1,
@@ -230,40 +273,33 @@ __global__ __launch_bounds__(256, 2) void dif_eval_local_kernel(LeOperand x1, Le
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int b = blockIdx.y;
-    const long r = i / len, c = i - r * len;
-    const long i2 = r * x2.w + x2.start + c;
-    u64 m0 = alpha0[i] - x2.p0[i2], m1 = alpha1[i] - x2.p1[i2];
-    if (x1.p0) {
-        const long i1 = r * x1.w + x1.start + c;
-        m0 += x1.p0[i1];
-        m1 += x1.p1[i1];
-    }
-    const u32 xv = (u32)(m0 + m1);
+    const u32 xv = (u32)le_masked_sum(x1, x2, len, alpha0, alpha1, i);
     const u64* __restrict__ s0 = b ? s0_1 : s0_0;
     u64 sa = s0[i], sb = s0[n + i];
     u64 t = (u64)b;
     u64 acc = 0;
     const long sgn = b ? -1 : 1;
-    for (int lvl = 0; lvl < 32; ++lvl) {
-        u64 buf[8];
-        sha512_seed(sa, sb, buf);
-        const int bit = (xv >> (31 - lvl)) & 1;
-        HSide hs = h_side(buf, bit);
-        const u64 m = (u64)0 - t;
-        const u32 cb = cw_bits[(long)lvl * n + i];
-        const u64 csg1 = cw_sigma[((long)lvl * 2 + 1) * n + i];
-        const u64 cs0 = cw_s[((long)lvl * 2 + 0) * n + i], cs1 = cw_s[((long)lvl * 2 + 1) * n + i];
-        const u64 ctau = (cb >> (2 * bit)) & 1, ct = (cb >> (2 * bit + 1)) & 1;
-        const u64 sg1 = hs.sg1 ^ (csg1 & m);
-        const u64 tau = hs.tau ^ (ctau & m);
-        sa = hs.s0 ^ (cs0 & m);
-        sb = hs.s1 ^ (cs1 & m);
-        t = hs.t ^ (ct & m);
-        const long leaf = (long)cw_leaf[(long)lvl * n + i];
-        acc += (u64)(sgn * ((long)tau * leaf + conv31(sg1)));
-    }
-    const long leaf = (long)cw_leaf[32L * n + i];
-    acc += (u64)(sgn * ((long)t * leaf + conv31(sb)));
+    DIF_EVAL_WALK(32, (xv >> (31 - lvl)) & 1)
+    (b ? out1 : out0)[i] = (int64_t)acc;
+}
+// the same at a run-time width: masked = (...) mod 2^bits, `bits` levels
+__global__ __launch_bounds__(256, 2) void dif_eval_local_n_kernel(LeOperand x1, LeOperand x2, int len, int bits,
+                                                                 const u64* __restrict__ alpha0, const u64* __restrict__ alpha1,
+                                                                 const u64* __restrict__ s0_0, const u64* __restrict__ s0_1,
+                                                                 const uint8_t* __restrict__ cw_bits,
+                                                                 const u64* __restrict__ cw_sigma, const u64* __restrict__ cw_s,
+                                                                 const int32_t* __restrict__ cw_leaf, int64_t* __restrict__ out0,
+                                                                 int64_t* __restrict__ out1, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int b = blockIdx.y;
+    const u64 xv = le_masked_sum(x1, x2, len, alpha0, alpha1, i);      // (the walk reads its low `bits` bits)
+    const u64* __restrict__ s0 = b ? s0_1 : s0_0;
+    u64 sa = s0[i], sb = s0[n + i];
+    u64 t = (u64)b;
+    u64 acc = 0;
+    const long sgn = b ? -1 : 1;
+    DIF_EVAL_WALK(bits, (int)((xv >> (bits - 1 - lvl)) & 1))
     (b ? out1 : out0)[i] = (int64_t)acc;
 }
 
@@ -295,32 +331,41 @@ __global__ __launch_bounds__(256) void dpf_eval_kernel(int b, const u32* __restr
 // ---- build_fss_keys' host arithmetic on raw keystream words (mpc/primitives.py:237-253, mpc/fss.py:344-358,495-501), in place:
 // alpha and its mask r are reduced mod 2^32, word 0 of both parties' seeds keeps 63 bits (randbit), and party 0's share of alpha
 // is (alpha - r) mod 2^32 (party 1's is r) — what primia_amd.secure.Dealer did with torch `&` / `-` before round 6.
+__device__ __forceinline__ void alpha_split_one(u64* __restrict__ alpha, u64* __restrict__ s0p, u64* __restrict__ r,
+                                                u64* __restrict__ alpha0, long n, long i, u64 mw) {
+    const u64 m63 = 0x7FFFFFFFFFFFFFFFull;
+    const u64 a = alpha[i] & mw, rr = r[i] & mw;
+    alpha[i] = a;
+    r[i] = rr;
+    alpha0[i] = (a - rr) & mw;
+    s0p[i] &= m63;              // [party 0][word 0]
+    s0p[2 * n + i] &= m63;      // [party 1][word 0]
+}
 __global__ __launch_bounds__(256) void fss_alpha_split_kernel(u64* __restrict__ alpha, u64* __restrict__ s0p, u64* __restrict__ r,
                                                               u64* __restrict__ alpha0, long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const u64 m32 = 0xFFFFFFFFull, m63 = 0x7FFFFFFFFFFFFFFFull;
-    const u64 a = alpha[i] & m32, rr = r[i] & m32;
-    alpha[i] = a;
-    r[i] = rr;
-    alpha0[i] = (a - rr) & m32;
-    s0p[i] &= m63;              // [party 0][word 0]
-    s0p[2 * n + i] &= m63;      // [party 1][word 0]
+    alpha_split_one(alpha, s0p, r, alpha0, n, i, 0xFFFFFFFFull);
+}
+// the same mod 2^bits
+__global__ __launch_bounds__(256) void fss_alpha_split_n_kernel(u64* __restrict__ alpha, u64* __restrict__ s0p, u64* __restrict__ r,
+                                                                u64* __restrict__ alpha0, long n, int bits) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    alpha_split_one(alpha, s0p, r, alpha0, n, i, width_mask(bits));
 }
 
 // ---- DIF.keygen (fss.py:344-398), one comparison per lane --------------------------------------------
-__global__ __launch_bounds__(256, 2) void dif_keygen_kernel(const u64* __restrict__ alpha, const u64* __restrict__ s0p,
-                                                         uint8_t* __restrict__ cw_bits, u64* __restrict__ cw_sigma,
-                                                         u64* __restrict__ cw_s, int32_t* __restrict__ cw_leaf,
-                                                         long n) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const u32 av = (u32)alpha[i];
+// Comparison i with the low `bits` bits of alpha in av, most significant first (X: u32 with bits == 32 a constant, or u64).
+template <typename X>
+__device__ __forceinline__ void dif_keygen_walk(X av, int bits, const u64* __restrict__ s0p, uint8_t* __restrict__ cw_bits,
+                                                u64* __restrict__ cw_sigma, u64* __restrict__ cw_s,
+                                                int32_t* __restrict__ cw_leaf, long i, long n) {
     // s0_pair [party][word][n]
     u64 s[2][2] = {{s0p[i], s0p[n + i]}, {s0p[2 * n + i], s0p[3 * n + i]}};
     u64 t[2] = {0, 1};
-    for (int lvl = 0; lvl < 32; ++lvl) {
-        const int ai = (av >> (31 - lvl)) & 1;
+    for (int lvl = 0; lvl < bits; ++lvl) {
+        const int ai = (int)((av >> (bits - 1 - lvl)) & 1);
         u64 h0[8], h1[8];
         sha512_seed(s[0][0], s[0][1], h0);
         sha512_seed(s[1][0], s[1][1], h1);
@@ -383,7 +428,24 @@ __global__ __launch_bounds__(256, 2) void dif_keygen_kernel(const u64* __restric
         }
     }
     const long sign = t[1] ? -1 : 1;
-    cw_leaf[32L * n + i] = (int32_t)(sign * (1 - conv31(s[0][1]) + conv31(s[1][1])));
+    cw_leaf[(long)bits * n + i] = (int32_t)(sign * (1 - conv31(s[0][1]) + conv31(s[1][1])));
+}
+
+__global__ __launch_bounds__(256, 2) void dif_keygen_kernel(const u64* __restrict__ alpha, const u64* __restrict__ s0p,
+                                                         uint8_t* __restrict__ cw_bits, u64* __restrict__ cw_sigma,
+                                                         u64* __restrict__ cw_s, int32_t* __restrict__ cw_leaf,
+                                                         long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    dif_keygen_walk<u32>((u32)alpha[i], 32, s0p, cw_bits, cw_sigma, cw_s, cw_leaf, i, n);
+}
+__global__ __launch_bounds__(256, 2) void dif_keygen_n_kernel(const u64* __restrict__ alpha, const u64* __restrict__ s0p,
+                                                           uint8_t* __restrict__ cw_bits, u64* __restrict__ cw_sigma,
+                                                           u64* __restrict__ cw_s, int32_t* __restrict__ cw_leaf,
+                                                           long n, int bits) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    dif_keygen_walk<u64>(alpha[i] & width_mask(bits), bits, s0p, cw_bits, cw_sigma, cw_s, cw_leaf, i, n);
 }
 
 // ---- DPF.keygen (fss.py:286-318) ----------------------------------------------------------------------
@@ -443,6 +505,12 @@ __global__ __launch_bounds__(256) void fss_open_kernel(const u64* __restrict__ r
                                                        u32* __restrict__ x, long n) {
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) x[i] = (u32)(r0[i] + r1[i]);
+}
+__global__ __launch_bounds__(256) void fss_open_n_kernel(const u64* __restrict__ r0, const u64* __restrict__ r1,
+                                                         u64* __restrict__ x, long n, int bits) {
+    const long stride = (long)gridDim.x * 256;
+    const u64 mw = width_mask(bits);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) x[i] = (r0[i] + r1[i]) & mw;
 }
 
 }  // namespace primia
@@ -532,6 +600,66 @@ int primia_dpf_keygen(const uint64_t* alpha, const uint64_t* s0_pair, uint8_t* c
     if (n == 0) return PRIMIA_OK;
     dpf_keygen_kernel<<<ceil_div(n, 256), 256, 0, (hipStream_t)st>>>((const u64*)alpha, (const u64*)s0_pair, cw_bits,
                                                                       (u64*)cw_s, cw_n, n);
+    return launch_status();
+}
+
+// ---- the DIF comparison at a width of 32..64 bits: the entry points above with `bits` ----------------
+#define PRIMIA_REQUIRE_WIDTH(bits) PRIMIA_REQUIRE((bits) >= 32 && (bits) <= 64)
+
+int primia_fss_alpha_split_n(uint64_t* alpha, uint64_t* s0_pair, uint64_t* r, uint64_t* alpha0, int64_t n, int bits,
+                             primia_stream_t st) {
+    PRIMIA_REQUIRE_WIDTH(bits);
+    if (n == 0) return PRIMIA_OK;
+    PRIMIA_REQUIRE(alpha && s0_pair && r && alpha0 && n > 0);
+    fss_alpha_split_n_kernel<<<ceil_div(n, 256), 256, 0, (hipStream_t)st>>>((u64*)alpha, (u64*)s0_pair, (u64*)r, (u64*)alpha0, n,
+                                                                            bits);
+    return launch_status();
+}
+
+int primia_fss_open_n(const int64_t* r0, const int64_t* r1, uint64_t* x, int64_t n, int bits, primia_stream_t st) {
+    PRIMIA_REQUIRE_WIDTH(bits);
+    if (n == 0) return PRIMIA_OK;
+    PRIMIA_REQUIRE(r0 && r1 && x && n > 0);
+    long b = (n + 255) / 256;
+    fss_open_n_kernel<<<(int)(b > 4096 ? 4096 : b), 256, 0, (hipStream_t)st>>>((const u64*)r0, (const u64*)r1, (u64*)x, n, bits);
+    return launch_status();
+}
+
+int primia_dif_keygen_n(const uint64_t* alpha, const uint64_t* s0_pair, uint8_t* cw_bits, uint64_t* cw_sigma, uint64_t* cw_s,
+                        int32_t* cw_leaf, int64_t n, int bits, primia_stream_t st) {
+    PRIMIA_REQUIRE_WIDTH(bits);
+    if (n == 0) return PRIMIA_OK;
+    PRIMIA_REQUIRE(alpha && s0_pair && cw_bits && cw_sigma && cw_s && cw_leaf && n > 0);
+    dif_keygen_n_kernel<<<ceil_div(n, 256), 256, 0, (hipStream_t)st>>>((const u64*)alpha, (const u64*)s0_pair, cw_bits,
+                                                                        (u64*)cw_sigma, (u64*)cw_s, cw_leaf, n, bits);
+    return launch_status();
+}
+
+int primia_dif_eval_n(int b, const uint64_t* x, const uint64_t* s0, const uint8_t* cw_bits, const uint64_t* cw_sigma,
+                      const uint64_t* cw_s, const int32_t* cw_leaf, int64_t* out, int64_t n, int bits, primia_stream_t st) {
+    PRIMIA_REQUIRE_WIDTH(bits);
+    if (n == 0) return PRIMIA_OK;
+    PRIMIA_REQUIRE((b == 0 || b == 1) && x && s0 && cw_bits && cw_sigma && cw_s && cw_leaf && out && n > 0);
+    dif_eval_n_kernel<<<ceil_div(n, 256), 256, 0, (hipStream_t)st>>>(b, bits, (const u64*)x, (const u64*)s0, cw_bits,
+                                                                      (const u64*)cw_sigma, (const u64*)cw_s, cw_leaf, out, n);
+    return launch_status();
+}
+
+int primia_dif_eval_local_n(const int64_t* x1_0, const int64_t* x1_1, int w1, int start1, const int64_t* x2_0,
+                            const int64_t* x2_1, int w2, int start2, int len, const uint64_t* alpha0, const uint64_t* alpha1,
+                            const uint64_t* s0_0, const uint64_t* s0_1, const uint8_t* cw_bits, const uint64_t* cw_sigma,
+                            const uint64_t* cw_s, const int32_t* cw_leaf, int64_t* out0, int64_t* out1, int64_t n, int bits,
+                            primia_stream_t st) {
+    PRIMIA_REQUIRE_WIDTH(bits);
+    if (n == 0) return PRIMIA_OK;
+    PRIMIA_REQUIRE(x2_0 && x2_1 && ((x1_0 == nullptr) == (x1_1 == nullptr)) && alpha0 && alpha1 && s0_0 && s0_1 && cw_bits &&
+                   cw_sigma && cw_s && cw_leaf && out0 && out1 && n > 0 && len > 0 && n % len == 0);
+    PRIMIA_REQUIRE(w2 >= len && start2 >= 0 && start2 + len <= w2 && (!x1_0 || (w1 >= len && start1 >= 0 && start1 + len <= w1)));
+    const dim3 grid((unsigned)ceil_div(n, 256), 2);
+    dif_eval_local_n_kernel<<<grid, 256, 0, (hipStream_t)st>>>(
+        LeOperand{(const u64*)x1_0, (const u64*)x1_1, w1, start1}, LeOperand{(const u64*)x2_0, (const u64*)x2_1, w2, start2}, len,
+        bits, (const u64*)alpha0, (const u64*)alpha1, (const u64*)s0_0, (const u64*)s0_1, cw_bits, (const u64*)cw_sigma,
+        (const u64*)cw_s, cw_leaf, out0, out1, n);
     return launch_status();
 }
 

@@ -32,6 +32,33 @@ from ._lib import call
 
 I64 = torch.int64
 
+# The width of the FSS comparison: a comparison of d = x1 - x2 answers [(d + alpha) mod 2^n <= alpha], which is
+# [d <= 0] while |d| < 2^(n-1) and alpha + d does not wrap -- an error of probability |d| / 2^n over the dealer's draw.  32 is the
+# reference's width (mpc/fss.py:27) and the default; key bytes and the DIF kernels' time grow linearly with it.
+FSS_BITS = 32
+FSS_BITS_MAX = 64
+
+
+def check_fss_bits(bits):
+    bits = int(bits)
+    if not FSS_BITS <= bits <= FSS_BITS_MAX:
+        raise ValueError(f"fss_bits must be in [{FSS_BITS}, {FSS_BITS_MAX}], got {bits}")
+    return bits
+
+
+def fss_call(name, bits, *args):
+    """A DIF entry point of the library at width `bits`: the reference's 32-bit one (primia_<name>), or its width-general
+    form (primia_<name>_n, which takes the width last).  The one place where the width selects anything."""
+    if bits == FSS_BITS:
+        call("primia_" + name, *args)
+    else:
+        call("primia_" + name + "_n", *args, bits)
+
+
+def masked_dtype(bits):
+    """What holds an opened masked input: uint32 words at the reference's width, uint64 words above it."""
+    return torch.int32 if bits == FSS_BITS else I64
+
 
 def _empty_like(t):
     return torch.empty_like(t)
@@ -63,7 +90,8 @@ class Dealer:
     """The crypto provider: generates correlated randomness on the GPU.
 
     build_triple (mpc/beaver.py:7-63): a, b uniform int64, c = a∘b, each split into two shares.
-    build_fss_keys (mpc/primitives.py:237-253): DIF keys + alpha additively split mod 2^32.
+    build_fss_keys (mpc/primitives.py:237-253): DIF keys + alpha additively split mod 2^32 -- mod 2^fss_bits, with fss_bits
+    levels per key, for a dealer of another comparison width (the contexts it serves read the width from it).
 
     Randomness is a ChaCha20 keystream (`primia_chacha20_fill`) under a 256-bit key taken from the operating
     system's entropy pool (`os.urandom`) when the dealer is constructed — never shared, never derived from anything
@@ -71,11 +99,12 @@ class Dealer:
     public).  `seed` is for tests, benchmarks and oracle replay only: it derives the key from the seed
     (SHA-256), making the whole stream reproducible — and therefore worthless as a secret."""
 
-    def __init__(self, device, seed=None):
+    def __init__(self, device, seed=None, fss_bits=FSS_BITS):
         import hashlib
         import os
 
         self.device = torch.device(device)
+        self.fss_bits = check_fss_bits(fss_bits)
         self.seeded = seed is not None
         raw = os.urandom(40) if seed is None else hashlib.sha256(b"primia-dealer-debug-seed:%d" % int(seed)).digest() + bytes(8)
         self._key = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(4)]
@@ -135,20 +164,18 @@ class Dealer:
     def dif_keys(self, n):
         if self.requests is not None:
             self.requests.append(("dif_keys", (n,), {}))
-        dev = self.device
+        dev, w = self.device, self.fss_bits
         # raw keystream words, then build_fss_keys' arithmetic in place (primia_fss_alpha_split): alpha and its mask r below
         # 2^32 (mpc/fss.py:346, mpc/primitives.py:249), word 0 of each seed 63 bits (randbit, fss.py:495-501), and
-        # primitives.py:249-251: party 0 receives (alpha - mask) mod 2^32, party 1 the mask
+        # primitives.py:249-251: party 0 receives (alpha - mask) mod 2^32, party 1 the mask (2^fss_bits at another width: the
+        # same words are drawn, the width decides their reduction)
         alpha = self.rand64(n)
         s0 = self.rand64(2, 2, n)
         r = self.rand64(n)
         a0 = torch.empty(n, dtype=I64, device=dev)
-        call("primia_fss_alpha_split", alpha, s0, r, a0, n)
-        bits = torch.empty(32, n, dtype=torch.uint8, device=dev)
-        cw_sigma = torch.empty(32, 2, n, dtype=I64, device=dev)
-        cw_s = torch.empty(32, 2, n, dtype=I64, device=dev)
-        leaf = torch.empty(33, n, dtype=torch.int32, device=dev)
-        call("primia_dif_keygen", alpha, s0, bits, cw_sigma, cw_s, leaf, n)
+        fss_call("fss_alpha_split", w, alpha, s0, r, a0, n)
+        bits, cw_sigma, cw_s, leaf = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in dif_key_fields(n, w))
+        fss_call("dif_keygen", w, alpha, s0, bits, cw_sigma, cw_s, leaf, n)
         keys = [dict(alpha=[a0, r][b], s0=s0[b], bits=bits, cw_sigma=cw_sigma, cw_s=cw_s, cw_leaf=leaf) for b in range(2)]
         if self.log is not None:
             self.log.append(("dif", n, alpha.cpu().numpy(), s0.cpu().numpy(), r.cpu().numpy()))
@@ -169,12 +196,20 @@ class Dealer:
         return r
 
 
+def dif_key_fields(n, bits=FSS_BITS):
+    """(shape, dtype) of the correction words of n comparisons at width `bits`, common to both parties: the packed control
+    bits, cw_sigma, cw_s and the leaf words (include/primia_hip.h)."""
+    return [((bits, n), torch.uint8), ((bits, 2, n), I64), ((bits, 2, n), I64), ((bits + 1, n), torch.int32)]
+
+
 class PreloadedDealer:
     """Online phase only: hands out primitives that a Dealer generated earlier (its `tape`), in
-    the same order — the reference's pre-provisioned crypto store (mpc/primitives.py:161-235)."""
+    the same order — the reference's pre-provisioned crypto store (mpc/primitives.py:161-235).  `fss_bits`: the width of
+    the dealer that generated them."""
 
-    def __init__(self, tape, device):
+    def __init__(self, tape, device, fss_bits=FSS_BITS):
         self.tape, self.pos, self.device = tape, 0, torch.device(device)
+        self.fss_bits = check_fss_bits(fss_bits)
         self.log = None
 
     def _next(self):
@@ -241,6 +276,11 @@ class SecureContext:
     # The dealer's primitives are requested in exactly the order of the step-by-step chain, results are bit-identical;
     # `local_fused = False` selects the chain (what a three-role run executes, where the opens are messages).
     local_fused = True
+
+    @property
+    def fss_bits(self):
+        """The width of the comparisons, which is the width of the dealer's keys (32 for a dealer that names none)."""
+        return getattr(self.dealer, "fss_bits", FSS_BITS)
 
     @property
     def _in_process(self):
@@ -434,9 +474,9 @@ class SecureContext:
         keys = self.dealer.dif_keys(n)
         out = _pair(shape, x2[0].device)
         k0, k1 = keys
-        call("primia_dif_eval_local", None if x1 is None else x1[0], None if x1 is None else x1[1], cols1[0], cols1[1],
-             x2[0], x2[1], cols2[0], cols2[1], length, k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"],
-             k0["cw_sigma"], k0["cw_s"], k0["cw_leaf"], out[0], out[1], n)
+        fss_call("dif_eval_local", self.fss_bits, None if x1 is None else x1[0], None if x1 is None else x1[1], cols1[0], cols1[1],
+                 x2[0], x2[1], cols2[0], cols2[1], length, k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"],
+                 k0["cw_sigma"], k0["cw_s"], k0["cw_leaf"], out[0], out[1], n)
         self.stats["dif_evals"] += n
         return out
 
@@ -451,17 +491,18 @@ class SecureContext:
         for j in self.parties:  # mask_builder
             r[j] = _empty_like(xr)
             call("primia_fss_mask", x1[j], x2[j], keys[j]["alpha"], r[j], n)
-        masked = torch.empty(n, dtype=torch.int32, device=xr.device)
+        w = self.fss_bits
+        masked = torch.empty(n, dtype=masked_dtype(w), device=xr.device)
         if self.party is None:
-            call("primia_fss_open", r[0], r[1], masked, n)
-        else:  # the parties exchange their masked shares; the sum is taken mod 2^32 (fss.py:158-170)
+            fss_call("fss_open", w, r[0], r[1], masked, n)
+        else:  # the parties exchange their masked shares; the sum is taken mod 2^32 (fss.py:158-170; mod 2^fss_bits)
             opened = self.opener.open(r)
-            call("primia_fss_open", opened, self._const(0, opened.device, opened.numel()), masked, n)
+            fss_call("fss_open", w, opened, self._const(0, opened.device, opened.numel()), masked, n)
 
         def one(j):  # evaluate
             o = _empty_like(xr)
             k = keys[j]
-            call("primia_dif_eval", j, masked, k["s0"], k["bits"], k["cw_sigma"], k["cw_s"], k["cw_leaf"], o, n)
+            fss_call("dif_eval", w, j, masked, k["s0"], k["bits"], k["cw_sigma"], k["cw_s"], k["cw_leaf"], o, n)
             return o
 
         self.stats["dif_evals"] += n
@@ -509,10 +550,11 @@ class SecureContext:
           K   = share(full([B], k))                  const_mask(B): a public constant, re-shared like every other
           R   = beaver_mul(bit2, [x[:, k] - V, K - I])       triple ("mul", (B, 2), (B, 2)); the bit is unscaled: no truncation
           V  += R[:, 0];  I += R[:, 1]
-        Walking down with [x_k >= V] sends a tie to the lower index, torch.argmax's rule.  The comparison sees the low 32 bits
-        of the masked difference: the result is the true argmax while all pairwise differences of the encoded logits stay
-        below 2^31, and a deterministic function of the wrapped values otherwise.  (Like every comparison of the reference,
-        one on a difference d errs with probability |d| / 2^32 over the dealer's mask: 2e-7 for two pf = 3 logits 1.0 apart.)
+        Walking down with [x_k >= V] sends a tie to the lower index, torch.argmax's rule.  The comparison sees the low
+        `fss_bits` bits of the masked difference (32 unless the dealer says otherwise): the result is the true argmax while all
+        pairwise differences of the encoded logits stay below 2^(fss_bits-1), and a deterministic function of the wrapped values
+        otherwise.  (Like every comparison of the reference, one on a difference d errs with probability |d| / 2^fss_bits over
+        the dealer's mask: 2e-7 at 32 bits for two pf = 3 logits 1.0 apart.)
         Both parties here: two launches per class (primia_dif_eval_local, primia_argmax_combine_local); otherwise the
         step-by-step chain, which a three-role run executes -- same dealer requests, same bits.
         values=True: (I, V), with the shares of the maximum as well (tests; a deployment opens I alone)."""
@@ -1196,39 +1238,50 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
 
 
 # bytes of one comparison's DIF key as Dealer.dif_keys lays it out: raw alpha, its mask and party 0's share (3 x 8), both
-# parties' seeds (2 x 2 x 8), the packed control bits (32), cw_sigma and cw_s (32 x 2 x 8 each), the leaf words (33 x 4)
-DIF_KEY_BYTES = 3 * 8 + 32 + 32 + 2 * 32 * 2 * 8 + 33 * 4
+# parties' seeds (2 x 2 x 8), the packed control bits (32), cw_sigma and cw_s (32 x 2 x 8 each), the leaf words (33 x 4) --
+# at a width of n bits: n control bytes, n x 2 x 8 twice, n + 1 leaf words: 60 + 37 n
+class _DifKeyBytes(int):
+    """The bytes at the reference's width, as the number it has always been; called with a width, the bytes at that width."""
+
+    def __call__(self, bits=FSS_BITS):
+        bits = check_fss_bits(bits)
+        return 3 * 8 + 32 + bits + 2 * bits * 2 * 8 + (bits + 1) * 4
 
 
-def primitive_bytes(requests):
-    """Device bytes of the primitives a request list stands for (both parties' halves)."""
+DIF_KEY_BYTES = _DifKeyBytes(3 * 8 + 32 + 32 + 2 * 32 * 2 * 8 + 33 * 4)
+
+
+def primitive_bytes(requests, fss_bits=FSS_BITS):
+    """Device bytes of the primitives a request list stands for (both parties' halves), its comparison keys at `fss_bits`."""
+    key_bytes = DIF_KEY_BYTES(fss_bits)
     numel = lambda shape: int(torch.Size(shape).numel())
     total = 0
     for kind, args, _ in requests:
         if kind == "const_mask":
             total += 8 * numel(args)
         elif kind == "dif_keys":
-            total += DIF_KEY_BYTES * args[0]
+            total += key_bytes * args[0]
         else:
             op, xs, ys = args
             total += 16 * (numel(xs) + numel(ys) + numel(_triple_c_shape(op, xs, ys)))
     return total
 
 
-def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits"):
+def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS):
     """What GraphedSecureInference(batch=...) holds in static buffers: every primitive of one pass (dominated by the DIF
     keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image, 2,308,096 with pooling="avg") plus one eighth on top for the arena copy of
     their random words while both exist (5/6 of a triple, 48 of a key's 1,244 bytes) and the captured graph's activations
-    (im2col and pool-unroll operands: under 2 % of the keys at every layer)."""
-    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal))
+    (im2col and pool-unroll operands: under 2 % of the keys at every layer).  A key of `fss_bits` levels takes 60 + 37 fss_bits
+    bytes: 2,428 at 64."""
+    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal), fss_bits)
     return b + b // 8
 
 
-def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max", reveal="logits"):
+def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS):
     """The largest batch whose static buffers fit in `budget` bytes (0: not even one image).  serving_bytes is affine in the
     batch (a per-batch part, Newton and the weight masks, plus a per-image part) up to its rounding, so two evaluations
     give the answer and the neighbours settle the rounding."""
-    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal)
+    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal, fss_bits)
     one, two = need(1), need(2)
     per_image, fixed = two - one, 2 * one - two
     k = max(0, (int(budget) - fixed) // per_image)
@@ -1262,30 +1315,33 @@ class GraphedSecureInference:
     largest batch that would.
 
     reveal="class": the argmax tail is part of the captured graph and the static output is the int64 [batch] buffer of class
-    indices; nothing else is reconstructed."""
+    indices; nothing else is reconstructed.
+
+    fss_bits: the width of the comparisons (the dealer's; see FSS_BITS) -- wider keys count in the refusal above."""
 
     refill_graph = True
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
-                 memory_budget=None, pooling="max", reveal="logits"):
+                 memory_budget=None, pooling="max", reveal="logits", fss_bits=FSS_BITS):
         self.device = torch.device(device)
         self.batch = int(batch)
+        self.fss_bits = check_fss_bits(fss_bits)
         self.pooling = _check_pooling(pooling)
         self.reveal = _check_reveal(reveal)
         if self.batch < 1:
             raise ValueError("batch must be at least 1")
         arch = architecture_of(state_dict)
-        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal)
+        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal, self.fss_bits)
         if memory_budget is None:
             free, _ = torch.cuda.mem_get_info(self.device)
             memory_budget = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if self.static_bytes > memory_budget:
-            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal)
+            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal, self.fss_bits)
             raise ValueError(f"a batch of {self.batch} images at {input_size}x{input_size} needs {self.static_bytes} bytes of static "
                              f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
         self.image = torch.zeros(self.batch, state_dict["conv1.weight"].shape[1], input_size, input_size, dtype=torch.float32).to(self.device)
-        self.dealer = Dealer(self.device, seed)
+        self.dealer = Dealer(self.device, seed, self.fss_bits)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
         model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)
@@ -1295,7 +1351,7 @@ class GraphedSecureInference:
         self.dealer.tape = self.dealer.requests = None
         self.stats = dict(ctx.stats)
         self._rehome_tape()                            # per-image random words -> one arena (before any pointer is captured)
-        pre = PreloadedDealer(self.tape, self.device)
+        pre = PreloadedDealer(self.tape, self.device, self.fss_bits)
         self._ctx = SecureContext(pre, base, precision_fractional)
         self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)   # re-shares with the same masks
         self._model(self.image)                        # eager pass over the static buffers: builds the pointer tables
@@ -1393,8 +1449,8 @@ class GraphedSecureInference:
                 d.triple_c1(kind, xshape, yshape, a0, a1, b0, b1, c0, c1, scratch=self._mm_scratch)
             else:
                 _, m, alpha, s0, r, a0, bits, cw_sigma, cw_s, leaf = op
-                call("primia_fss_alpha_split", alpha, s0, r, a0, m)
-                call("primia_dif_keygen", alpha, s0, bits, cw_sigma, cw_s, leaf, m)
+                fss_call("fss_alpha_split", d.fss_bits, alpha, s0, r, a0, m)
+                fss_call("dif_keygen", d.fss_bits, alpha, s0, bits, cw_sigma, cw_s, leaf, m)
         call("primia_u64_add", self._ctr, (n + 7) // 8)
 
     def refill(self):
@@ -1447,11 +1503,11 @@ class PipelinedSecureInference:
     In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU."""
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
-                 batch=1, pooling="max", reveal="logits"):
+                 batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS):
         self.device = torch.device(device)
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
                                              None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling,
-                                             reveal=reveal)
+                                             reveal=reveal, fss_bits=fss_bits)
                       for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
@@ -1545,8 +1601,9 @@ class PartyDealer:
     (mpc/primitives.py:161-235 keeps the same per-worker store; here nothing is requested — the provider
     follows the public request schedule of the network, see model_requests and image_requests)."""
 
-    def __init__(self, link: PartyLink):
+    def __init__(self, link: PartyLink, fss_bits=FSS_BITS):
         self.link, self.device, self.j = link, link.device, link.role
+        self.fss_bits = check_fss_bits(fss_bits)      # the provider's width: public, like the request schedule
         self.log = None
 
     def _mine(self, v):
@@ -1561,10 +1618,8 @@ class PartyDealer:
     def dif_keys(self, n):
         f = self.link.from_dealer
         k = dict(alpha=f((n,)), s0=f((2, n)))
-        k["bits"] = f((32, n), torch.uint8, private=False)
-        k["cw_sigma"] = f((32, 2, n), I64, private=False)
-        k["cw_s"] = f((32, 2, n), I64, private=False)
-        k["cw_leaf"] = f((33, n), torch.int32, private=False)
+        for name, (shape, dt) in zip(("bits", "cw_sigma", "cw_s", "cw_leaf"), dif_key_fields(n, self.fss_bits)):
+            k[name] = f(shape, dt, private=False)
         return self._mine(k)
 
     def const_mask(self, *shape, owner=None):
@@ -1601,14 +1656,14 @@ class DealerService:
                 send(v, kw.get("owner"))
 
 
-def party_context(link: PartyLink, precision_fractional=16, base=10):
+def party_context(link: PartyLink, precision_fractional=16, base=10, fss_bits=FSS_BITS):
     """SecureContext of the party this rank plays."""
-    return SecureContext(PartyDealer(link), base, precision_fractional,
+    return SecureContext(PartyDealer(link, fss_bits), base, precision_fractional,
                          opener=DistOpener(link.parties_group, link.role), party=link.role, link=link)
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits"):
+                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
     all know the architecture, the input size, the stem pool (`pooling`), how many images will be classified and how many go
@@ -1617,18 +1672,20 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     orchestrator), the dealer None.
     reveal="class": every pass ends with the argmax tail and party 0 sends its share of the class indices to party 1, which
     returns one int64 [<= batch] tensor per pass; party 0 learns nothing and returns None, like the dealer, which follows
-    the extended schedule."""
+    the extended schedule.
+    fss_bits: the width of the comparisons, known to all three like the schedule."""
     _check_pooling(pooling)
     _check_reveal(reveal)
+    fss_bits = check_fss_bits(fss_bits)
     passes = (n_images + batch - 1) // batch
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
         image_req = image_requests(arch, input_size, batch, blocks, pooling, reveal)
-        svc = DealerService(Dealer(link.device, seed), link)
+        svc = DealerService(Dealer(link.device, seed, fss_bits), link)
         svc.serve(model_requests(arch))
         for _ in range(passes):
             svc.serve(image_req)
         return None
-    ctx = party_context(link, precision_fractional, base)
+    ctx = party_context(link, precision_fractional, base, fss_bits)
     if link.role == 0:
         if state_dict is None:
             raise ValueError("party 0 is the model owner: it needs the state dict")

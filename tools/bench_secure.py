@@ -6,7 +6,9 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
     --norm group:  a GroupNorm state dict (the network of differentially private training): every norm site computes its
                    statistics online -- a Beaver square and an 80-step Newton iteration on batch * 32 values per layer
     --reveal class: every pass ends with the secret-shared argmax and opens the class only (classes - 1 rounds of one comparison
-                   launch and one select launch on `batch` elements; the report names it)"""
+                   launch and one select launch on `batch` elements; the report names it)
+    --fss_bits N:  the width of the comparisons, 32 (default, the reference's) to 64: N levels per key and per evaluation (the
+                   report names it when it is not 32)"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -27,6 +29,9 @@ def main():
                     help="group: a synthetic GroupNorm(32, C) state dict, no running statistics (the report names it)")
     ap.add_argument("--reveal", choices=("logits", "class"), default="logits",
                     help="class: the passes end with SecureContext.argmax and open the predicted class only (the report names it)")
+    ap.add_argument("--fss_bits", type=int, default=32,
+                    help="the width of the DIF comparisons (32..64): key bytes and DIF kernel time grow linearly with it (the report "
+                         "names it when it is not 32)")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
     ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph replay of the online phase")
     ap.add_argument("--only-fss-roofline", action="store_true",
@@ -84,6 +89,7 @@ def main():
     pool_kw = {} if a.pooling == "max" else {"pooling": a.pooling}
     norm_kw = {} if a.norm == "batch" else {"norm": a.norm}
     reveal_kw = {} if a.reveal == "logits" else {"reveal": a.reveal}
+    bits_kw = {} if a.fss_bits == 32 else {"fss_bits": a.fss_bits}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
@@ -163,7 +169,7 @@ def main():
         B, reps = a.batch, max(a.images, 3)
         imgs = torch.randn(B, 3, a.size, a.size, generator=g).to(dev)
         free = torch.cuda.mem_get_info(dev)[0]
-        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw, **reveal_kw)
+        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw, **reveal_kw, **bits_kw)
         gi(imgs, refill=False); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(reps):
@@ -176,12 +182,12 @@ def main():
             gi(imgs)                    # the dealer's refill graph, then the online graph, on one stream
         torch.cuda.synchronize()
         both = (time.perf_counter() - t0) / reps * 1e3
-        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, **reveal_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
+        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, **reveal_kw, **bits_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
                           "online_ms_per_image": round(online / B, 2), "with_refill_ms_per_image": round(both / B, 2),
                           "online_ms_per_pass": round(online, 2), "with_refill_ms_per_pass": round(both, 2),
                           "static_primitive_bytes": gi.static_bytes, "arena_mb": round(gi._arena.numel() * 8 / 1e6, 1),
                           "device_free_bytes_before": free,
-                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw, **reveal_kw),
+                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw, **reveal_kw, **bits_kw),
                           "dif_evals": gi.stats["dif_evals"], "beaver_matmul": gi.stats["beaver_matmul"],
                           "beaver_mul": gi.stats["beaver_mul"]}))
         return
@@ -194,12 +200,12 @@ def main():
         return
 
     # warm-up (JIT-free, but first launches / allocator)
-    run(Dealer(dev, seed=0))
+    run(Dealer(dev, seed=0, **bits_kw))
     res = []
     for i in range(a.images):
-        d = Dealer(dev, seed=100 + i); d.tape = []
+        d = Dealer(dev, seed=100 + i, **bits_kw); d.tape = []
         t_total, out_a, ctx = run(d)
-        t_online, out_b, _ = run(PreloadedDealer(d.tape, dev))
+        t_online, out_b, _ = run(PreloadedDealer(d.tape, dev, **bits_kw))
         assert torch.equal(out_a.cpu(), out_b.cpu()), "replayed run must be bit-identical"
         res.append((t_total, t_online))
         del d
@@ -213,8 +219,8 @@ def main():
         try:
             from primia_amd.secure import GraphedSecureInference
 
-            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, **pool_kw, **reveal_kw)
-            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev), 10, a.pf)
+            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, **pool_kw, **reveal_kw, **bits_kw)
+            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, **bits_kw), 10, a.pf)
             out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, **pool_kw, **reveal_kw)(img)
             assert torch.equal(gi(img, refill=False).cpu(), out_ref.cpu()), "graph replay must be bit-identical"
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -236,7 +242,7 @@ def main():
             # on its own stream while the other replays): wall time per image, every image on fresh primitives
             from primia_amd.secure import PipelinedSecureInference
 
-            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, **pool_kw, **reveal_kw)
+            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, **pool_kw, **reveal_kw, **bits_kw)
             for _ in range(2):
                 pi(img)
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -264,7 +270,7 @@ def main():
 
     extra = {"cpu_baseline": cpu_sample_report(cpu_t, ctx.stats["dif_evals"])} if cpu_t else {}
     extra["roofline"] = fss_roofline()
-    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, **norm_kw, **reveal_kw, "online_ms": round(to * 1e3, 1),
+    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, **norm_kw, **reveal_kw, **bits_kw, "online_ms": round(to * 1e3, 1),
                       "online_graph_ms": None if graph_ms is None else round(graph_ms, 1),
                       "dealer_refill_ms": None if refill_ms is None else round(refill_ms, 1),
                       "dealer_refill_launches": refill_nodes, "dealer_keystream_mb_per_image": None if arena_mb is None else round(arena_mb, 1),
