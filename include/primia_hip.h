@@ -1004,6 +1004,15 @@ int primia_newton_reciprocal_local(const int64_t* v0, const int64_t* v1, const i
  *                                ("mul", (B, 2), (B, 2)), both opens inside, no truncation), V += R[:, 0], I += R[:, 1].
  *                                k0 / k1: shares of the re-shared constant k [B]; v / i: the running maximum and its index
  *                                [B], updated IN PLACE (four distinct buffers, none of them an input)
+ *   primia_dpf_eval_local        fss.eq(x1, x2) (mpc/fss.py:97-185 with op = "eq"): mask_builder, the mod-2^32 open and both
+ *                                parties' DPF evaluations (the walk of primia_dpf_eval) on the operands of
+ *                                primia_dif_eval_local, both required: out_j = party j's share of [x1 == x2 mod 2^32], unscaled
+ *   primia_confusion_combine_local  the confusion-matrix step of an encrypted evaluation: M += Y^T @ P, the
+ *                                Beaver matmul of Y^T [C, B] and P [B, C] on the triple ("matmul", (C, B), (B, C)) with both
+ *                                opens inside and no truncation.  y: shares of the one-hot labels [B][C], read row-major
+ *                                (no transposed copy); p: shares of the one-hot predicted class [B][C]; a [C][B], b [B][C],
+ *                                c [C][C]; m: the accumulator [C][C], updated IN PLACE (two distinct buffers, neither an
+ *                                input).  Wrapping int64 as primia_beaver_combine_matmul; C <= 16, any B >= 1
  *   primia_bn_eval_local         batch_norm in eval mode (nn/functional.py:44-75) of one image: NCHW in, NCHW out, both
  *                                FPT products and the row / column re-layouts inside; t1 / t2: HOST arrays of the two
  *                                triples' six pointers (t1: a ~ inv [C], b, c ~ rows [HW, C]; t2: a, c ~ rows, b ~ weight)
@@ -1034,6 +1043,13 @@ int primia_argmax_combine_local(const int64_t* bit0, const int64_t* bit1, const 
                                 int start, const int64_t* k0, const int64_t* k1, const int64_t* a0, const int64_t* b0,
                                 const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1, int64_t* v0,
                                 int64_t* v1, int64_t* i0, int64_t* i1, int64_t B, primia_stream_t stream);
+int primia_dpf_eval_local(const int64_t* x1_0, const int64_t* x1_1, int w1, int start1, const int64_t* x2_0,
+                          const int64_t* x2_1, int w2, int start2, int len, const uint64_t* alpha0, const uint64_t* alpha1,
+                          const uint64_t* s0_0, const uint64_t* s0_1, const uint8_t* cw_bits, const uint64_t* cw_s,
+                          const int64_t* cw_n, int64_t* out0, int64_t* out1, int64_t n, primia_stream_t stream);
+int primia_confusion_combine_local(const int64_t* y0, const int64_t* y1, const int64_t* p0, const int64_t* p1, const int64_t* a0,
+                                   const int64_t* b0, const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1,
+                                   int64_t* m0, int64_t* m1, int64_t B, int C, primia_stream_t stream);
 int primia_bn_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
                          const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
                          const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,

@@ -13,6 +13,11 @@ differentially_private = yes: GroupNorm(32, C) at every norm site) is served as 
 The encrypted GroupNorm takes its inverse square root from the reference's Newton iteration, which is accurate to under 1 %
 for group variances in about [0.05, 16] (1.6 % off at 0.01, 15 % at 0.001).  `--reveal class` ends every encrypted pass with
 a secret-shared argmax and opens the predicted class alone: the logits, the model owner's asset, are never reconstructed.  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
+
+`--evaluate` scores the model on a labelled set instead (`--data_dir` a class-folder tree <dir>/<class>/<image>, or `synthetic`
+for seeded images and labels), plain or encrypted, and prints the reference's validation table and one JSON line
+{"Evaluation": {"n": ..., "confusion_matrix": [[...]], "mcc": ...}}.  With `--reveal confusion` an encrypted evaluation opens
+the confusion matrix and nothing else: no logit, no predicted class and no label leaves its owner.
 """
 import argparse
 import json
@@ -27,23 +32,81 @@ from primia_amd.secure import Dealer, SecureContext, SecureResNet18, norm_of
 from primia_amd.torchlib_compat import Arguments  # noqa: F401  (checkpoints pickle an Arguments instance)
 
 
-def load_images(data_dir, n, size, channels, device, mean, std, seed=0, clahe=False):
+def synthetic_labels(n, classes, seed=1):
+    """The seeded labels that go with the seeded noise images of `--evaluate --data_dir synthetic`: int64 [n]."""
+    return torch.randint(0, classes, (n,), generator=torch.Generator().manual_seed(seed))
+
+
+def labelled_files(data_dir, n, classes):
+    """The class-folder tree <dir>/<class>/<image> of an evaluation, listed like the validation folder (imagefolder.scan):
+    (files, int64 labels, class names).  `n` = None takes every image, else n of them evenly spaced over the listing, so
+    that every class keeps its share."""
+    from primia_amd import imagefolder
+
+    if not os.path.isdir(data_dir):
+        raise SystemExit("data_dir {!r} does not exist (pass 'synthetic' for seeded images and labels)".format(data_dir))
+    names, samples = imagefolder.scan(data_dir)
+    if not samples:
+        raise SystemExit("no images under {!r}: --evaluate reads <dir>/<class>/<image>".format(data_dir))
+    if len(names) > classes:
+        raise SystemExit("{!r} holds {} class folders, the checkpoint has {} classes".format(data_dir, len(names), classes))
+    if n is not None and n < len(samples):
+        samples = [samples[i * len(samples) // n] for i in range(n)]
+    return [f for f, _ in samples], torch.tensor([c for _, c in samples], dtype=torch.int64), names
+
+
+def confusion_of(labels, predictions, classes):
+    """int64 [classes, classes] counts of (label, prediction) pairs."""
+    m = torch.zeros(classes, classes, dtype=torch.int64)
+    for t, p in zip(labels.tolist(), predictions):
+        m[int(t), int(p)] += 1
+    return m
+
+
+def roc_auc_of(labels, logits):
+    """torchlib/utils.py:1418-1431: one-vs-one ROC AUC on the min-shifted, row-normalised logits; 0 where it is undefined."""
+    from sklearn import metrics as mt
+
+    scores = logits.double().numpy().copy()
+    scores -= scores.min(axis=1)[:, None]
+    scores = scores / scores.sum(axis=1)[:, None]
+    auc = float("nan")
+    try:
+        import warnings
+
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            if scores.shape[1] == 2:
+                auc = float(mt.roc_auc_score(labels.numpy(), scores[:, 1]))
+            else:
+                auc = float(mt.roc_auc_score(labels.numpy(), scores, multi_class="ovo", labels=list(range(scores.shape[1]))))
+    except ValueError:
+        pass
+    if auc != auc:      # undefined (one class among the labels, a row of equal logits): scikit-learn raises or answers nan
+        print("ROC AUC score could not be calculated and was set to zero.", file=sys.stderr)
+        return 0.0
+    return auc
+
+
+def load_images(data_dir, n, size, channels, device, mean, std, seed=0, clahe=False, files=None):
     """The reference's inference transform (inference.py:176-196: a.Resize(R, R) -> a.CenterCrop(R, R) -> a.ToFloat ->
     a.Normalize with the checkpoint's mean / std) for the first `n` images of `data_dir`, on the GPU through
     primia_image_prepare; RGB or single channel as the checkpoint's stem says (CombinedLoader.change_channels).
-    `synthetic` (or no folder given) -> seeded noise; a folder that does not exist is an error."""
-    if data_dir in (None, "synthetic"):
+    `synthetic` (or no folder given) -> seeded noise; a folder that does not exist is an error.  `files`: these files
+    instead of the folder's listing."""
+    if files is None and data_dir in (None, "synthetic"):
         g = torch.Generator().manual_seed(seed)
         return torch.randn(n, channels, size, size, generator=g).to(device)
-    if not os.path.isdir(data_dir):
+    if files is None and not os.path.isdir(data_dir):
         raise SystemExit("data_dir {!r} does not exist (pass 'synthetic' for seeded noise)".format(data_dir))
     import numpy as np
 
     from primia_amd import imagefolder
     from primia_amd._lib import call
 
-    files = sorted(os.path.join(dp, f) for dp, _, fs in os.walk(data_dir) for f in fs
-                   if f.lower().endswith(imagefolder.EXTENSIONS) and not f.startswith("._"))[:n]
+    if files is None:
+        files = sorted(os.path.join(dp, f) for dp, _, fs in os.walk(data_dir) for f in fs
+                       if f.lower().endswith(imagefolder.EXTENSIONS) and not f.startswith("._"))[:n]
     if not files:
         raise SystemExit("no images under {!r}".format(data_dir))
     out = torch.empty(len(files), channels, size, size, dtype=torch.float32, device=device)
@@ -80,7 +143,12 @@ if __name__ == "__main__":
     parser.add_argument("--websockets_config", default=None, help="accepted for compatibility (in-process parties)")
     parser.add_argument("--cuda", action="store_true", help="Use GPU acceleration (always on here).")
     parser.add_argument("--http_protocol", action="store_true", help="accepted for compatibility")
-    parser.add_argument("--num_images", type=int, default=4)
+    parser.add_argument("--num_images", type=int, default=None,
+                        help="how many images (default 4; with --evaluate on a folder: all of them)")
+    parser.add_argument("--evaluate", action="store_true",
+                        help="score the model on a labelled set: --data_dir is a class-folder tree <dir>/<class>/<image> "
+                             "(or `synthetic`: seeded images and labels); prints the validation table and one JSON line "
+                             '{"Evaluation": {"n", "confusion_matrix", "mcc"}}.  Plain or encrypted, with every --reveal')
     parser.add_argument("--batch_size", type=int, default=1,
                         help="encrypted inference: images per protocol pass (default 1, the reference's loop); the last "
                              "pass of --hip_graph / --three_role is padded with all-zero images whose rows are dropped")
@@ -102,11 +170,13 @@ if __name__ == "__main__":
                         help="encrypted inference with model_owner, data_owner and crypto_provider as three ranks "
                              "(launch with `python -m torch.distributed.run --nproc-per-node 3 inference.py ...`): "
                              "one GPU each over RCCL when three are visible, else all on GPU 0 over gloo")
-    parser.add_argument("--reveal", choices=("logits", "class"), default="logits",
+    parser.add_argument("--reveal", choices=("logits", "class", "confusion"), default="logits",
                         help="encrypted inference: what a pass opens.  logits (default, the reference): the full score "
                              "vector, whose argmax is taken in the clear; class: the predicted class alone, through a "
                              "secret-shared argmax of classes - 1 comparison rounds (the logits are never reconstructed, so "
-                             "PRIMIA_DUMP_LOGITS is refused)")
+                             "PRIMIA_DUMP_LOGITS is refused); confusion (with --evaluate only): nothing per image -- every "
+                             "pass adds into a secret-shared confusion matrix through classes equality tests per image, and "
+                             "the matrix alone is opened after the last pass (ROC AUC needs logits and is not reported)")
     parser.add_argument("--debug_dealer_seed", type=int, default=None,
                         help="DEBUG ONLY: derive the crypto provider's key from this number (reproducible, hence "
                              "NOT private); by default the key comes from the OS entropy pool and never leaves the "
@@ -119,8 +189,15 @@ if __name__ == "__main__":
     fss_bits = cmd_args.fss_bits
     if not 32 <= fss_bits <= 64:
         raise SystemExit(f"--fss_bits must be in [32, 64], got {fss_bits}")
-    if reveal == "class" and os.environ.get("PRIMIA_DUMP_LOGITS"):
-        raise SystemExit("--reveal class: the logits are never opened, there is nothing for PRIMIA_DUMP_LOGITS to write")
+    evaluate = cmd_args.evaluate
+    if reveal == "confusion" and not evaluate:
+        raise SystemExit("--reveal confusion opens the confusion matrix of a labelled set and nothing per image: an inference "
+                         "has no labels to count against and would print nothing -- pass --evaluate (and a class-folder "
+                         "--data_dir or `synthetic`)")
+    if reveal == "confusion" and not cmd_args.encrypted_inference:
+        raise SystemExit("--reveal says what an ENCRYPTED run opens: --reveal confusion needs --encrypted_inference")
+    if reveal != "logits" and os.environ.get("PRIMIA_DUMP_LOGITS"):
+        raise SystemExit(f"--reveal {reveal}: the logits are never opened, there is nothing for PRIMIA_DUMP_LOGITS to write")
     if not torch.cuda.is_available():
         raise SystemExit("primia_amd runs inference on the GPU only (HIP kernels); no GPU visible")
     device = torch.device("cuda:0")
@@ -134,8 +211,19 @@ if __name__ == "__main__":
     channels = int(sd["conv1.weight"].shape[1])       # 3 for pretrained = yes, else 1 (train.py:262)
     # inference.py:163-174: the checkpoint's statistics, else 0.5 / 0.2
     mean, std = state.get("val_mean_std", (torch.full((channels,), 0.5), torch.full((channels,), 0.2)))
-    images = load_images(cmd_args.data_dir, cmd_args.num_images, size, channels, device, mean, std,
-                         clahe=bool(getattr(args, "clahe", False)))
+    classes = int(sd["fc.weight"].shape[0])
+    labels = class_names = None
+    if evaluate and cmd_args.data_dir not in (None, "synthetic"):
+        files, labels, class_names = labelled_files(cmd_args.data_dir, cmd_args.num_images, classes)
+        images = load_images(cmd_args.data_dir, len(files), size, channels, device, mean, std,
+                             clahe=bool(getattr(args, "clahe", False)), files=files)
+    else:
+        images = load_images(cmd_args.data_dir, 4 if cmd_args.num_images is None else cmd_args.num_images, size, channels,
+                             device, mean, std, clahe=bool(getattr(args, "clahe", False)))
+        if evaluate:
+            labels = synthetic_labels(images.shape[0], classes)
+    matrix = None      # --reveal confusion: the opened confusion matrix, all such a run learns
+    logits = []        # the logits a run opened, pass by pass (none with --reveal class / confusion)
     total_pred = []
     bs = cmd_args.batch_size
     if bs < 1:
@@ -156,38 +244,47 @@ if __name__ == "__main__":
             link = PartyLink(device)
             # one checkpoint file serves all three ranks of a single-node launch; each role is handed only what
             # it owns: the weights (party 0), the images (party 1), the architecture (everyone)
-            logits = run_three_role(link, architecture_of(sd), size, images.shape[0],
+            result = run_three_role(link, architecture_of(sd), size, images.shape[0],
                                     state_dict=sd if link.role == 0 else None,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
                                     precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal,
-                                    fss_bits=fss_bits)
+                                    fss_bits=fss_bits, labels=labels if link.role == 1 and reveal == "confusion" else None)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
                 sys.exit(0)
-            # (reveal = class: party 1 holds the class indices themselves)
-            total_pred = [int(c) for o in logits for c in (o if reveal == "class" else o.argmax(dim=1)).tolist()]
-            if os.environ.get("PRIMIA_DUMP_LOGITS"):
-                torch.save(torch.cat(logits).cpu(), os.environ["PRIMIA_DUMP_LOGITS"])
-        elif cmd_args.hip_graph:
-            from primia_amd.secure import GraphedSecureInference
-
-            model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
-                                           seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal,
-                                           fss_bits=fss_bits)
+            if reveal == "confusion":      # both parties hold the matrix; the data owner's rank reports it
+                matrix = result.cpu()
+            elif reveal == "class":        # party 1 holds the class indices themselves
+                total_pred = [int(c) for o in result for c in o.tolist()]
+            else:
+                logits = result
+                total_pred = [int(c) for o in logits for c in o.argmax(dim=1).tolist()]
         else:
-            ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
-                                precision_fractional=cmd_args.precision_fractional)
-            model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling, reveal=reveal)
-        logits = []
-        for i in range(0, 0 if cmd_args.three_role else images.shape[0], bs):
-            out = model(images[i:i + bs]).clone()     # (the graphed form returns its static output buffer: keep a copy)
-            if reveal == "class":      # int64 class indices: all the pass opened
-                total_pred += [int(c) for c in out.tolist()]
-                continue
-            logits.append(out)
-            total_pred += [int(c) for c in out.argmax(dim=1).tolist()]
+            if cmd_args.hip_graph:
+                from primia_amd.secure import GraphedSecureInference
+
+                model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
+                                               seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal,
+                                               fss_bits=fss_bits)
+            else:
+                ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
+                                    precision_fractional=cmd_args.precision_fractional)
+                model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling, reveal=reveal)
+            if reveal == "confusion":      # an evaluation: the passes return nothing, the matrix is opened after the last
+                model.begin()
+                for i in range(0, images.shape[0], bs):
+                    model(images[i:i + bs], labels=labels[i:i + bs])
+                matrix = model.finish().cpu()
+            else:
+                for i in range(0, images.shape[0], bs):
+                    out = model(images[i:i + bs]).clone()     # (the graphed form returns its static output buffer: keep a copy)
+                    if reveal == "class":      # int64 class indices: all the pass opened
+                        total_pred += [int(c) for c in out.tolist()]
+                    else:
+                        logits.append(out)
+                        total_pred += [int(c) for c in out.argmax(dim=1).tolist()]
         if logits and os.environ.get("PRIMIA_DUMP_LOGITS"):
             torch.save(torch.cat(logits).cpu(), os.environ["PRIMIA_DUMP_LOGITS"])
     else:
@@ -197,6 +294,21 @@ if __name__ == "__main__":
         eng.load_state_dict(sd)
         eng.eval()
         for i in range(images.shape[0]):
-            total_pred.append(int(eng.forward(images[i:i + 1]).argmax(dim=1).item()))
+            logits.append(eng.forward(images[i:i + 1]).float().cpu())
+            total_pred.append(int(logits[-1].argmax(dim=1).item()))
+    if evaluate:
+        from primia_amd.torchlib_compat import confusion_mcc, confusion_report, stats_table
+
+        # everything below is a function of the confusion matrix alone -- which is all --reveal confusion opened; the other
+        # forms count the predictions they opened against the labels.  ROC AUC needs the logits.
+        if matrix is None:
+            matrix = confusion_of(labels, total_pred, classes)
+        cm = matrix.numpy()
+        mcc = confusion_mcc(cm)
+        auc = roc_auc_of(labels, torch.cat([t.float().cpu() for t in logits])) if reveal == "logits" and logits else None
+        print(stats_table(cm, confusion_report(cm), roc_auc=auc, matthews_coeff=mcc, class_names=class_names))
+        print(json.dumps({"Evaluation": {"n": int(cm.sum()), "confusion_matrix": cm.tolist(), "mcc": mcc}}))
+        print("Took {:s} seconds.".format(str(datetime.now() - start_time)), file=sys.stderr)
+        sys.exit(0)
     print(json.dumps({"Inference Results": {i: p for i, p in enumerate(total_pred)}}))
     print("Took {:s} seconds.".format(str(datetime.now() - start_time)), file=sys.stderr)

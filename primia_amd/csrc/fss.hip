@@ -304,15 +304,12 @@ __global__ __launch_bounds__(256, 2) void dif_eval_local_n_kernel(LeOperand x1, 
 }
 
 // ---- DPF.eval (fss.py:320-338) ------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dpf_eval_kernel(int b, const u32* __restrict__ x, const u64* __restrict__ s0,
-                                                       const uint8_t* __restrict__ cw_bits,
-                                                       const u64* __restrict__ cw_s, const int64_t* __restrict__ cw_n,
-                                                       int64_t* __restrict__ out, long n) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+// Party b's walk of equality test i down the 32 levels on the masked input xv, and the leaf: its int64 share of [xv == alpha].
+// One function for primia_dpf_eval and primia_dpf_eval_local.
+__device__ __forceinline__ int64_t dpf_eval_walk(int b, u32 xv, const u64* __restrict__ s0, const uint8_t* __restrict__ cw_bits,
+                                                 const u64* __restrict__ cw_s, const int64_t* __restrict__ cw_n, long i, long n) {
     u64 sa = s0[i], sb = s0[n + i];
     u64 t = (u64)b;
-    const u32 xv = x[i];
     for (int lvl = 0; lvl < 32; ++lvl) {
         u64 buf[4];
         sha256_seed(sa, sb, buf);
@@ -325,7 +322,28 @@ __global__ __launch_bounds__(256) void dpf_eval_kernel(int b, const u32* __restr
         t = (w0 & 1ULL) ^ ((u64)((cb >> bit) & 1) & m);
     }
     const long sgn = b ? -1 : 1;
-    out[i] = sgn * ((long)t * cw_n[i] + conv31(sb));
+    return sgn * ((long)t * cw_n[i] + conv31(sb));
+}
+__global__ __launch_bounds__(256) void dpf_eval_kernel(int b, const u32* __restrict__ x, const u64* __restrict__ s0,
+                                                       const uint8_t* __restrict__ cw_bits,
+                                                       const u64* __restrict__ cw_s, const int64_t* __restrict__ cw_n,
+                                                       int64_t* __restrict__ out, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = dpf_eval_walk(b, x[i], s0, cw_bits, cw_s, cw_n, i, n);
+}
+// fss.eq for both parties hosted on this GPU (mpc/fss.py:97-185 with op = "eq"): mask_builder, the open mod 2^32 and both
+// parties' DPF.eval in ONE launch (blockIdx.y = party), on the operands of dif_eval_local_kernel
+__global__ __launch_bounds__(256) void dpf_eval_local_kernel(LeOperand x1, LeOperand x2, int len, const u64* __restrict__ alpha0,
+                                                             const u64* __restrict__ alpha1, const u64* __restrict__ s0_0,
+                                                             const u64* __restrict__ s0_1, const uint8_t* __restrict__ cw_bits,
+                                                             const u64* __restrict__ cw_s, const int64_t* __restrict__ cw_n,
+                                                             int64_t* __restrict__ out0, int64_t* __restrict__ out1, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int b = blockIdx.y;
+    const u32 xv = (u32)le_masked_sum(x1, x2, len, alpha0, alpha1, i);
+    (b ? out1 : out0)[i] = dpf_eval_walk(b, xv, b ? s0_1 : s0_0, cw_bits, cw_s, cw_n, i, n);
 }
 
 // ---- build_fss_keys' host arithmetic on raw keystream words (mpc/primitives.py:237-253, mpc/fss.py:344-358,495-501), in place:
@@ -573,6 +591,23 @@ int primia_dpf_eval(int b, const uint32_t* x, const uint64_t* s0, const uint8_t*
     if (n == 0) return PRIMIA_OK;
     dpf_eval_kernel<<<ceil_div(n, 256), 256, 0, (hipStream_t)st>>>(b, x, (const u64*)s0, cw_bits, (const u64*)cw_s,
                                                                     cw_n, out, n);
+    return launch_status();
+}
+
+int primia_dpf_eval_local(const int64_t* x1_0, const int64_t* x1_1, int w1, int start1, const int64_t* x2_0,
+                          const int64_t* x2_1, int w2, int start2, int len, const uint64_t* alpha0, const uint64_t* alpha1,
+                          const uint64_t* s0_0, const uint64_t* s0_1, const uint8_t* cw_bits, const uint64_t* cw_s,
+                          const int64_t* cw_n, int64_t* out0, int64_t* out1, int64_t n, primia_stream_t st) {
+    if (n == 0) return PRIMIA_OK;
+    // (both operands are required: equality against shares of zero has no caller)
+    PRIMIA_REQUIRE(x1_0 && x1_1 && x2_0 && x2_1 && alpha0 && alpha1 && s0_0 && s0_1 && cw_bits && cw_s && cw_n && out0 && out1 &&
+                   out0 != out1 && n > 0 && len > 0 && n % len == 0);
+    PRIMIA_REQUIRE(w2 >= len && start2 >= 0 && start2 + len <= w2 && w1 >= len && start1 >= 0 && start1 + len <= w1);
+    const dim3 grid((unsigned)ceil_div(n, 256), 2);
+    dpf_eval_local_kernel<<<grid, 256, 0, (hipStream_t)st>>>(
+        LeOperand{(const u64*)x1_0, (const u64*)x1_1, w1, start1}, LeOperand{(const u64*)x2_0, (const u64*)x2_1, w2, start2}, len,
+        (const u64*)alpha0, (const u64*)alpha1, (const u64*)s0_0, (const u64*)s0_1, cw_bits, (const u64*)cw_s, cw_n, out0, out1,
+        n);
     return launch_status();
 }
 

@@ -127,6 +127,32 @@ __global__ __launch_bounds__(256) void argmax_combine_local_kernel(Pair bit, Col
     }
 }
 
+// ---- the confusion-matrix step of an encrypted evaluation (defined in tests/secure_confusion_nets.py) --------
+// M += Y^T @ P for both parties: Y [B][C] the data owner's shared one-hot labels, P [B][C] the shared one-hot of the
+// predicted class, both row-major; the product is spdz_mul "matmul" of Y^T [C, B] and P [B, C] on the triple
+// ("matmul", (C, B), (B, C)) -- a [C][B] masks Y^T, b [B][C] masks P, c [C][C] -- without truncation:
+//   delta = open(Y^T - a)   eps = open(P - b)   z_j = delta @ b_j + a_j @ eps + c_j  (+ delta @ eps for j = 0)
+// Y is read where it lies: element [r][i] of Y^T is y[i * C + r].  Thread (j, r, k) forms party j's cell [r][k] of the
+// product over the B images in wrapping 64-bit arithmetic and adds it to ITS word of M_j; no other thread touches that word.
+__global__ __launch_bounds__(256) void confusion_combine_local_kernel(Pair y, Pair p, Triple t, OutPair m, long B, int C) {
+    const int cells = C * C;
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id >= 2 * cells) return;
+    const int j = id >= cells;
+    const int cell = j ? id - cells : id;
+    const int r = cell / C, k = cell - r * C;
+    const u64* const aj = j ? t.a1 : t.a0;
+    const u64* const bj = j ? t.b1 : t.b0;
+    u64 acc = (j ? t.c1 : t.c0)[cell];
+    for (long i = 0; i < B; ++i) {
+        const long iy = i * C + r, ia = (long)r * B + i, ip = i * C + k;
+        const u64 delta = (y.p0[iy] - t.a0[ia]) + (y.p1[iy] - t.a1[ia]);
+        const u64 eps = (p.p0[ip] - t.b0[ip]) + (p.p1[ip] - t.b1[ip]);
+        acc += delta * (j ? bj[ip] : bj[ip] + eps) + aj[ia] * eps;
+    }
+    (j ? m.p1 : m.p0)[cell] += acc;
+}
+
 // ---- batch_norm in eval mode (nn/functional.py:44-75), both parties ---------------------------------------------------
 //   rows = x.permute(1,0,2,3).reshape(C,-1).t()                         [B*HW, C], row b*HW + p
 //   normalized = inv * (rows - mean)     (FPT mul: Beaver + truncation; triple t1: a ~ inv [C], b ~ rows, c ~ rows)
@@ -445,6 +471,19 @@ int primia_argmax_combine_local(const int64_t* bit0, const int64_t* bit1, const 
     argmax_combine_local_kernel<<<sl_blocks(2 * B), 256, 0, (hipStream_t)st>>>(
         Pair{U(bit0), U(bit1)}, ColOperand{U(logits0), U(logits1), w, start}, Pair{U(k0), U(k1)},
         Triple{U(a0), U(b0), U(c0), U(a1), U(b1), U(c1)}, OutPair{(u64*)v0, (u64*)v1}, OutPair{(u64*)i0, (u64*)i1}, B);
+    return launch_status();
+}
+
+int primia_confusion_combine_local(const int64_t* y0, const int64_t* y1, const int64_t* p0, const int64_t* p1, const int64_t* a0,
+                                   const int64_t* b0, const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1,
+                                   int64_t* m0, int64_t* m1, int64_t B, int C, primia_stream_t st) {
+    PRIMIA_REQUIRE(y0 && y1 && p0 && p1 && a0 && b0 && c0 && a1 && b1 && c1 && m0 && m1 && B > 0 && C > 0 && C <= 16);
+    // M is updated in place, one word per thread: two buffers, neither of them an input
+    PRIMIA_REQUIRE(m0 != m1);
+    const int64_t* const in[] = {y0, y1, p0, p1, a0, b0, c0, a1, b1, c1};
+    for (const int64_t* q : in) PRIMIA_REQUIRE(q != m0 && q != m1);
+    confusion_combine_local_kernel<<<(2 * C * C + 255) / 256, 256, 0, (hipStream_t)st>>>(
+        Pair{U(y0), U(y1)}, Pair{U(p0), U(p1)}, Triple{U(a0), U(b0), U(c0), U(a1), U(b1), U(c1)}, OutPair{(u64*)m0, (u64*)m1}, B, C);
     return launch_status();
 }
 

@@ -183,6 +183,27 @@ class Dealer:
             self.tape.append(keys)
         return keys
 
+    def dpf_keys(self, n):
+        """Keys of n equality tests (fss.eq, the reference's DPF): the raw words of dif_keys -- alpha, both parties' seeds,
+        alpha's mask -- and the same split of alpha, always mod 2^32: the operands are class indices, and equality mod 2^32
+        has no error term, so the dealer's comparison width does not enter."""
+        if self.requests is not None:
+            self.requests.append(("dpf_keys", (n,), {}))
+        dev = self.device
+        alpha = self.rand64(n)
+        s0 = self.rand64(2, 2, n)
+        r = self.rand64(n)
+        a0 = torch.empty(n, dtype=I64, device=dev)
+        call("primia_fss_alpha_split", alpha, s0, r, a0, n)
+        bits, cw_s, cw_n = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in dpf_key_fields(n))
+        call("primia_dpf_keygen", alpha, s0, bits, cw_s, cw_n, n)
+        keys = [dict(alpha=[a0, r][b], s0=s0[b], bits=bits, cw_s=cw_s, cw_n=cw_n) for b in range(2)]
+        if self.log is not None:
+            self.log.append(("dpf", n, alpha.cpu().numpy(), s0.cpu().numpy(), r.cpu().numpy()))
+        if self.tape is not None:
+            self.tape.append(keys)
+        return keys
+
     def const_mask(self, *shape, owner=None):
         """The mask of a fresh sharing; `owner` (None = public value, else the party that holds the secret)
         only matters to a distributed dealer, which sends the mask to the owner alone."""
@@ -200,6 +221,12 @@ def dif_key_fields(n, bits=FSS_BITS):
     """(shape, dtype) of the correction words of n comparisons at width `bits`, common to both parties: the packed control
     bits, cw_sigma, cw_s and the leaf words (include/primia_hip.h)."""
     return [((bits, n), torch.uint8), ((bits, 2, n), I64), ((bits, 2, n), I64), ((bits + 1, n), torch.int32)]
+
+
+def dpf_key_fields(n):
+    """(shape, dtype) of the correction words of n equality tests, common to both parties: the packed control bits, cw_s and
+    the leaf word (include/primia_hip.h; always 32 levels)."""
+    return [((FSS_BITS, n), torch.uint8), ((FSS_BITS, 2, n), I64), ((n,), I64)]
 
 
 class PreloadedDealer:
@@ -221,6 +248,9 @@ class PreloadedDealer:
         return self._next()
 
     def dif_keys(self, n):
+        return self._next()
+
+    def dpf_keys(self, n):
         return self._next()
 
     def const_mask(self, *shape, owner=None):
@@ -593,6 +623,94 @@ class SecureContext:
             I = self.add(I, self._each(lambda j: Rt[j][1]))
         return (I, V) if values else I
 
+    # ---- equality and the confusion-matrix tail of an encrypted evaluation ---------------------------------------
+    def eq(self, x1, x2, cols1=(1, 0), cols2=(1, 0), length=1, shape=None):
+        """fss.eq(x1, x2) (mpc/fss.py:97-185 with op = "eq"): raw int64 shares of the bit [x1 == x2 mod 2^32], one DPF key per
+        element (`dpf_keys(n)`, row-major).  Always 32 bits wide: equality has no error term, and what it compares here are
+        class indices.  Both parties here: mask, open and both evaluations in one launch (primia_dpf_eval_local), where
+        colsK = (row width, first column) and `length` make operand K a column range of a matrix and `shape` = (rows, length)
+        the result's; otherwise primia_fss_mask, the open and primia_dpf_eval, on whole tensors -- same keys, same bits."""
+        ref = self._ref(x2)
+        shape = tuple(ref.shape) if shape is None else tuple(shape)
+        n = int(torch.Size(shape).numel())
+        keys = self.dealer.dpf_keys(n)
+        self.stats["dpf_evals"] = self.stats.get("dpf_evals", 0) + n
+        if self._local:
+            out = _pair(shape, ref.device)
+            k0, k1 = keys
+            call("primia_dpf_eval_local", x1[0], x1[1], cols1[0], cols1[1], x2[0], x2[1], cols2[0], cols2[1], length,
+                 k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"], k0["cw_s"], k0["cw_n"], out[0], out[1], n)
+            return out
+        if (cols1, cols2, length) != ((1, 0), (1, 0), 1):
+            x1 = self._cols(x1, n // length, cols1[0], cols1[1], length)
+            x2 = self._cols(x2, n // length, cols2[0], cols2[1], length)
+        r = [None, None]
+        for j in self.parties:  # mask_builder
+            r[j] = torch.empty(n, dtype=I64, device=ref.device)
+            call("primia_fss_mask", x1[j], x2[j], keys[j]["alpha"], r[j], n)
+        masked = torch.empty(n, dtype=torch.int32, device=ref.device)
+        if self.party is None:
+            call("primia_fss_open", r[0], r[1], masked, n)
+        else:
+            opened = self.opener.open(r)
+            call("primia_fss_open", opened, self._const(0, opened.device, n), masked, n)
+
+        def one(j):  # evaluate
+            o = torch.empty(shape, dtype=I64, device=ref.device)
+            k = keys[j]
+            call("primia_dpf_eval", j, masked, k["s0"], k["bits"], k["cw_s"], k["cw_n"], o, n)
+            return o
+
+        return self._each(one)
+
+    def _class_grid(self, B, C, device):
+        """tile(arange(C), (B, 1)) as a device tensor, uploaded once per shape and kept (see _const)."""
+        cache = self.__dict__.setdefault("_consts", {})
+        key = ("class_grid", B, C, str(device))
+        if key not in cache:
+            cache[key] = torch.arange(C, dtype=I64).repeat(B, 1).contiguous().to(device)
+        return cache[key]
+
+    def confusion(self, logits, labels_onehot, acc):
+        """One pass of an encrypted evaluation (defined by tests/secure_confusion_nets.py's oracle_confusion, not
+        pinned against the reference, which opens the predictions): acc += Y^T @ onehot(argmax(logits)) on shares, nothing
+        opened but masked operands.  logits: shares [B, C]; labels_onehot: the data owner's raw int64 one-hot labels [B, C]
+        (all-zero rows for padding images; None in the process of party 0); acc: the shares of the [C, C] confusion matrix,
+        updated IN PLACE -- acc[j][k] counts label j predicted as k.
+          I    = argmax(logits)                        the class form's tail and requests, unchanged
+          Y    = share(labels_onehot, owner=1)         const_mask((B, C), owner=1)
+          Kmat = share(tile(arange(C), (B, 1)))        const_mask((B, C)); Ib = I repeated along the classes, party-local
+          P    = eq(Ib, Kmat)                          dpf_keys(B * C)
+          acc += beaver_matmul(Y^T, P)                 triple ("matmul", (C, B), (B, C)), no truncation
+        Both parties here: primia_dpf_eval_local and primia_confusion_combine_local (Y is read row-major, no transposed
+        copy); otherwise the step-by-step chain -- same requests, same bits.  Returns the shares of P (tests)."""
+        xr = self._ref(logits)
+        B, C = xr.shape
+        dev = xr.device
+        I = self.argmax(logits)
+        if self.party in (None, 1):
+            if labels_onehot is None or tuple(labels_onehot.shape) != (B, C) or labels_onehot.dtype != I64:
+                raise ValueError(f"the data owner passes int64 one-hot labels [{B}, {C}]")
+            Y = self.share(labels_onehot.contiguous(), owner=1)
+        else:
+            Y = self.share(None, owner=1, shape=(B, C))
+        Kmat = self.share(self._class_grid(B, C, dev))
+        zero = self._const(0, dev, C * B)
+        rows = self.add(self._each(lambda j: zero), I)                  # [C, B]: every row is I
+        Ib = self._each(lambda j: _transposed(rows[j], C, B))           # [B, C]: I repeated along the class axis
+        P = self.eq(Ib, Kmat)
+        if self._local:
+            t = self.dealer.triple("matmul", (C, B), (B, C))
+            call("primia_confusion_combine_local", Y[0], Y[1], P[0], P[1], *_six(t), acc[0], acc[1], B, C)
+            self.stats["beaver_matmul"] += 1
+            return P
+        Mc = self.beaver_matmul(self._each(lambda j: _transposed(Y[j], B, C)), P)
+        for j in self.parties:      # (out of place, then back into the accumulator's own buffer)
+            o = _empty_like(acc[j])
+            call("primia_ring_add", acc[j], Mc[j], o, C * C, C * C)
+            acc[j].copy_(o)
+        return P
+
     def _stack2(self, a, b, n):
         """stack([a, b], axis=1) of two [n] vectors, per share: [n, 2]."""
         def one(j):
@@ -936,13 +1054,16 @@ def _check_pooling(pooling):
     return pooling
 
 
-REVEALS = ("logits", "class")
+REVEALS = ("logits", "class")      # what a pass of an inference may open, per image
+CONFUSION = "confusion"            # an evaluation on labelled images: nothing per image, the confusion matrix at the end
+EVALUATION_REVEALS = REVEALS + (CONFUSION,)
 
 
 def _check_reveal(reveal):
-    """What a pass opens: "logits", the full score vector (the reference's behaviour), or "class", the argmax alone."""
-    if reveal not in REVEALS:
-        raise ValueError(f"reveal must be one of {REVEALS}, got {reveal!r}")
+    """What a pass opens: "logits", the full score vector (the reference's behaviour), "class", the argmax alone, or
+    "confusion": nothing -- the passes of an evaluation add into a shared confusion matrix, which is opened after the last."""
+    if reveal not in EVALUATION_REVEALS:
+        raise ValueError(f"reveal must be one of {EVALUATION_REVEALS}, got {reveal!r}")
     return reveal
 
 
@@ -1005,7 +1126,11 @@ class SecureResNet18:
 
     reveal="class" ends the pass with `SecureContext.argmax` on the logit shares and opens the class indices alone (to the
     data owner): the logits, the model owner's asset, are never reconstructed.  "logits" (the default) is the reference's
-    behaviour, unchanged down to the dealer's request list, which is a strict prefix of the class form's."""
+    behaviour, unchanged down to the dealer's request list, which is a strict prefix of the class form's.
+
+    reveal="confusion" scores the model on labelled images: `begin()`, then passes with the data owner's labels, each ending
+    with `SecureContext.confusion` and returning nothing, then `finish()`, which opens the confusion matrix -- to both parties
+    -- and nothing else: no logit, no class, no label.  The class form's request list is a strict prefix of this one's."""
 
     def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max",
                  norm=None, reveal="logits"):
@@ -1038,6 +1163,37 @@ class SecureResNet18:
                 self.p[k] = ctx.share(ctx.encode(v.to(dev)), owner=0)
             else:
                 self.p[k] = ctx.share(None, owner=0, shape=v.shape)
+        self.acc = None
+        if self.reveal == CONFUSION:
+            self.classes = int(state_dict["fc.weight"].shape[0])
+            self.acc = ctx._each(lambda j: torch.zeros(self.classes, self.classes, dtype=I64).to(dev))
+
+    def begin(self):
+        """Start an evaluation: the shares of the confusion matrix are zeroed."""
+        if self.reveal != CONFUSION:
+            raise ValueError('begin() belongs to reveal="confusion"')
+        for j in self.ctx.parties:
+            self.acc[j].zero_()
+
+    def finish(self):
+        """End an evaluation: open the confusion matrix -- int64 [classes, classes], row = label, column = predicted class --
+        through the context's opener, which hands it to both parties."""
+        if self.reveal != CONFUSION:
+            raise ValueError('finish() belongs to reveal="confusion"')
+        return self.ctx.reconstruct(self.acc)
+
+    def onehot(self, labels, batch):
+        """int64 labels [n <= batch] -> raw int64 one-hot [batch, classes] on the device, the rows past n all zero (padding
+        images count nowhere); formed on the host and uploaded.  A [batch, classes] tensor is taken as the one-hot itself."""
+        dev = self.ctx.dealer.device
+        if labels.dim() == 2:
+            return labels
+        lab = labels.detach().to("cpu", I64).reshape(-1)
+        if lab.numel() > batch or (lab.numel() and not (0 <= int(lab.min()) and int(lab.max()) < self.classes)):
+            raise ValueError(f"labels: at most {batch} values in [0, {self.classes}), got {lab.tolist()}")
+        y = torch.zeros(batch, self.classes, dtype=I64)
+        y[torch.arange(lab.numel()), lab] = 1
+        return y.to(dev)
 
     def bn_prefixes(self):
         return _norm_prefixes(self.p, self.blocks)
@@ -1114,12 +1270,14 @@ class SecureResNet18:
         x = [None if t is None else t.reshape(B, -1) for t in x]
         return c.linear(x, p["fc.weight"], p["fc.bias"])
 
-    def __call__(self, image, batch=1):
+    def __call__(self, image, batch=1, labels=None):
         """image: fp32 [B, C, S, S] on the GPU -> decoded fp32 logits [B, classes]: the B images go through ONE protocol
         pass.  The data owner is party 1 (inference.py:292-300); in a distributed run party 0 passes image = None and
         `batch`, the number of images it is to expect (it receives shares, never an image).
         reveal="class": -> int64 [B] class indices, the only value the pass reconstructs; in a distributed run party 0 sends
-        its share of them to party 1, which returns the classes, and returns None itself."""
+        its share of them to party 1, which returns the classes, and returns None itself.
+        reveal="confusion": `labels` are the data owner's int64 labels [n <= B] of the first n images (the rest are padding and
+        count nowhere); party 0 passes none.  The pass adds into the shared confusion matrix and returns None."""
         c = self.ctx
         if c.party in (None, 1):
             xs = c.share(c.encode(image), owner=1)
@@ -1127,6 +1285,14 @@ class SecureResNet18:
             cin = c._ref(self.p["conv1.weight"]).shape[1]        # 3 (pretrained) or 1 (train.py:262)
             xs = c.share(None, owner=1, shape=(int(batch), cin, self.input_size, self.input_size))
         out = self.forward_shares(xs)
+        if self.reveal == CONFUSION:
+            y = None
+            if c.party in (None, 1):
+                if labels is None:
+                    raise ValueError('reveal="confusion": the data owner passes the labels of the images')
+                y = self.onehot(labels, c._ref(out).shape[0])
+            c.confusion(out, y, self.acc)
+            return None
         if self.reveal == "class":
             return c.open_to(c.argmax(out), to=1)
         return c.decode(c.reconstruct(out))
@@ -1150,6 +1316,15 @@ def argmax_requests(batch, classes):
     return [mask] + (int(classes) - 1) * [("dif_keys", (B,), {}), mask, ("triple", ("mul", (B, 2), (B, 2)), {})]
 
 
+def confusion_requests(batch, classes):
+    """What the tail of `SecureContext.confusion` requests after the argmax walk on [batch, classes] logits: the mask of the
+    data owner's one-hot labels, the mask of the re-shared class indices, the keys of batch * classes equality tests and the
+    triple of the [C, B] x [B, C] product."""
+    B, C = int(batch), int(classes)
+    return [("const_mask", (B, C), {"owner": 1}), ("const_mask", (B, C), {"owner": None}), ("dpf_keys", (B * C,), {}),
+            ("triple", ("matmul", (C, B), (B, C)), {})]
+
+
 def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits"):
     """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
     `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
@@ -1160,7 +1335,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree).
     An architecture without running statistics is the GroupNorm network: no hoisted Newton; every norm site requests its
     square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples.
-    reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix)."""
+    reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix).
+    reveal="confusion": the confusion tail's requests follow the argmax tail's (the class form's list is a strict prefix)."""
     _check_pooling(pooling)
     _check_reveal(reveal)
     B, req = int(batch), []
@@ -1232,8 +1408,10 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
         c, h = o, ho
     classes, feat = arch["fc.weight"]
     triple("matmul", (B, feat), (feat, classes))
-    if reveal == "class":
+    if reveal != "logits":
         req += argmax_requests(B, classes)
+    if reveal == CONFUSION:
+        req += confusion_requests(B, classes)
     return req
 
 
@@ -1251,6 +1429,17 @@ class _DifKeyBytes(int):
 DIF_KEY_BYTES = _DifKeyBytes(3 * 8 + 32 + 32 + 2 * 32 * 2 * 8 + 33 * 4)
 
 
+def _dpf_key_bytes():
+    """Bytes of one equality test's DPF key as Dealer.dpf_keys lays it out: raw alpha, its mask and party 0's share (3 x 8),
+    both parties' seeds (2 x 2 x 8) and the correction words at the sizes their field shapes give (32 control bytes,
+    32 x 2 x 8 of cw_s, one int64 leaf): 608, whatever the comparison width."""
+    cw = sum(int(torch.Size(shape).numel()) * torch.empty(0, dtype=dt).element_size() for shape, dt in dpf_key_fields(1))
+    return 3 * 8 + 2 * 2 * 8 + cw
+
+
+DPF_KEY_BYTES = _dpf_key_bytes()
+
+
 def primitive_bytes(requests, fss_bits=FSS_BITS):
     """Device bytes of the primitives a request list stands for (both parties' halves), its comparison keys at `fss_bits`."""
     key_bytes = DIF_KEY_BYTES(fss_bits)
@@ -1261,6 +1450,8 @@ def primitive_bytes(requests, fss_bits=FSS_BITS):
             total += 8 * numel(args)
         elif kind == "dif_keys":
             total += key_bytes * args[0]
+        elif kind == "dpf_keys":
+            total += DPF_KEY_BYTES * args[0]
         else:
             op, xs, ys = args
             total += 16 * (numel(xs) + numel(ys) + numel(_triple_c_shape(op, xs, ys)))
@@ -1317,6 +1508,10 @@ class GraphedSecureInference:
     reveal="class": the argmax tail is part of the captured graph and the static output is the int64 [batch] buffer of class
     indices; nothing else is reconstructed.
 
+    reveal="confusion": the confusion tail is part of the captured graph too; the one-hot labels are a static int64
+    [batch, classes] buffer next to the images (`load` zero-fills the rows of padding images), the shares of the confusion
+    matrix a static buffer the captured pass adds into; `begin()` zeroes it, `finish()` opens it, a pass returns None.
+
     fss_bits: the width of the comparisons (the dealer's; see FSS_BITS) -- wider keys count in the refusal above."""
 
     refill_graph = True
@@ -1341,12 +1536,15 @@ class GraphedSecureInference:
                              f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
         self.image = torch.zeros(self.batch, state_dict["conv1.weight"].shape[1], input_size, input_size, dtype=torch.float32).to(self.device)
+        self.labels = None
+        if reveal == CONFUSION:      # (all-zero one-hot rows: the warm-up images are padding)
+            self.labels = torch.zeros(self.batch, int(state_dict["fc.weight"].shape[0]), dtype=I64).to(self.device)
         self.dealer = Dealer(self.device, seed, self.fss_bits)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
         model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)
         self._n_model = len(self.dealer.tape)          # primitives consumed by sharing the model (kept)
-        model(self.image)                              # offline pass: fills the tape, warms every kernel
+        model(self.image, labels=self.labels)          # offline pass: fills the tape, warms every kernel
         self.tape, self.requests = self.dealer.tape, self.dealer.requests
         self.dealer.tape = self.dealer.requests = None
         self.stats = dict(ctx.stats)
@@ -1354,14 +1552,14 @@ class GraphedSecureInference:
         pre = PreloadedDealer(self.tape, self.device, self.fss_bits)
         self._ctx = SecureContext(pre, base, precision_fractional)
         self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)   # re-shares with the same masks
-        self._model(self.image)                        # eager pass over the static buffers: builds the pointer tables
+        self._model(self.image, labels=self.labels)    # eager pass over the static buffers: builds the pointer tables
         pre.pos, self._ctx._newton_calls = self._n_model, 0
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=side):
-                self.out = self._model(self.image)
+                self.out = self._model(self.image, labels=self.labels)
         torch.cuda.current_stream().wait_stream(side)
         # the provider's block counter moves to the device, behind everything the offline pass drew
         self._ctr = torch.tensor([self.dealer._block], dtype=I64).to(self.device)      # (uploaded: no fill kernel)
@@ -1377,6 +1575,16 @@ class GraphedSecureInference:
                 with torch.cuda.graph(self._refill_g, stream=side):
                     self._refill_launches()
             torch.cuda.current_stream().wait_stream(side)
+        if reveal == CONFUSION:
+            self.begin()                               # (the warm-up passes added shares of zero)
+
+    def begin(self):
+        """Start an evaluation: zero the static shares of the confusion matrix."""
+        self._model.begin()
+
+    def finish(self):
+        """Open the confusion matrix of the passes since begin(): int64 [classes, classes], row = label."""
+        return self._model.finish()
 
     def _rehome_tape(self):
         """Move every uniformly random tensor of the per-image primitives into ONE int64 arena (64-byte aligned slices, current
@@ -1392,7 +1600,7 @@ class GraphedSecureInference:
             elif kind == "triple":
                 (a0, b0, c0), (a1, b1, _c1) = e
                 sizes = [a0.numel(), a1.numel(), b0.numel(), b1.numel(), c0.numel()]
-            elif kind == "dif_keys":
+            elif kind in ("dif_keys", "dpf_keys"):
                 sizes = [args[0], 4 * args[0], args[0]]        # raw alpha, both parties' seeds, alpha's mask
             else:
                 raise _lib.PrimiaError(f"unknown primitive kind {kind!r}")
@@ -1436,6 +1644,9 @@ class GraphedSecureInference:
                 s0[1].copy_(k1["s0"])
                 r = view(offs[2], k1["alpha"])
                 k0["s0"], k1["s0"], k1["alpha"] = s0[0], s0[1], r
+                if kind == "dpf_keys":
+                    self._ops.append(("dpf", n, alpha, s0, r, k0["alpha"], k0["bits"], k0["cw_s"], k0["cw_n"]))
+                    continue
                 self._ops.append(("dif", n, alpha, s0, r, k0["alpha"], k0["bits"], k0["cw_sigma"], k0["cw_s"], k0["cw_leaf"]))
         self._mm_scratch = torch.empty(max_kn, dtype=I64, device=dev)
 
@@ -1447,6 +1658,10 @@ class GraphedSecureInference:
             if op[0] == "triple":
                 _, kind, xshape, yshape, a0, a1, b0, b1, c0, c1 = op
                 d.triple_c1(kind, xshape, yshape, a0, a1, b0, b1, c0, c1, scratch=self._mm_scratch)
+            elif op[0] == "dpf":
+                _, m, alpha, s0, r, a0, bits, cw_s, cw_n = op
+                call("primia_fss_alpha_split", alpha, s0, r, a0, m)
+                call("primia_dpf_keygen", alpha, s0, bits, cw_s, cw_n, m)
             else:
                 _, m, alpha, s0, r, a0, bits, cw_sigma, cw_s, leaf = op
                 fss_call("fss_alpha_split", d.fss_bits, alpha, s0, r, a0, m)
@@ -1461,8 +1676,14 @@ class GraphedSecureInference:
             self._refill_launches()
         self.refills += 1
 
-    def load(self, image):
-        """Copy [n <= batch, C, S, S] images into the static input buffer, the rest of it zero; returns n."""
+    def load(self, image, labels=None):
+        """Copy [n <= batch, C, S, S] images into the static input buffer, the rest of it zero; returns n.
+        reveal="confusion": `labels`, int64 [n], become the one-hot rows of the static label buffer; the rows of padding images
+        are zero-filled."""
+        if self.labels is not None:
+            if labels is None or labels.numel() != image.shape[0]:
+                raise ValueError('reveal="confusion": one label per image')
+            self.labels.copy_(self._model.onehot(labels, self.batch))
         if self.batch == 1:
             self.image.copy_(image)
             return 1
@@ -1476,16 +1697,18 @@ class GraphedSecureInference:
 
     def rows(self, n):
         """The first n rows of the static output (all of it, the very buffer, for a full batch)."""
+        if self.out is None:      # reveal="confusion": a pass returns nothing
+            return None
         return self.out if n == self.batch else self.out[:n]
 
-    def __call__(self, image, refill=True):
+    def __call__(self, image, refill=True, labels=None):
         """image [n <= batch, C, S, S] -> logits [n, classes], or with reveal="class" int64 class indices [n] (a view of the
         static output buffer).
         refill=False replays on the primitives the buffers hold (bit-identity checks against an eager forward on the
         same tape; a deployment never serves two images on one set of primitives)."""
         if refill:
             self.refill()
-        n = self.load(image)
+        n = self.load(image, labels)
         self.graph.replay()
         return self.rows(n)
 
@@ -1505,6 +1728,8 @@ class PipelinedSecureInference:
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
                  batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS):
         self.device = torch.device(device)
+        if reveal == CONFUSION:
+            raise ValueError('reveal="confusion" accumulates in one set of static buffers: use GraphedSecureInference')
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
                                              None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling,
                                              reveal=reveal, fss_bits=fss_bits)
@@ -1589,6 +1814,9 @@ class PartyLink:
         return t
 
 
+DPF_CW_NAMES = ("bits", "cw_s", "cw_n")
+
+
 def _triple_c_shape(op, xshape, yshape):
     if op == "mul":
         nx = int(torch.Size(xshape).numel())
@@ -1622,6 +1850,13 @@ class PartyDealer:
             k[name] = f(shape, dt, private=False)
         return self._mine(k)
 
+    def dpf_keys(self, n):
+        f = self.link.from_dealer
+        k = dict(alpha=f((n,)), s0=f((2, n)))
+        for name, (shape, dt) in zip(DPF_CW_NAMES, dpf_key_fields(n)):
+            k[name] = f(shape, dt, private=False)
+        return self._mine(k)
+
     def const_mask(self, *shape, owner=None):
         return self.link.from_dealer(shape, private=owner is not None)
 
@@ -1652,6 +1887,12 @@ class DealerService:
                     send(v[j]["s0"], j)
                 for name in ("bits", "cw_sigma", "cw_s", "cw_leaf"):
                     send(v[0][name], None)
+            elif kind == "dpf_keys":      # alpha share and seed private, correction words to both
+                for j in range(2):
+                    send(v[j]["alpha"], j)
+                    send(v[j]["s0"], j)
+                for name in DPF_CW_NAMES:
+                    send(v[0][name], None)
             else:
                 send(v, kw.get("owner"))
 
@@ -1663,7 +1904,7 @@ def party_context(link: PartyLink, precision_fractional=16, base=10, fss_bits=FS
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS):
+                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, labels=None):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
     all know the architecture, the input size, the stem pool (`pooling`), how many images will be classified and how many go
@@ -1673,6 +1914,8 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     reveal="class": every pass ends with the argmax tail and party 0 sends its share of the class indices to party 1, which
     returns one int64 [<= batch] tensor per pass; party 0 learns nothing and returns None, like the dealer, which follows
     the extended schedule.
+    reveal="confusion": party 1 also passes `labels`, int64 [n_images]; every pass ends with the confusion tail, after the last
+    the confusion matrix is opened between the parties, and both return it (int64 [classes, classes]); the dealer returns None.
     fss_bits: the width of the comparisons, known to all three like the schedule."""
     _check_pooling(pooling)
     _check_reveal(reveal)
@@ -1695,6 +1938,10 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
             raise ValueError("party 1 is the data owner: it needs the images")
         shapes = {k: torch.empty(shape, device="meta") for k, shape in arch.items()}
     model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling, reveal=reveal)
+    if reveal == CONFUSION:
+        if link.role == 1 and (labels is None or labels.numel() != n_images):
+            raise ValueError("party 1 is the data owner: it needs one label per image")
+        model.begin()
     out = []
     for i in range(0, n_images, batch):
         n = min(batch, n_images - i)
@@ -1703,7 +1950,9 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
             chunk = images[i:i + n]
             if n < batch:
                 chunk = torch.cat([chunk, chunk.new_zeros((batch - n,) + tuple(chunk.shape[1:]))])
-        res = model(chunk, batch=batch)
+        res = model(chunk, batch=batch, labels=labels[i:i + n] if reveal == CONFUSION and link.role == 1 else None)
         if res is not None:
             out.append(res if n == batch else res[:n])
+    if reveal == CONFUSION:
+        return model.finish()
     return None if reveal == "class" and link.role == 0 else out

@@ -387,15 +387,48 @@ def matthews_corrcoef(y_true, y_pred, num_classes):
     c = np.zeros((num_classes, num_classes), dtype=np.float64)
     for t, p in zip(y_true, y_pred):
         c[int(t), int(p)] += 1
+    return confusion_mcc(c)
+
+
+def confusion_mcc(conf_matrix):
+    """Multi-class MCC of a confusion matrix (row = label, column = prediction)."""
+    import numpy as np
+
+    c = np.asarray(conf_matrix, dtype=np.float64)
     t_k, p_k, n, tr = c.sum(1), c.sum(0), c.sum(), np.trace(c)
     num = tr * n - t_k @ p_k
     den = np.sqrt(n * n - p_k @ p_k) * np.sqrt(n * n - t_k @ t_k)
     return float(num / den) if den > 0 else 0.0
 
 
+def confusion_report(conf_matrix):
+    """What stats_table reads of sklearn's classification_report(output_dict=True, zero_division=0), from the confusion
+    matrix alone (row = label, column = prediction): per class recall, precision, F1 and support, their macro and
+    support-weighted averages, and the accuracy -- so that an evaluation which opens nothing but the matrix prints the
+    reference's table."""
+    import numpy as np
+
+    c = np.asarray(conf_matrix, dtype=np.float64)
+    k = c.shape[0]
+    support, predicted, hit = c.sum(1), c.sum(0), np.diag(c)
+    div = lambda a, b: np.divide(a, b, out=np.zeros_like(a), where=b > 0)
+    recall, precision = div(hit, support), div(hit, predicted)
+    f1 = div(2 * precision * recall, precision + recall)
+    total = float(support.sum())
+    rep = {str(i): {"precision": float(precision[i]), "recall": float(recall[i]), "f1-score": float(f1[i]),
+                    "support": int(support[i])} for i in range(k)}
+    weights = support / total if total > 0 else np.zeros(k)
+    for key, w in (("macro avg", np.full(k, 1.0 / k)), ("weighted avg", weights)):
+        rep[key] = {"precision": float(precision @ w), "recall": float(recall @ w), "f1-score": float(f1 @ w),
+                    "support": int(total)}
+    rep["accuracy"] = float(hit.sum() / total) if total > 0 else 0.0
+    return rep
+
+
 def stats_table(conf_matrix, report, roc_auc=0.0, matthews_coeff=0.0, class_names=None, epoch=0):
     """The validation table of torchlib/utils.py:1295-1351: one row per class (recall, precision, F1, support,
-    confusion-matrix row), macro / weighted averages, then micro recall, MCC and ROC AUC; `fancy_grid`."""
+    confusion-matrix row), macro / weighted averages, then micro recall, MCC and ROC AUC; `fancy_grid`.  roc_auc=None: the
+    score is not available (an encrypted evaluation that opens no logits) and is shown as "n/a"."""
     from tabulate import tabulate
 
     pct = lambda v: "{:.1f} %".format(v * 100.0)
@@ -410,7 +443,8 @@ def stats_table(conf_matrix, report, roc_auc=0.0, matthews_coeff=0.0, class_name
         e = report[key]
         rows.append([title, pct(e["recall"]), pct(e["precision"]), pct(e["f1-score"]), e["support"]])
     rows.append(["Overall stats", "micro recall", "matthews coeff", "AUC ROC score"])
-    rows.append(["", pct(report["accuracy"]), "{:.3f}".format(matthews_coeff), "{:.3f}".format(roc_auc)])
+    rows.append(["", pct(report["accuracy"]), "{:.3f}".format(matthews_coeff),
+                 "n/a" if roc_auc is None else "{:.3f}".format(roc_auc)])
     headers = ["Epoch {:d}".format(epoch), "Recall", "Precision", "F1 score", "n total"] + [label(i) for i in range(n)]
     return tabulate(rows, headers=headers, tablefmt="fancy_grid")
 

@@ -7,6 +7,8 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    statistics online -- a Beaver square and an 80-step Newton iteration on batch * 32 values per layer
     --reveal class: every pass ends with the secret-shared argmax and opens the class only (classes - 1 rounds of one comparison
                    launch and one select launch on `batch` elements; the report names it)
+    --reveal confusion (with --batch): the passes of an encrypted evaluation -- the argmax, then batch * classes equality tests and
+                   one [C, B] x [B, C] Beaver product into the shared confusion matrix; seeded labels, nothing opened per pass
     --fss_bits N:  the width of the comparisons, 32 (default, the reference's) to 64: N levels per key and per evaluation (the
                    report names it when it is not 32)"""
 import argparse, json, os, sys, time
@@ -27,8 +29,9 @@ def main():
                     help="the stem pool of the served network (a checkpoint's pooling_type); the report names it when it is avg")
     ap.add_argument("--norm", choices=("batch", "group"), default="batch",
                     help="group: a synthetic GroupNorm(32, C) state dict, no running statistics (the report names it)")
-    ap.add_argument("--reveal", choices=("logits", "class"), default="logits",
-                    help="class: the passes end with SecureContext.argmax and open the predicted class only (the report names it)")
+    ap.add_argument("--reveal", choices=("logits", "class", "confusion"), default="logits",
+                    help="class: the passes end with SecureContext.argmax and open the predicted class only (the report names it); "
+                         "confusion (with --batch): the passes of an encrypted evaluation, which add into the shared confusion matrix")
     ap.add_argument("--fss_bits", type=int, default=32,
                     help="the width of the DIF comparisons (32..64): key bytes and DIF kernel time grow linearly with it (the report "
                          "names it when it is not 32)")
@@ -37,6 +40,8 @@ def main():
     ap.add_argument("--only-fss-roofline", action="store_true",
                     help="run the DIF keygen / eval kernels alone (the command the rocprofv3 --pmc passes of tools/pmc_secure.sh wrap)")
     a = ap.parse_args()
+    if a.reveal == "confusion" and not (a.batch and not a.only_fss_roofline):
+        ap.error("--reveal confusion is timed in the serving form: pass --batch N")
 
 
     def cpu_sample_timings():
@@ -170,16 +175,18 @@ def main():
         imgs = torch.randn(B, 3, a.size, a.size, generator=g).to(dev)
         free = torch.cuda.mem_get_info(dev)[0]
         gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw, **reveal_kw, **bits_kw)
-        gi(imgs, refill=False); torch.cuda.synchronize()
+        # (an evaluation's passes carry the data owner's labels: seeded, one per image)
+        lab_kw = {"labels": torch.randint(0, 3, (B,), generator=g)} if a.reveal == "confusion" else {}
+        gi(imgs, refill=False, **lab_kw); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(reps):
-            gi(imgs, refill=False)
+            gi(imgs, refill=False, **lab_kw)
         torch.cuda.synchronize()
         online = (time.perf_counter() - t0) / reps * 1e3
-        gi(imgs); torch.cuda.synchronize()
+        gi(imgs, **lab_kw); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(reps):
-            gi(imgs)                    # the dealer's refill graph, then the online graph, on one stream
+            gi(imgs, **lab_kw)          # the dealer's refill graph, then the online graph, on one stream
         torch.cuda.synchronize()
         both = (time.perf_counter() - t0) / reps * 1e3
         print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, **reveal_kw, **bits_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
@@ -188,7 +195,8 @@ def main():
                           "static_primitive_bytes": gi.static_bytes, "arena_mb": round(gi._arena.numel() * 8 / 1e6, 1),
                           "device_free_bytes_before": free,
                           "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw, **reveal_kw, **bits_kw),
-                          "dif_evals": gi.stats["dif_evals"], "beaver_matmul": gi.stats["beaver_matmul"],
+                          "dif_evals": gi.stats["dif_evals"], **({"dpf_evals": gi.stats["dpf_evals"]} if "dpf_evals" in gi.stats else {}),
+                          "beaver_matmul": gi.stats["beaver_matmul"],
                           "beaver_mul": gi.stats["beaver_mul"]}))
         return
 
