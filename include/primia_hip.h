@@ -1013,6 +1013,20 @@ int primia_newton_reciprocal_local(const int64_t* v0, const int64_t* v1, const i
  *                                (no transposed copy); p: shares of the one-hot predicted class [B][C]; a [C][B], b [B][C],
  *                                c [C][C]; m: the accumulator [C][C], updated IN PLACE (two distinct buffers, neither an
  *                                input).  Wrapping int64 as primia_beaver_combine_matmul; C <= 16, any B >= 1
+ *   primia_auc_cross_local       the comparison operands of one row block of the rank-count tail of an encrypted evaluation
+ *                                with a ROC AUC, rows [row0, row0 + R) of the N held: A [R][C][N] with
+ *                                A[i][a][j] = n[row0 + i][a] * d[j] and Bm [R][C][N] with Bm[i][a][j] = d[row0 + i] * n[j][a],
+ *                                each a Beaver matmul with K = 1, both opens inside, no truncation -- bit-identical to
+ *                                primia_beaver_matmul_local of n[blk].reshape(R C, 1) with d.reshape(1, N) on the triple
+ *                                ("matmul", (R C, 1), (1, N)) and of d[blk].reshape(R, 1) with n^T.reshape(1, C N) on
+ *                                ("matmul", (R, 1), (1, C N)).  n: shares of the min-shifted logits [N][C] and d: of their
+ *                                row sums [N], both read in place (no transposed or reshaped copy); ta / tb: HOST arrays of
+ *                                the two triples' six pointers; four distinct outputs, none of them an input.  C <= 16
+ *   primia_auc_count_combine_local  the counting step of a row block: U += Y[blk]^T @ T, the Beaver matmul of Y[blk]^T
+ *                                [C, R] and T [R, C C] on the triple ("matmul", (C, R), (R, C C)), both opens inside, no
+ *                                truncation.  y: the block's rows of the shared one-hot labels [R][C], read row-major (no
+ *                                transposed copy); t: shares of T [R][C C]; a [C][R], b [R][C C], c [C][C C]; u: the
+ *                                accumulator [C][C C], updated IN PLACE (two distinct buffers, neither an input).  C <= 16
  *   primia_bn_eval_local         batch_norm in eval mode (nn/functional.py:44-75) of one image: NCHW in, NCHW out, both
  *                                FPT products and the row / column re-layouts inside; t1 / t2: HOST arrays of the two
  *                                triples' six pointers (t1: a ~ inv [C], b, c ~ rows [HW, C]; t2: a, c ~ rows, b ~ weight)
@@ -1050,6 +1064,12 @@ int primia_dpf_eval_local(const int64_t* x1_0, const int64_t* x1_1, int w1, int 
 int primia_confusion_combine_local(const int64_t* y0, const int64_t* y1, const int64_t* p0, const int64_t* p1, const int64_t* a0,
                                    const int64_t* b0, const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1,
                                    int64_t* m0, int64_t* m1, int64_t B, int C, primia_stream_t stream);
+int primia_auc_cross_local(const int64_t* n0, const int64_t* n1, const int64_t* d0, const int64_t* d1, const int64_t* const* ta,
+                           const int64_t* const* tb, int64_t* a_out0, int64_t* a_out1, int64_t* b_out0, int64_t* b_out1, int64_t N,
+                           int C, int64_t row0, int64_t R, primia_stream_t stream);
+int primia_auc_count_combine_local(const int64_t* y0, const int64_t* y1, const int64_t* t0, const int64_t* t1, const int64_t* a0,
+                                   const int64_t* b0, const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1,
+                                   int64_t* u0, int64_t* u1, int64_t R, int C, primia_stream_t stream);
 int primia_bn_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
                          const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
                          const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,

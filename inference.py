@@ -17,7 +17,9 @@ a secret-shared argmax and opens the predicted class alone: the logits, the mode
 `--evaluate` scores the model on a labelled set instead (`--data_dir` a class-folder tree <dir>/<class>/<image>, or `synthetic`
 for seeded images and labels), plain or encrypted, and prints the reference's validation table and one JSON line
 {"Evaluation": {"n": ..., "confusion_matrix": [[...]], "mcc": ...}}.  With `--reveal confusion` an encrypted evaluation opens
-the confusion matrix and nothing else: no logit, no predicted class and no label leaves its owner.
+the confusion matrix and nothing else: no logit, no predicted class and no label leaves its owner.  `--reveal metrics` opens,
+with the matrix, the pair counts of the reference's one-vs-one ROC AUC -- formed on shares after the last pass -- and prints the
+table with the AUC ({"Evaluation": {..., "roc_auc": ...}}); still nothing per image.
 """
 import argparse
 import json
@@ -170,13 +172,16 @@ if __name__ == "__main__":
                         help="encrypted inference with model_owner, data_owner and crypto_provider as three ranks "
                              "(launch with `python -m torch.distributed.run --nproc-per-node 3 inference.py ...`): "
                              "one GPU each over RCCL when three are visible, else all on GPU 0 over gloo")
-    parser.add_argument("--reveal", choices=("logits", "class", "confusion"), default="logits",
+    parser.add_argument("--reveal", choices=("logits", "class", "confusion", "metrics"), default="logits",
                         help="encrypted inference: what a pass opens.  logits (default, the reference): the full score "
                              "vector, whose argmax is taken in the clear; class: the predicted class alone, through a "
                              "secret-shared argmax of classes - 1 comparison rounds (the logits are never reconstructed, so "
                              "PRIMIA_DUMP_LOGITS is refused); confusion (with --evaluate only): nothing per image -- every "
                              "pass adds into a secret-shared confusion matrix through classes equality tests per image, and "
-                             "the matrix alone is opened after the last pass (ROC AUC needs logits and is not reported)")
+                             "the matrix alone is opened after the last pass (no ROC AUC); metrics (with --evaluate only): the "
+                             "confusion passes, then classes * n^2 64-bit comparisons of cross-multiplied scores on shares: "
+                             "the matrix and 2 * classes * (classes - 1) pair counts are opened, from which the reference's "
+                             "one-vs-one ROC AUC follows -- nothing per image")
     parser.add_argument("--debug_dealer_seed", type=int, default=None,
                         help="DEBUG ONLY: derive the crypto provider's key from this number (reproducible, hence "
                              "NOT private); by default the key comes from the OS entropy pool and never leaves the "
@@ -190,12 +195,12 @@ if __name__ == "__main__":
     if not 32 <= fss_bits <= 64:
         raise SystemExit(f"--fss_bits must be in [32, 64], got {fss_bits}")
     evaluate = cmd_args.evaluate
-    if reveal == "confusion" and not evaluate:
-        raise SystemExit("--reveal confusion opens the confusion matrix of a labelled set and nothing per image: an inference "
+    if reveal in ("confusion", "metrics") and not evaluate:
+        raise SystemExit(f"--reveal {reveal} opens the confusion matrix of a labelled set and nothing per image: an inference "
                          "has no labels to count against and would print nothing -- pass --evaluate (and a class-folder "
                          "--data_dir or `synthetic`)")
-    if reveal == "confusion" and not cmd_args.encrypted_inference:
-        raise SystemExit("--reveal says what an ENCRYPTED run opens: --reveal confusion needs --encrypted_inference")
+    if reveal in ("confusion", "metrics") and not cmd_args.encrypted_inference:
+        raise SystemExit(f"--reveal says what an ENCRYPTED run opens: --reveal {reveal} needs --encrypted_inference")
     if reveal != "logits" and os.environ.get("PRIMIA_DUMP_LOGITS"):
         raise SystemExit(f"--reveal {reveal}: the logits are never opened, there is nothing for PRIMIA_DUMP_LOGITS to write")
     if not torch.cuda.is_available():
@@ -223,6 +228,7 @@ if __name__ == "__main__":
         if evaluate:
             labels = synthetic_labels(images.shape[0], classes)
     matrix = None      # --reveal confusion: the opened confusion matrix, all such a run learns
+    rank_counts = None # --reveal metrics: the opened pair counts of the ROC AUC, next to the matrix
     logits = []        # the logits a run opened, pass by pass (none with --reveal class / confusion)
     total_pred = []
     bs = cmd_args.batch_size
@@ -249,12 +255,14 @@ if __name__ == "__main__":
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
                                     precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal,
-                                    fss_bits=fss_bits, labels=labels if link.role == 1 and reveal == "confusion" else None)
+                                    fss_bits=fss_bits, labels=labels if link.role == 1 and reveal in ("confusion", "metrics") else None)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
                 sys.exit(0)
-            if reveal == "confusion":      # both parties hold the matrix; the data owner's rank reports it
+            if reveal == "metrics":        # both parties hold the matrix and the counts
+                matrix, rank_counts = result[0].cpu(), result[1].cpu()
+            elif reveal == "confusion":    # both parties hold the matrix; the data owner's rank reports it
                 matrix = result.cpu()
             elif reveal == "class":        # party 1 holds the class indices themselves
                 total_pred = [int(c) for o in result for c in o.tolist()]
@@ -272,11 +280,14 @@ if __name__ == "__main__":
                 ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
                                     precision_fractional=cmd_args.precision_fractional)
                 model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling, reveal=reveal)
-            if reveal == "confusion":      # an evaluation: the passes return nothing, the matrix is opened after the last
+            if reveal in ("confusion", "metrics"):      # an evaluation: the passes return nothing, the matrix is opened after the last
                 model.begin()
                 for i in range(0, images.shape[0], bs):
                     model(images[i:i + bs], labels=labels[i:i + bs])
-                matrix = model.finish().cpu()
+                if reveal == "metrics":
+                    matrix, rank_counts = (t.cpu() for t in model.finish())
+                else:
+                    matrix = model.finish().cpu()
             else:
                 for i in range(0, images.shape[0], bs):
                     out = model(images[i:i + bs]).clone()     # (the graphed form returns its static output buffer: keep a copy)
@@ -297,17 +308,21 @@ if __name__ == "__main__":
             logits.append(eng.forward(images[i:i + 1]).float().cpu())
             total_pred.append(int(logits[-1].argmax(dim=1).item()))
     if evaluate:
-        from primia_amd.torchlib_compat import confusion_mcc, confusion_report, stats_table
+        from primia_amd.torchlib_compat import auc_from_rank_counts, confusion_mcc, confusion_report, stats_table
 
         # everything below is a function of the confusion matrix alone -- which is all --reveal confusion opened; the other
-        # forms count the predictions they opened against the labels.  ROC AUC needs the logits.
+        # forms count the predictions they opened against the labels.  The ROC AUC comes from the logits, or with --reveal metrics from
+        # the opened pair counts.
         if matrix is None:
             matrix = confusion_of(labels, total_pred, classes)
         cm = matrix.numpy()
         mcc = confusion_mcc(cm)
         auc = roc_auc_of(labels, torch.cat([t.float().cpu() for t in logits])) if reveal == "logits" and logits else None
+        result = {"n": int(cm.sum()), "confusion_matrix": cm.tolist(), "mcc": mcc}
+        if rank_counts is not None:
+            auc = result["roc_auc"] = auc_from_rank_counts(rank_counts.numpy(), cm.sum(axis=1))
         print(stats_table(cm, confusion_report(cm), roc_auc=auc, matthews_coeff=mcc, class_names=class_names))
-        print(json.dumps({"Evaluation": {"n": int(cm.sum()), "confusion_matrix": cm.tolist(), "mcc": mcc}}))
+        print(json.dumps({"Evaluation": result}))
         print("Took {:s} seconds.".format(str(datetime.now() - start_time)), file=sys.stderr)
         sys.exit(0)
     print(json.dumps({"Inference Results": {i: p for i, p in enumerate(total_pred)}}))

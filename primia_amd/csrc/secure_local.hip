@@ -153,6 +153,60 @@ __global__ __launch_bounds__(256) void confusion_combine_local_kernel(Pair y, Pa
     (j ? m.p1 : m.p0)[cell] += acc;
 }
 
+// ---- the rank-count tail of an encrypted evaluation with a ROC AUC (defined in tests/secure_auc_nets.py) -------
+// Steps 1 and 2 of a row block [row0, row0 + R) of the N rows: the operands of the comparison [p_a(i) <= p_a(j)] of the
+// normalised scores p_a = n_a / d, cross-multiplied so that nothing is divided on shares:
+//   A  [i][a][j] = n[row0 + i][a] * d[j]      spdz_mul "matmul" of n[blk].reshape(R C, 1) and d.reshape(1, N) on the triple
+//                                             ("matmul", (R C, 1), (1, N)):  a [R C], b [N], c [R C][N]
+//   Bm [i][a][j] = d[row0 + i] * n[j][a]      spdz_mul "matmul" of d[blk].reshape(R, 1) and n^T.reshape(1, C N) on the triple
+//                                             ("matmul", (R, 1), (1, C N)):  a [R], b [C][N], c [R][C N]
+// With K = 1 a product cell is  z_j = c_j + delta b_j + a_j eps (+ delta eps for j = 0); ring arithmetic is exact, so this is
+// what the two GEMM launches of primia_beaver_matmul_local give, bit for bit.  n [N][C] and d [N] are read where they lie:
+// element [a][j] of n^T is n[j C + a].  Thread (i, j) -- j fastest -- walks the classes: it reads row j of n as C consecutive
+// words, and for each class a wavefront writes 64 consecutive words of A and of Bm; (i, a) sides are uniform in a wavefront.
+__global__ __launch_bounds__(256) void auc_cross_local_kernel(Pair n, Pair d, Triple ta, Triple tb, OutPair A, OutPair Bm, long N,
+                                                              int C, long row0, long R) {
+    const long stride = (long)gridDim.x * 256;
+    for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < R * N; id += stride) {
+        const long i = id / N, j = id - i * N;
+        const u64 eps_a = (d.p0[j] - ta.b0[j]) + (d.p1[j] - ta.b1[j]);                       // open(d - b) of A's product
+        const u64 delta_b = (d.p0[row0 + i] - tb.a0[i]) + (d.p1[row0 + i] - tb.a1[i]);       // open(d[blk] - a) of Bm's
+        const u64 ab0 = ta.b0[j], ab1 = ta.b1[j], ba0 = tb.a0[i], ba1 = tb.a1[i];
+        for (int a = 0; a < C; ++a) {
+            const long ia = i * C + a, in = (row0 + i) * C + a, jn = j * C + a, aj = (long)a * N + j, o = ia * N + j;
+            const u64 delta_a = (n.p0[in] - ta.a0[ia]) + (n.p1[in] - ta.a1[ia]);
+            const u64 eps_b = (n.p0[jn] - tb.b0[aj]) + (n.p1[jn] - tb.b1[aj]);
+            A.p0[o] = ta.c0[o] + delta_a * (ab0 + eps_a) + ta.a0[ia] * eps_a;
+            A.p1[o] = ta.c1[o] + delta_a * ab1 + ta.a1[ia] * eps_a;
+            Bm.p0[o] = tb.c0[o] + delta_b * (tb.b0[aj] + eps_b) + ba0 * eps_b;
+            Bm.p1[o] = tb.c1[o] + delta_b * tb.b1[aj] + ba1 * eps_b;
+        }
+    }
+}
+
+// Step 5 of a row block: U [C][C C] += Y[blk]^T [C][R] @ T [R][C C] for both parties, the confusion step's form with C C
+// columns: spdz_mul "matmul" on the triple ("matmul", (C, R), (R, C C)) -- a [C][R] masks Y^T, b [R][C C] masks T, c [C][C C]
+// -- without truncation.  y: the block's R rows of the shared one-hot labels, row-major (element [p][i] of Y^T is y[i C + p]).
+// Thread (j, p, k) -- k fastest -- forms party j's cell [p][k] over the R rows and adds it to ITS word of U_j.
+__global__ __launch_bounds__(256) void auc_count_combine_local_kernel(Pair y, Pair tt, Triple t, OutPair u, long R, int C) {
+    const int CC = C * C, cells = C * CC;
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id >= 2 * cells) return;
+    const int j = id >= cells;
+    const int cell = j ? id - cells : id;
+    const int p = cell / CC, k = cell - p * CC;
+    const u64* const aj = j ? t.a1 : t.a0;
+    const u64* const bj = j ? t.b1 : t.b0;
+    u64 acc = (j ? t.c1 : t.c0)[cell];
+    for (long i = 0; i < R; ++i) {
+        const long iy = i * C + p, ia = (long)p * R + i, it = i * CC + k;
+        const u64 delta = (y.p0[iy] - t.a0[ia]) + (y.p1[iy] - t.a1[ia]);
+        const u64 eps = (tt.p0[it] - t.b0[it]) + (tt.p1[it] - t.b1[it]);
+        acc += delta * (j ? bj[it] : bj[it] + eps) + aj[ia] * eps;
+    }
+    (j ? u.p1 : u.p0)[cell] += acc;
+}
+
 // ---- batch_norm in eval mode (nn/functional.py:44-75), both parties ---------------------------------------------------
 //   rows = x.permute(1,0,2,3).reshape(C,-1).t()                         [B*HW, C], row b*HW + p
 //   normalized = inv * (rows - mean)     (FPT mul: Beaver + truncation; triple t1: a ~ inv [C], b ~ rows, c ~ rows)
@@ -484,6 +538,40 @@ int primia_confusion_combine_local(const int64_t* y0, const int64_t* y1, const i
     for (const int64_t* q : in) PRIMIA_REQUIRE(q != m0 && q != m1);
     confusion_combine_local_kernel<<<(2 * C * C + 255) / 256, 256, 0, (hipStream_t)st>>>(
         Pair{U(y0), U(y1)}, Pair{U(p0), U(p1)}, Triple{U(a0), U(b0), U(c0), U(a1), U(b1), U(c1)}, OutPair{(u64*)m0, (u64*)m1}, B, C);
+    return launch_status();
+}
+
+int primia_auc_cross_local(const int64_t* n0, const int64_t* n1, const int64_t* d0, const int64_t* d1, const int64_t* const* ta,
+                           const int64_t* const* tb, int64_t* a_out0, int64_t* a_out1, int64_t* b_out0, int64_t* b_out1, int64_t N,
+                           int C, int64_t row0, int64_t R, primia_stream_t st) {
+    PRIMIA_REQUIRE(n0 && n1 && d0 && d1 && ta && tb && a_out0 && a_out1 && b_out0 && b_out1 && N > 0 && C > 0 && C <= 16 &&
+                   row0 >= 0 && R > 0 && R <= N && row0 <= N - R && N <= (1L << 40) / (16 * R));
+    for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(ta[k] && tb[k]);
+    // four output buffers, none of them an input (n and d are read by every thread)
+    int64_t* const out[] = {a_out0, a_out1, b_out0, b_out1};
+    for (int x = 0; x < 4; ++x) {
+        for (int z = x + 1; z < 4; ++z) PRIMIA_REQUIRE(out[x] != out[z]);
+        PRIMIA_REQUIRE(out[x] != n0 && out[x] != n1 && out[x] != d0 && out[x] != d1);
+        for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(out[x] != ta[k] && out[x] != tb[k]);
+    }
+    auc_cross_local_kernel<<<sl_blocks(R * N), 256, 0, (hipStream_t)st>>>(
+        Pair{U(n0), U(n1)}, Pair{U(d0), U(d1)}, Triple{U(ta[0]), U(ta[1]), U(ta[2]), U(ta[3]), U(ta[4]), U(ta[5])},
+        Triple{U(tb[0]), U(tb[1]), U(tb[2]), U(tb[3]), U(tb[4]), U(tb[5])}, OutPair{(u64*)a_out0, (u64*)a_out1},
+        OutPair{(u64*)b_out0, (u64*)b_out1}, (long)N, C, (long)row0, (long)R);
+    return launch_status();
+}
+
+int primia_auc_count_combine_local(const int64_t* y0, const int64_t* y1, const int64_t* t0, const int64_t* t1, const int64_t* a0,
+                                   const int64_t* b0, const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1,
+                                   int64_t* u0, int64_t* u1, int64_t R, int C, primia_stream_t st) {
+    PRIMIA_REQUIRE(y0 && y1 && t0 && t1 && a0 && b0 && c0 && a1 && b1 && c1 && u0 && u1 && R > 0 && C > 0 && C <= 16);
+    // U is updated in place, one word per thread: two buffers, neither of them an input
+    PRIMIA_REQUIRE(u0 != u1);
+    const int64_t* const in[] = {y0, y1, t0, t1, a0, b0, c0, a1, b1, c1};
+    for (const int64_t* q : in) PRIMIA_REQUIRE(q != u0 && q != u1);
+    auc_count_combine_local_kernel<<<(2 * C * C * C + 255) / 256, 256, 0, (hipStream_t)st>>>(
+        Pair{U(y0), U(y1)}, Pair{U(t0), U(t1)}, Triple{U(a0), U(b0), U(c0), U(a1), U(b1), U(c1)}, OutPair{(u64*)u0, (u64*)u1},
+        (long)R, C);
     return launch_status();
 }
 

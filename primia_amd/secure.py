@@ -161,10 +161,13 @@ class Dealer:
                 scratch = torch.empty(M * K + K * N, dtype=I64, device=self.device)
             call("primia_triple_matmul_c1", a0, a1, b0, b1, c0, c1, scratch, M, K, N)
 
-    def dif_keys(self, n):
+    def dif_keys(self, n, bits=None):
+        """bits=None: keys of the dealer's comparison width; a value: keys of that width -- the same keystream words are drawn,
+        the width decides their reduction and the number of levels (the rank comparisons of an evaluation with a ROC AUC
+        are 64 bits wide whatever the dealer's width, SecureContext.auc_counts)."""
         if self.requests is not None:
-            self.requests.append(("dif_keys", (n,), {}))
-        dev, w = self.device, self.fss_bits
+            self.requests.append(("dif_keys", (n,), {} if bits is None else {"bits": int(bits)}))
+        dev, w = self.device, self.fss_bits if bits is None else check_fss_bits(bits)
         # raw keystream words, then build_fss_keys' arithmetic in place (primia_fss_alpha_split): alpha and its mask r below
         # 2^32 (mpc/fss.py:346, mpc/primitives.py:249), word 0 of each seed 63 bits (randbit, fss.py:495-501), and
         # primitives.py:249-251: party 0 receives (alpha - mask) mod 2^32, party 1 the mask (2^fss_bits at another width: the
@@ -247,7 +250,7 @@ class PreloadedDealer:
     def triple(self, op, xshape, yshape):
         return self._next()
 
-    def dif_keys(self, n):
+    def dif_keys(self, n, bits=None):
         return self._next()
 
     def dpf_keys(self, n):
@@ -498,30 +501,37 @@ class SecureContext:
         return self.trunc(self.beaver_matmul(x, y), self.scale)
 
     # ---- FSS comparison ------------------------------------------------------------------------------
-    def _le_local(self, x1, x2, n, shape, cols1=(1, 0), cols2=(1, 0), length=1):
+    def _dif_keys(self, n, bits):
+        """(keys, width) of n comparisons: the dealer's width, or `bits` when the caller fixes one."""
+        if bits is None:
+            return self.dealer.dif_keys(n), self.fss_bits
+        return self.dealer.dif_keys(n, bits=bits), check_fss_bits(bits)
+
+    def _le_local(self, x1, x2, n, shape, cols1=(1, 0), cols2=(1, 0), length=1, bits=None):
         """fss.le with both parties here: mask_builder, the open and both DIF evaluations in one launch.  x1 = None stands
-        for shares of zero; colsK = (row width, first column) when operand K is a column range of a matrix."""
-        keys = self.dealer.dif_keys(n)
+        for shares of zero; colsK = (row width, first column) when operand K is a column range of a matrix; bits: a width
+        other than the dealer's."""
+        keys, w = self._dif_keys(n, bits)
         out = _pair(shape, x2[0].device)
         k0, k1 = keys
-        fss_call("dif_eval_local", self.fss_bits, None if x1 is None else x1[0], None if x1 is None else x1[1], cols1[0], cols1[1],
+        fss_call("dif_eval_local", w, None if x1 is None else x1[0], None if x1 is None else x1[1], cols1[0], cols1[1],
                  x2[0], x2[1], cols2[0], cols2[1], length, k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"],
                  k0["cw_sigma"], k0["cw_s"], k0["cw_leaf"], out[0], out[1], n)
         self.stats["dif_evals"] += n
         return out
 
-    def le(self, x1, x2):
-        """fss.le(x1, x2) (mpc/fss.py:97-185, 279): int64 shares of the bit [x1 <= x2]."""
+    def le(self, x1, x2, bits=None):
+        """fss.le(x1, x2) (mpc/fss.py:97-185, 279): int64 shares of the bit [x1 <= x2], compared at the dealer's width or at
+        `bits` (requested as dif_keys(n, bits=bits))."""
         xr = self._ref(x1)
         n = xr.numel()
         if self._local:
-            return self._le_local(x1, x2, n, tuple(xr.shape))
-        keys = self.dealer.dif_keys(n)
+            return self._le_local(x1, x2, n, tuple(xr.shape), bits=bits)
+        keys, w = self._dif_keys(n, bits)
         r = [None, None]
         for j in self.parties:  # mask_builder
             r[j] = _empty_like(xr)
             call("primia_fss_mask", x1[j], x2[j], keys[j]["alpha"], r[j], n)
-        w = self.fss_bits
         masked = torch.empty(n, dtype=masked_dtype(w), device=xr.device)
         if self.party is None:
             fss_call("fss_open", w, r[0], r[1], masked, n)
@@ -671,7 +681,7 @@ class SecureContext:
             cache[key] = torch.arange(C, dtype=I64).repeat(B, 1).contiguous().to(device)
         return cache[key]
 
-    def confusion(self, logits, labels_onehot, acc):
+    def confusion(self, logits, labels_onehot, acc, kept=None):
         """One pass of an encrypted evaluation (defined by tests/secure_confusion_nets.py's oracle_confusion, not
         pinned against the reference, which opens the predictions): acc += Y^T @ onehot(argmax(logits)) on shares, nothing
         opened but masked operands.  logits: shares [B, C]; labels_onehot: the data owner's raw int64 one-hot labels [B, C]
@@ -683,7 +693,9 @@ class SecureContext:
           P    = eq(Ib, Kmat)                          dpf_keys(B * C)
           acc += beaver_matmul(Y^T, P)                 triple ("matmul", (C, B), (B, C)), no truncation
         Both parties here: primia_dpf_eval_local and primia_confusion_combine_local (Y is read row-major, no transposed
-        copy); otherwise the step-by-step chain -- same requests, same bits.  Returns the shares of P (tests)."""
+        copy); otherwise the step-by-step chain -- same requests, same bits.  Returns the shares of P (tests).
+        kept: a list that receives this pass's (logits, Y) shares, copied party-locally (reveal="metrics": the rank-count
+        tail after the last pass reads them; the requests are unchanged)."""
         xr = self._ref(logits)
         B, C = xr.shape
         dev = xr.device
@@ -694,6 +706,8 @@ class SecureContext:
             Y = self.share(labels_onehot.contiguous(), owner=1)
         else:
             Y = self.share(None, owner=1, shape=(B, C))
+        if kept is not None:
+            kept.append((self._copy(logits), self._copy(Y)))
         Kmat = self.share(self._class_grid(B, C, dev))
         zero = self._const(0, dev, C * B)
         rows = self.add(self._each(lambda j: zero), I)                  # [C, B]: every row is I
@@ -710,6 +724,103 @@ class SecureContext:
             call("primia_ring_add", acc[j], Mc[j], o, C * C, C * C)
             acc[j].copy_(o)
         return P
+
+    def _copy(self, x):
+        """A party-local copy of shares, by the library's own copy (a ring scale by 1)."""
+        def one(j):
+            src = x[j].contiguous()
+            o = _empty_like(src)
+            call("primia_ring_scale", src, 1, o, src.numel())
+            return o
+
+        return self._each(one)
+
+    def auc_counts(self, logits, labels_onehot, U, block_rows=None):
+        """The rank counts of the reference's one-vs-one ROC AUC over all rows of an encrypted evaluation (DESIGN.md §4;
+        defined by tests/secure_auc_nets.py's oracle_auc_counts, not pinned against the reference, which computes the AUC on
+        opened scores): U[p][a][q] += #{(i, j): label(i) = p, label(j) = q, p_a(i) <= p_a(j)} on shares, for the
+        min-shifted, row-normalised scores p_a = n_a / d -- nothing opened but masked operands.  logits: shares of the
+        fixed-point logits [N, C] of every row held; labels_onehot: SHARES of the raw one-hot labels [N, C] (all-zero rows
+        for padding images), the ones the confusion tail made; U: shares [C, C, C], updated IN PLACE.  Raw int64, no scale.
+          Vn  = argmax(-L, values=True)[1]             the class form's walk and requests on -L, its index dropped
+          n   = L + Vn[:, None];  d = rowsum(n)        party-local (n^T = L^T + Vn, then transposed back)
+          per block of Rb = auc_block_rows(N, C) rows (the last ragged), R rows `blk`:
+            A  = beaver_matmul(n[blk] [R C, 1], d [1, N])          triple ("matmul", (R C, 1), (1, N))
+            Bm = beaver_matmul(d[blk] [R, 1], n^T [1, C N])        triple ("matmul", (R, 1), (1, C N))
+            G  = le(A, Bm, bits=64) [R, C, N]                      dif_keys(R C N, bits=64): [p_a(i) <= p_a(j)], exact
+            T  = beaver_matmul(G [R C, N], Y)                      triple ("matmul", (R C, N), (N, C))
+            U += beaver_matmul(Y[blk]^T [C, R], T [R, C C])        triple ("matmul", (C, R), (R, C C))
+        The rank comparisons are 64 bits wide whatever the dealer's width: their operands are products of two fixed-point
+        values.  The products must stay below 2^63 (pf 3 and 6 with |logit| < 50; at pf 16 they wrap).  A row of all-equal
+        logits has d = 0 and ties with every row.
+        Both parties here: primia_auc_cross_local (A and Bm in one launch, n and d read in place), primia_dif_eval_local_n,
+        primia_beaver_matmul_local and primia_auc_count_combine_local; otherwise the step-by-step chain, which a three-role
+        run executes -- same requests, same bits."""
+        xr = self._ref(logits)
+        if xr.dim() != 2 or tuple(self._ref(labels_onehot).shape) != tuple(xr.shape):
+            raise ValueError(f"auc_counts takes logits and one-hot label shares [N, classes], got {tuple(xr.shape)}")
+        N, C = xr.shape
+        if tuple(self._ref(U).shape) != (C, C, C):
+            raise ValueError(f"auc_counts adds into shares [{C}, {C}, {C}]")
+        Rb = auc_block_rows(N, C) if block_rows is None else int(block_rows)
+        if Rb < 1:
+            raise ValueError("block_rows must be at least 1")
+        L = self._each(lambda j: logits[j].contiguous())
+        Y = self._each(lambda j: labels_onehot[j].contiguous())
+        _, Vn = self.argmax(self.neg(L), values=True)
+        nT = self.add(self._each(lambda j: _transposed(L[j], N, C)), Vn)      # [C, N]: L^T - min, the minimum broadcast
+        n = self._each(lambda j: _transposed(nT[j], C, N))                    # [N, C]
+
+        def rowsum(j):
+            o = torch.empty(N, dtype=I64, device=xr.device)
+            call("primia_ring_rowsum", n[j], o, N, C)
+            return o
+
+        d = self._each(rowsum)
+        for r0 in range(0, N, Rb):
+            R = min(Rb, N - r0)
+            Yb = self._each(lambda j: Y[j][r0:r0 + R])
+            if self._local:
+                ta = self.dealer.triple("matmul", (R * C, 1), (1, N))
+                tb = self.dealer.triple("matmul", (R, 1), (1, C * N))
+                A, Bm = _pair((R, C, N), xr.device), _pair((R, C, N), xr.device)
+                call("primia_auc_cross_local", n[0], n[1], d[0], d[1], _ptr_table(ta), _ptr_table(tb), A[0], A[1], Bm[0], Bm[1],
+                     N, C, r0, R)
+                self.stats["beaver_matmul"] += 2
+                G = self._le_local(A, Bm, R * C * N, (R, C, N), bits=AUC_BITS)
+                T = self.beaver_matmul([g.view(R * C, N) for g in G], Y)
+                t = self.dealer.triple("matmul", (C, R), (R, C * C))
+                call("primia_auc_count_combine_local", Yb[0], Yb[1], T[0], T[1], *_six(t), U[0], U[1], R, C)
+                self.stats["beaver_matmul"] += 1
+                continue
+            A = self.beaver_matmul(self._each(lambda j: n[j][r0:r0 + R].reshape(R * C, 1)), self._each(lambda j: d[j].view(1, N)))
+            Bm = self.beaver_matmul(self._each(lambda j: d[j][r0:r0 + R].reshape(R, 1)), self._each(lambda j: nT[j].view(1, C * N)))
+            G = self.le(self._each(lambda j: A[j].view(R, C, N)), self._each(lambda j: Bm[j].view(R, C, N)), bits=AUC_BITS)
+            T = self.beaver_matmul(self._each(lambda j: G[j].view(R * C, N)), Y)
+            Uc = self.beaver_matmul(self._each(lambda j: _transposed(Yb[j], R, C)), self._each(lambda j: T[j].view(R, C * C)))
+            for j in self.parties:      # (out of place, then back into the accumulator's own buffer)
+                o = _empty_like(U[j])
+                call("primia_ring_add", U[j], Uc[j], o, C * C * C, C * C * C)
+                U[j].copy_(o)
+        return U
+
+    def auc_open(self, M, U):
+        """The opening of an evaluation with a ROC AUC: each party zeroes its shares of the entries U[p][a][q] the score does
+        not read -- those with (p == a) == (q == a) -- by a ring product with a public 0 / 1 tensor; then M [C, C] and
+        U [C, C, C] are reconstructed through the context's opener, to both parties.  -> (M, U)."""
+        C = self._ref(M).shape[0]
+        cache = self.__dict__.setdefault("_consts", {})
+        dev = self._ref(U).device
+        key = ("auc_needed", C, str(dev))
+        if key not in cache:
+            cache[key] = auc_needed(C).to(I64).to(dev)
+
+        def masked(j):
+            o = _empty_like(U[j])
+            call("primia_ring_mul", U[j].contiguous(), cache[key], o, C * C * C, C * C * C)
+            return o
+
+        return self.reconstruct(M), self.reconstruct(self._each(masked))
 
     def _stack2(self, a, b, n):
         """stack([a, b], axis=1) of two [n] vectors, per share: [n, 2]."""
@@ -1056,12 +1167,36 @@ def _check_pooling(pooling):
 
 REVEALS = ("logits", "class")      # what a pass of an inference may open, per image
 CONFUSION = "confusion"            # an evaluation on labelled images: nothing per image, the confusion matrix at the end
-EVALUATION_REVEALS = REVEALS + (CONFUSION,)
+METRICS = "metrics"                # the same evaluation, which also opens the rank counts of the reference's ROC AUC
+EVALUATION_REVEALS = REVEALS + (CONFUSION, METRICS)
+ACCUMULATING = (CONFUSION, METRICS)
+
+# The rank comparisons of the ROC AUC tail (SecureContext.auc_counts) are 64 bits wide whatever the dealer's
+# width -- the mirror image of the equality test fixed at 32: their operands are products of two fixed-point values, whose
+# difference reaches about 2^28 at precision_fractional = 3.  They are made in blocks of rows of at most this many.
+AUC_BITS = 64
+AUC_BLOCK_COMPARISONS = 2 ** 20
+
+
+def auc_block_rows(rows, classes):
+    """Rows per block of the rank-count tail over `rows` rows: a public function of public sizes, and part of the layer's
+    definition -- the order of the dealer's requests depends on it."""
+    N, C = int(rows), int(classes)
+    return max(1, min(N, AUC_BLOCK_COMPARISONS // (C * N)))
+
+
+def auc_needed(classes):
+    """bool [C, C, C]: the entries U[p][a][q] the one-vs-one AUC reads -- exactly one of p, q is the score column a."""
+    k = torch.arange(int(classes))
+    pa, qa = (k[:, None, None] == k[None, :, None]), (k[None, None, :] == k[None, :, None])
+    return pa != qa
 
 
 def _check_reveal(reveal):
     """What a pass opens: "logits", the full score vector (the reference's behaviour), "class", the argmax alone, or
-    "confusion": nothing -- the passes of an evaluation add into a shared confusion matrix, which is opened after the last."""
+    "confusion": nothing -- the passes of an evaluation add into a shared confusion matrix, which is opened after the last;
+    "metrics": the same passes, which also keep their logit and label shares for the rank counts of the ROC AUC, opened
+    with the matrix."""
     if reveal not in EVALUATION_REVEALS:
         raise ValueError(f"reveal must be one of {EVALUATION_REVEALS}, got {reveal!r}")
     return reveal
@@ -1130,7 +1265,12 @@ class SecureResNet18:
 
     reveal="confusion" scores the model on labelled images: `begin()`, then passes with the data owner's labels, each ending
     with `SecureContext.confusion` and returning nothing, then `finish()`, which opens the confusion matrix -- to both parties
-    -- and nothing else: no logit, no class, no label.  The class form's request list is a strict prefix of this one's."""
+    -- and nothing else: no logit, no class, no label.  The class form's request list is a strict prefix of this one's.
+
+    reveal="metrics" is that evaluation with the reference's third overall figure, the one-vs-one ROC AUC: the passes are the
+    confusion passes, requests included, and keep their logit and label shares; `finish()` runs `SecureContext.auc_counts`
+    over every row held and opens the matrix and the rank counts U [C, C, C] -- `(M, U)`, to both parties -- and nothing per
+    image; `torchlib_compat.auc_from_rank_counts(U, M.sum(1))` is the score."""
 
     def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max",
                  norm=None, reveal="logits"):
@@ -1163,24 +1303,62 @@ class SecureResNet18:
                 self.p[k] = ctx.share(ctx.encode(v.to(dev)), owner=0)
             else:
                 self.p[k] = ctx.share(None, owner=0, shape=v.shape)
-        self.acc = None
-        if self.reveal == CONFUSION:
-            self.classes = int(state_dict["fc.weight"].shape[0])
-            self.acc = ctx._each(lambda j: torch.zeros(self.classes, self.classes, dtype=I64).to(dev))
+        self.acc = self.U = self.kept = None
+        if self.reveal in ACCUMULATING:
+            self.classes = C = int(state_dict["fc.weight"].shape[0])
+            self.acc = ctx._each(lambda j: torch.zeros(C, C, dtype=I64).to(dev))
+        if self.reveal == METRICS:
+            self.U = ctx._each(lambda j: torch.zeros(C, C, C, dtype=I64).to(dev))
+            self.kept = []      # per pass: (logit shares, one-hot label shares) [B, classes], padding rows included
 
     def begin(self):
-        """Start an evaluation: the shares of the confusion matrix are zeroed."""
-        if self.reveal != CONFUSION:
-            raise ValueError('begin() belongs to reveal="confusion"')
+        """Start an evaluation: the shares of the confusion matrix are zeroed (reveal="metrics": those of the rank counts
+        too, and the rows kept from earlier passes are dropped)."""
+        if self.reveal not in ACCUMULATING:
+            raise ValueError('begin() belongs to reveal="confusion" and "metrics"')
         for j in self.ctx.parties:
             self.acc[j].zero_()
+            if self.U is not None:
+                self.U[j].zero_()
+        if self.kept is not None:
+            self.kept = []
 
-    def finish(self):
+    def held_rows(self):
+        """reveal="metrics": (L, Y), the logit and one-hot label shares [N, classes] of every row since begin(), all passes
+        side by side (by the library's own copy)."""
+        c = self.ctx
+        if not self.kept:
+            raise ValueError('reveal="metrics": no pass since begin()')
+        total = sum(c._ref(l).shape[0] for l, _ in self.kept)
+
+        def cat(which):
+            def one(j):
+                out = torch.empty(total, self.classes, dtype=I64, device=self.kept[0][which][j].device)
+                off = 0
+                for entry in self.kept:
+                    v = entry[which][j]
+                    call("primia_ring_scale", v, 1, out[off:off + v.shape[0]], v.numel())
+                    off += v.shape[0]
+                return out
+
+            return c._each(one)
+
+        return cat(0), cat(1)
+
+    def finish(self, ctx=None, block_rows=None):
         """End an evaluation: open the confusion matrix -- int64 [classes, classes], row = label, column = predicted class --
-        through the context's opener, which hands it to both parties."""
-        if self.reveal != CONFUSION:
-            raise ValueError('finish() belongs to reveal="confusion"')
-        return self.ctx.reconstruct(self.acc)
+        through the context's opener, which hands it to both parties.
+        reveal="metrics": first the rank-count tail over every row held (`SecureContext.auc_counts`, on `ctx` when the
+        passes ran on a context whose dealer cannot serve it: the graphed form's), then the matrix AND the counts are
+        opened, nothing else: -> (M, U), U int64 [classes, classes, classes] (torchlib_compat.auc_from_rank_counts)."""
+        if self.reveal not in ACCUMULATING:
+            raise ValueError('finish() belongs to reveal="confusion" and "metrics"')
+        if self.reveal == CONFUSION:
+            return self.ctx.reconstruct(self.acc)
+        c = self.ctx if ctx is None else ctx
+        L, Y = self.held_rows()
+        c.auc_counts(L, Y, self.U, block_rows)
+        return c.auc_open(self.acc, self.U)
 
     def onehot(self, labels, batch):
         """int64 labels [n <= batch] -> raw int64 one-hot [batch, classes] on the device, the rows past n all zero (padding
@@ -1277,7 +1455,8 @@ class SecureResNet18:
         reveal="class": -> int64 [B] class indices, the only value the pass reconstructs; in a distributed run party 0 sends
         its share of them to party 1, which returns the classes, and returns None itself.
         reveal="confusion": `labels` are the data owner's int64 labels [n <= B] of the first n images (the rest are padding and
-        count nowhere); party 0 passes none.  The pass adds into the shared confusion matrix and returns None."""
+        count nowhere); party 0 passes none.  The pass adds into the shared confusion matrix and returns None.
+        reveal="metrics": the confusion pass, requests included; its logit and label shares are kept for `finish()`."""
         c = self.ctx
         if c.party in (None, 1):
             xs = c.share(c.encode(image), owner=1)
@@ -1285,13 +1464,13 @@ class SecureResNet18:
             cin = c._ref(self.p["conv1.weight"]).shape[1]        # 3 (pretrained) or 1 (train.py:262)
             xs = c.share(None, owner=1, shape=(int(batch), cin, self.input_size, self.input_size))
         out = self.forward_shares(xs)
-        if self.reveal == CONFUSION:
+        if self.reveal in ACCUMULATING:
             y = None
             if c.party in (None, 1):
                 if labels is None:
-                    raise ValueError('reveal="confusion": the data owner passes the labels of the images')
+                    raise ValueError(f'reveal="{self.reveal}": the data owner passes the labels of the images')
                 y = self.onehot(labels, c._ref(out).shape[0])
-            c.confusion(out, y, self.acc)
+            c.confusion(out, y, self.acc, kept=self.kept)
             return None
         if self.reveal == "class":
             return c.open_to(c.argmax(out), to=1)
@@ -1325,6 +1504,21 @@ def confusion_requests(batch, classes):
             ("triple", ("matmul", (C, B), (B, C)), {})]
 
 
+def auc_requests(rows, classes, block_rows=None):
+    """What `SecureContext.auc_counts` requests over `rows` rows (all passes, padding rows included): the argmax walk on
+    the negated logits, then per block of rows the two K = 1 product triples, the keys of R * C * N comparisons at 64 bits,
+    and the triples of the two counting products."""
+    N, C = int(rows), int(classes)
+    Rb = auc_block_rows(N, C) if block_rows is None else int(block_rows)
+    req = argmax_requests(N, C)
+    for r0 in range(0, N, Rb):
+        R = min(Rb, N - r0)
+        req += [("triple", ("matmul", (R * C, 1), (1, N)), {}), ("triple", ("matmul", (R, 1), (1, C * N)), {}),
+                ("dif_keys", (R * C * N,), {"bits": AUC_BITS}), ("triple", ("matmul", (R * C, N), (N, C)), {}),
+                ("triple", ("matmul", (C, R), (R, C * C)), {})]
+    return req
+
+
 def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits"):
     """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
     `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
@@ -1336,7 +1530,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     An architecture without running statistics is the GroupNorm network: no hoisted Newton; every norm site requests its
     square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples.
     reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix).
-    reveal="confusion": the confusion tail's requests follow the argmax tail's (the class form's list is a strict prefix)."""
+    reveal="confusion": the confusion tail's requests follow the argmax tail's (the class form's list is a strict prefix).
+    reveal="metrics": the confusion list (the rank-count tail runs once, after the last pass: auc_requests)."""
     _check_pooling(pooling)
     _check_reveal(reveal)
     B, req = int(batch), []
@@ -1410,7 +1605,7 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     triple("matmul", (B, feat), (feat, classes))
     if reveal != "logits":
         req += argmax_requests(B, classes)
-    if reveal == CONFUSION:
+    if reveal in ACCUMULATING:
         req += confusion_requests(B, classes)
     return req
 
@@ -1441,15 +1636,16 @@ DPF_KEY_BYTES = _dpf_key_bytes()
 
 
 def primitive_bytes(requests, fss_bits=FSS_BITS):
-    """Device bytes of the primitives a request list stands for (both parties' halves), its comparison keys at `fss_bits`."""
+    """Device bytes of the primitives a request list stands for (both parties' halves), its comparison keys at `fss_bits`
+    (a request that names a width of its own, {"bits": n}: at that width)."""
     key_bytes = DIF_KEY_BYTES(fss_bits)
     numel = lambda shape: int(torch.Size(shape).numel())
     total = 0
-    for kind, args, _ in requests:
+    for kind, args, kw in requests:
         if kind == "const_mask":
             total += 8 * numel(args)
         elif kind == "dif_keys":
-            total += key_bytes * args[0]
+            total += (DIF_KEY_BYTES(kw["bits"]) if "bits" in kw else key_bytes) * args[0]
         elif kind == "dpf_keys":
             total += DPF_KEY_BYTES * args[0]
         else:
@@ -1508,6 +1704,10 @@ class GraphedSecureInference:
     reveal="class": the argmax tail is part of the captured graph and the static output is the int64 [batch] buffer of class
     indices; nothing else is reconstructed.
 
+    reveal="metrics": the captured pass is the confusion pass; it leaves copies of its logit and label shares in buffers of
+    the graph, which are copied out after each replay, and `finish()` runs the rank-count tail eagerly (its primitives come
+    from a dealer of the tail's own, seeded apart under a debug seed) before it opens the matrix and the counts.
+
     reveal="confusion": the confusion tail is part of the captured graph too; the one-hot labels are a static int64
     [batch, classes] buffer next to the images (`load` zero-fills the rows of padding images), the shares of the confusion
     matrix a static buffer the captured pass adds into; `begin()` zeroes it, `finish()` opens it, a pass returns None.
@@ -1537,7 +1737,7 @@ class GraphedSecureInference:
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
         self.image = torch.zeros(self.batch, state_dict["conv1.weight"].shape[1], input_size, input_size, dtype=torch.float32).to(self.device)
         self.labels = None
-        if reveal == CONFUSION:      # (all-zero one-hot rows: the warm-up images are padding)
+        if reveal in ACCUMULATING:      # (all-zero one-hot rows: the warm-up images are padding)
             self.labels = torch.zeros(self.batch, int(state_dict["fc.weight"].shape[0]), dtype=I64).to(self.device)
         self.dealer = Dealer(self.device, seed, self.fss_bits)
         self.dealer.tape, self.dealer.requests = [], []
@@ -1561,6 +1761,14 @@ class GraphedSecureInference:
             with torch.cuda.graph(self.graph, stream=side):
                 self.out = self._model(self.image, labels=self.labels)
         torch.cuda.current_stream().wait_stream(side)
+        self._static_rows = self._tail_ctx = None
+        if reveal == METRICS:
+            # the captured pass left its copies of the logit and label shares in buffers of the graph's own: every replay
+            # rewrites them, and __call__ copies them out.  The tail runs eagerly after the last pass, on a dealer of its
+            # own (this form's dealer draws on the device from here on, inside the refill graph)
+            self._static_rows = self._model.kept[-1]
+            self._tail_ctx = SecureContext(Dealer(self.device, None if seed is None else seed + 104729, self.fss_bits), base,
+                                           precision_fractional)
         # the provider's block counter moves to the device, behind everything the offline pass drew
         self._ctr = torch.tensor([self.dealer._block], dtype=I64).to(self.device)      # (uploaded: no fill kernel)
         self.dealer._block = None                      # (the host counter is dead from here on: rand64 would raise)
@@ -1575,15 +1783,19 @@ class GraphedSecureInference:
                 with torch.cuda.graph(self._refill_g, stream=side):
                     self._refill_launches()
             torch.cuda.current_stream().wait_stream(side)
-        if reveal == CONFUSION:
+        if reveal in ACCUMULATING:
             self.begin()                               # (the warm-up passes added shares of zero)
 
     def begin(self):
-        """Start an evaluation: zero the static shares of the confusion matrix."""
+        """Start an evaluation: zero the static shares of the confusion matrix (reveal="metrics": and of the rank counts, and
+        drop the rows kept)."""
         self._model.begin()
 
-    def finish(self):
-        """Open the confusion matrix of the passes since begin(): int64 [classes, classes], row = label."""
+    def finish(self, block_rows=None):
+        """Open the confusion matrix of the passes since begin(): int64 [classes, classes], row = label.
+        reveal="metrics": run the rank-count tail eagerly over the rows the passes left, then open -> (M, U)."""
+        if self.reveal == METRICS:
+            return self._model.finish(ctx=self._tail_ctx, block_rows=block_rows)
         return self._model.finish()
 
     def _rehome_tape(self):
@@ -1682,7 +1894,7 @@ class GraphedSecureInference:
         are zero-filled."""
         if self.labels is not None:
             if labels is None or labels.numel() != image.shape[0]:
-                raise ValueError('reveal="confusion": one label per image')
+                raise ValueError(f'reveal="{self.reveal}": one label per image')
             self.labels.copy_(self._model.onehot(labels, self.batch))
         if self.batch == 1:
             self.image.copy_(image)
@@ -1697,7 +1909,7 @@ class GraphedSecureInference:
 
     def rows(self, n):
         """The first n rows of the static output (all of it, the very buffer, for a full batch)."""
-        if self.out is None:      # reveal="confusion": a pass returns nothing
+        if self.out is None:      # reveal="confusion" / "metrics": a pass returns nothing
             return None
         return self.out if n == self.batch else self.out[:n]
 
@@ -1710,6 +1922,8 @@ class GraphedSecureInference:
             self.refill()
         n = self.load(image, labels)
         self.graph.replay()
+        if self._static_rows is not None:
+            self._model.kept.append(tuple(self._ctx._copy(t) for t in self._static_rows))
         return self.rows(n)
 
 
@@ -1728,8 +1942,8 @@ class PipelinedSecureInference:
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
                  batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS):
         self.device = torch.device(device)
-        if reveal == CONFUSION:
-            raise ValueError('reveal="confusion" accumulates in one set of static buffers: use GraphedSecureInference')
+        if reveal in ACCUMULATING:
+            raise ValueError(f'reveal="{reveal}" accumulates in one set of static buffers: use GraphedSecureInference')
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
                                              None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling,
                                              reveal=reveal, fss_bits=fss_bits)
@@ -1843,10 +2057,11 @@ class PartyDealer:
         f = self.link.from_dealer
         return self._mine((f(xshape), f(yshape), f(_triple_c_shape(op, xshape, yshape))))
 
-    def dif_keys(self, n):
+    def dif_keys(self, n, bits=None):
         f = self.link.from_dealer
         k = dict(alpha=f((n,)), s0=f((2, n)))
-        for name, (shape, dt) in zip(("bits", "cw_sigma", "cw_s", "cw_leaf"), dif_key_fields(n, self.fss_bits)):
+        w = self.fss_bits if bits is None else check_fss_bits(bits)
+        for name, (shape, dt) in zip(("bits", "cw_sigma", "cw_s", "cw_leaf"), dif_key_fields(n, w)):
             k[name] = f(shape, dt, private=False)
         return self._mine(k)
 
@@ -1916,6 +2131,8 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     the extended schedule.
     reveal="confusion": party 1 also passes `labels`, int64 [n_images]; every pass ends with the confusion tail, after the last
     the confusion matrix is opened between the parties, and both return it (int64 [classes, classes]); the dealer returns None.
+    reveal="metrics": the same passes; after the last the dealer serves auc_requests(passes * batch, classes), the parties run
+    the rank-count tail and both return (M, U).
     fss_bits: the width of the comparisons, known to all three like the schedule."""
     _check_pooling(pooling)
     _check_reveal(reveal)
@@ -1927,6 +2144,8 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         svc.serve(model_requests(arch))
         for _ in range(passes):
             svc.serve(image_req)
+        if reveal == METRICS:      # the rank-count tail over every row held, padding rows included
+            svc.serve(auc_requests(passes * batch, arch["fc.weight"][0]))
         return None
     ctx = party_context(link, precision_fractional, base, fss_bits)
     if link.role == 0:
@@ -1938,7 +2157,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
             raise ValueError("party 1 is the data owner: it needs the images")
         shapes = {k: torch.empty(shape, device="meta") for k, shape in arch.items()}
     model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling, reveal=reveal)
-    if reveal == CONFUSION:
+    if reveal in ACCUMULATING:
         if link.role == 1 and (labels is None or labels.numel() != n_images):
             raise ValueError("party 1 is the data owner: it needs one label per image")
         model.begin()
@@ -1950,9 +2169,9 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
             chunk = images[i:i + n]
             if n < batch:
                 chunk = torch.cat([chunk, chunk.new_zeros((batch - n,) + tuple(chunk.shape[1:]))])
-        res = model(chunk, batch=batch, labels=labels[i:i + n] if reveal == CONFUSION and link.role == 1 else None)
+        res = model(chunk, batch=batch, labels=labels[i:i + n] if reveal in ACCUMULATING and link.role == 1 else None)
         if res is not None:
             out.append(res if n == batch else res[:n])
-    if reveal == CONFUSION:
+    if reveal in ACCUMULATING:
         return model.finish()
     return None if reveal == "class" and link.role == 0 else out

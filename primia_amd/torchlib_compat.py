@@ -401,6 +401,34 @@ def confusion_mcc(conf_matrix):
     return float(num / den) if den > 0 else 0.0
 
 
+def auc_from_rank_counts(U, label_counts):
+    """The reference's ROC AUC (torchlib/utils.py:1418-1431: roc_auc_score(..., multi_class="ovo") on the min-shifted,
+    row-normalised logits) from rank counts alone -- what an encrypted evaluation with reveal="metrics" opens.
+    U [C, C, C]: U[p][a][q] = the number of (image i of label p, image j of label q) with score_a(i) <= score_a(j); only the
+    entries where exactly one of p, q equals a are read.  label_counts [C]: images per label (the confusion matrix's row
+    sums).  With class a positive against class b on column a, ties counting one half,
+        AUC(a|b) = 1/2 + (U[b][a][a] - U[a][a][b]) / (2 n_a n_b),
+    and the score is the mean over pairs a < b of (AUC(a|b) + AUC(b|a)) / 2; two classes: AUC(1|0), the binary form.
+    A class without a labelled image leaves the score undefined: 0.0, with the reference's warning."""
+    import sys
+
+    import numpy as np
+
+    U = np.asarray(U)
+    n = [int(v) for v in np.asarray(label_counts).reshape(-1)]
+    C = len(n)
+    if U.shape != (C, C, C):
+        raise ValueError(f"rank counts [{C}, {C}, {C}] go with {C} label counts, got {U.shape}")
+    if C < 2 or min(n) <= 0:
+        print("ROC AUC score could not be calculated and was set to zero.", file=sys.stderr)
+        return 0.0
+    one = lambda a, b: 0.5 + (int(U[b, a, a]) - int(U[a, a, b])) / (2 * n[a] * n[b])
+    if C == 2:
+        return float(one(1, 0))
+    pairs = [(a, b) for a in range(C) for b in range(a + 1, C)]
+    return float(sum((one(a, b) + one(b, a)) / 2 for a, b in pairs) / len(pairs))
+
+
 def confusion_report(conf_matrix):
     """What stats_table reads of sklearn's classification_report(output_dict=True, zero_division=0), from the confusion
     matrix alone (row = label, column = prediction): per class recall, precision, F1 and support, their macro and

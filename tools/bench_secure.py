@@ -9,6 +9,9 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    launch and one select launch on `batch` elements; the report names it)
     --reveal confusion (with --batch): the passes of an encrypted evaluation -- the argmax, then batch * classes equality tests and
                    one [C, B] x [B, C] Beaver product into the shared confusion matrix; seeded labels, nothing opened per pass
+    --reveal metrics --eval_images N (with --batch): the confusion passes over N seeded images, then the rank-count tail of the
+                   ROC AUC on its own -- classes * N^2 comparisons at 64 bits -- timed with its dealer and on pre-provisioned
+                   primitives, next to the same run's per-image online time
     --fss_bits N:  the width of the comparisons, 32 (default, the reference's) to 64: N levels per key and per evaluation (the
                    report names it when it is not 32)"""
 import argparse, json, os, sys, time
@@ -29,9 +32,12 @@ def main():
                     help="the stem pool of the served network (a checkpoint's pooling_type); the report names it when it is avg")
     ap.add_argument("--norm", choices=("batch", "group"), default="batch",
                     help="group: a synthetic GroupNorm(32, C) state dict, no running statistics (the report names it)")
-    ap.add_argument("--reveal", choices=("logits", "class", "confusion"), default="logits",
+    ap.add_argument("--reveal", choices=("logits", "class", "confusion", "metrics"), default="logits",
                     help="class: the passes end with SecureContext.argmax and open the predicted class only (the report names it); "
-                         "confusion (with --batch): the passes of an encrypted evaluation, which add into the shared confusion matrix")
+                         "confusion (with --batch): the passes of an encrypted evaluation, which add into the shared confusion matrix; "
+                         "metrics (with --batch): those passes, then the rank-count tail of the ROC AUC over --eval_images images")
+    ap.add_argument("--eval_images", type=int, default=624,
+                    help="--reveal metrics: the images of the evaluation whose tail is timed (default 624)")
     ap.add_argument("--fss_bits", type=int, default=32,
                     help="the width of the DIF comparisons (32..64): key bytes and DIF kernel time grow linearly with it (the report "
                          "names it when it is not 32)")
@@ -40,8 +46,8 @@ def main():
     ap.add_argument("--only-fss-roofline", action="store_true",
                     help="run the DIF keygen / eval kernels alone (the command the rocprofv3 --pmc passes of tools/pmc_secure.sh wrap)")
     a = ap.parse_args()
-    if a.reveal == "confusion" and not (a.batch and not a.only_fss_roofline):
-        ap.error("--reveal confusion is timed in the serving form: pass --batch N")
+    if a.reveal in ("confusion", "metrics") and not (a.batch and not a.only_fss_roofline):
+        ap.error(f"--reveal {a.reveal} is timed in the serving form: pass --batch N")
 
 
     def cpu_sample_timings():
@@ -176,7 +182,7 @@ def main():
         free = torch.cuda.mem_get_info(dev)[0]
         gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw, **reveal_kw, **bits_kw)
         # (an evaluation's passes carry the data owner's labels: seeded, one per image)
-        lab_kw = {"labels": torch.randint(0, 3, (B,), generator=g)} if a.reveal == "confusion" else {}
+        lab_kw = {"labels": torch.randint(0, 3, (B,), generator=g)} if a.reveal in ("confusion", "metrics") else {}
         gi(imgs, refill=False, **lab_kw); torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(reps):
@@ -189,6 +195,34 @@ def main():
             gi(imgs, **lab_kw)          # the dealer's refill graph, then the online graph, on one stream
         torch.cuda.synchronize()
         both = (time.perf_counter() - t0) / reps * 1e3
+        tail_kw = {}
+        if a.reveal == "metrics":
+            # the tail on its own: an evaluation of --eval_images images (replayed on the primitives the buffers hold: only the
+            # rows matter here), finish() once on the tail's live dealer, which records its primitives, then once more on them
+            gi.begin()
+            passes = (a.eval_images + B - 1) // B
+            for _ in range(passes):
+                gi(imgs, refill=False, **lab_kw)
+            torch.cuda.synchronize()
+            tail_ctx = gi._tail_ctx
+            tail_ctx.dealer.tape = []
+            evals0 = tail_ctx.stats["dif_evals"]
+            t0 = time.perf_counter(); gi.finish(); torch.cuda.synchronize()
+            with_dealer = (time.perf_counter() - t0) * 1e3
+            rows, classes = passes * B, int(sd["fc.weight"].shape[0])
+            comparisons = tail_ctx.stats["dif_evals"] - evals0
+            pre = SecureContext(PreloadedDealer(tail_ctx.dealer.tape, dev, **bits_kw), 10, a.pf)
+            for u in gi._model.U:
+                u.zero_()
+            t0 = time.perf_counter(); gi._model.finish(ctx=pre); torch.cuda.synchronize()
+            tail_online = (time.perf_counter() - t0) * 1e3
+            # (of which: gathering the rows the passes left -- one copy launch per pass, share and party)
+            t0 = time.perf_counter(); gi._model.held_rows(); torch.cuda.synchronize()
+            gather = (time.perf_counter() - t0) * 1e3
+            tail_kw = {"eval_rows": rows, "tail_comparisons": comparisons, "tail_rank_comparisons_64bit": classes * rows * rows,
+                       "tail_online_ms": round(tail_online, 1), "tail_gather_rows_ms": round(gather, 1), "tail_with_dealer_ms": round(with_dealer, 1),
+                       "tail_online_in_images": round(tail_online / (online / B), 2),
+                       "tail_expected_in_images": round(2 * classes * rows * rows / 3311616, 2)}
         print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, **reveal_kw, **bits_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
                           "online_ms_per_image": round(online / B, 2), "with_refill_ms_per_image": round(both / B, 2),
                           "online_ms_per_pass": round(online, 2), "with_refill_ms_per_pass": round(both, 2),
@@ -197,7 +231,7 @@ def main():
                           "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw, **reveal_kw, **bits_kw),
                           "dif_evals": gi.stats["dif_evals"], **({"dpf_evals": gi.stats["dpf_evals"]} if "dpf_evals" in gi.stats else {}),
                           "beaver_matmul": gi.stats["beaver_matmul"],
-                          "beaver_mul": gi.stats["beaver_mul"]}))
+                          "beaver_mul": gi.stats["beaver_mul"], **tail_kw}))
         return
 
     if a.only_fss_roofline:
