@@ -747,6 +747,45 @@ int primia_dp_noise_add(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint
 int64_t primia_dp_noise_blocks(int64_t n);     /* ceil(n / 16): the blocks a call on n elements draws */
 
 /* ------------------------------------------------------------------------------------------
+ * DP-SGD on Poisson-sampled batches (csrc/dp_sample.hip).  The sampled-Gaussian privacy bound (primia_amd/dp_accountant.py)
+ * needs every record to join a step's batch independently with probability q by a secret draw.  Replaces the shuffled
+ * DataLoader of the reference's training loop (torch.randperm under the command line's seed) and, for the padded slots
+ * of the fixed-capacity batch, nn.CrossEntropyLoss(ignore_index=-1).
+ * ------------------------------------------------------------------------------------------ */
+/* Record i (0 <= i < n) reads 64-bit keystream word i % 8 of ChaCha20 block (counter ? *counter : 0) + block_offset +
+ * i / 8 (key, nonce and word layout of primia_chacha20_fill) and is selected iff word < threshold, i.e. with probability
+ * threshold / 2^64.  idx[0 .. kept) = the selected indices in ascending order, the first `capacity` of them;
+ * idx[kept .. capacity) = -1; count[0] = number selected, count[1] = kept = min(selected, capacity); *overflow_events grows
+ * by 1 when selected > capacity.  A pure function of its arguments (stable compaction, no atomics), one launch, no host
+ * synchronisation: capturable.  `counter` is read, not advanced: follow with primia_u64_add(counter,
+ * primia_poisson_blocks(n)).  n == 0 is valid (all -1).  PRIMIA_ERR_ARG for n < 0 or n >= 2^31 (count is 32-bit),
+ * capacity <= 0 or a NULL idx / count / overflow_events. */
+int primia_poisson_select(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce, const uint64_t* counter,
+                          uint64_t block_offset, uint64_t threshold, int64_t n, int capacity, int64_t* idx, int32_t* count,
+                          uint64_t* overflow_events, primia_stream_t stream);
+int64_t primia_poisson_blocks(int64_t n);      /* ceil(n / 8): the blocks a selection over n records draws */
+/* The batch of a selection in one launch — replaces torch.index_select on images and labels plus the padding cat:
+ * out[s] = data[row_offset + idx[s]], out_targets[s] = targets[row_offset + idx[s]] for 0 <= idx[s] < n_rows; every other
+ * slot (idx[s] < 0: padding, or out of range) gets a zero row and target -1, and nothing is read for it.  `data` holds at
+ * least row_offset + n_rows rows of row_elems elements of `dtype`.  PRIMIA_ERR_ARG when a row is not a whole number of
+ * 16-byte chunks or data / out are not 16-byte aligned. */
+int primia_gather_batch(const void* data, int64_t row_elems, int64_t n_rows, const int64_t* targets, const int64_t* idx,
+                        int64_t row_offset, void* out, int64_t* out_targets, int capacity, int dtype,
+                        primia_stream_t stream);
+/* primia_xent_hard (no class weights) on a padded batch — replaces nn.CrossEntropyLoss(ignore_index=-1) and its autograd,
+ * per sample: a row with target < 0 gets a zero dlogits row and is left out of the loss; a valid row gets softmax - onehot
+ * (fp64 inside, rounded once), the gradient of the sample's OWN loss, so no primia_scale by N follows;
+ * loss = sum over valid rows of nll_n / max(1, number of valid rows).  target >= C poisons as primia_xent_hard does. */
+int primia_xent_hard_masked(const float* logits, const int64_t* target, float* loss, float* dlogits, int N, int C,
+                            primia_stream_t stream);
+/* primia_dp_clip_factors with clip[n] = 0 where target[n] < 0 — replaces the per-sample clip factors of the reference's
+ * PrivacyEngine (max_grad_norm / (norm + 1e-6), capped at 1: train.py:325-334) on a batch whose padded slots are not
+ * samples at all (a padded slot's dlogits row is zero already: a second safeguard that padding adds nothing to the
+ * clipped sum). */
+int primia_dp_clip_factors_masked(const double* sq, const int64_t* target, float* clip, int N, float max_grad_norm,
+                                  primia_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * BatchNorm with FROZEN statistics: DP-SGD fine-tuning from pretrained (BatchNorm) weights.  Every norm layer is the
  * per-channel affine map z = (y - running_mean) * invstd * gamma + beta with invstd = 1 / sqrtf(running_var + eps);
  * gamma and beta train, the running statistics are never written.  A sample's gradient then depends on that sample

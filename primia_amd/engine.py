@@ -1187,7 +1187,8 @@ class ResNet18Engine:
     # ------------------------------------------------------------------------------------------
     # DP-SGD (BASELINE.json configs[3]; parameter values of train.py:325-334)
     # ------------------------------------------------------------------------------------------
-    def dp_loss_backward(self, target, max_grad_norm=1.0, noise_multiplier=1.3, noise=None, generator=None):
+    def dp_loss_backward(self, target, max_grad_norm=1.0, noise_multiplier=1.3, noise=None, generator=None,
+                         expected_batch=None):
         """Per-sample gradient clipping + Gaussian noise, pytorch-dp semantics:
             g = (1/B) * ( sum_n min(1, C / (||g_n|| + 1e-6)) * g_n  +  N(0, (noise_multiplier*C)^2 I) )
         with g_n the gradient of sample n's OWN loss over all 62 parameter tensors (flat L2 norm).
@@ -1199,14 +1200,23 @@ class ResNet18Engine:
         and has every block add the squares of ITS (complete) per-sample tile to ||g_n||^2 — the per-sample
         gradients are never written; then each sample's rows of
         dy are scaled by its clip factor and the ordinary batched wgrad — linear in dy — produces
-        sum_n clip_n * g_n directly."""
+        sum_n clip_n * g_n directly.
+
+        `expected_batch` (a float L: dp_params of a Poisson-sampled run, primia_amd.dp_sampling): the batch is a
+        fixed-capacity one whose padded slots carry target -1.  Those get a zero dlogits row and a zero clip factor —
+        every contribution of theirs to the norms and the clipped sums is exactly zero — and the noised sum is divided
+        by L, not by the number of slots: the sampled Gaussian mechanism the accountant (dp_accountant) bounds."""
+        masked = expected_batch is not None
         if self.norm not in ("group", "frozen"):
             raise _lib.PrimiaError("DP-SGD needs per-sample independent norm layers: ResNet18Engine(norm='group') or "
                                    "norm='frozen' (BatchNorm with fixed statistics)")
         N, nc, dev = self.N, self.spec.num_classes, self.device
         # per-sample loss gradients: softmax - onehot (xent gives them divided by the batch size)
-        call("primia_xent_hard", self.logits, target, None, self.loss, self.dlogits, N, nc)
-        call("primia_scale", self.dlogits, self.dlogits.numel(), float(N))
+        if masked:      # softmax - onehot on valid rows, zeros on padded ones; the loss is the mean over the valid rows
+            call("primia_xent_hard_masked", self.logits, target, self.loss, self.dlogits, N, nc)
+        else:
+            call("primia_xent_hard", self.logits, target, None, self.loss, self.dlogits, N, nc)
+            call("primia_scale", self.dlogits, self.dlogits.numel(), float(N))
         self.dp = {"wgrads": []}
         try:
             self.backward()
@@ -1264,7 +1274,10 @@ class ResNet18Engine:
                     call("primia_conv2d_wgrad_persample_sqnorm", c.desc, x, dy, sq, self.dt)
                 mark(name)
             clip = torch.empty(N, dtype=torch.float32, device=dev)
-            call("primia_dp_clip_factors", sq, clip, N, float(max_grad_norm))
+            if masked:
+                call("primia_dp_clip_factors_masked", sq, target, clip, N, float(max_grad_norm))
+            else:
+                call("primia_dp_clip_factors", sq, clip, N, float(max_grad_norm))
             # clipped sums
             # (a transition block's conv1 + downsample: ONE launch as in plain training, once both dy are scaled)
             pair_of, pair_wait = {}, {}
@@ -1343,13 +1356,14 @@ class ResNet18Engine:
                 self.dp_operands = list(self.dp["wgrads"])
             self.dp = None
         sigma = float(noise_multiplier * max_grad_norm)
+        inv_batch = 1.0 / float(expected_batch) if masked else 1.0 / N
         if noise is None and generator is None and self._root.dp_noise is not None:
             # the ROOT's stream, whichever sibling runs the step: a halved or ragged batch advances the one counter
-            self._root.dp_noise.add_to(self.grads, self.P, sigma, 1.0 / N)
+            self._root.dp_noise.add_to(self.grads, self.P, sigma, inv_batch)
         else:
             if noise is None:
                 noise = torch.randn(self.P, dtype=torch.float32, device=dev, generator=generator)
-            call("primia_dp_add_noise", self.grads, noise, self.P, sigma, 1.0 / N)
+            call("primia_dp_add_noise", self.grads, noise, self.P, sigma, inv_batch)
         self.dp_stats = {"sq_norms": sq, "clip": clip}
         return self.loss
 

@@ -20,7 +20,9 @@ Graphs live on the engine they replay (the root engine or a `sibling()`, so that
 buffers), keyed by batch size, soft targets, optimizer kind, fuse_sgd_tail and class-weight presence.  Only the root's
 batch size and MixUp's half batch are captured; other sizes (a loader's ragged last batch) run eagerly, and so does DP-SGD
 unless its noise comes from a device stream (engine.dp_noise, primia_amd.dp_noise.DeviceNoise: the noise node reads the
-stream's device counter and the next node advances it, so every replay draws fresh noise).  The
+stream's device counter and the next node advances it, so every replay draws fresh noise).  Poisson-sampled DP batches
+(dp_sampling.PoissonLoader) always have the engine's size — padded slots carry target -1 — so ONE graph, keyed
+"Poisson-sampled", serves every step whatever the number of records selected.  The
 first step of a key runs eagerly (real training that also allocates the engine's lazy buffers), the second is captured
 and replayed.
 """
@@ -69,6 +71,9 @@ def _key(eng, optimizer, soft):
         dp = root.dp_params
         key += ("DP with device noise", float(dp.get("max_grad_norm", 1.0)), float(dp.get("noise_multiplier", 1.3)),
                 root.dp_noise.key_words + (root.dp_noise.nonce,))
+        if dp.get("expected_batch") is not None:
+            # padded fixed-capacity batches (dp_sampling.PoissonLoader): other loss and clip kernels, 1 / L in the noise node
+            key += ("Poisson-sampled", float(dp["expected_batch"]))
     return key
 
 

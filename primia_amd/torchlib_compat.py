@@ -525,8 +525,9 @@ def test(args, model, device, val_loader, epoch, loss_fn, num_classes, verbose=T
     return test_loss, 100.0 * mcc
 
 
-def save_model(model, optim, path, args, epoch, val_mean_std):
-    """torchlib/utils.py:1470-1493 — same checkpoint keys, so reference tooling reads it."""
+def save_model(model, optim, path, args, epoch, val_mean_std, extra=None):
+    """torchlib/utils.py:1470-1493 — same checkpoint keys, so reference tooling reads it.  `extra`: further keys
+    (train.py --dp_sampling poisson: `dp_privacy`)."""
     import os
 
     import torch
@@ -538,7 +539,7 @@ def save_model(model, optim, path, args, epoch, val_mean_std):
     opt_state_dict = {name: sd(o) for name, o in optim.items()} if args.train_federated else sd(optim)
     model = model["local_model"] if isinstance(model, dict) else model
     torch.save({"epoch": epoch, "model_state_dict": model.state_dict(), "optim_state_dict": opt_state_dict,
-                "args": args, "val_mean_std": val_mean_std}, path)
+                "args": args, "val_mean_std": val_mean_std, **(extra or {})}, path)
 
 
 class Cross_entropy_one_hot:

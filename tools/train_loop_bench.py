@@ -9,7 +9,10 @@ a train() call over `--steps` batches bracketed by device synchronisations; one 
 images per second.  --dp times the DP-SGD loop (GroupNorm network, clip 1.0, noise multiplier 1.3: train.py with
 differentially_private = yes) with --dp_noise torch (torch.randn; --hip_graph leaves its steps eager) or chacha (the
 device ChaCha20 stream of primia_amd.dp_noise; --hip_graph replays the steps); --dp_norm frozen times it on the BatchNorm
-network with frozen statistics (train.py's --dp_norm frozen) instead.  Needs a GPU (there is no CPU path)."""
+network with frozen statistics (train.py's --dp_norm frozen) instead.  --dp_sampling poisson times train.py's Poisson-sampled
+loop: --records synthetic records, expected batch --batch, the engine at the capacity dp_accountant.capacity_for gives for
+--planned_steps; every step is select + gather (primia_amd.dp_sampling.PoissonLoader) and the masked DP step; images per
+second then counts the EXPECTED batch.  Needs a GPU (there is no CPU path)."""
 import argparse
 import json
 import os
@@ -36,7 +39,12 @@ def main():
     ap.add_argument("--dp", action="store_true", help="the DP-SGD loop (differentially_private = yes)")
     ap.add_argument("--dp_noise", choices=("torch", "chacha"), default="torch", help="with --dp: train.py's --dp_noise")
     ap.add_argument("--dp_norm", choices=("group", "frozen"), default="group", help="with --dp: train.py's --dp_norm")
+    ap.add_argument("--dp_sampling", choices=("shuffle", "poisson"), default="shuffle",
+                    help="with --dp: train.py's --dp_sampling")
+    ap.add_argument("--records", type=int, default=1721, help="--dp_sampling poisson: records sampled from")
+    ap.add_argument("--planned_steps", type=int, default=280, help="--dp_sampling poisson: steps the capacity is sized for")
     a = ap.parse_args()
+    poisson = a.dp and a.dp_sampling == "poisson"
     if not torch.cuda.is_available():
         raise SystemExit("train_loop_bench needs a GPU")
 
@@ -49,11 +57,32 @@ def main():
     bufs = [(torch.randn(a.batch, 3, a.size, a.size, generator=g).to(dev),
              torch.randint(0, 3, (a.batch,), generator=g).to(dev)) for _ in range(a.buffers)]
     loader = [bufs[i % a.buffers] for i in range(a.steps)]
+    capacity = a.batch
+    if poisson:
+        from primia_amd import dp_accountant
+        from primia_amd.dp_sampling import DeviceSampler, PoissonLoader
+
+        q = dp_accountant.q_of_threshold(dp_accountant.threshold_for((a.batch, a.records)))
+        capacity = dp_accountant.capacity_for(a.records, q, a.planned_steps, 1e-5, sigma=1.3)
+        records = torch.cat([bufs[i % a.buffers][0] for i in range(-(-a.records // a.batch))])[:a.records].contiguous()
+        labels = torch.cat([bufs[i % a.buffers][1] for i in range(-(-a.records // a.batch))])[:a.records].contiguous()
+
+        class Draws:
+            """`count` Poisson batches of one PoissonLoader, whatever its epoch length."""
+
+            def __init__(self, pl, count):
+                self.pl, self.count = pl, count
+
+            def __len__(self):
+                return self.count
+
+            def __iter__(self):
+                return (self.pl.draw() for _ in range(self.count))
     modes = a.modes.split(",")
     runs = {}
     for m in modes:
         torch.manual_seed(42)
-        eng = ResNet18Engine(a.batch, 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
+        eng = ResNet18Engine(capacity, 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
                              norm=a.dp_norm if a.dp else "batch")
         eng.init_weights()
         if a.dp:
@@ -62,18 +91,23 @@ def main():
                 from primia_amd.dp_noise import DeviceNoise
 
                 eng.dp_noise = DeviceNoise(dev)
+            if poisson:
+                pl = PoissonLoader(records, labels, a.batch, capacity, DeviceSampler(dev))
+                eng.dp_params["expected_batch"] = pl.expected_batch
         args = SimpleNamespace(optimizer="SGD", lr=1e-4, weight_decay=5e-4, log_interval=10 ** 9, mixup=False,
                                hip_graph=m == "graph")
         opt = EngineOptimizer.from_args(eng, args)
-        train(args, eng, dev, loader[:max(3, a.buffers)], opt, 0, None, verbose=False)   # warm-up (+ capture)
-        runs[m] = (eng, args, opt, [])
+        mine = Draws(pl, a.steps) if poisson else loader
+        warm = Draws(pl, max(3, a.buffers)) if poisson else loader[:max(3, a.buffers)]
+        train(args, eng, dev, warm, opt, 0, None, verbose=False)   # warm-up (+ capture)
+        runs[m] = (eng, args, opt, [], mine)
     torch.cuda.synchronize()
     for _ in range(a.runs):
         for m in modes:
-            eng, args, opt, ts = runs[m]
+            eng, args, opt, ts, mine = runs[m]
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            train(args, eng, dev, loader, opt, 1, None, verbose=False)
+            train(args, eng, dev, mine, opt, 1, None, verbose=False)
             torch.cuda.synchronize()
             ts.append((time.perf_counter() - t0) / a.steps * 1e3)
     out = {"metric": "train_loop", "batch": a.batch, "size": a.size, "dtype": "bf16", "optimizer": "SGD",
@@ -84,6 +118,10 @@ def main():
         out["dp_noise"] = a.dp_noise
         out["dp_norm"] = a.dp_norm
         out["graphed_keys"] = {m: len(captures(runs[m][0])) for m in modes}
+        out["dp_sampling"] = a.dp_sampling
+        if poisson:
+            out.update(records=a.records, capacity=capacity, planned_steps=a.planned_steps,
+                       overflow_events={m: runs[m][4].pl.sampler.overflow_events() for m in modes})
     for m in modes:
         ts = runs[m][3]
         med = statistics.median(ts)

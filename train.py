@@ -6,7 +6,7 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
     python train.py --config configs/torch/pneumonia-resnet-pretrained.ini --train_federated \
         [--unencrypted_aggregation] [--data_dir DIR|synthetic] [--cuda] [--resume_checkpoint P] \
         [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N] \
-        [--dp_norm {group,frozen}]
+        [--dp_norm {group,frozen}] [--dp_sampling {shuffle,poisson}] [--dp_delta D]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -23,6 +23,10 @@ Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 `--data_dir synthetic` trains on seeded synthetic batches; a folder is read as the reference lays it out
 (`<data_dir>/worker<i>/<class>/<image>` per client, `<data_dir>/validation/<class>/<image>`; vanilla training reads
 `<data_dir>/<class>/<image>`), resized / cropped / normalised on the GPU (primia_amd.imagefolder).
+
+`--dp_sampling poisson` (with differentially_private = yes) draws every step's batch by Poisson sampling on the device
+(primia_amd.dp_sampling), divides the noised sum by the expected batch size and reports the (epsilon, delta) the run
+has spent per client after every epoch (primia_amd.dp_accountant); the ledger travels in the checkpoint (`dp_privacy`).
 
 `main(args, verbose, optuna_trial, cmd_args)` returns the best validation MCC like the reference's.
 """
@@ -172,10 +176,12 @@ def init_distributed():
     return dist.get_rank(), world, device
 
 
-def resume(cmd_args, args, model, optimizer, worker_names):
+def resume(cmd_args, args, model, optimizer, worker_names, state=None):
     """The four checkpoint / configuration combinations of train.py:344-389.  Returns the epoch to start at —
-    `state["epoch"]` itself, as the reference does (the saved epoch is run again)."""
-    state = torch.load(cmd_args.resume_checkpoint, map_location="cpu", weights_only=False)
+    `state["epoch"]` itself, as the reference does (the saved epoch is run again).  `state`: the checkpoint, when the
+    caller has loaded it already."""
+    if state is None:
+        state = torch.load(cmd_args.resume_checkpoint, map_location="cpu", weights_only=False)
     ckpt_args = state["args"]
     was_federated = bool(getattr(ckpt_args, "train_federated", False))
     opt_sd = state["optim_state_dict"]
@@ -204,6 +210,50 @@ def resume(cmd_args, args, model, optimizer, worker_names):
         optimizer.load_state_dict(opt_sd)
         model.load_state_dict(state["model_state_dict"])
     return state["epoch"]
+
+
+def poisson_mode(args, cmd_args):
+    """Whether this run samples its batches by Poisson sampling: --dp_sampling poisson with differentially_private = yes
+    (without it the flag warns and does nothing, like --dp_noise chacha and --dp_norm frozen)."""
+    kind = getattr(cmd_args, "dp_sampling", "shuffle") if cmd_args is not None else "shuffle"
+    if kind == "poisson" and not args.differentially_private:
+        warn("--dp_sampling poisson has no effect: the config has differentially_private = no, batches are shuffled "
+             "as usual and no (epsilon, delta) is reported")
+    return kind == "poisson" and bool(args.differentially_private)
+
+
+def poisson_plan(name, n, batch_size, epochs, delta, sigma, spent=None):
+    """(q, planned steps, capacity) of a client with n records: q = floor(batch_size * 2^64 / n) / 2^64 — the probability
+    the kernel samples with is the one the accountant is given — over epochs * ceil(n / batch_size) steps.  An expected
+    batch that is not below the record count (q >= 1) ends the run: that is not a sampled mechanism.
+    `spent` (a resumed run): the checkpoint's ledger.  The plan is then its steps plus the `epochs` still to run, and the
+    capacity is the one that keeps the truncation event of ALL of them — the earlier steps at the capacities they ran
+    at — within its 1% of delta."""
+    from primia_amd import dp_accountant
+
+    try:
+        q = dp_accountant.q_of_threshold(dp_accountant.threshold_for((batch_size, n)))
+    except ValueError as e:
+        raise SystemExit("--dp_sampling poisson, {:s}: batch_size {:d} over {:d} records: {:s}".format(
+            name, batch_size, n, str(e)))
+    ahead = epochs * -(-n // batch_size)
+    if spent is None or not spent.steps:
+        return q, ahead, dp_accountant.capacity_for(n, q, ahead, delta, sigma=sigma)
+    eps = dp_accountant.epsilon(spent.segments + [[q, sigma, ahead]], dp_accountant.DELTA_SHARE * delta)[0]
+    return q, spent.steps + ahead, dp_accountant.capacity_for(n, q, ahead, delta, eps=eps,
+                                                              spent=spent.truncation_mass())
+
+
+def saved_privacy(state):
+    """{client: Ledger} of a loaded checkpoint's `dp_privacy` ({} with a warning when it has none: it was not trained
+    under Poisson sampling, what it spent is unknown)."""
+    from primia_amd.dp_accountant import Ledger
+
+    saved = state.get("dp_privacy")
+    if saved is None:
+        warn("the checkpoint holds no dp_privacy ledger: the reported (epsilon, delta) covers this run's steps only")
+        return {}
+    return {name: Ledger.from_state_dict(d) for name, d in saved.items()}
 
 
 def main(args, verbose=True, optuna_trial=None, cmd_args=None):
@@ -245,14 +295,58 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         warn("--dp_norm frozen without pretrained = yes: the frozen statistics are the initial mean 0 / variance 1, every "
              "norm layer is a learned per-channel affine map")
 
-    def make_engine(client=None):
+    dp_delta = float(getattr(cmd_args, "dp_delta", 1e-5)) if cmd_args is not None else 1e-5
+    poisson = poisson_mode(args, cmd_args)
+    dp_sigma = 1.3
+    privacy = {}        # Poisson sampling: {client name: dp_accountant.Ledger}
+    # a resumed Poisson run sizes every client's capacity from what the checkpoint's ledger has spent plus the epochs
+    # still to run, so the checkpoint is read before the loaders are built (and once: resume() below takes it)
+    resume_state, spent, epochs_ahead = None, {}, args.epochs
+    if cmd_args is not None and getattr(cmd_args, "resume_checkpoint", None):
+        resume_state = torch.load(cmd_args.resume_checkpoint, map_location="cpu", weights_only=False)
+        if poisson:
+            spent = saved_privacy(resume_state)
+            epochs_ahead = max(0, args.epochs - int(resume_state["epoch"]) + 1)      # (the saved epoch is run again)
+    reps = args.repetitions_dataset if "repetitions_dataset" in vars(args) else 1
+
+    def poisson_loader(name, base, client):
+        """The Poisson-sampled form of a client's loader: its records, an expected batch of batch_size, the capacity the
+        planned number of steps needs, a sampler and a ledger of the client's own (nonce rule: make_engine's)."""
+        from primia_amd import dp_accountant, dp_sampling as dps
+
+        # (a registered folder holds repetitions_dataset walks of its records; synthetic shards are not repeated)
+        fed_reps = int(reps or 1) if args.train_federated and not synthetic else 1
+        n = dps.records_of(base, fed_reps)
+        old = spent.get(name)
+        if spent and old is None:
+            warn("the checkpoint's dp_privacy has no ledger for {:s}: its count starts at zero".format(name))
+        if old is not None and old.n != n:
+            warn("{:s}: the checkpoint counted {:d} records, this run has {:d}; its segments are kept as they are".format(
+                name, old.n, n))
+        _, planned, capacity = poisson_plan(name, n, args.batch_size, epochs_ahead, dp_delta, dp_sigma, spent=old)
+        nonce = client if client is not None else 0
+        sampler = dps.DeviceSampler(device, nonce=nonce, debug_seed=dp_noise_seed)
+        led = privacy[name] = dp_accountant.Ledger(n, capacity, dp_delta, planned)
+        if old is not None:     # the ledger goes on counting; a changed q, sigma or capacity opens a new segment
+            led.segments, led.capacities, led.overflow_events = old.segments, old.capacities, old.overflow_events
+        return dps.from_loader(base, args.batch_size, capacity, sampler, fed_reps, (channels, size, size))
+
+    def synthetic_records(batches, seed):
+        sl = SyntheticLoader(batches, args.batch_size, size, num_classes, device, seed, channels)
+        from primia_amd.imagefolder import DeviceLoader
+
+        return DeviceLoader(torch.cat([d for d, _ in sl.data]), sl.targets, args.batch_size, True, seed)
+
+    def make_engine(client=None, batch=None, expected_batch=None):
         # differentially_private = yes (train.py:304-334 of the reference): BatchNorm is rejected by the
         # PrivacyEngine, so the network is built with GroupNorm — or (--dp_norm frozen) BatchNorm is applied with its
         # running statistics held fixed, which keeps samples independent too — and every step clips / noises per sample
-        eng = ResNet18Engine(args.batch_size, num_classes, channels, size, args.pooling_type,
+        eng = ResNet18Engine(args.batch_size if batch is None else batch, num_classes, channels, size, args.pooling_type,
                              dtype=dtype, device=device, norm=dp_norm if args.differentially_private else "batch")
         if args.differentially_private:
-            eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": 1.3}
+            eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": dp_sigma}
+            if expected_batch is not None:      # padded Poisson batches: masked loss / clip, the noised sum over q * n
+                eng.dp_params["expected_batch"] = float(expected_batch)
             if dp_noise_kind == "chacha":
                 # a key of its own from the OS entropy pool per engine; the nonce is the client index (the model that
                 # holds a federated run's aggregate never takes a step: it gets the last nonce; a vanilla run's one model
@@ -263,7 +357,18 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                 eng.dp_noise = DeviceNoise(device, nonce=nonce, debug_seed=dp_noise_seed)
         return eng
 
-    local = make_engine()
+    vanilla_loader = None
+    if poisson and not args.train_federated:
+        # the engine's batch is the capacity, which follows from the record count: the loader comes first
+        if synthetic:
+            base = synthetic_records(max(2, n_batches), args.seed)
+        else:
+            base, (m, s) = imagefolder.client_loader(args.data_dir, args, device, channels, args.seed)
+            val_mean_std_vanilla = (m.cpu(), s.cpu())
+        vanilla_loader = poisson_loader("model", base, None)
+        local = make_engine(batch=vanilla_loader.capacity, expected_batch=vanilla_loader.expected_batch)
+    else:
+        local = make_engine()
     local.init_weights()
     if args.pretrained:
         load_pretrained(local, num_classes, rank, world)
@@ -286,13 +391,14 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         else:
             mine = list(workers)
         model = {"local_model": local}
-        for w in mine:
-            model[w] = make_engine(client=workers.index(w))
-            model[w].load_state_dict(local.state_dict())
         train_loader, stats = {}, {}
-        for w in mine:
+
+        def client_data(w):
             i = workers.index(w)
-            if synthetic:
+            if synthetic and poisson:
+                train_loader[w] = poisson_loader(w, synthetic_records(max(2, n_batches - i), args.seed + i), i)
+                stats[w] = (torch.zeros(channels, device=device), torch.ones(channels, device=device))
+            elif synthetic:
                 # deliberately uneven shards (exercises weighted averaging and exhausted clients)
                 train_loader[w] = SyntheticLoader(max(1, n_batches - i), args.batch_size, size, num_classes, device,
                                                   args.seed + i, channels, args)
@@ -300,6 +406,20 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             else:
                 train_loader[w], stats[w] = imagefolder.client_loader(
                     path.join(args.data_dir, "worker{:d}".format(i + 1)), args, device, channels, args.seed + i)
+                if poisson:
+                    train_loader[w] = poisson_loader(w, train_loader[w], i)
+
+        if poisson:     # the engine's batch is the capacity, which follows from the record count: the loaders come first
+            for w in mine:
+                client_data(w)
+        for w in mine:
+            tl = train_loader.get(w)
+            model[w] = make_engine(client=workers.index(w), batch=tl.capacity if poisson else None,
+                                   expected_batch=tl.expected_batch if poisson else None)
+            model[w].load_state_dict(local.state_dict())
+        if not poisson:
+            for w in mine:
+                client_data(w)
         # setup_pysyft's secure average of the clients' (mean, std) (utils.py:764-794) -> val_mean_std
         if world > 1 and not args.unencrypted_aggregation:
             masks = fed.PairwiseMasks.setup(local.flat.numel(), device, group)
@@ -317,7 +437,11 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
     else:
         workers, mine = [], []
         model = local
-        if synthetic:
+        if vanilla_loader is not None:
+            train_loader = vanilla_loader
+            if not synthetic:
+                val_mean_std = val_mean_std_vanilla
+        elif synthetic:
             train_loader = SyntheticLoader(n_batches, args.batch_size, size, num_classes, device, args.seed, channels)
         else:
             train_loader, (m, s) = imagefolder.client_loader(args.data_dir, args, device, channels, args.seed)
@@ -356,9 +480,38 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
     start_at_epoch = 1
     if cmd_args is not None and getattr(cmd_args, "resume_checkpoint", None):
         print("Resume training from a given checkpoint.")
-        start_at_epoch = resume(cmd_args, args, model, optimizer, workers)
+        start_at_epoch = resume(cmd_args, args, model, optimizer, workers, state=resume_state)
     scheduler = LearningRateScheduler(args.epochs, np.log10(args.lr), np.log10(args.end_lr), restarts=args.restarts)
-    reps = args.repetitions_dataset if "repetitions_dataset" in vars(args) else 1
+    poisson_loaders = train_loader if isinstance(train_loader, dict) else {"model": train_loader}
+    overflow_before = {name: led.overflow_events for name, led in privacy.items()}
+    counted = {name: 0 for name in privacy}
+
+    def account(final=False):
+        """The steps this epoch sampled go into the ledgers; rank 0 prints every client's (epsilon, delta).  Returns the
+        checkpoint's `dp_privacy` entry ({client: ledger state}; every rank's under torch.distributed.run)."""
+        for name, led in privacy.items():
+            tl = poisson_loaders[name]
+            led.add_steps(tl.q, dp_sigma, tl.draws - counted[name])
+            counted[name] = tl.draws
+            led.overflow_events = overflow_before[name] + tl.sampler.overflow_events()
+        states = {name: led.state_dict() for name, led in privacy.items()}
+        if world > 1:
+            import torch.distributed as dist
+
+            gathered = [None] * world
+            dist.all_gather_object(gathered, states)
+            states = {k: v for g in gathered for k, v in g.items()}
+        if rank == 0:
+            from primia_amd.dp_accountant import Ledger
+
+            for name in sorted(states):
+                led = Ledger.from_state_dict(states[name])
+                if not led.report()["within_plan"]:
+                    warn("{:s}: the truncation event of {:d} steps ({:d} were planned for, capacity {:d}) no longer fits "
+                         "its share of delta; the reported delta is larger than --dp_delta".format(
+                             name, led.steps, led.planned_steps, led.capacity))
+                print(led.line(name) + (" (end of run)" if final else ""))
+        return states
 
     objectives, model_paths = [], []
     local_flat = None
@@ -384,6 +537,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         else:
             model = train(args, model, device, train_loader, optimizer, epoch, loss_fn, num_classes, verbose=verbose)
             eval_model = model
+        dp_privacy = account() if poisson else None
         if epoch % args.test_interval == 0:
             opt_for_ckpt = optimizer
             if world > 1:
@@ -408,7 +562,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                             verdict[0] = "pruned"
                     if verdict[0] is None:
                         p = "model_weights/{:s}_epoch_{:03d}.pt".format(exp_name, epoch * reps)
-                        save_model(eval_model, opt_for_ckpt, p, args, epoch, val_mean_std=val_mean_std)
+                        save_model(eval_model, opt_for_ckpt, p, args, epoch, val_mean_std=val_mean_std,
+                                   extra={"dp_privacy": dp_privacy} if poisson else None)
                         model_paths.append(p)
                 except Exception as e:  # noqa: BLE001 - forwarded to every rank, re-raised below
                     verdict[0] = e
@@ -425,6 +580,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                     except ImportError:
                         raise RuntimeError("trial pruned") from None
                 raise verdict[0]
+    if poisson:
+        account(final=True)
     best_score = 0.0
     if rank == 0 and objectives:
         # the LAST occurrence of the highest score wins (train.py:514-521)
@@ -484,6 +641,15 @@ def build_parser():
                              "GroupNorm(32, C), trained from a random initialisation (pretrained = yes is refused).  frozen: "
                              "the BatchNorm network applied with its running statistics held fixed (gamma / beta train): "
                              "DP-SGD fine-tuning of pretrained weights; the checkpoint is an ordinary BatchNorm state dict.")
+    parser.add_argument("--dp_sampling", choices=("shuffle", "poisson"), default="shuffle",
+                        help="differentially_private = yes: how a step's batch is drawn.  shuffle: the loaders' seeded "
+                             "shuffle, as before; no (epsilon, delta) is reported.  poisson: every record joins every "
+                             "step's batch independently with probability batch_size / records, drawn on the device from a "
+                             "ChaCha20 stream under an OS key; batches are padded to a fixed capacity, the noised sum is "
+                             "divided by batch_size, and the (epsilon, delta) spent is printed per client after every epoch "
+                             "and stored in the checkpoint (dp_privacy).")
+    parser.add_argument("--dp_delta", type=float, default=1e-5,
+                        help="--dp_sampling poisson: the delta of the reported (epsilon, delta)")
     return parser
 
 
