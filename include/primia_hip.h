@@ -1071,6 +1071,22 @@ int primia_newton_reciprocal_local(const int64_t* v0, const int64_t* v1, const i
  *                                triples' six pointers (t1: a ~ inv [C], b, c ~ rows [HW, C]; t2: a, c ~ rows, b ~ weight)
  *   primia_bn_eval_local_batch   the same for a batch (the reference's batch_norm on [B,C,H,W]): x / out [B][C][HW], the
  *                                triples' rows side [B*HW, C] with row b*HW + p, i.e. x.permute(1,0,2,3).reshape(C,-1).t()
+ *   primia_affine_eval_local     a norm site of a network whose BatchNorm the model owner folded before sharing
+ *                                (primia_amd.secure.fold_batch_norm: scale = gamma / sqrt(running_var + 1e-5) and
+ *                                shift = beta - running_mean * scale, computed in plaintext and shared in place of the four
+ *                                BatchNorm tensors; DESIGN.md §4 -- defined here, not pinned against the reference, which has
+ *                                no such form): SecureContext.affine_eval, out = fpt_mul(rows(x), scale) + shift back in
+ *                                NCHW, of one image.  Exactly the affine tail of primia_bn_eval_local: x / out [C][HW],
+ *                                scale / shift [C]; t: HOST array of the six pointers of the triple ("mul", (HW, C), (C,))
+ *                                (a, c ~ rows [HW, C], b ~ scale); both opens inside, each party truncating its share by
+ *                                `div` before it adds its share of the shift.  For element (c, p), with i = p*C + c:
+ *                                delta = (x0 - a0[i]) + (x1 - a1[i]), eps = (s0[c] - b0[c]) + (s1[c] - b1[c]),
+ *                                z0 = delta*b0[c] + a0[i]*eps + c0[i] + delta*eps, z1 = delta*b1[c] + a1[i]*eps + c1[i],
+ *                                out_j = trunc(z_j, div) + shift_j[c].  Bit-identical to primia_col2out_syft ->
+ *                                primia_fpt_mul_local -> primia_ring_add -> primia_col2out_syft on the same triple.  No
+ *                                allocation and no copy inside: capturable.  out0 / out1: two distinct buffers
+ *   primia_affine_eval_local_batch   the same for a batch: x / out [B][C][HW], the triple ("mul", (B*HW, C), (C,)) with
+ *                                row b*HW + p (i = (b*HW + p)*C + c), as in primia_bn_eval_local_batch; B <= 65535
  *   primia_im2col_syft_2p, primia_pool_unroll_syft_2p   the PySyft layouts of both shares
  *   primia_avg_pool_syft_2p      primia_avg_pool_syft on both parties' shares (nothing is opened: a party-local step)
  *   primia_beaver_matmul_local   spdz_mul "matmul": both opens, then z_j = c_j + delta @ (b_j [+ eps]) + a_j @ eps for
@@ -1118,6 +1134,12 @@ int primia_bn_eval_local_batch(const int64_t* x0, const int64_t* x1, const int64
                                const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1,
                                const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW, int64_t div,
                                primia_stream_t stream);
+int primia_affine_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                             const int64_t* shift0, const int64_t* shift1, const int64_t* const* t, int64_t* out0,
+                             int64_t* out1, int C, int HW, int64_t div, primia_stream_t stream);
+int primia_affine_eval_local_batch(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                   const int64_t* shift0, const int64_t* shift1, const int64_t* const* t, int64_t* out0,
+                                   int64_t* out1, int B, int C, int HW, int64_t div, primia_stream_t stream);
 int primia_im2col_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* im0, int64_t* im1, int B, int C, int H, int W, int R,
                           int S, int stride, int pad, primia_stream_t stream);
 int64_t primia_beaver_matmul_local_scratch_elems(int M, int K, int N);

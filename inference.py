@@ -11,7 +11,12 @@ reference's loop, or `--batch_size N` images per protocol pass; the checkpoint's
 of the plain and of every encrypted form, and a checkpoint without BatchNorm running statistics (train.py with
 differentially_private = yes: GroupNorm(32, C) at every norm site) is served as the GroupNorm network, plain and encrypted.
 The encrypted GroupNorm takes its inverse square root from the reference's Newton iteration, which is accurate to under 1 %
-for group variances in about [0.05, 16] (1.6 % off at 0.01, 15 % at 0.001).  `--reveal class` ends every encrypted pass with
+for group variances in about [0.05, 16] (1.6 % off at 0.01, 15 % at 0.001).  The encrypted BatchNorm runs the same
+iteration on shares of running_var, as the reference does, and is accurate on the same window only (the wrong sign from a
+variance of 22); `--fold_norm` has the model owner fold every BatchNorm into scale = gamma / sqrt(running_var + 1e-5) and
+shift = beta - running_mean * scale before sharing, so that each norm site is one private multiply-add and the encrypted pass
+follows the plaintext model for any running statistics -- a form defined here, not by the reference; the plain path always
+evaluates the checkpoint as it is.  `--reveal class` ends every encrypted pass with
 a secret-shared argmax and opens the predicted class alone: the logits, the model owner's asset, are never reconstructed.  Output: the reference's JSON on stdout, {"Inference Results": {index: class}}.
 
 `--evaluate` scores the model on a labelled set instead (`--data_dir` a class-folder tree <dir>/<class>/<image>, or `synthetic`
@@ -26,11 +31,12 @@ import json
 import os
 import sys
 from datetime import datetime
+from warnings import warn
 
 import torch
 
 from primia_amd.engine import ResNet18Engine
-from primia_amd.secure import Dealer, SecureContext, SecureResNet18, norm_of
+from primia_amd.secure import Dealer, SecureContext, SecureResNet18, fold_batch_norm, norm_of
 from primia_amd.torchlib_compat import Arguments  # noqa: F401  (checkpoints pickle an Arguments instance)
 
 
@@ -182,6 +188,16 @@ if __name__ == "__main__":
                              "confusion passes, then classes * n^2 64-bit comparisons of cross-multiplied scores on shares: "
                              "the matrix and 2 * classes * (classes - 1) pair counts are opened, from which the reference's "
                              "one-vs-one ROC AUC follows -- nothing per image")
+    parser.add_argument("--fold_norm", action="store_true",
+                        help="encrypted inference on a BatchNorm checkpoint: the model owner folds every BatchNorm into one "
+                             "per-channel map before sharing -- scale = gamma / sqrt(running_var + 1e-5) and shift = beta - "
+                             "running_mean * scale, computed in plaintext and shared in place of the statistics -- so a norm "
+                             "site is one private multiply-add and the pass follows the plaintext model for any running "
+                             "statistics.  The reference's form (the default) runs its Newton iteration on shares of "
+                             "running_var and is accurate only for running variances in about [0.05, 16] (15 %% off at "
+                             "0.001, the wrong sign from 22); the folded form is defined here, not by the reference.  Per "
+                             "pass it drops the 237 Newton triples, their 80 masks and one of the two products of each of "
+                             "the 20 norm sites.  Refused for a GroupNorm checkpoint, whose statistics depend on the image")
     parser.add_argument("--debug_dealer_seed", type=int, default=None,
                         help="DEBUG ONLY: derive the crypto provider's key from this number (reproducible, hence "
                              "NOT private); by default the key comes from the OS entropy pool and never leaves the "
@@ -235,12 +251,22 @@ if __name__ == "__main__":
     if bs < 1:
         raise SystemExit("--batch_size must be at least 1")
     pooling = getattr(args, "pooling_type", "max")
+    fold = False
+    if cmd_args.fold_norm and not args.encrypted_inference:
+        warn("--fold_norm has no effect: without --encrypted_inference nothing is shared, the plain engine evaluates the "
+             "checkpoint's BatchNorm as it is")
+    elif cmd_args.fold_norm:
+        if norm_of(sd.keys()) != "batch":
+            raise SystemExit("--fold_norm folds BatchNorm running statistics, which are the model owner's plaintext; this is a "
+                             "GroupNorm checkpoint (no running statistics), whose statistics depend on the image and cannot "
+                             "be folded before sharing")
+        fold = True
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
         if cmd_args.three_role:
             import torch.distributed as dist
 
-            from primia_amd.secure import PartyLink, architecture_of, run_three_role
+            from primia_amd.secure import PartyLink, architecture_of, folded_architecture, run_three_role
 
             multi = torch.cuda.device_count() >= 3
             rank = int(os.environ["RANK"])
@@ -249,9 +275,14 @@ if __name__ == "__main__":
             dist.init_process_group(os.environ.get("PRIMIA_PARTY_BACKEND", "nccl" if multi else "gloo"))
             link = PartyLink(device)
             # one checkpoint file serves all three ranks of a single-node launch; each role is handed only what
-            # it owns: the weights (party 0), the images (party 1), the architecture (everyone)
-            result = run_three_role(link, architecture_of(sd), size, images.shape[0],
-                                    state_dict=sd if link.role == 0 else None,
+            # it owns: the weights (party 0), the images (party 1), the architecture (everyone).  --fold_norm: the model
+            # owner folds its weights, the other two ranks fold the architecture
+            arch = architecture_of(sd)
+            owned = None
+            if link.role == 0:
+                owned = fold_batch_norm(sd) if fold else sd
+            result = run_three_role(link, folded_architecture(arch) if fold else arch, size, images.shape[0],
+                                    state_dict=owned,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
                                     precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal,
@@ -270,16 +301,18 @@ if __name__ == "__main__":
                 logits = result
                 total_pred = [int(c) for o in logits for c in o.argmax(dim=1).tolist()]
         else:
+            # --fold_norm: what the model owner shares is the folded dict; `sd` itself stays the checkpoint
+            shared_sd = fold_batch_norm(sd) if fold else sd
             if cmd_args.hip_graph:
                 from primia_amd.secure import GraphedSecureInference
 
-                model = GraphedSecureInference(sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
+                model = GraphedSecureInference(shared_sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
                                                seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal,
                                                fss_bits=fss_bits)
             else:
                 ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
                                     precision_fractional=cmd_args.precision_fractional)
-                model = SecureResNet18(ctx, sd, input_size=size, pooling=pooling, reveal=reveal)
+                model = SecureResNet18(ctx, shared_sd, input_size=size, pooling=pooling, reveal=reveal)
             if reveal in ("confusion", "metrics"):      # an evaluation: the passes return nothing, the matrix is opened after the last
                 model.begin()
                 for i in range(0, images.shape[0], bs):

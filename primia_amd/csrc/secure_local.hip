@@ -283,6 +283,63 @@ __global__ __launch_bounds__(256) void bn_eval_local_kernel(Pair x, BnVec v, Tri
     }
 }
 
+// ---- a BatchNorm folded by the model owner (defined in tests/secure_folded_nets.py), both parties ------------
+// The model owner holds the running statistics in plaintext and shares s = gamma / sqrt(var + eps) and t = beta - mean * s
+// in their place; a norm site is then the affine tail of batch_norm alone:
+//   rows = x.permute(1,0,2,3).reshape(C,-1).t()                         [B*HW, C], row b*HW + p
+//   result = rows * scale + shift        (FPT mul: Beaver + truncation; triple t: a ~ rows, b ~ scale [C], c ~ rows)
+//   out = result.t().reshape(C, B, H, W).permute(1,0,2,3)               [B, C, H, W]
+// bn_eval_local_kernel's structure with its second product only: the same grid (p-tile, c-tile, b), the same padded tile and
+// the same two transposes -- x / out along p, the triple along c -- so the bank argument above applies unchanged.
+__global__ __launch_bounds__(256) void affine_eval_local_kernel(Pair x, Pair scale, Pair shift, Triple t, OutPair out, int C,
+                                                                int HW, u64 div) {
+    __shared__ u64 tile[2][32][33];
+    const int p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
+    const long img = (long)blockIdx.z * C * HW;                   // this image's [C][HW] plane of x / out
+    const long row0 = (long)blockIdx.z * HW;                      // ... and its first row of the triple
+    // load x[c][p] (coalesced along p)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = c0 + ty + 8 * k, p = p0 + tx;
+        if (c < C && p < HW) {
+            tile[0][ty + 8 * k][tx] = x.p0[img + (long)c * HW + p];
+            tile[1][ty + 8 * k][tx] = x.p1[img + (long)c * HW + p];
+        }
+    }
+    __syncthreads();
+    // rows layout: thread (p, c) with c fastest
+    u64 r0[4], r1[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int p = p0 + ty + 8 * k, c = c0 + tx;
+        r0[k] = r1[k] = 0;
+        if (c < C && p < HW) {
+            const long i = (row0 + p) * C + c;
+            u64 z0, z1;
+            sl_beaver(tile[0][tx][ty + 8 * k], tile[1][tx][ty + 8 * k], scale.p0[c], scale.p1[c], t.a0[i], t.b0[c], t.c0[i],
+                      t.a1[i], t.b1[c], t.c1[i], z0, z1);
+            r0[k] = sl_trunc(z0, div) + shift.p0[c];
+            r1[k] = sl_trunc(z1, div) + shift.p1[c];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        tile[0][tx][ty + 8 * k] = r0[k];
+        tile[1][tx][ty + 8 * k] = r1[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = c0 + ty + 8 * k, p = p0 + tx;
+        if (c < C && p < HW) {
+            out.p0[img + (long)c * HW + p] = tile[0][ty + 8 * k][tx];
+            out.p1[img + (long)c * HW + p] = tile[1][ty + 8 * k][tx];
+        }
+    }
+}
+
 // ---- conv2d / linear pieces ------------------------------------------------------------------------------------------
 // im2col of both parties' shares (the layout of im2col_syft_kernel, ring.hip)
 __global__ __launch_bounds__(256) void im2col_2p_kernel(Pair x, OutPair im, int B, int C, int H, int W, int R, int S, int stride,
@@ -603,6 +660,31 @@ int primia_bn_eval_local_batch(const int64_t* x0, const int64_t* x1, const int64
                                const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW, int64_t div,
                                primia_stream_t st) {
     return bn_eval_local_launch(x0, x1, mean0, mean1, inv0, inv1, w0, w1, bias0, bias1, t1, t2, out0, out1, B, C, HW, div, st);
+}
+
+static int affine_eval_local_launch(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                    const int64_t* shift0, const int64_t* shift1, const int64_t* const* t, int64_t* out0,
+                                    int64_t* out1, int B, int C, int HW, int64_t div, primia_stream_t st) {
+    PRIMIA_REQUIRE(x0 && x1 && scale0 && scale1 && shift0 && shift1 && t && out0 && out1 && out0 != out1 && B > 0 &&
+                   B <= 65535 && C > 0 && HW > 0 && div > 0);
+    for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(t[k]);
+    const dim3 grid((HW + 31) / 32, (C + 31) / 32, B);
+    affine_eval_local_kernel<<<grid, 256, 0, (hipStream_t)st>>>(
+        Pair{U(x0), U(x1)}, Pair{U(scale0), U(scale1)}, Pair{U(shift0), U(shift1)},
+        Triple{U(t[0]), U(t[1]), U(t[2]), U(t[3]), U(t[4]), U(t[5])}, OutPair{(u64*)out0, (u64*)out1}, C, HW, (u64)div);
+    return launch_status();
+}
+
+int primia_affine_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                             const int64_t* shift0, const int64_t* shift1, const int64_t* const* t, int64_t* out0,
+                             int64_t* out1, int C, int HW, int64_t div, primia_stream_t st) {
+    return affine_eval_local_launch(x0, x1, scale0, scale1, shift0, shift1, t, out0, out1, 1, C, HW, div, st);
+}
+
+int primia_affine_eval_local_batch(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                   const int64_t* shift0, const int64_t* shift1, const int64_t* const* t, int64_t* out0,
+                                   int64_t* out1, int B, int C, int HW, int64_t div, primia_stream_t st) {
+    return affine_eval_local_launch(x0, x1, scale0, scale1, shift0, shift1, t, out0, out1, B, C, HW, div, st);
 }
 
 int primia_im2col_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* im0, int64_t* im1, int B, int C, int H, int W, int R,

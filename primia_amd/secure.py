@@ -1019,6 +1019,32 @@ class SecureContext:
         normalized = self.fpt_mul(inv, self.sub(rows, mean))
         return self._affine_to_nchw(normalized, weight, bias, B, C, H, W)
 
+    def affine_eval(self, x, scale, shift):
+        """A norm site of a network whose BatchNorm the model owner folded before sharing (`fold_batch_norm`): the
+        per-channel map x * scale + shift on shares [B, C, H, W], scale / shift shares [C].  The reference has no such form:
+        it is DEFINED here (tests/secure_folded_nets.py's oracle_affine_eval) as exactly the affine tail of
+        batch_norm_eval and is not pinned against the reference:
+          rows = x.permute(1,0,2,3).reshape(C,-1).t()          [B*H*W, C], row b*H*W + p
+          out  = fpt_mul(rows, scale) + shift                  triple ("mul", (B*H*W, C), (C,)), truncation per share
+        back in NCHW.  The element order inside the triple is part of the definition.  No Newton iteration: the result
+        follows the plaintext BatchNorm for any running statistics.
+        Both parties here: one launch (primia_affine_eval_local / _batch); otherwise the step-by-step chain, which a
+        three-role run executes -- same dealer request, same bits."""
+        B, C, H, W = self._ref(x).shape
+        if self._local:
+            t = self.dealer.triple("mul", (B * H * W, C), (C,))
+            out = _pair((B, C, H, W), x[0].device)
+            x = [x[0].contiguous(), x[1].contiguous()]
+            if B == 1:
+                call("primia_affine_eval_local", x[0], x[1], scale[0], scale[1], shift[0], shift[1], _ptr_table(t), out[0],
+                     out[1], C, H * W, int(self.scale))
+            else:
+                call("primia_affine_eval_local_batch", x[0], x[1], scale[0], scale[1], shift[0], shift[1], _ptr_table(t),
+                     out[0], out[1], B, C, H * W, int(self.scale))
+            self.stats["beaver_mul"] += 1
+            return out
+        return self._affine_to_nchw(self._to_rows(x, B, C, H * W), scale, shift, B, C, H, W)
+
     def group_norm(self, x, weight, bias, groups=32):
         """GroupNorm(groups, C) on shares [B, C, H, W] -- the norm of the BatchNorm-free network that differentially private
         training builds.  The reference has no secret-shared GroupNorm: this layer is DEFINED here from the reference's
@@ -1202,22 +1228,88 @@ def _check_reveal(reveal):
     return reveal
 
 
-NORMS = ("batch", "group")
+NORMS = ("batch", "group", "folded")
 GN_GROUPS = 32      # GroupNorm(32, C) at every norm site: the network train.py builds for differentially_private = yes
+BN_EPS = 1e-5       # nn.BatchNorm2d's eps, which the plaintext model adds to running_var (the reference's encrypted form does not)
 
 
 def norm_of(keys, norm=None):
-    """The normalisation a state dict / architecture holds: "group" when it has no running statistics (the BatchNorm-free
-    network of differentially private training), else "batch".  An explicit `norm` is checked against the keys."""
-    found = "batch" if "bn1.running_mean" in keys else "group"
+    """The normalisation a state dict / architecture holds: "folded" when it has bn1.scale (a BatchNorm network after
+    `fold_batch_norm`), "group" when it has no running statistics (the BatchNorm-free network of differentially private
+    training), else "batch".  An explicit `norm` is checked against the keys."""
+    found = "folded" if "bn1.scale" in keys else "batch" if "bn1.running_mean" in keys else "group"
     if norm is None:
         return found
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {NORMS} or None, got {norm!r}")
     if norm != found:
-        raise ValueError(f"norm={norm!r}, but the state dict holds a {found}-norm network (bn1.running_mean is "
+        raise ValueError(f"norm={norm!r}, but the state dict holds a {found}-norm network (bn1.scale is "
+                         f"{'present' if found == 'folded' else 'absent'}, bn1.running_mean is "
                          f"{'present' if found == 'batch' else 'absent'})")
     return norm
+
+
+_BN_TENSORS = (".weight", ".bias", ".running_mean", ".running_var", ".num_batches_tracked")
+
+
+def _foldable_prefixes(keys):
+    """The norm prefixes of a BatchNorm state dict / architecture (`_norm_prefixes`, read off the keys: every site has a
+    running_var), after the refusals folding makes on the keys alone."""
+    if any(k.endswith(".scale") or k.endswith(".shift") for k in keys):
+        raise ValueError("the state dict is already folded (it holds <norm>.scale / <norm>.shift)")
+    prefixes = [k[:-len(".running_var")] for k in keys if k.endswith(".running_var")]
+    if not prefixes:
+        raise ValueError("folding needs BatchNorm statistics: this state dict has no running_mean / running_var (a GroupNorm "
+                         "network's statistics depend on the image and cannot be folded)")
+    return prefixes
+
+
+def _fold_keys(items, prefixes, scale_of, shift_of):
+    """The folded mapping in the unfolded one's order: <prefix>.weight becomes <prefix>.scale, <prefix>.bias becomes
+    <prefix>.shift, the statistics drop out, everything else passes through."""
+    norm_keys = {p + s: (p, s) for p in prefixes for s in _BN_TENSORS}
+    out = {}
+    for k, v in items:
+        if k not in norm_keys:
+            out[k] = v
+            continue
+        p, s = norm_keys[k]
+        if s == ".weight":
+            out[p + ".scale"] = scale_of(p)
+        elif s == ".bias":
+            out[p + ".shift"] = shift_of(p)
+    return out
+
+
+def fold_batch_norm(state_dict, eps=BN_EPS):
+    """The model owner's fold of every eval-mode BatchNorm into one per-channel affine map, BEFORE sharing: the statistics
+    are its own plaintext, so scale = gamma / sqrt(running_var + eps) and shift = beta - running_mean * scale are computed
+    exactly (in float64 from the checkpoint's float32 values, stored as float32) and shared as <prefix>.scale /
+    <prefix>.shift in place of the five BatchNorm tensors; conv and fc tensors pass through untouched.  A SecureResNet18 on
+    the result evaluates every norm site as `SecureContext.affine_eval`: it follows F.batch_norm(..., training=False)
+    for any statistics, where the reference's form (no eps, Newton's iteration on shares of running_var) is accurate only
+    for variances in about [0.05, 16].  Refused (ValueError): a dict without running statistics, a dict that is already
+    folded, a negative or non-finite variance."""
+    prefixes = _foldable_prefixes(state_dict.keys())
+    scale, shift = {}, {}
+    for p in prefixes:
+        var = state_dict[p + ".running_var"].detach().double()
+        if not bool(torch.isfinite(var).all()) or bool((var < 0).any()):
+            raise ValueError(f"{p}.running_var holds a negative or non-finite variance")
+        s = state_dict[p + ".weight"].detach().double() / torch.sqrt(var + float(eps))
+        t = state_dict[p + ".bias"].detach().double() - state_dict[p + ".running_mean"].detach().double() * s
+        if not bool(torch.isfinite(s).all() and torch.isfinite(t).all()):
+            raise ValueError(f"{p}: the folded scale / shift is not finite (running_var + eps = 0, or a non-finite tensor)")
+        scale[p], shift[p] = s.float(), t.float()
+    return _fold_keys(state_dict.items(), prefixes, scale.__getitem__, shift.__getitem__)
+
+
+def folded_architecture(arch):
+    """`fold_batch_norm` on a name -> shape map (`architecture_of`): all the data owner and the crypto provider of a
+    three-role run, who never see the weights, need to follow a folded model."""
+    prefixes = _foldable_prefixes(arch.keys())
+    shape = lambda p: tuple(arch[p + ".running_var"])
+    return _fold_keys(arch.items(), prefixes, shape, shape)
 
 
 def _eps_q(base, pf):
@@ -1259,6 +1351,12 @@ class SecureResNet18:
     on the image -- one Beaver square and one 80-step Newton iteration on B * 32 values per layer, online.  Like the avg
     stem it is NOT pinned against the reference, which has no such layer; it follows the plaintext model.
 
+    norm="folded" serves a BatchNorm checkpoint after the model owner's `fold_batch_norm` (<norm>.scale / <norm>.shift in
+    place of the BatchNorm tensors, shared in `share_order` as parameters; no buffers): every norm site is
+    `SecureContext.affine_eval`, one Beaver product -- no Newton iteration, hoisted or not, and no `precompute_inv`.  NOT
+    pinned against the reference either: it follows the plaintext model (F.batch_norm in eval mode, eps included) for any
+    running statistics, where the reference's form is accurate only for variances in about [0.05, 16].
+
     reveal="class" ends the pass with `SecureContext.argmax` on the logit shares and opens the class indices alone (to the
     data owner): the logits, the model owner's asset, are never reconstructed.  "logits" (the default) is the reference's
     behaviour, unchanged down to the dealer's request list, which is a strict prefix of the class form's.
@@ -1277,8 +1375,9 @@ class SecureResNet18:
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
         default hoists the image-independent iterations of all BatchNorm layers into one batched vector.  (Ignored with
-        GroupNorm: nothing there is image independent.)
-        norm=None: "group" when the state dict has no bn1.running_mean, else "batch"; an explicit value must agree."""
+        GroupNorm: nothing there is image independent; and with a folded dict: there is no iteration.)
+        norm=None: "folded" when the state dict has bn1.scale, "group" when it has no bn1.running_mean, else "batch"; an
+        explicit value must agree."""
         self.ctx = ctx
         self.input_size = input_size
         self.batched_newton = batched_newton
@@ -1418,6 +1517,8 @@ class SecureResNet18:
         p = self.p
         if self.norm == "group":
             return self.ctx.group_norm(x, p[prefix + ".weight"], p[prefix + ".bias"], GN_GROUPS)
+        if self.norm == "folded":
+            return self.ctx.affine_eval(x, p[prefix + ".scale"], p[prefix + ".shift"])
         return self.ctx.batch_norm_eval(x, p[prefix + ".running_mean"], p[prefix + ".running_var"],
                                         p[prefix + ".weight"], p[prefix + ".bias"], inv=self._inv[prefix])
 
@@ -1529,6 +1630,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree).
     An architecture without running statistics is the GroupNorm network: no hoisted Newton; every norm site requests its
     square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples.
+    A folded architecture (`folded_architecture`, bn1.scale among its names): no Newton at all; every norm site requests the
+    single triple ("mul", (B*h*h, c), (c,)) of `SecureContext.affine_eval`.
     reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix).
     reveal="confusion": the confusion tail's requests follow the argmax tail's (the class form's list is a strict prefix).
     reveal="metrics": the confusion list (the rank-count tail runs once, after the last pass: auc_requests)."""
@@ -1541,7 +1644,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     out_hw = lambda h, k, stride, pad: (h + 2 * pad - k) // stride + 1
     cin = arch["conv1.weight"][1]
     mask((B, cin, input_size, input_size), 1)                                  # the images, shared by the data owner
-    group = norm_of(arch) == "group"
+    norm = norm_of(arch)
+    group = norm == "group"
     names = _norm_prefixes(arch, blocks)
 
     def newton(n):
@@ -1552,7 +1656,7 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
             mask((1,), None)
             triple("mul", (n,), (n,))
 
-    if not group:
+    if norm == "batch":
         newton(sum(arch[n + ".running_var"][0] for n in names))                # reciprocal_newton of all layers at once
 
     def conv(name, h, stride, pad):
@@ -1570,9 +1674,9 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
             mask((1,), None)                                                   # + eps
             newton(R)
             triple("mul", (R,), (m, R))
-        else:
+        elif norm == "batch":
             triple("mul", (c,), (B * h * h, c))
-        triple("mul", (B * h * h, c), (c,))
+        triple("mul", (B * h * h, c), (c,))                                    # (a folded norm: SecureContext.affine_eval's, alone)
 
     def relu(c, h):
         req.append(("dif_keys", (B * c * h * h,), {}))

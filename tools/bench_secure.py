@@ -5,6 +5,8 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
     --pooling avg: the stem of a checkpoint trained with pooling_type = avg (ReLU, then a party-local average pool)
     --norm group:  a GroupNorm state dict (the network of differentially private training): every norm site computes its
                    statistics online -- a Beaver square and an 80-step Newton iteration on batch * 32 values per layer
+    --norm folded: the benchmark's BatchNorm state dict after the model owner's fold (primia_amd.secure.fold_batch_norm): the
+                   same legs as --norm batch, without the Newton iteration and with one product per norm site
     --reveal class: every pass ends with the secret-shared argmax and opens the class only (classes - 1 rounds of one comparison
                    launch and one select launch on `batch` elements; the report names it)
     --reveal confusion (with --batch): the passes of an encrypted evaluation -- the argmax, then batch * classes equality tests and
@@ -18,7 +20,7 @@ import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from primia_amd import resnet_spec as rs
-from primia_amd.secure import Dealer, PreloadedDealer, SecureContext, SecureResNet18
+from primia_amd.secure import Dealer, PreloadedDealer, SecureContext, SecureResNet18, fold_batch_norm
 
 def main():
     ap = argparse.ArgumentParser()
@@ -30,8 +32,9 @@ def main():
                          "(--images passes each), the static primitive bytes and the largest batch the card admits")
     ap.add_argument("--pooling", choices=("max", "avg"), default="max",
                     help="the stem pool of the served network (a checkpoint's pooling_type); the report names it when it is avg")
-    ap.add_argument("--norm", choices=("batch", "group"), default="batch",
-                    help="group: a synthetic GroupNorm(32, C) state dict, no running statistics (the report names it)")
+    ap.add_argument("--norm", choices=("batch", "group", "folded"), default="batch",
+                    help="group: a synthetic GroupNorm(32, C) state dict, no running statistics; folded: the BatchNorm state "
+                         "dict of --norm batch, folded by the model owner before sharing (the report names either)")
     ap.add_argument("--reveal", choices=("logits", "class", "confusion", "metrics"), default="logits",
                     help="class: the passes end with SecureContext.argmax and open the predicted class only (the report names it); "
                          "confusion (with --batch): the passes of an encrypted evaluation, which add into the shared confusion matrix; "
@@ -95,7 +98,9 @@ def main():
     cpu_t = cpu_sample_timings() if (a.cpu_sample and not a.only_fss_roofline) else None   # before the first GPU call
     dev = torch.device("cuda:0")
     torch.manual_seed(42)
-    sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, a.pooling), a.norm)
+    sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, a.pooling), "group" if a.norm == "group" else "batch")
+    if a.norm == "folded":
+        sd = fold_batch_norm(sd)
     # (the report of the default keeps its keys: "pooling" appears for avg only, "norm" for group only)
     pool_kw = {} if a.pooling == "max" else {"pooling": a.pooling}
     norm_kw = {} if a.norm == "batch" else {"norm": a.norm}
