@@ -62,24 +62,3 @@ CRAFTED = {
              np.array([[-8, -3, -3, -9, -3], [BIG, 0, -BIG, BIG, 1], [-1000, -999, -998, -997, -998]], I64),
              np.array([[9, 0, 0, 0, 0], [0, 0, 5, 5, 0], [-2, -2, -2, -2, -1]], I64)],
 }
-
-
-# ---- whole networks ---------------------------------------------------------------------------------------------------------
-# norm -> the 8-block network at 32 x 32 and four images whose float64 plaintext classes differ, each with a margin between
-# its two largest logits of more than twice the project's bound on pf = 3 logits (batch: classes 0, 2, 2, 0 with margins 0.19,
-# 0.69, 0.14, 1.44 against 2 x 0.05; group: 0, 2, 0, 0 with 0.15, 0.22, 0.14, 0.11 against 2 x 0.0124), so that the secure
-# passes see two classes as well.  (The BatchNorm networks of this initialisation barely look at a unit-variance image: two
-# of the four are scaled by 3.)
-def network_case(norm):
-    import torch
-
-    from tests.secure_batch_nets import resnet18
-    from tests.secure_groupnorm_nets import group_resnet18
-
-    if norm == "batch":
-        images = torch.randn(4, 3, 32, 32, generator=torch.Generator().manual_seed(522))
-        return resnet18(32, 333), images * torch.tensor([1.0, 3.0, 1.0, 3.0]).view(4, 1, 1, 1)
-    return group_resnet18(32, 520), torch.randn(4, 3, 32, 32, generator=torch.Generator().manual_seed(521))
-
-
-THREE_RANK_BATCH = 3      # four images at three per pass: the second pass is padded with two all-zero images

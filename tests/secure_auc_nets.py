@@ -1,8 +1,8 @@
 """The definition of the rank-count tail that ends an encrypted evaluation with reveal="metrics" (the reference computes its
 one-vs-one ROC AUC on opened scores), the exact counts in Python ints, crafted evaluations and host-side dealers that serve
-comparison keys at a requested width, shared by tests/test_secure_auc_host.py, tests/test_gpu_secure_auc.py and
-tests/auc_party_worker.py: a module of helpers, not of tests.  Everything is composed from oracle.secure_oracle's own functions
-and tests/fss_wide_ref.py's restatement of the wide comparison; nothing under oracle/ knows about the layer."""
+comparison keys at a requested width, shared by tests/test_secure_auc_host.py and tests/test_gpu_secure_auc.py: a
+module of helpers, not of tests.  Everything is composed from oracle.secure_oracle's own functions and
+tests/fss_wide_ref.py's restatement of the wide comparison; nothing under oracle/ knows about the layer."""
 import numpy as np
 
 from oracle import secure_oracle as S

@@ -1,7 +1,10 @@
-"""What the GPU tests of encrypted inference (tests/test_gpu_secure*.py) and their three-role worker (tests/party_worker.py)
-share: share comparison, seeded contexts, the oracle's worker pool, guard words, and the three-role cases with their launch.
-A module of helpers, not of tests."""
+"""What the GPU tests of encrypted inference (tests/test_gpu_secure*.py) share: share comparison, seeded contexts, the oracle's
+worker pool, guard words, runs of inference.py, and the launch of the three-role cases (tests/three_role_cases.py) with
+their in-process reference.  A module of helpers, not of tests."""
+import argparse
 import contextlib
+import ctypes
+import json
 import multiprocessing as mp
 import os
 import signal
@@ -13,10 +16,9 @@ import pytest
 import torch
 
 from oracle import secure_oracle as S
-from primia_amd.secure import (Dealer, SecureContext, SecureResNet18, architecture_of, image_requests,
+from primia_amd.secure import (Dealer, SecureContext, SecureResNet18, architecture_of, fold_batch_norm, image_requests,
                                model_requests)
-from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet
-from tests.secure_groupnorm_nets import group_mini
+from tests.three_role_cases import CASES
 
 I64 = torch.int64
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,53 +102,129 @@ def guards_intact(buf, n):
     return bool((buf[:64] == GUARD).all()) and bool((buf[64 + n:] == GUARD).all())
 
 
+def six(t):
+    """The six tensors of a Beaver triple's two halves, party 0's first."""
+    return (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])
+
+
+def host_ptrs(t):
+    return (ctypes.c_void_p * 6)(*[q.data_ptr() for q in six(t)])
+
+
+def padded(chunk, batch):
+    """A ragged last pass filled up with all-zero images."""
+    pad = batch - len(chunk)
+    return torch.cat([chunk, torch.zeros_like(chunk[:1]).expand(pad, -1, -1, -1)]) if pad else chunk
+
+
+def chunks(images, labels, batch):
+    return [(images[i:i + batch], labels[i:i + batch]) for i in range(0, len(images), batch)]
+
+
+# ---- inference.py on a 32 x 32 checkpoint -----------------------------------------------------------------------------------
+def write_checkpoint(path, sd, pooling="max", encrypted_inference=False):
+    """`sd` as train.py saves it, with the pickled arguments inference.py reads; returns the path as a string."""
+    args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type=pooling,
+                              encrypted_inference=encrypted_inference)
+    torch.save({"model_state_dict": sd, "args": args}, str(path))
+    return str(path)
+
+
+def run_inference(ckpt, num_images, pf, extra=(), batch_size=None, dump=None):
+    """inference.py on `synthetic` under debug dealer seed 7, its own time limit 600 s; PRIMIA_DUMP_LOGITS is `dump` or unset.
+    Returns the CompletedProcess: the caller checks the exit status."""
+    cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", str(num_images),
+           "--cuda", "--debug_dealer_seed", "7", "--precision_fractional", str(pf)]
+    if batch_size is not None:
+        cmd += ["--batch_size", str(batch_size)]
+    env = {k: v for k, v in os.environ.items() if k != "PRIMIA_DUMP_LOGITS"}
+    if dump is not None:
+        env["PRIMIA_DUMP_LOGITS"] = dump
+    return subprocess.run(cmd + list(extra), cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+
+
+def json_line(r):
+    """The JSON object on the last line a successful inference.py run printed."""
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
 # ---- three roles ----------------------------------------------------------------------------------------------------------
-# name -> (network, seed of the generator that draws it and then the images, images, input size, images per protocol pass,
-#          stem pool, shapes of the logits each party holds per pass): three images at two per pass pad the second pass
-THREE_ROLE_CASES = {
-    "mini": (mini_resnet, 21, 2, 16, 1, "max", [(1, 3), (1, 3)]),
-    "batch": (mini_resnet, 61, 3, 32, 2, "max", [(2, 3), (1, 3)]),
-    "avg": (mini_resnet, 61, 3, 32, 2, "avg", [(2, 3), (1, 3)]),
-    "group": (group_mini, 71, 3, 32, 2, "max", [(2, 3), (1, 3)]),
-}
-
-
-def three_role_case(case):
-    """(state dict, images, blocks, input size, batch, pooling) of a three-role test, identical in every process."""
-    net, seed, n, size, batch, pooling, _ = THREE_ROLE_CASES[case]
-    gen = torch.Generator().manual_seed(seed)
-    sd = net(gen)
-    return sd, torch.randn(n, 3, size, size, generator=gen), MINI_BLOCKS, size, batch, pooling
-
-
 def in_process_logits(cuda, case, pf, seed):
-    """The three-role case in ONE process under the same debug seed: the logits both parties must end up with.  What its
-    dealer was asked for is held to the host-side schedule the dealer rank will follow -- model_requests once, image_requests
-    per pass -- so a schedule mismatch fails here, as an assertion, and not as a stall between three processes."""
-    sd, images, blocks, size, batch, pooling = three_role_case(case)
-    dealer = Dealer(cuda, seed=seed)
+    """A logits-form three-role case in ONE process under the same debug seed: the logits both parties must end up with.  What
+    its dealer was asked for is held to the host-side schedule the dealer rank will follow -- model_requests once,
+    image_requests per pass -- so a schedule mismatch fails here, as an assertion, and not as a stall between three processes."""
+    c = CASES[case]
+    assert c.reveal == "logits"
+    sd, images = c.tensors()
+    if c.fold:
+        sd = fold_batch_norm(sd)
+    dealer = Dealer(cuda, seed=seed, fss_bits=c.fss_bits)
     dealer.requests = []
-    model = SecureResNet18(SecureContext(dealer, 10, pf), sd, input_size=size, blocks=blocks, pooling=pooling)
+    model = SecureResNet18(SecureContext(dealer, 10, pf), sd, input_size=c.size, blocks=c.blocks, pooling=c.pooling)
     dv, rows = images.to(cuda), []
-    for i in range(0, len(dv), batch):
-        chunk = dv[i:i + batch]
-        pad = batch - len(chunk)
-        rows.append(model(torch.cat([chunk, torch.zeros_like(dv[:pad])]) if pad else chunk)[:len(chunk)])
+    for i in range(0, len(dv), c.batch):
+        chunk = dv[i:i + c.batch]
+        rows.append(model(padded(chunk, c.batch))[:len(chunk)])
+    assert [tuple(r.shape) for r in rows] == c.shapes
     arch = architecture_of(sd)
-    assert dealer.requests == model_requests(arch) + len(rows) * image_requests(arch, size, batch, blocks, pooling)
+    assert dealer.requests == model_requests(arch) + len(rows) * image_requests(arch, c.size, c.batch, c.blocks, c.pooling)
     return torch.cat(rows).cpu()
 
 
-def three_role_logits(case, pf, seed, tmp_path):
-    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (tests/party_worker.py under
-    torch.distributed.run): the decoded logits of party 0 and party 1."""
+ROLE_LIMIT = 240      # seconds, each role's own
+_role_failures = []      # what failed first in this pytest session: after it no three-role test starts a process
+
+
+def run_roles(commands, out, limit=ROLE_LIMIT, failures=_role_failures, what="three roles"):
+    """One process per command -- rank r runs commands[r] with RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR and MASTER_PORT set,
+    under `timeout -k 10 <limit>` of its own, writing to `out`.log<r>.  The processes are polled; when one exits with a
+    non-zero status its peers, which would wait for it, are terminated.  Returns [(rank, exit status, log)] when every
+    status is zero; otherwise the assertion names the first role that failed and carries rank, status and log tail of every
+    role that did not exit with 0, and `failures` keeps it: while `failures` holds anything, nothing is started."""
     from tests.conftest import free_port
 
+    assert not failures, f"an earlier three-role run failed ({failures[0]}): no further processes are started"
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), WORLD_SIZE=str(len(commands)))
+    logs = [open(f"{out}.log{r}", "w+") for r in range(len(commands))]
+    procs = [subprocess.Popen(["timeout", "-k", "10", str(limit)] + list(cmd), cwd=ROOT,
+                              env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=logs[r], stderr=subprocess.STDOUT)
+             for r, cmd in enumerate(commands)]
+    first = []
+    while any(p.poll() is None for p in procs):
+        for p in procs:
+            try:
+                p.wait(timeout=0.25)
+            except subprocess.TimeoutExpired:
+                pass
+        first = first or [(r, p.poll()) for r, p in enumerate(procs) if p.poll() not in (None, 0)]
+        if first:      # its peers wait for a role that is gone: end them
+            for q in procs:
+                if q.poll() is None:
+                    q.terminate()      # (`timeout` hands the signal on to the role's process, and kills it 10 s later)
+                    q.wait()
+    results = []
+    for r, (p, log) in enumerate(zip(procs, logs)):
+        log.seek(0)
+        results.append((r, p.returncode, log.read()))
+        log.close()
+    bad = [(r, rc, text[-3000:]) for r, rc, text in results if rc != 0]
+    if bad:
+        r, rc = first[0] if first else bad[0][:2]
+        failures.append(f"{what}: rank {r} exited with {rc}")
+    assert not bad, (failures[-1], bad)
+    return results
+
+
+def three_roles(case, pf, seed, out):
+    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (tests/party_worker.py, run_roles):
+    each role that holds a result leaves it in `out`.<role>."""
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "party_worker.py"), out, case, str(pf), str(seed)]
+    run_roles([cmd] * 3, out, what=case)
+
+
+def three_role_logits(case, pf, seed, tmp_path):
+    """The decoded logits of party 0 and party 1 of a logits-form case."""
     out = str(tmp_path / "logits")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
-           "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "tests", "party_worker.py"),
-           out, case, str(pf), str(seed)]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True,
-                       timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    three_roles(case, pf, seed, out)
     return [torch.load(f"{out}.{j}") for j in range(2)]

@@ -1,7 +1,7 @@
 """The definition of the confusion-matrix tail that ends the passes of an encrypted evaluation with reveal="confusion" (the
 reference's encrypted test() opens the predictions and counts them in the clear), the labels that go with the crafted logits of
 tests/secure_argmax_nets.py, and host-side dealers that know the one new primitive, shared by
-tests/test_secure_confusion_host.py, tests/test_gpu_secure_confusion.py and tests/confusion_party_worker.py: a module of
+tests/test_secure_confusion_host.py, tests/test_gpu_secure_confusion.py and tests/three_role_cases.py: a module of
 helpers, not of tests.  Everything is composed from oracle.secure_oracle's own functions; nothing under oracle/ knows about the
 layer."""
 import numpy as np
@@ -136,7 +136,7 @@ GPU_TAIL_SEEDS = {(1, 2): 31, (1, 3): 32, (4, 3): 33, (3, 5): 34}
 
 
 def plaintext_classes(norm, sd, images, pf):
-    """The float64 plaintext classes of a network of tests.secure_argmax_nets.network_case (its margins are documented there)."""
+    """The float64 plaintext classes of a network of tests.three_role_cases.network_case (its margins are documented there)."""
     from tests.secure_batch_nets import plain_forward
     from tests.secure_groupnorm_nets import default_blocks, plain_group_forward
 

@@ -10,7 +10,7 @@ from oracle import secure_oracle as S
 from oracle import train_oracle as O
 from tests import fss_wide_ref as W
 from tests.secure_avgpool_nets import oracle_avg_pool
-from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet, resnet18
+from tests.secure_batch_nets import mini_resnet, resnet18
 from tests.secure_groupnorm_nets import ChaChaDealer
 
 I64, U64 = np.int64, np.uint64
@@ -134,14 +134,6 @@ def narrow_resnet18(size, seed):
 def wide_mini(gen):
     """The mini network (stem, an identity block, a projection block) with the wide variances."""
     return set_variances(mini_resnet(gen), WIDE_VARIANCES)
-
-
-def three_role_case():
-    """(checkpoint, images, blocks, input size, batch) of the three-role test, identical in every process: the generator draws
-    the network and then the images; three images at two per pass pad the second pass."""
-    gen = torch.Generator().manual_seed(81)
-    sd = wide_mini(gen)
-    return sd, torch.randn(3, 3, 32, 32, generator=gen), MINI_BLOCKS, 32, 2
 
 
 def quantise(v, pf):

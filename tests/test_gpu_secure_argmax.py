@@ -5,11 +5,7 @@ last pass, three ranks, the CLI -- to the first-index argmax of the encoded logi
 same shares; a recording opener shows what a pass opens.
 (No MI355X run of this file has been made yet; the kernel's index arithmetic and the fused walk have so far been checked against
 oracle_argmax in a host model only.)"""
-import argparse
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -23,16 +19,14 @@ from primia_amd._lib import PrimiaError, call  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, LocalOpener, PipelinedSecureInference,  # noqa: E402
                                PreloadedDealer, SecureContext, SecureResNet18, architecture_of, image_requests,
                                model_requests)
-from tests.secure_argmax_nets import THREE_RANK_BATCH, first_argmax, network_case, oracle_argmax, spread  # noqa: E402
+from tests.secure_argmax_nets import first_argmax, oracle_argmax, spread  # noqa: E402
 from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet  # noqa: E402
-from tests.secure_common import ROOT, context, guarded, guards_intact, host, shares_equal, wrapping_shares  # noqa: E402
+from tests.secure_common import (context, guarded, guards_intact, host, json_line, padded, run_inference,  # noqa: E402
+                                 shares_equal, six, three_roles, wrapping_shares, write_checkpoint)
+from tests.three_role_cases import THREE_RANK_BATCH, network_case  # noqa: E402
 
 I64 = torch.int64
 SHAPES = [(1, 2), (3, 5), (70, 3)]      # one thread pair, an odd count inside a wavefront, a tail past one wavefront (140 threads)
-
-
-def six(t):
-    return (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])
 
 
 # ---- 1. the kernel ----------------------------------------------------------------------------------------------------------
@@ -141,11 +135,6 @@ def test_context_argmax_equals_the_definition(cuda, shape, pf):
 PF, SEED = 3, 83
 
 
-def padded(chunk, batch):
-    pad = batch - len(chunk)
-    return torch.cat([chunk, torch.zeros_like(chunk[:1]).expand(pad, -1, -1, -1)]) if pad else chunk
-
-
 def logits_form_classes(cuda, sd, tape, chunk):
     """The logits form (SecureResNet18 as it was: reveal="logits") on the primitives in `tape`, of which it consumes a
     prefix: the ENCODED logits it reconstructs, their spread asserted below 2^31, and their first-index argmax."""
@@ -250,16 +239,11 @@ def test_three_ranks_reveal_the_class_to_the_data_owner_only(cuda, net, tmp_path
     """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo, four images at three per pass (a
     ragged last pass): party 1 ends up with the first-index argmax of the encoded logits, party 0 returns None (asserted in
     its process) and writes nothing, the dealer follows the extended schedule (a mismatch would stall: the worker's limit)."""
-    from tests.conftest import free_port
-
     norm, sd, images = net
     want, got = in_process_reference(cuda, sd, images, THREE_RANK_BATCH)
     assert np.array_equal(got, want) and len(set(want.tolist())) >= 2
     out = str(tmp_path / "classes")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "tests", "argmax_party_worker.py"), out, norm, str(PF), str(SEED)]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    three_roles(f"class-{norm}", PF, SEED, out)
     assert not os.path.exists(out + ".0")
     seen = torch.load(out + ".1")
     assert seen.dtype == I64 and np.array_equal(seen.numpy(), want), (seen.tolist(), want.tolist())
@@ -327,28 +311,17 @@ def test_cli_reveal_class(cuda, tmp_path):
     seed at --precision_fractional 3 (one pass over the three images); --hip_graph --batch_size 2 serves the same images; with PRIMIA_DUMP_LOGITS set it refuses, saying
     that the logits are never opened, and writes nothing."""
     sd, _ = network_case("batch")
-    args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type="max", encrypted_inference=False)
-    ckpt = str(tmp_path / "bn.pt")
-    torch.save({"model_state_dict": sd, "args": args}, ckpt)
-    env = {k: v for k, v in os.environ.items() if k != "PRIMIA_DUMP_LOGITS"}
-
-    def run(extra, env=env):
-        cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "3", "--cuda",
-               "--encrypted_inference", "--debug_dealer_seed", "7", "--precision_fractional", "3"] + extra
-        if "--batch_size" not in extra:      # one pass over the three images: both forms then walk the same dealer stream, and
-            cmd += ["--batch_size", "3"]     # the logits under the argmax are the same shares, bit for bit
-
-        return subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-
-    def results(r):
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        return json.loads(r.stdout.strip().splitlines()[-1])
+    ckpt = write_checkpoint(tmp_path / "bn.pt", sd)
+    # by default one pass over the three images: both forms then walk the same dealer stream, and the logits under the argmax
+    # are the same shares, bit for bit
+    run = lambda extra, batch_size=3, dump=None: run_inference(ckpt, 3, 3, ["--encrypted_inference"] + extra, batch_size, dump)
+    results = json_line
 
     base = results(run(["--reveal", "logits"]))
     assert sorted(base["Inference Results"]) == ["0", "1", "2"]
     assert results(run(["--reveal", "class"])) == base
-    graphed = results(run(["--reveal", "class", "--hip_graph", "--batch_size", "2"]))["Inference Results"]      # (other primitives
+    graphed = results(run(["--reveal", "class", "--hip_graph"], 2))["Inference Results"]      # (other primitives
     assert graphed.keys() == base["Inference Results"].keys() and set(graphed.values()) <= {0, 1, 2}            # after a refill)
     dump = str(tmp_path / "logits.pt")
-    r = run(["--reveal", "class"], dict(env, PRIMIA_DUMP_LOGITS=dump))
+    r = run(["--reveal", "class"], dump=dump)
     assert r.returncode != 0 and "never opened" in r.stderr and not os.path.exists(dump)

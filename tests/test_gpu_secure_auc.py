@@ -3,11 +3,7 @@ image (reveal="metrics").  The tail is defined in tests/secure_auc_nets.py from 
 held bit for bit to the chain of existing launches they replace, `SecureContext.auc_counts`, fused and step by step, to that
 definition on the dealer's log, and whole networks -- eager, graphed, three roles, the CLI -- to the counts in Python ints of
 the logit shares the evaluation itself kept; a recording opener shows what an evaluation opens."""
-import argparse
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -22,18 +18,15 @@ from primia_amd.secure import (Dealer, GraphedSecureInference, LocalOpener, Prel
                                SecureResNet18, _ptr_table, architecture_of, argmax_requests, auc_requests, image_requests,
                                model_requests)
 from primia_amd.torchlib_compat import auc_from_rank_counts  # noqa: E402
-from tests.secure_argmax_nets import THREE_RANK_BATCH, network_case  # noqa: E402
 from tests.secure_auc_nets import (GPU_BLOCK_ROWS, GPU_CASE, HOST_SEEDS, AucReplayDealer, crafted_case, exact_counts,  # noqa: E402
                                    oracle_auc_counts, zero_counts)
-from tests.secure_common import ROOT, context, guarded, guards_intact, host, shares_equal, wrapping_shares  # noqa: E402
+from tests.secure_common import (chunks, context, guarded, guards_intact, host, json_line, padded, run_inference,  # noqa: E402
+                                 shares_equal, six, three_roles, wrapping_shares, write_checkpoint)
+from tests.three_role_cases import AUC_LABELS as LABELS, THREE_RANK_BATCH, network_case  # noqa: E402
 
 I64 = torch.int64
 PF, SEED = 3, 83
 ids = lambda s: "x".join(map(str, s))
-
-
-def six(t):
-    return (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])
 
 
 # ---- 1. the kernels ---------------------------------------------------------------------------------------------------------
@@ -188,18 +181,6 @@ def test_context_auc_counts_equal_the_definition(cuda):
 
 
 # ---- 3. whole networks ------------------------------------------------------------------------------------------------------
-LABELS = [0, 1, 2, 1]      # of the four images of network_case: every class is labelled, so the score is defined
-
-
-def padded(chunk, batch):
-    pad = batch - len(chunk)
-    return torch.cat([chunk, torch.zeros_like(chunk[:1]).expand(pad, -1, -1, -1)]) if pad else chunk
-
-
-def chunks(images, labels, batch):
-    return [(images[i:i + batch], labels[i:i + batch]) for i in range(0, len(images), batch)]
-
-
 def roc_auc_of_kept(q, labels):
     """inference.roc_auc_of -- scikit-learn on the min-shifted, row-normalised scores -- on the decoded kept logits."""
     import inference
@@ -352,18 +333,11 @@ def test_an_evaluation_opens_masked_operands_and_the_two_results(cuda, net, monk
 
 
 # ---- 4. three roles ---------------------------------------------------------------------------------------------------------
-ROLE_LIMIT = 240      # seconds, each process's own
-_role_failure = []
-
-
 def test_three_roles_both_parties_hold_the_matrix_and_the_counts(cuda, net, tmp_path):
     """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo, four images at three per pass, each
     process under its own time limit; every exit status is checked and after a failure nothing further is started.  Both
     parties hold the (M, U) of the in-process evaluation under the same debug seed -- itself held to the integers of its
     kept rows -- and the dealer, which served auc_requests after the last pass, holds nothing (asserted in its process)."""
-    from tests.conftest import free_port
-
-    assert not _role_failure, f"an earlier three-role run failed ({_role_failure[0]}): no further processes are started"
     norm, sd, images, labels, want = net
     B = THREE_RANK_BATCH
     dealer = Dealer(cuda, seed=SEED)
@@ -378,32 +352,7 @@ def test_three_roles_both_parties_hold_the_matrix_and_the_counts(cuda, net, tmp_
     assert dealer.requests == model_requests(arch) + 2 * image_requests(arch, 32, B, reveal="metrics") + auc_requests(2 * B, 3)
     check_against_the_kept_rows(model, ctx, M, U, want, labels, B)
     out = str(tmp_path / "metrics")
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), WORLD_SIZE="3")
-    cmd = ["timeout", "-k", "10", str(ROLE_LIMIT), sys.executable, os.path.join(ROOT, "tests", "auc_party_worker.py"), out,
-           norm, str(PF), str(SEED), ",".join(map(str, LABELS))]
-    logs = [open(f"{out}.log{r}", "w+") for r in range(3)]
-    procs = [subprocess.Popen(cmd, cwd=ROOT, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=logs[r],
-                              stderr=subprocess.STDOUT) for r in range(3)]
-    while any(p.poll() is None for p in procs):
-        for p in procs:
-            try:
-                p.wait(timeout=0.25)
-            except subprocess.TimeoutExpired:
-                pass
-        if any(p.poll() not in (None, 0) for p in procs):      # its peers wait for a role that is gone: end them
-            for q in procs:
-                if q.poll() is None:
-                    q.terminate()      # (`timeout` hands the signal on to the role's process, and kills it 10 s later)
-                    q.wait()
-    results = []
-    for r, (p, log) in enumerate(zip(procs, logs)):
-        log.seek(0)
-        results.append((r, p.returncode, log.read()))
-        log.close()
-    bad = [(r, rc, text[-3000:]) for r, rc, text in results if rc != 0]
-    if bad:
-        _role_failure.append(f"{norm}: rank {bad[0][0]} exited with {bad[0][1]}")
-    assert not bad, bad
+    three_roles(f"metrics-{norm}", PF, SEED, out)
     for j in range(2):
         sM, sU = torch.load(f"{out}.{j}")
         assert np.array_equal(sM.numpy(), host(M)) and np.array_equal(sU.numpy(), host(U)), (j, sM.tolist(), sU.tolist())
@@ -420,27 +369,17 @@ def test_cli_evaluate_metrics(cuda, tmp_path):
     import inference
 
     sd, _ = network_case("batch")
-    args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type="max", encrypted_inference=False)
-    ckpt = str(tmp_path / "bn.pt")
-    torch.save({"model_state_dict": sd, "args": args}, ckpt)
+    ckpt = write_checkpoint(tmp_path / "bn.pt", sd)
     dump = str(tmp_path / "logits.pt")
-    base_env = {k: v for k, v in os.environ.items() if k != "PRIMIA_DUMP_LOGITS"}
-
-    def run(extra, env=base_env):
-        cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "4", "--cuda",
-               "--encrypted_inference", "--debug_dealer_seed", "7", "--precision_fractional", "3", "--batch_size", "4"] + extra
-        return subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-
-    def results(r):
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        return json.loads(r.stdout.strip().splitlines()[-1])
+    run = lambda extra, dump=None: run_inference(ckpt, 4, 3, ["--encrypted_inference"] + extra, batch_size=4, dump=dump)
+    results = json_line
 
     labels = inference.synthetic_labels(4, 3)
     assert set(labels.tolist()) == {0, 1, 2}
     r = run(["--evaluate", "--reveal", "metrics"])
     got = results(r)["Evaluation"]
     assert sorted(got) == ["confusion_matrix", "mcc", "n", "roc_auc"] and got["n"] == 4
-    plain = results(run(["--evaluate", "--reveal", "logits"], dict(base_env, PRIMIA_DUMP_LOGITS=dump)))["Evaluation"]
+    plain = results(run(["--evaluate", "--reveal", "logits"], dump))["Evaluation"]
     assert sorted(plain) == ["confusion_matrix", "mcc", "n"]
     assert got["confusion_matrix"] == plain["confusion_matrix"] and got["mcc"] == plain["mcc"]
     want = inference.roc_auc_of(labels, torch.load(dump))

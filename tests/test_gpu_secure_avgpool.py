@@ -3,12 +3,6 @@ trained with, conv1 -> bn1 -> ReLU -> AvgPool2d(3, 2, 1) (the reference's pool /
 only); the pool is a party-local window sum and truncating division by 9, read in place by primia_avg_pool_syft(_2p).
 Kernels and whole networks are held BIT-EXACT to the CPU oracle, the decoded logits to the float64 plaintext forward of the
 avg model, in the eager, graphed, pipelined, three-role and CLI forms."""
-import argparse
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -22,8 +16,9 @@ from primia_amd.secure import (Dealer, GraphedSecureInference, PipelinedSecureIn
                                SecureContext, SecureResNet18, architecture_of, image_requests, model_requests)
 from tests.secure_avgpool_nets import oracle_avg_pool, plaintext_logits  # noqa: E402
 from tests.secure_batch_nets import MINI_BLOCKS, draw_bn, mini_resnet, numpy_sd, oracle_forward, resnet18  # noqa: E402
-from tests.secure_common import (I64, PLAIN_TOL, ROOT, context, guarded, guards_intact, host, in_process_logits,  # noqa: E402,F401
-                                 oracle_pool, shares_equal, three_role_logits, time_limit, wrapping_shares)
+from tests.secure_common import (I64, PLAIN_TOL, context, guarded, guards_intact, host, in_process_logits,  # noqa: E402,F401
+                                 json_line, oracle_pool, run_inference, shares_equal, three_role_logits, time_limit,
+                                 wrapping_shares, write_checkpoint)
 
 
 # ---- 1. the kernels -----------------------------------------------------------------------------------------------------
@@ -264,19 +259,11 @@ def test_cli_serves_the_pooling_the_checkpoint_holds(cuda, tmp_path):
     images = torch.randn(3, 3, 32, 32, generator=torch.Generator().manual_seed(0))      # load_images' synthetic set
 
     def checkpoint(pooling):
-        args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type=pooling,
-                                  encrypted_inference=False)
-        path = str(tmp_path / f"net_{pooling}.pt")
-        torch.save({"model_state_dict": sd, "args": args}, path)
-        return path
+        return write_checkpoint(tmp_path / f"net_{pooling}.pt", sd, pooling)
 
     def run(ckpt, extra, dump):
-        cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "3", "--cuda",
-               "--encrypted_inference", "--debug_dealer_seed", "7", "--precision_fractional", "3"] + extra
-        r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, PRIMIA_DUMP_LOGITS=dump), capture_output=True, text=True,
-                           timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        return json.loads(r.stdout.strip().splitlines()[-1])["Inference Results"], torch.load(dump)
+        r = run_inference(ckpt, 3, 3, ["--encrypted_inference"] + extra, dump=dump)
+        return json_line(r)["Inference Results"], torch.load(dump)
 
     def eager(pooling):
         ctx = SecureContext(Dealer(cuda, seed=7), 10, 3)

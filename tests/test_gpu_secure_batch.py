@@ -2,11 +2,6 @@
 replaying the GPU dealer's stream (oracle/secure_oracle.py's OracleContext is written for [B, C, H, W]; the forward is
 composed from its methods in tests/secure_batch_nets.py because secure_resnet_forward ends in reshape(1, -1)), on the fused
 in-process path and on the step-by-step path a three-role run executes; B = 1 stays what it was."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -19,8 +14,8 @@ from primia_amd._lib import call  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PipelinedSecureInference, PreloadedDealer,  # noqa: E402
                                SecureContext, SecureResNet18, architecture_of, image_requests, model_requests)
 from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet, numpy_sd, oracle_forward, plain_forward, resnet18  # noqa: E402
-from tests.secure_common import (I64, PLAIN_TOL, ROOT, context, host, in_process_logits, oracle_pool,  # noqa: E402,F401
-                                 shares_equal, three_role_logits)
+from tests.secure_common import (I64, PLAIN_TOL, context, host, in_process_logits, json_line, oracle_pool,  # noqa: E402,F401
+                                 run_inference, shares_equal, three_role_logits, write_checkpoint)
 
 
 # ---- 0. the layout kernels on their own ---------------------------------------------------------------------------------
@@ -322,25 +317,16 @@ def test_cli_batch_size(cuda, tmp_path):
     the eager and the --hip_graph form, at three fractional digits (where logits depend on the image); the dumped rows are
     within PLAIN_TOL of the float64 plaintext forward -- the bound of the 224 network, which the same eight blocks on 49
     times fewer positions per layer do not exceed -- and agree in class with per-image eager runs on tapes of their own."""
-    import argparse
-
     sd = resnet18(32, 320)
-    args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type="max",
-                              encrypted_inference=False)
-    ckpt = str(tmp_path / "net.pt")
-    torch.save({"model_state_dict": sd, "args": args}, ckpt)
-    base = ["inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "3", "--cuda",
-            "--encrypted_inference", "--debug_dealer_seed", "7", "--precision_fractional", "3"]
+    ckpt = write_checkpoint(tmp_path / "net.pt", sd)
 
-    def run(extra, dump):
-        r = subprocess.run([sys.executable] + base + extra, cwd=ROOT, env=dict(os.environ, PRIMIA_DUMP_LOGITS=dump),
-                           capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        return json.loads(r.stdout.strip().splitlines()[-1])["Inference Results"], torch.load(dump)
+    def run(batch_size, extra, dump):
+        r = run_inference(ckpt, 3, 3, ["--encrypted_inference"] + extra, batch_size, dump)
+        return json_line(r)["Inference Results"], torch.load(dump)
 
-    one, l_one = run([], str(tmp_path / "one.pt"))
-    two, l_two = run(["--batch_size", "2"], str(tmp_path / "two.pt"))
-    gr, l_gr = run(["--batch_size", "2", "--hip_graph"], str(tmp_path / "graph.pt"))
+    one, l_one = run(None, [], str(tmp_path / "one.pt"))
+    two, l_two = run(2, [], str(tmp_path / "two.pt"))
+    gr, l_gr = run(2, ["--hip_graph"], str(tmp_path / "graph.pt"))
     assert sorted(one) == ["0", "1", "2"] and one == two == gr
     assert l_one.shape == l_two.shape == l_gr.shape == (3, 3)
     images = torch.randn(3, 3, 32, 32, generator=torch.Generator().manual_seed(0))      # load_images' synthetic set

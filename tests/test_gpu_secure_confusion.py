@@ -2,11 +2,7 @@
 tests/secure_confusion_nets.py from the oracle's own methods; `SecureContext.eq` and `SecureContext.confusion`, fused and step
 by step, are held bit for bit to that definition on the dealer's log, whole networks -- eager, graphed, three roles, the CLI --
 to the counts of the float64 plaintext classes against chosen labels, and a recording opener shows what an evaluation opens."""
-import argparse
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,18 +15,16 @@ from primia_amd import secure  # noqa: E402
 from primia_amd._lib import PrimiaError, call  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, LocalOpener, PreloadedDealer, SecureContext,  # noqa: E402
                                SecureResNet18, architecture_of, confusion_requests, image_requests, model_requests)
-from tests.secure_argmax_nets import CRAFTED, THREE_RANK_BATCH, first_argmax, network_case  # noqa: E402
-from tests.secure_common import ROOT, context, guarded, guards_intact, host, shares_equal, wrapping_shares  # noqa: E402
+from tests.secure_argmax_nets import CRAFTED, first_argmax  # noqa: E402
+from tests.secure_common import (chunks, context, guarded, guards_intact, host, json_line, padded, run_inference,  # noqa: E402
+                                 shares_equal, six, three_roles, wrapping_shares, write_checkpoint)
 from tests.secure_confusion_nets import (GPU_TAIL_SEEDS, ConfusionReplayDealer, chosen_labels, crafted_cases,  # noqa: E402
                                          numpy_confusion, onehot, oracle_confusion, oracle_eq, plaintext_classes, zero_matrix)
+from tests.three_role_cases import THREE_RANK_BATCH, network_case  # noqa: E402
 
 I64 = torch.int64
 PF, SEED = 3, 83
 ids = lambda s: "x".join(map(str, s))
-
-
-def six(t):
-    return (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])
 
 
 def dev_pair(arrs, cuda):
@@ -193,11 +187,6 @@ def test_context_confusion_equals_the_definition(cuda, shape):
 
 
 # ---- 4. whole networks ------------------------------------------------------------------------------------------------------
-def padded(chunk, batch):
-    pad = batch - len(chunk)
-    return torch.cat([chunk, torch.zeros_like(chunk[:1]).expand(pad, -1, -1, -1)]) if pad else chunk
-
-
 @pytest.fixture(scope="module", params=["batch", "group"])
 def net(request, cuda):
     """(norm, state dict, images on the device, labels, the counts of the float64 plaintext classes against the labels)."""
@@ -207,10 +196,6 @@ def net(request, cuda):
     want = numpy_confusion(labels, classes, 3)
     assert np.trace(want) > 0 and want.sum() - np.trace(want) > 0 and want.sum() == 4
     return request.param, sd, images.to(cuda), torch.from_numpy(labels), want
-
-
-def chunks(images, labels, batch=THREE_RANK_BATCH):
-    return [(images[i:i + batch], labels[i:i + batch]) for i in range(0, len(images), batch)]
 
 
 def test_eager_and_graphed_evaluation(cuda, net):
@@ -229,7 +214,7 @@ def test_eager_and_graphed_evaluation(cuda, net):
     assert not acc[0].any() and not acc[1].any()      # the constructor's warm-up passes were wiped
     ptrs = [a.data_ptr() for a in acc]
     prev = [a.clone() for a in acc]
-    for step, (chunk, lab) in enumerate(chunks(images, labels)):
+    for step, (chunk, lab) in enumerate(chunks(images, labels, THREE_RANK_BATCH)):
         assert g(chunk, refill=step > 0, labels=lab) is None
         assert np.array_equal(host(g.labels), onehot(lab.numpy().tolist() + [-1] * (B - len(lab)), 3))
         # the eager form on the very primitives the buffers hold: a model of its own, whose accumulator starts at zero
@@ -293,7 +278,7 @@ def test_eager_evaluation_requests_and_opens(cuda, net, monkeypatch):
         marks = []
         if reveal == "confusion":
             model.begin()
-        for chunk, lab in chunks(images, labels):
+        for chunk, lab in chunks(images, labels, THREE_RANK_BATCH):
             model(padded(chunk, B), **({"labels": lab} if reveal == "confusion" else {}))
             marks.append(len(events))
         out = model.finish() if reveal == "confusion" else None
@@ -317,56 +302,24 @@ def test_eager_evaluation_requests_and_opens(cuda, net, monkeypatch):
 
 
 # ---- 5. three roles ---------------------------------------------------------------------------------------------------------
-ROLE_LIMIT = 240      # seconds, each process's own
-_role_failure = []
-
-
 def test_three_roles_both_parties_hold_the_matrix(cuda, net, tmp_path):
     """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo, four images at three per pass,
     each process under its own time limit; every exit status is checked and after a failure nothing further is started.
     Both parties hold the matrix of the in-process evaluation under the same debug seed -- the expected counts -- and the
     dealer, which followed the extended schedule, holds nothing (asserted in its process)."""
-    from tests.conftest import free_port
-
-    assert not _role_failure, f"an earlier three-role run failed ({_role_failure[0]}): no further processes are started"
     norm, sd, images, labels, want = net
     dealer = Dealer(cuda, seed=SEED)
     dealer.requests = []
     model = SecureResNet18(SecureContext(dealer, 10, PF), sd, 32, reveal="confusion")
     model.begin()
-    for chunk, lab in chunks(images, labels):
+    for chunk, lab in chunks(images, labels, THREE_RANK_BATCH):
         model(padded(chunk, THREE_RANK_BATCH), labels=lab)
     arch = architecture_of(sd)
     assert dealer.requests == model_requests(arch) + 2 * image_requests(arch, 32, THREE_RANK_BATCH, reveal="confusion")
     in_process = host(model.finish())
     assert np.array_equal(in_process, want)
     out = str(tmp_path / "matrix")
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), WORLD_SIZE="3")
-    cmd = ["timeout", "-k", "10", str(ROLE_LIMIT), sys.executable, os.path.join(ROOT, "tests", "confusion_party_worker.py"), out,
-           norm, str(PF), str(SEED)]
-    logs = [open(f"{out}.log{r}", "w+") for r in range(3)]
-    procs = [subprocess.Popen(cmd, cwd=ROOT, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=logs[r],
-                              stderr=subprocess.STDOUT) for r in range(3)]
-    while any(p.poll() is None for p in procs):
-        for p in procs:
-            try:
-                p.wait(timeout=0.25)
-            except subprocess.TimeoutExpired:
-                pass
-        if any(p.poll() not in (None, 0) for p in procs):      # its peers wait for a role that is gone: end them
-            for q in procs:
-                if q.poll() is None:
-                    q.terminate()      # (`timeout` hands the signal on to the role's process, and kills it 10 s later)
-                    q.wait()
-    results = []
-    for r, (p, log) in enumerate(zip(procs, logs)):
-        log.seek(0)
-        results.append((r, p.returncode, log.read()))
-        log.close()
-    bad = [(r, rc, text[-3000:]) for r, rc, text in results if rc != 0]
-    if bad:
-        _role_failure.append(f"{norm}: rank {bad[0][0]} exited with {bad[0][1]}")
-    assert not bad, bad
+    three_roles(f"confusion-{norm}", PF, SEED, out)
     for j in range(2):
         seen = torch.load(f"{out}.{j}")
         assert seen.dtype == I64 and np.array_equal(seen.numpy(), in_process), (j, seen.tolist())
@@ -384,20 +337,9 @@ def test_cli_evaluate(cuda, tmp_path):
     from primia_amd.torchlib_compat import confusion_mcc
 
     sd, _ = network_case("batch")
-    args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type="max", encrypted_inference=False)
-    ckpt = str(tmp_path / "bn.pt")
-    torch.save({"model_state_dict": sd, "args": args}, ckpt)
-    env = {k: v for k, v in os.environ.items() if k != "PRIMIA_DUMP_LOGITS"}
-
-    def run(extra):
-        cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "3", "--cuda",
-               "--encrypted_inference", "--debug_dealer_seed", "7", "--precision_fractional", "3", "--batch_size", "3"] + extra
-        return subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-
-    def results(r):
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        return json.loads(r.stdout.strip().splitlines()[-1])
-
+    ckpt = write_checkpoint(tmp_path / "bn.pt", sd)
+    run = lambda extra: run_inference(ckpt, 3, 3, ["--encrypted_inference"] + extra, batch_size=3)
+    results = json_line
     classes = results(run(["--reveal", "class"]))["Inference Results"]
     labels = inference.synthetic_labels(3, 3)
     want = inference.confusion_of(labels, [classes[str(i)] for i in range(3)], 3)

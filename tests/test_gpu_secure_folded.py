@@ -2,12 +2,7 @@
 The reference has no such form: a folded norm site is defined in tests/secure_folded_nets.py from the oracle's own methods;
 the kernel and whole networks are held BIT-EXACT to that composition, the decoded logits to the float64 plaintext model and
 to the plain engine on running variances far outside the Newton domain, in the eager, graphed, three-role and CLI forms."""
-import argparse
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,14 +16,12 @@ from primia_amd.engine import ResNet18Engine  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PreloadedDealer, SecureContext, SecureResNet18,  # noqa: E402
                                architecture_of, fold_batch_norm, image_requests, model_requests, serving_bytes)
 from tests.secure_batch_nets import MINI_BLOCKS, numpy_sd  # noqa: E402
-from tests.secure_common import (I64, PLAIN_TOL, ROOT, context, guarded, guards_intact, host, oracle_pool,  # noqa: E402,F401
-                                 shares_equal, time_limit, wrapping_shares)
+from tests.secure_common import (I64, PLAIN_TOL, context, guarded, guards_intact, host, host_ptrs, in_process_logits,  # noqa: E402,F401
+                                 json_line, oracle_pool, run_inference, shares_equal, three_role_logits, time_limit,
+                                 wrapping_shares, write_checkpoint)
 from tests.secure_folded_nets import (FOLDED_TOL, oracle_affine_eval, oracle_folded_forward, plaintext_logits,  # noqa: E402
-                                      three_role_case, wide_mini, wide_resnet18)
+                                      wide_mini, wide_resnet18)
 from tests.secure_groupnorm_nets import group_resnet18  # noqa: E402
-
-def host_ptrs(t):
-    return (ctypes.c_void_p * 6)(*[q.data_ptr() for j in range(2) for q in t[j]])
 
 
 # ---- 1. the kernel ----------------------------------------------------------------------------------------------------------
@@ -185,32 +178,15 @@ def test_graphed_folded_matches_eager_across_a_refill(cuda, reveal):
 
 # ---- 4. three roles -----------------------------------------------------------------------------------------------------------
 def test_three_role_folded_bit_identical_to_in_process(cuda, tmp_path):
-    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (tests/folded_party_worker.py): rank 0
-    folds the weights, the other two the architecture alone; both parties' decoded logits equal the in-process run's under
-    the same debug seed."""
-    from tests.conftest import free_port
-
+    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (tests/party_worker.py): rank 0 folds
+    the weights, the other two the architecture alone; both parties' decoded logits equal the in-process run's under the
+    same debug seed."""
     pf, seed = 3, 5
     with time_limit(600):
-        sd, images, blocks, size, batch = three_role_case()
-        folded = fold_batch_norm(sd)
-        dealer = Dealer(cuda, seed=seed)
-        dealer.requests = []
-        model = SecureResNet18(SecureContext(dealer, 10, pf), folded, input_size=size, blocks=blocks)
-        dv = images.to(cuda)
-        rows = [model(dv[:2]), model(torch.cat([dv[2:], torch.zeros_like(dv[:1])]))[:1]]
-        arch = architecture_of(folded)
-        assert dealer.requests == model_requests(arch) + 2 * image_requests(arch, size, batch, blocks)
-        want = torch.cat(rows).cpu()
+        want = in_process_logits(cuda, "folded", pf, seed)
         assert not torch.allclose(want[0], want[1], atol=1e-2)
-        out = str(tmp_path / "logits")
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
-               "--master-port", str(free_port()), os.path.join(ROOT, "tests", "folded_party_worker.py"), out, str(pf), str(seed)]
-        r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True,
-                           timeout=540)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-        for j in range(2):
-            assert torch.equal(torch.load(f"{out}.{j}"), want), j
+        for j, got in enumerate(three_role_logits("folded", pf, seed, tmp_path)):
+            assert torch.equal(got, want), j
 
 
 # ---- 5. it is the plaintext model, for any statistics ----------------------------------------------------------------------------
@@ -244,21 +220,13 @@ def test_cli_fold_norm(cuda, tmp_path):
     same command prints (the plain path keeps the unfolded checkpoint; with it the flag only warns), --hip_graph too; a
     GroupNorm checkpoint is refused with the reason."""
     def checkpoint(name, state):
-        args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type="max",
-                                  encrypted_inference=False)
-        path = str(tmp_path / f"{name}.pt")
-        torch.save({"model_state_dict": state, "args": args}, path)
-        return path
+        return write_checkpoint(tmp_path / f"{name}.pt", state)
 
     def run(ckpt, extra):
-        cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "3", "--cuda",
-               "--debug_dealer_seed", "7", "--precision_fractional", "6", "--fss_bits", "64", "--fold_norm"] + extra
-        return subprocess.run(cmd, cwd=ROOT, env={k: v for k, v in os.environ.items() if k != "PRIMIA_DUMP_LOGITS"},
-                              capture_output=True, text=True, timeout=300)
+        return run_inference(ckpt, 3, 6, ["--fss_bits", "64", "--fold_norm"] + extra)
 
     def classes(r):
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        return json.loads(r.stdout.strip().splitlines()[-1])["Inference Results"]
+        return json_line(r)["Inference Results"]
 
     ckpt = checkpoint("wide", wide_resnet18(32, 720))
     plain = run(ckpt, [])

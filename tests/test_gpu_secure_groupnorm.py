@@ -4,11 +4,7 @@ oracle's own methods, the kernels and whole networks are held BIT-EXACT to that 
 float64 plaintext forward, in the eager, graphed, pipelined, three-role and CLI forms.
 (The bounds come from the CPU composition, tests/secure_groupnorm_nets.py; no MI355X run of this file has been made yet, and
 the kernels' index arithmetic has so far been checked against the oracle in a host model only.)"""
-import argparse
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -22,20 +18,11 @@ from primia_amd.engine import ResNet18Engine  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PipelinedSecureInference, PreloadedDealer,  # noqa: E402
                                SecureContext, SecureResNet18, architecture_of, image_requests, model_requests)
 from tests.secure_batch_nets import MINI_BLOCKS, numpy_sd, oracle_forward, resnet18  # noqa: E402
-from tests.secure_common import (I64, ROOT, context, guarded, guards_intact, host, in_process_logits,  # noqa: E402,F401
-                                 oracle_pool, shares_equal, three_role_logits, time_limit, wrapping_shares)
+from tests.secure_common import (I64, context, guarded, guards_intact, host, host_ptrs, in_process_logits,  # noqa: E402,F401
+                                 json_line, oracle_pool, run_inference, shares_equal, six, three_role_logits, time_limit,
+                                 wrapping_shares, write_checkpoint)
 from tests.secure_groupnorm_nets import (GROUP_TOL, VAR_DOMAIN, ChaChaDealer, default_blocks, group_mini,  # noqa: E402
                                          group_resnet18, oracle_group_norm, plain_group_forward, plaintext_group_logits)
-
-
-def six(t):
-    return (t[0][0], t[0][1], t[0][2], t[1][0], t[1][1], t[1][2])
-
-
-def host_ptrs(t):
-    import ctypes
-
-    return (ctypes.c_void_p * 6)(*[q.data_ptr() for q in six(t)])
 
 
 def moments(cuda, x, ts, R, m, scale):
@@ -371,19 +358,10 @@ def test_cli_serves_a_groupnorm_checkpoint(cuda, tmp_path):
     images = torch.randn(3, 3, 32, 32, generator=torch.Generator().manual_seed(0))      # load_images' synthetic set
 
     def checkpoint(name, state):
-        args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type="max",
-                                  encrypted_inference=False)
-        path = str(tmp_path / f"{name}.pt")
-        torch.save({"model_state_dict": state, "args": args}, path)
-        return path
+        return write_checkpoint(tmp_path / f"{name}.pt", state)
 
     def run(ckpt, extra, dump):
-        cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "3", "--cuda",
-               "--debug_dealer_seed", "7", "--precision_fractional", "3"] + extra
-        r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, PRIMIA_DUMP_LOGITS=dump), capture_output=True, text=True,
-                           timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-        res = json.loads(r.stdout.strip().splitlines()[-1])["Inference Results"]
+        res = json_line(run_inference(ckpt, 3, 3, extra, dump=dump))["Inference Results"]
         return res, (torch.load(dump) if os.path.exists(dump) else None)
 
     def eager(state):

@@ -2,12 +2,6 @@
 fused and step by step, the argmax tail, whole networks eager, graphed and revealing the class only, three ranks, the CLI -- is
 held bit for bit to tests/fss_wide_ref.py's WideOracleContext replaying the GPU dealer's log, and to the plain comparison
 [d <= 0] where Python ints say the masked difference does not wrap."""
-import argparse
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
@@ -19,8 +13,10 @@ from primia_amd.secure import (Dealer, GraphedSecureInference, PreloadedDealer, 
                                architecture_of, image_requests, model_requests, serving_bytes)
 from tests import fss_wide_ref as W  # noqa: E402
 from tests.secure_argmax_nets import CRAFTED, first_argmax, oracle_argmax  # noqa: E402
-from tests.secure_batch_nets import numpy_sd, oracle_forward, resnet18  # noqa: E402
-from tests.secure_common import ROOT, host, oracle_pool, shares_equal  # noqa: E402,F401
+from tests.secure_batch_nets import numpy_sd, oracle_forward  # noqa: E402
+from tests.secure_common import (host, in_process_logits, json_line, oracle_pool, run_inference, shares_equal,  # noqa: E402,F401
+                                 three_role_logits, write_checkpoint)
+from tests.three_role_cases import wide_net as net  # noqa: E402
 
 I64 = torch.int64
 PF = 6
@@ -106,12 +102,6 @@ def test_argmax_at_64_bits_is_np_argmax(cuda, fused):
 SEED = 96
 
 
-def net():
-    sd = resnet18(32, 320)
-    images = torch.randn(2, 3, 32, 32, generator=torch.Generator().manual_seed(321)) * torch.tensor([1.0, 3.0]).view(2, 1, 1, 1)
-    return sd, images
-
-
 @pytest.fixture(scope="module")
 def eager64(cuda, oracle_pool):  # noqa: F811
     """The 8-block network at 32 x 32, two images, pf = 6, 64-bit comparisons, with the argmax tail: the GPU's logit shares
@@ -170,20 +160,11 @@ def test_eager_network_at_40_bits_bit_exact(cuda, oracle_pool):  # noqa: F811
 
 # ---- 4. three roles -------------------------------------------------------------------------------------------------------
 def test_three_roles_at_64_bits_equal_the_in_process_run(cuda, tmp_path):
-    """model_owner / data_owner / crypto_provider as three fresh processes on one GPU over gloo (tests/fss_wide_party_worker.py):
-    both parties decode the logits of the in-process run under the same dealer seed."""
-    from tests.conftest import free_port
-
-    sd, images = net()
-    want = SecureResNet18(SecureContext(Dealer(cuda, seed=SEED + 3, fss_bits=64), 10, PF), sd, 32)(images.to(cuda)).cpu()
-    out = str(tmp_path / "logits")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "tests", "fss_wide_party_worker.py"), out, str(PF), str(SEED + 3),
-           "64"]
-    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, MASTER_ADDR="127.0.0.1"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
-    for j in range(2):
-        assert torch.equal(torch.load(f"{out}.{j}"), want), j
+    """model_owner / data_owner / crypto_provider as three fresh processes on one GPU over gloo (tests/party_worker.py): both
+    parties decode the logits of the in-process run under the same dealer seed."""
+    want = in_process_logits(cuda, "wide", PF, SEED + 3)
+    for j, got in enumerate(three_role_logits("wide", PF, SEED + 3, tmp_path)):
+        assert torch.equal(got, want), j
 
 
 # ---- 5. CLI ---------------------------------------------------------------------------------------------------------------
@@ -191,20 +172,9 @@ def test_cli_fss_bits(cuda, tmp_path):
     """inference.py --fss_bits 64 --precision_fractional 6 prints the classes of the in-process run under the same debug seed;
     --fss_bits 70 is refused before anything runs."""
     sd, _ = net()
-    args = argparse.Namespace(train_resolution=32, inference_resolution=32, clahe=False, pooling_type="max", encrypted_inference=False)
-    ckpt = str(tmp_path / "bn.pt")
-    torch.save({"model_state_dict": sd, "args": args}, ckpt)
-    env = {k: v for k, v in os.environ.items() if k != "PRIMIA_DUMP_LOGITS"}
-
-    def run(bits):
-        cmd = [sys.executable, "inference.py", "--model_weights", ckpt, "--data_dir", "synthetic", "--num_images", "2", "--cuda",
-               "--encrypted_inference", "--debug_dealer_seed", "7", "--precision_fractional", str(PF), "--batch_size", "2",
-               "--fss_bits", str(bits)]
-        return subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
-
-    r = run(64)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])["Inference Results"]
+    ckpt = write_checkpoint(tmp_path / "bn.pt", sd)
+    run = lambda bits: run_inference(ckpt, 2, PF, ["--encrypted_inference", "--fss_bits", str(bits)], batch_size=2)
+    res = json_line(run(64))["Inference Results"]
     assert sorted(res) == ["0", "1"] and set(res.values()) <= {0, 1, 2}
     bad = run(70)
     assert bad.returncode != 0 and "--fss_bits must be in [32, 64]" in bad.stderr
