@@ -745,6 +745,23 @@ int primia_dp_add_noise(float* g, const float* noise, int64_t n, float sigma, fl
 int primia_dp_noise_add(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce, const uint64_t* counter,
                         uint64_t block_offset, float* g, int64_t n, float sigma, float inv_batch, primia_stream_t stream);
 int64_t primia_dp_noise_blocks(int64_t n);     /* ceil(n / 16): the blocks a call on n elements draws */
+/* A DP-SGD step cut into micro-batch passes (primia_amd/dp_micro.py): the step is linear in the per-sample terms, so
+ * sum_n clip_n g_n = sum over the passes of each pass's clipped sum; noise and the division by the batch happen once.
+ * Replaces the gradient accumulation of pytorch-dp's virtual_step (not part of the reference tree).
+ * primia_dp_accumulate: acc[i] = g[i] (overwrite != 0: a step's first pass) or acc[i] += g[i], one pass of 16-byte
+ * accesses with a scalar tail.  n == 0 is a no-op; PRIMIA_ERR_ARG for n < 0, a NULL pointer or one that is not 16-byte
+ * aligned, before any launch. */
+int primia_dp_accumulate(float* acc, const float* g, int64_t n, int overwrite, primia_stream_t stream);
+/* The last pass: g[i] = ((acc[i] + g[i]) + sigma * z[i]) * inv_batch with z the noise primia_dp_noise_add defines for the
+ * same key, nonce, counter, block_offset and i — bit for bit primia_dp_noise_add applied to the float32 sum acc + g.  acc is
+ * read only.  Arguments, counter rule and refusals as primia_dp_noise_add (acc must be 16-byte aligned too);
+ * primia_dp_noise_blocks(n) blocks are drawn. */
+int primia_dp_noise_add_acc(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce, const uint64_t* counter,
+                            uint64_t block_offset, float* g, const float* acc, int64_t n, float sigma, float inv_batch,
+                            primia_stream_t stream);
+/* The same for host-supplied noise: primia_dp_add_noise applied to acc + g. */
+int primia_dp_add_noise_acc(float* g, const float* acc, const float* noise, int64_t n, float sigma, float inv_batch,
+                            primia_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * DP-SGD on Poisson-sampled batches (csrc/dp_sample.hip).  The sampled-Gaussian privacy bound (primia_amd/dp_accountant.py)

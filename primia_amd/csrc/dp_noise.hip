@@ -32,16 +32,27 @@ __device__ __forceinline__ void dp_noise_pair(uint32_t a, uint32_t c, float& z_e
     z_odd = r * sn;
 }
 
+// ACC = false: primia_dp_noise_add as described above (`acc` is not read).  ACC = true (primia_dp_noise_add_acc: the last
+// pass of a step cut into micro-batches, primia_amd/dp_micro.py) reads a second, read-only arena `acc` — the clipped sums
+// of the earlier passes — and the expression gets v = acc + g in front: g = ((acc + g) + z * sigma) * inv_b, the same
+// rounding as the ACC = false kernel applied to the float32 sum.  The acc loads are issued with the g loads.
+template <bool ACC>
 __global__ __launch_bounds__(256) void dp_noise_add_kernel(ChaChaKey key, uint64_t block0, const uint64_t* __restrict__ counter,
-                                                           float* __restrict__ g, int64_t n, float sigma, float inv_b) {
+                                                           float* __restrict__ g, const float* __restrict__ acc, int64_t n,
+                                                           float sigma, float inv_b) {
     const int64_t blk = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (blk * 16 >= n) return;
     float* o = g + blk * 16;
+    const float* a = ACC ? acc + blk * 16 : nullptr;
     const bool full = blk * 16 + 16 <= n;
-    f32x4 v[4];
+    f32x4 v[4], w[4];
     if (full) {     // issued before the 20 rounds: their latency hides behind the integer work
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = *(const f32x4*)(o + 4 * i);
+        if (ACC) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) w[i] = *(const f32x4*)(a + 4 * i);
+        }
     }
     const uint64_t ctr = block0 + (counter ? *counter : 0) + (uint64_t)blk;
     uint32_t x[16];
@@ -52,6 +63,7 @@ __global__ __launch_bounds__(256) void dp_noise_add_kernel(ChaChaKey key, uint64
     if (full) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
+            if (ACC) v[i] = w[i] + v[i];
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] + z[4 * i + j] * sigma) * inv_b;
             *(f32x4*)(o + 4 * i) = v[i];
@@ -59,7 +71,39 @@ __global__ __launch_bounds__(256) void dp_noise_add_kernel(ChaChaKey key, uint64
     } else {        // the partial last block: its first n % 16 values
 #pragma unroll
         for (int i = 0; i < 16; ++i)
-            if (blk * 16 + i < n) o[i] = (o[i] + z[i] * sigma) * inv_b;
+            if (blk * 16 + i < n) {
+                const float vi = ACC ? a[i] + o[i] : o[i];
+                o[i] = (vi + z[i] * sigma) * inv_b;
+            }
+    }
+}
+
+// The clipped sum of one micro-batch pass into the step's fp32 accumulator: acc = g (the first pass) or acc += g.  One
+// HBM-bound pass: a thread moves four 16-byte chunks 4 KiB apart (a wave's access is 1 KiB contiguous), every load issued
+// before the first store; the n % 4 elements behind the last whole chunk go through scalar accesses of block 0.
+template <bool OVERWRITE>
+__global__ __launch_bounds__(256) void dp_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n) {
+    const int64_t n4 = n >> 2;
+    const int64_t base = (int64_t)blockIdx.x * 1024 + threadIdx.x;      // in 16-byte chunks
+    const f32x4* g4 = (const f32x4*)g;
+    f32x4* a4 = (f32x4*)acc;
+    f32x4 v[4], w[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = base + u * 256;
+        if (i < n4) {
+            v[u] = g4[i];
+            if (!OVERWRITE) w[u] = a4[i];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = base + u * 256;
+        if (i < n4) a4[i] = OVERWRITE ? v[u] : w[u] + v[u];
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const int64_t j = n4 * 4 + threadIdx.x;
+        acc[j] = OVERWRITE ? g[j] : acc[j] + g[j];
     }
 }
 
@@ -76,7 +120,30 @@ extern "C" int primia_dp_noise_add(uint64_t k0, uint64_t k1, uint64_t k2, uint64
     PRIMIA_REQUIRE(g && n > 0 && ((uintptr_t)g & 15) == 0);
     const ChaChaKey key = chacha_key(k0, k1, k2, k3, nonce);
     const int64_t blocks = primia_dp_noise_blocks(n);
-    dp_noise_add_kernel<<<ceil_div(blocks, 256), 256, 0, (hipStream_t)st>>>(key, block_offset, counter, g, n, sigma,
-                                                                            inv_batch);
+    dp_noise_add_kernel<false><<<ceil_div(blocks, 256), 256, 0, (hipStream_t)st>>>(key, block_offset, counter, g, nullptr, n,
+                                                                                   sigma, inv_batch);
+    return launch_status();
+}
+
+extern "C" int primia_dp_noise_add_acc(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce,
+                                       const uint64_t* counter, uint64_t block_offset, float* g, const float* acc, int64_t n,
+                                       float sigma, float inv_batch, primia_stream_t st) {
+    if (n == 0) return PRIMIA_OK;  // empty input: no-op, pointers may be null
+    PRIMIA_REQUIRE(g && acc && n > 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)acc & 15) == 0);
+    const ChaChaKey key = chacha_key(k0, k1, k2, k3, nonce);
+    const int64_t blocks = primia_dp_noise_blocks(n);
+    dp_noise_add_kernel<true><<<ceil_div(blocks, 256), 256, 0, (hipStream_t)st>>>(key, block_offset, counter, g, acc, n,
+                                                                                  sigma, inv_batch);
+    return launch_status();
+}
+
+extern "C" int primia_dp_accumulate(float* acc, const float* g, int64_t n, int overwrite, primia_stream_t st) {
+    if (n == 0) return PRIMIA_OK;  // empty input: no-op, pointers may be null
+    PRIMIA_REQUIRE(acc && g && n > 0 && ((uintptr_t)acc & 15) == 0 && ((uintptr_t)g & 15) == 0);
+    const int grid = ceil_div(n >> 2, 1024) > 0 ? ceil_div(n >> 2, 1024) : 1;      // (n < 4: the scalar tail alone)
+    if (overwrite)
+        dp_accumulate_kernel<true><<<grid, 256, 0, (hipStream_t)st>>>(acc, g, n);
+    else
+        dp_accumulate_kernel<false><<<grid, 256, 0, (hipStream_t)st>>>(acc, g, n);
     return launch_status();
 }

@@ -702,6 +702,15 @@ __global__ __launch_bounds__(256) void dp_noise_kernel(float* __restrict__ g, co
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) g[i] = (g[i] + noise[i] * sigma) * inv_b;
 }
 
+// ... with the clipped sums of a step's earlier micro-batch passes (acc, read only) added in front
+__global__ __launch_bounds__(256) void dp_noise_acc_kernel(float* __restrict__ g, const float* __restrict__ acc,
+                                                           const float* __restrict__ noise, long n, float sigma,
+                                                           float inv_b) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+        g[i] = ((acc[i] + g[i]) + noise[i] * sigma) * inv_b;
+}
+
 static inline int gn_stream_blocks(long nchunks) {
     long b = (nchunks + 255) / 256;
     return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
@@ -1034,6 +1043,15 @@ int primia_dp_add_noise(float* g, const float* noise, int64_t n, float sigma, fl
     if (n == 0) return PRIMIA_OK;
     long b = (n + 255) / 256;
     dp_noise_kernel<<<(int)(b > 4096 ? 4096 : b), 256, 0, (hipStream_t)stream>>>(g, noise, n, sigma, inv_batch);
+    return launch_status();
+}
+
+int primia_dp_add_noise_acc(float* g, const float* acc, const float* noise, int64_t n, float sigma, float inv_batch,
+                            primia_stream_t stream) {
+    if (n == 0) return PRIMIA_OK;  // empty input: no-op, pointers may be null
+    PRIMIA_REQUIRE(g && acc && noise && n > 0);
+    long b = (n + 255) / 256;
+    dp_noise_acc_kernel<<<(int)(b > 4096 ? 4096 : b), 256, 0, (hipStream_t)stream>>>(g, acc, noise, n, sigma, inv_batch);
     return launch_status();
 }
 

@@ -46,9 +46,14 @@ class DeviceNoise:
         """The counter's value (synchronises: tests and tools)."""
         return int(self.counter.item()) & (2 ** 64 - 1)
 
-    def add_to(self, g, n, sigma, inv_batch):
+    def add_to(self, g, n, sigma, inv_batch, acc=None):
         """g[:n] = (g[:n] + sigma * z) * inv_batch with z the next ceil(n / 16) blocks of the stream; two launches on the
-        current stream, both capturable."""
+        current stream, both capturable.  `acc` (fp32, read only: the clipped sums of a step's earlier micro-batch
+        passes) is added to g first, in the same kernel."""
         ctr = self.counter
-        call("primia_dp_noise_add", *self.key_words, self.nonce, ctr, 0, g, int(n), float(sigma), float(inv_batch))
+        if acc is None:
+            call("primia_dp_noise_add", *self.key_words, self.nonce, ctr, 0, g, int(n), float(sigma), float(inv_batch))
+        else:
+            call("primia_dp_noise_add_acc", *self.key_words, self.nonce, ctr, 0, g, acc, int(n), float(sigma),
+                 float(inv_batch))
         call("primia_u64_add", ctr, query("primia_dp_noise_blocks", int(n)))

@@ -8,7 +8,8 @@ device word, exactly as for the noise (dp_noise.DeviceNoise) — under a key of 
 independent.
 
 A Poisson batch changes size at every step; the engine's buffers and a captured step do not.  Every batch therefore
-has `capacity` slots: the selected records in ascending order, then padding (a zero image, target -1) which the masked
+has `capacity` slots (K * ceil(capacity / K) with `micro_batches=K`: a step run as K passes of an engine that size,
+dp_micro): the selected records in ascending order, then padding (a zero image, target -1) which the masked
 loss and clip kernels of ResNet18Engine.dp_loss_backward(expected_batch=L) turn into exactly nothing.  Select, counter
 advance and gather are three launches on the current stream without a host synchronisation, into ONE reused buffer
 pair whose addresses a replayed graph (graphed_train) reads as its static input.
@@ -77,8 +78,15 @@ class _PoissonBase:
     """`expected_batch`: the integer L of q = L / n (threshold = floor(L * 2^64 / n), in integers), or None with an
     explicit `threshold` (tests)."""
 
-    def __init__(self, n, expected_batch, capacity, sampler, threshold=None):
+    def __init__(self, n, expected_batch, capacity, sampler, threshold=None, micro_batches=1):
         self.n, self.capacity, self.sampler = int(n), int(capacity), sampler
+        # a step run as K micro-batch passes (dp_micro): an engine of M = ceil(capacity / K) slots walks K * M >= capacity
+        # slots; the selection, its capacity and its stream do not know about K, the extra slots are padding for ever
+        self.micro_batches = int(micro_batches)
+        if self.micro_batches < 1:
+            raise ValueError("micro_batches must be at least 1")
+        self.micro_size = -(-self.capacity // self.micro_batches)
+        self.slots = self.micro_batches * self.micro_size
         if threshold is None:
             threshold = dp_accountant.threshold_for((int(expected_batch), self.n))     # refuses q >= 1
         self.threshold = int(threshold)
@@ -102,11 +110,11 @@ class PoissonLoader(_PoissonBase):
     accountant however many augmented copies are stored.  __len__ = ceil(n / L).  Every iteration yields the SAME
     [capacity, ...] buffer pair, rewritten in place."""
 
-    def __init__(self, data, targets, expected_batch, capacity, sampler, repetitions=1, threshold=None):
+    def __init__(self, data, targets, expected_batch, capacity, sampler, repetitions=1, threshold=None, micro_batches=1):
         reps = int(repetitions)
         if data.shape[0] % reps or targets.shape[0] != data.shape[0] or targets.dtype != torch.int64 or targets.dim() != 1:
             raise ValueError("PoissonLoader: data [repetitions * n, ...] with hard int64 targets [repetitions * n]")
-        super().__init__(data.shape[0] // reps, expected_batch, capacity, sampler, threshold)
+        super().__init__(data.shape[0] // reps, expected_batch, capacity, sampler, threshold, micro_batches)
         self.data, self.targets, self.repetitions = data.contiguous(), targets.contiguous(), reps
         self.row_elems = int(self.data[0].numel())
         self.dt = dtype_code(self.data.dtype)
@@ -117,8 +125,9 @@ class PoissonLoader(_PoissonBase):
                              "16-byte chunks; the batch gather needs that (one-channel fp32 images: an even "
                              "train_resolution)".format(tuple(self.data.shape[1:]), self.row_elems, self.data.dtype,
                                                         row_bytes))
-        self.x = torch.zeros((self.capacity,) + tuple(self.data.shape[1:]), dtype=self.data.dtype, device=data.device)
-        self.y = torch.full((self.capacity,), -1, dtype=torch.int64, device=data.device)
+        # (the gather writes the first `capacity` slots; the K * M - capacity behind them stay a zero image with target -1)
+        self.x = torch.zeros((self.slots,) + tuple(self.data.shape[1:]), dtype=self.data.dtype, device=data.device)
+        self.y = torch.full((self.slots,), -1, dtype=torch.int64, device=data.device)
         self.epochs = 0
 
     def draw(self, walk=0):
@@ -141,11 +150,11 @@ class PoissonAugmentingLoader(_PoissonBase):
     folder).  The selection is the same kernel; idx and count are read back (one small copy per step: this loader is
     host-driven anyway), the kept images go through TrainTransform.batch and the result is padded to capacity."""
 
-    def __init__(self, images, targets, transform, rng, expected_batch, capacity, sampler, shape):
-        super().__init__(len(images), expected_batch, capacity, sampler)
+    def __init__(self, images, targets, transform, rng, expected_batch, capacity, sampler, shape, micro_batches=1):
+        super().__init__(len(images), expected_batch, capacity, sampler, micro_batches=micro_batches)
         self.images, self.targets, self.tf, self.rng = images, targets, transform, rng
-        self.x = torch.zeros((self.capacity,) + tuple(shape), dtype=torch.float32, device=sampler.device)
-        self.y = torch.full((self.capacity,), -1, dtype=torch.int64, device=sampler.device)
+        self.x = torch.zeros((self.slots,) + tuple(shape), dtype=torch.float32, device=sampler.device)
+        self.y = torch.full((self.slots,), -1, dtype=torch.int64, device=sampler.device)
 
     def __iter__(self):
         for _ in range(len(self)):
@@ -168,10 +177,11 @@ def records_of(loader, repetitions=1):
     return int(loader.data.shape[0]) // int(repetitions)
 
 
-def from_loader(loader, expected_batch, capacity, sampler, repetitions=1, shape=None):
+def from_loader(loader, expected_batch, capacity, sampler, repetitions=1, shape=None, micro_batches=1):
     """The Poisson-sampled form of imagefolder.DeviceLoader (-> PoissonLoader) or imagefolder.AugmentingLoader
     (-> PoissonAugmentingLoader; `shape`: one transformed image's)."""
     if hasattr(loader, "images"):
         return PoissonAugmentingLoader(loader.images, loader.targets, loader.tf, loader.rng, expected_batch, capacity,
-                                       sampler, shape)
-    return PoissonLoader(loader.data, loader.targets, expected_batch, capacity, sampler, repetitions)
+                                       sampler, shape, micro_batches=micro_batches)
+    return PoissonLoader(loader.data, loader.targets, expected_batch, capacity, sampler, repetitions,
+                         micro_batches=micro_batches)

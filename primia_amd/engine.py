@@ -398,7 +398,7 @@ class ResNet18Engine:
                                     groups=self.groups, options=self._root._options, share=self._root)
         # what the host sets on the root after construction travels with every call: the optimizer's fused tail and —
         # above all — the DP-SGD parameters (a halved or ragged batch must be clipped and noised like every other)
-        for attr in ("fuse_sgd_tail", "dp_params", "dp_noise", "class_weight"):
+        for attr in ("fuse_sgd_tail", "dp_params", "dp_noise", "dp_micro_batches", "class_weight"):
             setattr(sib[n], attr, getattr(self._root, attr))
         sib[n].train(self.training)
         return sib[n]
@@ -645,6 +645,21 @@ class ResNet18Engine:
     # ------------------------------------------------------------------------------------------
     dp_params = None  # e.g. {"max_grad_norm": 1.0, "noise_multiplier": 1.3}: loss_backward() becomes DP-SGD
     dp_noise = None   # a primia_amd.dp_noise.DeviceNoise: the DP-SGD noise is its ChaCha20 stream instead of torch.randn
+    # A logical DP-SGD step larger than the engine (primia_amd.dp_micro.step): the host loops run it as this many passes of
+    # N slots each.  The step helper sets, on the ROOT, the phase of the pass about to run (None: an ordinary step;
+    # "first" / "more": clipped sum into dp_acc; "last": dp_acc + this pass, noise, division) and the logical batch size.
+    dp_micro_batches = 1
+    dp_phase = None
+    dp_logical_batch = None
+
+    @property
+    def dp_acc(self):
+        """fp32 [P]: the clipped sums of a logical step's passes so far.  The root's, like dp_noise: a ragged piece on a
+        sibling accumulates into the same sum.  Created at first use — before any capture (graphed_train)."""
+        root = self._root
+        if root.__dict__.get("_dp_acc") is None:
+            root._dp_acc = torch.zeros(self.P, dtype=torch.float32, device=self.device)
+        return root._dp_acc
 
     def loss_backward(self, target, soft=False):
         """Cross entropy (hard int64 labels, or soft [N, classes] fp32 targets as in
@@ -652,6 +667,10 @@ class ResNet18Engine:
         if self.dp_params is not None:
             if soft:
                 raise _lib.PrimiaError("DP-SGD path takes hard labels")
+            phase = getattr(self._root, "dp_phase", None)
+            if phase is not None:
+                return self.dp_loss_backward(target, **self.dp_params, accumulate=phase,
+                                             logical_batch=self._root.dp_logical_batch)
             return self.dp_loss_backward(target, **self.dp_params)
         if soft:
             call("primia_xent_soft", self.logits, target, self.class_weight, self.loss, self.dlogits, self.N,
@@ -1188,7 +1207,7 @@ class ResNet18Engine:
     # DP-SGD (BASELINE.json configs[3]; parameter values of train.py:325-334)
     # ------------------------------------------------------------------------------------------
     def dp_loss_backward(self, target, max_grad_norm=1.0, noise_multiplier=1.3, noise=None, generator=None,
-                         expected_batch=None):
+                         expected_batch=None, accumulate=None, logical_batch=None):
         """Per-sample gradient clipping + Gaussian noise, pytorch-dp semantics:
             g = (1/B) * ( sum_n min(1, C / (||g_n|| + 1e-6)) * g_n  +  N(0, (noise_multiplier*C)^2 I) )
         with g_n the gradient of sample n's OWN loss over all 62 parameter tensors (flat L2 norm).
@@ -1205,8 +1224,18 @@ class ResNet18Engine:
         `expected_batch` (a float L: dp_params of a Poisson-sampled run, primia_amd.dp_sampling): the batch is a
         fixed-capacity one whose padded slots carry target -1.  Those get a zero dlogits row and a zero clip factor —
         every contribution of theirs to the norms and the clipped sums is exactly zero — and the noised sum is divided
-        by L, not by the number of slots: the sampled Gaussian mechanism the accountant (dp_accountant) bounds."""
+        by L, not by the number of slots: the sampled Gaussian mechanism the accountant (dp_accountant) bounds.
+
+        `accumulate` (primia_amd.dp_micro: a logical step of `logical_batch` samples cut into passes of N slots; the sum
+        above splits exactly into the passes' clipped sums).  "first" / "more": everything up to the clipped sums as
+        usual, then dp_acc = grads / dp_acc += grads — no noise, no division.  "last": grads = ((dp_acc + grads) +
+        noise) / B in one kernel, B = expected_batch on masked batches and logical_batch otherwise: one noise draw and
+        one counter advance per logical step.  None: an ordinary step."""
         masked = expected_batch is not None
+        if accumulate not in (None, "first", "more", "last"):
+            raise ValueError("dp_loss_backward: accumulate is None, 'first', 'more' or 'last'")
+        if accumulate is not None and not masked and not logical_batch:
+            raise ValueError("dp_loss_backward: a micro-batch pass needs logical_batch (or expected_batch)")
         if self.norm not in ("group", "frozen"):
             raise _lib.PrimiaError("DP-SGD needs per-sample independent norm layers: ResNet18Engine(norm='group') or "
                                    "norm='frozen' (BatchNorm with fixed statistics)")
@@ -1355,16 +1384,23 @@ class ResNet18Engine:
             if getattr(self, "dp_keep_operands", False):      # tests: the (layer, x, dy) triples the norm pass walked
                 self.dp_operands = list(self.dp["wgrads"])
             self.dp = None
+        self.dp_stats = {"sq_norms": sq, "clip": clip}
+        if accumulate in ("first", "more"):
+            call("primia_dp_accumulate", self.dp_acc, self.grads, self.P, 1 if accumulate == "first" else 0)
+            return self.loss
+        acc = self.dp_acc if accumulate == "last" else None
         sigma = float(noise_multiplier * max_grad_norm)
-        inv_batch = 1.0 / float(expected_batch) if masked else 1.0 / N
+        inv_batch = 1.0 / float(expected_batch) if masked else 1.0 / (N if acc is None else int(logical_batch))
         if noise is None and generator is None and self._root.dp_noise is not None:
             # the ROOT's stream, whichever sibling runs the step: a halved or ragged batch advances the one counter
-            self._root.dp_noise.add_to(self.grads, self.P, sigma, inv_batch)
+            self._root.dp_noise.add_to(self.grads, self.P, sigma, inv_batch, acc=acc)
         else:
             if noise is None:
                 noise = torch.randn(self.P, dtype=torch.float32, device=dev, generator=generator)
-            call("primia_dp_add_noise", self.grads, noise, self.P, sigma, inv_batch)
-        self.dp_stats = {"sq_norms": sq, "clip": clip}
+            if acc is None:
+                call("primia_dp_add_noise", self.grads, noise, self.P, sigma, inv_batch)
+            else:
+                call("primia_dp_add_noise_acc", self.grads, acc, noise, self.P, sigma, inv_batch)
         return self.loss
 
     dp_keep = True

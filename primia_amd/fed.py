@@ -301,7 +301,12 @@ def federated_epoch(engine, loader, args, optimizer=None, group=None, ops=None, 
     for batch_idx in range(sched.max_batches):
         if sched.trains(rank, batch_idx):
             data, target = next(it)
-            if hip_graph:
+            if getattr(engine, "dp_micro_batches", 1) > 1:
+                # the loader's batch is ONE logical DP-SGD step, run as passes of the engine's size (dp_micro)
+                from . import dp_micro
+
+                losses.append(dp_micro.step(engine, optimizer, data, target, hip_graph=hip_graph).clone())
+            elif hip_graph:
                 losses.append(graphed_step(engine, optimizer, data, target, soft=soft_targets).clone())
             else:
                 optimizer.zero_grad()

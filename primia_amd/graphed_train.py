@@ -25,6 +25,12 @@ stream's device counter and the next node advances it, so every replay draws fre
 "Poisson-sampled", serves every step whatever the number of records selected.  The
 first step of a key runs eagerly (real training that also allocates the engine's lazy buffers), the second is captured
 and replayed.
+
+A DP-SGD step cut into micro-batch passes (primia_amd.dp_micro: the root's `dp_phase` is set) is captured per PHASE: the
+key gains ("micro-batch", phase, 1 / batch), the "first" and "more" graphs end with the clipped sum going into the root's
+accumulator and hold no optimizer step (they advance no step count), the "last" graph holds the noise node and the
+optimizer step.  Two graphs per engine for two passes, three for more.  A ragged final pass runs eagerly under the size
+rule above, between replayed ones: the accumulator is a plain buffer.
 """
 import gc
 import warnings
@@ -52,12 +58,18 @@ def eager_reason(engine, optimizer, batch_size):
     return None
 
 
+def _phase(eng):
+    """The micro-batch phase the step helper (dp_micro.step) has set on the root engine, or None."""
+    return getattr(getattr(eng, "_root", eng), "dp_phase", None)
+
+
 def _eager(engine, eng, optimizer, data, target, soft):
     """The loops' step as it is without --hip_graph."""
     optimizer.zero_grad()
     eng.forward(data)
     loss = eng.loss_backward(target, soft=soft)
-    optimizer.step() if eng is engine else optimizer.step(eng)
+    if _phase(eng) in (None, "last"):       # (an accumulating micro-batch pass takes no optimizer step)
+        optimizer.step() if eng is engine else optimizer.step(eng)
     return loss
 
 
@@ -74,6 +86,11 @@ def _key(eng, optimizer, soft):
         if dp.get("expected_batch") is not None:
             # padded fixed-capacity batches (dp_sampling.PoissonLoader): other loss and clip kernels, 1 / L in the noise node
             key += ("Poisson-sampled", float(dp["expected_batch"]))
+        phase = getattr(root, "dp_phase", None)
+        if phase is not None:
+            # a pass of a step cut into micro-batches: other tail kernels per phase, 1 / batch in the last one's noise node
+            inv = 1.0 / float(dp["expected_batch"] if dp.get("expected_batch") is not None else root.dp_logical_batch)
+            key += ("micro-batch", phase, inv)
     return key
 
 
@@ -110,6 +127,7 @@ def _fingerprint(eng, g):
         ts += list(eng.opt_state)
     if getattr(eng._root, "dp_params", None) is not None:       # (the per-step DP buffers are the graph pool's own)
         ts += [eng._root.dp_noise.counter] + list(eng._dp_keep_buffers().values())
+        ts += [eng._root.__dict__.get("_dp_acc")]         # (None unless a step has run as micro-batch passes)
     return tuple(t.data_ptr() if t is not None else 0 for t in ts) + (len(eng.relu_masks),)
 
 
@@ -126,6 +144,9 @@ class _StepGraph:
             _sync_moments(root)
         if getattr(root, "dp_noise", None) is not None:
             root.dp_noise.counter       # exists BEFORE the capture: allocated inside, every replay would zero it again
+        phase = _phase(eng)
+        if phase is not None:
+            eng.dp_acc                  # likewise: the passes of a step hand their sums on through it
         # capture runs the step's Python (forward / optimizer.step advance the host counters) without executing a kernel:
         # keep what one step advances them by, and put them back
         nbt = dict(eng.num_batches_tracked)
@@ -142,7 +163,8 @@ class _StepGraph:
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
                 eng.forward(self.x)
                 eng.loss_backward(self.target, soft=self.soft)
-                optimizer.step(eng, hyper=self.hyper)
+                if phase in (None, "last"):
+                    optimizer.step(eng, hyper=self.hyper)
         finally:
             if gc_on:
                 gc.enable()

@@ -303,6 +303,13 @@ def secure_aggregation_epoch(args, models, device, train_loaders, optimizers, ep
             optimizers[i].zero_grad()
             data, target = next(it)
             soft = getattr(loss_fns.get(i), "soft", False) if loss_fns else False
+            if getattr(models[i], "dp_micro_batches", 1) > 1:
+                # the loader's batch is ONE logical DP-SGD step, run as passes of the engine's size (dp_micro)
+                from . import dp_micro
+
+                loss = dp_micro.step(models[i], optimizers[i], data, target, hip_graph=hip_graph)
+                avg_loss.append(loss.clone() if hip_graph else loss.item())
+                continue
             if hip_graph:
                 # the device loss stays on the device until the epoch ends (no wait on the GPU per step)
                 avg_loss.append(graphed_step(models[i], optimizers[i], data, target, soft=soft).clone())
@@ -363,7 +370,12 @@ def train(args, model, device, train_loader, optimizer, epoch, loss_fn, num_clas
             soft = True
         # MixUp mixes the two halves of a batch with probability mixup_prob and passes it on whole otherwise: consecutive
         # steps see B or B / 2 samples (:1262-1267).  A sibling engine serves the other size on the same parameters.
-        if getattr(args, "hip_graph", False):
+        if getattr(model, "dp_micro_batches", 1) > 1:
+            # the loader's batch is ONE logical DP-SGD step, run as passes of the engine's size (dp_micro)
+            from . import dp_micro
+
+            loss = dp_micro.step(model, optimizer, data, target, hip_graph=getattr(args, "hip_graph", False))
+        elif getattr(args, "hip_graph", False):
             from .graphed_train import graphed_step
 
             loss = graphed_step(model, optimizer, data, target, soft=soft)
@@ -492,7 +504,14 @@ def test(args, model, device, val_loader, epoch, loss_fn, num_classes, verbose=T
     for data, target in val_loader:
         # (a ragged final batch — every validation sample counts — runs on a sibling engine of that size; eval-mode
         # BatchNorm makes the logits independent of how the samples are batched)
-        logits = (model.sibling(data.shape[0]) if hasattr(model, "sibling") else model).forward(data)
+        if getattr(model, "dp_micro_batches", 1) > 1 and data.shape[0] > model._root.N:
+            # an engine built for micro-batches is smaller than a validation batch: walk it in views of the engine's size
+            # (a sibling of the whole batch would spend the memory the micro-batches save; logits do not depend on batching)
+            m = model._root.N
+            logits = torch.cat([model.sibling(min(m, data.shape[0] - s)).forward(data[s:s + m]).clone()
+                                for s in range(0, data.shape[0], m)])
+        else:
+            logits = (model.sibling(data.shape[0]) if hasattr(model, "sibling") else model).forward(data)
         ls = torch.log_softmax(logits, dim=1)
         nll.append(-ls.gather(1, target.view(-1, 1)).reshape(-1).double().cpu())
         scores.append(logits.detach().float().cpu().numpy().copy())

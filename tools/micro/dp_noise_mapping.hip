@@ -71,7 +71,7 @@ int main(int argc, char** argv) {
     CHECK(hipMalloc(&gb, bytes));
     auto launch = [&](int which, float* g, float inv_b) {
         if (which == 0)
-            dp_noise_add_kernel<<<ceil_div((n + 15) / 16, 256), 256>>>(key, 7, nullptr, g, n, 1.3f, inv_b);
+            dp_noise_add_kernel<false><<<ceil_div((n + 15) / 16, 256), 256>>>(key, 7, nullptr, g, nullptr, n, 1.3f, inv_b);
         else
             dp_noise_add_quarter_kernel<<<ceil_div((n + 3) / 4, 256), 256>>>(key, 7, nullptr, g, n, 1.3f, inv_b);
     };

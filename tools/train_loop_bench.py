@@ -12,7 +12,11 @@ device ChaCha20 stream of primia_amd.dp_noise; --hip_graph replays the steps); -
 network with frozen statistics (train.py's --dp_norm frozen) instead.  --dp_sampling poisson times train.py's Poisson-sampled
 loop: --records synthetic records, expected batch --batch, the engine at the capacity dp_accountant.capacity_for gives for
 --planned_steps; every step is select + gather (primia_amd.dp_sampling.PoissonLoader) and the masked DP step; images per
-second then counts the EXPECTED batch.  Needs a GPU (there is no CPU path)."""
+second then counts the EXPECTED batch.  --dp_micro_batches K (train.py's flag) runs every step as K passes on an engine of
+1 / K of the batch or capacity (primia_amd.dp_micro); ms per step is then per LOGICAL step.  With --dp the line also
+carries the engine's slots and, per mode, the peak of torch.cuda.max_memory_allocated() over what was allocated before that
+mode's engine was built (the batches, the records, an earlier mode's engine), read after the mode's warm-up: the engine,
+its DP buffers and, graphed, the graphs' pools.  Needs a GPU (there is no CPU path)."""
 import argparse
 import json
 import os
@@ -43,8 +47,12 @@ def main():
                     help="with --dp: train.py's --dp_sampling")
     ap.add_argument("--records", type=int, default=1721, help="--dp_sampling poisson: records sampled from")
     ap.add_argument("--planned_steps", type=int, default=280, help="--dp_sampling poisson: steps the capacity is sized for")
+    ap.add_argument("--dp_micro_batches", type=int, default=1, help="with --dp: train.py's --dp_micro_batches")
     a = ap.parse_args()
     poisson = a.dp and a.dp_sampling == "poisson"
+    K = a.dp_micro_batches if a.dp else 1
+    if K < 1 or (not poisson and a.batch % K):
+        raise SystemExit("--dp_micro_batches: at least 1, and in shuffle mode a divisor of --batch")
     if not torch.cuda.is_available():
         raise SystemExit("train_loop_bench needs a GPU")
 
@@ -79,20 +87,24 @@ def main():
             def __iter__(self):
                 return (self.pl.draw() for _ in range(self.count))
     modes = a.modes.split(",")
-    runs = {}
+    runs, peak = {}, {}
     for m in modes:
         torch.manual_seed(42)
-        eng = ResNet18Engine(capacity, 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
+        torch.cuda.synchronize()
+        held = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        eng = ResNet18Engine(-(-capacity // K), 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
                              norm=a.dp_norm if a.dp else "batch")
         eng.init_weights()
         if a.dp:
             eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": 1.3}
+            eng.dp_micro_batches = K
             if a.dp_noise == "chacha":
                 from primia_amd.dp_noise import DeviceNoise
 
                 eng.dp_noise = DeviceNoise(dev)
             if poisson:
-                pl = PoissonLoader(records, labels, a.batch, capacity, DeviceSampler(dev))
+                pl = PoissonLoader(records, labels, a.batch, capacity, DeviceSampler(dev), micro_batches=K)
                 eng.dp_params["expected_batch"] = pl.expected_batch
         args = SimpleNamespace(optimizer="SGD", lr=1e-4, weight_decay=5e-4, log_interval=10 ** 9, mixup=False,
                                hip_graph=m == "graph")
@@ -101,6 +113,8 @@ def main():
         warm = Draws(pl, max(3, a.buffers)) if poisson else loader[:max(3, a.buffers)]
         train(args, eng, dev, warm, opt, 0, None, verbose=False)   # warm-up (+ capture)
         runs[m] = (eng, args, opt, [], mine)
+        torch.cuda.synchronize()
+        peak[m] = torch.cuda.max_memory_allocated() - held
     torch.cuda.synchronize()
     for _ in range(a.runs):
         for m in modes:
@@ -119,6 +133,7 @@ def main():
         out["dp_norm"] = a.dp_norm
         out["graphed_keys"] = {m: len(captures(runs[m][0])) for m in modes}
         out["dp_sampling"] = a.dp_sampling
+        out.update(dp_micro_batches=K, engine_slots=runs[modes[0]][0].N, peak_bytes_over_held=peak)
         if poisson:
             out.update(records=a.records, capacity=capacity, planned_steps=a.planned_steps,
                        overflow_events={m: runs[m][4].pl.sampler.overflow_events() for m in modes})

@@ -6,7 +6,7 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
     python train.py --config configs/torch/pneumonia-resnet-pretrained.ini --train_federated \
         [--unencrypted_aggregation] [--data_dir DIR|synthetic] [--cuda] [--resume_checkpoint P] \
         [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N] \
-        [--dp_norm {group,frozen}] [--dp_sampling {shuffle,poisson}] [--dp_delta D]
+        [--dp_norm {group,frozen}] [--dp_sampling {shuffle,poisson}] [--dp_delta D] [--dp_micro_batches K]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -27,6 +27,8 @@ Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 `--dp_sampling poisson` (with differentially_private = yes) draws every step's batch by Poisson sampling on the device
 (primia_amd.dp_sampling), divides the noised sum by the expected batch size and reports the (epsilon, delta) the run
 has spent per client after every epoch (primia_amd.dp_accountant); the ledger travels in the checkpoint (`dp_privacy`).
+`--dp_micro_batches K` runs every DP-SGD step as K passes on an engine of 1 / K of the batch (primia_amd.dp_micro): a
+logical batch larger than one engine's activations allow, with one noise draw and one optimizer step per batch.
 
 `main(args, verbose, optuna_trial, cmd_args)` returns the best validation MCC like the reference's.
 """
@@ -222,6 +224,29 @@ def poisson_mode(args, cmd_args):
     return kind == "poisson" and bool(args.differentially_private)
 
 
+def micro_batch_mode(args, cmd_args):
+    """K of --dp_micro_batches: every loader batch is one logical DP-SGD step run as K passes of an engine of 1 / K of its
+    size (primia_amd.dp_micro).  1 without differentially_private = yes, where the flag warns and does nothing like the
+    other --dp_* flags (plain gradient accumulation would change BatchNorm's statistics)."""
+    k = int(getattr(cmd_args, "dp_micro_batches", 1)) if cmd_args is not None else 1
+    if k > 1 and not args.differentially_private:
+        warn("--dp_micro_batches {:d} has no effect: the config has differentially_private = no, every batch is one "
+             "pass".format(k))
+        return 1
+    return max(1, k)
+
+
+def micro_batch_size(slots, k, poisson):
+    """M, the slots of one pass: batch_size / K in shuffle mode, where a batch_size K does not divide is refused;
+    ceil(capacity / K) in Poisson mode (the K * M - capacity extra slots are padding)."""
+    if poisson:
+        return -(-int(slots) // int(k))
+    if int(slots) % int(k):
+        raise SystemExit("--dp_micro_batches {:d} does not divide batch_size {:d}: the passes of a shuffled batch are all "
+                         "the same size".format(int(k), int(slots)))
+    return int(slots) // int(k)
+
+
 def poisson_plan(name, n, batch_size, epochs, delta, sigma, spent=None):
     """(q, planned steps, capacity) of a client with n records: q = floor(batch_size * 2^64 / n) / 2^64 — the probability
     the kernel samples with is the one the accountant is given — over epochs * ceil(n / batch_size) steps.  An expected
@@ -297,6 +322,12 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
 
     dp_delta = float(getattr(cmd_args, "dp_delta", 1e-5)) if cmd_args is not None else 1e-5
     poisson = poisson_mode(args, cmd_args)
+    micro = micro_batch_mode(args, cmd_args)
+    if micro > 1 and not poisson:       # (refused before any data is registered; a Poisson capacity is rounded up)
+        m = micro_batch_size(args.batch_size, micro, False)
+        if rank == 0:
+            print("dp_micro_batches: every step of {:d} samples runs as K = {:d} passes on an engine of M = {:d} "
+                  "slots".format(args.batch_size, micro, m))
     dp_sigma = 1.3
     privacy = {}        # Poisson sampling: {client name: dp_accountant.Ledger}
     # a resumed Poisson run sizes every client's capacity from what the checkpoint's ledger has spent plus the epochs
@@ -329,7 +360,11 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         led = privacy[name] = dp_accountant.Ledger(n, capacity, dp_delta, planned)
         if old is not None:     # the ledger goes on counting; a changed q, sigma or capacity opens a new segment
             led.segments, led.capacities, led.overflow_events = old.segments, old.capacities, old.overflow_events
-        return dps.from_loader(base, args.batch_size, capacity, sampler, fed_reps, (channels, size, size))
+        if micro > 1 and rank == 0:
+            print("dp_micro_batches: {:s}'s steps of capacity {:d} run as K = {:d} passes on an engine of M = {:d} "
+                  "slots".format(name, capacity, micro, micro_batch_size(capacity, micro, True)))
+        return dps.from_loader(base, args.batch_size, capacity, sampler, fed_reps, (channels, size, size),
+                               micro_batches=micro)
 
     def synthetic_records(batches, seed):
         sl = SyntheticLoader(batches, args.batch_size, size, num_classes, device, seed, channels)
@@ -341,9 +376,12 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         # differentially_private = yes (train.py:304-334 of the reference): BatchNorm is rejected by the
         # PrivacyEngine, so the network is built with GroupNorm — or (--dp_norm frozen) BatchNorm is applied with its
         # running statistics held fixed, which keeps samples independent too — and every step clips / noises per sample
-        eng = ResNet18Engine(args.batch_size if batch is None else batch, num_classes, channels, size, args.pooling_type,
+        # (--dp_micro_batches K: the engine holds one PASS, 1 / K of the loaders' batch or capacity)
+        slots = micro_batch_size(args.batch_size if batch is None else batch, micro, poisson)
+        eng = ResNet18Engine(slots, num_classes, channels, size, args.pooling_type,
                              dtype=dtype, device=device, norm=dp_norm if args.differentially_private else "batch")
         if args.differentially_private:
+            eng.dp_micro_batches = micro
             eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": dp_sigma}
             if expected_batch is not None:      # padded Poisson batches: masked loss / clip, the noised sum over q * n
                 eng.dp_params["expected_batch"] = float(expected_batch)
@@ -650,6 +688,20 @@ def build_parser():
                              "and stored in the checkpoint (dp_privacy).")
     parser.add_argument("--dp_delta", type=float, default=1e-5,
                         help="--dp_sampling poisson: the delta of the reported (epsilon, delta)")
+
+    def passes(text):
+        k = int(text)
+        if k < 1:
+            raise argparse.ArgumentTypeError("at least 1 pass per step")
+        return k
+
+    parser.add_argument("--dp_micro_batches", type=passes, default=1, metavar="K",
+                        help="differentially_private = yes: run every step as K passes of (forward, per-sample clip, "
+                             "clipped sum) on an engine of 1 / K of the batch (shuffle: batch_size must be a multiple of K) "
+                             "or of the capacity (poisson: rounded up, the extra slots are padding); the sums meet in an "
+                             "fp32 accumulator, noise is added once, the sum is divided once and one optimizer step "
+                             "follows.  The mechanism and the reported (epsilon, delta) are those of the whole batch; "
+                             "activation memory is that of one pass.")
     return parser
 
 
