@@ -764,6 +764,46 @@ int primia_dp_add_noise_acc(float* g, const float* acc, const float* noise, int6
                             primia_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DP-SGD with an adaptive clipping norm C held in a device word (csrc/dp_clip.hip, primia_amd/dp_clip.py): quantile-based
+ * adaptive clipping (Andrew, Thakkar, McMahan, Ramaswamy, NeurIPS 2021).  Replaces Opacus-style adaptive clipping on top
+ * of the reference's PrivacyEngine (AdaClipDPOptimizer; not part of the reference tree, whose max_grad_norm is the
+ * literal 1.0 of train.py:325-334).  A captured step freezes its launch arguments, so every kernel that needs C reads
+ * *clip_norm, one float32 on the device, and C moving never re-captures a graph.
+ * ------------------------------------------------------------------------------------------ */
+/* clip[n] = primia_dp_clip_factors' value (target == NULL) or primia_dp_clip_factors_masked's (0 where target[n] < 0) with
+ * max_grad_norm = *clip_norm, bit for bit, and the two counts the update releases: below = #{valid n : sq[n] <=
+ * (double)C * (double)C}, valid = #{n : target == NULL or target[n] >= 0}.  counts[0..1] = {below, valid} (overwrite != 0:
+ * a step's first or only pass) or += them.  One block, a wave reduction and a cross-wave one in LDS, no atomics: a pure
+ * function of its inputs.  PRIMIA_ERR_ARG for N <= 0 or a NULL sq / clip / clip_norm / counts. */
+int primia_dp_clip_factors_dev(const double* sq, const int64_t* target, float* clip, int N, const float* clip_norm,
+                               int32_t* counts, int overwrite, primia_stream_t stream);
+/* primia_dp_noise_add (acc == NULL) / primia_dp_noise_add_acc called with sigma = noise_multiplier * *clip_norm, one
+ * float32 product, bit for bit.  Arguments, counter rule and refusals as those; a NULL clip_norm is refused too. */
+int primia_dp_noise_add_dev(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce, const uint64_t* counter,
+                            uint64_t block_offset, float* g, const float* acc, int64_t n, const float* clip_norm,
+                            float noise_multiplier, float inv_batch, primia_stream_t stream);
+/* The same for host-supplied noise: primia_dp_add_noise (acc == NULL) / primia_dp_add_noise_acc with that sigma. */
+int primia_dp_add_noise_dev(float* g, const float* acc, const float* noise, int64_t n, const float* clip_norm,
+                            float noise_multiplier, float inv_batch, primia_stream_t stream);
+/* The geometric update towards the target quantile gamma, float64 inside:
+ *     s = (counts[0] - counts[1] / 2) + sigma_b * z0          the released scalar; one record moves it by 1 / 2
+ *     b = s * inv_batch + 1 / 2                                the noisy fraction of norms at or below C
+ *     C' = clamp(C * exp(-eta * (b - gamma)), c_min, c_max)    rounded once to float32 and stored in *clip_norm
+ * released[0] = (float)b when released is not NULL.  z0 = *z, a device float (a standard normal value the caller drew).
+ * The stored C is always inside [c_min, c_max] (a NaN product goes to c_min).  PRIMIA_ERR_ARG for a NULL clip_norm /
+ * counts / z, sigma_b <= 0, inv_batch <= 0, eta < 0, gamma outside (0, 1), a range that is not 0 < c_min <= c_max, or a
+ * non-finite argument. */
+int primia_dp_clip_update(float* clip_norm, const int32_t* counts, const float* z, float sigma_b, float inv_batch, float eta,
+                          float gamma, float c_min, float c_max, float* released, primia_stream_t stream);
+/* The same with z0 = element 0 of block (counter ? *counter : 0) + block_offset of primia_dp_noise_add's noise (the same
+ * device function).  `counter` is read, not advanced: a step that noises P elements and then updates C passes
+ * block_offset = primia_dp_noise_blocks(P) and follows with primia_u64_add(counter, primia_dp_noise_blocks(P) + 1). */
+int primia_dp_clip_update_chacha(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce, const uint64_t* counter,
+                                 uint64_t block_offset, float* clip_norm, const int32_t* counts, float sigma_b,
+                                 float inv_batch, float eta, float gamma, float c_min, float c_max, float* released,
+                                 primia_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DP-SGD on Poisson-sampled batches (csrc/dp_sample.hip).  The sampled-Gaussian privacy bound (primia_amd/dp_accountant.py)
  * needs every record to join a step's batch independently with probability q by a secret draw.  Replaces the shuffled
  * DataLoader of the reference's training loop (torch.randperm under the command line's seed) and, for the padded slots

@@ -156,6 +156,16 @@ __host__ __device__ __forceinline__ bool pool_xhat_recoverable(float gamma, floa
 // (optim.hip) and the fused gradient-finalize + step + weight-refresh tiles (layout.hip): the two must agree bit for bit.
 __device__ __forceinline__ float sgd_update(float p, float g, float lr, float wd) { return p - lr * (g + wd * p); }
 
+// DP-SGD's per-sample clip factor min(1, C / (||g_n|| + 1e-6)) from the float64 squared norm (pytorch-dp's expression), and
+// the Gaussian mechanism on one element of the clipped sum.  ONE definition each for the entry points that take C and
+// sigma as host floats (gn.hip, dp_sample.hip, dp_noise.hip) and the ones that read C from a device word (dp_clip.hip): the
+// two families must agree bit for bit.
+__device__ __forceinline__ float dp_clip_factor(double sq, float max_norm) {
+    const double f = (double)max_norm / (sqrt(sq) + 1e-6);
+    return (float)(f < 1.0 ? f : 1.0);
+}
+__device__ __forceinline__ float dp_noise_apply(float v, float z, float sigma, float inv_b) { return (v + z * sigma) * inv_b; }
+
 // Word offsets of an optimizer's device scalars (the `hyper` array of the *_dev entry points, primia_opt_hyper_set):
 // {lr, weight_decay, beta1, beta2, eps, lr / bc1, 1 / sqrt(bc2), 0}
 enum { kHyperLr = 0, kHyperWd, kHyperBeta1, kHyperBeta2, kHyperEps, kHyperStepSize, kHyperInvSqrtBc2, kHyperWords = 8 };

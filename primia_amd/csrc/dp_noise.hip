@@ -17,65 +17,18 @@
 // One thread = one 64-byte block = 16 gradient elements, read and written as four 16-byte accesses; a workgroup covers
 // 4096 elements.  (The other mapping measured — four lanes per block, 16 bytes each, every lane computing the block —
 // is tools/micro/dp_noise_mapping.hip; profiles/dp_noise.txt has both.)
-#include "chacha_block.h"
+#include "dp_noise_core.h"
 
 namespace primia {
 
-// Box-Muller on one 64-bit keystream word (a = low half, c = high half)
-__device__ __forceinline__ void dp_noise_pair(uint32_t a, uint32_t c, float& z_even, float& z_odd) {
-    const float u1 = (float)((a >> 8) + 1u) * 0x1p-24f;      // integers <= 2^24: both conversions are exact
-    const float u2 = (float)(c >> 8) * 0x1p-24f;
-    const float r = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(2.0f * u2, &sn, &cs);
-    z_even = r * cs;
-    z_odd = r * sn;
-}
-
 // ACC = false: primia_dp_noise_add as described above (`acc` is not read).  ACC = true (primia_dp_noise_add_acc: the last
-// pass of a step cut into micro-batches, primia_amd/dp_micro.py) reads a second, read-only arena `acc` — the clipped sums
-// of the earlier passes — and the expression gets v = acc + g in front: g = ((acc + g) + z * sigma) * inv_b, the same
-// rounding as the ACC = false kernel applied to the float32 sum.  The acc loads are issued with the g loads.
+// pass of a step cut into micro-batches, primia_amd/dp_micro.py) adds the clipped sums of the earlier passes in front.
+// The body is dp_noise_core.h's, shared with the kernels that read the clipping norm from the device (dp_clip.hip).
 template <bool ACC>
 __global__ __launch_bounds__(256) void dp_noise_add_kernel(ChaChaKey key, uint64_t block0, const uint64_t* __restrict__ counter,
                                                            float* __restrict__ g, const float* __restrict__ acc, int64_t n,
                                                            float sigma, float inv_b) {
-    const int64_t blk = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (blk * 16 >= n) return;
-    float* o = g + blk * 16;
-    const float* a = ACC ? acc + blk * 16 : nullptr;
-    const bool full = blk * 16 + 16 <= n;
-    f32x4 v[4], w[4];
-    if (full) {     // issued before the 20 rounds: their latency hides behind the integer work
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = *(const f32x4*)(o + 4 * i);
-        if (ACC) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) w[i] = *(const f32x4*)(a + 4 * i);
-        }
-    }
-    const uint64_t ctr = block0 + (counter ? *counter : 0) + (uint64_t)blk;
-    uint32_t x[16];
-    chacha20_block(key, ctr, x);
-    float z[16];
-#pragma unroll
-    for (int p = 0; p < 8; ++p) dp_noise_pair(x[2 * p], x[2 * p + 1], z[2 * p], z[2 * p + 1]);
-    if (full) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (ACC) v[i] = w[i] + v[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] + z[4 * i + j] * sigma) * inv_b;
-            *(f32x4*)(o + 4 * i) = v[i];
-        }
-    } else {        // the partial last block: its first n % 16 values
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (blk * 16 + i < n) {
-                const float vi = ACC ? a[i] + o[i] : o[i];
-                o[i] = (vi + z[i] * sigma) * inv_b;
-            }
-    }
+    dp_noise_add_block<ACC>(key, block0, counter, g, acc, n, sigma, inv_b);
 }
 
 // The clipped sum of one micro-batch pass into the step's fp32 accumulator: acc = g (the first pass) or acc += g.  One

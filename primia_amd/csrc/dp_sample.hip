@@ -156,8 +156,7 @@ __global__ void dp_clip_factor_masked_kernel(const double* __restrict__ sq, cons
                                              float* __restrict__ clip, int N, float max_norm) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    const double f = (double)max_norm / (sqrt(sq[n]) + 1e-6);      // dp_clip_factor_kernel's expression (gn.hip)
-    clip[n] = target[n] < 0 ? 0.f : (float)(f < 1.0 ? f : 1.0);
+    clip[n] = target[n] < 0 ? 0.f : dp_clip_factor(sq[n], max_norm);      // dp_clip_factor_kernel's expression (common.h)
 }
 
 }  // namespace primia

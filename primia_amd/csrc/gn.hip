@@ -595,8 +595,7 @@ __global__ __launch_bounds__(256) void persample_sqnorm_many_kernel(const float*
 __global__ void dp_clip_factor_kernel(const double* __restrict__ sq, float* __restrict__ clip, int N, float max_norm) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    const double f = (double)max_norm / (sqrt(sq[n]) + 1e-6);
-    clip[n] = (float)(f < 1.0 ? f : 1.0);
+    clip[n] = dp_clip_factor(sq[n], max_norm);
 }
 
 // x[row][:] *= s[row / rows_per_sample]
@@ -699,7 +698,8 @@ __global__ __launch_bounds__(256) void fc_persample_kernel(const float* __restri
 __global__ __launch_bounds__(256) void dp_noise_kernel(float* __restrict__ g, const float* __restrict__ noise, long n,
                                                        float sigma, float inv_b) {
     const long stride = (long)gridDim.x * 256;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) g[i] = (g[i] + noise[i] * sigma) * inv_b;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+        g[i] = dp_noise_apply(g[i], noise[i], sigma, inv_b);
 }
 
 // ... with the clipped sums of a step's earlier micro-batch passes (acc, read only) added in front
@@ -708,7 +708,7 @@ __global__ __launch_bounds__(256) void dp_noise_acc_kernel(float* __restrict__ g
                                                            float inv_b) {
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-        g[i] = ((acc[i] + g[i]) + noise[i] * sigma) * inv_b;
+        g[i] = dp_noise_apply(acc[i] + g[i], noise[i], sigma, inv_b);
 }
 
 static inline int gn_stream_blocks(long nchunks) {

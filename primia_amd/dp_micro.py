@@ -9,7 +9,8 @@ The logical batch runs as passes of (forward, per-sample clip, clipped sum) on a
 but the last adds its clipped sum to the root's fp32 accumulator (primia_dp_accumulate into engine.dp_acc), the last one
 adds the accumulator, the noise — ONE draw, one counter advance — and the division in one kernel
 (primia_dp_noise_add_acc), and ONE optimizer step follows.  The mechanism, its sensitivity and the accountant are those
-of the whole batch; only the execution is cut into pieces (pytorch-dp calls this a virtual step).
+of the whole batch; only the execution is cut into pieces (pytorch-dp calls this a virtual step).  An adaptive clipping
+norm (engine.dp_clip) is read by every pass and moved once, by the last one, on the counts summed over all passes.
 
 Not bit-identical to the same batch on one large engine: the clipped sum is added up in another order (per pass, then
 across passes in float32).  Bit-identical: a pass whose slots are all padding (target -1) adds exact zeros, and a step

@@ -398,7 +398,7 @@ class ResNet18Engine:
                                     groups=self.groups, options=self._root._options, share=self._root)
         # what the host sets on the root after construction travels with every call: the optimizer's fused tail and —
         # above all — the DP-SGD parameters (a halved or ragged batch must be clipped and noised like every other)
-        for attr in ("fuse_sgd_tail", "dp_params", "dp_noise", "dp_micro_batches", "class_weight"):
+        for attr in ("fuse_sgd_tail", "dp_params", "dp_noise", "dp_clip", "dp_micro_batches", "class_weight"):
             setattr(sib[n], attr, getattr(self._root, attr))
         sib[n].train(self.training)
         return sib[n]
@@ -645,6 +645,9 @@ class ResNet18Engine:
     # ------------------------------------------------------------------------------------------
     dp_params = None  # e.g. {"max_grad_norm": 1.0, "noise_multiplier": 1.3}: loss_backward() becomes DP-SGD
     dp_noise = None   # a primia_amd.dp_noise.DeviceNoise: the DP-SGD noise is its ChaCha20 stream instead of torch.randn
+    # a primia_amd.dp_clip.AdaptiveClip: the clipping norm is ITS device word (dp_params' max_grad_norm is not read), every
+    # logical step releases a noisy count and moves it.  The root's, like dp_noise: a sibling on a ragged batch uses it.
+    dp_clip = None
     # A logical DP-SGD step larger than the engine (primia_amd.dp_micro.step): the host loops run it as this many passes of
     # N slots each.  The step helper sets, on the ROOT, the phase of the pass about to run (None: an ordinary step;
     # "first" / "more": clipped sum into dp_acc; "last": dp_acc + this pass, noise, division) and the logical batch size.
@@ -1230,7 +1233,11 @@ class ResNet18Engine:
         above splits exactly into the passes' clipped sums).  "first" / "more": everything up to the clipped sums as
         usual, then dp_acc = grads / dp_acc += grads — no noise, no division.  "last": grads = ((dp_acc + grads) +
         noise) / B in one kernel, B = expected_batch on masked batches and logical_batch otherwise: one noise draw and
-        one counter advance per logical step.  None: an ordinary step."""
+        one counter advance per logical step.  None: an ordinary step.
+
+        With the root's `dp_clip` set (primia_amd.dp_clip.AdaptiveClip) C is that object's device word instead of
+        `max_grad_norm`: the clip factors come with the step's {below, valid} counts (dp_stats["counts"]: private, for
+        tests), the noise is z_delta * C, and the last (or only) pass moves C once — see _dp_adaptive_tail."""
         masked = expected_batch is not None
         if accumulate not in (None, "first", "more", "last"):
             raise ValueError("dp_loss_backward: accumulate is None, 'first', 'more' or 'last'")
@@ -1303,7 +1310,10 @@ class ResNet18Engine:
                     call("primia_conv2d_wgrad_persample_sqnorm", c.desc, x, dy, sq, self.dt)
                 mark(name)
             clip = torch.empty(N, dtype=torch.float32, device=dev)
-            if masked:
+            adaptive = self._root.dp_clip
+            if adaptive is not None:    # C from the device word; the step's counts start over on its first (or only) pass
+                adaptive.factors(sq, target if masked else None, clip, N, overwrite=accumulate in (None, "first"))
+            elif masked:
                 call("primia_dp_clip_factors_masked", sq, target, clip, N, float(max_grad_norm))
             else:
                 call("primia_dp_clip_factors", sq, clip, N, float(max_grad_norm))
@@ -1385,12 +1395,17 @@ class ResNet18Engine:
                 self.dp_operands = list(self.dp["wgrads"])
             self.dp = None
         self.dp_stats = {"sq_norms": sq, "clip": clip}
+        if adaptive is not None:        # (tests: the raw count is private, never printed or saved)
+            self.dp_stats["counts"] = adaptive.counts
         if accumulate in ("first", "more"):
             call("primia_dp_accumulate", self.dp_acc, self.grads, self.P, 1 if accumulate == "first" else 0)
             return self.loss
         acc = self.dp_acc if accumulate == "last" else None
+        batch = float(expected_batch) if masked else (N if acc is None else int(logical_batch))
+        inv_batch = 1.0 / batch
+        if adaptive is not None:
+            return self._dp_adaptive_tail(adaptive, acc, batch, inv_batch, noise_multiplier, noise, generator)
         sigma = float(noise_multiplier * max_grad_norm)
-        inv_batch = 1.0 / float(expected_batch) if masked else 1.0 / (N if acc is None else int(logical_batch))
         if noise is None and generator is None and self._root.dp_noise is not None:
             # the ROOT's stream, whichever sibling runs the step: a halved or ragged batch advances the one counter
             self._root.dp_noise.add_to(self.grads, self.P, sigma, inv_batch, acc=acc)
@@ -1401,6 +1416,31 @@ class ResNet18Engine:
                 call("primia_dp_add_noise", self.grads, noise, self.P, sigma, inv_batch)
             else:
                 call("primia_dp_add_noise_acc", self.grads, acc, noise, self.P, sigma, inv_batch)
+        return self.loss
+
+    def _dp_adaptive_tail(self, adaptive, acc, batch, inv_batch, z, noise, generator):
+        """The end of a logical DP-SGD step under an adaptive clipping norm (engine.dp_clip): noise z_delta * C on the
+        clipped sum — C read on the device, z_delta paying for the count's release so that the step as a whole is a
+        Gaussian mechanism with multiplier z — then the update of C on the step's counts, once per logical step.  The
+        count's draw is the block right after the gradient's: one counter advance of blocks(P) + 1.  Host-supplied noise
+        has P + 1 elements, the last one the count's."""
+        dev, P = self.device, self.P
+        nm = adaptive.noise_multiplier(z, batch)
+        stream = self._root.dp_noise
+        if noise is None and generator is None and stream is not None:
+            blocks = query("primia_dp_noise_blocks", P)
+            call("primia_dp_noise_add_dev", *stream.key_words, stream.nonce, stream.counter, 0, self.grads, acc, P,
+                 adaptive.norm, nm, inv_batch)
+            adaptive.update(batch, noise=stream, block_offset=blocks)
+            call("primia_u64_add", stream.counter, blocks + 1)
+        else:
+            if noise is None:
+                noise = torch.randn(P + 1, dtype=torch.float32, device=dev, generator=generator)
+            if noise.numel() != P + 1:
+                raise ValueError(f"dp_loss_backward: with an adaptive clipping norm the noise has P + 1 = {P + 1} elements "
+                                 f"(the last one is the count's), got {noise.numel()}")
+            call("primia_dp_add_noise_dev", self.grads, acc, noise, P, adaptive.norm, nm, inv_batch)
+            adaptive.update(batch, z0=noise[P:])
         return self.loss
 
     dp_keep = True

@@ -31,6 +31,10 @@ key gains ("micro-batch", phase, 1 / batch), the "first" and "more" graphs end w
 accumulator and hold no optimizer step (they advance no step count), the "last" graph holds the noise node and the
 optimizer step.  Two graphs per engine for two passes, three for more.  A ragged final pass runs eagerly under the size
 rule above, between replayed ones: the accumulator is a plain buffer.
+
+An adaptive clipping norm (engine.dp_clip, primia_amd.dp_clip.AdaptiveClip) adds its parameters — rate, quantile, the
+count's noise, the range and z_delta — to the key, never the value of C: the clip-factor, noise and update nodes read and
+write C, the counts and the released fraction in device tensors that exist before the capture.
 """
 import gc
 import warnings
@@ -91,7 +95,22 @@ def _key(eng, optimizer, soft):
             # a pass of a step cut into micro-batches: other tail kernels per phase, 1 / batch in the last one's noise node
             inv = 1.0 / float(dp["expected_batch"] if dp.get("expected_batch") is not None else root.dp_logical_batch)
             key += ("micro-batch", phase, inv)
+        clip = getattr(root, "dp_clip", None)
+        if clip is not None:
+            # an adaptive clipping norm (dp_clip.AdaptiveClip): its PARAMETERS are launch arguments of the update and noise
+            # nodes; the value of C is a device word the nodes read, so C moving never captures again
+            key += ("adaptive clip",) + clip.key(float(dp.get("noise_multiplier", 1.3)), _divisor(eng, dp))
     return key
+
+
+def _divisor(eng, dp):
+    """B, what a DP-SGD step of `eng` divides its noised sum by (dp_loss_backward's rule)."""
+    root = eng._root
+    if dp.get("expected_batch") is not None:
+        return float(dp["expected_batch"])
+    if getattr(root, "dp_phase", None) is not None:
+        return int(root.dp_logical_batch)
+    return eng.N
 
 
 def _sync_moments(root):
@@ -128,6 +147,8 @@ def _fingerprint(eng, g):
     if getattr(eng._root, "dp_params", None) is not None:       # (the per-step DP buffers are the graph pool's own)
         ts += [eng._root.dp_noise.counter] + list(eng._dp_keep_buffers().values())
         ts += [eng._root.__dict__.get("_dp_acc")]         # (None unless a step has run as micro-batch passes)
+        if getattr(eng._root, "dp_clip", None) is not None:         # C, the counts and the released fraction
+            ts += eng._root.dp_clip.tensors()
     return tuple(t.data_ptr() if t is not None else 0 for t in ts) + (len(eng.relu_masks),)
 
 
@@ -147,10 +168,14 @@ class _StepGraph:
         phase = _phase(eng)
         if phase is not None:
             eng.dp_acc                  # likewise: the passes of a step hand their sums on through it
+        clip = getattr(root, "dp_clip", None)
+        if clip is not None:
+            clip.tensors()              # likewise: C lives across replays
         # capture runs the step's Python (forward / optimizer.step advance the host counters) without executing a kernel:
         # keep what one step advances them by, and put them back
         nbt = dict(eng.num_batches_tracked)
         steps = root._opt_steps
+        updates = clip.updates if clip is not None else 0
         self.graph = torch.cuda.CUDAGraph()
         # No garbage collection inside the capture: a collected engine (every engine is a reference cycle through
         # `_root`) would destroy its own graphs and release their memory pools in the middle of this capture, which the
@@ -172,6 +197,9 @@ class _StepGraph:
         self.steps_delta = root._opt_steps - steps
         eng.num_batches_tracked.update(nbt)
         root._opt_steps = steps
+        self.clip_updates_delta = 0
+        if clip is not None:
+            self.clip_updates_delta, clip.updates = clip.updates - updates, updates
         self.fingerprint = _fingerprint(eng, self)
         self.captures = 1
 
@@ -193,6 +221,8 @@ class _StepGraph:
         for k, d in self.nbt_delta.items():
             eng.num_batches_tracked[k] += d
         root._opt_steps += self.steps_delta
+        if self.clip_updates_delta:
+            root.dp_clip.updates += self.clip_updates_delta
         return eng.loss
 
 

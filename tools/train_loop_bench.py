@@ -13,7 +13,10 @@ network with frozen statistics (train.py's --dp_norm frozen) instead.  --dp_samp
 loop: --records synthetic records, expected batch --batch, the engine at the capacity dp_accountant.capacity_for gives for
 --planned_steps; every step is select + gather (primia_amd.dp_sampling.PoissonLoader) and the masked DP step; images per
 second then counts the EXPECTED batch.  --dp_micro_batches K (train.py's flag) runs every step as K passes on an engine of
-1 / K of the batch or capacity (primia_amd.dp_micro); ms per step is then per LOGICAL step.  With --dp the line also
+1 / K of the batch or capacity (primia_amd.dp_micro); ms per step is then per LOGICAL step.  --dp_clip adaptive (train.py's
+flag) gives every mode's engine an adaptive clipping norm (primia_amd.dp_clip, its defaults); a mode named "eager:adaptive"
+or "graph:adaptive" has one whatever the flag says, so `--modes graph,graph:adaptive` alternates the fixed and the adaptive
+loop in one session, and the line then carries each such mode's final C.  With --dp the line also
 carries the engine's slots and, per mode, the peak of torch.cuda.max_memory_allocated() over what was allocated before that
 mode's engine was built (the batches, the records, an earlier mode's engine), read after the mode's warm-up: the engine,
 its DP buffers and, graphed, the graphs' pools.  Needs a GPU (there is no CPU path)."""
@@ -48,6 +51,7 @@ def main():
     ap.add_argument("--records", type=int, default=1721, help="--dp_sampling poisson: records sampled from")
     ap.add_argument("--planned_steps", type=int, default=280, help="--dp_sampling poisson: steps the capacity is sized for")
     ap.add_argument("--dp_micro_batches", type=int, default=1, help="with --dp: train.py's --dp_micro_batches")
+    ap.add_argument("--dp_clip", choices=("fixed", "adaptive"), default="fixed", help="with --dp: train.py's --dp_clip")
     a = ap.parse_args()
     poisson = a.dp and a.dp_sampling == "poisson"
     K = a.dp_micro_batches if a.dp else 1
@@ -87,6 +91,9 @@ def main():
             def __iter__(self):
                 return (self.pl.draw() for _ in range(self.count))
     modes = a.modes.split(",")
+    for m in modes:
+        if m not in ("eager", "graph") and not (a.dp and m in ("eager:adaptive", "graph:adaptive")):
+            raise SystemExit(f"mode {m!r}: eager or graph, with --dp also eager:adaptive or graph:adaptive")
     runs, peak = {}, {}
     for m in modes:
         torch.manual_seed(42)
@@ -103,11 +110,16 @@ def main():
                 from primia_amd.dp_noise import DeviceNoise
 
                 eng.dp_noise = DeviceNoise(dev)
+            if a.dp_clip == "adaptive" or m.endswith(":adaptive"):
+                from primia_amd.dp_clip import AdaptiveClip
+
+                eng.dp_clip = AdaptiveClip(dev, sigma_b=a.batch / 20.0)
+                eng.dp_clip.tensors()
             if poisson:
                 pl = PoissonLoader(records, labels, a.batch, capacity, DeviceSampler(dev), micro_batches=K)
                 eng.dp_params["expected_batch"] = pl.expected_batch
         args = SimpleNamespace(optimizer="SGD", lr=1e-4, weight_decay=5e-4, log_interval=10 ** 9, mixup=False,
-                               hip_graph=m == "graph")
+                               hip_graph=m.startswith("graph"))
         opt = EngineOptimizer.from_args(eng, args)
         mine = Draws(pl, a.steps) if poisson else loader
         warm = Draws(pl, max(3, a.buffers)) if poisson else loader[:max(3, a.buffers)]
@@ -133,6 +145,7 @@ def main():
         out["dp_norm"] = a.dp_norm
         out["graphed_keys"] = {m: len(captures(runs[m][0])) for m in modes}
         out["dp_sampling"] = a.dp_sampling
+        out["dp_clip"] = {m: runs[m][0].dp_clip.value() if runs[m][0].dp_clip is not None else "fixed" for m in modes}
         out.update(dp_micro_batches=K, engine_slots=runs[modes[0]][0].N, peak_bytes_over_held=peak)
         if poisson:
             out.update(records=a.records, capacity=capacity, planned_steps=a.planned_steps,

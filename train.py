@@ -6,7 +6,8 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
     python train.py --config configs/torch/pneumonia-resnet-pretrained.ini --train_federated \
         [--unencrypted_aggregation] [--data_dir DIR|synthetic] [--cuda] [--resume_checkpoint P] \
         [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N] \
-        [--dp_norm {group,frozen}] [--dp_sampling {shuffle,poisson}] [--dp_delta D] [--dp_micro_batches K]
+        [--dp_norm {group,frozen}] [--dp_sampling {shuffle,poisson}] [--dp_delta D] [--dp_micro_batches K] \
+        [--dp_clip {fixed,adaptive}] [--dp_clip_quantile G] [--dp_clip_lr R] [--dp_clip_sigma S] [--dp_clip_init C]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -29,6 +30,10 @@ Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 has spent per client after every epoch (primia_amd.dp_accountant); the ledger travels in the checkpoint (`dp_privacy`).
 `--dp_micro_batches K` runs every DP-SGD step as K passes on an engine of 1 / K of the batch (primia_amd.dp_micro): a
 logical batch larger than one engine's activations allow, with one noise draw and one optimizer step per batch.
+`--dp_clip adaptive` lets every client's clipping norm follow a quantile of its per-sample gradient norms
+(primia_amd.dp_clip): each step releases a noisy count, the gradient noise is raised to pay for it, and the configured
+noise multiplier — what the ledger is given — stays what it was.  C and the last released fraction are printed per client
+after every epoch and travel in the checkpoint (`dp_clip`).
 
 `main(args, verbose, optuna_trial, cmd_args)` returns the best validation MCC like the reference's.
 """
@@ -247,6 +252,45 @@ def micro_batch_size(slots, k, poisson):
     return int(slots) // int(k)
 
 
+def adaptive_clip_mode(args, cmd_args, sigma):
+    """The AdaptiveClip parameters of --dp_clip adaptive with differentially_private = yes (without it the flag warns and
+    does nothing, like the other --dp_* flags), or None for the fixed C = 1.  The count's noise is --dp_clip_sigma or
+    batch_size / 20 — the step's divisor B in shuffle and in Poisson mode alike, and a loader's ragged last batch keeps
+    it — and must exceed sigma / 2 (sigma: the configured noise multiplier), else the run ends here."""
+    kind = getattr(cmd_args, "dp_clip", "fixed") if cmd_args is not None else "fixed"
+    if kind != "adaptive":
+        return None
+    if not args.differentially_private:
+        warn("--dp_clip adaptive has no effect: the config has differentially_private = no, no gradient is clipped")
+        return None
+    from primia_amd import dp_clip
+
+    given = getattr(cmd_args, "dp_clip_sigma", None)
+    sigma_b = float(given) if given is not None else args.batch_size / 20.0
+    try:
+        z_delta = dp_clip.z_delta(sigma, sigma_b)
+    except ValueError:
+        raise SystemExit("--dp_clip adaptive: the count's noise {:s} = {:g} must exceed half the noise multiplier, "
+                         "{:g} / 2 = {:g}: below that bound no gradient noise can pay for the count's release".format(
+                             "--dp_clip_sigma" if given is not None else "batch_size / 20", sigma_b, sigma, sigma / 2.0))
+    params = {"init": float(getattr(cmd_args, "dp_clip_init", 1.0)), "quantile": float(getattr(cmd_args, "dp_clip_quantile", 0.5)),
+              "lr": float(getattr(cmd_args, "dp_clip_lr", 0.2)), "sigma_b": sigma_b}
+    try:
+        dp_clip.AdaptiveClip("cpu", **params)       # (refuses a quantile outside (0, 1), a negative rate, an init out of range)
+    except ValueError as e:
+        raise SystemExit("--dp_clip adaptive: {:s}".format(str(e)))
+    return dict(params, z_delta=z_delta)
+
+
+def saved_clip(state):
+    """{client: AdaptiveClip state} of a loaded checkpoint's `dp_clip` ({} with a warning when it has none)."""
+    saved = state.get("dp_clip")
+    if saved is None:
+        warn("the checkpoint holds no dp_clip entry: every client's clipping norm starts at --dp_clip_init")
+        return {}
+    return dict(saved)
+
+
 def poisson_plan(name, n, batch_size, epochs, delta, sigma, spent=None):
     """(q, planned steps, capacity) of a client with n records: q = floor(batch_size * 2^64 / n) / 2^64 — the probability
     the kernel samples with is the one the accountant is given — over epochs * ceil(n / batch_size) steps.  An expected
@@ -329,6 +373,13 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             print("dp_micro_batches: every step of {:d} samples runs as K = {:d} passes on an engine of M = {:d} "
                   "slots".format(args.batch_size, micro, m))
     dp_sigma = 1.3
+    # --dp_clip adaptive: the ledger keeps receiving dp_sigma — the count's release is paid for by the gradient's noise
+    clip_params = adaptive_clip_mode(args, cmd_args, dp_sigma)
+    if clip_params is not None and rank == 0:
+        print("dp_clip: adaptive clipping norm from C = {init:g}, target quantile {quantile:g}, rate {lr:g}, count noise "
+              "{sigma_b:g}; gradient noise {z_delta:.4f} * C for a mechanism of multiplier {z:g}".format(z=dp_sigma,
+                                                                                                       **clip_params))
+    clips = {}          # {client name: dp_clip.AdaptiveClip} of the engines that take steps
     privacy = {}        # Poisson sampling: {client name: dp_accountant.Ledger}
     # a resumed Poisson run sizes every client's capacity from what the checkpoint's ledger has spent plus the epochs
     # still to run, so the checkpoint is read before the loaders are built (and once: resume() below takes it)
@@ -372,7 +423,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
 
         return DeviceLoader(torch.cat([d for d, _ in sl.data]), sl.targets, args.batch_size, True, seed)
 
-    def make_engine(client=None, batch=None, expected_batch=None):
+    def make_engine(client=None, batch=None, expected_batch=None, name=None):
         # differentially_private = yes (train.py:304-334 of the reference): BatchNorm is rejected by the
         # PrivacyEngine, so the network is built with GroupNorm — or (--dp_norm frozen) BatchNorm is applied with its
         # running statistics held fixed, which keeps samples independent too — and every step clips / noises per sample
@@ -393,6 +444,12 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
 
                 nonce = client if client is not None else (2 ** 64 - 1 if args.train_federated else 0)
                 eng.dp_noise = DeviceNoise(device, nonce=nonce, debug_seed=dp_noise_seed)
+            if clip_params is not None and name is not None:
+                # a state of its own per model that takes steps (FedAvg averages weights, never clipping norms)
+                from primia_amd.dp_clip import AdaptiveClip
+
+                eng.dp_clip = clips[name] = AdaptiveClip(device, **{k: v for k, v in clip_params.items() if k != "z_delta"})
+                eng.dp_clip.tensors()       # on the device before any step graph is captured
         return eng
 
     vanilla_loader = None
@@ -404,9 +461,10 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             base, (m, s) = imagefolder.client_loader(args.data_dir, args, device, channels, args.seed)
             val_mean_std_vanilla = (m.cpu(), s.cpu())
         vanilla_loader = poisson_loader("model", base, None)
-        local = make_engine(batch=vanilla_loader.capacity, expected_batch=vanilla_loader.expected_batch)
+        local = make_engine(batch=vanilla_loader.capacity, expected_batch=vanilla_loader.expected_batch,
+                            name=None if args.train_federated else "model")
     else:
-        local = make_engine()
+        local = make_engine(name=None if args.train_federated else "model")
     local.init_weights()
     if args.pretrained:
         load_pretrained(local, num_classes, rank, world)
@@ -453,7 +511,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         for w in mine:
             tl = train_loader.get(w)
             model[w] = make_engine(client=workers.index(w), batch=tl.capacity if poisson else None,
-                                   expected_batch=tl.expected_batch if poisson else None)
+                                   expected_batch=tl.expected_batch if poisson else None, name=w)
             model[w].load_state_dict(local.state_dict())
         if not poisson:
             for w in mine:
@@ -519,6 +577,22 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
     if cmd_args is not None and getattr(cmd_args, "resume_checkpoint", None):
         print("Resume training from a given checkpoint.")
         start_at_epoch = resume(cmd_args, args, model, optimizer, workers, state=resume_state)
+        if clips:
+            old = saved_clip(resume_state)
+            for name, clip in clips.items():
+                if name in old:
+                    # C and the update count come from the checkpoint; the parameters stay the command line's, which
+                    # this run has checked against the bound and announced
+                    for k, (mine_, saved) in clip.differing_parameters(old[name]).items():
+                        warn("{:s}: the checkpoint's dp_clip was saved with {:s} = {}, this run uses {}".format(
+                            name, k, saved, mine_))
+                    clip.load_state_dict(old[name], keep_parameters=True)
+                    if rank == 0:
+                        print("dp_clip: {:s}: resumed at C = {:.9g} after {:d} updates".format(name, clip.value(),
+                                                                                              clip.updates))
+                elif old:
+                    warn("the checkpoint's dp_clip has no entry for {:s}: its clipping norm starts at --dp_clip_init".format(
+                        name))
     scheduler = LearningRateScheduler(args.epochs, np.log10(args.lr), np.log10(args.end_lr), restarts=args.restarts)
     poisson_loaders = train_loader if isinstance(train_loader, dict) else {"model": train_loader}
     overflow_before = {name: led.overflow_events for name, led in privacy.items()}
@@ -551,6 +625,24 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                 print(led.line(name) + (" (end of run)" if final else ""))
         return states
 
+    def clip_report():
+        """Rank 0 prints every client's C and last released fraction — functions of released values, unlike the raw
+        counts, which never leave the device.  Returns the checkpoint's `dp_clip` entry ({client: state}; every rank's
+        under torch.distributed.run)."""
+        states = {name: clip.state_dict() for name, clip in clips.items()}
+        if world > 1:
+            import torch.distributed as dist
+
+            gathered = [None] * world
+            dist.all_gather_object(gathered, states)
+            states = {k: v for g in gathered for k, v in g.items()}
+        if rank == 0:
+            for name in sorted(states):
+                print("dp_clip: {:s}: C = {:.6g}, released fraction at or below C = {:.4f} (target {:g}), {:d} "
+                      "updates".format(name, states[name]["clip_norm"], states[name]["released"],
+                                       states[name]["quantile"], states[name]["updates"]))
+        return states
+
     objectives, model_paths = [], []
     local_flat = None
     for epoch in range(start_at_epoch, args.epochs + 1):
@@ -576,6 +668,9 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             model = train(args, model, device, train_loader, optimizer, epoch, loss_fn, num_classes, verbose=verbose)
             eval_model = model
         dp_privacy = account() if poisson else None
+        ckpt_extra = {"dp_privacy": dp_privacy} if poisson else {}
+        if clip_params is not None:
+            ckpt_extra["dp_clip"] = clip_report()
         if epoch % args.test_interval == 0:
             opt_for_ckpt = optimizer
             if world > 1:
@@ -601,7 +696,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                     if verdict[0] is None:
                         p = "model_weights/{:s}_epoch_{:03d}.pt".format(exp_name, epoch * reps)
                         save_model(eval_model, opt_for_ckpt, p, args, epoch, val_mean_std=val_mean_std,
-                                   extra={"dp_privacy": dp_privacy} if poisson else None)
+                                   extra=ckpt_extra or None)
                         model_paths.append(p)
                 except Exception as e:  # noqa: BLE001 - forwarded to every rank, re-raised below
                     verdict[0] = e
@@ -688,6 +783,21 @@ def build_parser():
                              "and stored in the checkpoint (dp_privacy).")
     parser.add_argument("--dp_delta", type=float, default=1e-5,
                         help="--dp_sampling poisson: the delta of the reported (epsilon, delta)")
+
+    parser.add_argument("--dp_clip", choices=("fixed", "adaptive"), default="fixed",
+                        help="differentially_private = yes: the per-sample clipping norm C.  fixed: 1.0, as before.  "
+                             "adaptive: a device word that follows a quantile of the per-sample gradient norms (each step "
+                             "releases a noisy count of the samples at or below C; the gradient noise is raised so that "
+                             "the step keeps the configured noise multiplier and the reported (epsilon, delta)); C is "
+                             "printed per client after every epoch and stored in the checkpoint (dp_clip).")
+    parser.add_argument("--dp_clip_quantile", type=float, default=0.5,
+                        help="--dp_clip adaptive: the fraction of per-sample norms C aims to sit above")
+    parser.add_argument("--dp_clip_lr", type=float, default=0.2,
+                        help="--dp_clip adaptive: the geometric rate, C *= exp(-rate * (fraction - quantile))")
+    parser.add_argument("--dp_clip_sigma", type=float, default=None,
+                        help="--dp_clip adaptive: the standard deviation of the count's noise (default batch_size / 20); "
+                             "must exceed half the noise multiplier, 0.65")
+    parser.add_argument("--dp_clip_init", type=float, default=1.0, help="--dp_clip adaptive: the C of the first step")
 
     def passes(text):
         k = int(text)
