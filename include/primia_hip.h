@@ -1239,6 +1239,33 @@ int primia_gn_apply_local(const int64_t* x0, const int64_t* x1, const int64_t* m
                           const int64_t* inv1, const int64_t* w0, const int64_t* w1, const int64_t* bias0, const int64_t* bias1,
                           const int64_t* const* t1, const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW,
                           int groups, int64_t div, primia_stream_t stream);
+/* The wide-range form of that GroupNorm (SecureContext.group_norm(wide=True)): the variance and v^-1/2 are
+ * carried at the iteration scale s_it = 10^6 whatever the fixed-point scale s, and v^-1/2 comes from the UNDAMPED Newton
+ * iteration, which is a reciprocal square root for every 0 < v < 3 / x0^2.
+ *   primia_gn_moments_wide_local  primia_gn_moments_local with the squares truncated by `sq_div` = s * s / s_it (1: the raw
+ *                                 products are kept); same scratch (primia_gn_moments_local_scratch_elems).
+ *   primia_rsqrt_newton_local     n elements, both parties, one launch: x_1 = 3 x0 / 2 - trunc(v, first_div) (party 0 holds
+ *                                 the public constant), then steps - 1 times xx = trunc(x * x, s_it), vxx = trunc(v * xx,
+ *                                 s_it), y = 3 s_it - vxx (the constant re-shared with a fresh mask), x = trunc(y * x,
+ *                                 2 s_it), every product a Beaver multiplication.  `prim`: DEVICE array of (steps - 1) * 19
+ *                                 pointers in consumption order, per step triple(x*x) as (a0, b0, c0, a1, b1, c1) [n each],
+ *                                 triple(v*xx), the constant's mask [1], triple(y*x); may be NULL when steps == 1.
+ *                                 Bit-identical to the chain of primia_trunc_div / primia_ring_scale / primia_ring_add /
+ *                                 primia_fpt_mul_local / primia_ring_sub calls.
+ *   primia_gn_apply_wide_local    primia_gn_apply_local with the first product (inv at scale s_it) truncated by `div_it`
+ *                                 and the second by `div`.
+ * Bad arguments: PRIMIA_ERR_ARG.  No host synchronisation: all three may be captured. */
+int primia_gn_moments_wide_local(const int64_t* x0, const int64_t* x1, const int64_t* a0, const int64_t* b0, const int64_t* c0,
+                                 const int64_t* a1, const int64_t* b1, const int64_t* c1, int64_t* mean0, int64_t* mean1,
+                                 int64_t* var0, int64_t* var1, int64_t* scratch, int64_t R, int64_t m, int64_t sq_div,
+                                 primia_stream_t stream);
+int primia_rsqrt_newton_local(const int64_t* v0, const int64_t* v1, const int64_t* const* prim, int64_t s_it, int64_t x0,
+                              int64_t first_div, int steps, int64_t* out0, int64_t* out1, int64_t n, primia_stream_t stream);
+int primia_gn_apply_wide_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
+                               const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
+                               const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,
+                               int64_t* out0, int64_t* out1, int B, int C, int HW, int groups, int64_t div_it, int64_t div,
+                               primia_stream_t stream);
 /* spdz_compute (mpc/spdz.py:63-122), party j in {0,1}:
  *   mul   : z = delta*b + a*eps + c (+ delta*eps if j == 0), element-wise; b / eps hold nb
  *           elements and broadcast over the leading dims when nb < n;

@@ -11,7 +11,9 @@ reference's loop, or `--batch_size N` images per protocol pass; the checkpoint's
 of the plain and of every encrypted form, and a checkpoint without BatchNorm running statistics (train.py with
 differentially_private = yes: GroupNorm(32, C) at every norm site) is served as the GroupNorm network, plain and encrypted.
 The encrypted GroupNorm takes its inverse square root from the reference's Newton iteration, which is accurate to under 1 %
-for group variances in about [0.05, 16] (1.6 % off at 0.01, 15 % at 0.001).  The encrypted BatchNorm runs the same
+for group variances in about [0.05, 16] (1.6 % off at 0.01, 15 % at 0.001, orders of magnitude above 21); `--wide_norm` serves
+a GroupNorm checkpoint for any group variance below 30,000 with the undamped iteration at a scale of 10^-6 (--precision_fractional
+3 to 6; a form defined here, not by the reference).  The encrypted BatchNorm runs the same
 iteration on shares of running_var, as the reference does, and is accurate on the same window only (the wrong sign from a
 variance of 22); `--fold_norm` has the model owner fold every BatchNorm into scale = gamma / sqrt(running_var + 1e-5) and
 shift = beta - running_mean * scale before sharing, so that each norm site is one private multiply-add and the encrypted pass
@@ -36,7 +38,7 @@ from warnings import warn
 import torch
 
 from primia_amd.engine import ResNet18Engine
-from primia_amd.secure import Dealer, SecureContext, SecureResNet18, fold_batch_norm, norm_of
+from primia_amd.secure import Dealer, SecureContext, SecureResNet18, check_wide_norm, fold_batch_norm, norm_of
 from primia_amd.torchlib_compat import Arguments  # noqa: F401  (checkpoints pickle an Arguments instance)
 
 
@@ -139,6 +141,26 @@ def load_images(data_dir, n, size, channels, device, mean, std, seed=0, clahe=Fa
     return out
 
 
+def wide_norm_choice(requested, encrypted, keys, precision_fractional):
+    """What --wide_norm comes to: True when the encrypted pass is to use the wide-range GroupNorm.  Without
+    --encrypted_inference it warns and does nothing; on a BatchNorm checkpoint, or at a precision the form is not defined
+    for, the run ends."""
+    if not requested:
+        return False
+    if not encrypted:
+        warn("--wide_norm has no effect: without --encrypted_inference nothing is shared, the plain engine computes "
+             "GroupNorm in floating point for any group variance")
+        return False
+    if norm_of(keys) != "group":
+        raise SystemExit("--wide_norm is a form of the secret-shared GroupNorm; this is a BatchNorm checkpoint, whose running "
+                         "statistics are the model owner's plaintext: pass --fold_norm, which serves it for any running variance")
+    try:
+        check_wide_norm(10, precision_fractional)
+    except ValueError as e:
+        raise SystemExit(f"--wide_norm: {e} -- pass --precision_fractional 3 to 6")
+    return True
+
+
 if __name__ == "__main__":
     start_time = datetime.now()
     parser = argparse.ArgumentParser()
@@ -198,6 +220,15 @@ if __name__ == "__main__":
                              "0.001, the wrong sign from 22); the folded form is defined here, not by the reference.  Per "
                              "pass it drops the 237 Newton triples, their 80 masks and one of the two products of each of "
                              "the 20 norm sites.  Refused for a GroupNorm checkpoint, whose statistics depend on the image")
+    parser.add_argument("--wide_norm", action="store_true",
+                        help="encrypted inference on a GroupNorm checkpoint: the wide-range form of the secret-shared "
+                             "GroupNorm -- the variance and its inverse square root carried at a scale of 10^-6 whatever "
+                             "--precision_fractional, and the inverse square root from the undamped Newton iteration, which "
+                             "is one for every group variance below 30,000 (the default form: about [0.05, 16], and off by "
+                             "orders of magnitude above).  Defined here, not by the reference (DESIGN.md §4); 128 dealer "
+                             "requests per norm site against 321; needs --precision_fractional 3 to 6.  With every "
+                             "--reveal, --hip_graph, --batch_size, --evaluate and --three_role.  Refused for a BatchNorm "
+                             "checkpoint: --fold_norm serves that one for any running variance")
     parser.add_argument("--debug_dealer_seed", type=int, default=None,
                         help="DEBUG ONLY: derive the crypto provider's key from this number (reproducible, hence "
                              "NOT private); by default the key comes from the OS entropy pool and never leaves the "
@@ -261,6 +292,7 @@ if __name__ == "__main__":
                              "GroupNorm checkpoint (no running statistics), whose statistics depend on the image and cannot "
                              "be folded before sharing")
         fold = True
+    wide = wide_norm_choice(cmd_args.wide_norm, args.encrypted_inference, sd.keys(), cmd_args.precision_fractional)
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
         if cmd_args.three_role:
@@ -286,7 +318,8 @@ if __name__ == "__main__":
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
                                     precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal,
-                                    fss_bits=fss_bits, labels=labels if link.role == 1 and reveal in ("confusion", "metrics") else None)
+                                    fss_bits=fss_bits, labels=labels if link.role == 1 and reveal in ("confusion", "metrics") else None,
+                                    wide_norm=wide)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
@@ -308,11 +341,11 @@ if __name__ == "__main__":
 
                 model = GraphedSecureInference(shared_sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
                                                seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal,
-                                               fss_bits=fss_bits)
+                                               fss_bits=fss_bits, wide_norm=wide)
             else:
                 ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
                                     precision_fractional=cmd_args.precision_fractional)
-                model = SecureResNet18(ctx, shared_sd, input_size=size, pooling=pooling, reveal=reveal)
+                model = SecureResNet18(ctx, shared_sd, input_size=size, pooling=pooling, reveal=reveal, wide_norm=wide)
             if reveal in ("confusion", "metrics"):      # an evaluation: the passes return nothing, the matrix is opened after the last
                 model.begin()
                 for i in range(0, images.shape[0], bs):

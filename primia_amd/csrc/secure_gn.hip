@@ -15,6 +15,10 @@
 // composition of OracleContext methods (tests/test_gpu_secure_groupnorm.py).  Ring sums are exact in any order, so a group is
 // summed by as many workgroups as its size asks for and the partial sums are added in a second pass: no atomics, the same
 // bits in every run.
+// The wide-range form (SecureContext.group_norm(wide=True), tests/secure_gn_wide_nets.py) carries var and inv at the scale
+// s_it = 10^6 whatever `div`: the squares are truncated by div * div / s_it (primia_gn_moments_wide_local), inv comes from
+// the undamped Newton iteration of rsqrt_newton_local_kernel below, and inv * Xc.T is truncated by s_it
+// (primia_gn_apply_wide_local).  Same kernels, same triples, same order.
 #include "common.h"
 
 namespace primia {
@@ -198,8 +202,10 @@ __global__ __launch_bounds__(GN_THREADS) void gn_var_kernel(const u64* __restric
 struct GnVec {
     const u64 *mean0, *mean1, *inv0, *inv1, *w0, *w1, *bias0, *bias1;
 };
+// div1 truncates the first product, div2 the second: equal in the default form (both at the fixed-point scale); the
+// wide-range form keeps inv at the iteration's finer scale and takes that scale back out with div1.
 __global__ __launch_bounds__(256) void gn_apply_local_kernel(GnPair x, GnVec v, GnTriple t1, GnTriple t2, GnOut out, int C, int HW,
-                                                             int groups, int cg, u64 div) {
+                                                             int groups, int cg, u64 div1, u64 div2) {
     __shared__ u64 tile[2][32][33];
     const int p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
@@ -231,14 +237,14 @@ __global__ __launch_bounds__(256) void gn_apply_local_kernel(GnPair x, GnVec v, 
             {
                 const u64 delta = (v.inv0[r] - t1.a0[r]) + (v.inv1[r] - t1.a1[r]);
                 const u64 eps = (y0 - t1.b0[i1]) + (y1 - t1.b1[i1]);
-                n0 = gn_trunc(delta * t1.b0[i1] + t1.a0[r] * eps + t1.c0[i1] + delta * eps, div);
-                n1 = gn_trunc(delta * t1.b1[i1] + t1.a1[r] * eps + t1.c1[i1], div);
+                n0 = gn_trunc(delta * t1.b0[i1] + t1.a0[r] * eps + t1.c0[i1] + delta * eps, div1);
+                n1 = gn_trunc(delta * t1.b1[i1] + t1.a1[r] * eps + t1.c1[i1], div1);
             }
             // fpt_mul(rows, weight) + bias
             const u64 delta = (n0 - t2.a0[i2]) + (n1 - t2.a1[i2]);
             const u64 eps = (v.w0[c] - t2.b0[c]) + (v.w1[c] - t2.b1[c]);
-            r0[k] = gn_trunc(delta * t2.b0[c] + t2.a0[i2] * eps + t2.c0[i2] + delta * eps, div) + v.bias0[c];
-            r1[k] = gn_trunc(delta * t2.b1[c] + t2.a1[i2] * eps + t2.c1[i2], div) + v.bias1[c];
+            r0[k] = gn_trunc(delta * t2.b0[c] + t2.a0[i2] * eps + t2.c0[i2] + delta * eps, div2) + v.bias0[c];
+            r1[k] = gn_trunc(delta * t2.b1[c] + t2.a1[i2] * eps + t2.c1[i2], div2) + v.bias1[c];
         }
     }
     __syncthreads();
@@ -256,6 +262,43 @@ __global__ __launch_bounds__(256) void gn_apply_local_kernel(GnPair x, GnVec v, 
             out.p1[img + (long)c * HW + p] = tile[1][ty + 8 * k][tx];
         }
     }
+}
+
+// ---- v^-1/2 by the UNDAMPED Newton iteration x <- x (3 - v x^2) / 2, both parties in one launch ------------------------
+// The sibling of newton_local_kernel (csrc/ring.hip) for the wide-range GroupNorm: one thread carries one element of both
+// parties through all `steps` iterates, at the iteration's own scale s_it.
+//   x_1 = 3 x0 / 2 - trunc(v, first_div)            x0 public: formed by the parties locally (party 0 adds the constant)
+//   x_{k+1}: xx = trunc(x * x, s_it); vxx = trunc(v * xx, s_it); y = 3 s_it - vxx; x = trunc(y * x, 2 s_it)
+// every product a Beaver multiplication with its open inside, every truncation per share, `3 s_it - t` the re-sharing
+// of the public constant with a fresh mask -- the order and arithmetic of SecureContext.rsqrt_newton's chain.
+//   prim: device array of pointers, in consumption order:  (steps - 1) x { T1 (a0,b0,c0,a1,b1,c1), T2, mask, T3 }
+__global__ __launch_bounds__(64) void rsqrt_newton_local_kernel(const u64* __restrict__ v0, const u64* __restrict__ v1,
+                                                                const u64* const* __restrict__ prim, u64 s_it, u64 x0, u64 first_div,
+                                                                int steps, u64* __restrict__ o0, u64* __restrict__ o1, long n) {
+    const long i = (long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const u64 c3 = 3 * s_it;
+    const u64 va = v0[i], vb = v1[i];
+    auto mul = [&](u64 xa, u64 xb, u64 ya, u64 yb, const u64* const* t, u64 d, u64& za, u64& zb) {
+        const u64 a0 = t[0][i], b0 = t[1][i], c0 = t[2][i], a1 = t[3][i], b1 = t[4][i], c1 = t[5][i];
+        const u64 delta = (xa - a0) + (xb - a1), eps = (ya - b0) + (yb - b1);
+        za = gn_trunc(delta * b0 + a0 * eps + c0 + delta * eps, d);
+        zb = gn_trunc(delta * b1 + a1 * eps + c1, d);
+    };
+    u64 xa = gn_trunc(3 * x0, 2) - gn_trunc(va, first_div);
+    u64 xb = (u64)0 - gn_trunc(vb, first_div);
+    const u64* const* pp = prim;
+#pragma unroll 1
+    for (int it = 1; it < steps; ++it, pp += 19) {
+        u64 qa, qb, ta, tb;
+        mul(xa, xb, xa, xb, pp, s_it, qa, qb);             // x * x
+        mul(va, vb, qa, qb, pp + 6, s_it, ta, tb);         // v * (x * x)
+        const u64 r = pp[12][0];                           // 3 - ...: the constant re-shared as (r, 3 s_it - r)
+        const u64 ya = (u64)0 - (ta - r), yb = (u64)0 - (tb - (c3 - r));
+        mul(ya, yb, xa, xb, pp + 13, 2 * s_it, xa, xb);    // y * x / 2
+    }
+    o0[i] = xa;
+    o1[i] = xb;
 }
 
 inline bool gn_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -311,12 +354,12 @@ int primia_gn_moments_local(const int64_t* x0, const int64_t* x1, const int64_t*
     return launch_status();
 }
 
-int primia_gn_apply_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1, const int64_t* inv0,
-                          const int64_t* inv1, const int64_t* w0, const int64_t* w1, const int64_t* bias0, const int64_t* bias1,
-                          const int64_t* const* t1, const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW,
-                          int groups, int64_t div, primia_stream_t st) {
+static int gn_apply_launch(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1, const int64_t* inv0,
+                           const int64_t* inv1, const int64_t* w0, const int64_t* w1, const int64_t* bias0, const int64_t* bias1,
+                           const int64_t* const* t1, const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW,
+                           int groups, int64_t div1, int64_t div2, primia_stream_t st) {
     PRIMIA_REQUIRE(x0 && x1 && mean0 && mean1 && inv0 && inv1 && w0 && w1 && bias0 && bias1 && t1 && t2 && out0 && out1 &&
-                   out0 != out1 && B > 0 && B <= 65535 && C > 0 && HW > 0 && groups > 0 && div > 0);
+                   out0 != out1 && B > 0 && B <= 65535 && C > 0 && HW > 0 && groups > 0 && div1 > 0 && div2 > 0);
     for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(t1[k] && t2[k]);
     if (C % groups != 0) return PRIMIA_ERR_UNSUPPORTED;
     PRIMIA_REQUIRE((C + 31) / 32 <= 65535);
@@ -325,7 +368,44 @@ int primia_gn_apply_local(const int64_t* x0, const int64_t* x1, const int64_t* m
         GnPair{U(x0), U(x1)}, GnVec{U(mean0), U(mean1), U(inv0), U(inv1), U(w0), U(w1), U(bias0), U(bias1)},
         GnTriple{U(t1[0]), U(t1[1]), U(t1[2]), U(t1[3]), U(t1[4]), U(t1[5])},
         GnTriple{U(t2[0]), U(t2[1]), U(t2[2]), U(t2[3]), U(t2[4]), U(t2[5])}, GnOut{(u64*)out0, (u64*)out1}, C, HW, groups,
-        C / groups, (u64)div);
+        C / groups, (u64)div1, (u64)div2);
+    return launch_status();
+}
+
+int primia_gn_apply_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1, const int64_t* inv0,
+                          const int64_t* inv1, const int64_t* w0, const int64_t* w1, const int64_t* bias0, const int64_t* bias1,
+                          const int64_t* const* t1, const int64_t* const* t2, int64_t* out0, int64_t* out1, int B, int C, int HW,
+                          int groups, int64_t div, primia_stream_t st) {
+    return gn_apply_launch(x0, x1, mean0, mean1, inv0, inv1, w0, w1, bias0, bias1, t1, t2, out0, out1, B, C, HW, groups, div, div,
+                           st);
+}
+
+int primia_gn_apply_wide_local(const int64_t* x0, const int64_t* x1, const int64_t* mean0, const int64_t* mean1,
+                               const int64_t* inv0, const int64_t* inv1, const int64_t* w0, const int64_t* w1,
+                               const int64_t* bias0, const int64_t* bias1, const int64_t* const* t1, const int64_t* const* t2,
+                               int64_t* out0, int64_t* out1, int B, int C, int HW, int groups, int64_t div_it, int64_t div,
+                               primia_stream_t st) {
+    return gn_apply_launch(x0, x1, mean0, mean1, inv0, inv1, w0, w1, bias0, bias1, t1, t2, out0, out1, B, C, HW, groups, div_it,
+                           div, st);
+}
+
+int primia_gn_moments_wide_local(const int64_t* x0, const int64_t* x1, const int64_t* a0, const int64_t* b0, const int64_t* c0,
+                                 const int64_t* a1, const int64_t* b1, const int64_t* c1, int64_t* mean0, int64_t* mean1,
+                                 int64_t* var0, int64_t* var1, int64_t* scratch, int64_t R, int64_t m, int64_t sq_div,
+                                 primia_stream_t st) {
+    // the kernels divide by whatever they are given and gn_trunc(v, 1) == v for every v: the wide form's moments are the
+    // default form's with the squares' divisor chosen by the caller
+    return primia_gn_moments_local(x0, x1, a0, b0, c0, a1, b1, c1, mean0, mean1, var0, var1, scratch, R, m, sq_div, st);
+}
+
+int primia_rsqrt_newton_local(const int64_t* v0, const int64_t* v1, const int64_t* const* prim, int64_t s_it, int64_t x0,
+                              int64_t first_div, int steps, int64_t* out0, int64_t* out1, int64_t n, primia_stream_t st) {
+    PRIMIA_REQUIRE(v0 && v1 && out0 && out1 && out0 != out1 && n > 0 && s_it > 0 && x0 > 0 && first_div > 0 && steps >= 1);
+    PRIMIA_REQUIRE(steps == 1 || prim);
+    PRIMIA_REQUIRE(n <= 0x7fffffffL * 64);
+    rsqrt_newton_local_kernel<<<(unsigned)((n + 63) / 64), 64, 0, (hipStream_t)st>>>(U(v0), U(v1), (const u64* const*)prim,
+                                                                                     (u64)s_it, (u64)x0, (u64)first_div, steps,
+                                                                                     (u64*)out0, (u64*)out1, (long)n);
     return launch_status();
 }
 

@@ -929,6 +929,63 @@ class SecureContext:
             x = self.trunc(self.fpt_mul(y, x), C)
         return x
 
+    def rsqrt_newton(self, v):
+        """v^-1/2 of shares v at the scale GN_WIDE_SCALE by the UNDAMPED Newton iteration x <- x (3 - v x^2) / 2: a reciprocal
+        square root for every 0 < v < 3 / x0^2 (x0 = 0.01: 30,000), where `reciprocal_newton`'s damped form is one on about
+        [0.05, 16].  From x0 below v^-1/2 it rises monotonically -- 1.5x per step, then quadratically -- and, in exact arithmetic, never overshoots;
+        GN_WIDE_STEPS iterates reach v^-1/2 for v down to the floor of `group_norm(wide=True)`.  Defined by
+        tests/secure_gn_wide_nets.py's oracle_rsqrt_newton:
+          x_1 = 3 x0 / 2 - trunc(v, 2 / x0^3)          x0 public: party local, party 0 holds the constant, no dealer request
+          xx = trunc(x * x, s_it); vxx = trunc(v * xx, s_it); y = 3 s_it - vxx (re-shared constant); x = trunc(y * x, 2 s_it)
+        Both parties here: one launch (`primia_rsqrt_newton_local`), its primitives requested in the order the chain below
+        consumes them; the chain is what a three-role run executes and what `fuse_newton = False` selects -- same bits."""
+        s_it, x0 = GN_WIDE_SCALE, GN_WIDE_X0
+        first_div = 2 * s_it ** 3 // x0 ** 3
+        if self._in_process and self.fuse_newton:
+            shape, n, dev = tuple(v[0].shape), v[0].numel(), v[0].device
+            prims = []
+            for _ in range(GN_WIDE_STEPS - 1):
+                prims += _six(self.dealer.triple("mul", shape, shape))
+                prims += _six(self.dealer.triple("mul", shape, shape))
+                prims.append(self.dealer.const_mask(1, owner=None))
+                prims += _six(self.dealer.triple("mul", shape, shape))
+            table = self._newton_table([p.data_ptr() for p in prims], dev)
+            out = _pair(shape, dev)
+            call("primia_rsqrt_newton_local", v[0].contiguous(), v[1].contiguous(), table, s_it, x0, first_div, GN_WIDE_STEPS,
+                 out[0], out[1], n)
+            self.stats["beaver_mul"] += 3 * (GN_WIDE_STEPS - 1)
+            return out
+        x = self.neg(self.trunc(v, first_div))
+        if 0 in self.parties:
+            x1 = _empty_like(x[0])
+            call("primia_ring_add", x[0], self._const(3 * x0 // 2, x[0].device), x1, x1.numel(), 1)
+            x[0] = x1
+        for _ in range(GN_WIDE_STEPS - 1):
+            xx = self.beaver_mul(x, x, trunc=s_it)
+            vxx = self.beaver_mul(v, xx, trunc=s_it)
+            y = self.neg(self.sub_public_scalar(vxx, 3 * s_it))
+            x = self.beaver_mul(y, x, trunc=2 * s_it)
+        return x
+
+    def _newton_table(self, ptrs, dev):
+        """The device pointer table of a fused iteration's primitives.  Static primitive buffers (pre-provisioned store,
+        GraphedSecureInference): cached per call position, so a replayed / captured forward uploads nothing (a
+        host-to-device copy cannot be captured into a hipGraph); nothing is retained beyond the table: the tape owns the
+        buffers.  Live dealer: fresh primitives every call -- the table is built and every reference dropped (the launch is
+        on the current stream and torch's allocator is stream-ordered)."""
+        if not isinstance(self.dealer, PreloadedDealer):
+            return torch.tensor(ptrs, dtype=I64).to(dev)
+        idx = self._newton_calls
+        self._newton_calls += 1
+        if idx < len(self._newton_tables) and self._newton_tables[idx][0] == ptrs:
+            return self._newton_tables[idx][1]
+        table = torch.tensor(ptrs, dtype=I64).to(dev)
+        if idx < len(self._newton_tables):
+            self._newton_tables[idx] = (ptrs, table)
+        else:
+            self._newton_tables.append((ptrs, table))
+        return table
+
     def _reciprocal_newton_fused(self, v):
         shape = tuple(v[0].shape)
         n = v[0].numel()
@@ -941,26 +998,7 @@ class SecureContext:
                     prims.append(m)
                 t = self.dealer.triple("mul", shape, shape)
                 prims += _six(t)
-        ptrs = [p.data_ptr() for p in prims]
-        if isinstance(self.dealer, PreloadedDealer):
-            # static primitive buffers (pre-provisioned store, GraphedSecureInference): the device pointer table is
-            # cached per call position, so a replayed / captured forward uploads nothing (a host-to-device copy
-            # cannot be captured into a hipGraph).  Nothing is retained beyond the table: the tape owns the buffers.
-            idx = self._newton_calls
-            self._newton_calls += 1
-            if idx < len(self._newton_tables) and self._newton_tables[idx][0] == ptrs:
-                table = self._newton_tables[idx][1]
-            else:
-                table = torch.tensor(ptrs, dtype=I64).to(dev)
-                if idx < len(self._newton_tables):
-                    self._newton_tables[idx] = (ptrs, table)
-                else:
-                    self._newton_tables.append((ptrs, table))
-        else:
-            # live dealer: fresh primitives every call — build the table, launch, drop every reference.  The launch
-            # is on the current stream and torch's allocator is stream-ordered, so the 237 triples may be recycled
-            # as soon as this function returns (round 2 pinned all of them per image: ~55 MB leaked per forward).
-            table = torch.tensor(ptrs, dtype=I64).to(dev)
+        table = self._newton_table([p.data_ptr() for p in prims], dev)      # (the 237 triples are dropped on return)
         out = _pair(shape, dev)
         call("primia_newton_reciprocal_local", v[0].contiguous(), v[1].contiguous(), table, int(self.scale), out[0], out[1], n)
         self.stats["beaver_mul"] += 3 * 79
@@ -1045,7 +1083,7 @@ class SecureContext:
             return out
         return self._affine_to_nchw(self._to_rows(x, B, C, H * W), scale, shift, B, C, H, W)
 
-    def group_norm(self, x, weight, bias, groups=32):
+    def group_norm(self, x, weight, bias, groups=32, wide=False):
         """GroupNorm(groups, C) on shares [B, C, H, W] -- the norm of the BatchNorm-free network that differentially private
         training builds.  The reference has no secret-shared GroupNorm: this layer is DEFINED here from the reference's
         building blocks and is not pinned against the reference.  With X_j = x_j.reshape(R, m), R = B * groups
@@ -1060,13 +1098,31 @@ class SecureContext:
         The Newton iteration approximates v^-1/2 to under 1 % for v in about [0.05, 16]: group variances outside that range
         are normalised wrongly (1.6 % at 0.01, 15 % at 0.001).
         Both parties here: two fused launches around the Newton launch (primia_gn_moments_local, primia_gn_apply_local);
-        otherwise the step-by-step chain, which a three-role run executes -- same dealer requests, same bits."""
+        otherwise the step-by-step chain, which a three-role run executes -- same dealer requests, same bits.
+
+        wide=True: the wide-range form (tests/secure_gn_wide_nets.py's oracle_group_norm_wide), right for any
+        group variance in (0, 30,000) and defined for 3 <= precision_fractional <= 6.  With s_it = GN_WIDE_SCALE = 10^6:
+          var  = trunc_div(row sum of trunc(beaver_mul(Xc, Xc), s * s / s_it)_j, m)          at scale s_it (pf 3: raw squares)
+          inv  = rsqrt_newton(var + eps + floor)       one re-shared constant; floor = GN_WIDE_FLOOR units of 1 / s_it, above
+                                                       the truncations' largest negative error: v > 0 for a constant group
+          N    = trunc(beaver_mul(inv, Xc.T), s_it).T  at scale s
+        and the mean and the affine tail as above; the same triples in the same order, 128 dealer requests per site against
+        321.  Launches: primia_gn_moments_wide_local, primia_rsqrt_newton_local, primia_gn_apply_wide_local."""
         B, C, H, W = self._ref(x).shape
         groups = int(groups)
         if groups < 1 or C % groups != 0:
             raise ValueError(f"group_norm: {C} channels do not divide into {groups} groups")
         R, m, HW = B * groups, (C // groups) * H * W, H * W
-        eps_q = _eps_q(self.base, self.pf)
+        scale = int(self.scale)
+        if wide:
+            check_wide_norm(self.base, self.pf)
+            sq_div, inv_div = scale * scale // GN_WIDE_SCALE, GN_WIDE_SCALE
+            eps_q = GN_WIDE_SCALE // 100000 + GN_WIDE_FLOOR      # eps = 1e-5 at s_it, and the floor
+            newton = self.rsqrt_newton
+        else:
+            sq_div = inv_div = scale
+            eps_q = _eps_q(self.base, self.pf)
+            newton = self.reciprocal_newton
         if self._local:
             dev = x[0].device
             x = [x[0].contiguous(), x[1].contiguous()]
@@ -1074,15 +1130,19 @@ class SecureContext:
             mean, var = _pair((R,), dev), _pair((R,), dev)
             n_scratch = _lib.query("primia_gn_moments_local_scratch_elems", R, m)
             scratch = torch.empty(n_scratch, dtype=I64, device=dev) if n_scratch > 0 else None
-            call("primia_gn_moments_local", x[0], x[1], *_six(ts), mean[0], mean[1], var[0], var[1], scratch, R, m,
-                 int(self.scale))
+            call("primia_gn_moments_wide_local" if wide else "primia_gn_moments_local", x[0], x[1], *_six(ts), mean[0], mean[1],
+                 var[0], var[1], scratch, R, m, sq_div)
             self.stats["beaver_mul"] += 1
-            inv = self.reciprocal_newton(self.sub_public_scalar(var, -eps_q))
+            inv = newton(self.sub_public_scalar(var, -eps_q))
             t1 = self.dealer.triple("mul", (R,), (m, R))             # fpt_mul(inv, Xc.T)
             t2 = self.dealer.triple("mul", (B * HW, C), (C,))        # fpt_mul(rows, weight)
             out = _pair((B, C, H, W), dev)
-            call("primia_gn_apply_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0], bias[1],
-                 _ptr_table(t1), _ptr_table(t2), out[0], out[1], B, C, HW, groups, int(self.scale))
+            if wide:
+                call("primia_gn_apply_wide_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
+                     bias[1], _ptr_table(t1), _ptr_table(t2), out[0], out[1], B, C, HW, groups, inv_div, scale)
+            else:
+                call("primia_gn_apply_local", x[0], x[1], mean[0], mean[1], inv[0], inv[1], weight[0], weight[1], bias[0],
+                     bias[1], _ptr_table(t1), _ptr_table(t2), out[0], out[1], B, C, HW, groups, scale)
             self.stats["beaver_mul"] += 2
             return out
 
@@ -1102,9 +1162,9 @@ class SecureContext:
         mean = row_mean(x)
         xct = self.sub(transpose(x, R, m), mean)                     # Xc.T [m, R]: the mean broadcasts over the leading dim
         xc = transpose(xct, m, R)                                    # Xc [R, m]
-        var = row_mean(self.fpt_mul(xc, xc))
-        inv = self.reciprocal_newton(self.sub_public_scalar(var, -eps_q))
-        nt = self.fpt_mul(inv, xct)                                  # [m, R]
+        var = row_mean(self.beaver_mul(xc, xc, trunc=sq_div))
+        inv = newton(self.sub_public_scalar(var, -eps_q))
+        nt = self.beaver_mul(inv, xct, trunc=inv_div)                # [m, R]
         n = [None if t is None else t.view(B, C, H, W) for t in transpose(nt, m, R)]
         return self._affine_to_nchw(self._to_rows(n, B, C, HW), weight, bias, B, C, H, W)
 
@@ -1230,6 +1290,12 @@ def _check_reveal(reveal):
 
 NORMS = ("batch", "group", "folded")
 GN_GROUPS = 32      # GroupNorm(32, C) at every norm site: the network train.py builds for differentially_private = yes
+# the wide-range GroupNorm (SecureContext.group_norm(wide=True)); fixed from tools/secure_gn_range.py's output
+GN_WIDE_SCALE = 10 ** 6     # scale of the variance and of v^-1/2, whatever the network's fixed-point scale
+GN_WIDE_X0 = 10 ** 4        # the public first guess 0.01 at that scale: serves 0 < v < 3 / 0.01^2
+GN_WIDE_STEPS = 32          # iterates, the locally formed first one included
+GN_WIDE_FLOOR = 2           # units of 1 / GN_WIDE_SCALE added to var + eps
+GN_WIDE_PF = (3, 6)
 BN_EPS = 1e-5       # nn.BatchNorm2d's eps, which the plaintext model adds to running_var (the reference's encrypted form does not)
 
 
@@ -1312,6 +1378,18 @@ def folded_architecture(arch):
     return _fold_keys(arch.items(), prefixes, shape, shape)
 
 
+def check_wide_norm(base, pf, norm="group"):
+    """The wide-range GroupNorm is a form of the GroupNorm network at 3 <= precision_fractional <= 6, base 10: refuse the rest."""
+    if norm != "group":
+        raise ValueError(f"wide_norm is a form of the secret-shared GroupNorm, and this is a {norm}-norm network: a BatchNorm "
+                         f"checkpoint is served for any running variance by folding its statistics (fold_batch_norm, "
+                         f"inference.py --fold_norm)")
+    if base != 10 or not GN_WIDE_PF[0] <= pf <= GN_WIDE_PF[1]:
+        raise ValueError(f"wide_norm is defined for base 10 and {GN_WIDE_PF[0]} <= precision_fractional <= {GN_WIDE_PF[1]} (below, "
+                         f"the squares are coarser than the iteration's scale 10^-6; above, the products do not fit the "
+                         f"ring), got base {base}, precision_fractional {pf}")
+
+
 def _eps_q(base, pf):
     """GroupNorm's eps = 1e-5 in fixed point, as fix_precision encodes it (precision.py:117-132: a float32 product,
     truncated): 0 below five fractional digits."""
@@ -1371,13 +1449,16 @@ class SecureResNet18:
     image; `torchlib_compat.auc_from_rank_counts(U, M.sum(1))` is the score."""
 
     def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max",
-                 norm=None, reveal="logits"):
+                 norm=None, reveal="logits", wide_norm=False):
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
         default hoists the image-independent iterations of all BatchNorm layers into one batched vector.  (Ignored with
         GroupNorm: nothing there is image independent; and with a folded dict: there is no iteration.)
         norm=None: "folded" when the state dict has bn1.scale, "group" when it has no bn1.running_mean, else "batch"; an
-        explicit value must agree."""
+        explicit value must agree.
+        wide_norm=True: every norm site of a GroupNorm network is `group_norm(wide=True)`, right for any group variance in
+        (0, 30,000) at 3 <= precision_fractional <= 6; refused for a BatchNorm or folded network (fold_batch_norm is the
+        remedy there)."""
         self.ctx = ctx
         self.input_size = input_size
         self.batched_newton = batched_newton
@@ -1385,6 +1466,9 @@ class SecureResNet18:
         self.reveal = _check_reveal(reveal)
         self.norm = norm_of(state_dict.keys(), norm)
         self.blocks = blocks if blocks is not None else _default_blocks()
+        self.wide_norm = bool(wide_norm)
+        if self.wide_norm:
+            check_wide_norm(ctx.base, ctx.pf, self.norm)
         if self.norm == "group":
             for n in _norm_prefixes(state_dict.keys(), self.blocks):
                 c = int(state_dict[n + ".weight"].shape[0])
@@ -1516,7 +1600,7 @@ class SecureResNet18:
     def _bn(self, x, prefix):
         p = self.p
         if self.norm == "group":
-            return self.ctx.group_norm(x, p[prefix + ".weight"], p[prefix + ".bias"], GN_GROUPS)
+            return self.ctx.group_norm(x, p[prefix + ".weight"], p[prefix + ".bias"], GN_GROUPS, wide=self.wide_norm)
         if self.norm == "folded":
             return self.ctx.affine_eval(x, p[prefix + ".scale"], p[prefix + ".shift"])
         return self.ctx.batch_norm_eval(x, p[prefix + ".running_mean"], p[prefix + ".running_var"],
@@ -1620,7 +1704,7 @@ def auc_requests(rows, classes, block_rows=None):
     return req
 
 
-def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits"):
+def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits", wide_norm=False):
     """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
     `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
     what `SecureResNet18.__call__` asks for (tests hold the two equal), so that the memory a serving form needs is known
@@ -1630,6 +1714,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree).
     An architecture without running statistics is the GroupNorm network: no hoisted Newton; every norm site requests its
     square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples.
+    wide_norm=True (GroupNorm only): that iteration is `rsqrt_newton`'s, GN_WIDE_STEPS - 1 steps of three triples and a mask
+    with no leading mask: 128 requests per site against 321.
     A folded architecture (`folded_architecture`, bn1.scale among its names): no Newton at all; every norm site requests the
     single triple ("mul", (B*h*h, c), (c,)) of `SecureContext.affine_eval`.
     reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix).
@@ -1646,11 +1732,14 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     mask((B, cin, input_size, input_size), 1)                                  # the images, shared by the data owner
     norm = norm_of(arch)
     group = norm == "group"
+    if wide_norm:
+        check_wide_norm(10, GN_WIDE_PF[0], norm)      # (the list does not depend on the precision: only the norm is checked)
     names = _norm_prefixes(arch, blocks)
 
-    def newton(n):
-        mask((1,), None)
-        for _ in range(79):
+    def newton(n, wide=False):
+        if not wide:
+            mask((1,), None)
+        for _ in range(GN_WIDE_STEPS - 1 if wide else 79):
             triple("mul", (n,), (n,))
             triple("mul", (n,), (n,))
             mask((1,), None)
@@ -1671,8 +1760,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
                 raise ValueError(f"{c} channels do not divide into {GN_GROUPS} groups")
             R, m = B * GN_GROUPS, (c // GN_GROUPS) * h * h
             triple("mul", (R, m), (R, m))
-            mask((1,), None)                                                   # + eps
-            newton(R)
+            mask((1,), None)                                                   # + eps (wide: + eps + floor)
+            newton(R, wide_norm)
             triple("mul", (R,), (m, R))
         elif norm == "batch":
             triple("mul", (c,), (B * h * h, c))
@@ -1758,21 +1847,22 @@ def primitive_bytes(requests, fss_bits=FSS_BITS):
     return total
 
 
-def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS):
+def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False):
     """What GraphedSecureInference(batch=...) holds in static buffers: every primitive of one pass (dominated by the DIF
     keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image, 2,308,096 with pooling="avg") plus one eighth on top for the arena copy of
     their random words while both exist (5/6 of a triple, 48 of a key's 1,244 bytes) and the captured graph's activations
     (im2col and pool-unroll operands: under 2 % of the keys at every layer).  A key of `fss_bits` levels takes 60 + 37 fss_bits
     bytes: 2,428 at 64."""
-    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal), fss_bits)
+    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm), fss_bits)
     return b + b // 8
 
 
-def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS):
+def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS,
+                            wide_norm=False):
     """The largest batch whose static buffers fit in `budget` bytes (0: not even one image).  serving_bytes is affine in the
     batch (a per-batch part, Newton and the weight masks, plus a per-image part) up to its rounding, so two evaluations
     give the answer and the neighbours settle the rounding."""
-    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal, fss_bits)
+    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal, fss_bits, wide_norm)
     one, two = need(1), need(2)
     per_image, fixed = two - one, 2 * one - two
     k = max(0, (int(budget) - fixed) // per_image)
@@ -1821,21 +1911,22 @@ class GraphedSecureInference:
     refill_graph = True
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
-                 memory_budget=None, pooling="max", reveal="logits", fss_bits=FSS_BITS):
+                 memory_budget=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False):
         self.device = torch.device(device)
         self.batch = int(batch)
+        self.wide_norm = bool(wide_norm)
         self.fss_bits = check_fss_bits(fss_bits)
         self.pooling = _check_pooling(pooling)
         self.reveal = _check_reveal(reveal)
         if self.batch < 1:
             raise ValueError("batch must be at least 1")
         arch = architecture_of(state_dict)
-        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal, self.fss_bits)
+        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal, self.fss_bits, wide_norm)
         if memory_budget is None:
             free, _ = torch.cuda.mem_get_info(self.device)
             memory_budget = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if self.static_bytes > memory_budget:
-            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal, self.fss_bits)
+            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal, self.fss_bits, wide_norm)
             raise ValueError(f"a batch of {self.batch} images at {input_size}x{input_size} needs {self.static_bytes} bytes of static "
                              f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
@@ -1846,7 +1937,7 @@ class GraphedSecureInference:
         self.dealer = Dealer(self.device, seed, self.fss_bits)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
-        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)
+        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal, wide_norm=wide_norm)
         self._n_model = len(self.dealer.tape)          # primitives consumed by sharing the model (kept)
         model(self.image, labels=self.labels)          # offline pass: fills the tape, warms every kernel
         self.tape, self.requests = self.dealer.tape, self.dealer.requests
@@ -1855,7 +1946,8 @@ class GraphedSecureInference:
         self._rehome_tape()                            # per-image random words -> one arena (before any pointer is captured)
         pre = PreloadedDealer(self.tape, self.device, self.fss_bits)
         self._ctx = SecureContext(pre, base, precision_fractional)
-        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal)   # re-shares with the same masks
+        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal,
+                                     wide_norm=wide_norm)                      # re-shares with the same masks
         self._model(self.image, labels=self.labels)    # eager pass over the static buffers: builds the pointer tables
         pre.pos, self._ctx._newton_calls = self._n_model, 0
         side = torch.cuda.Stream(device=self.device)
@@ -2044,13 +2136,13 @@ class PipelinedSecureInference:
     In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU."""
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
-                 batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS):
+                 batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False):
         self.device = torch.device(device)
         if reveal in ACCUMULATING:
             raise ValueError(f'reveal="{reveal}" accumulates in one set of static buffers: use GraphedSecureInference')
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
                                              None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling,
-                                             reveal=reveal, fss_bits=fss_bits)
+                                             reveal=reveal, fss_bits=fss_bits, wide_norm=wide_norm)
                       for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
@@ -2223,7 +2315,8 @@ def party_context(link: PartyLink, precision_fractional=16, base=10, fss_bits=FS
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, labels=None):
+                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, labels=None,
+                   wide_norm=False):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
     all know the architecture, the input size, the stem pool (`pooling`), how many images will be classified and how many go
@@ -2237,13 +2330,17 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     the confusion matrix is opened between the parties, and both return it (int64 [classes, classes]); the dealer returns None.
     reveal="metrics": the same passes; after the last the dealer serves auc_requests(passes * batch, classes), the parties run
     the rank-count tail and both return (M, U).
-    fss_bits: the width of the comparisons, known to all three like the schedule."""
+    fss_bits: the width of the comparisons, known to all three like the schedule.
+    wide_norm: the wide-range GroupNorm at every norm site (a GroupNorm architecture only), known to all three as well: the
+    parties run its step-by-step chain, the dealer follows image_requests(..., wide_norm=True)."""
     _check_pooling(pooling)
     _check_reveal(reveal)
     fss_bits = check_fss_bits(fss_bits)
+    if wide_norm:
+        check_wide_norm(base, precision_fractional, norm_of(arch))
     passes = (n_images + batch - 1) // batch
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
-        image_req = image_requests(arch, input_size, batch, blocks, pooling, reveal)
+        image_req = image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm)
         svc = DealerService(Dealer(link.device, seed, fss_bits), link)
         svc.serve(model_requests(arch))
         for _ in range(passes):
@@ -2260,7 +2357,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         if images is None:
             raise ValueError("party 1 is the data owner: it needs the images")
         shapes = {k: torch.empty(shape, device="meta") for k, shape in arch.items()}
-    model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling, reveal=reveal)
+    model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling, reveal=reveal, wide_norm=wide_norm)
     if reveal in ACCUMULATING:
         if link.role == 1 and (labels is None or labels.numel() != n_images):
             raise ValueError("party 1 is the data owner: it needs one label per image")
