@@ -1207,6 +1207,41 @@ int primia_trunc_col2out_2p(const int64_t* res0, const int64_t* res1, const int6
                             int64_t* out0, int64_t* out1, int B, int HoWo, int O, int64_t div, primia_stream_t stream);
 int primia_pool_unroll_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* out0, int64_t* out1, int B, int C, int H, int W,
                                int k, int stride, int pad, primia_stream_t stream);
+
+/* The faithful truncation of a shared product (SecureContext(faithful_trunc=True), DESIGN.md §4 -- defined in
+ * tests/secure_faithful_nets.py, not pinned against the reference, whose per-share truncation is off by 2^64 / d whenever
+ * the signed shares wrap).  For shares z_0 + z_1 = z (mod 2^64) with |z| < 2^62, all words unsigned:
+ *   u_0 = z_0 + 2^62, u_1 = z_1;  m_j = u_j >> 63;  p = m_0 * m_1 by ONE Beaver product on a triple ("mul", shape, shape),
+ *   first operand shared as [m_0, 0], second as [0, m_1];  w_j = m_j - p_j;
+ *   out_j = u_j / d - w_j * floor(2^64 / d) - [j = 0] * floor(2^62 / d)
+ * which is floor(z / d) + e with e in {-1, 0, 1, 2} for every mask.  1 <= d < 2^62.
+ * The chain a party runs (valid in every deployment): primia_ring_add (party 0: + 2^62) -> primia_trunc_carry_bits ->
+ * primia_beaver_mask (the other operand share is a buffer of zeros) -> the two opens -> primia_beaver_combine_mul ->
+ * primia_trunc_faithful_finish:
+ *   primia_trunc_carry_bits        m[i] = (uint64) u[i] >> 63, n elements; out of place
+ *   primia_trunc_faithful_finish   out[i] of party j from u, m and the party's product share p, n elements; out of place
+ * Both parties here, one launch each, bit-identical to the chain on the same triples (tc: HOST array of the carry triple's
+ * six pointers a0, b0, c0, a1, b1, c1, indexed like the product):
+ *   primia_trunc_faithful_col2out_2p        primia_trunc_col2out_2p with the faithful truncation: res [B][HoWo][O] ->
+ *                                           out [B][O][HoWo] (+ bias[o]); HoWo = 1 is the identity layout (linear)
+ *   primia_affine_eval_faithful_local       primia_affine_eval_local with the faithful truncation of its product; tc is
+ *   primia_affine_eval_faithful_local_batch the triple ("mul", (B*HW, C), (B*HW, C)) at the product's index (b*HW + p)*C + c
+ * Null pointers, zero sizes, one buffer for both parties' outputs, d = 0 or d >= 2^62: PRIMIA_ERR_ARG.  No allocation, no
+ * host synchronisation: capturable. */
+int primia_trunc_carry_bits(const int64_t* u, int64_t* m, int64_t n, primia_stream_t stream);
+int primia_trunc_faithful_finish(int j, const int64_t* u, const int64_t* m, const int64_t* p, int64_t d, int64_t* out, int64_t n,
+                                 primia_stream_t stream);
+int primia_trunc_faithful_col2out_2p(const int64_t* res0, const int64_t* res1, const int64_t* bias0, const int64_t* bias1,
+                                     const int64_t* const* tc, int64_t* out0, int64_t* out1, int B, int HoWo, int O, int64_t div,
+                                     primia_stream_t stream);
+int primia_affine_eval_faithful_local(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                      const int64_t* shift0, const int64_t* shift1, const int64_t* const* t,
+                                      const int64_t* const* tc, int64_t* out0, int64_t* out1, int C, int HW, int64_t div,
+                                      primia_stream_t stream);
+int primia_affine_eval_faithful_local_batch(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                            const int64_t* shift0, const int64_t* shift1, const int64_t* const* t,
+                                            const int64_t* const* tc, int64_t* out0, int64_t* out1, int B, int C, int HW,
+                                            int64_t div, primia_stream_t stream);
 int primia_avg_pool_syft_2p(const int64_t* x0, const int64_t* x1, int64_t* out0, int64_t* out1, int B, int C, int H, int W,
                             int k, int stride, int pad, primia_stream_t stream);
 /* GroupNorm(groups, C) on shares, both parties here (csrc/secure_gn.hip) -- the norm of the BatchNorm-free network of

@@ -38,7 +38,8 @@ from warnings import warn
 import torch
 
 from primia_amd.engine import ResNet18Engine
-from primia_amd.secure import Dealer, SecureContext, SecureResNet18, check_wide_norm, fold_batch_norm, norm_of
+from primia_amd.secure import (Dealer, SecureContext, SecureResNet18, check_faithful_trunc, check_wide_norm, expected_wraps,
+                               fold_batch_norm, norm_of)
 from primia_amd.torchlib_compat import Arguments  # noqa: F401  (checkpoints pickle an Arguments instance)
 
 
@@ -141,6 +142,32 @@ def load_images(data_dir, n, size, channels, device, mean, std, seed=0, clahe=Fa
     return out
 
 
+def faithful_trunc_choice(requested, encrypted, keys, fold):
+    """What --faithful_trunc comes to: True when the encrypted pass is to truncate its products faithfully.  Without
+    --encrypted_inference it warns and does nothing; on a network that is not folded the run ends with the reason."""
+    if not requested:
+        return False
+    if not encrypted:
+        warn("--faithful_trunc has no effect: without --encrypted_inference nothing is shared and nothing is truncated")
+        return False
+    norm = norm_of(keys)
+    try:
+        check_faithful_trunc("folded" if fold and norm == "batch" else norm)
+    except ValueError as e:
+        raise SystemExit(f"--faithful_trunc: {e}" + (" -- pass --fold_norm" if norm == "batch" else ""))
+    return True
+
+
+def warn_of_large_products(sd, images, precision_fractional, pooling):
+    """--faithful_trunc holds while every product stays below 2^62 at scale^2: the plaintext forward of the data says how
+    close this run comes (in a deployment each owner can bound its own factor; here one process holds both)."""
+    e = expected_wraps(sd, images, precision_fractional, pooling=pooling)
+    if e["max_ratio"] >= 0.5:
+        warn(f"--faithful_trunc: the largest product of this run is {e['max_ratio']:.2f} x 2^62 at --precision_fractional "
+             f"{precision_fractional}; at 1 the truncation's precondition |z| < 2^62 fails and the result is undefined -- lower "
+             f"--precision_fractional or rescale the inputs")
+
+
 def wide_norm_choice(requested, encrypted, keys, precision_fractional):
     """What --wide_norm comes to: True when the encrypted pass is to use the wide-range GroupNorm.  Without
     --encrypted_inference it warns and does nothing; on a BatchNorm checkpoint, or at a precision the form is not defined
@@ -220,6 +247,16 @@ if __name__ == "__main__":
                              "0.001, the wrong sign from 22); the folded form is defined here, not by the reference.  Per "
                              "pass it drops the 237 Newton triples, their 80 masks and one of the two products of each of "
                              "the 20 norm sites.  Refused for a GroupNorm checkpoint, whose statistics depend on the image")
+    parser.add_argument("--faithful_trunc", action="store_true",
+                        help="encrypted inference with --fold_norm: truncate the products of conv2d, the folded norm and fc "
+                             "with a form no mask can make wrap.  The reference has each party divide its own share, which "
+                             "is off by 2^64 / scale whenever the signed shares wrap -- with probability |z| / 2^64 per "
+                             "element: never in practice at --precision_fractional 3, about once in a few 224 x 224 images "
+                             "at 6, where it puts 1.8e7 into an activation.  The faithful form costs one more element-wise "
+                             "Beaver product on carry bits per site and is within two units of the last digit for every "
+                             "mask while |z| < 2^62 (DESIGN.md §4; defined here, not by the reference).  With every "
+                             "--reveal, --hip_graph, --batch_size, --evaluate and --three_role.  Refused without "
+                             "--fold_norm and for a GroupNorm checkpoint: their Newton iterations truncate per share")
     parser.add_argument("--wide_norm", action="store_true",
                         help="encrypted inference on a GroupNorm checkpoint: the wide-range form of the secret-shared "
                              "GroupNorm -- the variance and its inverse square root carried at a scale of 10^-6 whatever "
@@ -293,6 +330,9 @@ if __name__ == "__main__":
                              "be folded before sharing")
         fold = True
     wide = wide_norm_choice(cmd_args.wide_norm, args.encrypted_inference, sd.keys(), cmd_args.precision_fractional)
+    faithful = faithful_trunc_choice(cmd_args.faithful_trunc, args.encrypted_inference, sd.keys(), fold)
+    if faithful:
+        warn_of_large_products(sd, images, cmd_args.precision_fractional, pooling)
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
         if cmd_args.three_role:
@@ -319,7 +359,7 @@ if __name__ == "__main__":
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
                                     precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal,
                                     fss_bits=fss_bits, labels=labels if link.role == 1 and reveal in ("confusion", "metrics") else None,
-                                    wide_norm=wide)
+                                    wide_norm=wide, faithful_trunc=faithful)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
@@ -341,11 +381,12 @@ if __name__ == "__main__":
 
                 model = GraphedSecureInference(shared_sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
                                                seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal,
-                                               fss_bits=fss_bits, wide_norm=wide)
+                                               fss_bits=fss_bits, wide_norm=wide, faithful_trunc=faithful)
             else:
                 ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
                                     precision_fractional=cmd_args.precision_fractional)
-                model = SecureResNet18(ctx, shared_sd, input_size=size, pooling=pooling, reveal=reveal, wide_norm=wide)
+                model = SecureResNet18(ctx, shared_sd, input_size=size, pooling=pooling, reveal=reveal, wide_norm=wide,
+                                       faithful_trunc=faithful)
             if reveal in ("confusion", "metrics"):      # an evaluation: the passes return nothing, the matrix is opened after the last
                 model.begin()
                 for i in range(0, images.shape[0], bs):

@@ -3,6 +3,7 @@
 // (SPDZ) combine step.  Integer work: results are bit-exact by construction (unsigned wrap-around
 // arithmetic on the int64 bit patterns).  Everything except the GEMM is an HBM streaming pass.
 #include "common.h"
+#include "trunc_faithful.h"
 
 namespace primia {
 
@@ -174,6 +175,21 @@ __global__ __launch_bounds__(256) void beaver_mul_trunc_kernel(int j, const u64*
         const u64 q = mag / div;
         z[i] = sv < 0 ? (int64_t)((u64)0 - q) : (int64_t)q;
     }
+}
+
+// ---- the faithful truncation of a shared product, party local (trunc_faithful.h) ---------------------
+// m = u >> 63: the party's carry bit, written as an int64 word -- its operand share of the carry product
+__global__ __launch_bounds__(256) void trunc_carry_bits_kernel(const u64* __restrict__ u, u64* __restrict__ m, long n) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) m[i] = u[i] >> 63;
+}
+
+// out = u / d (unsigned) - (m - p) q64 - [j = 0] q62, p the party's share of m_0 m_1
+__global__ __launch_bounds__(256) void trunc_faithful_finish_kernel(int j, const u64* __restrict__ u, const u64* __restrict__ m,
+                                                                    const u64* __restrict__ p, u64* __restrict__ out, FaithDiv f,
+                                                                    long n) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) out[i] = faith_finish(j, u[i], m[i] - p[i], f);
 }
 
 // spdz_mask of both operands in one launch: d = x - a (n elements), e = y - b (nb elements)
@@ -518,6 +534,21 @@ int primia_beaver_mask(const int64_t* x, const int64_t* a, int64_t* d, int64_t n
     PRIMIA_REQUIRE(n >= 0 && nb >= 0 && (n == 0 || (x && a && d)) && (nb == 0 || (y && b && e)));
     beaver_mask_kernel<<<ew_blocks(n + nb), 256, 0, (hipStream_t)st>>>((const u64*)x, (const u64*)a, (u64*)d, n,
                                                                        (const u64*)y, (const u64*)b, (u64*)e, nb);
+    return launch_status();
+}
+
+int primia_trunc_carry_bits(const int64_t* u, int64_t* m, int64_t n, primia_stream_t st) {
+    PRIMIA_REQUIRE(u && m && u != m && n > 0);
+    trunc_carry_bits_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)st>>>((const u64*)u, (u64*)m, n);
+    return launch_status();
+}
+
+int primia_trunc_faithful_finish(int j, const int64_t* u, const int64_t* m, const int64_t* p, int64_t d, int64_t* out, int64_t n,
+                                 primia_stream_t st) {
+    FaithDiv f;
+    PRIMIA_REQUIRE((j == 0 || j == 1) && u && m && p && out && out != u && out != m && out != p && n > 0 && faith_div_make(d, &f));
+    trunc_faithful_finish_kernel<<<ew_blocks(n), 256, 0, (hipStream_t)st>>>(j, (const u64*)u, (const u64*)m, (const u64*)p,
+                                                                             (u64*)out, f, n);
     return launch_status();
 }
 

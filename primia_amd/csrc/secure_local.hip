@@ -14,6 +14,7 @@
 // Reference: syft/frameworks/torch/mpc/spdz.py:125-197 (spdz_mul), tensors/interpreters/precision.py:309-316,419-463
 // (FPT mul / matmul + truncation), nn/functional.py:44-75 (batch_norm), :204-308 (conv2d), :460-508 (_pool2d).
 #include "common.h"
+#include "trunc_faithful.h"
 
 namespace primia {
 
@@ -45,6 +46,19 @@ __device__ __forceinline__ void sl_beaver(u64 x0, u64 x1, u64 y0, u64 y1, u64 a0
     const u64 delta = (x0 - a0) + (x1 - a1), eps = (y0 - b0) + (y1 - b1);
     z0 = delta * b0 + a0 * eps + c0 + delta * eps;
     z1 = delta * b1 + a1 * eps + c1;
+}
+
+// The faithful truncation of both parties' product shares (z0, z1) by f.d (trunc_faithful.h): the carry bits,
+// their Beaver product on element i of the carry triple tc -- first operand shared as [m_0, 0], second as [0, m_1], both
+// opens inside -- the correction and the division, in the order of the chain primia_ring_add (party 0: + 2^62) ->
+// primia_trunc_carry_bits -> primia_beaver_mask -> open, open -> primia_beaver_combine_mul -> primia_trunc_faithful_finish.
+__device__ __forceinline__ void sl_trunc_faithful(u64 z0, u64 z1, const Triple& tc, long i, const FaithDiv& f, u64& o0, u64& o1) {
+    const u64 u0 = z0 + (1ULL << 62), u1 = z1;
+    const u64 m0 = u0 >> 63, m1 = u1 >> 63;
+    u64 p0, p1;
+    sl_beaver(m0, 0, 0, m1, tc.a0[i], tc.b0[i], tc.c0[i], tc.a1[i], tc.b1[i], tc.c1[i], p0, p1);
+    o0 = faith_finish(0, u0, m0 - p0, f);
+    o1 = faith_finish(1, u1, m1 - p1, f);
 }
 
 // ---- element-wise on both parties' shares: out_j = a_j (op) b_j[i % nb] --------------------------------------------
@@ -291,8 +305,11 @@ __global__ __launch_bounds__(256) void bn_eval_local_kernel(Pair x, BnVec v, Tri
 //   out = result.t().reshape(C, B, H, W).permute(1,0,2,3)               [B, C, H, W]
 // bn_eval_local_kernel's structure with its second product only: the same grid (p-tile, c-tile, b), the same padded tile and
 // the same two transposes -- x / out along p, the triple along c -- so the bank argument above applies unchanged.
+// FAITHFUL: the product shares are truncated by sl_trunc_faithful on the carry triple tc ("mul", (B*HW, C), (B*HW, C)), read at
+// the product's own index; otherwise tc and f are not read.
+template <bool FAITHFUL>
 __global__ __launch_bounds__(256) void affine_eval_local_kernel(Pair x, Pair scale, Pair shift, Triple t, OutPair out, int C,
-                                                                int HW, u64 div) {
+                                                                int HW, u64 div, Triple tc, FaithDiv f) {
     __shared__ u64 tile[2][32][33];
     const int p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;       // 32 x 8
@@ -319,8 +336,14 @@ __global__ __launch_bounds__(256) void affine_eval_local_kernel(Pair x, Pair sca
             u64 z0, z1;
             sl_beaver(tile[0][tx][ty + 8 * k], tile[1][tx][ty + 8 * k], scale.p0[c], scale.p1[c], t.a0[i], t.b0[c], t.c0[i],
                       t.a1[i], t.b1[c], t.c1[i], z0, z1);
-            r0[k] = sl_trunc(z0, div) + shift.p0[c];
-            r1[k] = sl_trunc(z1, div) + shift.p1[c];
+            if (FAITHFUL) {
+                sl_trunc_faithful(z0, z1, tc, i, f, z0, z1);
+            } else {
+                z0 = sl_trunc(z0, div);
+                z1 = sl_trunc(z1, div);
+            }
+            r0[k] = z0 + shift.p0[c];
+            r1[k] = z1 + shift.p1[c];
         }
     }
     __syncthreads();
@@ -467,6 +490,25 @@ __global__ __launch_bounds__(256) void trunc_col2out_2p_kernel(Pair res, Pair bi
     const long src = ((long)b * P + p) * O + o;
     out.p0[i] = sl_trunc(res.p0[src], div) + (bias.p0 ? bias.p0[o] : (u64)0);
     out.p1[i] = sl_trunc(res.p1[src], div) + (bias.p1 ? bias.p1[o] : (u64)0);
+}
+
+// trunc_col2out_2p_kernel with the faithful truncation: the carry triple tc ("mul", (B, P, O), (B, P, O)) is read at the
+// product's own index.  P = 1 is the identity layout (linear's [B, O] product, or any flat tensor as B = P = 1)
+__global__ __launch_bounds__(256) void trunc_faithful_col2out_2p_kernel(Pair res, Pair bias, Triple tc, OutPair out, int B, int P,
+                                                                        int O, FaithDiv f) {
+    const long total = (long)B * P * O;
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+        const int p = (int)(i % P);
+        const long t = i / P;
+        const int o = (int)(t % O);
+        const long b = t / O;
+        const long src = (b * P + p) * O + o;
+        u64 z0, z1;
+        sl_trunc_faithful(res.p0[src], res.p1[src], tc, src, f, z0, z1);
+        out.p0[i] = z0 + (bias.p0 ? bias.p0[o] : (u64)0);
+        out.p1[i] = z1 + (bias.p1 ? bias.p1[o] : (u64)0);
+    }
 }
 
 // pool unroll of both parties (pool_unroll_kernel, ring.hip)
@@ -669,10 +711,41 @@ static int affine_eval_local_launch(const int64_t* x0, const int64_t* x1, const 
                    B <= 65535 && C > 0 && HW > 0 && div > 0);
     for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(t[k]);
     const dim3 grid((HW + 31) / 32, (C + 31) / 32, B);
-    affine_eval_local_kernel<<<grid, 256, 0, (hipStream_t)st>>>(
+    affine_eval_local_kernel<false><<<grid, 256, 0, (hipStream_t)st>>>(
         Pair{U(x0), U(x1)}, Pair{U(scale0), U(scale1)}, Pair{U(shift0), U(shift1)},
-        Triple{U(t[0]), U(t[1]), U(t[2]), U(t[3]), U(t[4]), U(t[5])}, OutPair{(u64*)out0, (u64*)out1}, C, HW, (u64)div);
+        Triple{U(t[0]), U(t[1]), U(t[2]), U(t[3]), U(t[4]), U(t[5])}, OutPair{(u64*)out0, (u64*)out1}, C, HW, (u64)div, Triple{},
+        FaithDiv{});
     return launch_status();
+}
+
+static int affine_eval_faithful_launch(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                       const int64_t* shift0, const int64_t* shift1, const int64_t* const* t,
+                                       const int64_t* const* tc, int64_t* out0, int64_t* out1, int B, int C, int HW, int64_t div,
+                                       primia_stream_t st) {
+    FaithDiv f;
+    PRIMIA_REQUIRE(x0 && x1 && scale0 && scale1 && shift0 && shift1 && t && tc && out0 && out1 && out0 != out1 && B > 0 &&
+                   B <= 65535 && C > 0 && HW > 0 && faith_div_make(div, &f));
+    for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(t[k] && tc[k]);
+    const dim3 grid((HW + 31) / 32, (C + 31) / 32, B);
+    affine_eval_local_kernel<true><<<grid, 256, 0, (hipStream_t)st>>>(
+        Pair{U(x0), U(x1)}, Pair{U(scale0), U(scale1)}, Pair{U(shift0), U(shift1)},
+        Triple{U(t[0]), U(t[1]), U(t[2]), U(t[3]), U(t[4]), U(t[5])}, OutPair{(u64*)out0, (u64*)out1}, C, HW, (u64)div,
+        Triple{U(tc[0]), U(tc[1]), U(tc[2]), U(tc[3]), U(tc[4]), U(tc[5])}, f);
+    return launch_status();
+}
+
+int primia_affine_eval_faithful_local(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                      const int64_t* shift0, const int64_t* shift1, const int64_t* const* t,
+                                      const int64_t* const* tc, int64_t* out0, int64_t* out1, int C, int HW, int64_t div,
+                                      primia_stream_t st) {
+    return affine_eval_faithful_launch(x0, x1, scale0, scale1, shift0, shift1, t, tc, out0, out1, 1, C, HW, div, st);
+}
+
+int primia_affine_eval_faithful_local_batch(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
+                                            const int64_t* shift0, const int64_t* shift1, const int64_t* const* t,
+                                            const int64_t* const* tc, int64_t* out0, int64_t* out1, int B, int C, int HW,
+                                            int64_t div, primia_stream_t st) {
+    return affine_eval_faithful_launch(x0, x1, scale0, scale1, shift0, shift1, t, tc, out0, out1, B, C, HW, div, st);
 }
 
 int primia_affine_eval_local(const int64_t* x0, const int64_t* x1, const int64_t* scale0, const int64_t* scale1,
@@ -741,6 +814,21 @@ int primia_trunc_col2out_2p(const int64_t* res0, const int64_t* res1, const int6
     const long total = (long)B * HoWo * O;
     trunc_col2out_2p_kernel<<<ceil_div(total, 256), 256, 0, (hipStream_t)st>>>(
         Pair{U(res0), U(res1)}, Pair{U(bias0), U(bias1)}, OutPair{(u64*)out0, (u64*)out1}, B, HoWo, O, (u64)div);
+    return launch_status();
+}
+
+int primia_trunc_faithful_col2out_2p(const int64_t* res0, const int64_t* res1, const int64_t* bias0, const int64_t* bias1,
+                                     const int64_t* const* tc, int64_t* out0, int64_t* out1, int B, int HoWo, int O, int64_t div,
+                                     primia_stream_t st) {
+    FaithDiv f;
+    PRIMIA_REQUIRE(res0 && res1 && tc && out0 && out1 && out0 != out1 && B > 0 && HoWo > 0 && O > 0 && faith_div_make(div, &f) &&
+                   ((bias0 == nullptr) == (bias1 == nullptr)));
+    PRIMIA_REQUIRE(res0 != out0 && res0 != out1 && res1 != out0 && res1 != out1);      // (a re-layout: out of place)
+    for (int k = 0; k < 6; ++k) PRIMIA_REQUIRE(tc[k]);
+    const long total = (long)B * HoWo * O;
+    trunc_faithful_col2out_2p_kernel<<<sl_blocks(total), 256, 0, (hipStream_t)st>>>(
+        Pair{U(res0), U(res1)}, Pair{U(bias0), U(bias1)}, Triple{U(tc[0]), U(tc[1]), U(tc[2]), U(tc[3]), U(tc[4]), U(tc[5])},
+        OutPair{(u64*)out0, (u64*)out1}, B, HoWo, O, f);
     return launch_status();
 }
 

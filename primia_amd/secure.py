@@ -287,11 +287,14 @@ class DistOpener:
 
 
 class SecureContext:
-    def __init__(self, dealer, base=10, precision_fractional=16, opener=None, party=None, link=None):
+    def __init__(self, dealer, base=10, precision_fractional=16, opener=None, party=None, link=None, faithful_trunc=False):
         """party=None: both parties' shares live in this process (a share is a 2-list).  party=j: this process
         is party j of a distributed run — every 2-list carries only entry j (the other is None), `opener` must
-        be a DistOpener and `link` a PartyLink for the owner-to-peer transfer of freshly shared secrets."""
+        be a DistOpener and `link` a PartyLink for the owner-to-peer transfer of freshly shared secrets.
+        faithful_trunc=True: conv2d, affine_eval and linear truncate their products with `trunc_faithful`, which no mask
+        can make wrap, where the reference's per-share division is off by 2^64 / scale with probability |z| / 2^64."""
         self.dealer = dealer
+        self.faithful_trunc = bool(faithful_trunc)
         self.base = base
         self.pf = precision_fractional
         self.scale = base ** precision_fractional
@@ -414,6 +417,58 @@ class SecureContext:
             return o
 
         return self._each(one)
+
+    def _carry_triple(self, shape):
+        """The triple of a faithful truncation's carry product, requested right after the site's product triple."""
+        self.stats["beaver_mul"] += 1
+        return self.dealer.triple("mul", tuple(shape), tuple(shape))
+
+    def trunc_faithful(self, z, d):
+        """Shares of floor(z / d) + e, e in {-1, 0, 1, 2}, for EVERY mask, from shares z of a value |z| < 2^62.  The
+        reference has no such form (each party divides its own share, which is off by 2^64 / d whenever the signed shares
+        wrap: with probability |z| / 2^64 over the mask); it is DEFINED by tests/secure_faithful_nets.py's
+        oracle_trunc_faithful and not pinned against the reference.  On unsigned words mod 2^64:
+          u_0 = z_0 + 2^62, u_1 = z_1                 shares of z + 2^62, which lies in [0, 2^63)
+          m_j = u_j >> 63                              party local; the carry of u_0 + u_1 is m_0 OR m_1
+          p   = beaver_mul([m_0, 0], [0, m_1])         triple ("mul", shape, shape), both opens, no truncation
+          out_j = u_j / d - (m_j - p_j) floor(2^64 / d) - [j = 0] floor(2^62 / d)
+        Both parties here: one launch (primia_trunc_faithful_col2out_2p in its identity layout); otherwise the chain, which
+        a three-role run executes -- same dealer request, same bits."""
+        zr = self._ref(z)
+        shape, n, dev = tuple(zr.shape), zr.numel(), zr.device
+        t = self._carry_triple(shape)
+        if self._local:
+            out = _pair(shape, dev)
+            call("primia_trunc_faithful_col2out_2p", z[0].contiguous(), z[1].contiguous(), None, None, _ptr_table(t), out[0],
+                 out[1], 1, 1, n, int(d))
+            return out
+        u, m = [None, None], [None, None]
+        for j in self.parties:
+            u[j] = z[j].contiguous()
+            if j == 0:
+                u[j] = _empty_like(u[j])
+                call("primia_ring_add", z[j].contiguous(), self._const(2 ** 62, dev), u[j], n, 1)
+            m[j] = _empty_like(u[j])
+            call("primia_trunc_carry_bits", u[j], m[j], n)
+        zero = self._const(0, dev, n)
+        dm, em = [None, None], [None, None]
+        for j in self.parties:  # spdz_mask: the first operand is [m_0, 0], the second [0, m_1]
+            dm[j], em[j] = _empty_like(u[j]), _empty_like(u[j])
+            call("primia_beaver_mask", m[j] if j == 0 else zero, t[j][0], dm[j], n, zero if j == 0 else m[j], t[j][1], em[j], n)
+        delta, eps = self.opener.open(dm), self.opener.open(em)
+
+        def one(j):
+            p = _empty_like(u[j])
+            call("primia_beaver_combine_mul", j, delta, eps, *t[j], p, n, n)
+            o = _empty_like(u[j])
+            call("primia_trunc_faithful_finish", j, u[j], m[j], p, int(d), o, n)
+            return o
+
+        return self._each(one)
+
+    def trunc_product(self, z):
+        """The truncation of a product at scale s^2 back to s: the reference's per-share division, or `trunc_faithful`."""
+        return self.trunc_faithful(z, self.scale) if self.faithful_trunc else self.trunc(z, self.scale)
 
     def sub_public_scalar(self, a, value):
         """AST - int (additive_shared.py:453-484, 506-524): the constant becomes a FRESH random
@@ -862,6 +917,11 @@ class SecureContext:
             wt = self._weight_t(w, O, K)
             res = self.beaver_matmul(im, wt)
             out = _pair((B, O, Ho, Wo), dev)
+            if self.faithful_trunc:
+                tc = self._carry_triple((B, Ho * Wo, O))
+                call("primia_trunc_faithful_col2out_2p", res[0], res[1], None, None, _ptr_table(tc), out[0], out[1], B, Ho * Wo,
+                     O, int(self.scale))
+                return out
             call("primia_trunc_col2out_2p", res[0], res[1], None, None, out[0], out[1], B, Ho * Wo, O, int(self.scale))
             return out
         im, wt = [None, None], [None, None]
@@ -870,7 +930,7 @@ class SecureContext:
             call("primia_im2col_syft", x[j], a, B, C, H, W, R, S, stride, padding)
             im[j] = a
             wt[j] = _transposed(w[j], O, K)
-        res = self.fpt_matmul(im, wt)
+        res = self.trunc_product(self.beaver_matmul(im, wt))      # (fpt_matmul, or its faithful form)
 
         def one(j):
             o = torch.empty(B, O, Ho, Wo, dtype=I64, device=res[j].device)
@@ -1016,9 +1076,11 @@ class SecureContext:
 
         return self._each(one)
 
-    def _affine_to_nchw(self, rows, weight, bias, B, C, H, W):
-        """fpt_mul(rows, weight) + bias on [B*H*W, C] rows, back to NCHW: the affine tail of both norms' step-by-step paths."""
-        result = self.add(self.fpt_mul(rows, weight), bias)
+    def _affine_to_nchw(self, rows, weight, bias, B, C, H, W, faithful=False):
+        """fpt_mul(rows, weight) + bias on [B*H*W, C] rows, back to NCHW: the affine tail of both norms' step-by-step paths.
+        faithful: the product is truncated by `trunc_faithful` (a folded norm site of a faithful_trunc context)."""
+        prod = self.trunc_faithful(self.beaver_mul(rows, weight), self.scale) if faithful else self.fpt_mul(rows, weight)
+        result = self.add(prod, bias)
 
         def back(j):
             o = torch.empty(B, C, H, W, dtype=I64, device=result[j].device)
@@ -1073,15 +1135,23 @@ class SecureContext:
             t = self.dealer.triple("mul", (B * H * W, C), (C,))
             out = _pair((B, C, H, W), x[0].device)
             x = [x[0].contiguous(), x[1].contiguous()]
-            if B == 1:
+            self.stats["beaver_mul"] += 1
+            if self.faithful_trunc:
+                tc = self._carry_triple((B * H * W, C))
+                if B == 1:
+                    call("primia_affine_eval_faithful_local", x[0], x[1], scale[0], scale[1], shift[0], shift[1], _ptr_table(t),
+                         _ptr_table(tc), out[0], out[1], C, H * W, int(self.scale))
+                else:
+                    call("primia_affine_eval_faithful_local_batch", x[0], x[1], scale[0], scale[1], shift[0], shift[1],
+                         _ptr_table(t), _ptr_table(tc), out[0], out[1], B, C, H * W, int(self.scale))
+            elif B == 1:
                 call("primia_affine_eval_local", x[0], x[1], scale[0], scale[1], shift[0], shift[1], _ptr_table(t), out[0],
                      out[1], C, H * W, int(self.scale))
             else:
                 call("primia_affine_eval_local_batch", x[0], x[1], scale[0], scale[1], shift[0], shift[1], _ptr_table(t),
                      out[0], out[1], B, C, H * W, int(self.scale))
-            self.stats["beaver_mul"] += 1
             return out
-        return self._affine_to_nchw(self._to_rows(x, B, C, H * W), scale, shift, B, C, H, W)
+        return self._affine_to_nchw(self._to_rows(x, B, C, H * W), scale, shift, B, C, H, W, faithful=self.faithful_trunc)
 
     def group_norm(self, x, weight, bias, groups=32, wide=False):
         """GroupNorm(groups, C) on shares [B, C, H, W] -- the norm of the BatchNorm-free network that differentially private
@@ -1238,7 +1308,15 @@ class SecureContext:
         precision.py:822-827): matmul + truncation, then + bias."""
         O, I = self._ref(w).shape
         wt = self._weight_t(w, O, I) if self._local else self._each(lambda j: _transposed(w[j], O, I))
-        return self.add(self.fpt_matmul(x, wt), b)
+        if self.faithful_trunc and self._local:      # truncation and bias in one launch: HoWo = 1 is the identity layout
+            res = self.beaver_matmul(x, wt)
+            rows = res[0].numel() // O
+            tc = self._carry_triple((rows, O))
+            out = _pair(tuple(res[0].shape), res[0].device)
+            call("primia_trunc_faithful_col2out_2p", res[0], res[1], b[0], b[1], _ptr_table(tc), out[0], out[1], rows, 1, O,
+                 int(self.scale))
+            return out
+        return self.add(self.trunc_product(self.beaver_matmul(x, wt)), b)
 
 
 POOLINGS = ("max", "avg")
@@ -1390,6 +1468,60 @@ def check_wide_norm(base, pf, norm="group"):
                          f"ring), got base {base}, precision_fractional {pf}")
 
 
+def check_faithful_trunc(norm):
+    """The faithful truncation covers the three product sites of a FOLDED network (conv2d, affine_eval, linear): refuse the
+    networks whose norm sites truncate products of their own."""
+    if norm != "folded":
+        raise ValueError(f"faithful_trunc covers the products of a folded network (conv2d, affine_eval, linear), and this is a "
+                         f"{norm}-norm network, whose Newton iteration truncates per share about a million small products per "
+                         f"pass that the flag would leave as they are: "
+                         + ("fold the BatchNorm statistics first (fold_batch_norm, inference.py --fold_norm)" if norm == "batch"
+                            else "a GroupNorm network's statistics depend on the image and cannot be folded"))
+
+
+def expected_wraps(state_dict, images, pf, base=10, blocks=None, pooling="max"):
+    """What the reference's per-share truncation is expected to get wrong on these images: the float64 plaintext forward of
+    a BatchNorm or folded state dict (folded here when it is not), which at each of the three kinds of product site of the
+    folded network takes the pre-truncation values z = product * scale^2 and sums |z| / 2^64 -- the probability, over the
+    mask, that the signed shares of z wrap and the sum of the per-share quotients is off by 2^64 / scale.
+    -> {"conv2d": sum, "affine_eval": sum, "linear": sum, "total": their sum, "max_ratio": the largest |z| / 2^62}: the
+    faithful form's precondition is max_ratio < 1.  Host only, no device."""
+    import torch.nn.functional as F
+
+    sd = dict(state_dict)
+    if norm_of(sd.keys()) == "batch":
+        sd = fold_batch_norm(sd)
+    check_faithful_trunc(norm_of(sd.keys()))
+    _check_pooling(pooling)
+    blocks = _default_blocks() if blocks is None else blocks
+    s2 = float(base ** pf) ** 2
+    sums = {"conv2d": 0.0, "affine_eval": 0.0, "linear": 0.0}
+    peak = [0.0]
+
+    def site(kind, product):
+        z = product.abs() * s2
+        sums[kind] += float(z.sum()) / 2.0 ** 64
+        peak[0] = max(peak[0], float(z.max()) / 2.0 ** 62)
+        return product
+
+    p = {k: v.detach().double().cpu() for k, v in sd.items()}
+    conv = lambda x, name, stride, pad: site("conv2d", F.conv2d(x, p[name + ".weight"], None, stride, pad))
+    bn = lambda x, name: site("affine_eval", x * p[name + ".scale"].view(1, -1, 1, 1)) + p[name + ".shift"].view(1, -1, 1, 1)
+    with torch.no_grad():
+        x = bn(conv(images.detach().double().cpu(), "conv1", 2, 3), "bn1")
+        x = torch.relu(F.max_pool2d(x, 3, 2, 1)) if pooling == "max" else F.avg_pool2d(torch.relu(x), 3, 2, 1)
+        for prefix, stride in blocks:
+            identity = x
+            out = torch.relu(bn(conv(x, prefix + ".conv1", stride, 1), prefix + ".bn1"))
+            out = bn(conv(out, prefix + ".conv2", 1, 1), prefix + ".bn2")
+            if (prefix + ".downsample.0.weight") in p:
+                identity = bn(conv(x, prefix + ".downsample.0", stride, 0), prefix + ".downsample.1")
+            x = torch.relu(out + identity)
+        x = F.avg_pool2d(x, x.shape[-1]).reshape(x.shape[0], -1)
+        site("linear", x @ p["fc.weight"].t())
+    return dict(sums, total=sum(sums.values()), max_ratio=peak[0])
+
+
 def _eps_q(base, pf):
     """GroupNorm's eps = 1e-5 in fixed point, as fix_precision encodes it (precision.py:117-132: a float32 product,
     truncated): 0 below five fractional digits."""
@@ -1449,7 +1581,7 @@ class SecureResNet18:
     image; `torchlib_compat.auc_from_rank_counts(U, M.sum(1))` is the score."""
 
     def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max",
-                 norm=None, reveal="logits", wide_norm=False):
+                 norm=None, reveal="logits", wide_norm=False, faithful_trunc=False):
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
         default hoists the image-independent iterations of all BatchNorm layers into one batched vector.  (Ignored with
@@ -1458,7 +1590,9 @@ class SecureResNet18:
         explicit value must agree.
         wide_norm=True: every norm site of a GroupNorm network is `group_norm(wide=True)`, right for any group variance in
         (0, 30,000) at 3 <= precision_fractional <= 6; refused for a BatchNorm or folded network (fold_batch_norm is the
-        remedy there)."""
+        remedy there).
+        faithful_trunc=True: the context's products are truncated by `SecureContext.trunc_faithful` (the context's flag is set
+        here); a folded network only -- the Newton norms of the others truncate per share and are refused."""
         self.ctx = ctx
         self.input_size = input_size
         self.batched_newton = batched_newton
@@ -1469,6 +1603,10 @@ class SecureResNet18:
         self.wide_norm = bool(wide_norm)
         if self.wide_norm:
             check_wide_norm(ctx.base, ctx.pf, self.norm)
+        self.faithful_trunc = bool(faithful_trunc) or ctx.faithful_trunc
+        if self.faithful_trunc:
+            check_faithful_trunc(self.norm)
+            ctx.faithful_trunc = True
         if self.norm == "group":
             for n in _norm_prefixes(state_dict.keys(), self.blocks):
                 c = int(state_dict[n + ".weight"].shape[0])
@@ -1704,7 +1842,8 @@ def auc_requests(rows, classes, block_rows=None):
     return req
 
 
-def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits", wide_norm=False):
+def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits", wide_norm=False,
+                   faithful_trunc=False):
     """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
     `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
     what `SecureResNet18.__call__` asks for (tests hold the two equal), so that the memory a serving form needs is known
@@ -1718,6 +1857,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     with no leading mask: 128 requests per site against 321.
     A folded architecture (`folded_architecture`, bn1.scale among its names): no Newton at all; every norm site requests the
     single triple ("mul", (B*h*h, c), (c,)) of `SecureContext.affine_eval`.
+    faithful_trunc=True (folded only): every conv2d, affine_eval and linear site requests the carry triple
+    ("mul", shape, shape) of `SecureContext.trunc_faithful` right after its product triple, shape that of the product.
     reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix).
     reveal="confusion": the confusion tail's requests follow the argmax tail's (the class form's list is a strict prefix).
     reveal="metrics": the confusion list (the rank-count tail runs once, after the last pass: auc_requests)."""
@@ -1734,6 +1875,9 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     group = norm == "group"
     if wide_norm:
         check_wide_norm(10, GN_WIDE_PF[0], norm)      # (the list does not depend on the precision: only the norm is checked)
+    if faithful_trunc:
+        check_faithful_trunc(norm)
+    carry = lambda *shape: triple("mul", shape, shape) if faithful_trunc else None
     names = _norm_prefixes(arch, blocks)
 
     def newton(n, wide=False):
@@ -1752,6 +1896,7 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
         o, c, r, _ = arch[name + ".weight"]
         ho = out_hw(h, r, stride, pad)
         triple("matmul", (B, ho * ho, c * r * r), (c * r * r, o))
+        carry(B, ho * ho, o)
         return o, ho
 
     def bn(c, h):
@@ -1766,6 +1911,7 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
         elif norm == "batch":
             triple("mul", (c,), (B * h * h, c))
         triple("mul", (B * h * h, c), (c,))                                    # (a folded norm: SecureContext.affine_eval's, alone)
+        carry(B * h * h, c)
 
     def relu(c, h):
         req.append(("dif_keys", (B * c * h * h,), {}))
@@ -1796,6 +1942,7 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
         c, h = o, ho
     classes, feat = arch["fc.weight"]
     triple("matmul", (B, feat), (feat, classes))
+    carry(B, classes)
     if reveal != "logits":
         req += argmax_requests(B, classes)
     if reveal in ACCUMULATING:
@@ -1847,22 +1994,23 @@ def primitive_bytes(requests, fss_bits=FSS_BITS):
     return total
 
 
-def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False):
+def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False,
+                  faithful_trunc=False):
     """What GraphedSecureInference(batch=...) holds in static buffers: every primitive of one pass (dominated by the DIF
     keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image, 2,308,096 with pooling="avg") plus one eighth on top for the arena copy of
     their random words while both exist (5/6 of a triple, 48 of a key's 1,244 bytes) and the captured graph's activations
     (im2col and pool-unroll operands: under 2 % of the keys at every layer).  A key of `fss_bits` levels takes 60 + 37 fss_bits
     bytes: 2,428 at 64."""
-    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm), fss_bits)
+    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm, faithful_trunc), fss_bits)
     return b + b // 8
 
 
 def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS,
-                            wide_norm=False):
+                            wide_norm=False, faithful_trunc=False):
     """The largest batch whose static buffers fit in `budget` bytes (0: not even one image).  serving_bytes is affine in the
     batch (a per-batch part, Newton and the weight masks, plus a per-image part) up to its rounding, so two evaluations
     give the answer and the neighbours settle the rounding."""
-    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal, fss_bits, wide_norm)
+    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal, fss_bits, wide_norm, faithful_trunc)
     one, two = need(1), need(2)
     per_image, fixed = two - one, 2 * one - two
     k = max(0, (int(budget) - fixed) // per_image)
@@ -1911,22 +2059,25 @@ class GraphedSecureInference:
     refill_graph = True
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
-                 memory_budget=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False):
+                 memory_budget=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False, faithful_trunc=False):
         self.device = torch.device(device)
         self.batch = int(batch)
         self.wide_norm = bool(wide_norm)
+        self.faithful_trunc = bool(faithful_trunc)
         self.fss_bits = check_fss_bits(fss_bits)
         self.pooling = _check_pooling(pooling)
         self.reveal = _check_reveal(reveal)
         if self.batch < 1:
             raise ValueError("batch must be at least 1")
         arch = architecture_of(state_dict)
-        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal, self.fss_bits, wide_norm)
+        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal, self.fss_bits, wide_norm,
+                                          faithful_trunc)
         if memory_budget is None:
             free, _ = torch.cuda.mem_get_info(self.device)
             memory_budget = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if self.static_bytes > memory_budget:
-            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal, self.fss_bits, wide_norm)
+            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal, self.fss_bits, wide_norm,
+                                           faithful_trunc)
             raise ValueError(f"a batch of {self.batch} images at {input_size}x{input_size} needs {self.static_bytes} bytes of static "
                              f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
@@ -1937,7 +2088,8 @@ class GraphedSecureInference:
         self.dealer = Dealer(self.device, seed, self.fss_bits)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
-        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal, wide_norm=wide_norm)
+        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal, wide_norm=wide_norm,
+                               faithful_trunc=faithful_trunc)
         self._n_model = len(self.dealer.tape)          # primitives consumed by sharing the model (kept)
         model(self.image, labels=self.labels)          # offline pass: fills the tape, warms every kernel
         self.tape, self.requests = self.dealer.tape, self.dealer.requests
@@ -1947,7 +2099,7 @@ class GraphedSecureInference:
         pre = PreloadedDealer(self.tape, self.device, self.fss_bits)
         self._ctx = SecureContext(pre, base, precision_fractional)
         self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal,
-                                     wide_norm=wide_norm)                      # re-shares with the same masks
+                                     wide_norm=wide_norm, faithful_trunc=faithful_trunc)      # re-shares with the same masks
         self._model(self.image, labels=self.labels)    # eager pass over the static buffers: builds the pointer tables
         pre.pos, self._ctx._newton_calls = self._n_model, 0
         side = torch.cuda.Stream(device=self.device)
@@ -2136,13 +2288,14 @@ class PipelinedSecureInference:
     In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU."""
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
-                 batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False):
+                 batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False, faithful_trunc=False):
         self.device = torch.device(device)
         if reveal in ACCUMULATING:
             raise ValueError(f'reveal="{reveal}" accumulates in one set of static buffers: use GraphedSecureInference')
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
                                              None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling,
-                                             reveal=reveal, fss_bits=fss_bits, wide_norm=wide_norm)
+                                             reveal=reveal, fss_bits=fss_bits, wide_norm=wide_norm,
+                                             faithful_trunc=faithful_trunc)
                       for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
@@ -2308,15 +2461,16 @@ class DealerService:
                 send(v, kw.get("owner"))
 
 
-def party_context(link: PartyLink, precision_fractional=16, base=10, fss_bits=FSS_BITS):
+def party_context(link: PartyLink, precision_fractional=16, base=10, fss_bits=FSS_BITS, faithful_trunc=False):
     """SecureContext of the party this rank plays."""
     return SecureContext(PartyDealer(link, fss_bits), base, precision_fractional,
-                         opener=DistOpener(link.parties_group, link.role), party=link.role, link=link)
+                         opener=DistOpener(link.parties_group, link.role), party=link.role, link=link,
+                         faithful_trunc=faithful_trunc)
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
                    precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, labels=None,
-                   wide_norm=False):
+                   wide_norm=False, faithful_trunc=False):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
     all know the architecture, the input size, the stem pool (`pooling`), how many images will be classified and how many go
@@ -2332,15 +2486,19 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     the rank-count tail and both return (M, U).
     fss_bits: the width of the comparisons, known to all three like the schedule.
     wide_norm: the wide-range GroupNorm at every norm site (a GroupNorm architecture only), known to all three as well: the
-    parties run its step-by-step chain, the dealer follows image_requests(..., wide_norm=True)."""
+    parties run its step-by-step chain, the dealer follows image_requests(..., wide_norm=True).
+    faithful_trunc: the faithful truncation at the product sites of a folded architecture, known to all three too: the parties
+    run `trunc_faithful`'s chain (two more opens per site), the dealer follows image_requests(..., faithful_trunc=True)."""
     _check_pooling(pooling)
     _check_reveal(reveal)
     fss_bits = check_fss_bits(fss_bits)
     if wide_norm:
         check_wide_norm(base, precision_fractional, norm_of(arch))
+    if faithful_trunc:
+        check_faithful_trunc(norm_of(arch))
     passes = (n_images + batch - 1) // batch
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
-        image_req = image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm)
+        image_req = image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm, faithful_trunc)
         svc = DealerService(Dealer(link.device, seed, fss_bits), link)
         svc.serve(model_requests(arch))
         for _ in range(passes):
@@ -2348,7 +2506,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         if reveal == METRICS:      # the rank-count tail over every row held, padding rows included
             svc.serve(auc_requests(passes * batch, arch["fc.weight"][0]))
         return None
-    ctx = party_context(link, precision_fractional, base, fss_bits)
+    ctx = party_context(link, precision_fractional, base, fss_bits, faithful_trunc)
     if link.role == 0:
         if state_dict is None:
             raise ValueError("party 0 is the model owner: it needs the state dict")

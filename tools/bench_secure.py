@@ -7,6 +7,8 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    statistics online -- a Beaver square and an 80-step Newton iteration on batch * 32 values per layer
     --norm folded: the benchmark's BatchNorm state dict after the model owner's fold (primia_amd.secure.fold_batch_norm): the
                    same legs as --norm batch, without the Newton iteration and with one product per norm site
+    --faithful_trunc (with --norm folded): the products of conv2d, the folded norm and fc are truncated by
+                   SecureContext.trunc_faithful, one more element-wise triple per site
     --wide_norm (with --norm group, --pf 3 to 6): the wide-range GroupNorm at every norm site -- a 32-iterate undamped Newton
                    iteration at a scale of 10^-6 in place of the 80-step damped one (the report names it)
     --reveal class: every pass ends with the secret-shared argmax and opens the class only (classes - 1 rounds of one comparison
@@ -37,6 +39,8 @@ def main():
     ap.add_argument("--norm", choices=("batch", "group", "folded"), default="batch",
                     help="group: a synthetic GroupNorm(32, C) state dict, no running statistics; folded: the BatchNorm state "
                          "dict of --norm batch, folded by the model owner before sharing (the report names either)")
+    ap.add_argument("--faithful_trunc", action="store_true",
+                    help="with --norm folded: SecureContext.trunc_faithful at every product site (the report names it)")
     ap.add_argument("--wide_norm", action="store_true",
                     help="with --norm group and --pf 3..6: SecureContext.group_norm(wide=True) at every norm site (the report names it)")
     ap.add_argument("--reveal", choices=("logits", "class", "confusion", "metrics"), default="logits",
@@ -55,6 +59,8 @@ def main():
     a = ap.parse_args()
     if a.wide_norm and a.norm != "group":
         ap.error("--wide_norm is a form of the GroupNorm network: pass --norm group (a BatchNorm network: --norm folded)")
+    if a.faithful_trunc and a.norm != "folded":
+        ap.error("--faithful_trunc covers the products of a folded network: pass --norm folded")
     if a.reveal in ("confusion", "metrics") and not (a.batch and not a.only_fss_roofline):
         ap.error(f"--reveal {a.reveal} is timed in the serving form: pass --batch N")
 
@@ -112,13 +118,13 @@ def main():
     norm_kw = {} if a.norm == "batch" else {"norm": a.norm}
     reveal_kw = {} if a.reveal == "logits" else {"reveal": a.reveal}
     bits_kw = {} if a.fss_bits == 32 else {"fss_bits": a.fss_bits}
-    wide_kw = {"wide_norm": True} if a.wide_norm else {}
+    form_kw = {**({"wide_norm": True} if a.wide_norm else {}), **({"faithful_trunc": True} if a.faithful_trunc else {})}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
     def run(dealer, share_model=True):
         ctx = SecureContext(dealer, 10, a.pf)
-        model = SecureResNet18(ctx, sd, input_size=a.size, **pool_kw, **reveal_kw, **wide_kw)
+        model = SecureResNet18(ctx, sd, input_size=a.size, **pool_kw, **reveal_kw, **form_kw)
         torch.cuda.synchronize(); t0 = time.perf_counter()
         out = model(img)
         torch.cuda.synchronize()
@@ -192,7 +198,7 @@ def main():
         B, reps = a.batch, max(a.images, 3)
         imgs = torch.randn(B, 3, a.size, a.size, generator=g).to(dev)
         free = torch.cuda.mem_get_info(dev)[0]
-        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw, **reveal_kw, **bits_kw, **wide_kw)
+        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw, **reveal_kw, **bits_kw, **form_kw)
         # (an evaluation's passes carry the data owner's labels: seeded, one per image)
         lab_kw = {"labels": torch.randint(0, 3, (B,), generator=g)} if a.reveal in ("confusion", "metrics") else {}
         gi(imgs, refill=False, **lab_kw); torch.cuda.synchronize()
@@ -235,12 +241,12 @@ def main():
                        "tail_online_ms": round(tail_online, 1), "tail_gather_rows_ms": round(gather, 1), "tail_with_dealer_ms": round(with_dealer, 1),
                        "tail_online_in_images": round(tail_online / (online / B), 2),
                        "tail_expected_in_images": round(2 * classes * rows * rows / 3311616, 2)}
-        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, **wide_kw, **reveal_kw, **bits_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
+        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, **form_kw, **reveal_kw, **bits_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
                           "online_ms_per_image": round(online / B, 2), "with_refill_ms_per_image": round(both / B, 2),
                           "online_ms_per_pass": round(online, 2), "with_refill_ms_per_pass": round(both, 2),
                           "static_primitive_bytes": gi.static_bytes, "arena_mb": round(gi._arena.numel() * 8 / 1e6, 1),
                           "device_free_bytes_before": free,
-                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw, **reveal_kw, **bits_kw, **wide_kw),
+                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw, **reveal_kw, **bits_kw, **form_kw),
                           "dif_evals": gi.stats["dif_evals"], **({"dpf_evals": gi.stats["dpf_evals"]} if "dpf_evals" in gi.stats else {}),
                           "beaver_matmul": gi.stats["beaver_matmul"],
                           "beaver_mul": gi.stats["beaver_mul"], **tail_kw}))
@@ -273,9 +279,9 @@ def main():
         try:
             from primia_amd.secure import GraphedSecureInference
 
-            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, **pool_kw, **reveal_kw, **bits_kw, **wide_kw)
+            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, **pool_kw, **reveal_kw, **bits_kw, **form_kw)
             ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, **bits_kw), 10, a.pf)
-            out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, **pool_kw, **reveal_kw, **wide_kw)(img)
+            out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, **pool_kw, **reveal_kw, **form_kw)(img)
             assert torch.equal(gi(img, refill=False).cpu(), out_ref.cpu()), "graph replay must be bit-identical"
             torch.cuda.synchronize(); t0 = time.perf_counter()
             for _ in range(3):
@@ -296,7 +302,7 @@ def main():
             # on its own stream while the other replays): wall time per image, every image on fresh primitives
             from primia_amd.secure import PipelinedSecureInference
 
-            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, **pool_kw, **reveal_kw, **bits_kw, **wide_kw)
+            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, **pool_kw, **reveal_kw, **bits_kw, **form_kw)
             for _ in range(2):
                 pi(img)
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -324,7 +330,7 @@ def main():
 
     extra = {"cpu_baseline": cpu_sample_report(cpu_t, ctx.stats["dif_evals"])} if cpu_t else {}
     extra["roofline"] = fss_roofline()
-    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, **norm_kw, **wide_kw, **reveal_kw, **bits_kw, "online_ms": round(to * 1e3, 1),
+    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, **norm_kw, **form_kw, **reveal_kw, **bits_kw, "online_ms": round(to * 1e3, 1),
                       "online_graph_ms": None if graph_ms is None else round(graph_ms, 1),
                       "dealer_refill_ms": None if refill_ms is None else round(refill_ms, 1),
                       "dealer_refill_launches": refill_nodes, "dealer_keystream_mb_per_image": None if arena_mb is None else round(arena_mb, 1),
