@@ -38,8 +38,8 @@ from warnings import warn
 import torch
 
 from primia_amd.engine import ResNet18Engine
-from primia_amd.secure import (Dealer, SecureContext, SecureResNet18, check_faithful_trunc, check_wide_norm, expected_wraps,
-                               fold_batch_norm, norm_of)
+from primia_amd.secure import (Dealer, ProtocolForm, SecureContext, SecureResNet18, check_faithful_trunc, check_wide_norm,
+                               expected_wraps, fold_batch_norm, norm_of)
 from primia_amd.torchlib_compat import Arguments  # noqa: F401  (checkpoints pickle an Arguments instance)
 
 
@@ -335,6 +335,7 @@ if __name__ == "__main__":
         warn_of_large_products(sd, images, cmd_args.precision_fractional, pooling)
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
+        form = ProtocolForm(pooling=pooling, reveal=reveal, fss_bits=fss_bits, wide_norm=wide, faithful_trunc=faithful)
         if cmd_args.three_role:
             import torch.distributed as dist
 
@@ -357,9 +358,8 @@ if __name__ == "__main__":
                                     state_dict=owned,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
-                                    precision_fractional=cmd_args.precision_fractional, pooling=pooling, reveal=reveal,
-                                    fss_bits=fss_bits, labels=labels if link.role == 1 and reveal in ("confusion", "metrics") else None,
-                                    wide_norm=wide, faithful_trunc=faithful)
+                                    precision_fractional=cmd_args.precision_fractional, form=form,
+                                    labels=labels if link.role == 1 and reveal in ("confusion", "metrics") else None)
             dist.barrier()
             dist.destroy_process_group()
             if link.role != 1:
@@ -380,13 +380,11 @@ if __name__ == "__main__":
                 from primia_amd.secure import GraphedSecureInference
 
                 model = GraphedSecureInference(shared_sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
-                                               seed=cmd_args.debug_dealer_seed, batch=bs, pooling=pooling, reveal=reveal,
-                                               fss_bits=fss_bits, wide_norm=wide, faithful_trunc=faithful)
+                                               seed=cmd_args.debug_dealer_seed, batch=bs, form=form)
             else:
                 ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
                                     precision_fractional=cmd_args.precision_fractional)
-                model = SecureResNet18(ctx, shared_sd, input_size=size, pooling=pooling, reveal=reveal, wide_norm=wide,
-                                       faithful_trunc=faithful)
+                model = SecureResNet18(ctx, shared_sd, input_size=size, form=form)
             if reveal in ("confusion", "metrics"):      # an evaluation: the passes return nothing, the matrix is opened after the last
                 model.begin()
                 for i in range(0, images.shape[0], bs):

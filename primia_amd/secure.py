@@ -23,6 +23,7 @@ Reference map (paths under syft/frameworks/torch/):
   public add / sub / rsub    additive_shared.py:440-527 (constants are RE-SHARED with fresh randomness)
 """
 import ctypes
+import dataclasses
 import os
 
 import torch
@@ -1357,10 +1358,7 @@ def auc_needed(classes):
 
 
 def _check_reveal(reveal):
-    """What a pass opens: "logits", the full score vector (the reference's behaviour), "class", the argmax alone, or
-    "confusion": nothing -- the passes of an evaluation add into a shared confusion matrix, which is opened after the last;
-    "metrics": the same passes, which also keep their logit and label shares for the rank counts of the ROC AUC, opened
-    with the matrix."""
+    """What a pass opens (`ProtocolForm`)."""
     if reveal not in EVALUATION_REVEALS:
         raise ValueError(f"reveal must be one of {EVALUATION_REVEALS}, got {reveal!r}")
     return reveal
@@ -1457,12 +1455,13 @@ def folded_architecture(arch):
 
 
 def check_wide_norm(base, pf, norm="group"):
-    """The wide-range GroupNorm is a form of the GroupNorm network at 3 <= precision_fractional <= 6, base 10: refuse the rest."""
+    """The wide-range GroupNorm is a form of the GroupNorm network at 3 <= precision_fractional <= 6, base 10: refuse the rest.
+    base = pf = None (a request list, which does not depend on the precision): the norm part alone."""
     if norm != "group":
         raise ValueError(f"wide_norm is a form of the secret-shared GroupNorm, and this is a {norm}-norm network: a BatchNorm "
                          f"checkpoint is served for any running variance by folding its statistics (fold_batch_norm, "
                          f"inference.py --fold_norm)")
-    if base != 10 or not GN_WIDE_PF[0] <= pf <= GN_WIDE_PF[1]:
+    if (base, pf) != (None, None) and (base != 10 or not GN_WIDE_PF[0] <= pf <= GN_WIDE_PF[1]):
         raise ValueError(f"wide_norm is defined for base 10 and {GN_WIDE_PF[0]} <= precision_fractional <= {GN_WIDE_PF[1]} (below, "
                          f"the squares are coarser than the iteration's scale 10^-6; above, the products do not fit the "
                          f"ring), got base {base}, precision_fractional {pf}")
@@ -1477,6 +1476,75 @@ def check_faithful_trunc(norm):
                          f"pass that the flag would leave as they are: "
                          + ("fold the BatchNorm statistics first (fold_batch_norm, inference.py --fold_norm)" if norm == "batch"
                             else "a GroupNorm network's statistics depend on the image and cannot be folded"))
+
+
+@dataclasses.dataclass(frozen=True)
+class ProtocolForm:
+    """The options of an encrypted inference the three roles must agree on beyond the architecture, the input size, the blocks
+    and the batch -- public, like the request schedule they select.  Every entry point takes one as `form=`, or its fields as
+    keywords (`of`); construction validates the values, `check` makes the refusals that depend on the network.
+    pooling: the stem pool the checkpoint was trained with (train.py's pooling_type).  "max" is the reference's stem, swap
+    included (conv1 -> bn1 -> MAXPOOL -> RELU).  That swap is an identity for a max pool only (relu(avg(x)) != avg(relu(x))), so
+    "avg" keeps the order the network was trained with, conv1 -> bn1 -> RELU -> AvgPool2d(3, 2, 1), with zero padding and the
+    divisor 9 for every window: it decodes to the model the checkpoint holds.  This stem is NOT pinned against the reference
+    (whose behaviour for this case has not been checked); it follows the plaintext model.  It requests one ReLU at conv1's
+    output resolution and a party-local average pool that requests nothing (2,308,096 comparisons and 294 element-wise triples
+    per 224 x 224 image, against 3,311,616 and 298 with the max tree).
+    reveal: what a pass opens.  "logits" (the default) is the reference's behaviour, unchanged down to the dealer's request
+    list, which is a strict prefix of the class form's.
+    "class" ends the pass with `SecureContext.argmax` on the logit shares (its requests follow the fc triple) and opens the
+    class indices alone, to the data owner: the logits, the model owner's asset, are never reconstructed.  Graphed: the tail is
+    part of the captured graph and the static output is the int64 [batch] buffer of class indices.  Three roles: party 0 sends
+    its share of the indices to party 1, which returns one int64 [<= batch] tensor per pass; party 0 learns nothing and returns
+    None, like the dealer, which follows the extended schedule.
+    "confusion" scores the model on labelled images: `begin()`, then passes with the data owner's labels, each ending with
+    `SecureContext.confusion` (its requests follow the argmax tail's: the class form's list is a strict prefix) and returning
+    nothing, then `finish()`, which opens the confusion matrix -- to both parties -- and nothing else: no logit, no class, no
+    label.  Graphed: the tail is captured too; the one-hot labels are a static int64 [batch, classes] buffer next to the images
+    (`load` zero-fills the rows of padding images), the shares of the matrix a static buffer the captured pass adds into.  Three
+    roles: party 1 also passes `labels`, int64 [n_images]; both parties return the matrix, the dealer None.
+    "metrics" is that evaluation with the reference's third overall figure, the one-vs-one ROC AUC: the passes are the
+    confusion passes, requests included, and keep their logit and label shares; `finish()` runs `SecureContext.auc_counts` over
+    every row held (once, after the last pass: auc_requests) and opens the matrix and the rank counts U [C, C, C] -- `(M, U)`,
+    to both parties -- and nothing per image; `torchlib_compat.auc_from_rank_counts(U, M.sum(1))` is the score.  Graphed: the
+    captured pass leaves copies of its logit and label shares in buffers of the graph, copied out after each replay; the tail
+    runs eagerly on a dealer of its own, seeded apart under a debug seed.  Three roles: after the last pass the dealer serves
+    auc_requests(passes * batch, classes), the parties run the tail and both return (M, U).
+    fss_bits: the width of the comparisons (see FSS_BITS), the dealer's.  A request list does not depend on it (image_requests
+    ignores it); wider keys count in serving_bytes and in the serving form's refusal of a batch that does not fit.
+    SecureResNet18 takes the width from its context's dealer, not from here.
+    wide_norm (GroupNorm only): every norm site is `group_norm(wide=True)`, right for any group variance in (0, 30,000) at 3 <=
+    precision_fractional <= 6; refused for a BatchNorm or folded network (fold_batch_norm is the remedy there).  The site's
+    iteration is `rsqrt_newton`'s, GN_WIDE_STEPS - 1 steps of three triples and a mask with no leading mask: 128 requests per
+    site against 321.  Three roles: the parties run its step-by-step chain.
+    faithful_trunc (folded only): the products of conv2d, affine_eval and linear are truncated by `SecureContext.trunc_faithful`
+    (SecureResNet18 sets its context's flag), each site requesting the carry triple ("mul", shape, shape) right after its
+    product triple, shape that of the product; the Newton norms of the other networks truncate per share and are refused.  Three
+    roles: the parties run the chain (two more opens per site)."""
+    pooling: str = "max"
+    reveal: str = "logits"
+    fss_bits: int = FSS_BITS
+    wide_norm: bool = False
+    faithful_trunc: bool = False
+
+    def __post_init__(self):
+        for name, checked in (("pooling", _check_pooling), ("reveal", _check_reveal), ("fss_bits", check_fss_bits),
+                              ("wide_norm", bool), ("faithful_trunc", bool)):
+            object.__setattr__(self, name, checked(getattr(self, name)))
+
+    @classmethod
+    def of(cls, form=None, **options):
+        """`form` itself, or the form the options spell; both at once, or an unknown option, is a TypeError."""
+        if form is not None and options:
+            raise TypeError(f"pass form= or the options {sorted(options)}, not both")
+        return cls(**options) if form is None else form
+
+    def check(self, norm, base=None, pf=None):
+        """The refusals that depend on the network (`norm_of`) and, where a context is built (`base`, `pf`), on its precision."""
+        if self.wide_norm:
+            check_wide_norm(base, pf, norm)
+        if self.faithful_trunc:
+            check_faithful_trunc(norm)
 
 
 def expected_wraps(state_dict, images, pf, base=10, blocks=None, pooling="max"):
@@ -1545,16 +1613,18 @@ def share_order(keys):
     return [k for k in keys if k not in buf] + buf
 
 
-class SecureResNet18:
+class _FormFields:
+    """The fields of `self.form`, readable on the object that holds it."""
+    pooling = property(lambda self: self.form.pooling)
+    reveal = property(lambda self: self.form.reveal)
+    wide_norm = property(lambda self: self.form.wide_norm)
+    faithful_trunc = property(lambda self: self.form.faithful_trunc)
+
+
+class SecureResNet18(_FormFields):
     """ResNet-18 forward on secret shares — `model.fix_precision().share()` followed by
     `model(data)` in inference.py:279-321, including the stem swap `model.pool, model.relu =
     model.relu, model.pool` (:289): conv1 -> bn1 -> MAXPOOL -> RELU.
-
-    pooling="avg" serves a checkpoint trained with pooling_type = avg.  The reference's swap is an identity for a max pool
-    only (relu(avg(x)) != avg(relu(x))), so the avg stem keeps the order the network was trained with,
-    conv1 -> bn1 -> RELU -> AvgPool2d(3, 2, 1), with zero padding and the divisor 9 for every window: it decodes to the
-    model the checkpoint holds.  This stem is NOT pinned against the reference (whose behaviour for this case has not been
-    checked); it follows the plaintext model.
 
     norm="group" serves the BatchNorm-free network of differentially private training (GroupNorm(32, C) at every norm
     site, no running statistics in the state dict): every norm site is `SecureContext.group_norm`, whose statistics depend
@@ -1565,48 +1635,26 @@ class SecureResNet18:
     place of the BatchNorm tensors, shared in `share_order` as parameters; no buffers): every norm site is
     `SecureContext.affine_eval`, one Beaver product -- no Newton iteration, hoisted or not, and no `precompute_inv`.  NOT
     pinned against the reference either: it follows the plaintext model (F.batch_norm in eval mode, eps included) for any
-    running statistics, where the reference's form is accurate only for variances in about [0.05, 16].
+    running statistics, where the reference's form is accurate only for variances in about [0.05, 16]."""
 
-    reveal="class" ends the pass with `SecureContext.argmax` on the logit shares and opens the class indices alone (to the
-    data owner): the logits, the model owner's asset, are never reconstructed.  "logits" (the default) is the reference's
-    behaviour, unchanged down to the dealer's request list, which is a strict prefix of the class form's.
-
-    reveal="confusion" scores the model on labelled images: `begin()`, then passes with the data owner's labels, each ending
-    with `SecureContext.confusion` and returning nothing, then `finish()`, which opens the confusion matrix -- to both parties
-    -- and nothing else: no logit, no class, no label.  The class form's request list is a strict prefix of this one's.
-
-    reveal="metrics" is that evaluation with the reference's third overall figure, the one-vs-one ROC AUC: the passes are the
-    confusion passes, requests included, and keep their logit and label shares; `finish()` runs `SecureContext.auc_counts`
-    over every row held and opens the matrix and the rank counts U [C, C, C] -- `(M, U)`, to both parties -- and nothing per
-    image; `torchlib_compat.auc_from_rank_counts(U, M.sum(1))` is the score."""
-
-    def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, pooling="max",
-                 norm=None, reveal="logits", wide_norm=False, faithful_trunc=False):
+    def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, *, norm=None,
+                 form=None, **options):
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
         default hoists the image-independent iterations of all BatchNorm layers into one batched vector.  (Ignored with
         GroupNorm: nothing there is image independent; and with a folded dict: there is no iteration.)
         norm=None: "folded" when the state dict has bn1.scale, "group" when it has no bn1.running_mean, else "batch"; an
         explicit value must agree.
-        wide_norm=True: every norm site of a GroupNorm network is `group_norm(wide=True)`, right for any group variance in
-        (0, 30,000) at 3 <= precision_fractional <= 6; refused for a BatchNorm or folded network (fold_batch_norm is the
-        remedy there).
-        faithful_trunc=True: the context's products are truncated by `SecureContext.trunc_faithful` (the context's flag is set
-        here); a folded network only -- the Newton norms of the others truncate per share and are refused."""
+        `form` or its fields by keyword: `ProtocolForm` (the width is the context's dealer's; a faithful context makes it faithful)."""
+        form = ProtocolForm.of(form, **options)
         self.ctx = ctx
         self.input_size = input_size
         self.batched_newton = batched_newton
-        self.pooling = _check_pooling(pooling)
-        self.reveal = _check_reveal(reveal)
         self.norm = norm_of(state_dict.keys(), norm)
         self.blocks = blocks if blocks is not None else _default_blocks()
-        self.wide_norm = bool(wide_norm)
-        if self.wide_norm:
-            check_wide_norm(ctx.base, ctx.pf, self.norm)
-        self.faithful_trunc = bool(faithful_trunc) or ctx.faithful_trunc
-        if self.faithful_trunc:
-            check_faithful_trunc(self.norm)
-            ctx.faithful_trunc = True
+        self.form = dataclasses.replace(form, faithful_trunc=True) if ctx.faithful_trunc else form
+        self.form.check(self.norm, ctx.base, ctx.pf)
+        ctx.faithful_trunc = self.form.faithful_trunc
         if self.norm == "group":
             for n in _norm_prefixes(state_dict.keys(), self.blocks):
                 c = int(state_dict[n + ".weight"].shape[0])
@@ -1842,28 +1890,19 @@ def auc_requests(rows, classes, block_rows=None):
     return req
 
 
-def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal="logits", wide_norm=False,
-                   faithful_trunc=False):
+def image_requests(arch, input_size, batch=1, blocks=None, pooling=..., *, form=None, **options):
     """The primitives ONE protocol pass over `batch` images requests from the crypto provider, in order and in the form
     `Dealer.requests` records them — derived on the host from the architecture (name -> shape) alone, without a device:
     what `SecureResNet18.__call__` asks for (tests hold the two equal), so that the memory a serving form needs is known
     BEFORE anything is allocated.  Per batch, not per image: the 80-step Newton reciprocal (237 triples over all BatchNorm
     channels) and the weight side of every matmul triple; per image: everything with a row of its own.
-    pooling="avg": the stem is one ReLU at conv1's output resolution and a party-local average pool that requests nothing
-    (2,308,096 comparisons and 294 element-wise triples per 224 x 224 image, against 3,311,616 and 298 with the max tree).
     An architecture without running statistics is the GroupNorm network: no hoisted Newton; every norm site requests its
     square triple, the mask of eps, a Newton iteration on batch * 32 values and the two product triples.
-    wide_norm=True (GroupNorm only): that iteration is `rsqrt_newton`'s, GN_WIDE_STEPS - 1 steps of three triples and a mask
-    with no leading mask: 128 requests per site against 321.
     A folded architecture (`folded_architecture`, bn1.scale among its names): no Newton at all; every norm site requests the
     single triple ("mul", (B*h*h, c), (c,)) of `SecureContext.affine_eval`.
-    faithful_trunc=True (folded only): every conv2d, affine_eval and linear site requests the carry triple
-    ("mul", shape, shape) of `SecureContext.trunc_faithful` right after its product triple, shape that of the product.
-    reveal="class": the argmax tail's requests follow the fc triple (the logits form's list is a strict prefix).
-    reveal="confusion": the confusion tail's requests follow the argmax tail's (the class form's list is a strict prefix).
-    reveal="metrics": the confusion list (the rank-count tail runs once, after the last pass: auc_requests)."""
-    _check_pooling(pooling)
-    _check_reveal(reveal)
+    `form` or its fields by keyword: `ProtocolForm`, which says what each option requests; the width is ignored.  (`pooling`
+    alone is still taken as fifth positional argument too, here and in the two functions below: existing callers pass it so.)"""
+    form = ProtocolForm.of(form, **(options if pooling is ... else {"pooling": pooling, **options}))
     B, req = int(batch), []
     blocks = _default_blocks() if blocks is None else blocks
     triple = lambda op, xs, ys: req.append(("triple", (op, tuple(xs), tuple(ys)), {}))
@@ -1873,11 +1912,8 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     mask((B, cin, input_size, input_size), 1)                                  # the images, shared by the data owner
     norm = norm_of(arch)
     group = norm == "group"
-    if wide_norm:
-        check_wide_norm(10, GN_WIDE_PF[0], norm)      # (the list does not depend on the precision: only the norm is checked)
-    if faithful_trunc:
-        check_faithful_trunc(norm)
-    carry = lambda *shape: triple("mul", shape, shape) if faithful_trunc else None
+    form.check(norm)
+    carry = lambda *shape: triple("mul", shape, shape) if form.faithful_trunc else None
     names = _norm_prefixes(arch, blocks)
 
     def newton(n, wide=False):
@@ -1906,7 +1942,7 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
             R, m = B * GN_GROUPS, (c // GN_GROUPS) * h * h
             triple("mul", (R, m), (R, m))
             mask((1,), None)                                                   # + eps (wide: + eps + floor)
-            newton(R, wide_norm)
+            newton(R, form.wide_norm)
             triple("mul", (R,), (m, R))
         elif norm == "batch":
             triple("mul", (c,), (B * h * h, c))
@@ -1919,7 +1955,7 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
 
     c, h = conv("conv1", input_size, 2, 3)
     bn(c, h)
-    if pooling == "avg":
+    if form.pooling == "avg":
         relu(c, h)                                                             # ReLU first, then the pool: no primitives
         h = out_hw(h, 3, 2, 1)
     else:
@@ -1943,9 +1979,9 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling="max", reveal
     classes, feat = arch["fc.weight"]
     triple("matmul", (B, feat), (feat, classes))
     carry(B, classes)
-    if reveal != "logits":
+    if form.reveal != "logits":
         req += argmax_requests(B, classes)
-    if reveal in ACCUMULATING:
+    if form.reveal in ACCUMULATING:
         req += confusion_requests(B, classes)
     return req
 
@@ -1994,23 +2030,23 @@ def primitive_bytes(requests, fss_bits=FSS_BITS):
     return total
 
 
-def serving_bytes(arch, input_size, batch, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False,
-                  faithful_trunc=False):
+def serving_bytes(arch, input_size, batch, blocks=None, pooling=..., *, form=None, **options):
     """What GraphedSecureInference(batch=...) holds in static buffers: every primitive of one pass (dominated by the DIF
     keys: 1,244 bytes per comparison, 3,311,616 comparisons per 224 x 224 image, 2,308,096 with pooling="avg") plus one eighth on top for the arena copy of
     their random words while both exist (5/6 of a triple, 48 of a key's 1,244 bytes) and the captured graph's activations
     (im2col and pool-unroll operands: under 2 % of the keys at every layer).  A key of `fss_bits` levels takes 60 + 37 fss_bits
-    bytes: 2,428 at 64."""
-    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm, faithful_trunc), fss_bits)
+    bytes: 2,428 at 64.  `form` or its fields by keyword: `ProtocolForm`."""
+    form = ProtocolForm.of(form, **(options if pooling is ... else {"pooling": pooling, **options}))
+    b = primitive_bytes(image_requests(arch, input_size, batch, blocks, form=form), form.fss_bits)
     return b + b // 8
 
 
-def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max", reveal="logits", fss_bits=FSS_BITS,
-                            wide_norm=False, faithful_trunc=False):
+def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling=..., *, form=None, **options):
     """The largest batch whose static buffers fit in `budget` bytes (0: not even one image).  serving_bytes is affine in the
     batch (a per-batch part, Newton and the weight masks, plus a per-image part) up to its rounding, so two evaluations
-    give the answer and the neighbours settle the rounding."""
-    need = lambda k: serving_bytes(arch, input_size, k, blocks, pooling, reveal, fss_bits, wide_norm, faithful_trunc)
+    give the answer and the neighbours settle the rounding.  `form` or its fields by keyword: `ProtocolForm`."""
+    form = ProtocolForm.of(form, **(options if pooling is ... else {"pooling": pooling, **options}))
+    need = lambda k: serving_bytes(arch, input_size, k, blocks, form=form)
     one, two = need(1), need(2)
     per_image, fixed = two - one, 2 * one - two
     k = max(0, (int(budget) - fixed) // per_image)
@@ -2021,7 +2057,7 @@ def largest_batch_that_fits(arch, input_size, budget, blocks=None, pooling="max"
     return k
 
 
-class GraphedSecureInference:
+class GraphedSecureInference(_FormFields):
     """Serving form of the encrypted forward: the online phase (about 6,500 small launches per image) is
     captured ONCE as a hipGraph over static buffers — the input image and every correlated-randomness
     primitive — and replayed per image; `refill()` has the dealer regenerate all per-image primitives into
@@ -2042,54 +2078,36 @@ class GraphedSecureInference:
     and are dropped.  The static buffers are sized on the host first (`serving_bytes`) and a batch that does not fit in
     `memory_budget` bytes (default: the device's free memory plus what torch's allocator holds unused) is refused with the
     largest batch that would.
-
-    reveal="class": the argmax tail is part of the captured graph and the static output is the int64 [batch] buffer of class
-    indices; nothing else is reconstructed.
-
-    reveal="metrics": the captured pass is the confusion pass; it leaves copies of its logit and label shares in buffers of
-    the graph, which are copied out after each replay, and `finish()` runs the rank-count tail eagerly (its primitives come
-    from a dealer of the tail's own, seeded apart under a debug seed) before it opens the matrix and the counts.
-
-    reveal="confusion": the confusion tail is part of the captured graph too; the one-hot labels are a static int64
-    [batch, classes] buffer next to the images (`load` zero-fills the rows of padding images), the shares of the confusion
-    matrix a static buffer the captured pass adds into; `begin()` zeroes it, `finish()` opens it, a pass returns None.
-
-    fss_bits: the width of the comparisons (the dealer's; see FSS_BITS) -- wider keys count in the refusal above."""
+    `form` or its fields by keyword: `ProtocolForm`, which says what each `reveal` captures and holds in static buffers."""
 
     refill_graph = True
+    fss_bits = property(lambda self: self.form.fss_bits)      # (this form's own dealers are built at the form's width)
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
-                 memory_budget=None, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False, faithful_trunc=False):
+                 memory_budget=None, *, form=None, **options):
+        self.form = form = ProtocolForm.of(form, **options)
         self.device = torch.device(device)
         self.batch = int(batch)
-        self.wide_norm = bool(wide_norm)
-        self.faithful_trunc = bool(faithful_trunc)
-        self.fss_bits = check_fss_bits(fss_bits)
-        self.pooling = _check_pooling(pooling)
-        self.reveal = _check_reveal(reveal)
         if self.batch < 1:
             raise ValueError("batch must be at least 1")
         arch = architecture_of(state_dict)
-        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, pooling, reveal, self.fss_bits, wide_norm,
-                                          faithful_trunc)
+        self.static_bytes = serving_bytes(arch, input_size, self.batch, blocks, form=form)
         if memory_budget is None:
             free, _ = torch.cuda.mem_get_info(self.device)
             memory_budget = free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         if self.static_bytes > memory_budget:
-            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, pooling, reveal, self.fss_bits, wide_norm,
-                                           faithful_trunc)
+            fits = largest_batch_that_fits(arch, input_size, memory_budget, blocks, form=form)
             raise ValueError(f"a batch of {self.batch} images at {input_size}x{input_size} needs {self.static_bytes} bytes of static "
                              f"primitives, {int(memory_budget)} are free: the largest batch that fits is {fits}")
         # (all-zero warm-up images, uploaded: no fill kernel of torch's on the path)
         self.image = torch.zeros(self.batch, state_dict["conv1.weight"].shape[1], input_size, input_size, dtype=torch.float32).to(self.device)
         self.labels = None
-        if reveal in ACCUMULATING:      # (all-zero one-hot rows: the warm-up images are padding)
+        if self.reveal in ACCUMULATING:      # (all-zero one-hot rows: the warm-up images are padding)
             self.labels = torch.zeros(self.batch, int(state_dict["fc.weight"].shape[0]), dtype=I64).to(self.device)
         self.dealer = Dealer(self.device, seed, self.fss_bits)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
-        model = SecureResNet18(ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal, wide_norm=wide_norm,
-                               faithful_trunc=faithful_trunc)
+        model = SecureResNet18(ctx, state_dict, input_size, blocks, form=form)
         self._n_model = len(self.dealer.tape)          # primitives consumed by sharing the model (kept)
         model(self.image, labels=self.labels)          # offline pass: fills the tape, warms every kernel
         self.tape, self.requests = self.dealer.tape, self.dealer.requests
@@ -2098,8 +2116,7 @@ class GraphedSecureInference:
         self._rehome_tape()                            # per-image random words -> one arena (before any pointer is captured)
         pre = PreloadedDealer(self.tape, self.device, self.fss_bits)
         self._ctx = SecureContext(pre, base, precision_fractional)
-        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, pooling=pooling, reveal=reveal,
-                                     wide_norm=wide_norm, faithful_trunc=faithful_trunc)      # re-shares with the same masks
+        self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, form=form)      # re-shares with the same masks
         self._model(self.image, labels=self.labels)    # eager pass over the static buffers: builds the pointer tables
         pre.pos, self._ctx._newton_calls = self._n_model, 0
         side = torch.cuda.Stream(device=self.device)
@@ -2110,7 +2127,7 @@ class GraphedSecureInference:
                 self.out = self._model(self.image, labels=self.labels)
         torch.cuda.current_stream().wait_stream(side)
         self._static_rows = self._tail_ctx = None
-        if reveal == METRICS:
+        if self.reveal == METRICS:
             # the captured pass left its copies of the logit and label shares in buffers of the graph's own: every replay
             # rewrites them, and __call__ copies them out.  The tail runs eagerly after the last pass, on a dealer of its
             # own (this form's dealer draws on the device from here on, inside the refill graph)
@@ -2131,7 +2148,7 @@ class GraphedSecureInference:
                 with torch.cuda.graph(self._refill_g, stream=side):
                     self._refill_launches()
             torch.cuda.current_stream().wait_stream(side)
-        if reveal in ACCUMULATING:
+        if self.reveal in ACCUMULATING:
             self.begin()                               # (the warm-up passes added shares of zero)
 
     def begin(self):
@@ -2285,17 +2302,17 @@ class PipelinedSecureInference:
     vector ALUs with the online evaluation.  Events order a slot's refill after the replay that consumed it and the next replay after
     the refill.  Every image's shares are those of an eager SecureResNet18 on the slot's primitives (the graph is
     bit-identical to it, tests/test_gpu_secure.py); nothing about the protocol changes, only who waits for whom.
-    In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU."""
+    In the three-role deployment the same overlap is physical: the dealer rank runs ahead of the parties on its own GPU.
+    `form` or its fields by keyword: `ProtocolForm`; every slot is built with the one form."""
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
-                 batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, wide_norm=False, faithful_trunc=False):
+                 batch=1, *, form=None, **options):
+        self.form = form = ProtocolForm.of(form, **options)
         self.device = torch.device(device)
-        if reveal in ACCUMULATING:
-            raise ValueError(f'reveal="{reveal}" accumulates in one set of static buffers: use GraphedSecureInference')
+        if form.reveal in ACCUMULATING:
+            raise ValueError(f'reveal="{form.reveal}" accumulates in one set of static buffers: use GraphedSecureInference')
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
-                                             None if seed is None else seed + 7919 * k, blocks, batch, pooling=pooling,
-                                             reveal=reveal, fss_bits=fss_bits, wide_norm=wide_norm,
-                                             faithful_trunc=faithful_trunc)
+                                             None if seed is None else seed + 7919 * k, blocks, batch, form=form)
                       for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
@@ -2461,52 +2478,35 @@ class DealerService:
                 send(v, kw.get("owner"))
 
 
-def party_context(link: PartyLink, precision_fractional=16, base=10, fss_bits=FSS_BITS, faithful_trunc=False):
-    """SecureContext of the party this rank plays."""
-    return SecureContext(PartyDealer(link, fss_bits), base, precision_fractional,
+def party_context(link: PartyLink, precision_fractional=16, base=10, *, form=None, **options):
+    """SecureContext of the party this rank plays, at the width and with the truncation of the `ProtocolForm`."""
+    form = ProtocolForm.of(form, **options)
+    return SecureContext(PartyDealer(link, form.fss_bits), base, precision_fractional,
                          opener=DistOpener(link.parties_group, link.role), party=link.role, link=link,
-                         faithful_trunc=faithful_trunc)
+                         faithful_trunc=form.faithful_trunc)
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10, batch=1, pooling="max", reveal="logits", fss_bits=FSS_BITS, labels=None,
-                   wide_norm=False, faithful_trunc=False):
+                   precision_fractional=16, base=10, batch=1, *, labels=None, form=None, **options):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
-    all know the architecture, the input size, the stem pool (`pooling`), how many images will be classified and how many go
-    through one protocol pass (`batch`; the last pass is padded with all-zero images, whose rows are dropped).  Parties return the
-    list of decoded logits, one [<= batch, classes] tensor per pass (the reference `.get()`s the prediction to the
-    orchestrator), the dealer None.
-    reveal="class": every pass ends with the argmax tail and party 0 sends its share of the class indices to party 1, which
-    returns one int64 [<= batch] tensor per pass; party 0 learns nothing and returns None, like the dealer, which follows
-    the extended schedule.
-    reveal="confusion": party 1 also passes `labels`, int64 [n_images]; every pass ends with the confusion tail, after the last
-    the confusion matrix is opened between the parties, and both return it (int64 [classes, classes]); the dealer returns None.
-    reveal="metrics": the same passes; after the last the dealer serves auc_requests(passes * batch, classes), the parties run
-    the rank-count tail and both return (M, U).
-    fss_bits: the width of the comparisons, known to all three like the schedule.
-    wide_norm: the wide-range GroupNorm at every norm site (a GroupNorm architecture only), known to all three as well: the
-    parties run its step-by-step chain, the dealer follows image_requests(..., wide_norm=True).
-    faithful_trunc: the faithful truncation at the product sites of a folded architecture, known to all three too: the parties
-    run `trunc_faithful`'s chain (two more opens per site), the dealer follows image_requests(..., faithful_trunc=True)."""
-    _check_pooling(pooling)
-    _check_reveal(reveal)
-    fss_bits = check_fss_bits(fss_bits)
-    if wide_norm:
-        check_wide_norm(base, precision_fractional, norm_of(arch))
-    if faithful_trunc:
-        check_faithful_trunc(norm_of(arch))
+    all know the architecture, the input size, the `ProtocolForm` (`form`, or its fields by keyword), how many images will be
+    classified and how many go through one protocol pass (`batch`; the last pass is padded with all-zero images, whose rows are
+    dropped).  Parties return the list of decoded logits, one [<= batch, classes] tensor per pass (the reference `.get()`s the
+    prediction to the orchestrator), the dealer None; what the other `reveal`s return, and who passes `labels`: `ProtocolForm`."""
+    form = ProtocolForm.of(form, **options)
+    form.check(norm_of(arch), base, precision_fractional)
     passes = (n_images + batch - 1) // batch
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
-        image_req = image_requests(arch, input_size, batch, blocks, pooling, reveal, wide_norm, faithful_trunc)
-        svc = DealerService(Dealer(link.device, seed, fss_bits), link)
+        image_req = image_requests(arch, input_size, batch, blocks, form=form)
+        svc = DealerService(Dealer(link.device, seed, form.fss_bits), link)
         svc.serve(model_requests(arch))
         for _ in range(passes):
             svc.serve(image_req)
-        if reveal == METRICS:      # the rank-count tail over every row held, padding rows included
+        if form.reveal == METRICS:      # the rank-count tail over every row held, padding rows included
             svc.serve(auc_requests(passes * batch, arch["fc.weight"][0]))
         return None
-    ctx = party_context(link, precision_fractional, base, fss_bits, faithful_trunc)
+    ctx = party_context(link, precision_fractional, base, form=form)
     if link.role == 0:
         if state_dict is None:
             raise ValueError("party 0 is the model owner: it needs the state dict")
@@ -2515,8 +2515,8 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         if images is None:
             raise ValueError("party 1 is the data owner: it needs the images")
         shapes = {k: torch.empty(shape, device="meta") for k, shape in arch.items()}
-    model = SecureResNet18(ctx, shapes, input_size, blocks, pooling=pooling, reveal=reveal, wide_norm=wide_norm)
-    if reveal in ACCUMULATING:
+    model = SecureResNet18(ctx, shapes, input_size, blocks, form=form)
+    if form.reveal in ACCUMULATING:
         if link.role == 1 and (labels is None or labels.numel() != n_images):
             raise ValueError("party 1 is the data owner: it needs one label per image")
         model.begin()
@@ -2528,9 +2528,9 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
             chunk = images[i:i + n]
             if n < batch:
                 chunk = torch.cat([chunk, chunk.new_zeros((batch - n,) + tuple(chunk.shape[1:]))])
-        res = model(chunk, batch=batch, labels=labels[i:i + n] if reveal in ACCUMULATING and link.role == 1 else None)
+        res = model(chunk, batch=batch, labels=labels[i:i + n] if form.reveal in ACCUMULATING and link.role == 1 else None)
         if res is not None:
             out.append(res if n == batch else res[:n])
-    if reveal in ACCUMULATING:
+    if form.reveal in ACCUMULATING:
         return model.finish()
-    return None if reveal == "class" and link.role == 0 else out
+    return None if form.reveal == "class" and link.role == 0 else out

@@ -30,8 +30,7 @@ if __name__ == "__main__":
         labels = case.labels(sd, images, pf)
     res = run_three_role(link, arch, case.size, len(images), state_dict=sd if link.role == 0 else None,
                          images=images.to(device) if link.role == 1 else None, seed=seed, blocks=case.blocks,
-                         precision_fractional=pf, batch=case.batch, pooling=case.pooling, reveal=case.reveal,
-                         fss_bits=case.fss_bits, labels=labels)
+                         precision_fractional=pf, batch=case.batch, labels=labels, form=case.form())
     if link.role in ((1,) if case.reveal == "class" else (0, 1)):
         held = [res] if case.reveal == "confusion" else list(res)
         assert [tuple(t.shape) for t in held] == case.shapes

@@ -168,7 +168,7 @@ def in_process_logits(cuda, case, pf, seed):
         rows.append(model(padded(chunk, c.batch))[:len(chunk)])
     assert [tuple(r.shape) for r in rows] == c.shapes
     arch = architecture_of(sd)
-    assert dealer.requests == model_requests(arch) + len(rows) * image_requests(arch, c.size, c.batch, c.blocks, c.pooling)
+    assert dealer.requests == model_requests(arch) + len(rows) * image_requests(arch, c.size, c.batch, c.blocks, pooling=c.pooling)
     return torch.cat(rows).cpu()
 
 

@@ -4,8 +4,6 @@ folded networks are held BIT-EXACT to that composition, the reference's per-shar
 same shares, and the decoded logits follow the float64 plaintext model where the reference's form does not -- in the eager,
 graphed, three-role and CLI forms."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -18,8 +16,8 @@ from primia_amd._lib import PrimiaError, call  # noqa: E402
 from primia_amd.secure import (Dealer, GraphedSecureInference, PreloadedDealer, SecureContext, SecureResNet18,  # noqa: E402
                                architecture_of, expected_wraps, fold_batch_norm, image_requests, model_requests, serving_bytes)
 from tests.secure_batch_nets import MINI_BLOCKS, numpy_sd  # noqa: E402
-from tests.secure_common import (I64, ROOT, context, guarded, guards_intact, host, host_ptrs, json_line, oracle_pool,  # noqa: E402,F401
-                                 padded, run_inference, run_roles, shares_equal, time_limit, wrapping_shares, write_checkpoint)
+from tests.secure_common import (I64, context, guarded, guards_intact, host, host_ptrs, json_line, oracle_pool,  # noqa: E402,F401
+                                 padded, run_inference, shares_equal, three_roles, time_limit, wrapping_shares, write_checkpoint)
 from tests.secure_faithful_nets import (ERR, FAITHFUL_TOL, FaithfulOracleContext, oracle_trunc_faithful, wrap_case,  # noqa: E402
                                         wrapping_pair)
 from tests.secure_folded_nets import oracle_affine_eval, oracle_folded_forward, plaintext_logits, wide_mini, wide_resnet18  # noqa: E402
@@ -325,11 +323,12 @@ def test_graphed_faithful_matches_eager_across_a_refill(cuda, reveal):
 
 # ---- 5. three roles ---------------------------------------------------------------------------------------------------------------
 def test_three_role_faithful_bit_identical_to_in_process(cuda, tmp_path):
-    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (tests/party_worker_faithful.py
-    through the suite's launcher): the parties run the faithful chain, whose two opens per site are messages, the dealer
+    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (the "faithful" case of
+    tests/three_role_cases.py through the suite's worker and launcher): the parties run the faithful chain, whose two opens per site are messages, the dealer
     follows image_requests(faithful_trunc=True); both parties' logits equal the in-process run's under the same debug seed."""
     pf, seed = 6, 5
-    case = CASES["folded"]
+    case = CASES["faithful"]
+    assert case.batch == CASES["folded"].batch == 2
     sd, images = case.tensors()
     folded = fold_batch_norm(sd)
     with time_limit(600):
@@ -345,8 +344,7 @@ def test_three_role_faithful_bit_identical_to_in_process(cuda, tmp_path):
         assert dealer.requests == model_requests(arch) + 2 * image_requests(arch, case.size, case.batch, case.blocks,
                                                                             faithful_trunc=True)
         out = str(tmp_path / "logits")
-        cmd = [sys.executable, os.path.join(ROOT, "tests", "party_worker_faithful.py"), out, str(pf), str(seed), str(case.batch)]
-        run_roles([cmd] * 3, out, what="faithful truncation")
+        three_roles("faithful", pf, seed, out)
         for j in range(2):
             assert torch.equal(torch.load(f"{out}.{j}"), want), j
 

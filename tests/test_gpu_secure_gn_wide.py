@@ -3,8 +3,6 @@ defined in tests/secure_gn_wide_nets.py from the oracle's own methods; the new e
 step-by-step chain and whole networks are held BIT-EXACT to that composition, the decoded logits to the float64 plaintext
 forward within twice what the CPU composition measured, in the eager, graphed, three-role and CLI forms."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
@@ -19,8 +17,9 @@ from primia_amd.secure import (GN_WIDE_FLOOR, GN_WIDE_SCALE, GN_WIDE_STEPS, GN_W
                                image_requests, model_requests, serving_bytes)
 from tests import secure_gn_wide_nets as W  # noqa: E402
 from tests.secure_batch_nets import MINI_BLOCKS, mini_resnet, numpy_sd  # noqa: E402
-from tests.secure_common import (ROOT, context, guarded, guards_intact, host, host_ptrs, json_line,  # noqa: E402,F401
-                                 oracle_pool, run_inference, run_roles, shares_equal, six, write_checkpoint)
+from tests.secure_common import (context, guarded, guards_intact, host, host_ptrs, json_line,  # noqa: E402,F401
+                                 oracle_pool, run_inference, shares_equal, six, three_roles, write_checkpoint)
+from tests.three_role_cases import CASES  # noqa: E402
 from tests.secure_groupnorm_nets import VAR_DOMAIN, default_blocks, plain_group_forward  # noqa: E402
 
 SHAPES = [(1, 64, 6, 6), (3, 64, 5, 5), (2, 128, 4, 4)]      # (3, 64, 5, 5): m = 50, R = 96, two workgroups of the iteration
@@ -254,10 +253,11 @@ def test_graphed_wide_matches_eager_on_two_image_sets(cuda):
 
 
 def test_three_role_wide_bit_identical_to_in_process(cuda, tmp_path):
-    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (tests/party_worker_gn_wide.py
-    through the suite's launcher): the parties run the wide form's step-by-step chain, the dealer follows
+    """model_owner / data_owner / crypto_provider as three processes on one GPU over gloo (the "gn-wide" case of
+    tests/three_role_cases.py through the suite's worker and launcher): the parties run the wide form's step-by-step chain, the dealer follows
     image_requests(wide_norm=True); both parties' logits equal the in-process run's under the same debug seed."""
-    pf, seed, batch = 3, 5, 2
+    pf, seed, batch = 3, 5, CASES["gn-wide"].batch
+    assert batch == 2
     sd, blocks = W.wide_networks()["mini"]
     images = W.spread_images()
     dealer = Dealer(cuda, seed=seed)
@@ -269,8 +269,7 @@ def test_three_role_wide_bit_identical_to_in_process(cuda, tmp_path):
     arch = architecture_of(sd)
     assert dealer.requests == model_requests(arch) + 2 * image_requests(arch, 32, batch, blocks, wide_norm=True)
     out = str(tmp_path / "logits")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "party_worker_gn_wide.py"), out, str(pf), str(seed), str(batch)]
-    run_roles([cmd] * 3, out, what="wide GroupNorm")
+    three_roles("gn-wide", pf, seed, out)
     for j in range(2):
         assert torch.equal(torch.load(f"{out}.{j}"), want), j
 

@@ -104,15 +104,16 @@ def flat(req):
 def test_image_requests_with_the_flag(B, reveal):
     """image_requests(faithful_trunc=True) of a folded architecture is the flag-off list with one ("mul", shape, shape) triple
     right after each conv2d, affine_eval and linear product triple, shape that of the product; it is what a walk of
-    oracle_folded_forward on a context with FaithfulProducts asks for; with the flag off the list is the one the positional
-    call of old gives; the primitive bytes grow by exactly the carry triples', the static bytes follow."""
+    oracle_folded_forward on a context with FaithfulProducts asks for; with the flag off the list is the default's, and an option
+    passed by position is a TypeError; the primitive bytes grow by exactly the carry triples', the static bytes follow."""
     for sd, blocks, convs in ((mini_resnet(torch.Generator().manual_seed(21)), MINI_BLOCKS, 6), (resnet18(32, 320), None, 20)):
         folded = fold_batch_norm(sd)
         arch = architecture_of(folded)
-        off = image_requests(arch, 32, B, blocks, "max", reveal)
-        assert off == image_requests(arch, 32, B, blocks, "max", reveal, False, False)
-        assert off == image_requests(arch, 32, B, blocks, "max", reveal, faithful_trunc=False)
-        on = image_requests(arch, 32, B, blocks, "max", reveal, faithful_trunc=True)
+        off = image_requests(arch, 32, B, blocks, pooling="max", reveal=reveal)
+        with pytest.raises(TypeError):      # an option by position
+            image_requests(arch, 32, B, blocks, "max", reveal, False, False)
+        assert off == image_requests(arch, 32, B, blocks, pooling="max", reveal=reveal, faithful_trunc=False)
+        on = image_requests(arch, 32, B, blocks, pooling="max", reveal=reveal, faithful_trunc=True)
         want, carries = [], []
         for kind, args, kw in off:
             want.append((kind, args, kw))
@@ -129,12 +130,12 @@ def test_image_requests_with_the_flag(B, reveal):
         extra = sum(16 * 3 * int(np.prod(s)) for s in carries)
         b_off, b_on = primitive_bytes(off), primitive_bytes(on)
         assert b_on - b_off == extra
-        assert serving_bytes(arch, 32, B, blocks, "max", reveal) == b_off + b_off // 8
-        assert serving_bytes(arch, 32, B, blocks, "max", reveal, faithful_trunc=True) == b_on + b_on // 8
-        budget = serving_bytes(arch, 32, 2, blocks, "max", reveal, faithful_trunc=True)
-        assert largest_batch_that_fits(arch, 32, budget, blocks, "max", reveal, faithful_trunc=True) == 2
-        assert largest_batch_that_fits(arch, 32, budget - 1, blocks, "max", reveal, faithful_trunc=True) == 1
-        assert largest_batch_that_fits(arch, 32, budget - 1, blocks, "max", reveal) >= 2
+        assert serving_bytes(arch, 32, B, blocks, pooling="max", reveal=reveal) == b_off + b_off // 8
+        assert serving_bytes(arch, 32, B, blocks, pooling="max", reveal=reveal, faithful_trunc=True) == b_on + b_on // 8
+        budget = serving_bytes(arch, 32, 2, blocks, pooling="max", reveal=reveal, faithful_trunc=True)
+        assert largest_batch_that_fits(arch, 32, budget, blocks, pooling="max", reveal=reveal, faithful_trunc=True) == 2
+        assert largest_batch_that_fits(arch, 32, budget - 1, blocks, pooling="max", reveal=reveal, faithful_trunc=True) == 1
+        assert largest_batch_that_fits(arch, 32, budget - 1, blocks, pooling="max", reveal=reveal) >= 2
 
 
 # ---- 3. expected_wraps ----------------------------------------------------------------------------------------------------------

@@ -141,7 +141,7 @@ def test_image_requests_of_a_folded_pass(B, pooling):
         assert len(first) == sites
         rest = [r for r in bn_req[:1] + bn_req[318:] if r not in first]
         assert rest == got and len(bn_req) - len(got) == 237 + 80 + sites
-        assert bn_req == image_requests(architecture_of(sd), 32, B, blocks, pooling, "logits")
+        assert bn_req == image_requests(architecture_of(sd), 32, B, blocks, pooling, reveal="logits")
         b = primitive_bytes(got)
         assert serving_bytes(arch, 32, B, blocks, pooling) == b + b // 8 == b * 9 // 8
         assert serving_bytes(arch, 32, B, blocks, pooling) < serving_bytes(architecture_of(sd), 32, B, blocks, pooling)

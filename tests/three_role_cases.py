@@ -58,16 +58,31 @@ def auc_labels(sd, images, pf):
 
 # tensors: () -> (checkpoint, images); blocks None: the eight of a ResNet-18; fold: the model owner folds the BatchNorm sites
 # before sharing; labels: (checkpoint, images, pf) -> the data owner's int64 labels, or None; shapes: of what a party that
-# holds a result holds -- logits and classes per pass, the opened matrix, the matrix and the rank counts
-Case = namedtuple("Case", "tensors size blocks batch pooling reveal fss_bits fold labels shapes")
+# holds a result holds -- logits and classes per pass, the opened matrix, the matrix and the rank counts; pooling, reveal,
+# fss_bits, wide_norm, faithful_trunc: the fields of the ProtocolForm the three roles run under (Case.form)
+class Case(namedtuple("Case", "tensors size blocks batch pooling reveal fss_bits fold labels shapes wide_norm faithful_trunc")):
+    def form(self):
+        from primia_amd.secure import ProtocolForm
+
+        return ProtocolForm(pooling=self.pooling, reveal=self.reveal, fss_bits=self.fss_bits, wide_norm=self.wide_norm,
+                            faithful_trunc=self.faithful_trunc)
 
 
-def logits_case(tensors, size, blocks, batch, shapes, pooling="max", fss_bits=32, fold=False):
-    return Case(tensors, size, blocks, batch, pooling, "logits", fss_bits, fold, None, shapes)
+def logits_case(tensors, size, blocks, batch, shapes, pooling="max", fss_bits=32, fold=False, wide_norm=False,
+                faithful_trunc=False):
+    return Case(tensors, size, blocks, batch, pooling, "logits", fss_bits, fold, None, shapes, wide_norm, faithful_trunc)
 
 
 def reveal_case(norm, reveal, labels, shapes):
-    return Case(lambda: network_case(norm), 32, None, THREE_RANK_BATCH, "max", reveal, 32, False, labels, shapes)
+    return Case(lambda: network_case(norm), 32, None, THREE_RANK_BATCH, "max", reveal, 32, False, labels, shapes, False, False)
+
+
+def gn_wide_net():
+    """The mini GroupNorm network whose group variances spread over four decades, and its three images (the wide-range
+    GroupNorm's whole-network case)."""
+    from tests import secure_gn_wide_nets as W
+
+    return W.wide_networks()["mini"][0], W.spread_images()
 
 
 # three images at two per pass pad the second pass
@@ -78,7 +93,9 @@ CASES = {
     "group": logits_case(drawn(group_mini, 71, 3, 32), 32, MINI_BLOCKS, 2, [(2, 3), (1, 3)]),
     "folded": logits_case(drawn(wide_mini, 81, 3, 32), 32, MINI_BLOCKS, 2, [(2, 3), (1, 3)], fold=True),
     "wide": logits_case(wide_net, 32, None, 2, [(2, 3)], fss_bits=64),
+    "gn-wide": logits_case(gn_wide_net, 32, MINI_BLOCKS, 2, [(2, 3), (1, 3)], wide_norm=True),
 }
+CASES["faithful"] = CASES["folded"]._replace(faithful_trunc=True)      # the folded case's tensors, truncated faithfully
 for _norm in ("batch", "group"):
     CASES[f"class-{_norm}"] = reveal_case(_norm, "class", None, [(3,), (1,)])
     CASES[f"confusion-{_norm}"] = reveal_case(_norm, "confusion", confusion_labels(_norm), [(3, 3)])

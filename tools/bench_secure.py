@@ -20,11 +20,15 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    primitives, next to the same run's per-image online time
     --fss_bits N:  the width of the comparisons, 32 (default, the reference's) to 64: N levels per key and per evaluation (the
                    report names it when it is not 32)"""
-import argparse, json, os, sys, time
+import argparse, dataclasses, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from primia_amd import resnet_spec as rs
-from primia_amd.secure import Dealer, PreloadedDealer, SecureContext, SecureResNet18, fold_batch_norm
+from primia_amd.secure import Dealer, PreloadedDealer, ProtocolForm, SecureContext, SecureResNet18, fold_batch_norm
+
+def non_default(form):
+    """The fields of a ProtocolForm that differ from their defaults, as a dict."""
+    return {f.name: getattr(form, f.name) for f in dataclasses.fields(form) if getattr(form, f.name) != f.default}
 
 def main():
     ap = argparse.ArgumentParser()
@@ -113,18 +117,18 @@ def main():
     sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, a.pooling), "group" if a.norm == "group" else "batch")
     if a.norm == "folded":
         sd = fold_batch_norm(sd)
-    # (the report of the default keeps its keys: "pooling" appears for avg only, "norm" for group only)
-    pool_kw = {} if a.pooling == "max" else {"pooling": a.pooling}
-    norm_kw = {} if a.norm == "batch" else {"norm": a.norm}
-    reveal_kw = {} if a.reveal == "logits" else {"reveal": a.reveal}
-    bits_kw = {} if a.fss_bits == 32 else {"fss_bits": a.fss_bits}
-    form_kw = {**({"wide_norm": True} if a.wide_norm else {}), **({"faithful_trunc": True} if a.faithful_trunc else {})}
+    form = ProtocolForm(pooling=a.pooling, reveal=a.reveal, fss_bits=a.fss_bits, wide_norm=a.wide_norm,
+                        faithful_trunc=a.faithful_trunc)
+    # (the report of the default keeps its keys: an option is named only where it differs from the default -- "pooling" for
+    # avg only, "norm" for group and folded only -- and in the order the report has always had)
+    named = {**non_default(form), **({} if a.norm == "batch" else {"norm": a.norm})}
+    form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits") if k in named}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
     def run(dealer, share_model=True):
         ctx = SecureContext(dealer, 10, a.pf)
-        model = SecureResNet18(ctx, sd, input_size=a.size, **pool_kw, **reveal_kw, **form_kw)
+        model = SecureResNet18(ctx, sd, input_size=a.size, form=form)
         torch.cuda.synchronize(); t0 = time.perf_counter()
         out = model(img)
         torch.cuda.synchronize()
@@ -198,7 +202,7 @@ def main():
         B, reps = a.batch, max(a.images, 3)
         imgs = torch.randn(B, 3, a.size, a.size, generator=g).to(dev)
         free = torch.cuda.mem_get_info(dev)[0]
-        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, **pool_kw, **reveal_kw, **bits_kw, **form_kw)
+        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, form=form)
         # (an evaluation's passes carry the data owner's labels: seeded, one per image)
         lab_kw = {"labels": torch.randint(0, 3, (B,), generator=g)} if a.reveal in ("confusion", "metrics") else {}
         gi(imgs, refill=False, **lab_kw); torch.cuda.synchronize()
@@ -229,7 +233,7 @@ def main():
             with_dealer = (time.perf_counter() - t0) * 1e3
             rows, classes = passes * B, int(sd["fc.weight"].shape[0])
             comparisons = tail_ctx.stats["dif_evals"] - evals0
-            pre = SecureContext(PreloadedDealer(tail_ctx.dealer.tape, dev, **bits_kw), 10, a.pf)
+            pre = SecureContext(PreloadedDealer(tail_ctx.dealer.tape, dev, fss_bits=form.fss_bits), 10, a.pf)
             for u in gi._model.U:
                 u.zero_()
             t0 = time.perf_counter(); gi._model.finish(ctx=pre); torch.cuda.synchronize()
@@ -241,12 +245,12 @@ def main():
                        "tail_online_ms": round(tail_online, 1), "tail_gather_rows_ms": round(gather, 1), "tail_with_dealer_ms": round(with_dealer, 1),
                        "tail_online_in_images": round(tail_online / (online / B), 2),
                        "tail_expected_in_images": round(2 * classes * rows * rows / 3311616, 2)}
-        print(json.dumps({"metric": "encrypted_inference_batch", **pool_kw, **norm_kw, **form_kw, **reveal_kw, **bits_kw, "batch": B, "size": a.size, "precision_fractional": a.pf,
+        print(json.dumps({"metric": "encrypted_inference_batch", **form_report, "batch": B, "size": a.size, "precision_fractional": a.pf,
                           "online_ms_per_image": round(online / B, 2), "with_refill_ms_per_image": round(both / B, 2),
                           "online_ms_per_pass": round(online, 2), "with_refill_ms_per_pass": round(both, 2),
                           "static_primitive_bytes": gi.static_bytes, "arena_mb": round(gi._arena.numel() * 8 / 1e6, 1),
                           "device_free_bytes_before": free,
-                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, **pool_kw, **reveal_kw, **bits_kw, **form_kw),
+                          "largest_batch_that_fits": largest_batch_that_fits(architecture_of(sd), a.size, free, form=form),
                           "dif_evals": gi.stats["dif_evals"], **({"dpf_evals": gi.stats["dpf_evals"]} if "dpf_evals" in gi.stats else {}),
                           "beaver_matmul": gi.stats["beaver_matmul"],
                           "beaver_mul": gi.stats["beaver_mul"], **tail_kw}))
@@ -260,12 +264,12 @@ def main():
         return
 
     # warm-up (JIT-free, but first launches / allocator)
-    run(Dealer(dev, seed=0, **bits_kw))
+    run(Dealer(dev, seed=0, fss_bits=form.fss_bits))
     res = []
     for i in range(a.images):
-        d = Dealer(dev, seed=100 + i, **bits_kw); d.tape = []
+        d = Dealer(dev, seed=100 + i, fss_bits=form.fss_bits); d.tape = []
         t_total, out_a, ctx = run(d)
-        t_online, out_b, _ = run(PreloadedDealer(d.tape, dev, **bits_kw))
+        t_online, out_b, _ = run(PreloadedDealer(d.tape, dev, fss_bits=form.fss_bits))
         assert torch.equal(out_a.cpu(), out_b.cpu()), "replayed run must be bit-identical"
         res.append((t_total, t_online))
         del d
@@ -279,9 +283,9 @@ def main():
         try:
             from primia_amd.secure import GraphedSecureInference
 
-            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, **pool_kw, **reveal_kw, **bits_kw, **form_kw)
-            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, **bits_kw), 10, a.pf)
-            out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, **pool_kw, **reveal_kw, **form_kw)(img)
+            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, form=form)
+            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, fss_bits=form.fss_bits), 10, a.pf)
+            out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, form=form)(img)
             assert torch.equal(gi(img, refill=False).cpu(), out_ref.cpu()), "graph replay must be bit-identical"
             torch.cuda.synchronize(); t0 = time.perf_counter()
             for _ in range(3):
@@ -302,7 +306,7 @@ def main():
             # on its own stream while the other replays): wall time per image, every image on fresh primitives
             from primia_amd.secure import PipelinedSecureInference
 
-            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, **pool_kw, **reveal_kw, **bits_kw, **form_kw)
+            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, form=form)
             for _ in range(2):
                 pi(img)
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -330,7 +334,7 @@ def main():
 
     extra = {"cpu_baseline": cpu_sample_report(cpu_t, ctx.stats["dif_evals"])} if cpu_t else {}
     extra["roofline"] = fss_roofline()
-    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **pool_kw, **norm_kw, **form_kw, **reveal_kw, **bits_kw, "online_ms": round(to * 1e3, 1),
+    print(json.dumps({"metric": "encrypted_inference_ms_per_image", **form_report, "online_ms": round(to * 1e3, 1),
                       "online_graph_ms": None if graph_ms is None else round(graph_ms, 1),
                       "dealer_refill_ms": None if refill_ms is None else round(refill_ms, 1),
                       "dealer_refill_launches": refill_nodes, "dealer_keystream_mb_per_image": None if arena_mb is None else round(arena_mb, 1),
