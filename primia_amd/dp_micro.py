@@ -5,7 +5,9 @@ statistics, so the clipped sum splits exactly:
 
     sum_n clip_n g_n  =  sum over micro-batches k of ( sum over the samples of micro-batch k of clip_n g_n )
 
-The logical batch runs as passes of (forward, per-sample clip, clipped sum) on an engine of M = root.N slots; every pass
+The logical batch runs as passes of (forward, per-sample clip, clipped sum) on an engine of M = root.N slots.  Every pass
+is told its phase ("first", "more", "last"; None for a step of one pass) and the logical batch size as ARGUMENTS, which
+step.eager_step / graphed_train.graphed_step hand to loss_backward: nothing is left on the engine between passes.  Every pass
 but the last adds its clipped sum to the root's fp32 accumulator (primia_dp_accumulate into engine.dp_acc), the last one
 adds the accumulator, the noise — ONE draw, one counter advance — and the division in one kernel
 (primia_dp_noise_add_acc), and ONE optimizer step follows.  The mechanism, its sensitivity and the accountant are those
@@ -33,45 +35,34 @@ def phase_of(i, count):
     return "first" if i == 0 else ("last" if i == count - 1 else "more")
 
 
-def step(engine, optimizer, data, target, hip_graph=False):
+def step(engine, optimizer, data, target, hip_graph=False, soft=False):
     """One logical DP-SGD step of `engine` (the loop's model) on (data, target): contiguous views of root.N rows — a
-    shorter final view runs on sibling() — each through forward and loss_backward under its phase, then optimizer.step()
-    once.  `hip_graph`: every full-size pass goes through graphed_step (one graph per phase; the last phase's graph holds
-    the optimizer step).  Returns a device scalar, the mean of the pass losses weighted by their valid rows; nothing
-    here waits for the device."""
+    shorter final view runs on sibling() — each through eager_step under its phase, the last of which takes the ONE
+    optimizer step.  `hip_graph`: every pass goes through graphed_step instead (one graph per phase; the last phase's
+    graph holds the optimizer step; a ragged pass runs eagerly there).  `soft`: handed on — a DP engine refuses soft
+    targets.  Returns a device scalar, the mean of the pass losses weighted by their valid rows; nothing here waits for
+    the device."""
     root = engine._root
     if root.dp_params is None:
         raise _lib.PrimiaError("dp_micro.step: the engine has no dp_params (micro-batches are a DP-SGD feature: plain "
                                "gradient accumulation would change BatchNorm's statistics)")
+    if hip_graph:
+        from .graphed_train import graphed_step as one_pass
+    else:
+        from .step import eager_step as one_pass
     masked = root.dp_params.get("expected_batch") is not None
     n = int(data.shape[0])
     cuts = views(n, root.N)
-    if hip_graph:
-        from .graphed_train import graphed_step
     total, weight = None, None
-    try:
-        root.dp_logical_batch = n
-        for i, (a, b) in enumerate(cuts):
-            root.dp_phase = phase = phase_of(i, len(cuts))
-            x, y = data[a:b], target[a:b]
-            if hip_graph:
-                loss = graphed_step(engine, optimizer, x, y)
-            else:
-                eng = root.sibling(b - a)
-                optimizer.zero_grad()
-                eng.forward(x)
-                loss = eng.loss_backward(y)
-                if phase in (None, "last"):
-                    optimizer.step() if eng is optimizer.engine else optimizer.step(eng)
-            if len(cuts) == 1:
-                return loss
-            # (a masked pass's loss is the mean over ITS valid rows, 0 when it has none)
-            w = (y >= 0).sum().to(torch.float32) if masked else float(b - a)
-            total = loss * w if total is None else total + loss * w
-            weight = w if weight is None else weight + w
-    finally:
-        root.dp_phase = None
-        root.dp_logical_batch = None
+    for i, (a, b) in enumerate(cuts):
+        x, y = data[a:b], target[a:b]
+        loss = one_pass(engine, optimizer, x, y, soft=soft, phase=phase_of(i, len(cuts)), logical_batch=n)
+        if len(cuts) == 1:
+            return loss
+        # (a masked pass's loss is the mean over ITS valid rows, 0 when it has none)
+        w = (y >= 0).sum().to(torch.float32) if masked else float(b - a)
+        total = loss * w if total is None else total + loss * w
+        weight = w if weight is None else weight + w
     if masked:
         return (total / weight.clamp(min=1.0)).reshape(loss.shape)
     return (total / weight).reshape(loss.shape)

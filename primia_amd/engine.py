@@ -649,11 +649,8 @@ class ResNet18Engine:
     # logical step releases a noisy count and moves it.  The root's, like dp_noise: a sibling on a ragged batch uses it.
     dp_clip = None
     # A logical DP-SGD step larger than the engine (primia_amd.dp_micro.step): the host loops run it as this many passes of
-    # N slots each.  The step helper sets, on the ROOT, the phase of the pass about to run (None: an ordinary step;
-    # "first" / "more": clipped sum into dp_acc; "last": dp_acc + this pass, noise, division) and the logical batch size.
+    # N slots each, and tell loss_backward the phase of each pass.
     dp_micro_batches = 1
-    dp_phase = None
-    dp_logical_batch = None
 
     @property
     def dp_acc(self):
@@ -664,17 +661,15 @@ class ResNet18Engine:
             root._dp_acc = torch.zeros(self.P, dtype=torch.float32, device=self.device)
         return root._dp_acc
 
-    def loss_backward(self, target, soft=False):
+    def loss_backward(self, target, soft=False, phase=None, logical_batch=None):
         """Cross entropy (hard int64 labels, or soft [N, classes] fp32 targets as in
-        Cross_entropy_one_hot) + full backward into `grads`.  Returns the device loss scalar."""
+        Cross_entropy_one_hot) + full backward into `grads`.  Returns the device loss scalar.
+        `phase`, `logical_batch` (DP-SGD only): this call is a pass of a logical step cut into micro-batches
+        (primia_amd.dp_micro) — dp_loss_backward's `accumulate` and `logical_batch`."""
         if self.dp_params is not None:
             if soft:
                 raise _lib.PrimiaError("DP-SGD path takes hard labels")
-            phase = getattr(self._root, "dp_phase", None)
-            if phase is not None:
-                return self.dp_loss_backward(target, **self.dp_params, accumulate=phase,
-                                             logical_batch=self._root.dp_logical_batch)
-            return self.dp_loss_backward(target, **self.dp_params)
+            return self.dp_loss_backward(target, **self.dp_params, accumulate=phase, logical_batch=logical_batch)
         if soft:
             call("primia_xent_soft", self.logits, target, self.class_weight, self.loss, self.dlogits, self.N,
                  self.spec.num_classes)

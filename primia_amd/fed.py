@@ -22,6 +22,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
+from .step import train_step
 
 
 class HipArenaOps:
@@ -286,8 +287,6 @@ def federated_epoch(engine, loader, args, optimizer=None, group=None, ops=None, 
     losses = []
     it = iter(loader)
     hip_graph = getattr(args, "hip_graph", False)
-    if hip_graph:
-        from .graphed_train import graphed_step
 
     def sync(final, batch_idx):
         fedavg_allreduce(engine.flat, local_flat, weight, secure, pf, 10, group, ops, scratch, masks)
@@ -301,20 +300,7 @@ def federated_epoch(engine, loader, args, optimizer=None, group=None, ops=None, 
     for batch_idx in range(sched.max_batches):
         if sched.trains(rank, batch_idx):
             data, target = next(it)
-            if getattr(engine, "dp_micro_batches", 1) > 1:
-                # the loader's batch is ONE logical DP-SGD step, run as passes of the engine's size (dp_micro)
-                from . import dp_micro
-
-                losses.append(dp_micro.step(engine, optimizer, data, target, hip_graph=hip_graph).clone())
-            elif hip_graph:
-                losses.append(graphed_step(engine, optimizer, data, target, soft=soft_targets).clone())
-            else:
-                optimizer.zero_grad()
-                sib = getattr(engine, "sibling", None)       # (the ragged final batch of a client's loader)
-                eng = engine if sib is None else sib(data.shape[0])
-                eng.forward(data)
-                losses.append(eng.loss_backward(target, soft=soft_targets).clone())
-                optimizer.step() if eng is engine else optimizer.step(eng)
+            losses.append(train_step(engine, optimizer, data, target, soft=soft_targets, hip_graph=hip_graph).clone())
         if sched.sync_after(batch_idx):
             sync(False, batch_idx)
             if not args.keep_optim_dict:

@@ -26,8 +26,9 @@ stream's device counter and the next node advances it, so every replay draws fre
 first step of a key runs eagerly (real training that also allocates the engine's lazy buffers), the second is captured
 and replayed.
 
-A DP-SGD step cut into micro-batch passes (primia_amd.dp_micro: the root's `dp_phase` is set) is captured per PHASE: the
-key gains ("micro-batch", phase, 1 / batch), the "first" and "more" graphs end with the clipped sum going into the root's
+A DP-SGD step cut into micro-batch passes (primia_amd.dp_micro hands graphed_step each pass's `phase` and the
+`logical_batch`, which go on to _key, _StepGraph and loss_backward as arguments) is captured per PHASE: the key gains
+("micro-batch", phase, 1 / batch), the "first" and "more" graphs end with the clipped sum going into the root's
 accumulator and hold no optimizer step (they advance no step count), the "last" graph holds the noise node and the
 optimizer step.  Two graphs per engine for two passes, three for more.  A ragged final pass runs eagerly under the size
 rule above, between replayed ones: the accumulator is a plain buffer.
@@ -43,6 +44,7 @@ import torch
 
 from . import _lib
 from ._lib import call, query
+from .step import eager_step
 
 _dp_warned = False
 
@@ -62,22 +64,7 @@ def eager_reason(engine, optimizer, batch_size):
     return None
 
 
-def _phase(eng):
-    """The micro-batch phase the step helper (dp_micro.step) has set on the root engine, or None."""
-    return getattr(getattr(eng, "_root", eng), "dp_phase", None)
-
-
-def _eager(engine, eng, optimizer, data, target, soft):
-    """The loops' step as it is without --hip_graph."""
-    optimizer.zero_grad()
-    eng.forward(data)
-    loss = eng.loss_backward(target, soft=soft)
-    if _phase(eng) in (None, "last"):       # (an accumulating micro-batch pass takes no optimizer step)
-        optimizer.step() if eng is engine else optimizer.step(eng)
-    return loss
-
-
-def _key(eng, optimizer, soft):
+def _key(eng, optimizer, soft, phase=None, logical_batch=None):
     key = (eng.N, bool(soft), optimizer.kind, bool(eng.fuse_sgd_tail), eng.class_weight is not None)
     if eng.norm == "frozen":        # (a frozen-statistics step launches other kernels than a GroupNorm one)
         key += ("frozen BatchNorm",)
@@ -90,26 +77,24 @@ def _key(eng, optimizer, soft):
         if dp.get("expected_batch") is not None:
             # padded fixed-capacity batches (dp_sampling.PoissonLoader): other loss and clip kernels, 1 / L in the noise node
             key += ("Poisson-sampled", float(dp["expected_batch"]))
-        phase = getattr(root, "dp_phase", None)
         if phase is not None:
             # a pass of a step cut into micro-batches: other tail kernels per phase, 1 / batch in the last one's noise node
-            inv = 1.0 / float(dp["expected_batch"] if dp.get("expected_batch") is not None else root.dp_logical_batch)
+            inv = 1.0 / float(dp["expected_batch"] if dp.get("expected_batch") is not None else logical_batch)
             key += ("micro-batch", phase, inv)
         clip = getattr(root, "dp_clip", None)
         if clip is not None:
             # an adaptive clipping norm (dp_clip.AdaptiveClip): its PARAMETERS are launch arguments of the update and noise
             # nodes; the value of C is a device word the nodes read, so C moving never captures again
-            key += ("adaptive clip",) + clip.key(float(dp.get("noise_multiplier", 1.3)), _divisor(eng, dp))
+            key += ("adaptive clip",) + clip.key(float(dp.get("noise_multiplier", 1.3)), _divisor(eng, dp, phase, logical_batch))
     return key
 
 
-def _divisor(eng, dp):
+def _divisor(eng, dp, phase=None, logical_batch=None):
     """B, what a DP-SGD step of `eng` divides its noised sum by (dp_loss_backward's rule)."""
-    root = eng._root
     if dp.get("expected_batch") is not None:
         return float(dp["expected_batch"])
-    if getattr(root, "dp_phase", None) is not None:
-        return int(root.dp_logical_batch)
+    if phase is not None:
+        return int(logical_batch)
     return eng.N
 
 
@@ -155,7 +140,7 @@ def _fingerprint(eng, g):
 class _StepGraph:
     """One captured training step of one engine and key."""
 
-    def __init__(self, eng, optimizer, soft, data, target):
+    def __init__(self, eng, optimizer, soft, data, target, phase=None, logical_batch=None):
         root = eng._root
         self.kind, self.soft = optimizer.kind, bool(soft)      # (no reference to the engine: it owns this object)
         self.x = torch.empty_like(data, memory_format=torch.contiguous_format)
@@ -165,8 +150,9 @@ class _StepGraph:
             _sync_moments(root)
         if getattr(root, "dp_noise", None) is not None:
             root.dp_noise.counter       # exists BEFORE the capture: allocated inside, every replay would zero it again
-        phase = _phase(eng)
+        step_kw = {}
         if phase is not None:
+            step_kw = {"phase": phase, "logical_batch": logical_batch}
             eng.dp_acc                  # likewise: the passes of a step hand their sums on through it
         clip = getattr(root, "dp_clip", None)
         if clip is not None:
@@ -187,7 +173,7 @@ class _StepGraph:
             # thread_local: another thread of the process (a process group's watchdog) may touch the runtime meanwhile
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
                 eng.forward(self.x)
-                eng.loss_backward(self.target, soft=self.soft)
+                eng.loss_backward(self.target, soft=self.soft, **step_kw)
                 if phase in (None, "last"):
                     optimizer.step(eng, hyper=self.hyper)
         finally:
@@ -226,27 +212,28 @@ class _StepGraph:
         return eng.loss
 
 
-def graphed_step(engine, optimizer, data, target, soft=False):
+def graphed_step(engine, optimizer, data, target, soft=False, phase=None, logical_batch=None):
     """One training step of `engine` (the loop's model: its sibling of data's batch size runs it) with `optimizer`
     (primia_amd.optim.EngineOptimizer), as a replayed hipGraph where it can be (see the module docstring), eagerly
-    otherwise.  Returns the engine's device loss scalar; the next step overwrites it, so keep a `.clone()`."""
+    (step.eager_step) otherwise.  `phase`, `logical_batch`: a pass of a DP-SGD step cut into micro-batches (dp_micro).
+    Returns the engine's device loss scalar; the next step overwrites it, so keep a `.clone()`."""
     global _dp_warned
     n = int(data.shape[0])
-    eng = engine if n == engine.N else engine.sibling(n)
     reason = eager_reason(engine, optimizer, n)
     if reason is not None:
         if reason.startswith("DP-SGD") and not _dp_warned:
             _dp_warned = True
             warnings.warn("hip_graph: " + reason, RuntimeWarning, stacklevel=2)
-        return _eager(engine, eng, optimizer, data, target, soft)
-    key = _key(eng, optimizer, soft)
+        return eager_step(engine, optimizer, data, target, soft, phase, logical_batch)
+    eng = engine if n == engine.N else engine.sibling(n)
+    key = _key(eng, optimizer, soft, phase, logical_batch)
     graphs = eng.__dict__.setdefault("_step_graphs", {})
     g = graphs.get(key)
     if g is None:
         warm = eng.__dict__.setdefault("_step_graphs_warm", set())
         if key not in warm:
             warm.add(key)
-            return _eager(engine, eng, optimizer, data, target, soft)
+            return eager_step(engine, optimizer, data, target, soft, phase, logical_batch)
     if query("primia_options_epoch") != eng._options_epoch:
         raise _lib.PrimiaError("library options changed (primia_set_option) after this engine sized its buffers: "
                                "set options first, then construct the engine")
@@ -260,7 +247,7 @@ def graphed_step(engine, optimizer, data, target, soft=False):
             del graphs[key]
             g = None
     if g is None:
-        g = graphs[key] = _StepGraph(eng, optimizer, soft, data, target)
+        g = graphs[key] = _StepGraph(eng, optimizer, soft, data, target, phase, logical_batch)
         g.captures += earlier
     return g.replay(eng, optimizer, data, target)
 

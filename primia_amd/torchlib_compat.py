@@ -8,6 +8,8 @@ from typing import Optional
 
 import numpy as np
 
+from .step import train_step
+
 
 class LearningRateScheduler:
     """Epoch -> learning rate on a log10 scale (torchlib/utils.py:37-89).
@@ -289,8 +291,6 @@ def secure_aggregation_epoch(args, models, device, train_loaders, optimizers, ep
         optimizers[w] = (EngineOptimizer.from_args(models[w], args) if not args.keep_optim_dict
                          else _as_optimizer(models[w], optimizers[w], args))
     hip_graph = getattr(args, "hip_graph", False)
-    if hip_graph:
-        from .graphed_train import graphed_step
     avg_loss = []
     num_batches = {wid(w): len(tl) for w, tl in train_loaders.items()}
     loaders = {w: iter(tl) for w, tl in train_loaders.items()}
@@ -300,26 +300,11 @@ def secure_aggregation_epoch(args, models, device, train_loaders, optimizers, ep
             i = wid(w)
             if batch_idx >= num_batches[i]:
                 continue
-            optimizers[i].zero_grad()
             data, target = next(it)
             soft = getattr(loss_fns.get(i), "soft", False) if loss_fns else False
-            if getattr(models[i], "dp_micro_batches", 1) > 1:
-                # the loader's batch is ONE logical DP-SGD step, run as passes of the engine's size (dp_micro)
-                from . import dp_micro
-
-                loss = dp_micro.step(models[i], optimizers[i], data, target, hip_graph=hip_graph)
-                avg_loss.append(loss.clone() if hip_graph else loss.item())
-                continue
-            if hip_graph:
-                # the device loss stays on the device until the epoch ends (no wait on the GPU per step)
-                avg_loss.append(graphed_step(models[i], optimizers[i], data, target, soft=soft).clone())
-                continue
-            sib = getattr(models[i], "sibling", None)    # (the ragged final batch of a client's loader)
-            eng = models[i] if sib is None else sib(data.shape[0])
-            eng.forward(data)
-            loss = eng.loss_backward(target, soft=soft)
-            optimizers[i].step() if eng is models[i] else optimizers[i].step(eng)
-            avg_loss.append(loss.item())
+            loss = train_step(models[i], optimizers[i], data, target, soft=soft, hip_graph=hip_graph)
+            # under hip_graph the device loss stays on the device until the epoch ends (no wait on the GPU per step)
+            avg_loss.append(loss.clone() if hip_graph else loss.item())
         if batch_idx > 0 and batch_idx % args.sync_every_n_batch == 0:
             models["local_model"] = aggregation(models["local_model"], models, train_loaders.keys(), crypto_provider,
                                                 args, test_params, weights=weights, secure=secure)
@@ -370,21 +355,7 @@ def train(args, model, device, train_loader, optimizer, epoch, loss_fn, num_clas
             soft = True
         # MixUp mixes the two halves of a batch with probability mixup_prob and passes it on whole otherwise: consecutive
         # steps see B or B / 2 samples (:1262-1267).  A sibling engine serves the other size on the same parameters.
-        if getattr(model, "dp_micro_batches", 1) > 1:
-            # the loader's batch is ONE logical DP-SGD step, run as passes of the engine's size (dp_micro)
-            from . import dp_micro
-
-            loss = dp_micro.step(model, optimizer, data, target, hip_graph=getattr(args, "hip_graph", False))
-        elif getattr(args, "hip_graph", False):
-            from .graphed_train import graphed_step
-
-            loss = graphed_step(model, optimizer, data, target, soft=soft)
-        else:
-            eng = model if data.shape[0] == getattr(model, "N", data.shape[0]) else model.sibling(data.shape[0])
-            optimizer.zero_grad()
-            eng.forward(data)
-            loss = eng.loss_backward(target, soft=soft)
-            optimizer.step() if eng is model else optimizer.step(eng)
+        loss = train_step(model, optimizer, data, target, soft=soft, hip_graph=getattr(args, "hip_graph", False))
         if batch_idx % args.log_interval == 0:
             losses.append(loss.item())
             if verbose:

@@ -192,13 +192,13 @@ def cmd(**kw):
 def test_adaptive_clip_without_dp_warns_and_does_nothing():
     plain = SimpleNamespace(differentially_private=False, batch_size=8)
     with pytest.warns(UserWarning, match="--dp_clip adaptive has no effect"):
-        assert train.adaptive_clip_mode(plain, cmd(dp_clip_sigma=0.1), 1.3) is None        # (not even the bound is looked at)
+        assert train.DPOptions.from_args(plain, cmd(dp_clip_sigma=0.1)).clip is None        # (not even the bound is looked at)
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        assert train.adaptive_clip_mode(plain, cmd(dp_clip="fixed"), 1.3) is None
-        assert train.adaptive_clip_mode(plain, SimpleNamespace(), 1.3) is None
-        assert train.adaptive_clip_mode(SimpleNamespace(differentially_private=True, batch_size=8), None, 1.3) is None
-        got = train.adaptive_clip_mode(SimpleNamespace(differentially_private=True, batch_size=256), cmd(), 1.3)
+        assert train.DPOptions.from_args(plain, cmd(dp_clip="fixed")).clip is None
+        assert train.DPOptions.from_args(plain, SimpleNamespace()).clip is None
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=True, batch_size=8), None).clip is None
+        got = train.DPOptions.from_args(SimpleNamespace(differentially_private=True, batch_size=256), cmd()).clip
     assert got == dict(init=1.0, quantile=0.5, lr=0.2, sigma_b=12.8, z_delta=dp_clip.z_delta(1.3, 12.8))
 
 
@@ -206,15 +206,15 @@ def test_a_count_noise_at_or_below_half_the_multiplier_ends_the_run():
     dp = SimpleNamespace(differentially_private=True, batch_size=256)
     for sigma in (0.65, 0.5, 0.0, -1.0):
         with pytest.raises(SystemExit, match=r"--dp_clip_sigma = .* must exceed half the noise multiplier, 1\.3 / 2 = 0\.65"):
-            train.adaptive_clip_mode(dp, cmd(dp_clip_sigma=sigma), 1.3)
-    assert train.adaptive_clip_mode(dp, cmd(dp_clip_sigma=0.66), 1.3)["sigma_b"] == 0.66
+            train.DPOptions.from_args(dp, cmd(dp_clip_sigma=sigma)).clip
+    assert train.DPOptions.from_args(dp, cmd(dp_clip_sigma=0.66)).clip["sigma_b"] == 0.66
     # the default batch_size / 20: batches under 14 fall at or below the bound
     for batch in (13, 8, 1):
         with pytest.raises(SystemExit, match=r"batch_size / 20 = .* 1\.3 / 2 = 0\.65"):
-            train.adaptive_clip_mode(SimpleNamespace(differentially_private=True, batch_size=batch), cmd(), 1.3)
-    assert train.adaptive_clip_mode(SimpleNamespace(differentially_private=True, batch_size=14), cmd(), 1.3)["sigma_b"] == 0.7
+            train.DPOptions.from_args(SimpleNamespace(differentially_private=True, batch_size=batch), cmd()).clip
+    assert train.DPOptions.from_args(SimpleNamespace(differentially_private=True, batch_size=14), cmd()).clip["sigma_b"] == 0.7
     with pytest.raises(SystemExit, match="quantile"):
-        train.adaptive_clip_mode(dp, cmd(dp_clip_quantile=1.0), 1.3)
+        train.DPOptions.from_args(dp, cmd(dp_clip_quantile=1.0)).clip
 
 
 def test_a_checkpoint_without_the_entry_warns():
@@ -254,7 +254,6 @@ def test_the_graph_key_holds_the_parameters_and_never_c():
     # the default count noise follows the step's divisor: N, the logical batch of a micro-batch pass, the expected batch
     eng.dp_clip = dp_clip.AdaptiveClip("cpu")
     assert graphed_train._key(eng, _Opt(), False)[-4] == 32 / 20
-    eng.dp_phase, eng.dp_logical_batch = "first", 64
-    assert graphed_train._key(eng, _Opt(), False)[-4] == 64 / 20
+    assert graphed_train._key(eng, _Opt(), False, phase="first", logical_batch=64)[-4] == 64 / 20
     eng.dp_params["expected_batch"] = 48.0
-    assert graphed_train._key(eng, _Opt(), False)[-4] == 48.0 / 20
+    assert graphed_train._key(eng, _Opt(), False, phase="first", logical_batch=64)[-4] == 48.0 / 20

@@ -24,13 +24,14 @@ def test_parser_default_and_refusal():
 def test_micro_batches_without_dp_warn_and_do_nothing():
     cmd = SimpleNamespace(dp_micro_batches=4)
     with pytest.warns(UserWarning, match="--dp_micro_batches 4 has no effect"):
-        assert train.micro_batch_mode(SimpleNamespace(differentially_private=False), cmd) == 1
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=False), cmd).micro == 1
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        assert train.micro_batch_mode(SimpleNamespace(differentially_private=True), cmd) == 4
-        assert train.micro_batch_mode(SimpleNamespace(differentially_private=False), SimpleNamespace()) == 1
-        assert train.micro_batch_mode(SimpleNamespace(differentially_private=False), SimpleNamespace(dp_micro_batches=1)) == 1
-        assert train.micro_batch_mode(SimpleNamespace(differentially_private=True), None) == 1
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=True), cmd).micro == 4
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=False), SimpleNamespace()).micro == 1
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=False),
+                                         SimpleNamespace(dp_micro_batches=1)).micro == 1
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=True), None).micro == 1
 
 
 def test_the_size_of_a_pass():
@@ -110,11 +111,8 @@ def test_the_key_without_a_phase_is_the_key_as_it_was():
     want = (4, False, "SGD", True, False, "DP with device noise", 1.0, 1.3, eng.dp_noise.key_words + (eng.dp_noise.nonce,),
             "Poisson-sampled", 6.0)
     assert graphed_train._key(eng, _Opt(), False) == want
-    eng.dp_phase = None
-    assert graphed_train._key(eng, _Opt(), False) == want
-    eng.dp_phase, eng.dp_logical_batch = "first", 8
-    assert graphed_train._key(eng, _Opt(), False) == want + ("micro-batch", "first", 1.0 / 6.0)
+    assert graphed_train._key(eng, _Opt(), False, phase=None, logical_batch=None) == want
+    assert graphed_train._key(eng, _Opt(), False, phase="first", logical_batch=8) == want + ("micro-batch", "first", 1.0 / 6.0)
     del eng.dp_params["expected_batch"]
-    eng.dp_phase = "last"
-    assert graphed_train._key(eng, _Opt(), False) == want[:-2] + ("micro-batch", "last", 1.0 / 8.0)
+    assert graphed_train._key(eng, _Opt(), False, phase="last", logical_batch=8) == want[:-2] + ("micro-batch", "last", 1.0 / 8.0)
     assert graphed_train.eager_reason(eng, _Opt(), 4) is None and "batch size 3" in graphed_train.eager_reason(eng, _Opt(), 3)

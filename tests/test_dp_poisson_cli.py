@@ -22,13 +22,14 @@ def test_parser_defaults():
 def test_poisson_without_dp_warns_and_does_nothing():
     cmd = SimpleNamespace(dp_sampling="poisson")
     with pytest.warns(UserWarning, match="--dp_sampling poisson has no effect"):
-        assert train.poisson_mode(SimpleNamespace(differentially_private=False), cmd) is False
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=False), cmd).poisson is False
     with warnings.catch_warnings():
         warnings.simplefilter("error")
-        assert train.poisson_mode(SimpleNamespace(differentially_private=True), cmd) is True
-        assert train.poisson_mode(SimpleNamespace(differentially_private=True), SimpleNamespace(dp_sampling="shuffle")) is False
-        assert train.poisson_mode(SimpleNamespace(differentially_private=False), SimpleNamespace()) is False
-        assert train.poisson_mode(SimpleNamespace(differentially_private=True), None) is False
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=True), cmd).poisson is True
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=True),
+                                         SimpleNamespace(dp_sampling="shuffle")).poisson is False
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=False), SimpleNamespace()).poisson is False
+        assert train.DPOptions.from_args(SimpleNamespace(differentially_private=True), None).poisson is False
 
 
 @pytest.mark.parametrize("n", [8, 7, 1])

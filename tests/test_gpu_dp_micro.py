@@ -157,7 +157,8 @@ def test_split_step_against_the_whole_one_and_the_oracle(cuda, norm, monkeypatch
         del stats[:]
         before = split.opt_steps
         loss = dp_micro.step(split, opt, x[:count].to(cuda), y[:count].to(cuda))
-        assert split.opt_steps == before + 1 and split.dp_phase is None and split.dp_logical_batch is None
+        assert split.opt_steps == before + 1
+        assert not hasattr(split, "dp_phase") and not hasattr(split, "dp_logical_batch")
         assert len(stats) == 2 and math.isfinite(float(loss))
         held_to_the_oracle(split, count)
         if count == 8:

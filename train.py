@@ -43,10 +43,11 @@ import os
 import random
 import shutil
 import sys
+from dataclasses import dataclass
 from os import path
-from warnings import warn
-
 from types import SimpleNamespace
+from typing import Optional
+from warnings import warn
 
 import numpy as np
 import torch
@@ -219,26 +220,76 @@ def resume(cmd_args, args, model, optimizer, worker_names, state=None):
     return state["epoch"]
 
 
-def poisson_mode(args, cmd_args):
-    """Whether this run samples its batches by Poisson sampling: --dp_sampling poisson with differentially_private = yes
-    (without it the flag warns and does nothing, like --dp_noise chacha and --dp_norm frozen)."""
-    kind = getattr(cmd_args, "dp_sampling", "shuffle") if cmd_args is not None else "shuffle"
-    if kind == "poisson" and not args.differentially_private:
-        warn("--dp_sampling poisson has no effect: the config has differentially_private = no, batches are shuffled "
-             "as usual and no (epsilon, delta) is reported")
-    return kind == "poisson" and bool(args.differentially_private)
+@dataclass(frozen=True)
+class DPOptions:
+    """What the command line and the config ask of DP-SGD, read once (`from_args`) at the top of main.  Without
+    differentially_private = yes every --dp_* flag warns and does nothing."""
+    on: bool = False                # differentially_private = yes
+    noise: str = "torch"            # --dp_noise
+    noise_seed: Optional[int] = None    # --debug_dp_noise_seed
+    norm: str = "group"             # --dp_norm
+    poisson: bool = False           # --dp_sampling poisson: batches are Poisson-sampled and an (epsilon, delta) is reported
+    delta: float = 1e-5             # --dp_delta
+    # K of --dp_micro_batches: every loader batch is one logical DP-SGD step run as K passes of an engine of 1 / K of its
+    # size (primia_amd.dp_micro; plain gradient accumulation would change BatchNorm's statistics)
+    micro: int = 1
+    sigma: float = 1.3              # the noise multiplier: what every engine applies and every ledger is given
+    # --dp_clip adaptive: the AdaptiveClip parameters and z_delta, or None for the fixed C = 1.  The count's noise is
+    # --dp_clip_sigma or batch_size / 20 — the step's divisor B in shuffle and in Poisson mode alike, and a loader's ragged
+    # last batch keeps it — and must exceed sigma / 2, else the run ends in from_args
+    clip: Optional[dict] = None
 
+    @classmethod
+    def from_args(cls, args, cmd_args):
+        """`cmd_args`: the parsed command line, a namespace that lacks some flags, or None (main() called from a study)."""
+        def flag(name, default):
+            return getattr(cmd_args, name, default)
 
-def micro_batch_mode(args, cmd_args):
-    """K of --dp_micro_batches: every loader batch is one logical DP-SGD step run as K passes of an engine of 1 / K of its
-    size (primia_amd.dp_micro).  1 without differentially_private = yes, where the flag warns and does nothing like the
-    other --dp_* flags (plain gradient accumulation would change BatchNorm's statistics)."""
-    k = int(getattr(cmd_args, "dp_micro_batches", 1)) if cmd_args is not None else 1
-    if k > 1 and not args.differentially_private:
-        warn("--dp_micro_batches {:d} has no effect: the config has differentially_private = no, every batch is one "
-             "pass".format(k))
-        return 1
-    return max(1, k)
+        on = bool(args.differentially_private)
+        sigma = cls.sigma       # (the field's default: the one place the number lives)
+
+        def no_effect(text, consequence):
+            warn("{:s} has no effect: the config has differentially_private = no, {:s}".format(text, consequence))
+
+        noise, norm, sampling = flag("dp_noise", "torch"), flag("dp_norm", "group"), flag("dp_sampling", "shuffle")
+        micro, adaptive = max(1, int(flag("dp_micro_batches", 1))), flag("dp_clip", "fixed") == "adaptive"
+        if not on:
+            if noise == "chacha":
+                no_effect("--dp_noise chacha", "no noise is applied")
+            if norm == "frozen":
+                no_effect("--dp_norm frozen", "BatchNorm trains as usual")
+            if sampling == "poisson":
+                no_effect("--dp_sampling poisson", "batches are shuffled as usual and no (epsilon, delta) is reported")
+            if micro > 1:
+                no_effect("--dp_micro_batches {:d}".format(micro), "every batch is one pass")
+            if adaptive:
+                no_effect("--dp_clip adaptive", "no gradient is clipped")
+        elif norm == "frozen" and not args.pretrained:
+            warn("--dp_norm frozen without pretrained = yes: the frozen statistics are the initial mean 0 / variance 1, every "
+                 "norm layer is a learned per-channel affine map")
+        clip = None
+        if on and adaptive:
+            from primia_amd import dp_clip
+
+            given = flag("dp_clip_sigma", None)
+            sigma_b = float(given) if given is not None else args.batch_size / 20.0
+            try:
+                z_delta = dp_clip.z_delta(sigma, sigma_b)
+            except ValueError:
+                raise SystemExit("--dp_clip adaptive: the count's noise {:s} = {:g} must exceed half the noise multiplier, "
+                                 "{:g} / 2 = {:g}: below that bound no gradient noise can pay for the count's release".format(
+                                     "--dp_clip_sigma" if given is not None else "batch_size / 20", sigma_b, sigma,
+                                     sigma / 2.0))
+            params = {"init": float(flag("dp_clip_init", 1.0)), "quantile": float(flag("dp_clip_quantile", 0.5)),
+                      "lr": float(flag("dp_clip_lr", 0.2)), "sigma_b": sigma_b}
+            try:
+                dp_clip.AdaptiveClip("cpu", **params)       # (refuses a quantile outside (0, 1), a negative rate, an init out of range)
+            except ValueError as e:
+                raise SystemExit("--dp_clip adaptive: {:s}".format(str(e)))
+            clip = dict(params, z_delta=z_delta)
+        return cls(on=on, noise=noise, noise_seed=flag("debug_dp_noise_seed", None), norm=norm,
+                   poisson=on and sampling == "poisson", delta=float(flag("dp_delta", 1e-5)), micro=micro if on else 1,
+                   sigma=sigma, clip=clip)
 
 
 def micro_batch_size(slots, k, poisson):
@@ -250,36 +301,6 @@ def micro_batch_size(slots, k, poisson):
         raise SystemExit("--dp_micro_batches {:d} does not divide batch_size {:d}: the passes of a shuffled batch are all "
                          "the same size".format(int(k), int(slots)))
     return int(slots) // int(k)
-
-
-def adaptive_clip_mode(args, cmd_args, sigma):
-    """The AdaptiveClip parameters of --dp_clip adaptive with differentially_private = yes (without it the flag warns and
-    does nothing, like the other --dp_* flags), or None for the fixed C = 1.  The count's noise is --dp_clip_sigma or
-    batch_size / 20 — the step's divisor B in shuffle and in Poisson mode alike, and a loader's ragged last batch keeps
-    it — and must exceed sigma / 2 (sigma: the configured noise multiplier), else the run ends here."""
-    kind = getattr(cmd_args, "dp_clip", "fixed") if cmd_args is not None else "fixed"
-    if kind != "adaptive":
-        return None
-    if not args.differentially_private:
-        warn("--dp_clip adaptive has no effect: the config has differentially_private = no, no gradient is clipped")
-        return None
-    from primia_amd import dp_clip
-
-    given = getattr(cmd_args, "dp_clip_sigma", None)
-    sigma_b = float(given) if given is not None else args.batch_size / 20.0
-    try:
-        z_delta = dp_clip.z_delta(sigma, sigma_b)
-    except ValueError:
-        raise SystemExit("--dp_clip adaptive: the count's noise {:s} = {:g} must exceed half the noise multiplier, "
-                         "{:g} / 2 = {:g}: below that bound no gradient noise can pay for the count's release".format(
-                             "--dp_clip_sigma" if given is not None else "batch_size / 20", sigma_b, sigma, sigma / 2.0))
-    params = {"init": float(getattr(cmd_args, "dp_clip_init", 1.0)), "quantile": float(getattr(cmd_args, "dp_clip_quantile", 0.5)),
-              "lr": float(getattr(cmd_args, "dp_clip_lr", 0.2)), "sigma_b": sigma_b}
-    try:
-        dp_clip.AdaptiveClip("cpu", **params)       # (refuses a quantile outside (0, 1), a negative rate, an init out of range)
-    except ValueError as e:
-        raise SystemExit("--dp_clip adaptive: {:s}".format(str(e)))
-    return dict(params, z_delta=z_delta)
 
 
 def saved_clip(state):
@@ -351,34 +372,17 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                 args.data_dir))
         from primia_amd import imagefolder
 
-    dp_noise_kind = getattr(cmd_args, "dp_noise", "torch") if cmd_args is not None else "torch"
-    dp_noise_seed = getattr(cmd_args, "debug_dp_noise_seed", None) if cmd_args is not None else None
-
-    if dp_noise_kind == "chacha" and not args.differentially_private:
-        warn("--dp_noise chacha has no effect: the config has differentially_private = no, no noise is applied")
-
-    dp_norm = getattr(cmd_args, "dp_norm", "group") if cmd_args is not None else "group"
-    if dp_norm == "frozen" and not args.differentially_private:
-        warn("--dp_norm frozen has no effect: the config has differentially_private = no, BatchNorm trains as usual")
-    elif dp_norm == "frozen" and not args.pretrained:
-        warn("--dp_norm frozen without pretrained = yes: the frozen statistics are the initial mean 0 / variance 1, every "
-             "norm layer is a learned per-channel affine map")
-
-    dp_delta = float(getattr(cmd_args, "dp_delta", 1e-5)) if cmd_args is not None else 1e-5
-    poisson = poisson_mode(args, cmd_args)
-    micro = micro_batch_mode(args, cmd_args)
-    if micro > 1 and not poisson:       # (refused before any data is registered; a Poisson capacity is rounded up)
-        m = micro_batch_size(args.batch_size, micro, False)
+    dp = DPOptions.from_args(args, cmd_args)
+    if dp.micro > 1 and not dp.poisson:     # (refused before any data is registered; a Poisson capacity is rounded up)
+        m = micro_batch_size(args.batch_size, dp.micro, False)
         if rank == 0:
             print("dp_micro_batches: every step of {:d} samples runs as K = {:d} passes on an engine of M = {:d} "
-                  "slots".format(args.batch_size, micro, m))
-    dp_sigma = 1.3
-    # --dp_clip adaptive: the ledger keeps receiving dp_sigma — the count's release is paid for by the gradient's noise
-    clip_params = adaptive_clip_mode(args, cmd_args, dp_sigma)
-    if clip_params is not None and rank == 0:
+                  "slots".format(args.batch_size, dp.micro, m))
+    # --dp_clip adaptive: the ledger keeps receiving dp.sigma — the count's release is paid for by the gradient's noise
+    if dp.clip is not None and rank == 0:
         print("dp_clip: adaptive clipping norm from C = {init:g}, target quantile {quantile:g}, rate {lr:g}, count noise "
-              "{sigma_b:g}; gradient noise {z_delta:.4f} * C for a mechanism of multiplier {z:g}".format(z=dp_sigma,
-                                                                                                       **clip_params))
+              "{sigma_b:g}; gradient noise {z_delta:.4f} * C for a mechanism of multiplier {z:g}".format(z=dp.sigma,
+                                                                                                       **dp.clip))
     clips = {}          # {client name: dp_clip.AdaptiveClip} of the engines that take steps
     privacy = {}        # Poisson sampling: {client name: dp_accountant.Ledger}
     # a resumed Poisson run sizes every client's capacity from what the checkpoint's ledger has spent plus the epochs
@@ -386,7 +390,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
     resume_state, spent, epochs_ahead = None, {}, args.epochs
     if cmd_args is not None and getattr(cmd_args, "resume_checkpoint", None):
         resume_state = torch.load(cmd_args.resume_checkpoint, map_location="cpu", weights_only=False)
-        if poisson:
+        if dp.poisson:
             spent = saved_privacy(resume_state)
             epochs_ahead = max(0, args.epochs - int(resume_state["epoch"]) + 1)      # (the saved epoch is run again)
     reps = args.repetitions_dataset if "repetitions_dataset" in vars(args) else 1
@@ -405,17 +409,17 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         if old is not None and old.n != n:
             warn("{:s}: the checkpoint counted {:d} records, this run has {:d}; its segments are kept as they are".format(
                 name, old.n, n))
-        _, planned, capacity = poisson_plan(name, n, args.batch_size, epochs_ahead, dp_delta, dp_sigma, spent=old)
+        _, planned, capacity = poisson_plan(name, n, args.batch_size, epochs_ahead, dp.delta, dp.sigma, spent=old)
         nonce = client if client is not None else 0
-        sampler = dps.DeviceSampler(device, nonce=nonce, debug_seed=dp_noise_seed)
-        led = privacy[name] = dp_accountant.Ledger(n, capacity, dp_delta, planned)
+        sampler = dps.DeviceSampler(device, nonce=nonce, debug_seed=dp.noise_seed)
+        led = privacy[name] = dp_accountant.Ledger(n, capacity, dp.delta, planned)
         if old is not None:     # the ledger goes on counting; a changed q, sigma or capacity opens a new segment
             led.segments, led.capacities, led.overflow_events = old.segments, old.capacities, old.overflow_events
-        if micro > 1 and rank == 0:
+        if dp.micro > 1 and rank == 0:
             print("dp_micro_batches: {:s}'s steps of capacity {:d} run as K = {:d} passes on an engine of M = {:d} "
-                  "slots".format(name, capacity, micro, micro_batch_size(capacity, micro, True)))
+                  "slots".format(name, capacity, dp.micro, micro_batch_size(capacity, dp.micro, True)))
         return dps.from_loader(base, args.batch_size, capacity, sampler, fed_reps, (channels, size, size),
-                               micro_batches=micro)
+                               micro_batches=dp.micro)
 
     def synthetic_records(batches, seed):
         sl = SyntheticLoader(batches, args.batch_size, size, num_classes, device, seed, channels)
@@ -428,32 +432,32 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         # PrivacyEngine, so the network is built with GroupNorm — or (--dp_norm frozen) BatchNorm is applied with its
         # running statistics held fixed, which keeps samples independent too — and every step clips / noises per sample
         # (--dp_micro_batches K: the engine holds one PASS, 1 / K of the loaders' batch or capacity)
-        slots = micro_batch_size(args.batch_size if batch is None else batch, micro, poisson)
+        slots = micro_batch_size(args.batch_size if batch is None else batch, dp.micro, dp.poisson)
         eng = ResNet18Engine(slots, num_classes, channels, size, args.pooling_type,
-                             dtype=dtype, device=device, norm=dp_norm if args.differentially_private else "batch")
-        if args.differentially_private:
-            eng.dp_micro_batches = micro
-            eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": dp_sigma}
+                             dtype=dtype, device=device, norm=dp.norm if dp.on else "batch")
+        if dp.on:
+            eng.dp_micro_batches = dp.micro
+            eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": dp.sigma}
             if expected_batch is not None:      # padded Poisson batches: masked loss / clip, the noised sum over q * n
                 eng.dp_params["expected_batch"] = float(expected_batch)
-            if dp_noise_kind == "chacha":
+            if dp.noise == "chacha":
                 # a key of its own from the OS entropy pool per engine; the nonce is the client index (the model that
                 # holds a federated run's aggregate never takes a step: it gets the last nonce; a vanilla run's one model
                 # has nonce 0 like federated client 0 — independent under OS keys, the SAME stream under a debug seed)
                 from primia_amd.dp_noise import DeviceNoise
 
                 nonce = client if client is not None else (2 ** 64 - 1 if args.train_federated else 0)
-                eng.dp_noise = DeviceNoise(device, nonce=nonce, debug_seed=dp_noise_seed)
-            if clip_params is not None and name is not None:
+                eng.dp_noise = DeviceNoise(device, nonce=nonce, debug_seed=dp.noise_seed)
+            if dp.clip is not None and name is not None:
                 # a state of its own per model that takes steps (FedAvg averages weights, never clipping norms)
                 from primia_amd.dp_clip import AdaptiveClip
 
-                eng.dp_clip = clips[name] = AdaptiveClip(device, **{k: v for k, v in clip_params.items() if k != "z_delta"})
+                eng.dp_clip = clips[name] = AdaptiveClip(device, **{k: v for k, v in dp.clip.items() if k != "z_delta"})
                 eng.dp_clip.tensors()       # on the device before any step graph is captured
         return eng
 
     vanilla_loader = None
-    if poisson and not args.train_federated:
+    if dp.poisson and not args.train_federated:
         # the engine's batch is the capacity, which follows from the record count: the loader comes first
         if synthetic:
             base = synthetic_records(max(2, n_batches), args.seed)
@@ -491,7 +495,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
 
         def client_data(w):
             i = workers.index(w)
-            if synthetic and poisson:
+            if synthetic and dp.poisson:
                 train_loader[w] = poisson_loader(w, synthetic_records(max(2, n_batches - i), args.seed + i), i)
                 stats[w] = (torch.zeros(channels, device=device), torch.ones(channels, device=device))
             elif synthetic:
@@ -502,18 +506,18 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             else:
                 train_loader[w], stats[w] = imagefolder.client_loader(
                     path.join(args.data_dir, "worker{:d}".format(i + 1)), args, device, channels, args.seed + i)
-                if poisson:
+                if dp.poisson:
                     train_loader[w] = poisson_loader(w, train_loader[w], i)
 
-        if poisson:     # the engine's batch is the capacity, which follows from the record count: the loaders come first
+        if dp.poisson:  # the engine's batch is the capacity, which follows from the record count: the loaders come first
             for w in mine:
                 client_data(w)
         for w in mine:
             tl = train_loader.get(w)
-            model[w] = make_engine(client=workers.index(w), batch=tl.capacity if poisson else None,
-                                   expected_batch=tl.expected_batch if poisson else None, name=w)
+            model[w] = make_engine(client=workers.index(w), batch=tl.capacity if dp.poisson else None,
+                                   expected_batch=tl.expected_batch if dp.poisson else None, name=w)
             model[w].load_state_dict(local.state_dict())
-        if not poisson:
+        if not dp.poisson:
             for w in mine:
                 client_data(w)
         # setup_pysyft's secure average of the clients' (mean, std) (utils.py:764-794) -> val_mean_std
@@ -598,21 +602,25 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
     overflow_before = {name: led.overflow_events for name, led in privacy.items()}
     counted = {name: 0 for name in privacy}
 
+    def all_ranks(states):
+        """{name: state} of every rank's clients, merged (this rank's own dict without torch.distributed.run)."""
+        if world == 1:
+            return states
+        import torch.distributed as dist
+
+        gathered = [None] * world
+        dist.all_gather_object(gathered, states)
+        return {k: v for g in gathered for k, v in g.items()}
+
     def account(final=False):
         """The steps this epoch sampled go into the ledgers; rank 0 prints every client's (epsilon, delta).  Returns the
         checkpoint's `dp_privacy` entry ({client: ledger state}; every rank's under torch.distributed.run)."""
         for name, led in privacy.items():
             tl = poisson_loaders[name]
-            led.add_steps(tl.q, dp_sigma, tl.draws - counted[name])
+            led.add_steps(tl.q, dp.sigma, tl.draws - counted[name])
             counted[name] = tl.draws
             led.overflow_events = overflow_before[name] + tl.sampler.overflow_events()
-        states = {name: led.state_dict() for name, led in privacy.items()}
-        if world > 1:
-            import torch.distributed as dist
-
-            gathered = [None] * world
-            dist.all_gather_object(gathered, states)
-            states = {k: v for g in gathered for k, v in g.items()}
+        states = all_ranks({name: led.state_dict() for name, led in privacy.items()})
         if rank == 0:
             from primia_amd.dp_accountant import Ledger
 
@@ -629,13 +637,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         """Rank 0 prints every client's C and last released fraction — functions of released values, unlike the raw
         counts, which never leave the device.  Returns the checkpoint's `dp_clip` entry ({client: state}; every rank's
         under torch.distributed.run)."""
-        states = {name: clip.state_dict() for name, clip in clips.items()}
-        if world > 1:
-            import torch.distributed as dist
-
-            gathered = [None] * world
-            dist.all_gather_object(gathered, states)
-            states = {k: v for g in gathered for k, v in g.items()}
+        states = all_ranks({name: clip.state_dict() for name, clip in clips.items()})
         if rank == 0:
             for name in sorted(states):
                 print("dp_clip: {:s}: C = {:.6g}, released fraction at or below C = {:.4f} (target {:g}), {:d} "
@@ -667,19 +669,14 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         else:
             model = train(args, model, device, train_loader, optimizer, epoch, loss_fn, num_classes, verbose=verbose)
             eval_model = model
-        dp_privacy = account() if poisson else None
-        ckpt_extra = {"dp_privacy": dp_privacy} if poisson else {}
-        if clip_params is not None:
+        ckpt_extra = {"dp_privacy": account()} if dp.poisson else {}
+        if dp.clip is not None:
             ckpt_extra["dp_clip"] = clip_report()
         if epoch % args.test_interval == 0:
-            opt_for_ckpt = optimizer
-            if world > 1:
-                # the checkpoint holds every worker's optimizer state (utils.py:1471-1472): collect them on rank 0
-                import torch.distributed as dist
-
-                gathered = [None] * world
-                dist.all_gather_object(gathered, (mine[0], optimizer[mine[0]].state_dict()))
-                opt_for_ckpt = dict(gathered)
+            # the checkpoint holds every worker's optimizer state (utils.py:1471-1472): collect them on rank 0.  (One process
+            # keeps handing save_model the optimizer OBJECTS, as before: not all_ranks' own world == 1 case, which would
+            # hand it state dicts.)
+            opt_for_ckpt = all_ranks({w: o.state_dict() for w, o in optimizer.items()}) if world > 1 else optimizer
             # rank 0 validates; what it decides (pruned / failed) reaches every rank BEFORE anybody moves on, so a
             # pruned trial or a validation error ends all ranks together instead of leaving them in a barrier until
             # the RCCL timeout.  The pruning check precedes the checkpoint, as train.py:505-517 of the reference.
@@ -713,7 +710,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                     except ImportError:
                         raise RuntimeError("trial pruned") from None
                 raise verdict[0]
-    if poisson:
+    if dp.poisson:
         account(final=True)
     best_score = 0.0
     if rank == 0 and objectives:
@@ -729,7 +726,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         if verbose:
             print("Highest matthews coefficient was {:.1f}% in epoch {:d}".format(
                 best_score, (best + 1) * args.test_interval * (reps if args.train_federated else 1)))
-    if args.hip_graph and args.differentially_private and dp_noise_kind == "chacha" and rank == 0:
+    if args.hip_graph and dp.on and dp.noise == "chacha" and rank == 0:
         from primia_amd.graphed_train import captures
 
         engines = [m for m in (model.values() if isinstance(model, dict) else [model]) if hasattr(m, "_root")]
