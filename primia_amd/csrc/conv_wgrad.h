@@ -30,6 +30,8 @@ struct WgradParams {
     float* ws;         // optional workspace of the store-and-reduce path (conv_wgrad_patch.hip); null: atomics
     size_t ws_bytes;
     int xpad;          // stem only: x is the padded NHWC4p input [N][H+6][W+8][4] (stem_conv.hip)
+    int rec_views;     // kWgPersampleSqnorm: images per RECORD (DP-SGD with augmentation multiplicity) — a split is a record
+                       // of rec_views consecutive images and sqnorm has N / rec_views entries; 1: a record is an image
 };
 
 // sum over the wave of the squares of `n` accumulator values per lane, added (fp64 atomic) to *dst
@@ -61,14 +63,15 @@ int wgrad_patch_group_dispatch(const WgradParams* p, int n, hipStream_t st);
 bool wgrad_tap_ok(const WgradParams& p);
 int wgrad_tap_dispatch(const WgradParams& p, hipStream_t st);
 size_t wgrad_tap_ws_bytes(const WgradParams& p);
-// ... and the DP-SGD norm pass of those layers (26): whole images per block, squared tile norms added to p.sqnorm
+// ... and the DP-SGD norm pass of those layers (26): whole images (whole records where p.rec_views > 1) per block,
+// squared tile norms added to p.sqnorm
 int wgrad_tap_persample_dispatch(const WgradParams& p, hipStream_t st);
 // conv1 + downsample of a transition block in one launch (the downsample = a tenth tap with its own dy)
 int wgrad_tap_pair_dispatch(const WgradParams& p, const WgradParams& p2, hipStream_t st);
 size_t wgrad_tap_pair_ws_bytes(const WgradParams& p, const WgradParams& p2);
 // stem (7x7/2) halo kernel on the padded input (stem_conv.hip)
 int stem_wgrad_halo_dispatch(const bf16* xp, const bf16* dy, float* dw, int N, int H, int W, hipStream_t st,
-                             float* ws = nullptr, size_t ws_bytes = 0, double* sqnorm = nullptr);
+                             float* ws = nullptr, size_t ws_bytes = 0, double* sqnorm = nullptr, int rec_views = 1);
 size_t stem_wgrad_halo_ws_bytes(int N, int H, int W);   // 0: shape not served by the halo kernel
 bool stem_wgrad_halo_blocks(int N, int H, int W, int* total, int* per_block, int* grid);
 // dw tile (kt, tap, ct) = sum over nsplit partial tiles of ws [combo][split][BMK*BNC], in split order

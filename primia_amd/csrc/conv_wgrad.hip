@@ -366,7 +366,7 @@ static void wgrad_geometry(WgradParams& p) {
     if (want < 1) want = 1;
     long pps = (p.Md + want - 1) / want;
     pps = (pps + KP - 1) / KP * KP;
-    if (wgrad_persample(p.form)) pps = (long)p.Ho * p.Wo;  // one split per image
+    if (wgrad_persample(p.form)) pps = (long)p.rec_views * p.Ho * p.Wo;  // one split per image (norm pass: per record)
     p.pix_per_split = pps;
     p.nsplit = (int)((p.Md + pps - 1) / pps);
     p.split_stride = wgrad_persample(p.form) ? (long)p.K * p.klen : 0;
@@ -413,6 +413,7 @@ static bool fill_wgrad_params(const primia_conv_desc* d, WgradParams& p, ConvGeo
     p.form = kWgAccumulate;
     p.split_stride = 0;
     p.xpad = 0;
+    p.rec_views = 1;
     p.sqnorm = nullptr;
     p.ws = nullptr; p.ws_bytes = 0;
     return true;
@@ -460,9 +461,10 @@ WgradRoute primia::wgrad_route(const WgradParams& p0, const ConvGeom& g, int dty
         const size_t n = !ws ? 0 : (dtype == PRIMIA_BF16 ? wgrad_generic_ws<bf16>(p, g) : wgrad_generic_ws<float>(p, g));
         return {g.stem ? 15 : 14, n};
     }
-    if (form == kWgPersampleSqnorm) {
+    if (form == kWgPersampleSqnorm && p.rec_views == 1) {
         // 7x7 outputs, 3x3: the norms come out of two Gram matrices per sample (dp_ghost.hip), the per-sample gradients are
-        // never formed
+        // never formed.  (Records of several images: the Gram matrices across a record's images do not fit the kernels'
+        // LDS plan — those shapes run on the patch kernel below, which served them before.)
         const int gh = dp_ghost_kernel_id(g.H, g.W, g.C, g.K, g.R, g.S, g.stride, g.pad);
         if (gh) return {gh, 0};
     }
@@ -478,11 +480,12 @@ WgradRoute primia::wgrad_route(const WgradParams& p0, const ConvGeom& g, int dty
 
 static int conv2d_wgrad_impl(const primia_conv_desc* d, const void* x, const void* dy, float* dw_acc, WgradForm form,
                              int dtype, primia_stream_t stream, double* sqnorm = nullptr, float* ws = nullptr,
-                             size_t ws_bytes = 0) {
+                             size_t ws_bytes = 0, int rec_views = 1) {
     PRIMIA_REQUIRE(d && x && dy && (dw_acc || sqnorm) && (dtype == PRIMIA_F32 || dtype == PRIMIA_BF16));
     ConvGeom g;
     WgradParams p;
     PRIMIA_REQUIRE(fill_wgrad_params(d, p, g));
+    p.rec_views = rec_views;
     WgradRoute r = wgrad_route(p, g, dtype, form);
     if (form == kWgWorkspace && !(ws && r.ws_bytes && ws_bytes >= r.ws_bytes)) {
         // without a (large enough) workspace the call is primia_conv2d_wgrad: accumulate into the zeroed dw
@@ -529,6 +532,16 @@ extern "C" int primia_stem_conv_wgrad_persample_sqnorm(const void* x_padded, con
     if (dtype != PRIMIA_BF16) return PRIMIA_ERR_UNSUPPORTED;
     return stem_wgrad_halo_dispatch((const bf16*)x_padded, (const bf16*)dy, nullptr, N, H, W, (hipStream_t)stream, nullptr,
                                     0, sqnorm);
+}
+
+// ... per record of `views` consecutive images: one block per record (see primia_conv2d_wgrad_record_sqnorm)
+extern "C" int primia_stem_conv_wgrad_record_sqnorm(const void* x_padded, const void* dy, double* sqnorm, int N, int H,
+                                                    int W, int views, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(x_padded && dy && sqnorm && N > 0 && H > 0 && W > 0 && views >= 1 && N % views == 0);
+    if (views == 1) return primia_stem_conv_wgrad_persample_sqnorm(x_padded, dy, sqnorm, N, H, W, dtype, stream);
+    if (dtype != PRIMIA_BF16) return PRIMIA_ERR_UNSUPPORTED;
+    return stem_wgrad_halo_dispatch((const bf16*)x_padded, (const bf16*)dy, nullptr, N, H, W, (hipStream_t)stream, nullptr,
+                                    0, sqnorm, views);
 }
 
 extern "C" int64_t primia_stem_conv_wgrad_ws_bytes(int N, int H, int W) {
@@ -691,11 +704,26 @@ extern "C" int primia_conv2d_wgrad_persample_sqnorm(const primia_conv_desc* d, c
     return conv2d_wgrad_impl(d, x, dy, nullptr, kWgPersampleSqnorm, dtype, stream, sqnorm);
 }
 
-static int wgrad_kernel_of(const primia_conv_desc* d, int dtype, WgradForm form) {
+// DP-SGD with augmentation multiplicity: the norm pass per RECORD of `views` consecutive images — the same kernels with
+// the tile completed over the record (wgrad_route takes the record size from p.rec_views)
+extern "C" int primia_conv2d_wgrad_record_sqnorm(const primia_conv_desc* d, const void* x, const void* dy, double* sqnorm,
+                                                 int views, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(d && sqnorm && views >= 1 && d->N > 0 && d->N % views == 0);
+    if (views == 1) return primia_conv2d_wgrad_persample_sqnorm(d, x, dy, sqnorm, dtype, stream);
+    return conv2d_wgrad_impl(d, x, dy, nullptr, kWgPersampleSqnorm, dtype, stream, sqnorm, nullptr, 0, views);
+}
+
+static int wgrad_kernel_of(const primia_conv_desc* d, int dtype, WgradForm form, int rec_views = 1) {
     ConvGeom g;
     WgradParams p;
     if (!fill_wgrad_params(d, p, g)) return PRIMIA_ERR_ARG;
+    p.rec_views = rec_views;
     return wgrad_route(p, g, dtype, form).kernel;
+}
+
+extern "C" int primia_conv_wgrad_record_kernel_id(const primia_conv_desc* d, int dtype, int views) {
+    if (!d || views < 1 || d->N <= 0 || d->N % views != 0) return PRIMIA_ERR_ARG;
+    return wgrad_kernel_of(d, dtype, kWgPersampleSqnorm, views);
 }
 
 extern "C" int primia_conv_wgrad_persample_kernel_id(const primia_conv_desc* d, int dtype) {
@@ -907,7 +935,7 @@ static bool wgrad_dma_geometry(WgradParams& p) {
     if (want < 1) want = 1;
     long pps = (p.Md + want - 1) / want;
     pps = (pps + KP - 1) / KP * KP;
-    if (wgrad_persample(p.form)) pps = (long)p.Ho * p.Wo;
+    if (wgrad_persample(p.form)) pps = (long)p.rec_views * p.Ho * p.Wo;
     p.pix_per_split = pps;
     p.nsplit = (int)((p.Md + pps - 1) / pps);
     p.split_stride = wgrad_persample(p.form) ? (long)p.K * p.klen : 0;

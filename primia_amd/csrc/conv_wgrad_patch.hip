@@ -57,6 +57,8 @@ struct PatchParams {
     float* ws;                // if set: every block stores its partial slab here (no atomics), see below
     int pairimg;              // v3, DP-SGD norm pass: a half owns whole images (units of t0 / per_block / total: images)
     int nimg;                 // batch size
+    int rec;                  // pairimg, template flag REC: images per record — a half owns whole RECORDS (units of t0 /
+                              // per_block / total: records), flushes after rec * PPI stages, sqnorm is indexed by record
     // v3, grouped launch: `ngroups` layers of ONE shape share the launch — blocks [g * group_blocks, (g + 1) * group_blocks)
     // work on layer g (x / dy of layers 1.. in xg / dyg; slabs of layer g behind those of layer g - 1)
     int ngroups, group_blocks;
@@ -259,8 +261,10 @@ __device__ unsigned long long* wgp33_prof_buffer_dev;
 // not the maximum of the two, because a blocked issue also holds the wave's own MFMAs behind it.  A third wave per SIMD does
 // not fit beside 144 accumulator registers — but ONE matrix wave per SIMD with nine independent accumulators keeps the matrix
 // pipe fed by itself, so the second wave of each SIMD can be a pure loader.  (DP-SGD's per-sample forms stay on the two-halves kernel.)
-template <int SW, int SH, int STAGES, bool LW = false>
+// REC (DP-SGD with augmentation multiplicity, pairimg only): the norm pass per record of p.rec consecutive images.
+template <int SW, int SH, int STAGES, bool LW = false, bool REC = false>
 __device__ __forceinline__ void patch33_body(const PatchParams& p, int bid_in) {
+    static_assert(!(LW && REC), "the record form is a norm pass: two halves");
     constexpr int FR = SW == 8 ? 2 : 1;         // rows of a k-step fragment
     constexpr int NK = SH / FR;                 // k-steps per sub-patch
     constexpr int HSX = SW == 8 ? 10 : 20;      // x row stride in slots
@@ -304,7 +308,8 @@ __device__ __forceinline__ void patch33_body(const PatchParams& p, int bid_in) {
     int t1 = t0 + p.per_block;
     if (t1 > p.total) t1 = p.total;
     // (pairimg: t0 / t1 count IMAGES; the two halves of a stage work on the same sub-patch position of two images)
-    const int nstages = p.pairimg ? ((t1 - t0 + 1) >> 1) * p.PPI : (t1 - t0 + 1) >> 1;
+    const int spu = REC ? p.PPI * p.rec : p.PPI;      // pairimg: stages of a half's unit (an image, or a record)
+    const int nstages = p.pairimg ? ((t1 - t0 + 1) >> 1) * spu : (t1 - t0 + 1) >> 1;
 
     const bf16* __restrict__ x = (gi == 0 ? p.x : p.xg[gi - 1]) + ct * 64;
     const bf16* __restrict__ dy = (gi == 0 ? p.dy : p.dyg[gi - 1]) + kt * 64;
@@ -373,6 +378,7 @@ __device__ __forceinline__ void patch33_body(const PatchParams& p, int bid_in) {
         spw = rem - sph * p.PW;
     }
     int st = t0;
+    int sv = 0;                                   // REC: image of the record being staged
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     unsigned voff[MAXIT], gdst[MAXIT];
     auto prep = [&](int buf) {
@@ -382,7 +388,9 @@ __device__ __forceinline__ void patch33_body(const PatchParams& p, int bid_in) {
         for (int q = 0; q < 2; ++q) {
             const bool live = p.pairimg ? sn + q < t1 : st < t1;
             const int rb = sph * SH, cb = spw * SW;
-            const int pixbase = ((p.pairimg ? sn + q : sn) * p.H + rb) * p.W + cb;
+            int simg = p.pairimg ? sn + q : sn;
+            if constexpr (REC) simg = simg * p.rec + sv;      // (sn counts records)
+            const int pixbase = (simg * p.H + rb) * p.W + cb;
             // valid row bits: image row rb + i - 1 in [0, H); columns likewise from bit 12
             int rhi = p.H - rb + 1, chi = p.W - cb + 1;
             rhi = rhi > SH + 2 ? SH + 2 : rhi;
@@ -398,7 +406,14 @@ __device__ __forceinline__ void patch33_body(const PatchParams& p, int bid_in) {
                 spw = 0;
                 if (++sph == p.PH) {
                     sph = 0;
-                    sn += p.pairimg ? 2 : 1;
+                    if constexpr (REC) {
+                        if (++sv == p.rec) {
+                            sv = 0;
+                            sn += 2;
+                        }
+                    } else {
+                        sn += p.pairimg ? 2 : 1;
+                    }
                 }
             }
         }
@@ -611,11 +626,12 @@ __device__ __forceinline__ void patch33_body(const PatchParams& p, int bid_in) {
                 if (do_issue) stage(nxt);
                 WGP33_MARK(0)
             }
-            if (p.pairimg && ++sp_done == p.PPI) {
+            if (p.pairimg && ++sp_done == spu) {
                 // DP-SGD norm pass: each half has just finished a whole image of its own, and the wave's accumulators are
                 // its complete share of that image's gradient tile — add its squared norm and start over.  (One block per
                 // (image, slab) — 16,384 blocks of a single stage for layer4 at batch 256, each with the prologue and the
-                // 144-KiB meeting of the halves — took 530 us per layer; this form ~40.)
+                // 144-KiB meeting of the halves — took 530 us per layer; this form ~40.)  REC: the same after a whole
+                // RECORD — the tile is the sum over the record's images, and `img` below is the record's index.
                 sp_done = 0;
                 const int img = t0 + 2 * img_pair + half;
                 ++img_pair;
@@ -667,6 +683,12 @@ __device__ __forceinline__ void patch33_body(const PatchParams& p, int bid_in) {
 template <int SW, int SH, int STAGES>
 __global__ __launch_bounds__(512) void conv_wgrad_patch33_kernel(PatchParams p) {
     patch33_body<SW, SH, STAGES>(p, xcd_remap(blockIdx.x, gridDim.x));
+}
+
+// the norm pass with whole RECORDS per half (DP-SGD with augmentation multiplicity)
+template <int SW, int SH, int STAGES>
+__global__ __launch_bounds__(512) void conv_wgrad_patch33rec_kernel(PatchParams p) {
+    patch33_body<SW, SH, STAGES, false, true>(p, xcd_remap(blockIdx.x, gridDim.x));
 }
 
 // the loader-wave form (the batched gradient only)
@@ -725,11 +747,12 @@ static PatchGeom patch_geom(const WgradParams& w, WgradForm form, int ngroup = 1
     long per = (g.total + want - 1) / want;
     per = (per + 1) & ~1L;
     if (per < 2) per = 2;
-    if (wgrad_persample(form)) per = g.PPI;  // one split per image
+    if (wgrad_persample(form)) per = (long)w.rec_views * g.PPI;  // one split per image (norm pass: per record)
     if (pairimg_mode(w, form, g)) {
-        // norm pass: a block walks many images, each half whole images of its own (see the kernel); units: images
-        g.total = w.N;
-        per = (w.N + want - 1) / want;
+        // norm pass: a block walks many images, each half whole images of its own (see the kernel); units: images — or
+        // records of w.rec_views images: each half whole records, each block whole records
+        g.total = w.N / w.rec_views;
+        per = (g.total + want - 1) / want;
         per = (per + 1) & ~1L;
         if (per < 2) per = 2;
     }
@@ -762,6 +785,7 @@ static void fill_patch_params(PatchParams& p, const WgradParams& w, const PatchG
     p.ws = store ? w.ws : nullptr;
     p.pairimg = pairimg_mode(w, w.form, g) ? 1 : 0;
     p.nimg = w.N;
+    p.rec = w.rec_views;
     p.ngroups = 1;
     p.group_blocks = 0;
 }
@@ -774,12 +798,15 @@ static int launch_patch33(const WgradParams& w, const PatchGeom& g, hipStream_t 
     const size_t lds = (size_t)kSlab * 4;
     // the batched gradient: four matrix waves (one per SIMD) + four loader waves; the DP-SGD norm passes: the two halves
     const bool lw = !p.pairimg && !p.sqnorm;
-    void (*kern)(PatchParams) = lw ? conv_wgrad_patch33lw_kernel<SW, SH, 3> : conv_wgrad_patch33_kernel<SW, SH, 3>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[lw]) {
+    const bool rec = p.pairimg && p.rec > 1;      // whole records per half
+    void (*kern)(PatchParams) = lw ? conv_wgrad_patch33lw_kernel<SW, SH, 3>
+                                : rec ? conv_wgrad_patch33rec_kernel<SW, SH, 3> : conv_wgrad_patch33_kernel<SW, SH, 3>;
+    static bool attr_set[3] = {false, false, false};
+    const int which = rec ? 2 : lw;
+    if (!attr_set[which]) {
         if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             return PRIMIA_ERR_LAUNCH;
-        attr_set[lw] = true;
+        attr_set[which] = true;
     }
     kern<<<(unsigned)(g.combos * g.nsplit), 512, lds, st>>>(p);
     if (p.ws) {

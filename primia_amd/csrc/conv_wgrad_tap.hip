@@ -46,8 +46,10 @@ struct TapParams {
     int slow;           // counters cannot be advanced with two conditional subtractions: divide every stage
     // per-sample norm pass (DP-SGD, template flag PS): a block walks whole images, each padded to `spi` stages of 64
     // pixels; after an image's last stage the squares of its tile are added to sqnorm[image] and the tile starts over
+    // (template flag REC, DP-SGD with augmentation multiplicity: the tile is completed over a RECORD of `views` consecutive
+    // images — ipb is a multiple of views, so no record straddles two blocks — and its squares go to sqnorm[record])
     double* sqnorm;
-    int nimg, ipb, spi;
+    int nimg, ipb, spi, views;
 };
 
 __device__ __forceinline__ void tap_bdma16(unsigned voff, tap_i32x4 rsrc, unsigned lds_addr) {
@@ -72,8 +74,9 @@ __device__ __forceinline__ int tap_key(int row) {
     return ROW >= 256 ? (row & 3) : ((row >> 1) & 1);
 }
 
-template <int BMK, int BNC, int WM, int WN, bool PS = false>
+template <int BMK, int BNC, int WM, int WN, bool PS = false, bool REC = false>
 __global__ __launch_bounds__(512) void conv_wgrad_tap_kernel(TapParams p) {
+    static_assert(PS || !REC, "the record form is a norm pass");
     constexpr int KP = 64, STAGES = 3;
     constexpr int ROW_A = BMK * 2, ROW_B = BNC * 2;
     constexpr int NA = KP * ROW_A / 1024, NX = KP * ROW_B / 1024;     // DMA pieces per stage
@@ -276,7 +279,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_tap_kernel(TapParams p) {
     for (int s = 0; s < STAGES - 1; ++s)
         if (s < nsteps) stage(s);
     int cur = 0, nxt = STAGES - 1;
-    int c_img = i0, c_sj = 0;     // PS: image and stage-in-image being multiplied
+    int c_img = REC ? i0 / p.views : i0, c_sj = 0;     // PS: image (REC: record) and stage-in-image being multiplied
+    int c_v = 0;                                       // REC: images of the record done
     for (int s = 0; s < nsteps; ++s) {
         wait_pieces(s + 1 < nsteps ? PA + PX : 0);      // stage s has landed; stage s + 1 may be in flight
         __builtin_amdgcn_s_barrier();                    // ... for every wave; buffer `nxt` is no longer read
@@ -285,7 +289,13 @@ __global__ __launch_bounds__(512) void conv_wgrad_tap_kernel(TapParams p) {
         cur = cur + 1 == STAGES ? 0 : cur + 1;
         nxt = nxt + 1 == STAGES ? 0 : nxt + 1;
         if constexpr (PS) {
-            if (++c_sj == p.spi) {     // the image's complete (tap, kt, ct) tile: its squares, then start over
+            bool flush = ++c_sj == p.spi;      // the image's complete (tap, kt, ct) tile: its squares, then start over
+            if constexpr (REC) {               // ... after the record's last image
+                if (flush) c_sj = 0;
+                flush = flush && ++c_v == p.views;
+            }
+            if (flush) {
+                c_v = 0;
                 double sq = 0.0;
 #pragma unroll
                 for (int i = 0; i < FM; ++i)
@@ -438,10 +448,13 @@ static int launch_tap_persample(const WgradParams& w, const TapGeom& g, hipStrea
     if (want < 1) want = 1;
     if (want > w.N) want = w.N;
     p.ipb = (int)((w.N + want - 1) / want);
+    p.views = w.rec_views;
+    if (p.views > 1) p.ipb = (p.ipb + p.views - 1) / p.views * p.views;      // whole records per block
     p.nsplit = (w.N + p.ipb - 1) / p.ipb;
     p.pps = 0;
     const int lds = 3 * 64 * (BMK + BNC) * 2;
-    auto kern = conv_wgrad_tap_kernel<BMK, BNC, WM, WN, true>;
+    void (*kern)(TapParams) = p.views > 1 ? conv_wgrad_tap_kernel<BMK, BNC, WM, WN, true, true>
+                                          : conv_wgrad_tap_kernel<BMK, BNC, WM, WN, true>;
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
         return PRIMIA_ERR_LAUNCH;
     kern<<<g.combos * p.nsplit, 512, lds, st>>>(p);

@@ -103,6 +103,36 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const u32x4* __restri
     if (part == 0 && threadIdx.x == 0) out_targets[slot] = valid ? targets[row_offset + r] : -1;
 }
 
+// Records of stored augmented walks: output slot o = s * views + v is walk (first_walk + v) % repetitions of record idx[s]
+// (data = `repetitions` walks of n_rows rows); padding as gather_batch_kernel
+__global__ __launch_bounds__(256) void gather_records_kernel(const u32x4* __restrict__ data, int64_t row_chunks,
+                                                             int64_t n_rows, const int64_t* __restrict__ targets,
+                                                             const int64_t* __restrict__ idx, int64_t first_walk,
+                                                             int repetitions, int views, u32x4* __restrict__ out,
+                                                             int64_t* __restrict__ out_targets, int parts) {
+    const int o = blockIdx.x / parts, part = blockIdx.x % parts;
+    const int s = o / views, v = o - s * views;
+    const int64_t r = idx[s];
+    const bool valid = r >= 0 && r < n_rows;
+    const int64_t row = ((first_walk + v) % repetitions) * n_rows + r;
+    u32x4* dst = out + (int64_t)o * row_chunks;
+    const int64_t c0 = (int64_t)part * 256 + threadIdx.x, step = (int64_t)parts * 256;
+    if (valid) {
+        const u32x4* src = data + row * row_chunks;
+        for (int64_t c = c0; c < row_chunks; c += step) dst[c] = src[c];
+    } else {
+        const u32x4 zero = {0u, 0u, 0u, 0u};
+        for (int64_t c = c0; c < row_chunks; c += step) dst[c] = zero;
+    }
+    if (part == 0 && threadIdx.x == 0) out_targets[o] = valid ? targets[row] : -1;
+}
+
+// clip_slots[n] = clip[n / views]: a record's clip factor on each of its slots
+__global__ void dp_expand_clip_kernel(const float* __restrict__ clip, float* __restrict__ clip_slots, int N, int views) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n < N) clip_slots[n] = clip[n / views];
+}
+
 // Cross entropy over the valid rows (target >= 0) of a padded batch, single block as xent_kernel (pool_fc_loss.hip).
 // Rows are a handful of classes wide and N is a batch size, so the softmax is formed in fp64 and rounded once: a valid
 // dlogits row is the fp32 rounding of softmax - onehot, the per-sample loss gradient DP-SGD clips.
@@ -190,6 +220,30 @@ extern "C" int primia_gather_batch(const void* data, int64_t row_elems, int64_t 
     PRIMIA_REQUIRE((int64_t)capacity * parts <= INT32_MAX);
     gather_batch_kernel<<<(unsigned)(capacity * parts), 256, 0, (hipStream_t)st>>>(
         (const u32x4*)data, row_chunks, n_rows, targets, idx, row_offset, (u32x4*)out, out_targets, (int)parts);
+    return launch_status();
+}
+
+extern "C" int primia_gather_records(const void* data, int64_t row_elems, int64_t n_rows, const int64_t* targets,
+                                     const int64_t* idx, int64_t first_walk, int repetitions, int views, void* out,
+                                     int64_t* out_targets, int capacity, int dtype, primia_stream_t st) {
+    PRIMIA_REQUIRE(data && targets && idx && out && out_targets);
+    PRIMIA_REQUIRE(row_elems > 0 && n_rows >= 0 && first_walk >= 0 && repetitions >= 1 && views >= 1 && capacity > 0);
+    PRIMIA_REQUIRE(dtype == PRIMIA_F32 || dtype == PRIMIA_BF16);
+    const int64_t per_chunk = dtype == PRIMIA_F32 ? 4 : 8;
+    PRIMIA_REQUIRE(row_elems % per_chunk == 0 && ((uintptr_t)data & 15) == 0 && ((uintptr_t)out & 15) == 0);
+    const int64_t row_chunks = row_elems / per_chunk;
+    int64_t parts = (row_chunks + 1023) / 1024;
+    if (parts > 64) parts = 64;
+    PRIMIA_REQUIRE((int64_t)capacity * views * parts <= INT32_MAX);
+    gather_records_kernel<<<(unsigned)(capacity * views * parts), 256, 0, (hipStream_t)st>>>(
+        (const u32x4*)data, row_chunks, n_rows, targets, idx, first_walk, repetitions, views, (u32x4*)out, out_targets,
+        (int)parts);
+    return launch_status();
+}
+
+extern "C" int primia_dp_expand_clip(const float* clip, float* clip_slots, int N, int views, primia_stream_t st) {
+    PRIMIA_REQUIRE(clip && clip_slots && N > 0 && views >= 1 && N % views == 0);
+    dp_expand_clip_kernel<<<(N + 255) / 256, 256, 0, (hipStream_t)st>>>(clip, clip_slots, N, views);
     return launch_status();
 }
 

@@ -591,6 +591,41 @@ __global__ __launch_bounds__(256) void persample_sqnorm_many_kernel(const float*
     if (threadIdx.x == 0) atomicAdd(out + n, sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
+// The record forms (DP-SGD with augmentation multiplicity): blockIdx.y is a record of `views` consecutive rows, whose sum
+// (fp64) is squared — out[record] += sum_j (sum_v x[record * views + v][j])^2
+__global__ __launch_bounds__(256) void record_sqnorm_kernel(const float* __restrict__ x, long per, int views, double* out) {
+    const int r = blockIdx.y;
+    const float* p = x + (long)r * views * per;
+    double s = 0.0;
+    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < per; j += (long)gridDim.x * 256) {
+        double v = 0.0;
+        for (int k = 0; k < views; ++k) v += (double)p[(long)k * per + j];
+        s += v * v;
+    }
+    s = wave_sum(s);
+    __shared__ double sh[4];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(out + r, sh[0] + sh[1] + sh[2] + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void record_sqnorm_many_kernel(const float* const* __restrict__ xs,
+                                                                 const int* __restrict__ pers, int views, double* out) {
+    const int r = blockIdx.y, per = pers[blockIdx.x];
+    const float* p = xs[blockIdx.x] + (long)r * views * per;
+    double s = 0.0;
+    for (int j = threadIdx.x; j < per; j += 256) {
+        double v = 0.0;
+        for (int k = 0; k < views; ++k) v += (double)p[(long)k * per + j];
+        s += v * v;
+    }
+    s = wave_sum(s);
+    __shared__ double sh[4];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(out + r, sh[0] + sh[1] + sh[2] + sh[3]);
+}
+
 // clip[n] = min(1, C / (sqrt(sq[n]) + 1e-6))   (pytorch-dp's per-sample clip factor)
 __global__ void dp_clip_factor_kernel(const double* __restrict__ sq, float* __restrict__ clip, int N, float max_norm) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -964,6 +999,24 @@ int primia_persample_sqnorm_many(const void* xs_dev, const int* widths_dev, int 
     PRIMIA_REQUIRE(xs_dev && widths_dev && sq_acc && count > 0 && N > 0);
     persample_sqnorm_many_kernel<<<dim3(count, N), 256, 0, (hipStream_t)stream>>>((const float* const*)xs_dev, widths_dev,
                                                                                  sq_acc);
+    return launch_status();
+}
+
+int primia_record_sqnorm(const float* x, int N, int64_t per_sample, int views, double* sq_acc, primia_stream_t stream) {
+    PRIMIA_REQUIRE(x && sq_acc && N > 0 && per_sample > 0 && views >= 1 && N % views == 0);
+    long b = (per_sample + 255) / 256;
+    if (b > 64) b = 64;
+    record_sqnorm_kernel<<<dim3((int)b, N / views), 256, 0, (hipStream_t)stream>>>(x, per_sample, views, sq_acc);
+    return launch_status();
+}
+
+int primia_record_sqnorm_many(const void* xs_dev, const int* widths_dev, int count, int N, int views, double* sq_acc,
+                              primia_stream_t stream) {
+    PRIMIA_REQUIRE(N > 0 && views >= 1 && N % views == 0);
+    if (count == 0) return PRIMIA_OK;
+    PRIMIA_REQUIRE(xs_dev && widths_dev && sq_acc && count > 0);
+    record_sqnorm_many_kernel<<<dim3(count, N / views), 256, 0, (hipStream_t)stream>>>((const float* const*)xs_dev,
+                                                                                       widths_dev, views, sq_acc);
     return launch_status();
 }
 

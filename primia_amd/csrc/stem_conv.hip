@@ -348,7 +348,8 @@ struct StemWgParams {
     const bf16* dy;
     float* dw;
     float* ws;      // atomic-free path: one [64][256] fp32 slab per block (or null: atomics into dw)
-    double* sqnorm; // DP-SGD norm pass: one block per image, adds ||dW_n||^2 to sqnorm[blockIdx.x] instead of writing
+    double* sqnorm; // DP-SGD norm pass: one block per image (per record of several images: the host sets per_block), adds
+                    // the squared norm of the block's gradient to sqnorm[blockIdx.x] instead of writing
     int N, Hp, Wp, Ho, Wo;
     int PH, PW, PPI;
     int total, per_block;
@@ -561,7 +562,7 @@ size_t stem_wgrad_halo_ws_bytes(int N, int H, int W) {
 
 // PRIMIA_ERR_UNSUPPORTED -> caller uses the per-tap stem kernel of conv_wgrad.hip
 int stem_wgrad_halo_dispatch(const bf16* xp, const bf16* dy, float* dw, int N, int H, int W, hipStream_t st, float* ws,
-                             size_t ws_bytes, double* sqnorm) {
+                             size_t ws_bytes, double* sqnorm, int rec_views) {
     if (!stem_wgrad_halo_ok(N, H, W)) return PRIMIA_ERR_UNSUPPORTED;
     StemWgParams p;
     p.xp = xp; p.dy = dy; p.dw = dw;
@@ -570,9 +571,10 @@ int stem_wgrad_halo_dispatch(const bf16* xp, const bf16* dy, float* dw, int N, i
     int grid;
     stem_wgrad_geometry(N, H, W, p.total, p.per_block, grid);
     p.sqnorm = sqnorm;
-    if (sqnorm) {          // one block per image
-        p.per_block = p.PPI;
-        grid = N;
+    if (sqnorm) {          // one block per image; rec_views > 1: per record, walking its consecutive images
+        if (rec_views < 1 || N % rec_views != 0 || (rec_views > 1 && ws)) return PRIMIA_ERR_ARG;
+        p.per_block = rec_views * p.PPI;
+        grid = N / rec_views;
     }
     const bool store = ws && ws_bytes >= (size_t)grid * 64 * 256 * sizeof(float);   // (norm pass: one slab per image)
     p.ws = store ? ws : nullptr;

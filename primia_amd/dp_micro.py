@@ -52,11 +52,14 @@ def step(engine, optimizer, data, target, hip_graph=False, soft=False):
         from .step import eager_step as one_pass
     masked = root.dp_params.get("expected_batch") is not None
     n = int(data.shape[0])
+    # (augmentation multiplicity: a record is dp_params["views"] consecutive rows, root.N a whole number of records — no
+    # record straddles two passes — and the logical batch is counted in records)
+    records = n // int(root.dp_params.get("views", 1))
     cuts = views(n, root.N)
     total, weight = None, None
     for i, (a, b) in enumerate(cuts):
         x, y = data[a:b], target[a:b]
-        loss = one_pass(engine, optimizer, x, y, soft=soft, phase=phase_of(i, len(cuts)), logical_batch=n)
+        loss = one_pass(engine, optimizer, x, y, soft=soft, phase=phase_of(i, len(cuts)), logical_batch=records)
         if len(cuts) == 1:
             return loss
         # (a masked pass's loss is the mean over ITS valid rows, 0 when it has none)

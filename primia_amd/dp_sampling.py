@@ -78,8 +78,14 @@ class _PoissonBase:
     """`expected_batch`: the integer L of q = L / n (threshold = floor(L * 2^64 / n), in integers), or None with an
     explicit `threshold` (tests)."""
 
-    def __init__(self, n, expected_batch, capacity, sampler, threshold=None, micro_batches=1):
+    def __init__(self, n, expected_batch, capacity, sampler, threshold=None, micro_batches=1, views=1):
         self.n, self.capacity, self.sampler = int(n), int(capacity), sampler
+        # augmentation multiplicity (train.py --dp_augmult): every record fills `views` consecutive rows of the batch.  n,
+        # expected_batch, capacity, micro_size and slots keep counting RECORDS — what the accountant sees does not change —
+        # and the batch (and an engine of one pass) has views times as many rows
+        self.views = int(views)
+        if self.views < 1:
+            raise ValueError("views must be at least 1")
         # a step run as K micro-batch passes (dp_micro): an engine of M = ceil(capacity / K) slots walks K * M >= capacity
         # slots; the selection, its capacity and its stream do not know about K, the extra slots are padding for ever
         self.micro_batches = int(micro_batches)
@@ -108,13 +114,16 @@ class PoissonLoader(_PoissonBase):
     `repetitions` walks of the same n records, laid out as walk * n + k (imagefolder.register): sampling is over the n
     RECORDS, and epoch e reads walk e % repetitions through the gather's row offset — one person is one record for the
     accountant however many augmented copies are stored.  __len__ = ceil(n / L).  Every iteration yields the SAME
-    [capacity, ...] buffer pair, rewritten in place."""
+    [capacity, ...] buffer pair, rewritten in place.  `views` = m > 1: a record fills rows s * m .. s * m + m - 1 with its
+    walks (e * m + v) % repetitions, v < m, of epoch e (primia_gather_records); with m > repetitions the views repeat
+    stored copies."""
 
-    def __init__(self, data, targets, expected_batch, capacity, sampler, repetitions=1, threshold=None, micro_batches=1):
+    def __init__(self, data, targets, expected_batch, capacity, sampler, repetitions=1, threshold=None, micro_batches=1,
+                 views=1):
         reps = int(repetitions)
         if data.shape[0] % reps or targets.shape[0] != data.shape[0] or targets.dtype != torch.int64 or targets.dim() != 1:
             raise ValueError("PoissonLoader: data [repetitions * n, ...] with hard int64 targets [repetitions * n]")
-        super().__init__(data.shape[0] // reps, expected_batch, capacity, sampler, threshold, micro_batches)
+        super().__init__(data.shape[0] // reps, expected_batch, capacity, sampler, threshold, micro_batches, views)
         self.data, self.targets, self.repetitions = data.contiguous(), targets.contiguous(), reps
         self.row_elems = int(self.data[0].numel())
         self.dt = dtype_code(self.data.dtype)
@@ -126,20 +135,30 @@ class PoissonLoader(_PoissonBase):
                              "train_resolution)".format(tuple(self.data.shape[1:]), self.row_elems, self.data.dtype,
                                                         row_bytes))
         # (the gather writes the first `capacity` slots; the K * M - capacity behind them stay a zero image with target -1)
-        self.x = torch.zeros((self.slots,) + tuple(self.data.shape[1:]), dtype=self.data.dtype, device=data.device)
-        self.y = torch.full((self.slots,), -1, dtype=torch.int64, device=data.device)
+        rows = self.slots * self.views
+        self.x = torch.zeros((rows,) + tuple(self.data.shape[1:]), dtype=self.data.dtype, device=data.device)
+        self.y = torch.full((rows,), -1, dtype=torch.int64, device=data.device)
         self.epochs = 0
 
+    def walks(self, epoch):
+        """The stored walks a record's views read in epoch `epoch`: (epoch * views + v) % repetitions."""
+        return [(int(epoch) * self.views + v) % self.repetitions for v in range(self.views)]
+
     def draw(self, walk=0):
-        """One batch into (self.x, self.y): select, advance, gather — no host synchronisation."""
+        """One batch into (self.x, self.y): select, advance, gather — no host synchronisation.  `walk`: the walk of a
+        record's first view (the next views - 1 follow it, modulo repetitions)."""
         self.sampler.select(self.threshold, self.n, self.idx, self.count)
-        call("primia_gather_batch", self.data, self.row_elems, self.n, self.targets, self.idx, int(walk) * self.n,
-             self.x, self.y, self.capacity, self.dt)
+        if self.views == 1:
+            call("primia_gather_batch", self.data, self.row_elems, self.n, self.targets, self.idx, int(walk) * self.n,
+                 self.x, self.y, self.capacity, self.dt)
+        else:
+            call("primia_gather_records", self.data, self.row_elems, self.n, self.targets, self.idx, int(walk),
+                 self.repetitions, self.views, self.x, self.y, self.capacity, self.dt)
         self.draws += 1
         return self.x, self.y
 
     def __iter__(self):
-        walk = self.epochs % self.repetitions
+        walk = self.walks(self.epochs)[0]
         self.epochs += 1
         for _ in range(len(self)):
             yield self.draw(walk)
@@ -148,13 +167,15 @@ class PoissonLoader(_PoissonBase):
 class PoissonAugmentingLoader(_PoissonBase):
     """Poisson batches over a transforming dataset (imagefolder.AugmentingLoader's case: vanilla training on an image
     folder).  The selection is the same kernel; idx and count are read back (one small copy per step: this loader is
-    host-driven anyway), the kept images go through TrainTransform.batch and the result is padded to capacity."""
+    host-driven anyway), the kept images go through TrainTransform.batch and the result is padded to capacity.  `views`
+    = m > 1: every kept image goes through the transform m times in a row, each time with its own draws."""
 
-    def __init__(self, images, targets, transform, rng, expected_batch, capacity, sampler, shape, micro_batches=1):
-        super().__init__(len(images), expected_batch, capacity, sampler, micro_batches=micro_batches)
+    def __init__(self, images, targets, transform, rng, expected_batch, capacity, sampler, shape, micro_batches=1, views=1):
+        super().__init__(len(images), expected_batch, capacity, sampler, micro_batches=micro_batches, views=views)
         self.images, self.targets, self.tf, self.rng = images, targets, transform, rng
-        self.x = torch.zeros((self.slots,) + tuple(shape), dtype=torch.float32, device=sampler.device)
-        self.y = torch.full((self.slots,), -1, dtype=torch.int64, device=sampler.device)
+        rows = self.slots * self.views
+        self.x = torch.zeros((rows,) + tuple(shape), dtype=torch.float32, device=sampler.device)
+        self.y = torch.full((rows,), -1, dtype=torch.int64, device=sampler.device)
 
     def __iter__(self):
         for _ in range(len(self)):
@@ -163,9 +184,13 @@ class PoissonAugmentingLoader(_PoissonBase):
             idx = self.idx[:kept]
             self.x.zero_()
             self.y.fill_(-1)
-            if kept:
+            if kept and self.views == 1:
                 self.x[:kept] = self.tf.batch([self.images[i] for i in idx.tolist()], self.rng)
                 self.y[:kept] = self.targets.index_select(0, idx)
+            elif kept:
+                m = self.views
+                self.x[:kept * m] = self.tf.batch([self.images[i] for i in idx.tolist() for _ in range(m)], self.rng)
+                self.y[:kept * m] = self.targets.index_select(0, idx).repeat_interleave(m)
             self.draws += 1
             yield self.x, self.y
 
@@ -177,11 +202,11 @@ def records_of(loader, repetitions=1):
     return int(loader.data.shape[0]) // int(repetitions)
 
 
-def from_loader(loader, expected_batch, capacity, sampler, repetitions=1, shape=None, micro_batches=1):
+def from_loader(loader, expected_batch, capacity, sampler, repetitions=1, shape=None, micro_batches=1, views=1):
     """The Poisson-sampled form of imagefolder.DeviceLoader (-> PoissonLoader) or imagefolder.AugmentingLoader
     (-> PoissonAugmentingLoader; `shape`: one transformed image's)."""
     if hasattr(loader, "images"):
         return PoissonAugmentingLoader(loader.images, loader.targets, loader.tf, loader.rng, expected_batch, capacity,
-                                       sampler, shape, micro_batches=micro_batches)
+                                       sampler, shape, micro_batches=micro_batches, views=views)
     return PoissonLoader(loader.data, loader.targets, expected_batch, capacity, sampler, repetitions,
-                         micro_batches=micro_batches)
+                         micro_batches=micro_batches, views=views)

@@ -1205,7 +1205,7 @@ class ResNet18Engine:
     # DP-SGD (BASELINE.json configs[3]; parameter values of train.py:325-334)
     # ------------------------------------------------------------------------------------------
     def dp_loss_backward(self, target, max_grad_norm=1.0, noise_multiplier=1.3, noise=None, generator=None,
-                         expected_batch=None, accumulate=None, logical_batch=None):
+                         expected_batch=None, accumulate=None, logical_batch=None, views=1):
         """Per-sample gradient clipping + Gaussian noise, pytorch-dp semantics:
             g = (1/B) * ( sum_n min(1, C / (||g_n|| + 1e-6)) * g_n  +  N(0, (noise_multiplier*C)^2 I) )
         with g_n the gradient of sample n's OWN loss over all 62 parameter tensors (flat L2 norm).
@@ -1232,7 +1232,17 @@ class ResNet18Engine:
 
         With the root's `dp_clip` set (primia_amd.dp_clip.AdaptiveClip) C is that object's device word instead of
         `max_grad_norm`: the clip factors come with the step's {below, valid} counts (dp_stats["counts"]: private, for
-        tests), the noise is z_delta * C, and the last (or only) pass moves C once — see _dp_adaptive_tail."""
+        tests), the noise is z_delta * C, and the last (or only) pass moves C once — see _dp_adaptive_tail.
+
+        `views` (m > 1: augmentation multiplicity, De et al. 2022; `train.py --dp_augmult`): the N slots are R = N / m
+        RECORDS of m consecutive views of one image (same target; a padded record has m targets of -1).  A record
+        contributes the AVERAGE of its views' gradients, clipped once:
+            g_r = (1/m) sum_{n in record r} g_n,   c_r = min(1, C / (||g_r|| + 1e-6)),   g = (sum_r c_r g_r + noise) / B
+        with B, expected_batch and logical_batch counted in records.  The dlogits rows are scaled by 1/m up front, so
+        every slot gradient below is g_n / m and a record's gradient a plain sum; the norm pass completes each kernel's
+        tile over a record's images (primia_conv2d_wgrad_record_sqnorm: the cross terms between views), dp_stats has
+        R entries, and each record's clip factor is expanded to its slots for the clipped sums.  The kept-tile forms
+        are per sample: an engine with views > 1 runs the two-pass form on every layer."""
         masked = expected_batch is not None
         if accumulate not in (None, "first", "more", "last"):
             raise ValueError("dp_loss_backward: accumulate is None, 'first', 'more' or 'last'")
@@ -1241,6 +1251,11 @@ class ResNet18Engine:
         if self.norm not in ("group", "frozen"):
             raise _lib.PrimiaError("DP-SGD needs per-sample independent norm layers: ResNet18Engine(norm='group') or "
                                    "norm='frozen' (BatchNorm with fixed statistics)")
+        if int(views) != 1:
+            if int(views) < 1 or self.N % int(views):
+                raise ValueError(f"dp_loss_backward: views = {views} does not cut the engine's {self.N} slots into records")
+            return self._dp_loss_backward_records(target, max_grad_norm, noise_multiplier, noise, generator, expected_batch,
+                                                  accumulate, logical_batch, int(views))
         N, nc, dev = self.N, self.spec.num_classes, self.device
         # per-sample loss gradients: softmax - onehot (xent gives them divided by the batch size)
         if masked:      # softmax - onehot on valid rows, zeros on padded ones; the loss is the mean over the valid rows
@@ -1312,83 +1327,97 @@ class ResNet18Engine:
                 call("primia_dp_clip_factors_masked", sq, target, clip, N, float(max_grad_norm))
             else:
                 call("primia_dp_clip_factors", sq, clip, N, float(max_grad_norm))
-            # clipped sums
-            # (a transition block's conv1 + downsample: ONE launch as in plain training, once both dy are scaled)
-            pair_of, pair_wait = {}, {}
-            if self.wgrad_ws is not None:
-                for blk in self.spec.blocks:
-                    if (blk.down is not None and self._pair_ws.get(blk.conv1.name, 0) > 0
-                            and blk.conv1.name not in kept and blk.down.name not in kept):
-                        pair_of[blk.conv1.name] = pair_of[blk.down.name] = blk
-            # every dy of a layer whose tiles are not kept, scaled by the clip factors in ONE launch (a dozen tensors)
-            to_scale = [dy for name, _, dy in self.dp["wgrads"] if name not in kept]
-            many = 0 < len(to_scale) <= 16
-            if many:
-                key = tuple(tt.data_ptr() for tt in to_scale)
-                if getattr(self, "_scale_many", (None,))[0] != key:
-                    import ctypes
-
-                    self._scale_many = (key, (ctypes.c_void_p * len(key))(*key),
-                                        (ctypes.c_int64 * len(key))(*[tt.numel() // N for tt in to_scale]))
-                call("primia_scale_rows_many", self._scale_many[1], self._scale_many[2], len(key), clip, N, self.dt)
-            for name, x, dy in self.dp["wgrads"]:
-                c = self.convs[name]
-                if name in pair_of:
-                    blk = pair_of[name]
-                    if not many:
-                        call("primia_scale_rows", dy, clip, N, dy.numel() // N, self.dt)
-                    got = pair_wait.setdefault(blk.prefix, {})
-                    got[name] = (x, dy)
-                    if len(got) == 2:
-                        c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
-                        call("primia_conv2d_wgrad_pair_ws", c1.desc, got[blk.conv1.name][0], got[blk.conv1.name][1], c1.acc,
-                             cd.desc, got[blk.down.name][1], cd.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)
-                    continue
-                if name in kept:
-                    if name == "conv1":
-                        call("primia_stem_conv_wgrad_clipped_sum", kept[name], clip, c.acc, N)
-                    else:
-                        call("primia_conv_wgrad_clipped_sum", c.desc, kept[name], clip, c.acc, self.dt)
-                    continue
-                if not many:
-                    call("primia_scale_rows", dy, clip, N, dy.numel() // N, self.dt)
-                # the clipped SUM is an ordinary batched weight gradient: atomic-free kernels, and for the stem the
-                # halo kernel on the padded input (118 us instead of 444 us for the per-tap one)
-                if self.wgrad_ws is not None and name in self._wg_group:     # same-shape layers: one launch per stage
-                    key, n = self._wg_group[name]
-                    held = self._wg_held.setdefault(key, [])
-                    held.append((name, x, dy))
-                    if len(held) == n:
-                        self._flush_wgrad_group(key)
-                    continue
-                if self.wgrad_ws is None:
-                    call("primia_conv2d_wgrad", c.desc, x, dy, c.acc, self.dt)
-                elif name == "conv1" and self._stem_padded:
-                    S = self.spec.input_size
-                    call("primia_stem_conv_wgrad_ws", self.x0p, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, N, S, S,
-                         self.dt)
-                else:
-                    call("primia_conv2d_wgrad_ws", c.desc, x, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)
-            self._finalize_wgrads()
-            # clipped sums of the per-sample affine gradients: all 40 (dgamma, dbeta) pairs in ONE launch
-            if getattr(self, "_colsum_many", None) is None:
-                xs, outs, ws_ = [], [], []
-                for b, (psg, psb) in self.ps_affine.items():
-                    xs += [psg.data_ptr(), psb.data_ptr()]
-                    outs += [self._gviews[b + ".weight"].data_ptr(), self._gviews[b + ".bias"].data_ptr()]
-                    ws_ += [psg.shape[1], psb.shape[1]]
-                self._colsum_many = (torch.tensor(xs, dtype=torch.int64, device=dev),
-                                     torch.tensor(outs, dtype=torch.int64, device=dev),
-                                     torch.tensor(ws_, dtype=torch.int32, device=dev), len(xs), max(ws_))
-            xs_d, outs_d, ws_d, cnt, mw = self._colsum_many
-            call("primia_weighted_colsum_many", xs_d, clip, outs_d, ws_d, cnt, mw, N)
-            call("primia_weighted_colsum", ps_fc[:, :nc * 512].contiguous(), clip, self._gviews["fc.weight"].view(-1), N,
-                 nc * 512)
-            call("primia_weighted_colsum", ps_fc[:, nc * 512:].contiguous(), clip, self._gviews["fc.bias"], N, nc)
+            self._dp_clipped_sums(clip, ps_fc, kept)
         finally:
             if getattr(self, "dp_keep_operands", False):      # tests: the (layer, x, dy) triples the norm pass walked
                 self.dp_operands = list(self.dp["wgrads"])
             self.dp = None
+        return self._dp_tail(sq, clip, adaptive, N, masked, expected_batch, accumulate, logical_batch, max_grad_norm,
+                             noise_multiplier, noise, generator)
+
+    def _dp_clipped_sums(self, clip, ps_fc, kept):
+        """grads = sum_n clip[n] g_n over the N slots of a DP-SGD pass (self.dp holds the backward pass's operands): the
+        rows of dy scaled and the batched weight gradient, the weighted reduce of the `kept` layers' tiles, the weighted
+        column sums of the per-sample affine and fc gradients."""
+        N, nc, dev = self.N, self.spec.num_classes, self.device
+        # (a transition block's conv1 + downsample: ONE launch as in plain training, once both dy are scaled)
+        pair_of, pair_wait = {}, {}
+        if self.wgrad_ws is not None:
+            for blk in self.spec.blocks:
+                if (blk.down is not None and self._pair_ws.get(blk.conv1.name, 0) > 0
+                        and blk.conv1.name not in kept and blk.down.name not in kept):
+                    pair_of[blk.conv1.name] = pair_of[blk.down.name] = blk
+        # every dy of a layer whose tiles are not kept, scaled by the clip factors in ONE launch (a dozen tensors)
+        to_scale = [dy for name, _, dy in self.dp["wgrads"] if name not in kept]
+        many = 0 < len(to_scale) <= 16
+        if many:
+            key = tuple(tt.data_ptr() for tt in to_scale)
+            if getattr(self, "_scale_many", (None,))[0] != key:
+                import ctypes
+
+                self._scale_many = (key, (ctypes.c_void_p * len(key))(*key),
+                                    (ctypes.c_int64 * len(key))(*[tt.numel() // N for tt in to_scale]))
+            call("primia_scale_rows_many", self._scale_many[1], self._scale_many[2], len(key), clip, N, self.dt)
+        for name, x, dy in self.dp["wgrads"]:
+            c = self.convs[name]
+            if name in pair_of:
+                blk = pair_of[name]
+                if not many:
+                    call("primia_scale_rows", dy, clip, N, dy.numel() // N, self.dt)
+                got = pair_wait.setdefault(blk.prefix, {})
+                got[name] = (x, dy)
+                if len(got) == 2:
+                    c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
+                    call("primia_conv2d_wgrad_pair_ws", c1.desc, got[blk.conv1.name][0], got[blk.conv1.name][1], c1.acc,
+                         cd.desc, got[blk.down.name][1], cd.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)
+                continue
+            if name in kept:
+                if name == "conv1":
+                    call("primia_stem_conv_wgrad_clipped_sum", kept[name], clip, c.acc, N)
+                else:
+                    call("primia_conv_wgrad_clipped_sum", c.desc, kept[name], clip, c.acc, self.dt)
+                continue
+            if not many:
+                call("primia_scale_rows", dy, clip, N, dy.numel() // N, self.dt)
+            # the clipped SUM is an ordinary batched weight gradient: atomic-free kernels, and for the stem the
+            # halo kernel on the padded input (118 us instead of 444 us for the per-tap one)
+            if self.wgrad_ws is not None and name in self._wg_group:     # same-shape layers: one launch per stage
+                key, n = self._wg_group[name]
+                held = self._wg_held.setdefault(key, [])
+                held.append((name, x, dy))
+                if len(held) == n:
+                    self._flush_wgrad_group(key)
+                continue
+            if self.wgrad_ws is None:
+                call("primia_conv2d_wgrad", c.desc, x, dy, c.acc, self.dt)
+            elif name == "conv1" and self._stem_padded:
+                S = self.spec.input_size
+                call("primia_stem_conv_wgrad_ws", self.x0p, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, N, S, S,
+                     self.dt)
+            else:
+                call("primia_conv2d_wgrad_ws", c.desc, x, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)
+        self._finalize_wgrads()
+        # clipped sums of the per-sample affine gradients: all 40 (dgamma, dbeta) pairs in ONE launch
+        if getattr(self, "_colsum_many", None) is None:
+            xs, outs, ws_ = [], [], []
+            for b, (psg, psb) in self.ps_affine.items():
+                xs += [psg.data_ptr(), psb.data_ptr()]
+                outs += [self._gviews[b + ".weight"].data_ptr(), self._gviews[b + ".bias"].data_ptr()]
+                ws_ += [psg.shape[1], psb.shape[1]]
+            self._colsum_many = (torch.tensor(xs, dtype=torch.int64, device=dev),
+                                 torch.tensor(outs, dtype=torch.int64, device=dev),
+                                 torch.tensor(ws_, dtype=torch.int32, device=dev), len(xs), max(ws_))
+        xs_d, outs_d, ws_d, cnt, mw = self._colsum_many
+        call("primia_weighted_colsum_many", xs_d, clip, outs_d, ws_d, cnt, mw, N)
+        call("primia_weighted_colsum", ps_fc[:, :nc * 512].contiguous(), clip, self._gviews["fc.weight"].view(-1), N,
+             nc * 512)
+        call("primia_weighted_colsum", ps_fc[:, nc * 512:].contiguous(), clip, self._gviews["fc.bias"], N, nc)
+
+    def _dp_tail(self, sq, clip, adaptive, units, masked, expected_batch, accumulate, logical_batch, max_grad_norm,
+                 noise_multiplier, noise, generator):
+        """The end of dp_loss_backward once `grads` holds the pass's clipped sum: accumulate, or noise and the division
+        by B — in samples, or in records (`units` of this engine) under augmentation multiplicity."""
+        dev = self.device
         self.dp_stats = {"sq_norms": sq, "clip": clip}
         if adaptive is not None:        # (tests: the raw count is private, never printed or saved)
             self.dp_stats["counts"] = adaptive.counts
@@ -1396,7 +1425,7 @@ class ResNet18Engine:
             call("primia_dp_accumulate", self.dp_acc, self.grads, self.P, 1 if accumulate == "first" else 0)
             return self.loss
         acc = self.dp_acc if accumulate == "last" else None
-        batch = float(expected_batch) if masked else (N if acc is None else int(logical_batch))
+        batch = float(expected_batch) if masked else (units if acc is None else int(logical_batch))
         inv_batch = 1.0 / batch
         if adaptive is not None:
             return self._dp_adaptive_tail(adaptive, acc, batch, inv_batch, noise_multiplier, noise, generator)
@@ -1412,6 +1441,80 @@ class ResNet18Engine:
             else:
                 call("primia_dp_add_noise_acc", self.grads, acc, noise, self.P, sigma, inv_batch)
         return self.loss
+
+    def _dp_loss_backward_records(self, target, max_grad_norm, noise_multiplier, noise, generator, expected_batch, accumulate,
+                                  logical_batch, m):
+        """dp_loss_backward for records of m > 1 views (see there): the two-pass form on every layer, norms per record."""
+        masked = expected_batch is not None
+        N, nc, dev = self.N, self.spec.num_classes, self.device
+        R = N // m
+        if masked:
+            call("primia_xent_hard_masked", self.logits, target, self.loss, self.dlogits, N, nc)
+            call("primia_scale", self.dlogits, self.dlogits.numel(), 1.0 / m)
+        else:
+            call("primia_xent_hard", self.logits, target, None, self.loss, self.dlogits, N, nc)
+            call("primia_scale", self.dlogits, self.dlogits.numel(), float(N) / m)
+        self.dp = {"wgrads": []}
+        try:
+            self.backward()
+            sq = torch.zeros(R, dtype=torch.float64, device=dev)
+            ps_fc = torch.empty(N, nc * 512 + nc, dtype=torch.float32, device=dev)
+            call("primia_fc_persample_grads", self.feat, self.dlogits, ps_fc, N, 512, nc)
+            trace = getattr(self, "dp_trace", None)
+
+            def mark(name):
+                if trace is not None:
+                    trace[name] = sq.clone()
+
+            call("primia_record_sqnorm", ps_fc, N, nc * 512 + nc, m, sq)
+            mark("fc")
+            if trace is None:
+                if getattr(self, "_sqnorm_many", None) is None:
+                    xs = [tt.data_ptr() for pair in self.ps_affine.values() for tt in pair]
+                    ws_ = [tt.shape[1] for pair in self.ps_affine.values() for tt in pair]
+                    self._sqnorm_many = (torch.tensor(xs, dtype=torch.int64, device=dev),
+                                         torch.tensor(ws_, dtype=torch.int32, device=dev), len(xs))
+                call("primia_record_sqnorm_many", self._sqnorm_many[0], self._sqnorm_many[1], self._sqnorm_many[2], N, m, sq)
+            else:
+                for b, (psg, psb) in self.ps_affine.items():
+                    call("primia_record_sqnorm", psg, N, psg.shape[1], m, sq)
+                    call("primia_record_sqnorm", psb, N, psb.shape[1], m, sq)
+                    mark(b)
+            for name, x, dy in self.dp["wgrads"]:
+                c = self.convs[name]
+                done = False
+                if name == "conv1" and self._stem_padded:   # halo kernel on the padded input, one block per record
+                    S = self.spec.input_size
+                    try:
+                        call("primia_stem_conv_wgrad_record_sqnorm", self.x0p, dy, sq, N, S, S, m, self.dt)
+                        done = True
+                    except _lib.PrimiaError:
+                        done = False
+                if not done:
+                    if name == "conv1" and not self._x0_valid:
+                        raise _lib.PrimiaError("per-record stem gradient: the padded-input kernel refused a shape it "
+                                               "advertised (primia_stem_conv_wgrad_ws_bytes > 0)")
+                    call("primia_conv2d_wgrad_record_sqnorm", c.desc, x, dy, sq, m, self.dt)
+                mark(name)
+            # the factor kernels run unchanged on the R records; record r's target is slot r * m's
+            clip_r = torch.empty(R, dtype=torch.float32, device=dev)
+            target_r = target[::m].contiguous() if masked else None
+            adaptive = self._root.dp_clip
+            if adaptive is not None:
+                adaptive.factors(sq, target_r, clip_r, R, overwrite=accumulate in (None, "first"))
+            elif masked:
+                call("primia_dp_clip_factors_masked", sq, target_r, clip_r, R, float(max_grad_norm))
+            else:
+                call("primia_dp_clip_factors", sq, clip_r, R, float(max_grad_norm))
+            clip = torch.empty(N, dtype=torch.float32, device=dev)
+            call("primia_dp_expand_clip", clip_r, clip, N, m)
+            self._dp_clipped_sums(clip, ps_fc, {})
+        finally:
+            if getattr(self, "dp_keep_operands", False):
+                self.dp_operands = list(self.dp["wgrads"])
+            self.dp = None
+        return self._dp_tail(sq, clip_r, adaptive, R, masked, expected_batch, accumulate, logical_batch, max_grad_norm,
+                             noise_multiplier, noise, generator)
 
     def _dp_adaptive_tail(self, adaptive, acc, batch, inv_batch, z, noise, generator):
         """The end of a logical DP-SGD step under an adaptive clipping norm (engine.dp_clip): noise z_delta * C on the

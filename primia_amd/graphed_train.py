@@ -77,6 +77,9 @@ def _key(eng, optimizer, soft, phase=None, logical_batch=None):
         if dp.get("expected_batch") is not None:
             # padded fixed-capacity batches (dp_sampling.PoissonLoader): other loss and clip kernels, 1 / L in the noise node
             key += ("Poisson-sampled", float(dp["expected_batch"]))
+        if int(dp.get("views", 1)) > 1:
+            # augmentation multiplicity: the record kernels, 1 / views in the loss gradient's scale
+            key += ("records of views", int(dp["views"]))
         if phase is not None:
             # a pass of a step cut into micro-batches: other tail kernels per phase, 1 / batch in the last one's noise node
             inv = 1.0 / float(dp["expected_batch"] if dp.get("expected_batch") is not None else logical_batch)
@@ -95,7 +98,7 @@ def _divisor(eng, dp, phase=None, logical_batch=None):
         return float(dp["expected_batch"])
     if phase is not None:
         return int(logical_batch)
-    return eng.N
+    return eng.N // int(dp.get("views", 1))       # (records under augmentation multiplicity)
 
 
 def _sync_moments(root):

@@ -16,7 +16,11 @@ second then counts the EXPECTED batch.  --dp_micro_batches K (train.py's flag) r
 1 / K of the batch or capacity (primia_amd.dp_micro); ms per step is then per LOGICAL step.  --dp_clip adaptive (train.py's
 flag) gives every mode's engine an adaptive clipping norm (primia_amd.dp_clip, its defaults); a mode named "eager:adaptive"
 or "graph:adaptive" has one whatever the flag says, so `--modes graph,graph:adaptive` alternates the fixed and the adaptive
-loop in one session, and the line then carries each such mode's final C.  With --dp the line also
+loop in one session, and the line then carries each such mode's final C.  --dp_augmult M (train.py's flag, with
+--dp_sampling poisson) gives every record M views: capacity and expected batch are divided by M, so the engine keeps its
+slots and a step does the same kernel work on M times fewer records; a mode with the suffix ":mM" (graph:m4) has M views
+whatever the flag says, so `--modes graph,graph:m4` alternates the two in one session.  --capacity C fixes the capacity (in
+slots of the M = 1 loop) instead of deriving it from --planned_steps.  With --dp the line also
 carries the engine's slots and, per mode, the peak of torch.cuda.max_memory_allocated() over what was allocated before that
 mode's engine was built (the batches, the records, an earlier mode's engine), read after the mode's warm-up: the engine,
 its DP buffers and, graphed, the graphs' pools.  Needs a GPU (there is no CPU path)."""
@@ -52,6 +56,8 @@ def main():
     ap.add_argument("--planned_steps", type=int, default=280, help="--dp_sampling poisson: steps the capacity is sized for")
     ap.add_argument("--dp_micro_batches", type=int, default=1, help="with --dp: train.py's --dp_micro_batches")
     ap.add_argument("--dp_clip", choices=("fixed", "adaptive"), default="fixed", help="with --dp: train.py's --dp_clip")
+    ap.add_argument("--dp_augmult", type=int, default=1, help="with --dp --dp_sampling poisson: train.py's --dp_augmult")
+    ap.add_argument("--capacity", type=int, default=0, help="--dp_sampling poisson: the capacity, instead of the accountant's")
     a = ap.parse_args()
     poisson = a.dp and a.dp_sampling == "poisson"
     K = a.dp_micro_batches if a.dp else 1
@@ -75,7 +81,7 @@ def main():
         from primia_amd.dp_sampling import DeviceSampler, PoissonLoader
 
         q = dp_accountant.q_of_threshold(dp_accountant.threshold_for((a.batch, a.records)))
-        capacity = dp_accountant.capacity_for(a.records, q, a.planned_steps, 1e-5, sigma=1.3)
+        capacity = a.capacity or dp_accountant.capacity_for(a.records, q, a.planned_steps, 1e-5, sigma=1.3)
         records = torch.cat([bufs[i % a.buffers][0] for i in range(-(-a.records // a.batch))])[:a.records].contiguous()
         labels = torch.cat([bufs[i % a.buffers][1] for i in range(-(-a.records // a.batch))])[:a.records].contiguous()
 
@@ -91,16 +97,25 @@ def main():
             def __iter__(self):
                 return (self.pl.draw() for _ in range(self.count))
     modes = a.modes.split(",")
+    views_of = {}
     for m in modes:
+        base, _, suffix = m.partition(":m")
+        views_of[m] = int(suffix) if suffix.isdigit() else (a.dp_augmult if a.dp else 1)
+        if suffix.isdigit():
+            m = base
         if m not in ("eager", "graph") and not (a.dp and m in ("eager:adaptive", "graph:adaptive")):
-            raise SystemExit(f"mode {m!r}: eager or graph, with --dp also eager:adaptive or graph:adaptive")
+            raise SystemExit(f"mode {m!r}: eager or graph, with --dp also eager:adaptive or graph:adaptive, and :mM")
+    if any(v < 1 or (v > 1 and not poisson) for v in views_of.values()):
+        raise SystemExit("--dp_augmult / a :mM mode: at least 1, and only with --dp --dp_sampling poisson")
     runs, peak = {}, {}
     for m in modes:
         torch.manual_seed(42)
         torch.cuda.synchronize()
         held = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
-        eng = ResNet18Engine(-(-capacity // K), 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
+        views = views_of[m]
+        cap_m = capacity // views               # records: the engine keeps its slots
+        eng = ResNet18Engine(-(-cap_m // K) * views, 3, 3, a.size, "max", dtype=torch.bfloat16, device=dev,
                              norm=a.dp_norm if a.dp else "batch")
         eng.init_weights()
         if a.dp:
@@ -110,14 +125,17 @@ def main():
                 from primia_amd.dp_noise import DeviceNoise
 
                 eng.dp_noise = DeviceNoise(dev)
-            if a.dp_clip == "adaptive" or m.endswith(":adaptive"):
+            if a.dp_clip == "adaptive" or ":adaptive" in m:
                 from primia_amd.dp_clip import AdaptiveClip
 
                 eng.dp_clip = AdaptiveClip(dev, sigma_b=a.batch / 20.0)
                 eng.dp_clip.tensors()
             if poisson:
-                pl = PoissonLoader(records, labels, a.batch, capacity, DeviceSampler(dev), micro_batches=K)
+                pl = PoissonLoader(records, labels, max(1, a.batch // views), cap_m, DeviceSampler(dev), micro_batches=K,
+                                   views=views)
                 eng.dp_params["expected_batch"] = pl.expected_batch
+                if views > 1:
+                    eng.dp_params["views"] = views
         args = SimpleNamespace(optimizer="SGD", lr=1e-4, weight_decay=5e-4, log_interval=10 ** 9, mixup=False,
                                hip_graph=m.startswith("graph"))
         opt = EngineOptimizer.from_args(eng, args)
@@ -147,13 +165,15 @@ def main():
         out["dp_sampling"] = a.dp_sampling
         out["dp_clip"] = {m: runs[m][0].dp_clip.value() if runs[m][0].dp_clip is not None else "fixed" for m in modes}
         out.update(dp_micro_batches=K, engine_slots=runs[modes[0]][0].N, peak_bytes_over_held=peak)
+        out["dp_augmult"] = views_of
         if poisson:
             out.update(records=a.records, capacity=capacity, planned_steps=a.planned_steps,
                        overflow_events={m: runs[m][4].pl.sampler.overflow_events() for m in modes})
     for m in modes:
         ts = runs[m][3]
         med = statistics.median(ts)
-        out[m] = {"ms_per_step": round(med, 3), "images_per_sec": round(a.batch / med * 1e3, 1),
+        # (M views: a.batch // M records per step, each M images)
+        out[m] = {"ms_per_step": round(med, 3), "images_per_sec": round(a.batch // views_of[m] * views_of[m] / med * 1e3, 1),
                   "ms_per_step_runs": [round(t, 3) for t in ts]}
     print(json.dumps(out))
 

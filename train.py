@@ -7,7 +7,8 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
         [--unencrypted_aggregation] [--data_dir DIR|synthetic] [--cuda] [--resume_checkpoint P] \
         [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N] \
         [--dp_norm {group,frozen}] [--dp_sampling {shuffle,poisson}] [--dp_delta D] [--dp_micro_batches K] \
-        [--dp_clip {fixed,adaptive}] [--dp_clip_quantile G] [--dp_clip_lr R] [--dp_clip_sigma S] [--dp_clip_init C]
+        [--dp_clip {fixed,adaptive}] [--dp_clip_quantile G] [--dp_clip_lr R] [--dp_clip_sigma S] [--dp_clip_init C] \
+        [--dp_augmult M]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -34,6 +35,10 @@ logical batch larger than one engine's activations allow, with one noise draw an
 (primia_amd.dp_clip): each step releases a noisy count, the gradient noise is raised to pay for it, and the configured
 noise multiplier — what the ledger is given — stays what it was.  C and the last released fraction are printed per client
 after every epoch and travel in the checkpoint (`dp_clip`).
+`--dp_augmult M` (with --dp_sampling poisson; augmentation multiplicity, De et al. 2022) gives every sampled record M
+augmented views — stored walks of a federated client, M passes through the training transform otherwise — averages their
+gradients and clips the average once: the sensitivity, the sampling rate and the reported (epsilon, delta) are those of
+M = 1, the engine holds M times as many slots (combine with --dp_micro_batches).
 
 `main(args, verbose, optuna_trial, cmd_args)` returns the best validation MCC like the reference's.
 """
@@ -238,6 +243,9 @@ class DPOptions:
     # --dp_clip_sigma or batch_size / 20 — the step's divisor B in shuffle and in Poisson mode alike, and a loader's ragged
     # last batch keeps it — and must exceed sigma / 2, else the run ends in from_args
     clip: Optional[dict] = None
+    # M of --dp_augmult: every Poisson-sampled record fills M consecutive slots with augmented views whose gradients are
+    # averaged and clipped once (engine.dp_loss_backward(views=M)); batches, capacities and the ledger count records
+    augmult: int = 1
 
     @classmethod
     def from_args(cls, args, cmd_args):
@@ -253,7 +261,15 @@ class DPOptions:
 
         noise, norm, sampling = flag("dp_noise", "torch"), flag("dp_norm", "group"), flag("dp_sampling", "shuffle")
         micro, adaptive = max(1, int(flag("dp_micro_batches", 1))), flag("dp_clip", "fixed") == "adaptive"
+        augmult = int(flag("dp_augmult", 1))
+        if augmult < 1:
+            raise SystemExit("--dp_augmult {:d}: the views of a record, at least 1".format(augmult))
+        if on and augmult > 1 and sampling != "poisson":
+            raise SystemExit("--dp_augmult {:d} needs --dp_sampling poisson: shuffled loaders hand out samples, not records "
+                             "with their augmented views".format(augmult))
         if not on:
+            if augmult > 1:
+                no_effect("--dp_augmult {:d}".format(augmult), "every sample is one view")
             if noise == "chacha":
                 no_effect("--dp_noise chacha", "no noise is applied")
             if norm == "frozen":
@@ -289,7 +305,7 @@ class DPOptions:
             clip = dict(params, z_delta=z_delta)
         return cls(on=on, noise=noise, noise_seed=flag("debug_dp_noise_seed", None), norm=norm,
                    poisson=on and sampling == "poisson", delta=float(flag("dp_delta", 1e-5)), micro=micro if on else 1,
-                   sigma=sigma, clip=clip)
+                   sigma=sigma, clip=clip, augmult=augmult if on else 1)
 
 
 def micro_batch_size(slots, k, poisson):
@@ -395,6 +411,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             epochs_ahead = max(0, args.epochs - int(resume_state["epoch"]) + 1)      # (the saved epoch is run again)
     reps = args.repetitions_dataset if "repetitions_dataset" in vars(args) else 1
 
+    augmult_warned = []     # (the warning about repeated stored views is given once)
+
     def poisson_loader(name, base, client):
         """The Poisson-sampled form of a client's loader: its records, an expected batch of batch_size, the capacity the
         planned number of steps needs, a sampler and a ledger of the client's own (nonce rule: make_engine's)."""
@@ -417,9 +435,18 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             led.segments, led.capacities, led.overflow_events = old.segments, old.capacities, old.overflow_events
         if dp.micro > 1 and rank == 0:
             print("dp_micro_batches: {:s}'s steps of capacity {:d} run as K = {:d} passes on an engine of M = {:d} "
-                  "slots".format(name, capacity, dp.micro, micro_batch_size(capacity, dp.micro, True)))
+                  "slots".format(name, capacity, dp.micro, micro_batch_size(capacity, dp.micro, True) * dp.augmult))
+        if dp.augmult > 1:
+            stored = not hasattr(base, "images")      # (stored walks; a transforming loader draws fresh views)
+            if stored and dp.augmult > fed_reps and not augmult_warned:
+                augmult_warned.append(name)
+                warn("--dp_augmult {:d} with {:d} stored walk(s) per record: the views repeat stored copies, and identical "
+                     "views add nothing to the average".format(dp.augmult, fed_reps))
+            if rank == 0:
+                print("dp_augmult: {:s}: capacity {:d} records, {:d} views per record, engine of {:d} slots".format(
+                    name, capacity, dp.augmult, micro_batch_size(capacity, dp.micro, True) * dp.augmult))
         return dps.from_loader(base, args.batch_size, capacity, sampler, fed_reps, (channels, size, size),
-                               micro_batches=dp.micro)
+                               micro_batches=dp.micro, views=dp.augmult)
 
     def synthetic_records(batches, seed):
         sl = SyntheticLoader(batches, args.batch_size, size, num_classes, device, seed, channels)
@@ -432,7 +459,9 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         # PrivacyEngine, so the network is built with GroupNorm — or (--dp_norm frozen) BatchNorm is applied with its
         # running statistics held fixed, which keeps samples independent too — and every step clips / noises per sample
         # (--dp_micro_batches K: the engine holds one PASS, 1 / K of the loaders' batch or capacity)
-        slots = micro_batch_size(args.batch_size if batch is None else batch, dp.micro, dp.poisson)
+        # (--dp_augmult M: batch, capacity and M-of-a-pass count records; the engine holds M slots per record)
+        views = dp.augmult if expected_batch is not None else 1     # (the model that only holds the aggregate: no records)
+        slots = micro_batch_size(args.batch_size if batch is None else batch, dp.micro, dp.poisson) * views
         eng = ResNet18Engine(slots, num_classes, channels, size, args.pooling_type,
                              dtype=dtype, device=device, norm=dp.norm if dp.on else "batch")
         if dp.on:
@@ -440,6 +469,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             eng.dp_params = {"max_grad_norm": 1.0, "noise_multiplier": dp.sigma}
             if expected_batch is not None:      # padded Poisson batches: masked loss / clip, the noised sum over q * n
                 eng.dp_params["expected_batch"] = float(expected_batch)
+            if views > 1:
+                eng.dp_params["views"] = views
             if dp.noise == "chacha":
                 # a key of its own from the OS entropy pool per engine; the nonce is the client index (the model that
                 # holds a federated run's aggregate never takes a step: it gets the last nonce; a vanilla run's one model
@@ -802,6 +833,10 @@ def build_parser():
             raise argparse.ArgumentTypeError("at least 1 pass per step")
         return k
 
+    parser.add_argument("--dp_augmult", type=int, default=1, metavar="M",
+                        help="with differentially_private = yes and --dp_sampling poisson: augmentation multiplicity — every "
+                             "sampled record contributes the average gradient of M augmented views, clipped once (De et al. "
+                             "2022).  The privacy cost is that of M = 1; the engine holds M times as many slots")
     parser.add_argument("--dp_micro_batches", type=passes, default=1, metavar="K",
                         help="differentially_private = yes: run every step as K passes of (forward, per-sample clip, "
                              "clipped sum) on an engine of 1 / K of the batch (shuffle: batch_size must be a multiple of K) "
