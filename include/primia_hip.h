@@ -190,13 +190,13 @@ int primia_stem_conv_wgrad(const void* x_padded, const void* dy, float* dw_acc, 
                            primia_stream_t stream);
 /* ... without atomics (see primia_conv2d_wgrad_ws): workspace from primia_stem_conv_wgrad_ws_bytes (0: this shape
  * takes the accumulate path, dw_acc must then be zeroed by the caller as for primia_stem_conv_wgrad). */
-int primia_stem_conv_wgrad_persample_sqnorm(const void* x_padded, const void* dy, double* sqnorm, int N, int H, int W,
-                                            int dtype, primia_stream_t stream);   /* DP-SGD norm pass, padded input */
-/* ... per RECORD of `views` consecutive images (augmentation multiplicity; clip rule of train.py:325-334): one block per
- * record walks its images, sqnorm[r] += ||sum_{n in record r} dW_n||_F^2.  views = 1 is the call above.  PRIMIA_ERR_ARG for
- * views < 1 or N % views != 0. */
+/* DP-SGD norm pass on the padded input, per RECORD of `views` consecutive images (augmentation multiplicity; a sample is
+ * a record of one view; clip rule of train.py:325-334): one block per record walks its images, sqnorm[r] +=
+ * ||sum_{n in record r} dW_n||_F^2.  PRIMIA_ERR_ARG for views < 1 or N % views != 0. */
 int primia_stem_conv_wgrad_record_sqnorm(const void* x_padded, const void* dy, double* sqnorm, int N, int H, int W,
                                          int views, int dtype, primia_stream_t stream);
+int primia_stem_conv_wgrad_persample_sqnorm(const void* x_padded, const void* dy, double* sqnorm, int N, int H, int W,
+                                            int dtype, primia_stream_t stream);   /* views = 1 of ..._record_sqnorm */
 int64_t primia_stem_conv_wgrad_ws_bytes(int N, int H, int W);
 int primia_stem_conv_wgrad_ws(const void* x_padded, const void* dy, float* dw_acc, void* ws, int64_t ws_bytes, int N,
                               int H, int W, int dtype, primia_stream_t stream);
@@ -221,18 +221,17 @@ int primia_stem_conv_wgrad_ws(const void* x_padded, const void* dy, float* dw_ac
  *   15 the stem's (stem_conv_wgrad_kernel on the padded bf16 input, conv_wgrad_kernel<STEM> otherwise) */
 int primia_conv_kernel_id(const primia_conv_desc* d, int pass, int dtype);
 int primia_conv_wgrad_kernel_id(const primia_conv_desc* d, int dtype);
-/* ... and the kernel that serves primia_conv2d_wgrad_persample_sqnorm (the DP-SGD norm pass, train.py:325-334) for `d`:
+/* ... and the kernel that serves primia_conv2d_wgrad_record_sqnorm (the DP-SGD norm pass of a record of `views`
+ * consecutive images, train.py:325-334; a sample is a record of one view) for `d`:
  *   21 dp_ghost_sqnorm7_kernel (7x7 outputs, two Gram matrices per sample)   22 dp_ghost_sqnorm7s2_kernel (stride 2)
  *   23 dp_ghost_sqnorm14_kernel   24 conv_wgrad_patch33_kernel, one block per (image, slab)
  *   25 conv_wgrad_patch33_kernel, whole images per half-block   26 conv_wgrad_tap_kernel, whole images per block
- *   13 / 14 / 15 as above */
-int primia_conv_wgrad_persample_kernel_id(const primia_conv_desc* d, int dtype);
-/* ... and the kernel that serves primia_conv2d_wgrad_record_sqnorm (DP-SGD with augmentation multiplicity: the norm pass
- * of a record of `views` consecutive images; clip rule of train.py:325-334) for `d`: the ids above, with the tile completed
- * over a record before its squares are added.  views = 1 answers as primia_conv_wgrad_persample_kernel_id does; for
- * views > 1 the Gram-matrix kernels (21 - 23) are never named: their shapes go to the patch kernel (24 / 25).
- * PRIMIA_ERR_ARG for views < 1 or a batch that is not a whole number of records. */
+ *   13 / 14 / 15 as above
+ * with the tile completed over a record before its squares are added.  For views > 1 the Gram-matrix kernels (21 - 23)
+ * are never named: their shapes go to the patch kernel (24 / 25).  PRIMIA_ERR_ARG for views < 1 or a batch that is not a
+ * whole number of records. */
 int primia_conv_wgrad_record_kernel_id(const primia_conv_desc* d, int dtype, int views);
+int primia_conv_wgrad_persample_kernel_id(const primia_conv_desc* d, int dtype);   /* views = 1 of ..._record_kernel_id */
 
 int primia_conv_stat_slots(void);
 /* Slots the kernel chosen for `d` writes: kernels that own whole output rows (layer1's 64->64 convolution)
@@ -345,20 +344,19 @@ int primia_conv2d_wgrad_group_ws(const primia_conv_desc* d, int n, const void* x
  * image n's gradient in slab n. */
 int primia_conv2d_wgrad_persample(const primia_conv_desc* d, const void* x, const void* dy,
                                   float* dw_ps, int dtype, primia_stream_t stream);
-/* The DP-SGD norm pass without the per-sample gradients themselves: sqnorm[n] += ||dW_n||_F^2 (fp64,
- * accumulated across calls, i.e. across layers).  Every kernel block of the per-sample form holds one
- * sample's complete gradient tile in registers, so the squares are summed there and the N x |W| slab
- * (11 GB per step for ResNet-18 at batch 256) is never written, zeroed or re-read. */
-int primia_conv2d_wgrad_persample_sqnorm(const primia_conv_desc* d, const void* x, const void* dy,
-                                         double* sqnorm, int dtype, primia_stream_t stream);
-/* The norm pass of DP-SGD with augmentation multiplicity (De et al. 2022; the clip rule is still pytorch-dp's,
- * train.py:325-334, applied to a record instead of a sample): record r = images r * views .. r * views + views - 1, and
- * sqnorm[r] += ||sum_{n in record r} dW_n||_F^2 — the cross terms between a record's images included, which no sum of
- * per-image norms yields.  Every kernel family completes its tile over the record's images before it adds the squares;
- * sqnorm has N / views entries.  views = 1 dispatches exactly as primia_conv2d_wgrad_persample_sqnorm.  PRIMIA_ERR_ARG
- * for views < 1 or N % views != 0. */
+/* The DP-SGD norm pass without the per-sample gradients themselves, per RECORD of `views` consecutive images (a sample
+ * is a record of one view; views > 1 is augmentation multiplicity, De et al. 2022 — the clip rule is still pytorch-dp's,
+ * train.py:325-334, applied to a record): record r = images r * views .. r * views + views - 1, and
+ * sqnorm[r] += ||sum_{n in record r} dW_n||_F^2 (fp64, accumulated across calls, i.e. across layers) — the cross terms
+ * between a record's images included, which no sum of per-image norms yields.  Every kernel block holds one record's
+ * complete gradient tile in registers (completed over the record's images), so the squares are summed there and the
+ * N x |W| slab (11 GB per step for ResNet-18 at batch 256) is never written, zeroed or re-read.  sqnorm has N / views
+ * entries.  PRIMIA_ERR_ARG for views < 1 or N % views != 0. */
 int primia_conv2d_wgrad_record_sqnorm(const primia_conv_desc* d, const void* x, const void* dy, double* sqnorm, int views,
                                       int dtype, primia_stream_t stream);
+/* views = 1 of primia_conv2d_wgrad_record_sqnorm: sqnorm[n] += ||dW_n||_F^2 */
+int primia_conv2d_wgrad_persample_sqnorm(const primia_conv_desc* d, const void* x, const void* dy,
+                                         double* sqnorm, int dtype, primia_stream_t stream);
 
 /* DP-SGD where a layer's per-sample gradients are small (the stem: 64 KiB per sample; layer1's 64 -> 64 convs: 144 KiB):
  * the norm pass KEEPS every sample's complete tile next to adding its squares, and the clipped sum  sum_n clip_n g_n  is
@@ -721,18 +719,18 @@ int primia_gn_relu_maxpool_bwd(const void* y, const void* pooled, const void* dp
                                const float* gamma, const float* beta, const float* save_mean, const float* save_invstd,
                                float* ps_dgamma, float* ps_dbeta, int N, int H, int W, int C, int G, void* workspace,
                                int64_t workspace_bytes, int dtype, primia_stream_t stream);
-/* sq_acc[n] += sum_j x[n][j]^2 (fp64): per-sample squared gradient norm, accumulated layer by layer. */
-int primia_persample_sqnorm(const float* x, int N, int64_t per_sample, double* sq_acc,
-                            primia_stream_t stream);
-/* ... for `count` small tensors x_k [N][width_k] in one launch (DEVICE arrays of pointers / widths) */
-int primia_persample_sqnorm_many(const void* xs_dev, const int* widths_dev, int count, int N, double* sq_acc,
-                                 primia_stream_t stream);
-/* The record forms (DP-SGD with augmentation multiplicity, clip rule of train.py:325-334): rows r * views .. + views - 1
- * of x are one record's; sq_acc[r] += sum_j (sum_v x[r * views + v][j])^2, the row sum and the squares in fp64.
- * sq_acc has N / views entries; PRIMIA_ERR_ARG for views < 1 or N % views != 0. */
+/* Squared gradient norm per record, accumulated layer by layer (clip rule of train.py:325-334): rows r * views ..
+ * + views - 1 of x are one record's (a sample is a record of one view); sq_acc[r] += sum_j (sum_v x[r * views + v][j])^2,
+ * the row sum and the squares in fp64.  sq_acc has N / views entries; PRIMIA_ERR_ARG for views < 1 or N % views != 0. */
 int primia_record_sqnorm(const float* x, int N, int64_t per_sample, int views, double* sq_acc, primia_stream_t stream);
+/* ... for `count` small tensors x_k [N][width_k] in one launch (DEVICE arrays of pointers / widths) */
 int primia_record_sqnorm_many(const void* xs_dev, const int* widths_dev, int count, int N, int views, double* sq_acc,
                               primia_stream_t stream);
+/* views = 1 of the two above: sq_acc[n] += sum_j x[n][j]^2 */
+int primia_persample_sqnorm(const float* x, int N, int64_t per_sample, double* sq_acc,
+                            primia_stream_t stream);
+int primia_persample_sqnorm_many(const void* xs_dev, const int* widths_dev, int count, int N, double* sq_acc,
+                                 primia_stream_t stream);
 /* clip_slots[n] = clip[n / views]: a record's clip factor on each of its slots, so that primia_scale_rows_many and
  * primia_weighted_colsum[_many] run unchanged on the N slots. */
 int primia_dp_expand_clip(const float* clip, float* clip_slots, int N, int views, primia_stream_t stream);
@@ -860,8 +858,9 @@ int primia_gather_batch(const void* data, int64_t row_elems, int64_t n_rows, con
 /* The same for records of `views` stored augmented walks (augmentation multiplicity): `data` / `targets` hold
  * `repetitions` walks of n_rows rows each, and out[s * views + v] = data[((first_walk + v) % repetitions) * n_rows + idx[s]]
  * with out_targets alike, for 0 <= s < capacity, 0 <= v < views; a padded or out-of-range idx[s] gives `views` zero rows
- * with target -1.  One launch, no host synchronisation: capturable.  Alignment rules of primia_gather_batch;
- * PRIMIA_ERR_ARG also for views < 1, repetitions < 1 or first_walk < 0. */
+ * with target -1.  One launch, no host synchronisation: capturable.  primia_gather_batch is one walk and one view of the
+ * same kernel, with row_offset added to the row; alignment rules as there.  PRIMIA_ERR_ARG also for views < 1,
+ * repetitions < 1 or first_walk < 0. */
 int primia_gather_records(const void* data, int64_t row_elems, int64_t n_rows, const int64_t* targets, const int64_t* idx,
                           int64_t first_walk, int repetitions, int views, void* out, int64_t* out_targets, int capacity,
                           int dtype, primia_stream_t stream);

@@ -523,25 +523,21 @@ extern "C" int primia_stem_conv_wgrad(const void* x_padded, const void* dy, floa
     return stem_conv_wgrad_impl(x_padded, dy, dw_acc, nullptr, 0, N, H, W, dtype, stream);
 }
 
-// DP-SGD norm pass for conv1 on the padded input: sqnorm[n] += ||dW_n||_F^2 (see primia_conv2d_wgrad_persample_sqnorm);
-// PRIMIA_ERR_UNSUPPORTED where the halo kernel does not serve the shape (caller uses the generic form on the
-// unpadded input)
-extern "C" int primia_stem_conv_wgrad_persample_sqnorm(const void* x_padded, const void* dy, double* sqnorm, int N, int H,
-                                                       int W, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(x_padded && dy && sqnorm && N > 0 && H > 0 && W > 0);
-    if (dtype != PRIMIA_BF16) return PRIMIA_ERR_UNSUPPORTED;
-    return stem_wgrad_halo_dispatch((const bf16*)x_padded, (const bf16*)dy, nullptr, N, H, W, (hipStream_t)stream, nullptr,
-                                    0, sqnorm);
-}
-
-// ... per record of `views` consecutive images: one block per record (see primia_conv2d_wgrad_record_sqnorm)
+// DP-SGD norm pass for conv1 on the padded input, one block per record of `views` consecutive images: sqnorm[r] +=
+// ||sum_{n in r} dW_n||_F^2 (see primia_conv2d_wgrad_record_sqnorm); PRIMIA_ERR_UNSUPPORTED where the halo kernel does
+// not serve the shape (caller uses the generic form on the unpadded input)
 extern "C" int primia_stem_conv_wgrad_record_sqnorm(const void* x_padded, const void* dy, double* sqnorm, int N, int H,
                                                     int W, int views, int dtype, primia_stream_t stream) {
     PRIMIA_REQUIRE(x_padded && dy && sqnorm && N > 0 && H > 0 && W > 0 && views >= 1 && N % views == 0);
-    if (views == 1) return primia_stem_conv_wgrad_persample_sqnorm(x_padded, dy, sqnorm, N, H, W, dtype, stream);
     if (dtype != PRIMIA_BF16) return PRIMIA_ERR_UNSUPPORTED;
     return stem_wgrad_halo_dispatch((const bf16*)x_padded, (const bf16*)dy, nullptr, N, H, W, (hipStream_t)stream, nullptr,
                                     0, sqnorm, views);
+}
+
+// views = 1 of primia_stem_conv_wgrad_record_sqnorm
+extern "C" int primia_stem_conv_wgrad_persample_sqnorm(const void* x_padded, const void* dy, double* sqnorm, int N, int H,
+                                                       int W, int dtype, primia_stream_t stream) {
+    return primia_stem_conv_wgrad_record_sqnorm(x_padded, dy, sqnorm, N, H, W, 1, dtype, stream);
 }
 
 extern "C" int64_t primia_stem_conv_wgrad_ws_bytes(int N, int H, int W) {
@@ -698,19 +694,19 @@ extern "C" int primia_conv2d_wgrad_persample(const primia_conv_desc* d, const vo
     return conv2d_wgrad_impl(d, x, dy, dw_ps, kWgPersampleTiles, dtype, stream);
 }
 
-extern "C" int primia_conv2d_wgrad_persample_sqnorm(const primia_conv_desc* d, const void* x, const void* dy,
-                                                    double* sqnorm, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(sqnorm);
-    return conv2d_wgrad_impl(d, x, dy, nullptr, kWgPersampleSqnorm, dtype, stream, sqnorm);
-}
-
-// DP-SGD with augmentation multiplicity: the norm pass per RECORD of `views` consecutive images — the same kernels with
-// the tile completed over the record (wgrad_route takes the record size from p.rec_views)
+// DP-SGD norm pass per RECORD of `views` consecutive images (augmentation multiplicity; a sample is a record of one
+// view): the weight-gradient kernels with the tile completed over the record (wgrad_route takes the record size from
+// p.rec_views)
 extern "C" int primia_conv2d_wgrad_record_sqnorm(const primia_conv_desc* d, const void* x, const void* dy, double* sqnorm,
                                                  int views, int dtype, primia_stream_t stream) {
     PRIMIA_REQUIRE(d && sqnorm && views >= 1 && d->N > 0 && d->N % views == 0);
-    if (views == 1) return primia_conv2d_wgrad_persample_sqnorm(d, x, dy, sqnorm, dtype, stream);
     return conv2d_wgrad_impl(d, x, dy, nullptr, kWgPersampleSqnorm, dtype, stream, sqnorm, nullptr, 0, views);
+}
+
+// views = 1 of primia_conv2d_wgrad_record_sqnorm
+extern "C" int primia_conv2d_wgrad_persample_sqnorm(const primia_conv_desc* d, const void* x, const void* dy,
+                                                    double* sqnorm, int dtype, primia_stream_t stream) {
+    return primia_conv2d_wgrad_record_sqnorm(d, x, dy, sqnorm, 1, dtype, stream);
 }
 
 static int wgrad_kernel_of(const primia_conv_desc* d, int dtype, WgradForm form, int rec_views = 1) {
@@ -726,8 +722,9 @@ extern "C" int primia_conv_wgrad_record_kernel_id(const primia_conv_desc* d, int
     return wgrad_kernel_of(d, dtype, kWgPersampleSqnorm, views);
 }
 
+// views = 1 of primia_conv_wgrad_record_kernel_id
 extern "C" int primia_conv_wgrad_persample_kernel_id(const primia_conv_desc* d, int dtype) {
-    return wgrad_kernel_of(d, dtype, kWgPersampleSqnorm);
+    return primia_conv_wgrad_record_kernel_id(d, dtype, 1);
 }
 
 extern "C" int primia_conv_wgrad_kernel_id(const primia_conv_desc* d, int dtype) {

@@ -82,39 +82,20 @@ __global__ __launch_bounds__(kSelThreads) void poisson_select_kernel(ChaChaKey k
     }
 }
 
-// One 16-byte chunk per thread and step; a slot's chunks are split over `parts` blocks.
-__global__ __launch_bounds__(256) void gather_batch_kernel(const u32x4* __restrict__ data, int64_t row_chunks,
-                                                           int64_t n_rows, const int64_t* __restrict__ targets,
-                                                           const int64_t* __restrict__ idx, int64_t row_offset,
-                                                           u32x4* __restrict__ out, int64_t* __restrict__ out_targets,
-                                                           int parts) {
-    const int slot = blockIdx.x / parts, part = blockIdx.x % parts;
-    const int64_t r = idx[slot];
-    const bool valid = r >= 0 && r < n_rows;    // everything else is padding: nothing is read
-    u32x4* dst = out + (int64_t)slot * row_chunks;
-    const int64_t c0 = (int64_t)part * 256 + threadIdx.x, step = (int64_t)parts * 256;
-    if (valid) {
-        const u32x4* src = data + (row_offset + r) * row_chunks;
-        for (int64_t c = c0; c < row_chunks; c += step) dst[c] = src[c];
-    } else {
-        const u32x4 zero = {0u, 0u, 0u, 0u};
-        for (int64_t c = c0; c < row_chunks; c += step) dst[c] = zero;
-    }
-    if (part == 0 && threadIdx.x == 0) out_targets[slot] = valid ? targets[row_offset + r] : -1;
-}
-
-// Records of stored augmented walks: output slot o = s * views + v is walk (first_walk + v) % repetitions of record idx[s]
-// (data = `repetitions` walks of n_rows rows); padding as gather_batch_kernel
-__global__ __launch_bounds__(256) void gather_records_kernel(const u32x4* __restrict__ data, int64_t row_chunks,
-                                                             int64_t n_rows, const int64_t* __restrict__ targets,
-                                                             const int64_t* __restrict__ idx, int64_t first_walk,
-                                                             int repetitions, int views, u32x4* __restrict__ out,
-                                                             int64_t* __restrict__ out_targets, int parts) {
+// One 16-byte chunk per thread and step; a slot's chunks are split over `parts` blocks.  Output slot o = s * views + v is
+// row base + ((first_walk + v) % repetitions) * n_rows + idx[s] of `data`: view v of record idx[s] among `repetitions`
+// stored walks of n_rows rows — or, with one walk and one view, row idx[s] of the split that starts at `base`.
+__global__ __launch_bounds__(256) void gather_rows_kernel(const u32x4* __restrict__ data, int64_t row_chunks,
+                                                          int64_t n_rows, const int64_t* __restrict__ targets,
+                                                          const int64_t* __restrict__ idx, int64_t base,
+                                                          int64_t first_walk, int repetitions, int views,
+                                                          u32x4* __restrict__ out, int64_t* __restrict__ out_targets,
+                                                          int parts) {
     const int o = blockIdx.x / parts, part = blockIdx.x % parts;
     const int s = o / views, v = o - s * views;
     const int64_t r = idx[s];
-    const bool valid = r >= 0 && r < n_rows;
-    const int64_t row = ((first_walk + v) % repetitions) * n_rows + r;
+    const bool valid = r >= 0 && r < n_rows;    // everything else is padding: nothing is read
+    const int64_t row = base + ((first_walk + v) % repetitions) * n_rows + r;
     u32x4* dst = out + (int64_t)o * row_chunks;
     const int64_t c0 = (int64_t)part * 256 + threadIdx.x, step = (int64_t)parts * 256;
     if (valid) {
@@ -206,39 +187,36 @@ extern "C" int primia_poisson_select(uint64_t k0, uint64_t k1, uint64_t k2, uint
     return launch_status();
 }
 
-extern "C" int primia_gather_batch(const void* data, int64_t row_elems, int64_t n_rows, const int64_t* targets,
-                                   const int64_t* idx, int64_t row_offset, void* out, int64_t* out_targets, int capacity,
-                                   int dtype, primia_stream_t st) {
+static int gather_rows(const void* data, int64_t row_elems, int64_t n_rows, const int64_t* targets, const int64_t* idx,
+                       int64_t base, int64_t first_walk, int repetitions, int views, void* out, int64_t* out_targets,
+                       int capacity, int dtype, primia_stream_t st) {
     PRIMIA_REQUIRE(data && targets && idx && out && out_targets);
-    PRIMIA_REQUIRE(row_elems > 0 && n_rows >= 0 && row_offset >= 0 && capacity > 0);
+    PRIMIA_REQUIRE(row_elems > 0 && n_rows >= 0 && base >= 0 && first_walk >= 0 && repetitions >= 1 && views >= 1 &&
+                   capacity > 0);
     PRIMIA_REQUIRE(dtype == PRIMIA_F32 || dtype == PRIMIA_BF16);
     const int64_t per_chunk = dtype == PRIMIA_F32 ? 4 : 8;
     PRIMIA_REQUIRE(row_elems % per_chunk == 0 && ((uintptr_t)data & 15) == 0 && ((uintptr_t)out & 15) == 0);
     const int64_t row_chunks = row_elems / per_chunk;
     int64_t parts = (row_chunks + 1023) / 1024;      // four chunks per thread where the row is long enough
     if (parts > 64) parts = 64;
-    PRIMIA_REQUIRE((int64_t)capacity * parts <= INT32_MAX);
-    gather_batch_kernel<<<(unsigned)(capacity * parts), 256, 0, (hipStream_t)st>>>(
-        (const u32x4*)data, row_chunks, n_rows, targets, idx, row_offset, (u32x4*)out, out_targets, (int)parts);
+    PRIMIA_REQUIRE((int64_t)capacity * views * parts <= INT32_MAX);
+    gather_rows_kernel<<<(unsigned)(capacity * views * parts), 256, 0, (hipStream_t)st>>>(
+        (const u32x4*)data, row_chunks, n_rows, targets, idx, base, first_walk, repetitions, views, (u32x4*)out,
+        out_targets, (int)parts);
     return launch_status();
+}
+
+extern "C" int primia_gather_batch(const void* data, int64_t row_elems, int64_t n_rows, const int64_t* targets,
+                                   const int64_t* idx, int64_t row_offset, void* out, int64_t* out_targets, int capacity,
+                                   int dtype, primia_stream_t st) {
+    return gather_rows(data, row_elems, n_rows, targets, idx, row_offset, 0, 1, 1, out, out_targets, capacity, dtype, st);
 }
 
 extern "C" int primia_gather_records(const void* data, int64_t row_elems, int64_t n_rows, const int64_t* targets,
                                      const int64_t* idx, int64_t first_walk, int repetitions, int views, void* out,
                                      int64_t* out_targets, int capacity, int dtype, primia_stream_t st) {
-    PRIMIA_REQUIRE(data && targets && idx && out && out_targets);
-    PRIMIA_REQUIRE(row_elems > 0 && n_rows >= 0 && first_walk >= 0 && repetitions >= 1 && views >= 1 && capacity > 0);
-    PRIMIA_REQUIRE(dtype == PRIMIA_F32 || dtype == PRIMIA_BF16);
-    const int64_t per_chunk = dtype == PRIMIA_F32 ? 4 : 8;
-    PRIMIA_REQUIRE(row_elems % per_chunk == 0 && ((uintptr_t)data & 15) == 0 && ((uintptr_t)out & 15) == 0);
-    const int64_t row_chunks = row_elems / per_chunk;
-    int64_t parts = (row_chunks + 1023) / 1024;
-    if (parts > 64) parts = 64;
-    PRIMIA_REQUIRE((int64_t)capacity * views * parts <= INT32_MAX);
-    gather_records_kernel<<<(unsigned)(capacity * views * parts), 256, 0, (hipStream_t)st>>>(
-        (const u32x4*)data, row_chunks, n_rows, targets, idx, first_walk, repetitions, views, (u32x4*)out, out_targets,
-        (int)parts);
-    return launch_status();
+    return gather_rows(data, row_elems, n_rows, targets, idx, 0, first_walk, repetitions, views, out, out_targets,
+                       capacity, dtype, st);
 }
 
 extern "C" int primia_dp_expand_clip(const float* clip, float* clip_slots, int N, int views, primia_stream_t st) {

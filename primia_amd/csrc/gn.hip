@@ -558,43 +558,12 @@ __global__ __launch_bounds__(256) void gn_relu_pool_bwd_apply2x2_kernel(
 }
 
 // ---- DP-SGD per-sample pieces -------------------------------------------------------------------------
-// out[n] += sum_j x[n][j]^2   (block per (sample, chunk); fp64 block sum, one atomic per block)
-__global__ __launch_bounds__(256) void persample_sqnorm_kernel(const float* __restrict__ x, long per, double* out) {
-    const int n = blockIdx.y;
-    const float* p = x + (long)n * per;
-    double s = 0.0;
-    for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < per; j += (long)gridDim.x * 256) {
-        const double v = (double)p[j];
-        s += v * v;
-    }
-    s = wave_sum(s);
-    __shared__ double sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out + n, sh[0] + sh[1] + sh[2] + sh[3]);
-}
-
-// the same for `count` small tensors x_k [N][per_k] in one launch (blockIdx.x = k)
-__global__ __launch_bounds__(256) void persample_sqnorm_many_kernel(const float* const* __restrict__ xs,
-                                                                    const int* __restrict__ pers, double* out) {
-    const int n = blockIdx.y, per = pers[blockIdx.x];
-    const float* p = xs[blockIdx.x] + (long)n * per;
-    double s = 0.0;
-    for (int j = threadIdx.x; j < per; j += 256) {
-        const double v = (double)p[j];
-        s += v * v;
-    }
-    s = wave_sum(s);
-    __shared__ double sh[4];
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out + n, sh[0] + sh[1] + sh[2] + sh[3]);
-}
-
-// The record forms (DP-SGD with augmentation multiplicity): blockIdx.y is a record of `views` consecutive rows, whose sum
-// (fp64) is squared — out[record] += sum_j (sum_v x[record * views + v][j])^2
-__global__ __launch_bounds__(256) void record_sqnorm_kernel(const float* __restrict__ x, long per, int views, double* out) {
-    const int r = blockIdx.y;
+// out[record] += sum_j (sum_v x[record * views + v][j])^2: blockIdx.y is a record of `views` consecutive rows, whose sum
+// (fp64) is squared; a sample is a record of one view (block per (record, chunk); fp64 block sum, one atomic per block).
+// ONE: views == 1 known to the compiler — the same body without the loop over views (profiles/dp_one_pass.txt section 4)
+template <bool ONE>
+__global__ __launch_bounds__(256) void record_sqnorm_kernel(const float* __restrict__ x, long per, int nviews, double* out) {
+    const int r = blockIdx.y, views = ONE ? 1 : nviews;
     const float* p = x + (long)r * views * per;
     double s = 0.0;
     for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < per; j += (long)gridDim.x * 256) {
@@ -609,9 +578,11 @@ __global__ __launch_bounds__(256) void record_sqnorm_kernel(const float* __restr
     if (threadIdx.x == 0) atomicAdd(out + r, sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
+// the same for `count` small tensors x_k [N][per_k] in one launch (blockIdx.x = k)
+template <bool ONE>
 __global__ __launch_bounds__(256) void record_sqnorm_many_kernel(const float* const* __restrict__ xs,
-                                                                 const int* __restrict__ pers, int views, double* out) {
-    const int r = blockIdx.y, per = pers[blockIdx.x];
+                                                                 const int* __restrict__ pers, int nviews, double* out) {
+    const int r = blockIdx.y, per = pers[blockIdx.x], views = ONE ? 1 : nviews;
     const float* p = xs[blockIdx.x] + (long)r * views * per;
     double s = 0.0;
     for (int j = threadIdx.x; j < per; j += 256) {
@@ -985,28 +956,12 @@ int primia_gn_relu_maxpool_bwd(const void* y, const void* pooled, const void* dp
     return PRIMIA_ERR_ARG;
 }
 
-int primia_persample_sqnorm(const float* x, int N, int64_t per_sample, double* sq_acc, primia_stream_t stream) {
-    PRIMIA_REQUIRE(x && sq_acc && N > 0 && per_sample > 0);
-    long b = (per_sample + 255) / 256;
-    if (b > 64) b = 64;
-    persample_sqnorm_kernel<<<dim3((int)b, N), 256, 0, (hipStream_t)stream>>>(x, per_sample, sq_acc);
-    return launch_status();
-}
-
-int primia_persample_sqnorm_many(const void* xs_dev, const int* widths_dev, int count, int N, double* sq_acc,
-                                 primia_stream_t stream) {
-    if (count == 0) return PRIMIA_OK;
-    PRIMIA_REQUIRE(xs_dev && widths_dev && sq_acc && count > 0 && N > 0);
-    persample_sqnorm_many_kernel<<<dim3(count, N), 256, 0, (hipStream_t)stream>>>((const float* const*)xs_dev, widths_dev,
-                                                                                 sq_acc);
-    return launch_status();
-}
-
 int primia_record_sqnorm(const float* x, int N, int64_t per_sample, int views, double* sq_acc, primia_stream_t stream) {
     PRIMIA_REQUIRE(x && sq_acc && N > 0 && per_sample > 0 && views >= 1 && N % views == 0);
     long b = (per_sample + 255) / 256;
     if (b > 64) b = 64;
-    record_sqnorm_kernel<<<dim3((int)b, N / views), 256, 0, (hipStream_t)stream>>>(x, per_sample, views, sq_acc);
+    const auto kern = views == 1 ? record_sqnorm_kernel<true> : record_sqnorm_kernel<false>;
+    kern<<<dim3((int)b, N / views), 256, 0, (hipStream_t)stream>>>(x, per_sample, views, sq_acc);
     return launch_status();
 }
 
@@ -1015,9 +970,19 @@ int primia_record_sqnorm_many(const void* xs_dev, const int* widths_dev, int cou
     PRIMIA_REQUIRE(N > 0 && views >= 1 && N % views == 0);
     if (count == 0) return PRIMIA_OK;
     PRIMIA_REQUIRE(xs_dev && widths_dev && sq_acc && count > 0);
-    record_sqnorm_many_kernel<<<dim3(count, N / views), 256, 0, (hipStream_t)stream>>>((const float* const*)xs_dev,
-                                                                                       widths_dev, views, sq_acc);
+    const auto kern = views == 1 ? record_sqnorm_many_kernel<true> : record_sqnorm_many_kernel<false>;
+    kern<<<dim3(count, N / views), 256, 0, (hipStream_t)stream>>>((const float* const*)xs_dev, widths_dev, views, sq_acc);
     return launch_status();
+}
+
+int primia_persample_sqnorm(const float* x, int N, int64_t per_sample, double* sq_acc, primia_stream_t stream) {
+    return primia_record_sqnorm(x, N, per_sample, 1, sq_acc, stream);
+}
+
+int primia_persample_sqnorm_many(const void* xs_dev, const int* widths_dev, int count, int N, double* sq_acc,
+                                 primia_stream_t stream) {
+    if (count == 0) return PRIMIA_OK;   // before any other argument is looked at
+    return primia_record_sqnorm_many(xs_dev, widths_dev, count, N, 1, sq_acc, stream);
 }
 
 int primia_dp_clip_factors(const double* sq, float* clip, int N, float max_grad_norm, primia_stream_t stream) {

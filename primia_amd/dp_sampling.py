@@ -112,11 +112,10 @@ class _PoissonBase:
 class PoissonLoader(_PoissonBase):
     """Poisson batches over a device-resident (data, targets) pair (imagefolder.DeviceLoader's case).  `data` holds
     `repetitions` walks of the same n records, laid out as walk * n + k (imagefolder.register): sampling is over the n
-    RECORDS, and epoch e reads walk e % repetitions through the gather's row offset — one person is one record for the
-    accountant however many augmented copies are stored.  __len__ = ceil(n / L).  Every iteration yields the SAME
-    [capacity, ...] buffer pair, rewritten in place.  `views` = m > 1: a record fills rows s * m .. s * m + m - 1 with its
-    walks (e * m + v) % repetitions, v < m, of epoch e (primia_gather_records); with m > repetitions the views repeat
-    stored copies."""
+    RECORDS — one person is one record for the accountant however many augmented copies are stored.  __len__ = ceil(n / L).
+    Every iteration yields the SAME [capacity, ...] buffer pair, rewritten in place.  A record fills rows s * m .. s * m +
+    m - 1 (m = `views`; 1: epoch e reads walk e % repetitions) with its walks (e * m + v) % repetitions, v < m, of epoch e
+    (primia_gather_records); with m > repetitions the views repeat stored copies."""
 
     def __init__(self, data, targets, expected_batch, capacity, sampler, repetitions=1, threshold=None, micro_batches=1,
                  views=1):
@@ -148,12 +147,8 @@ class PoissonLoader(_PoissonBase):
         """One batch into (self.x, self.y): select, advance, gather — no host synchronisation.  `walk`: the walk of a
         record's first view (the next views - 1 follow it, modulo repetitions)."""
         self.sampler.select(self.threshold, self.n, self.idx, self.count)
-        if self.views == 1:
-            call("primia_gather_batch", self.data, self.row_elems, self.n, self.targets, self.idx, int(walk) * self.n,
-                 self.x, self.y, self.capacity, self.dt)
-        else:
-            call("primia_gather_records", self.data, self.row_elems, self.n, self.targets, self.idx, int(walk),
-                 self.repetitions, self.views, self.x, self.y, self.capacity, self.dt)
+        call("primia_gather_records", self.data, self.row_elems, self.n, self.targets, self.idx, int(walk),
+             self.repetitions, self.views, self.x, self.y, self.capacity, self.dt)
         self.draws += 1
         return self.x, self.y
 
@@ -184,10 +179,7 @@ class PoissonAugmentingLoader(_PoissonBase):
             idx = self.idx[:kept]
             self.x.zero_()
             self.y.fill_(-1)
-            if kept and self.views == 1:
-                self.x[:kept] = self.tf.batch([self.images[i] for i in idx.tolist()], self.rng)
-                self.y[:kept] = self.targets.index_select(0, idx)
-            elif kept:
+            if kept:
                 m = self.views
                 self.x[:kept * m] = self.tf.batch([self.images[i] for i in idx.tolist() for _ in range(m)], self.rng)
                 self.y[:kept * m] = self.targets.index_select(0, idx).repeat_interleave(m)

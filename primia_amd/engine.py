@@ -1251,22 +1251,23 @@ class ResNet18Engine:
         if self.norm not in ("group", "frozen"):
             raise _lib.PrimiaError("DP-SGD needs per-sample independent norm layers: ResNet18Engine(norm='group') or "
                                    "norm='frozen' (BatchNorm with fixed statistics)")
-        if int(views) != 1:
-            if int(views) < 1 or self.N % int(views):
-                raise ValueError(f"dp_loss_backward: views = {views} does not cut the engine's {self.N} slots into records")
-            return self._dp_loss_backward_records(target, max_grad_norm, noise_multiplier, noise, generator, expected_batch,
-                                                  accumulate, logical_batch, int(views))
+        m = int(views)
+        if m < 1 or self.N % m:
+            raise ValueError(f"dp_loss_backward: views = {views} does not cut the engine's {self.N} slots into records")
         N, nc, dev = self.N, self.spec.num_classes, self.device
-        # per-sample loss gradients: softmax - onehot (xent gives them divided by the batch size)
+        R = N // m      # a sample is a record of one view
+        # per-slot loss gradients: softmax - onehot (xent gives them divided by the batch size), over the record's m views
         if masked:      # softmax - onehot on valid rows, zeros on padded ones; the loss is the mean over the valid rows
             call("primia_xent_hard_masked", self.logits, target, self.loss, self.dlogits, N, nc)
+            if m > 1:
+                call("primia_scale", self.dlogits, self.dlogits.numel(), 1.0 / m)
         else:
             call("primia_xent_hard", self.logits, target, None, self.loss, self.dlogits, N, nc)
-            call("primia_scale", self.dlogits, self.dlogits.numel(), float(N))
+            call("primia_scale", self.dlogits, self.dlogits.numel(), float(N) / m)
         self.dp = {"wgrads": []}
         try:
             self.backward()
-            sq = torch.zeros(N, dtype=torch.float64, device=dev)
+            sq = torch.zeros(R, dtype=torch.float64, device=dev)
             # fc: g_W[n] = dlogits[n]^T feat[n], g_b[n] = dlogits[n]
             ps_fc = torch.empty(N, nc * 512 + nc, dtype=torch.float32, device=dev)
             call("primia_fc_persample_grads", self.feat, self.dlogits, ps_fc, N, 512, nc)
@@ -1276,23 +1277,24 @@ class ResNet18Engine:
                 if trace is not None:
                     trace[name] = sq.clone()
 
-            call("primia_persample_sqnorm", ps_fc, N, nc * 512 + nc, sq)
+            call("primia_record_sqnorm", ps_fc, N, nc * 512 + nc, m, sq)
             mark("fc")
-            if trace is None:   # all 40 per-sample affine gradients in one launch
+            if trace is None:   # all 40 per-slot affine gradients in one launch
                 if getattr(self, "_sqnorm_many", None) is None:
                     xs = [tt.data_ptr() for pair in self.ps_affine.values() for tt in pair]
                     ws_ = [tt.shape[1] for pair in self.ps_affine.values() for tt in pair]
                     self._sqnorm_many = (torch.tensor(xs, dtype=torch.int64, device=dev),
                                          torch.tensor(ws_, dtype=torch.int32, device=dev), len(xs))
-                call("primia_persample_sqnorm_many", self._sqnorm_many[0], self._sqnorm_many[1], self._sqnorm_many[2], N, sq)
+                call("primia_record_sqnorm_many", self._sqnorm_many[0], self._sqnorm_many[1], self._sqnorm_many[2], N, m, sq)
             else:
                 for b, (psg, psb) in self.ps_affine.items():
-                    call("primia_persample_sqnorm", psg, N, psg.shape[1], sq)
-                    call("primia_persample_sqnorm", psb, N, psb.shape[1], sq)
+                    call("primia_record_sqnorm", psg, N, psg.shape[1], m, sq)
+                    call("primia_record_sqnorm", psb, N, psb.shape[1], m, sq)
                     mark(b)
             # layers whose per-sample gradient tiles are small enough to KEEP (the stem, layer1's 64 -> 64 convs): the
-            # norm pass stores them and the clipped sum is a weighted reduce — no row scaling of dy, no second pass
-            kept = self._dp_keep_buffers()
+            # norm pass stores them and the clipped sum is a weighted reduce — no row scaling of dy, no second pass.
+            # The kept-tile forms are per sample: records of several views run the two-pass form on every layer
+            kept = self._dp_keep_buffers() if m == 1 else {}
             for name, x, dy in self.dp["wgrads"]:
                 c = self.convs[name]
                 done = False
@@ -1306,33 +1308,39 @@ class ResNet18Engine:
                              kept[name].numel() * 4, self.dt)
                     mark(name)
                     continue
-                if name == "conv1" and self._stem_padded:   # halo kernel on the padded input, one block per image
+                if name == "conv1" and self._stem_padded:   # halo kernel on the padded input, one block per record
                     S = self.spec.input_size
                     try:
-                        call("primia_stem_conv_wgrad_persample_sqnorm", self.x0p, dy, sq, N, S, S, self.dt)
+                        call("primia_stem_conv_wgrad_record_sqnorm", self.x0p, dy, sq, N, S, S, m, self.dt)
                         done = True
                     except _lib.PrimiaError:
                         done = False
                 if not done:
                     if name == "conv1" and not self._x0_valid:
-                        raise _lib.PrimiaError("per-sample stem gradient: the padded-input kernel refused a shape it "
+                        raise _lib.PrimiaError("per-record stem gradient: the padded-input kernel refused a shape it "
                                                "advertised (primia_stem_conv_wgrad_ws_bytes > 0)")
-                    call("primia_conv2d_wgrad_persample_sqnorm", c.desc, x, dy, sq, self.dt)
+                    call("primia_conv2d_wgrad_record_sqnorm", c.desc, x, dy, sq, m, self.dt)
                 mark(name)
-            clip = torch.empty(N, dtype=torch.float32, device=dev)
+            # one clip factor per record (record r's target is slot r * m's), then one per slot for the clipped sums
+            clip = torch.empty(R, dtype=torch.float32, device=dev)
+            target_r = None if not masked else target if m == 1 else target[::m].contiguous()
             adaptive = self._root.dp_clip
             if adaptive is not None:    # C from the device word; the step's counts start over on its first (or only) pass
-                adaptive.factors(sq, target if masked else None, clip, N, overwrite=accumulate in (None, "first"))
+                adaptive.factors(sq, target_r, clip, R, overwrite=accumulate in (None, "first"))
             elif masked:
-                call("primia_dp_clip_factors_masked", sq, target, clip, N, float(max_grad_norm))
+                call("primia_dp_clip_factors_masked", sq, target_r, clip, R, float(max_grad_norm))
             else:
-                call("primia_dp_clip_factors", sq, clip, N, float(max_grad_norm))
-            self._dp_clipped_sums(clip, ps_fc, kept)
+                call("primia_dp_clip_factors", sq, clip, R, float(max_grad_norm))
+            clip_slots = clip
+            if m > 1:
+                clip_slots = torch.empty(N, dtype=torch.float32, device=dev)
+                call("primia_dp_expand_clip", clip, clip_slots, N, m)
+            self._dp_clipped_sums(clip_slots, ps_fc, kept)
         finally:
             if getattr(self, "dp_keep_operands", False):      # tests: the (layer, x, dy) triples the norm pass walked
                 self.dp_operands = list(self.dp["wgrads"])
             self.dp = None
-        return self._dp_tail(sq, clip, adaptive, N, masked, expected_batch, accumulate, logical_batch, max_grad_norm,
+        return self._dp_tail(sq, clip, adaptive, R, masked, expected_batch, accumulate, logical_batch, max_grad_norm,
                              noise_multiplier, noise, generator)
 
     def _dp_clipped_sums(self, clip, ps_fc, kept):
@@ -1441,80 +1449,6 @@ class ResNet18Engine:
             else:
                 call("primia_dp_add_noise_acc", self.grads, acc, noise, self.P, sigma, inv_batch)
         return self.loss
-
-    def _dp_loss_backward_records(self, target, max_grad_norm, noise_multiplier, noise, generator, expected_batch, accumulate,
-                                  logical_batch, m):
-        """dp_loss_backward for records of m > 1 views (see there): the two-pass form on every layer, norms per record."""
-        masked = expected_batch is not None
-        N, nc, dev = self.N, self.spec.num_classes, self.device
-        R = N // m
-        if masked:
-            call("primia_xent_hard_masked", self.logits, target, self.loss, self.dlogits, N, nc)
-            call("primia_scale", self.dlogits, self.dlogits.numel(), 1.0 / m)
-        else:
-            call("primia_xent_hard", self.logits, target, None, self.loss, self.dlogits, N, nc)
-            call("primia_scale", self.dlogits, self.dlogits.numel(), float(N) / m)
-        self.dp = {"wgrads": []}
-        try:
-            self.backward()
-            sq = torch.zeros(R, dtype=torch.float64, device=dev)
-            ps_fc = torch.empty(N, nc * 512 + nc, dtype=torch.float32, device=dev)
-            call("primia_fc_persample_grads", self.feat, self.dlogits, ps_fc, N, 512, nc)
-            trace = getattr(self, "dp_trace", None)
-
-            def mark(name):
-                if trace is not None:
-                    trace[name] = sq.clone()
-
-            call("primia_record_sqnorm", ps_fc, N, nc * 512 + nc, m, sq)
-            mark("fc")
-            if trace is None:
-                if getattr(self, "_sqnorm_many", None) is None:
-                    xs = [tt.data_ptr() for pair in self.ps_affine.values() for tt in pair]
-                    ws_ = [tt.shape[1] for pair in self.ps_affine.values() for tt in pair]
-                    self._sqnorm_many = (torch.tensor(xs, dtype=torch.int64, device=dev),
-                                         torch.tensor(ws_, dtype=torch.int32, device=dev), len(xs))
-                call("primia_record_sqnorm_many", self._sqnorm_many[0], self._sqnorm_many[1], self._sqnorm_many[2], N, m, sq)
-            else:
-                for b, (psg, psb) in self.ps_affine.items():
-                    call("primia_record_sqnorm", psg, N, psg.shape[1], m, sq)
-                    call("primia_record_sqnorm", psb, N, psb.shape[1], m, sq)
-                    mark(b)
-            for name, x, dy in self.dp["wgrads"]:
-                c = self.convs[name]
-                done = False
-                if name == "conv1" and self._stem_padded:   # halo kernel on the padded input, one block per record
-                    S = self.spec.input_size
-                    try:
-                        call("primia_stem_conv_wgrad_record_sqnorm", self.x0p, dy, sq, N, S, S, m, self.dt)
-                        done = True
-                    except _lib.PrimiaError:
-                        done = False
-                if not done:
-                    if name == "conv1" and not self._x0_valid:
-                        raise _lib.PrimiaError("per-record stem gradient: the padded-input kernel refused a shape it "
-                                               "advertised (primia_stem_conv_wgrad_ws_bytes > 0)")
-                    call("primia_conv2d_wgrad_record_sqnorm", c.desc, x, dy, sq, m, self.dt)
-                mark(name)
-            # the factor kernels run unchanged on the R records; record r's target is slot r * m's
-            clip_r = torch.empty(R, dtype=torch.float32, device=dev)
-            target_r = target[::m].contiguous() if masked else None
-            adaptive = self._root.dp_clip
-            if adaptive is not None:
-                adaptive.factors(sq, target_r, clip_r, R, overwrite=accumulate in (None, "first"))
-            elif masked:
-                call("primia_dp_clip_factors_masked", sq, target_r, clip_r, R, float(max_grad_norm))
-            else:
-                call("primia_dp_clip_factors", sq, clip_r, R, float(max_grad_norm))
-            clip = torch.empty(N, dtype=torch.float32, device=dev)
-            call("primia_dp_expand_clip", clip_r, clip, N, m)
-            self._dp_clipped_sums(clip, ps_fc, {})
-        finally:
-            if getattr(self, "dp_keep_operands", False):
-                self.dp_operands = list(self.dp["wgrads"])
-            self.dp = None
-        return self._dp_tail(sq, clip_r, adaptive, R, masked, expected_batch, accumulate, logical_batch, max_grad_norm,
-                             noise_multiplier, noise, generator)
 
     def _dp_adaptive_tail(self, adaptive, acc, batch, inv_batch, z, noise, generator):
         """The end of a logical DP-SGD step under an adaptive clipping norm (engine.dp_clip): noise z_delta * C on the

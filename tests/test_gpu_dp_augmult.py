@@ -222,7 +222,7 @@ def test_expand_clip(cuda, m):
 
 
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("m,reps,first", [(2, 5, 0), (3, 5, 4), (3, 2, 1), (2, 1, 0)])
+@pytest.mark.parametrize("m,reps,first", [(2, 5, 0), (3, 5, 4), (3, 2, 1), (2, 1, 0), (1, 5, 3)])
 def test_gather_records(cuda, dtype, m, reps, first):
     """out[s * m + v] = data[((first + v) % reps) * n_rows + idx[s]], targets alike; padded (-1) and out-of-range records
     give m zero rows with target -1; rows of one chunk, three chunks and a 3 x 32 x 32 image; guard bands on both outputs."""
@@ -431,6 +431,57 @@ def test_record_step_bf16_against_the_oracles(cuda, monkeypatch):
     bound = max(5e-3, 2 * o16)
     assert e16 < bound and torch.allclose(got_clip, clip16, rtol=bound)
     assert gvec.norm().item() <= C * 1.02
+
+
+def test_a_sample_is_a_record_of_one_view(cuda, monkeypatch):
+    """The engine of the test above (bf16, 64 x 64, 16 slots: it keeps tiles) without `views` and with views = 1 passed: one
+    pass, the same launches — kept tiles where there are buffers, the record entry points with one view everywhere else, no
+    launch that only records of several views need.  The two runs differ only in the order of the norm pass's fp64 atomics
+    (test_persample_sqnorm_many: below 1e-13 on a squared norm), which reaches the gradients through one fp32 rounding of
+    the clip factor: rel < 1e-6, and a factor of exactly 0 or 1 is the same in both."""
+    N, L = 16, 3.5
+    sd = weights("group", 64, 81)
+    g = torch.Generator().manual_seed(83)
+    x = torch.randn(N, 3, 64, 64, generator=g).to(cuda)
+    y = torch.randint(0, 3, (N,), generator=g)
+    ym = y.clone()
+    ym[[2, 7, 13, 14, 15]] = -1
+    y, ym = y.to(cuda), ym.to(cuda)
+    eng = ResNet18Engine(N, 3, 3, 64, "max", dtype=BF16, device=cuda, norm="group")
+    eng.load_state_dict(sd)
+    kept = eng._dp_keep_buffers()
+    assert len(kept) > 0
+    zeros = torch.zeros(eng.P, device=cuda)
+    eng.forward(x)
+    eng.dp_loss_backward(ym, 1e9, 0.0, noise=zeros, expected_batch=L)
+    C = float(eng.dp_stats["sq_norms"][ym >= 0].sqrt().median())       # half of the valid samples are clipped
+    names = []
+    real = engine_module.call
+    monkeypatch.setattr(engine_module, "call", lambda name, *a, **kw: (names.append(name), real(name, *a, **kw))[1])
+
+    def step(target, **kw):
+        del names[:]
+        eng.forward(x)
+        eng.dp_loss_backward(target, C, 0.0, noise=zeros, **kw)
+        return list(names), eng.grads.clone(), eng.dp_stats["clip"].clone()
+
+    plain, g0, c0 = step(ym, expected_batch=L)
+    one, g1, c1 = step(ym, expected_batch=L, views=1)
+    assert plain == one
+    assert c0.numel() == N and (c0[ym < 0] == 0).all() and (c0 == 1).any() and ((c0 > 0) & (c0 < 1)).any()
+    assert "primia_dp_expand_clip" not in plain and "primia_scale" not in plain
+    assert len([n for n in plain if "_keep" in n]) == len([n for n in plain if "clipped_sum" in n]) == len(kept)
+    assert plain.count("primia_conv2d_wgrad_record_sqnorm") + plain.count("primia_stem_conv_wgrad_record_sqnorm") == \
+        20 - len(kept)
+    assert plain.count("primia_record_sqnorm_many") == 1 and plain.count("primia_record_sqnorm") == 1
+    assert not [n for n in plain if "persample_sqnorm" in n and "_keep" not in n], plain
+    e = rel(g1, g0)
+    print(f"views = 1 against no views: rel = {e:.3e}")
+    assert float(g0.abs().max()) > 0 and e < 1e-6
+    fixed = (c0 == 0) | (c0 == 1)
+    assert torch.equal(c1[fixed], c0[fixed])
+    unmasked, _, _ = step(y)
+    assert unmasked.count("primia_scale") == 1 and "primia_dp_expand_clip" not in unmasked
 
 
 # ---- combinations ----------------------------------------------------------------------------------------------------------

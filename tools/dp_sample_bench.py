@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """us per call of the two launches a Poisson-sampled DP-SGD step adds in front of the step (csrc/dp_sample.hip):
 primia_poisson_select over n records (one workgroup walking n in chunks of 8192; timed together with the primia_u64_add
-that advances its counter, as DeviceSampler.select issues them) and primia_gather_batch of `capacity` fp32 images.
+that advances its counter, as DeviceSampler.select issues them) and primia_gather_batch of `capacity` fp32 images (one walk and one view
+of the kernel behind the loader's primia_gather_records).
 Each figure is the median over --runs timed loops of --calls back-to-back launches between two events (launch-rate
 included: what the training loop pays).  Prints one JSON line.  Needs a GPU."""
 import argparse
