@@ -25,6 +25,13 @@ from .resnet_spec import NetSpec, bn_name, buffer_entries, init_state_dict, para
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
+# Backward entries per norm kind: (relu without residual, 1-bit ReLU mask instead of z, general).  The kinds share one
+# argument frame (ResNet18Engine._bn_bwd, the only caller); what each takes for the statistics and where its affine
+# gradients go is chosen with the names at construction: the saved (mean, invstd) — frozen BatchNorm: (running_mean,
+# running_var, eps) — and the gradient views — GroupNorm and frozen BatchNorm: per-sample rows, and a groups slot.
+_NORM_BWD = {"batch": ("primia_bn_relu_bwd", "primia_bn_bwd_mask", "primia_bn_bwd"),
+             "group": ("primia_gn_relu_bwd", "primia_gn_bwd_mask", "primia_gn_bwd"),
+             "frozen": ("primia_bn_frozen_relu_bwd", "primia_bn_frozen_bwd_mask", "primia_bn_frozen_bwd")}
 
 
 class _Conv:
@@ -62,6 +69,14 @@ class ResNet18Engine:
         if norm not in ("batch", "group", "frozen"):
             raise ValueError("norm must be 'batch', 'group' or 'frozen'")
         self.norm, self.groups = norm, int(groups)
+        # the two questions the step methods ask of the kind.  batch_stats: BatchNorm proper — statistics of the batch in
+        # training (running ones in eval mode), the kernels that fuse across layers.  per_sample_norm: GroupNorm and frozen
+        # BatchNorm — a sample's output depends on that sample alone, the same pass in training and eval mode, affine
+        # gradients per sample (what DP-SGD needs).
+        self.batch_stats = norm == "batch"
+        self.per_sample_norm = not self.batch_stats
+        # (of the per-sample kinds GroupNorm alone has the stem tail norm -> relu -> maxpool as one kernel each way)
+        self._gn_stem_kernels = norm == "group"
         self.N = int(batch_size)
         self.dtype = dtype
         self.dt = _lib.dtype_code(dtype)
@@ -232,12 +247,11 @@ class ResNet18Engine:
             t[(blocks[i - 1].prefix + ".dout") if i > 0 else "pool.dout"] = din
         # stem tail bn1 -> relu -> maxpool as ONE fused op in training (z = relu(bn(y)) is never written)
         self.fuse_stem = True
-        self._stem_fused = False
         self.relu_masks = {}         # residual layers: 1-bit ReLU masks for the backward passes (see _bn)
         # the stem convolutions read the padded input copy; the unpadded one is written only where the halo kernels on the
         # padded one do not serve the shape
         self._stem_padded = self.x0p is not None
-        self._x0_valid = not self._stem_padded or (norm in ("group", "frozen") and self._stem_ws_bytes <= 0)
+        self._x0_valid = not self._stem_padded or (self.per_sample_norm and self._stem_ws_bytes <= 0)
         self.stat_slots = query("primia_conv_stat_slots")
         for c in self.spec.convs:   # slots the kernel serving this conv writes (per-block partials for layer1's)
             self.convs[c.name].stat_slots = (query("primia_conv_stat_slots_for", self.convs[c.name].desc, self.dt)
@@ -260,27 +274,36 @@ class ResNet18Engine:
         self.masked_acc_ok = {blk.conv1.name: query("primia_conv_dgrad_masked_acc_ok", self.convs[blk.conv1.name].desc,
                                                     self.dt) == 1
                               for blk in self.spec.blocks if blk.down is None}
-        self.save = {}
-        for c in self.spec.convs:
-            b = bn_name(c.name)
-            self.save[b] = (torch.empty(c.cout, dtype=torch.float32, device=dev),
-                            torch.empty(c.cout, dtype=torch.float32, device=dev))
-        self.bn_ws_bytes = max(query("primia_bn_workspace_bytes", 1, 512), 1024 * 3 * 512 * 4)   # (pair backward: 3 sums)
+        # ---- norm layers: what the kind keeps per layer; the step methods read these, none of them asks for the kind ----
+        def f32_pair(*shape):
+            return tuple(torch.empty(*shape, dtype=torch.float32, device=dev) for _ in range(2))
+
+        bns = [(bn_name(c.name), c) for c in self.spec.convs]
+        # saved (mean, invstd): per channel, GroupNorm's per (sample, group)
+        self.save = {b: f32_pair(N * self.groups if norm == "group" else c.cout) for b, c in bns}
+        norm_ws = [query("primia_bn_workspace_bytes", 1, 512), 1024 * 3 * 512 * 4]   # (pair backward: 3 sums)
         if norm == "group":
-            self.bn_ws_bytes = max(self.bn_ws_bytes, query("primia_gn_workspace_bytes", N, 512, self.groups))
-            # statistics are per (sample, group); per-sample affine gradients [N][C] per layer
-            self.save = {bn_name(c.name): (torch.empty(N * self.groups, dtype=torch.float32, device=dev),
-                                           torch.empty(N * self.groups, dtype=torch.float32, device=dev))
-                         for c in self.spec.convs}
+            norm_ws.append(query("primia_gn_workspace_bytes", N, 512, self.groups))
         if norm == "frozen":
-            self.bn_ws_bytes = max([self.bn_ws_bytes] + [
-                query("primia_bn_frozen_workspace_bytes", N, self.convs[c.name].desc.Ho ** 2, c.cout) for c in self.spec.convs])
-        if norm in ("group", "frozen"):
-            self.ps_affine = {bn_name(c.name): (torch.empty(N, c.cout, dtype=torch.float32, device=dev),
-                                                torch.empty(N, c.cout, dtype=torch.float32, device=dev))
-                              for c in self.spec.convs}
-            self.ones_n = torch.ones(N, dtype=torch.float32, device=dev)
+            norm_ws += [query("primia_bn_frozen_workspace_bytes", N, self.convs[c.name].desc.Ho ** 2, c.cout) for b, c in bns]
+        self.bn_ws_bytes = max(norm_ws)
         self.bn_ws = torch.zeros(self.bn_ws_bytes, dtype=torch.uint8, device=dev)  # holds a completion counter
+        # _bn_bwd's entries and, per layer, their operands for the statistics and for dgamma / dbeta
+        self._bwd_entries = _NORM_BWD[norm]
+        self._bwd_stats = {b: (self.views[b + ".running_mean"], self.views[b + ".running_var"], BN_EPS) if norm == "frozen"
+                           else self.save[b] for b, c in bns}
+        if self.per_sample_norm:
+            # per-sample affine gradients [N][C] per layer, summed over the samples by _reduce_affine
+            self.ps_affine = {b: f32_pair(N, c.cout) for b, c in bns}
+            self.ones_n = torch.ones(N, dtype=torch.float32, device=dev)
+            self._bwd_affine = self.ps_affine
+            self._ps_groups = (self.groups,) if norm == "group" else ()
+        else:
+            self._bwd_affine = {b: (self._gviews[b + ".weight"], self._gviews[b + ".bias"]) for b, c in bns}
+        # state of the stem's fusions: decided by every forward(), read by backward()
+        self._stem_fused = self._stem_fused_gn = False
+        self._stem_sums, self._stem_slots = None, 0   # bn1's partial sums out of the padded-input stem conv (first use)
+        self._pool_sums = None       # (partials, slots) of bn1's backward sums where layer1.0.conv1's data gradient forms them
         self.dp = None  # set by dp_backward: {"wgrads": [...]} defers the weight gradients
         self.feat = torch.empty(N, 512, dtype=torch.float32, device=dev)
         self.dfeat = torch.empty(N, 512, dtype=torch.float32, device=dev)
@@ -418,56 +441,52 @@ class ResNet18Engine:
     # ------------------------------------------------------------------------------------------
     # forward
     # ------------------------------------------------------------------------------------------
+    def _relu_mask(self, b, y):
+        """Norm layer b's 1-bit ReLU mask, sized from its input y.  Allocated at first use: an engine that only evaluates
+        holds none."""
+        mask = self.relu_masks.get(b)
+        if mask is None:
+            mask = self.relu_masks[b] = torch.empty(y.numel() * y.element_size() // 16, dtype=torch.uint8, device=y.device)
+        return mask
+
     def _bn(self, conv_name, y, z, residual, relu):
         b = bn_name(conv_name)
         C = y.shape[1]
         M = y.shape[0]
         g, be = self.views[b + ".weight"], self.views[b + ".bias"]
-        if self.norm == "frozen":  # identical in train and eval mode: the running statistics are read, never written
-            rm, rv = self.views[b + ".running_mean"], self.views[b + ".running_var"]
-            if self.training and residual is not None and relu and self.gn_relu_masks:
-                # residual layer: also write the 1-bit ReLU mask the backward passes read instead of z
-                if b not in self.relu_masks:
-                    self.relu_masks[b] = torch.empty(y.numel() * y.element_size() // 16, dtype=torch.uint8, device=y.device)
-                call("primia_bn_fwd_eval_mask", y, residual, z, self.relu_masks[b], g, be, rm, rv, M, C, BN_EPS, self.dt)
-                return
-            call("primia_bn_fwd_eval", y, residual, z, g, be, rm, rv, M, C, BN_EPS, int(relu), self.dt)
-            return
+        # residual layer in training: also write the 1-bit ReLU mask the backward passes read instead of z
+        mask = None
+        if self.training and residual is not None and relu and (self.batch_stats or self.gn_relu_masks):
+            mask = self._relu_mask(b, y)
+        sm, si = self.save[b]
         if self.norm == "group":  # identical in train and eval mode: no running statistics
-            sm, si = self.save[b]
-            if self.training and residual is not None and relu and self.gn_relu_masks:
-                # residual layer: also write the 1-bit ReLU mask the backward passes read instead of z
-                if b not in self.relu_masks:
-                    self.relu_masks[b] = torch.empty(y.numel() * y.element_size() // 16, dtype=torch.uint8, device=y.device)
-                call("primia_gn_fwd_mask", y, residual, z, self.relu_masks[b], g, be, sm, si, self.N, M // self.N, C,
-                     self.groups, BN_EPS, self.bn_ws, self.bn_ws_bytes, self.dt)
-                return
-            call("primia_gn_fwd", y, residual, z, g, be, sm, si, self.N, M // self.N, C, self.groups, BN_EPS, int(relu),
-                 self.bn_ws, self.bn_ws_bytes, self.dt)
+            if mask is not None:
+                call("primia_gn_fwd_mask", y, residual, z, mask, g, be, sm, si, self.N, M // self.N, C, self.groups, BN_EPS,
+                     self.bn_ws, self.bn_ws_bytes, self.dt)
+            else:
+                call("primia_gn_fwd", y, residual, z, g, be, sm, si, self.N, M // self.N, C, self.groups, BN_EPS, int(relu),
+                     self.bn_ws, self.bn_ws_bytes, self.dt)
             return
         rm, rv = self.views[b + ".running_mean"], self.views[b + ".running_var"]
-        if self.training and residual is not None and relu:
-            # residual layer: also write the 1-bit ReLU mask the backward passes read instead of z
-            sm, si = self.save[b]
-            if b not in self.relu_masks:
-                self.relu_masks[b] = torch.empty(y.numel() * y.element_size() // 16, dtype=torch.uint8, device=y.device)
-            have_sums = conv_name in self.free_stats
-            call("primia_bn_fwd_train_mask", y, residual, z, self.relu_masks[b], g, be, rm, rv, sm, si,
-                 self.convs[conv_name].sums if have_sums else None, self.convs[conv_name].stat_slots if have_sums else 0,
-                 M, C, BN_EPS, BN_MOMENTUM, self.bn_ws, self.bn_ws_bytes, self.dt)
-            self.num_batches_tracked[b] += 1
-        elif self.training:
-            sm, si = self.save[b]
-            if conv_name in self.free_stats:
-                call("primia_bn_fwd_train_from_sums", y, residual, z, g, be, rm, rv, sm, si,
-                     self.convs[conv_name].sums, self.convs[conv_name].stat_slots, M, C, BN_EPS, BN_MOMENTUM,
-                     int(relu), self.dt)
+        if not (self.batch_stats and self.training):
+            # eval mode — and frozen BatchNorm in either mode: the running statistics are read, never written
+            if mask is not None:
+                call("primia_bn_fwd_eval_mask", y, residual, z, mask, g, be, rm, rv, M, C, BN_EPS, self.dt)
             else:
-                call("primia_bn_fwd_train", y, residual, z, g, be, rm, rv, sm, si, M, C, BN_EPS, BN_MOMENTUM,
-                     int(relu), self.bn_ws, self.bn_ws_bytes, self.dt)
-            self.num_batches_tracked[b] += 1
+                call("primia_bn_fwd_eval", y, residual, z, g, be, rm, rv, M, C, BN_EPS, int(relu), self.dt)
+            return
+        c = self.convs[conv_name]
+        have_sums = conv_name in self.free_stats
+        if mask is not None:
+            call("primia_bn_fwd_train_mask", y, residual, z, mask, g, be, rm, rv, sm, si, c.sums if have_sums else None,
+                 c.stat_slots if have_sums else 0, M, C, BN_EPS, BN_MOMENTUM, self.bn_ws, self.bn_ws_bytes, self.dt)
+        elif have_sums:
+            call("primia_bn_fwd_train_from_sums", y, residual, z, g, be, rm, rv, sm, si, c.sums, c.stat_slots, M, C, BN_EPS,
+                 BN_MOMENTUM, int(relu), self.dt)
         else:
-            call("primia_bn_fwd_eval", y, residual, z, g, be, rm, rv, M, C, BN_EPS, int(relu), self.dt)
+            call("primia_bn_fwd_train", y, residual, z, g, be, rm, rv, sm, si, M, C, BN_EPS, BN_MOMENTUM, int(relu),
+                 self.bn_ws, self.bn_ws_bytes, self.dt)
+        self.num_batches_tracked[b] += 1
 
     # Optional per-launch timing of the convolution kernels (bench.py roofline leg): when
     # `self.prof` is a list, every conv launch is bracketed by events on the launch stream.
@@ -504,7 +523,7 @@ class ResNet18Engine:
     stem_eval_one_pass_min_batch = 160
 
     def _stem_eval_one_pass(self):
-        if self.training or self.norm != "batch" or self.spec.pooling != "max" or self.prof is not None:
+        if self.training or not self.batch_stats or self.spec.pooling != "max" or self.prof is not None:
             return False
         if self.N < self.stem_eval_one_pass_min_batch:
             return False
@@ -518,7 +537,7 @@ class ResNet18Engine:
             c1.pair_ok = self.fwd_pair and query("primia_conv_fwd_pair_ok", c1.desc, cd.desc, self.dt) == 1
         if not c1.pair_ok:
             return False
-        stats = self.training and self.norm == "batch"
+        stats = self.training and self.batch_stats
         s1 = c1.sums if stats and blk.conv1.name in self.free_stats else None
         sd = cd.sums if stats and blk.down.name in self.free_stats else None
         if stats and (s1 is None or sd is None):
@@ -543,8 +562,8 @@ class ResNet18Engine:
             call("primia_nchw_to_nhwc_padded", x_nchw, self.x0p, N, self.spec.in_channels, S, S, 4, 3, 3,
                  self.x0p_dims[0], self.x0p_dims[1], self.dt)
             c = self.convs["conv1"]
-            if self.training and self.norm == "batch":   # + bn1's per-block partial sums, for free
-                if getattr(self, "_stem_sums", None) is None:
+            if self.training and self.batch_stats:   # + bn1's per-block partial sums, for free
+                if self._stem_sums is None:
                     self._stem_slots = query("primia_stem_conv_stat_slots", N, S, S)
                     self._stem_sums = torch.zeros(self._stem_slots, 2, 64, dtype=torch.float32, device=self.device)
                 self._timed("fwd", c, lambda: call("primia_stem_conv_fwd_stats", self.x0p, c.w_fwd, t["stem.y"],
@@ -561,9 +580,9 @@ class ResNet18Engine:
         else:
             self._conv_fwd("conv1", self.x0, t["stem.y"])
         hw = self.stem_hw
-        self._stem_fused = self.fuse_stem and self.training and self.norm == "batch" and self.spec.pooling == "max"
+        self._stem_fused = self.fuse_stem and self.training and self.batch_stats and self.spec.pooling == "max"
         # GroupNorm: gn1 -> relu -> maxpool as one op each way (primia_gn_relu_maxpool_fwd / _bwd; _bwd wants even sizes)
-        self._stem_fused_gn = (self.fuse_stem and self.gn_stem_fused and self.norm == "group"
+        self._stem_fused_gn = (self.fuse_stem and self.gn_stem_fused and self._gn_stem_kernels
                                and self.spec.pooling == "max" and hw % 2 == 0)
         if stem_done:
             pass
@@ -602,21 +621,19 @@ class ResNet18Engine:
             self._bn(blk.conv1.name, t[p + ".y1"], t[p + ".a1"], None, True)
             self._conv_fwd(blk.conv2.name, t[p + ".a1"], t[p + ".y2"])
             idn = x
-            if blk.down is not None and self.training and self.norm == "batch":
+            if blk.down is not None and self.training and self.batch_stats:
                 # transition block: both BatchNorms in one apply pass (the downsample branch's output is never stored)
                 if not down_done:
                     self._conv_fwd(blk.down.name, x, t[p + ".yd"])
                 b2, bd = bn_name(blk.conv2.name), bn_name(blk.down.name)
                 y2 = t[p + ".y2"]
-                if b2 not in self.relu_masks:
-                    self.relu_masks[b2] = torch.empty(y2.numel() * y2.element_size() // 16, dtype=torch.uint8,
-                                                      device=y2.device)
+                mask = self._relu_mask(b2, y2)
                 c2 = self.convs[blk.conv2.name]
                 have = blk.conv2.name in self.free_stats
                 cd = self.convs[blk.down.name]
                 have_d = blk.down.name in self.free_stats
                 (sm2, si2), (smd, sid) = self.save[b2], self.save[bd]
-                call("primia_bn_fwd_train_pair", y2, t[p + ".yd"], t[p + ".out"], self.relu_masks[b2],
+                call("primia_bn_fwd_train_pair", y2, t[p + ".yd"], t[p + ".out"], mask,
                      self.views[b2 + ".weight"], self.views[b2 + ".bias"], self.views[b2 + ".running_mean"],
                      self.views[b2 + ".running_var"], sm2, si2, c2.sums if have else None, c2.stat_slots if have else 0,
                      self.views[bd + ".weight"], self.views[bd + ".bias"], self.views[bd + ".running_mean"],
@@ -679,68 +696,46 @@ class ResNet18Engine:
         self.backward()
         return self.loss
 
-    def _bn_bwd(self, conv_name, y, z, dz, dy, g_out, relu, keep_g=True, from_sums=None):
-        """keep_g=False (residual layers with a 1-bit mask only): the masked gradient g is NOT written back over dz —
-        the accumulating data gradient that consumes it applies the mask itself (primia_conv2d_dgrad_masked_acc)."""
+    def _bn_bwd(self, conv_name, y, z, dz, dy, g_out, relu, keep_g=True, from_sums=None, mask=None):
+        """Backward pass of the norm layer behind conv `conv_name`, whatever the kind.
+        `mask`: 1-bit ReLU mask applied to dz instead of reading z — by default the layer's own, where its forward pass
+        wrote one (residual layers); a transition block's downsample norm is given bn2's, with g_out=None.
+        keep_g=False (with a mask only): the masked gradient g is NOT written back over dz — the accumulating data
+        gradient that consumes it applies the mask itself (primia_conv2d_dgrad_masked_acc).
+        `from_sums` (partials, slots): the producer of dz has formed the backward sums (training BatchNorm statistics)."""
         b = bn_name(conv_name)
-        sm, si = self.save[b]
-        if self.norm == "frozen":
+        if mask is None and relu and g_out is not None:
+            mask = self.relu_masks.get(b)
+        gam = self.views[b + ".weight"]
+        M, C = y.shape
+        if mask is not None and from_sums is not None:
+            sm, si = self.save[b]
+            call("primia_bn_bwd_mask_from_sums", y, mask, dz, dy, g_out if keep_g else None, gam, sm, si,
+                 self._gviews[b + ".weight"], self._gviews[b + ".bias"], from_sums[0], from_sums[1], M, C, self.dt)
+            return
+        # one argument frame for the three kinds: the statistics operands, where dgamma / dbeta go (the gradient views; per
+        # sample for GroupNorm and frozen BatchNorm), the dimensions
+        relu_bwd, bwd_mask, bwd = self._bwd_entries
+        dims = (M, C) if self.batch_stats else (self.N, M // self.N, C) + self._ps_groups
+        frame = self._bwd_stats[b] + self._bwd_affine[b] + dims
+        if mask is not None:
+            # mask bytes instead of z
+            call(bwd_mask, y, mask, dz, dy, g_out if keep_g else None, gam, *frame, self.bn_ws, self.bn_ws_bytes, self.dt)
+        elif relu and g_out is None:
+            # z = relu(norm(y)), no residual: the mask is recomputed from y, z is not read
+            call(relu_bwd, y, dz, dy, gam, self.views[b + ".bias"], *frame, self.bn_ws, self.bn_ws_bytes, self.dt)
+        else:
+            call(bwd, y, z, dz, dy, g_out, gam, *frame, int(relu), self.bn_ws, self.bn_ws_bytes, self.dt)
+        self._reduce_affine(b)
+
+    def _reduce_affine(self, b):
+        """Per-sample kinds: dgamma / dbeta of norm layer b = the sum over samples of its per-sample affine gradients —
+        unless a DP-SGD pass is in flight, which clips them first (_dp_clipped_sums)."""
+        if self.per_sample_norm and self.dp is None:
             psg, psb = self.ps_affine[b]
-            C, HW = y.shape[1], y.shape[0] // self.N
-            gam, rm, rv = self.views[b + ".weight"], self.views[b + ".running_mean"], self.views[b + ".running_var"]
-            if relu and g_out is None:
-                # z = relu(bn(y)), no residual: the mask is recomputed from y, z is not read
-                call("primia_bn_frozen_relu_bwd", y, dz, dy, gam, self.views[b + ".bias"], rm, rv, BN_EPS, psg, psb,
-                     self.N, HW, C, self.bn_ws, self.bn_ws_bytes, self.dt)
-            elif relu and g_out is not None and b in self.relu_masks:
-                # residual layer: mask bytes instead of z; keep_g = False: the masked gradient is not written either
-                call("primia_bn_frozen_bwd_mask", y, self.relu_masks[b], dz, dy, g_out if keep_g else None, gam, rm, rv,
-                     BN_EPS, psg, psb, self.N, HW, C, self.bn_ws, self.bn_ws_bytes, self.dt)
-            else:
-                call("primia_bn_frozen_bwd", y, z, dz, dy, g_out, gam, rm, rv, BN_EPS, psg, psb, self.N, HW, C, int(relu),
-                     self.bn_ws, self.bn_ws_bytes, self.dt)
-            if self.dp is None:  # plain fine-tuning: dgamma / dbeta = sum over samples
-                call("primia_weighted_colsum", psg, self.ones_n, self._gviews[b + ".weight"], self.N, C)
-                call("primia_weighted_colsum", psb, self.ones_n, self._gviews[b + ".bias"], self.N, C)
-            return
-        if self.norm == "group":
-            psg, psb = self.ps_affine[b]
-            C = y.shape[1]
-            if relu and g_out is None:
-                # z = relu(gn(y)), no residual: the mask is recomputed from y, z is not read
-                call("primia_gn_relu_bwd", y, dz, dy, self.views[b + ".weight"], self.views[b + ".bias"], sm, si, psg, psb,
-                     self.N, y.shape[0] // self.N, C, self.groups, self.bn_ws, self.bn_ws_bytes, self.dt)
-            elif relu and g_out is not None and b in self.relu_masks:
-                # residual layer: mask bytes instead of z; keep_g = False: the masked gradient is not written either
-                call("primia_gn_bwd_mask", y, self.relu_masks[b], dz, dy, g_out if keep_g else None,
-                     self.views[b + ".weight"], sm, si, psg, psb, self.N, y.shape[0] // self.N, C, self.groups, self.bn_ws,
-                     self.bn_ws_bytes, self.dt)
-            else:
-                call("primia_gn_bwd", y, z, dz, dy, g_out, self.views[b + ".weight"], sm, si, psg, psb, self.N,
-                     y.shape[0] // self.N, C, self.groups, int(relu), self.bn_ws, self.bn_ws_bytes, self.dt)
-            if self.dp is None:  # plain training: dgamma / dbeta = sum over samples
-                call("primia_weighted_colsum", psg, self.ones_n, self._gviews[b + ".weight"], self.N, C)
-                call("primia_weighted_colsum", psb, self.ones_n, self._gviews[b + ".bias"], self.N, C)
-            return
-        if relu and g_out is not None and b in self.relu_masks and from_sums is not None:
-            call("primia_bn_bwd_mask_from_sums", y, self.relu_masks[b], dz, dy, g_out if keep_g else None,
-                 self.views[b + ".weight"], sm, si, self._gviews[b + ".weight"], self._gviews[b + ".bias"], from_sums[0],
-                 from_sums[1], y.shape[0], y.shape[1], self.dt)
-            return
-        if relu and g_out is not None and b in self.relu_masks:
-            call("primia_bn_bwd_mask", y, self.relu_masks[b], dz, dy, g_out if keep_g else None,
-                 self.views[b + ".weight"], sm, si,
-                 self._gviews[b + ".weight"], self._gviews[b + ".bias"], y.shape[0], y.shape[1], self.bn_ws,
-                 self.bn_ws_bytes, self.dt)
-            return
-        if relu and g_out is None:
-            # z = relu(bn(y)), no residual: the mask is recomputed from y, z is not read
-            call("primia_bn_relu_bwd", y, dz, dy, self.views[b + ".weight"], self.views[b + ".bias"], sm, si,
-                 self._gviews[b + ".weight"], self._gviews[b + ".bias"], y.shape[0], y.shape[1], self.bn_ws,
-                 self.bn_ws_bytes, self.dt)
-            return
-        call("primia_bn_bwd", y, z, dz, dy, g_out, self.views[b + ".weight"], sm, si, self._gviews[b + ".weight"],
-             self._gviews[b + ".bias"], y.shape[0], y.shape[1], int(relu), self.bn_ws, self.bn_ws_bytes, self.dt)
+            C = psg.shape[1]
+            call("primia_weighted_colsum", psg, self.ones_n, self._gviews[b + ".weight"], self.N, C)
+            call("primia_weighted_colsum", psb, self.ones_n, self._gviews[b + ".bias"], self.N, C)
 
     # a stage's LAST same-shape layer does not wait for a group that can no longer fill (layer4 at batch 256: groups of 2 for 3
     # layers): its weight gradient runs as soon as its dy exists instead of at the end of the backward pass (round 6)
@@ -820,6 +815,16 @@ class ResNet18Engine:
             torch.cuda.current_stream().wait_stream(self._wg_stream)
             self._wg_pending = False
 
+    @property
+    def _fuse_bwd_sums(self):
+        """Training BatchNorm statistics and no DP-SGD pass in flight: whatever completes a gradient may also form the
+        backward sums of the BatchNorm that consumes it (the *_bnsums entries).  Each site adds its own terms."""
+        return self.batch_stats and self.dp is None
+
+    @property
+    def _fuse_bwd_sums_bf16(self):
+        return self._fuse_bwd_sums and self.dtype == torch.bfloat16
+
     def _head_bnsums_ok(self):
         # primia_head_bwd_bnsums: 256 threads must be a multiple of the 16-byte chunks of a 512-channel row
         return 256 % (512 // (4 if self.dtype == torch.float32 else 8)) == 0
@@ -860,7 +865,8 @@ class ResNet18Engine:
         self._wgrad(blk.conv2.name, t[p + ".a1"], t[p + ".dy2"])
         # where the linear-halo kernels serve conv2, its data gradient also forms bn1's backward sums
         # (primia_conv2d_dgrad_bnsums): the reduction pass over (y1, da1) is dropped
-        slots = self._dgrad_bnsums_slots(blk.conv2.name) if self.norm == "batch" else 0
+        # (no DP or dtype term here: _dgrad_bnsums_slots has them)
+        slots = self._dgrad_bnsums_slots(blk.conv2.name) if self.batch_stats else 0
         if not slots:
             self._dgrad(blk.conv2.name, t[p + ".dy2"], t[p + ".da1"], False)
             self._bn_bwd(blk.conv1.name, t[p + ".y1"], t[p + ".a1"], t[p + ".da1"], t[p + ".dy1"], None, True)
@@ -900,7 +906,7 @@ class ResNet18Engine:
         # (primia_conv2d_dgrad_masked_acc_bnsums; 64 -> 64 layers): the previous block's bn2 (mode 2), or the stem's bn1
         # through the max-pool (mode 3) — the two most expensive reduction passes of the step (43 + 48 us)
         mode = 0
-        if self.norm == "batch" and self.dp is None and self.dtype == torch.bfloat16:
+        if self._fuse_bwd_sums_bf16:
             if prev is not None and prev.down is None and bn_name(prev.conv2.name) in self.relu_masks:
                 mode = 2
             elif prev is None and self._stem_bwd_fused_wanted():
@@ -932,39 +938,21 @@ class ResNet18Engine:
         t, p = self.t, blk.prefix
         dout, dy1, dyd = t[p + ".dout"], t[p + ".dy1"], t[p + ".dyd"]
         b2, bd = bn_name(blk.conv2.name), bn_name(blk.down.name)
-        masked = b2 in self.relu_masks
-        if masked and self.norm == "batch":
+        mask = self.relu_masks.get(b2)
+        if mask is not None and self.batch_stats:
             # bn2 and the downsample BatchNorm share the incoming gradient -> ONE fused backward pass (primia_bn_bwd_pair)
             (sm2, si2), (smd, sid) = self.save[b2], self.save[bd]
-            call("primia_bn_bwd_pair", t[p + ".y2"], t[p + ".yd"], dout, self.relu_masks[b2], t[p + ".dy2"], dyd,
+            call("primia_bn_bwd_pair", t[p + ".y2"], t[p + ".yd"], dout, mask, t[p + ".dy2"], dyd,
                  self.views[b2 + ".weight"], sm2, si2, self.views[bd + ".weight"], smd, sid, self._gviews[b2 + ".weight"],
                  self._gviews[b2 + ".bias"], self._gviews[bd + ".weight"], self._gviews[bd + ".bias"],
                  t[p + ".y2"].shape[0], t[p + ".y2"].shape[1], self.bn_ws, self.bn_ws_bytes, self.dt)
+            self._backward_conv2(blk)
         else:
-            # GroupNorm / frozen BatchNorm: the downsample's backward pass applies bn2's ReLU mask to dout itself
-            # (primia_gn_bwd_mask / primia_bn_frozen_bwd_mask on yd, below), so the masked gradient is not written here
-            self._bn_bwd(blk.conv2.name, t[p + ".y2"], t[p + ".out"], dout, t[p + ".dy2"], dout, True, keep_g=not masked)
-        self._backward_conv2(blk)
-        if masked and self.norm == "group":
-            (smd, sid), (psg, psb) = self.save[bd], self.ps_affine[bd]
-            yd = t[p + ".yd"]
-            call("primia_gn_bwd_mask", yd, self.relu_masks[b2], dout, dyd, None, self.views[bd + ".weight"], smd, sid, psg,
-                 psb, self.N, yd.shape[0] // self.N, yd.shape[1], self.groups, self.bn_ws, self.bn_ws_bytes, self.dt)
-            if self.dp is None:
-                call("primia_weighted_colsum", psg, self.ones_n, self._gviews[bd + ".weight"], self.N, yd.shape[1])
-                call("primia_weighted_colsum", psb, self.ones_n, self._gviews[bd + ".bias"], self.N, yd.shape[1])
-        elif masked and self.norm == "frozen":
-            # ... and so does the frozen downsample BatchNorm (primia_bn_frozen_bwd_mask on yd with bn2's mask bytes)
-            psg, psb = self.ps_affine[bd]
-            yd = t[p + ".yd"]
-            call("primia_bn_frozen_bwd_mask", yd, self.relu_masks[b2], dout, dyd, None, self.views[bd + ".weight"],
-                 self.views[bd + ".running_mean"], self.views[bd + ".running_var"], BN_EPS, psg, psb, self.N,
-                 yd.shape[0] // self.N, yd.shape[1], self.bn_ws, self.bn_ws_bytes, self.dt)
-            if self.dp is None:
-                call("primia_weighted_colsum", psg, self.ones_n, self._gviews[bd + ".weight"], self.N, yd.shape[1])
-                call("primia_weighted_colsum", psb, self.ones_n, self._gviews[bd + ".bias"], self.N, yd.shape[1])
-        elif not masked:
-            self._bn_bwd(blk.down.name, t[p + ".yd"], None, dout, dyd, None, False)
+            # no paired kernel: two calls.  With a mask the downsample norm's backward pass applies bn2's ReLU mask to dout
+            # itself, so bn2's does not write the masked gradient
+            self._bn_bwd(blk.conv2.name, t[p + ".y2"], t[p + ".out"], dout, t[p + ".dy2"], dout, True, keep_g=mask is None)
+            self._backward_conv2(blk)
+            self._bn_bwd(blk.down.name, t[p + ".yd"], None, dout, dyd, None, False, mask=mask)
         c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
         if self.wgrad_overlap == 1:
             self._join_wgrad_stream()
@@ -974,8 +962,7 @@ class ResNet18Engine:
         # layer3.0 / layer4.0)
         pslots = 0
         pb2 = bn_name(prev.conv2.name) if prev is not None else None
-        if (self.norm == "batch" and self.dp is None and prev is not None and prev.down is None and pb2 in self.relu_masks
-                and self.dtype == torch.bfloat16):
+        if self._fuse_bwd_sums_bf16 and prev is not None and prev.down is None and pb2 in self.relu_masks:
             if getattr(c1, "pair_bnsums_slots", None) is None:
                 c1.pair_bnsums_slots = query("primia_conv_dgrad_pair_bnsums_slots", c1.desc, self.dt)
             pslots = c1.pair_bnsums_slots
@@ -1014,8 +1001,7 @@ class ResNet18Engine:
         hw = self.final_hw
         blocks = self.spec.blocks
         lb2 = bn_name(blocks[-1].conv2.name)
-        if (self.norm == "batch" and self.dp is None and blocks[-1].down is None and lb2 in self.relu_masks
-                and self._head_bnsums_ok()):
+        if self._fuse_bwd_sums and blocks[-1].down is None and lb2 in self.relu_masks and self._head_bnsums_ok():
             # ... forming the backward sums of the last block's bn2 on the way (one value per image and channel)
             sums = self._bwd_sums("head", N, 512)
             sml, sil = self.save[lb2]
@@ -1039,7 +1025,7 @@ class ResNet18Engine:
         # pooled resolution, then conv1's weight gradient forming its dy tiles on the fly (primia_stem_bwd_fused)
         stem_bwd_fused = self._stem_bwd_fused_wanted()
         self.stem_bwd_fused_active = stem_bwd_fused
-        pool_sums, self._pool_sums = getattr(self, "_pool_sums", None), None
+        pool_sums, self._pool_sums = self._pool_sums, None
         if stem_bwd_fused:
             sm, si = self.save["bn1"]
             c = self.convs["conv1"]
@@ -1064,15 +1050,13 @@ class ResNet18Engine:
             call("primia_bn_relu_maxpool_bwd", t["stem.y"], t["pool.out"], t["pool.dout"], self.pool_argmax, t["stem.dy"],
                  self.views["bn1.weight"], self.views["bn1.bias"], sm, si, self._gviews["bn1.weight"],
                  self._gviews["bn1.bias"], N, hw, hw, 64, self.bn_ws, self.bn_ws_bytes, self.dt)
-        elif getattr(self, "_stem_fused_gn", False):
+        elif self._stem_fused_gn:
             sm, si = self.save["bn1"]
             psg, psb = self.ps_affine["bn1"]
             call("primia_gn_relu_maxpool_bwd", t["stem.y"], t["pool.out"], t["pool.dout"], self.pool_argmax, t["stem.dy"],
                  self.views["bn1.weight"], self.views["bn1.bias"], sm, si, psg, psb, N, hw, hw, 64, self.groups,
                  self.bn_ws, self.bn_ws_bytes, self.dt)
-            if self.dp is None:
-                call("primia_weighted_colsum", psg, self.ones_n, self._gviews["bn1.weight"], N, 64)
-                call("primia_weighted_colsum", psb, self.ones_n, self._gviews["bn1.bias"], N, 64)
+            self._reduce_affine("bn1")
         else:
             if self.spec.pooling == "max":
                 call("primia_maxpool3x3s2_bwd", t["pool.dout"], self.pool_argmax, t["stem.dz"], N, hw, hw, 64, self.dt)

@@ -123,7 +123,7 @@ def _sync_moments(root):
 def _fingerprint(eng, g):
     """Data pointers of every buffer the captured step reads or writes that may be (re)allocated after construction."""
     ts = [eng.flat, eng._grads, eng.dw_acc, eng.wgrad_ws, eng.x0, eng.x0p, eng.pool_argmax, eng.stat_sums, eng.bn_ws,
-          eng.feat, eng.dfeat, eng.logits, eng.dlogits, eng.loss, eng.class_weight, getattr(eng, "_stem_sums", None),
+          eng.feat, eng.dfeat, eng.logits, eng.dlogits, eng.loss, eng.class_weight, eng._stem_sums,
           g.x, g.target, g.hyper]
     ts += list(eng.t.values()) + list(eng.relu_masks.values())
     for sm, si in eng.save.values():
