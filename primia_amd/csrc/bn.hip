@@ -957,51 +957,112 @@ static inline void reduce_geometry(long M, int C, int& nblk, long& rows_per_bloc
     nblk = (int)((M + rows_per_block - 1) / rows_per_block);
 }
 
-static inline int stream_blocks(long nchunks) {
-    long b = (nchunks + 255) / 256;
-    return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
-}
+// =================================================================================================
+// Host layer.  A BatchNorm call is sums -> finalize -> one streaming apply pass; each stage below holds the only copy of
+// its launch, and the entry points at the end of the file compose them.
+// =================================================================================================
 
+// Partial sums [n][2][C] of one reduction: written by a pass here, or by the producer of the tensor (*_from_sums)
+struct Sums {
+    const float* p;
+    int n;
+};
+
+// column sums of (y, y * y)
 template <typename T>
-static int bn_fwd_train_impl(const void* y, const void* residual, void* z, const float* gamma,
-                             const float* beta, float* running_mean, float* running_var,
-                             float* save_mean, float* save_invstd, long M, int C, float eps,
-                             float momentum, int relu, float* partials, hipStream_t st) {
+static Sums batch_sums(const void* y, long M, int C, float* workspace, hipStream_t st) {
     int nblk;
     long rpb;
     reduce_geometry(M, C, nblk, rpb);
-    StatsFn<T> f{(const T*)y};
-    colreduce2_kernel<T, StatsFn<T>><<<nblk, 256, 0, st>>>(f, M, C, rpb, partials);
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partials, nblk, C, M, 0, eps, momentum, save_mean, save_invstd,
-                                           running_mean, running_var);
-    const long nchunks = M * C / Chunk<T>::N;
-    bn_apply_kernel<T><<<stream_blocks(nchunks), 256, 0, st>>>((const T*)y, (const T*)residual, (T*)z, gamma,
-                                                               beta, save_mean, save_invstd, eps, 0, nchunks,
-                                                               C, relu);
-    return launch_status();
+    colreduce2_kernel<T, StatsFn<T>><<<nblk, 256, 0, st>>>(StatsFn<T>{(const T*)y}, M, C, rpb, workspace);
+    return {workspace, nblk};
 }
 
+// column sums of (g, g * xhat), g = dz under the ReLU mask: from z, from the forward pass's mask bytes, or (beta given)
+// recomputed from y
 template <typename T>
-static int bn_bwd_impl(const void* y, const void* z, const void* dz, void* dy, void* g_out,
-                       const float* gamma, const float* save_mean, const float* save_invstd,
-                       float* dgamma, float* dbeta, long M, int C, int relu, float* partials,
-                       hipStream_t st, const float* beta = nullptr, const uint8_t* mask = nullptr) {
+static Sums bwd_sums(const void* y, const void* z, const uint8_t* mask, const void* dz, const float* gamma,
+                     const float* beta, const float* mean, const float* invstd, long M, int C, float* workspace,
+                     hipStream_t st) {
     int nblk;
     long rpb;
     reduce_geometry(M, C, nblk, rpb);
-    BwdFn<T> f{(const T*)y, relu ? (const T*)z : nullptr, (const T*)dz, save_mean, save_invstd, gamma, beta, mask};
-    colreduce2_kernel<T, BwdFn<T>><<<nblk, 256, 0, st>>>(f, M, C, rpb, partials);
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partials, nblk, C, M, 1, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr);
+    BwdFn<T> f{(const T*)y, (const T*)z, (const T*)dz, mean, invstd, gamma, beta, mask};
+    colreduce2_kernel<T, BwdFn<T>><<<nblk, 256, 0, st>>>(f, M, C, rpb, workspace);
+    return {workspace, nblk};
+}
+
+static void finalize(Sums s, int C, long M, int mode, float eps, float momentum, float* out1, float* out2,
+                     float* running_mean, float* running_var, hipStream_t st) {
+    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(s.p, s.n, C, M, mode, eps, momentum, out1, out2,
+                                                                  running_mean, running_var);
+}
+// sums of (y, y * y) -> mean / invstd, running statistics (may be null)
+static void finalize_stats(Sums s, int C, long M, float eps, float momentum, float* save_mean, float* save_invstd,
+                           float* running_mean, float* running_var, hipStream_t st) {
+    finalize(s, C, M, 0, eps, momentum, save_mean, save_invstd, running_mean, running_var, st);
+}
+// sums of (g, g * xhat) -> dbeta / dgamma
+static void finalize_grads(Sums s, int C, long M, float* dbeta, float* dgamma, hipStream_t st) {
+    finalize(s, C, M, 1, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr, st);
+}
+
+// z = act(bn(y) [+ residual]) from (mean, invstd), or with eval = 1 from (running_mean, running_var); relu_mask: also
+// the mask bytes.  inl.partials set: the statistics are finalized inside the kernel (primia_bn_fwd_train_apply_inline)
+template <typename T>
+static void apply(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma, const float* beta,
+                  const float* mean, const float* invstd_or_var, float eps, int eval, long M, int C, int relu,
+                  hipStream_t st, BnInline inl = BnInline{}) {
     const long nchunks = M * C / Chunk<T>::N;
-    if (nchunks >= 4L * 2048 * 256)     // two chunks per thread and trip on the large tensors
-        bn_bwd_apply_kernel<T, 2><<<stream_blocks(nchunks), 256, 0, st>>>(
-            (const T*)y, relu ? (const T*)z : nullptr, (const T*)dz, (T*)dy, (T*)g_out, gamma, save_mean,
-            save_invstd, dbeta, dgamma, (float)(1.0 / (double)M), nchunks, C, beta, mask);
-    else
-        bn_bwd_apply_kernel<T><<<stream_blocks(nchunks), 256, 0, st>>>(
-            (const T*)y, relu ? (const T*)z : nullptr, (const T*)dz, (T*)dy, (T*)g_out, gamma, save_mean,
-            save_invstd, dbeta, dgamma, (float)(1.0 / (double)M), nchunks, C, beta, mask);
-    return launch_status();
+    const int grid = stream_blocks(nchunks);
+    if (inl.partials && grid < (C + 3) / 4) {      // fewer blocks than finalize slices (tiny tensors): the two-launch form
+        finalize_stats({inl.partials, inl.nblk}, C, inl.M, inl.eps, inl.momentum, inl.save_mean, inl.save_invstd,
+                       inl.running_mean, inl.running_var, st);
+        inl = BnInline{};
+    }
+    bn_apply_kernel<T><<<grid, 256, 0, st>>>((const T*)y, (const T*)residual, (T*)z, gamma, beta, mean, invstd_or_var, eps,
+                                             eval, nchunks, C, relu, relu_mask, inl);
+}
+
+// dy = gamma * invstd * (g - dbeta / M - xhat * dgamma / M), g as in bwd_sums; optionally g_out = g
+template <typename T>
+static void bwd_apply(const void* y, const void* z, const uint8_t* mask, const void* dz, void* dy, void* g_out,
+                      const float* gamma, const float* beta, const float* mean, const float* invstd, const float* dbeta,
+                      const float* dgamma, long M, int C, hipStream_t st) {
+    const long nchunks = M * C / Chunk<T>::N;
+    // two chunks per thread and trip on the large tensors
+    auto kern = nchunks >= 4L * 2048 * 256 ? bn_bwd_apply_kernel<T, 2> : bn_bwd_apply_kernel<T, 1>;
+    kern<<<stream_blocks(nchunks), 256, 0, st>>>((const T*)y, (const T*)z, (const T*)dz, (T*)dy, (T*)g_out, gamma, mean,
+                                                 invstd, dbeta, dgamma, (float)(1.0 / (double)M), nchunks, C, beta, mask);
+}
+
+// Training forward pass (primia_bn_fwd_train, _from_sums, _mask): sums given or reduced here -> statistics -> apply
+static int bn_fwd_train(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
+                        const float* beta, float* running_mean, float* running_var, float* save_mean, float* save_invstd,
+                        const float* sums, int slots, long M, int C, float eps, float momentum, int relu, void* workspace,
+                        int dtype, hipStream_t st) {
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const Sums s = sums ? Sums{sums, slots} : batch_sums<T>(y, M, C, (float*)workspace, st);
+        finalize_stats(s, C, M, eps, momentum, save_mean, save_invstd, running_mean, running_var, st);
+        apply<T>(y, residual, z, relu_mask, gamma, beta, save_mean, save_invstd, eps, 0, M, C, relu, st);
+        return launch_status();
+    });
+}
+
+// Backward pass (primia_bn_bwd, _bwd_mask, _relu_bwd and their _from_sums forms): sums given or reduced here -> dgamma /
+// dbeta -> apply
+static int bn_bwd(const void* y, const void* z, const uint8_t* relu_mask, const void* dz, void* dy, void* g_out,
+                  const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* dgamma,
+                  float* dbeta, const float* sums, int slots, long M, int C, void* workspace, int dtype, hipStream_t st) {
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const Sums s = sums ? Sums{sums, slots}
+                            : bwd_sums<T>(y, z, relu_mask, dz, gamma, beta, save_mean, save_invstd, M, C, (float*)workspace, st);
+        finalize_grads(s, C, M, dbeta, dgamma, st);
+        bwd_apply<T>(y, z, relu_mask, dz, dy, g_out, gamma, beta, save_mean, save_invstd, dbeta, dgamma, M, C, st);
+        return launch_status();
+    });
 }
 
 // =================================================================================================
@@ -1150,27 +1211,10 @@ __global__ __launch_bounds__(256) void bn_bwd_pair_apply_kernel(
 }
 
 template <typename T>
-static int bn_bwd_pair_impl(const void* y2, const void* yd, const void* dz, const uint8_t* mask, void* dy2, void* dyd,
-                            const float* gamma2, const float* mean2, const float* invstd2, const float* gammad,
-                            const float* meand, const float* invstdd, float* dgamma2, float* dbeta2, float* dgammad,
-                            float* dbetad, long M, int C, float* partials, hipStream_t st) {
-    int nblk;
-    long rpb;
-    reduce_geometry(M, C, nblk, rpb);
-    bn_bwd_pair_reduce_kernel<T><<<nblk, 256, 0, st>>>((const T*)y2, (const T*)yd, (const T*)dz, mask, mean2, invstd2,
-                                                       meand, invstdd, M, C, rpb, partials);
-    bn_finalize3_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partials, nblk, C, dbeta2, dgamma2, dbetad, dgammad);
-    const long nchunks = M * C / Chunk<T>::N;
-    bn_bwd_pair_apply_kernel<T><<<stream_blocks(nchunks), 256, 0, st>>>(
-        (const T*)y2, (const T*)yd, (const T*)dz, mask, (T*)dy2, (T*)dyd, gamma2, mean2, invstd2, gammad, meand,
-        invstdd, dbeta2, dgamma2, dgammad, (float)(1.0 / (double)M), nchunks, C);
-    return launch_status();
-}
-
-template <typename T>
 static void launch_bn_relu_pool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
-                                    const float* mean, const float* invstd, int N, int H, int W, int C, int Ho, int Wo,
-                                    hipStream_t st, int G = 0) {
+                                    const float* mean, const float* invstd, int N, int H, int W, int C, hipStream_t st,
+                                    int G = 0) {
+    const int Ho = pool_out(H), Wo = pool_out(W);
     // Two windows along W per thread where the pooled row is even.  Variants measured and not kept (profiles/
     // r03_negative_results.txt): two windows along H as well (265 vs 258 us generic, 236 vs 225 us packed keys, batch
     // 256), whole output rows per block (no gain).
@@ -1190,31 +1234,28 @@ static void launch_bn_relu_pool_fwd(const void* y, void* pooled, uint8_t* argmax
 }
 
 // GroupNorm + ReLU + max-pool apply pass (statistics [N][G] already formed): csrc/gn.hip
-void launch_gn_relu_pool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
-                             const float* mean, const float* invstd, int N, int H, int W, int C, int G, int dtype,
-                             hipStream_t st) {
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    if (dtype == PRIMIA_F32)
-        launch_bn_relu_pool_fwd<float>(y, pooled, argmax, gamma, beta, mean, invstd, N, H, W, C, Ho, Wo, st, G);
-    else
-        launch_bn_relu_pool_fwd<bf16>(y, pooled, argmax, gamma, beta, mean, invstd, N, H, W, C, Ho, Wo, st, G);
+int launch_gn_relu_pool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
+                            const float* mean, const float* invstd, int N, int H, int W, int C, int G, int dtype,
+                            hipStream_t st) {
+    return with_dtype(dtype, [&](auto tag) {
+        launch_bn_relu_pool_fwd<decltype(tag)>(y, pooled, argmax, gamma, beta, mean, invstd, N, H, W, C, st, G);
+        return launch_status();
+    });
 }
 
-template <typename T>
-static int bn_relu_pool_fwd_impl(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
-                                 float* running_mean, float* running_var, float* save_mean, float* save_invstd, int N,
-                                 int H, int W, int C, float eps, float momentum, float* partials, hipStream_t st) {
-    const long M = (long)N * H * W;
-    int nblk;
-    long rpb;
-    reduce_geometry(M, C, nblk, rpb);
-    StatsFn<T> f{(const T*)y};
-    colreduce2_kernel<T, StatsFn<T>><<<nblk, 256, 0, st>>>(f, M, C, rpb, partials);
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partials, nblk, C, M, 0, eps, momentum, save_mean, save_invstd,
-                                                       running_mean, running_var);
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    launch_bn_relu_pool_fwd<T>(y, pooled, argmax, gamma, beta, save_mean, save_invstd, N, H, W, C, Ho, Wo, st);
-    return launch_status();
+// Stem forward pass (primia_bn_relu_maxpool_fwd, _from_sums): sums given or reduced here -> statistics -> pooled apply
+static int bn_relu_pool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
+                            float* running_mean, float* running_var, float* save_mean, float* save_invstd,
+                            const float* sums, int slots, int N, int H, int W, int C, float eps, float momentum,
+                            void* workspace, int dtype, hipStream_t st) {
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const long M = (long)N * H * W;
+        const Sums s = sums ? Sums{sums, slots} : batch_sums<T>(y, M, C, (float*)workspace, st);
+        finalize_stats(s, C, M, eps, momentum, save_mean, save_invstd, running_mean, running_var, st);
+        launch_bn_relu_pool_fwd<T>(y, pooled, argmax, gamma, beta, save_mean, save_invstd, N, H, W, C, st);
+        return launch_status();
+    });
 }
 
 // The same apply pass for even H and W, one thread per 2 x 2 block of input pixels (x one 16-byte channel chunk).
@@ -1311,7 +1352,7 @@ static int bn_relu_pool_bwd_impl(const void* y, const void* pooled, const void* 
                                  const float* save_invstd, float* dgamma, float* dbeta, int N, int H, int W, int C,
                                  float* partials, hipStream_t st) {
     const long M = (long)N * H * W;
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const int Ho = pool_out(H), Wo = pool_out(W);
     const long Mp = (long)N * Ho * Wo;
     int nblk;
     long rpb;
@@ -1319,7 +1360,7 @@ static int bn_relu_pool_bwd_impl(const void* y, const void* pooled, const void* 
     PoolScatterFn<T> f{(const T*)pooled, (const T*)dpooled, argmax, (const T*)y, save_mean, save_invstd, gamma, beta,
                        H, W, C, Ho, Wo, {}, {}, {}, {}, false};
     colreduce2_kernel<T, PoolScatterFn<T>><<<nblk, 256, 0, st>>>(f, Mp, C, rpb, partials);
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partials, nblk, C, M, 1, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr);
+    finalize_grads({partials, nblk}, C, M, dbeta, dgamma, st);
     if (!dy) return launch_status();   // sums only: the apply pass runs inside the consumer (primia_stem_bwd_fused)
     const long nchunks = M * C / Chunk<T>::N;
     if (H % 2 == 0 && W % 2 == 0) {
@@ -1339,39 +1380,7 @@ static int bn_relu_pool_bwd_impl(const void* y, const void* pooled, const void* 
 
 using namespace primia;
 
-template <typename T>
-static int bn_fwd_train_pair_impl(const void* y2, const void* yd, void* z, uint8_t* relu_mask, const float* gamma2,
-                                  const float* beta2, float* rm2, float* rv2, float* sm2, float* si2, const float* sums2,
-                                  int slots2, const float* gammad, const float* betad, float* rmd, float* rvd, float* smd,
-                                  float* sid, const float* sumsd, int slotsd, long M, int C, float eps, float momentum,
-                                  float* ws, hipStream_t st) {
-    int nblk;
-    long rpb;
-    reduce_geometry(M, C, nblk, rpb);
-    const float* partd = sumsd;
-    int nd = slotsd;
-    if (!sumsd) {
-        StatsFn<T> fd{(const T*)yd};
-        colreduce2_kernel<T, StatsFn<T>><<<nblk, 256, 0, st>>>(fd, M, C, rpb, ws);
-        partd = ws;
-        nd = nblk;
-    }
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partd, nd, C, M, 0, eps, momentum, smd, sid, rmd, rvd);
-    const float* part = sums2;
-    int n2 = slots2;
-    if (!sums2) {
-        StatsFn<T> f2{(const T*)y2};
-        colreduce2_kernel<T, StatsFn<T>><<<nblk, 256, 0, st>>>(f2, M, C, rpb, ws);
-        part = ws;
-        n2 = nblk;
-    }
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(part, n2, C, M, 0, eps, momentum, sm2, si2, rm2, rv2);
-    const long nchunks = M * C / Chunk<T>::N;
-    bn_apply_pair_kernel<T><<<stream_blocks(nchunks), 256, 0, st>>>((const T*)y2, (const T*)yd, (T*)z, gamma2, beta2, sm2,
-                                                                    si2, gammad, betad, smd, sid, nchunks, C, relu_mask);
-    return launch_status();
-}
-
+// Every entry point: pointers, shape (bn_shape_ok refuses an unknown dtype), workspace, and only then launches.
 extern "C" {
 
 int64_t primia_bn_workspace_bytes(int64_t M, int C) {
@@ -1388,16 +1397,11 @@ int primia_bn_fwd_train(const void* y, const void* residual, void* z, const floa
     PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
     PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
     if (workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_fwd_train_impl<float>(y, residual, z, gamma, beta, running_mean, running_var, save_mean,
-                                        save_invstd, M, C, eps, momentum, relu, (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return bn_fwd_train_impl<bf16>(y, residual, z, gamma, beta, running_mean, running_var, save_mean,
-                                       save_invstd, M, C, eps, momentum, relu, (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
+    return bn_fwd_train(y, residual, z, nullptr, gamma, beta, running_mean, running_var, save_mean, save_invstd, nullptr, 0,
+                        M, C, eps, momentum, relu, workspace, dtype, (hipStream_t)stream);
 }
 
+// `sums` has the layout of the partial blocks: [slots][2][C]
 int primia_bn_fwd_train_from_sums(const void* y, const void* residual, void* z, const float* gamma,
                                   const float* beta, float* running_mean, float* running_var, float* save_mean,
                                   float* save_invstd, const float* sums, int slots, int64_t M, int C, float eps,
@@ -1405,24 +1409,21 @@ int primia_bn_fwd_train_from_sums(const void* y, const void* residual, void* z, 
     PRIMIA_REQUIRE(y && z && gamma && beta && save_mean && save_invstd && sums && slots >= 1);
     PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
     PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
-    hipStream_t st = (hipStream_t)stream;
-    // `sums` has the layout of the partial blocks: [slots][2][C]
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(sums, slots, C, M, 0, eps, momentum, save_mean, save_invstd,
-                                                       running_mean, running_var);
-    if (dtype == PRIMIA_F32) {
-        const long nchunks = M * C / 4;
-        bn_apply_kernel<float><<<stream_blocks(nchunks), 256, 0, st>>>((const float*)y, (const float*)residual,
-                                                                       (float*)z, gamma, beta, save_mean, save_invstd,
-                                                                       eps, 0, nchunks, C, relu);
-    } else if (dtype == PRIMIA_BF16) {
-        const long nchunks = M * C / 8;
-        bn_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, (const bf16*)residual, (bf16*)z,
-                                                                      gamma, beta, save_mean, save_invstd, eps, 0,
-                                                                      nchunks, C, relu);
-    } else {
-        return PRIMIA_ERR_ARG;
-    }
-    return launch_status();
+    return bn_fwd_train(y, residual, z, nullptr, gamma, beta, running_mean, running_var, save_mean, save_invstd, sums, slots,
+                        M, C, eps, momentum, relu, nullptr, dtype, (hipStream_t)stream);
+}
+
+int primia_bn_fwd_train_mask(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
+                             const float* beta, float* running_mean, float* running_var, float* save_mean,
+                             float* save_invstd, const float* sums, int slots, int64_t M, int C, float eps,
+                             float momentum, void* workspace, int64_t workspace_bytes, int dtype,
+                             primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && z && relu_mask && gamma && beta && save_mean && save_invstd && (sums || workspace));
+    PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
+    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype) && (!sums || slots >= 1));
+    if (!sums && workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
+    return bn_fwd_train(y, residual, z, relu_mask, gamma, beta, running_mean, running_var, save_mean, save_invstd, sums,
+                        slots, M, C, eps, momentum, 1, workspace, dtype, (hipStream_t)stream);
 }
 
 // primia_bn_fwd_train_from_sums / primia_bn_fwd_train_mask with the finalize launch folded into the apply kernel
@@ -1435,225 +1436,46 @@ int primia_bn_fwd_train_apply_inline(const void* y, const void* residual, void* 
     PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
     PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
     hipStream_t st = (hipStream_t)stream;
-    const long nchunks = M * C / (dtype == PRIMIA_F32 ? 4 : 8);
-    const int grid = stream_blocks(nchunks);
-    if (relu_mask) relu = 1;
-    if (grid < (C + 3) / 4) {      // fewer blocks than finalize slices (tiny tensors): the two-launch form
-        bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(sums, slots, C, M, 0, eps, momentum, save_mean, save_invstd,
-                                                           running_mean, running_var);
-        if (dtype == PRIMIA_F32)
-            bn_apply_kernel<float><<<grid, 256, 0, st>>>((const float*)y, (const float*)residual, (float*)z, gamma, beta, save_mean,
-                                                          save_invstd, eps, 0, nchunks, C, relu, relu_mask);
-        else
-            bn_apply_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)y, (const bf16*)residual, (bf16*)z, gamma, beta, save_mean,
-                                                         save_invstd, eps, 0, nchunks, C, relu, relu_mask);
+    return with_dtype(dtype, [&](auto tag) {
+        BnInline q{sums, slots, (long)M, eps, momentum, running_mean, running_var, save_mean, save_invstd, flags};
+        apply<decltype(tag)>(y, residual, z, relu_mask, gamma, beta, save_mean, save_invstd, eps, 0, M, C,
+                             relu_mask ? 1 : relu, st, q);
         return launch_status();
-    }
-    BnInline q{sums, slots, (long)M, eps, momentum, running_mean, running_var, save_mean, save_invstd, flags};
-    if (dtype == PRIMIA_F32)
-        bn_apply_kernel<float><<<grid, 256, 0, st>>>((const float*)y, (const float*)residual, (float*)z, gamma, beta, save_mean,
-                                                      save_invstd, eps, 0, nchunks, C, relu, relu_mask, q);
-    else if (dtype == PRIMIA_BF16)
-        bn_apply_kernel<bf16><<<grid, 256, 0, st>>>((const bf16*)y, (const bf16*)residual, (bf16*)z, gamma, beta, save_mean,
-                                                     save_invstd, eps, 0, nchunks, C, relu, relu_mask, q);
-    else
-        return PRIMIA_ERR_ARG;
-    return launch_status();
+    });
+}
+
+// relu_mask (may be null): also the 1-bit ReLU mask of the stored z, the bytes primia_bn_frozen_bwd_mask reads
+static int bn_fwd_eval(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
+                       const float* beta, const float* running_mean, const float* running_var, int64_t M, int C, float eps,
+                       int relu, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && z && gamma && beta && running_mean && running_var);
+    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
+    return with_dtype(dtype, [&](auto tag) {
+        apply<decltype(tag)>(y, residual, z, relu_mask, gamma, beta, running_mean, running_var, eps, 1, M, C, relu,
+                             (hipStream_t)stream);
+        return launch_status();
+    });
 }
 
 int primia_bn_fwd_eval(const void* y, const void* residual, void* z, const float* gamma,
                        const float* beta, const float* running_mean, const float* running_var,
                        int64_t M, int C, float eps, int relu, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && z && gamma && beta && running_mean && running_var);
-    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32) {
-        const long nchunks = M * C / 4;
-        bn_apply_kernel<float><<<stream_blocks(nchunks), 256, 0, st>>>(
-            (const float*)y, (const float*)residual, (float*)z, gamma, beta, running_mean, running_var, eps, 1,
-            nchunks, C, relu);
-    } else if (dtype == PRIMIA_BF16) {
-        const long nchunks = M * C / 8;
-        bn_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>(
-            (const bf16*)y, (const bf16*)residual, (bf16*)z, gamma, beta, running_mean, running_var, eps, 1,
-            nchunks, C, relu);
-    } else {
-        return PRIMIA_ERR_ARG;
-    }
-    return launch_status();
+    return bn_fwd_eval(y, residual, z, nullptr, gamma, beta, running_mean, running_var, M, C, eps, relu, dtype, stream);
 }
 
-// primia_bn_fwd_eval on a residual layer, plus the 1-bit ReLU mask of the stored z (the bytes primia_bn_frozen_bwd_mask reads)
+// primia_bn_fwd_eval on a residual layer, plus the mask bytes
 int primia_bn_fwd_eval_mask(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
                             const float* beta, const float* running_mean, const float* running_var, int64_t M, int C,
                             float eps, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && z && relu_mask && gamma && beta && running_mean && running_var);
-    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32) {
-        const long nchunks = M * C / 4;
-        bn_apply_kernel<float><<<stream_blocks(nchunks), 256, 0, st>>>(
-            (const float*)y, (const float*)residual, (float*)z, gamma, beta, running_mean, running_var, eps, 1,
-            nchunks, C, 1, relu_mask);
-    } else if (dtype == PRIMIA_BF16) {
-        const long nchunks = M * C / 8;
-        bn_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>(
-            (const bf16*)y, (const bf16*)residual, (bf16*)z, gamma, beta, running_mean, running_var, eps, 1,
-            nchunks, C, 1, relu_mask);
-    } else {
-        return PRIMIA_ERR_ARG;
-    }
-    return launch_status();
-}
-
-int primia_bn_bwd(const void* y, const void* z, const void* dz, void* dy, void* g_out,
-                  const float* gamma, const float* save_mean, const float* save_invstd,
-                  float* dgamma, float* dbeta, int64_t M, int C, int relu, void* workspace,
-                  int64_t workspace_bytes, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && dz && dy && gamma && save_mean && save_invstd && dgamma && dbeta && workspace);
-    PRIMIA_REQUIRE(!relu || z);
-    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
-    if (workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_bwd_impl<float>(y, z, dz, dy, g_out, gamma, save_mean, save_invstd, dgamma, dbeta, M, C, relu,
-                                  (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return bn_bwd_impl<bf16>(y, z, dz, dy, g_out, gamma, save_mean, save_invstd, dgamma, dbeta, M, C, relu,
-                                 (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
-}
-
-
-int primia_bn_relu_maxpool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
-                               float* running_mean, float* running_var, float* save_mean, float* save_invstd, int N,
-                               int H, int W, int C, float eps, float momentum, void* workspace,
-                               int64_t workspace_bytes, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && pooled && argmax && gamma && beta && save_mean && save_invstd && workspace);
-    PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
-    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && bn_shape_ok((long)N * H * W, C, dtype));
-    if (workspace_bytes < primia_bn_workspace_bytes((int64_t)N * H * W, C)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_relu_pool_fwd_impl<float>(y, pooled, argmax, gamma, beta, running_mean, running_var, save_mean,
-                                            save_invstd, N, H, W, C, eps, momentum, (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return bn_relu_pool_fwd_impl<bf16>(y, pooled, argmax, gamma, beta, running_mean, running_var, save_mean,
-                                           save_invstd, N, H, W, C, eps, momentum, (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
+    PRIMIA_REQUIRE(relu_mask);
+    return bn_fwd_eval(y, residual, z, relu_mask, gamma, beta, running_mean, running_var, M, C, eps, 1, dtype, stream);
 }
 
 int primia_bn_finalize_stats(const float* sums, int slots, int64_t M, int C, float eps, float momentum, float* running_mean,
                              float* running_var, float* save_mean, float* save_invstd, primia_stream_t stream) {
     PRIMIA_REQUIRE(sums && slots >= 1 && M > 0 && C > 0 && save_mean && save_invstd);
     PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, (hipStream_t)stream>>>(sums, slots, C, M, 0, eps, momentum, save_mean,
-                                                                                  save_invstd, running_mean, running_var);
-    return launch_status();
-}
-
-int primia_bn_relu_maxpool_fwd_from_sums(const void* y, void* pooled, uint8_t* argmax, const float* gamma,
-                                         const float* beta, float* running_mean, float* running_var,
-                                         float* save_mean, float* save_invstd, const float* sums, int slots, int N,
-                                         int H, int W, int C, float eps, float momentum, int dtype,
-                                         primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && pooled && argmax && gamma && beta && save_mean && save_invstd && sums && slots >= 1);
-    PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
-    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && bn_shape_ok((long)N * H * W, C, dtype));
-    hipStream_t st = (hipStream_t)stream;
-    const long M = (long)N * H * W;
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(sums, slots, C, M, 0, eps, momentum, save_mean, save_invstd,
-                                                       running_mean, running_var);
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    if (dtype == PRIMIA_F32) {
-        launch_bn_relu_pool_fwd<float>(y, pooled, argmax, gamma, beta, save_mean, save_invstd, N, H, W, C, Ho, Wo, st);
-    } else if (dtype == PRIMIA_BF16) {
-        launch_bn_relu_pool_fwd<bf16>(y, pooled, argmax, gamma, beta, save_mean, save_invstd, N, H, W, C, Ho, Wo, st);
-    } else {
-        return PRIMIA_ERR_ARG;
-    }
-    return launch_status();
-}
-
-int primia_bn_relu_maxpool_bwd(const void* y, const void* pooled, const void* dpooled, const uint8_t* argmax,
-                               void* dy, const float* gamma, const float* beta, const float* save_mean,
-                               const float* save_invstd, float* dgamma, float* dbeta, int N, int H, int W, int C,
-                               void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && pooled && dpooled && argmax && gamma && beta && save_mean && save_invstd && dgamma &&
-                   dbeta && workspace);   // dy may be null: dgamma / dbeta only (see primia_stem_bwd_fused)
-    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && bn_shape_ok((long)N * H * W, C, dtype));
-    PRIMIA_REQUIRE((long)N * H * W < (1L << 31));
-    if (workspace_bytes < primia_bn_workspace_bytes((int64_t)N * H * W, C)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_relu_pool_bwd_impl<float>(y, pooled, dpooled, argmax, dy, gamma, beta, save_mean, save_invstd, dgamma,
-                                            dbeta, N, H, W, C, (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return bn_relu_pool_bwd_impl<bf16>(y, pooled, dpooled, argmax, dy, gamma, beta, save_mean, save_invstd, dgamma,
-                                           dbeta, N, H, W, C, (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
-}
-
-// primia_bn_relu_maxpool_bwd(dy = null) whose reduction pass over (pooled, dpooled) already happened in the write-back of the data
-// gradient that produced dpooled (primia_conv2d_dgrad_masked_acc_bnsums, mode 3): `sums` = its partials [slots][2][C].
-int primia_bn_relu_maxpool_bwd_from_sums(const void* y, const void* pooled, const void* dpooled, const uint8_t* argmax,
-                                         const float* gamma, const float* beta, const float* save_mean,
-                                         const float* save_invstd, float* dgamma, float* dbeta, const float* sums, int slots,
-                                         int N, int H, int W, int C, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && pooled && dpooled && argmax && gamma && beta && save_mean && save_invstd && dgamma && dbeta && sums);
-    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && slots >= 1 && bn_shape_ok((long)N * H * W, C, dtype));
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_BF16)
-        bn_finalize_pool_kernel<bf16><<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(
-            sums, slots, C, dbeta, dgamma, gamma, beta, save_mean, save_invstd, (const bf16*)pooled, (const bf16*)dpooled, argmax,
-            (const bf16*)y, N, H, W, Ho, Wo);
-    else if (dtype == PRIMIA_F32)
-        bn_finalize_pool_kernel<float><<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(
-            sums, slots, C, dbeta, dgamma, gamma, beta, save_mean, save_invstd, (const float*)pooled, (const float*)dpooled, argmax,
-            (const float*)y, N, H, W, Ho, Wo);
-    else
-        return PRIMIA_ERR_ARG;
-    return launch_status();
-}
-
-int primia_bn_fwd_train_mask(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
-                             const float* beta, float* running_mean, float* running_var, float* save_mean,
-                             float* save_invstd, const float* sums, int slots, int64_t M, int C, float eps,
-                             float momentum, void* workspace, int64_t workspace_bytes, int dtype,
-                             primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && z && relu_mask && gamma && beta && save_mean && save_invstd && (sums || workspace));
-    PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
-    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype) && (!sums || slots >= 1));
-    if (!sums && workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const float* part = sums;
-    int nblk = slots;
-    if (!sums) {
-        long rpb;
-        reduce_geometry(M, C, nblk, rpb);
-        part = (const float*)workspace;
-        if (dtype == PRIMIA_F32) {
-            StatsFn<float> f{(const float*)y};
-            colreduce2_kernel<float, StatsFn<float>><<<nblk, 256, 0, st>>>(f, M, C, rpb, (float*)workspace);
-        } else {
-            StatsFn<bf16> f{(const bf16*)y};
-            colreduce2_kernel<bf16, StatsFn<bf16>><<<nblk, 256, 0, st>>>(f, M, C, rpb, (float*)workspace);
-        }
-    }
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(part, nblk, C, M, 0, eps, momentum, save_mean, save_invstd,
-                                                       running_mean, running_var);
-    if (dtype == PRIMIA_F32) {
-        const long nchunks = M * C / 4;
-        bn_apply_kernel<float><<<stream_blocks(nchunks), 256, 0, st>>>((const float*)y, (const float*)residual,
-                                                                       (float*)z, gamma, beta, save_mean, save_invstd,
-                                                                       eps, 0, nchunks, C, 1, relu_mask);
-    } else {
-        const long nchunks = M * C / 8;
-        bn_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, (const bf16*)residual, (bf16*)z,
-                                                                      gamma, beta, save_mean, save_invstd, eps, 0,
-                                                                      nchunks, C, 1, relu_mask);
-    }
+    finalize_stats({sums, slots}, C, M, eps, momentum, save_mean, save_invstd, running_mean, running_var, (hipStream_t)stream);
     return launch_status();
 }
 
@@ -1671,17 +1493,31 @@ int primia_bn_fwd_train_pair(const void* y2, const void* yd, void* z, uint8_t* r
     PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype) && (!sums2 || slots2 >= 1) && (!sums_d || slots_d >= 1));
     if (workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_fwd_train_pair_impl<float>(y2, yd, z, relu_mask, gamma2, beta2, running_mean2, running_var2, save_mean2,
-                                             save_invstd2, sums2, slots2, gamma_d, beta_d, running_mean_d, running_var_d,
-                                             save_mean_d, save_invstd_d, sums_d, slots_d, M, C, eps, momentum,
-                                             (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return bn_fwd_train_pair_impl<bf16>(y2, yd, z, relu_mask, gamma2, beta2, running_mean2, running_var2, save_mean2,
-                                            save_invstd2, sums2, slots2, gamma_d, beta_d, running_mean_d, running_var_d,
-                                            save_mean_d, save_invstd_d, sums_d, slots_d, M, C, eps, momentum,
-                                            (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        // one workspace serves both reductions: the first one's finalize has read it before the second one writes
+        const Sums sd = sums_d ? Sums{sums_d, slots_d} : batch_sums<T>(yd, M, C, (float*)workspace, st);
+        finalize_stats(sd, C, M, eps, momentum, save_mean_d, save_invstd_d, running_mean_d, running_var_d, st);
+        const Sums s2 = sums2 ? Sums{sums2, slots2} : batch_sums<T>(y2, M, C, (float*)workspace, st);
+        finalize_stats(s2, C, M, eps, momentum, save_mean2, save_invstd2, running_mean2, running_var2, st);
+        const long nchunks = M * C / Chunk<T>::N;
+        bn_apply_pair_kernel<T><<<stream_blocks(nchunks), 256, 0, st>>>(
+            (const T*)y2, (const T*)yd, (T*)z, gamma2, beta2, save_mean2, save_invstd2, gamma_d, beta_d, save_mean_d,
+            save_invstd_d, nchunks, C, relu_mask);
+        return launch_status();
+    });
+}
+
+int primia_bn_bwd(const void* y, const void* z, const void* dz, void* dy, void* g_out,
+                  const float* gamma, const float* save_mean, const float* save_invstd,
+                  float* dgamma, float* dbeta, int64_t M, int C, int relu, void* workspace,
+                  int64_t workspace_bytes, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && dz && dy && gamma && save_mean && save_invstd && dgamma && dbeta && workspace);
+    PRIMIA_REQUIRE(!relu || z);
+    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
+    if (workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
+    return bn_bwd(y, relu ? z : nullptr, nullptr, dz, dy, g_out, gamma, nullptr, save_mean, save_invstd, dgamma, dbeta,
+                  nullptr, 0, M, C, workspace, dtype, (hipStream_t)stream);
 }
 
 int primia_bn_bwd_mask(const void* y, const uint8_t* relu_mask, const void* dz, void* dy, void* g_out,
@@ -1691,14 +1527,40 @@ int primia_bn_bwd_mask(const void* y, const uint8_t* relu_mask, const void* dz, 
     PRIMIA_REQUIRE(y && relu_mask && dz && dy && gamma && save_mean && save_invstd && dgamma && dbeta && workspace);
     PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
     if (workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_bwd_impl<float>(y, nullptr, dz, dy, g_out, gamma, save_mean, save_invstd, dgamma, dbeta, M, C, 0,
-                                  (float*)workspace, st, nullptr, relu_mask);
-    if (dtype == PRIMIA_BF16)
-        return bn_bwd_impl<bf16>(y, nullptr, dz, dy, g_out, gamma, save_mean, save_invstd, dgamma, dbeta, M, C, 0,
-                                 (float*)workspace, st, nullptr, relu_mask);
-    return PRIMIA_ERR_ARG;
+    return bn_bwd(y, nullptr, relu_mask, dz, dy, g_out, gamma, nullptr, save_mean, save_invstd, dgamma, dbeta, nullptr, 0, M,
+                  C, workspace, dtype, (hipStream_t)stream);
+}
+
+// primia_bn_bwd_mask with the reduction pass already done by the producer of dz (primia_conv2d_dgrad_pair_bnsums).
+int primia_bn_bwd_mask_from_sums(const void* y, const uint8_t* relu_mask, const void* dz, void* dy, void* g_out,
+                                 const float* gamma, const float* save_mean, const float* save_invstd, float* dgamma,
+                                 float* dbeta, const float* sums, int slots, int64_t M, int C, int dtype,
+                                 primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && relu_mask && dz && dy && gamma && save_mean && save_invstd && dgamma && dbeta && sums && slots >= 1);
+    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
+    return bn_bwd(y, nullptr, relu_mask, dz, dy, g_out, gamma, nullptr, save_mean, save_invstd, dgamma, dbeta, sums, slots,
+                  M, C, nullptr, dtype, (hipStream_t)stream);
+}
+
+int primia_bn_relu_bwd(const void* y, const void* dz, void* dy, const float* gamma, const float* beta,
+                       const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, int64_t M,
+                       int C, void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && dz && dy && gamma && beta && save_mean && save_invstd && dgamma && dbeta && workspace);
+    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
+    if (workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
+    return bn_bwd(y, nullptr, nullptr, dz, dy, nullptr, gamma, beta, save_mean, save_invstd, dgamma, dbeta, nullptr, 0, M, C,
+                  workspace, dtype, (hipStream_t)stream);
+}
+
+// primia_bn_relu_bwd with the reduction pass already done by the producer of dz (primia_conv2d_dgrad_bnsums): `sums` =
+// [slots][2][C] partials of (sum g, sum g * xhat); finalize + apply pass only.
+int primia_bn_relu_bwd_from_sums(const void* y, const void* dz, void* dy, const float* gamma, const float* beta,
+                                 const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
+                                 const float* sums, int slots, int64_t M, int C, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && dz && dy && gamma && beta && save_mean && save_invstd && dgamma && dbeta && sums && slots >= 1);
+    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
+    return bn_bwd(y, nullptr, nullptr, dz, dy, nullptr, gamma, beta, save_mean, save_invstd, dgamma, dbeta, sums, slots, M,
+                  C, nullptr, dtype, (hipStream_t)stream);
 }
 
 int primia_bn_bwd_pair(const void* y2, const void* yd, const void* dz, const uint8_t* relu_mask, void* dy2, void* dyd,
@@ -1711,93 +1573,77 @@ int primia_bn_bwd_pair(const void* y2, const void* yd, const void* dz, const uin
     PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
     if (workspace_bytes < (int64_t)kMaxPartialBlocks * 3 * C * (int64_t)sizeof(float)) return PRIMIA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_bwd_pair_impl<float>(y2, yd, dz, relu_mask, dy2, dyd, gamma2, save_mean2, save_invstd2, gamma_d,
-                                       save_mean_d, save_invstd_d, dgamma2, dbeta2, dgamma_d, dbeta_d, M, C,
-                                       (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return bn_bwd_pair_impl<bf16>(y2, yd, dz, relu_mask, dy2, dyd, gamma2, save_mean2, save_invstd2, gamma_d,
-                                      save_mean_d, save_invstd_d, dgamma2, dbeta2, dgamma_d, dbeta_d, M, C,
-                                      (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        float* partials = (float*)workspace;
+        int nblk;
+        long rpb;
+        reduce_geometry(M, C, nblk, rpb);
+        bn_bwd_pair_reduce_kernel<T><<<nblk, 256, 0, st>>>((const T*)y2, (const T*)yd, (const T*)dz, relu_mask, save_mean2,
+                                                           save_invstd2, save_mean_d, save_invstd_d, M, C, rpb, partials);
+        bn_finalize3_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(partials, nblk, C, dbeta2, dgamma2, dbeta_d, dgamma_d);
+        const long nchunks = M * C / Chunk<T>::N;
+        bn_bwd_pair_apply_kernel<T><<<stream_blocks(nchunks), 256, 0, st>>>(
+            (const T*)y2, (const T*)yd, (const T*)dz, relu_mask, (T*)dy2, (T*)dyd, gamma2, save_mean2, save_invstd2, gamma_d,
+            save_mean_d, save_invstd_d, dbeta2, dgamma2, dgamma_d, (float)(1.0 / (double)M), nchunks, C);
+        return launch_status();
+    });
 }
 
-int primia_bn_relu_bwd(const void* y, const void* dz, void* dy, const float* gamma, const float* beta,
-                       const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, int64_t M,
-                       int C, void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && dz && dy && gamma && beta && save_mean && save_invstd && dgamma && dbeta && workspace);
-    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
-    if (workspace_bytes < primia_bn_workspace_bytes(M, C)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return bn_bwd_impl<float>(y, nullptr, dz, dy, nullptr, gamma, save_mean, save_invstd, dgamma, dbeta, M, C, 0,
-                                  (float*)workspace, st, beta);
-    if (dtype == PRIMIA_BF16)
-        return bn_bwd_impl<bf16>(y, nullptr, dz, dy, nullptr, gamma, save_mean, save_invstd, dgamma, dbeta, M, C, 0,
-                                 (float*)workspace, st, beta);
-    return PRIMIA_ERR_ARG;
+int primia_bn_relu_maxpool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
+                               float* running_mean, float* running_var, float* save_mean, float* save_invstd, int N,
+                               int H, int W, int C, float eps, float momentum, void* workspace,
+                               int64_t workspace_bytes, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && pooled && argmax && gamma && beta && save_mean && save_invstd && workspace);
+    PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
+    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && bn_shape_ok((long)N * H * W, C, dtype));
+    if (workspace_bytes < primia_bn_workspace_bytes((int64_t)N * H * W, C)) return PRIMIA_ERR_WORKSPACE;
+    return bn_relu_pool_fwd(y, pooled, argmax, gamma, beta, running_mean, running_var, save_mean, save_invstd, nullptr, 0,
+                            N, H, W, C, eps, momentum, workspace, dtype, (hipStream_t)stream);
 }
 
-// primia_bn_relu_bwd with the reduction pass already done by the producer of dz (primia_conv2d_dgrad_bnsums): `sums` =
-// [slots][2][C] partials of (sum g, sum g * xhat); finalize + apply pass only.
-int primia_bn_relu_bwd_from_sums(const void* y, const void* dz, void* dy, const float* gamma, const float* beta,
-                                 const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta,
-                                 const float* sums, int slots, int64_t M, int C, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && dz && dy && gamma && beta && save_mean && save_invstd && dgamma && dbeta && sums && slots >= 1);
-    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
-    hipStream_t st = (hipStream_t)stream;
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(sums, slots, C, M, 1, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr);
-    const float inv_m = (float)(1.0 / (double)M);
-    if (dtype == PRIMIA_F32) {
-        const long nchunks = M * C / 4;
-        bn_bwd_apply_kernel<float><<<stream_blocks(nchunks), 256, 0, st>>>((const float*)y, nullptr, (const float*)dz, (float*)dy,
-                                                                           nullptr, gamma, save_mean, save_invstd, dbeta, dgamma,
-                                                                           inv_m, nchunks, C, beta, nullptr);
-    } else if (dtype == PRIMIA_BF16) {
-        const long nchunks = M * C / 8;
-        if (nchunks >= 4L * 2048 * 256)
-            bn_bwd_apply_kernel<bf16, 2><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, nullptr, (const bf16*)dz, (bf16*)dy,
-                                                                                 nullptr, gamma, save_mean, save_invstd, dbeta,
-                                                                                 dgamma, inv_m, nchunks, C, beta, nullptr);
-        else
-            bn_bwd_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, nullptr, (const bf16*)dz, (bf16*)dy,
-                                                                              nullptr, gamma, save_mean, save_invstd, dbeta, dgamma,
-                                                                              inv_m, nchunks, C, beta, nullptr);
-    } else {
-        return PRIMIA_ERR_ARG;
-    }
-    return launch_status();
+int primia_bn_relu_maxpool_fwd_from_sums(const void* y, void* pooled, uint8_t* argmax, const float* gamma,
+                                         const float* beta, float* running_mean, float* running_var,
+                                         float* save_mean, float* save_invstd, const float* sums, int slots, int N,
+                                         int H, int W, int C, float eps, float momentum, int dtype,
+                                         primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && pooled && argmax && gamma && beta && save_mean && save_invstd && sums && slots >= 1);
+    PRIMIA_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
+    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && bn_shape_ok((long)N * H * W, C, dtype));
+    return bn_relu_pool_fwd(y, pooled, argmax, gamma, beta, running_mean, running_var, save_mean, save_invstd, sums, slots,
+                            N, H, W, C, eps, momentum, nullptr, dtype, (hipStream_t)stream);
 }
 
-// primia_bn_bwd_mask with the reduction pass already done by the producer of dz (primia_conv2d_dgrad_pair_bnsums).
-int primia_bn_bwd_mask_from_sums(const void* y, const uint8_t* relu_mask, const void* dz, void* dy, void* g_out,
-                                 const float* gamma, const float* save_mean, const float* save_invstd, float* dgamma,
-                                 float* dbeta, const float* sums, int slots, int64_t M, int C, int dtype,
-                                 primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && relu_mask && dz && dy && gamma && save_mean && save_invstd && dgamma && dbeta && sums && slots >= 1);
-    PRIMIA_REQUIRE(bn_shape_ok(M, C, dtype));
-    hipStream_t st = (hipStream_t)stream;
-    bn_finalize_kernel<<<(C + 15) / 16, 16 * kFinSlices, 0, st>>>(sums, slots, C, M, 1, 0.f, 0.f, dbeta, dgamma, nullptr, nullptr);
-    const float inv_m = (float)(1.0 / (double)M);
-    if (dtype == PRIMIA_F32) {
-        const long nchunks = M * C / 4;
-        bn_bwd_apply_kernel<float><<<stream_blocks(nchunks), 256, 0, st>>>((const float*)y, nullptr, (const float*)dz, (float*)dy,
-                                                                           (float*)g_out, gamma, save_mean, save_invstd, dbeta,
-                                                                           dgamma, inv_m, nchunks, C, nullptr, relu_mask);
-    } else if (dtype == PRIMIA_BF16) {
-        const long nchunks = M * C / 8;
-        if (nchunks >= 4L * 2048 * 256)
-            bn_bwd_apply_kernel<bf16, 2><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, nullptr, (const bf16*)dz, (bf16*)dy,
-                                                                                 (bf16*)g_out, gamma, save_mean, save_invstd, dbeta,
-                                                                                 dgamma, inv_m, nchunks, C, nullptr, relu_mask);
-        else
-            bn_bwd_apply_kernel<bf16><<<stream_blocks(nchunks), 256, 0, st>>>((const bf16*)y, nullptr, (const bf16*)dz, (bf16*)dy,
-                                                                              (bf16*)g_out, gamma, save_mean, save_invstd, dbeta,
-                                                                              dgamma, inv_m, nchunks, C, nullptr, relu_mask);
-    } else {
-        return PRIMIA_ERR_ARG;
-    }
-    return launch_status();
+int primia_bn_relu_maxpool_bwd(const void* y, const void* pooled, const void* dpooled, const uint8_t* argmax,
+                               void* dy, const float* gamma, const float* beta, const float* save_mean,
+                               const float* save_invstd, float* dgamma, float* dbeta, int N, int H, int W, int C,
+                               void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && pooled && dpooled && argmax && gamma && beta && save_mean && save_invstd && dgamma &&
+                   dbeta && workspace);   // dy may be null: dgamma / dbeta only (see primia_stem_bwd_fused)
+    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && bn_shape_ok((long)N * H * W, C, dtype));
+    PRIMIA_REQUIRE((long)N * H * W < (1L << 31));
+    if (workspace_bytes < primia_bn_workspace_bytes((int64_t)N * H * W, C)) return PRIMIA_ERR_WORKSPACE;
+    return with_dtype(dtype, [&](auto tag) {
+        return bn_relu_pool_bwd_impl<decltype(tag)>(y, pooled, dpooled, argmax, dy, gamma, beta, save_mean, save_invstd,
+                                                    dgamma, dbeta, N, H, W, C, (float*)workspace, (hipStream_t)stream);
+    });
+}
+
+// primia_bn_relu_maxpool_bwd(dy = null) whose reduction pass over (pooled, dpooled) already happened in the write-back of the data
+// gradient that produced dpooled (primia_conv2d_dgrad_masked_acc_bnsums, mode 3): `sums` = its partials [slots][2][C].
+int primia_bn_relu_maxpool_bwd_from_sums(const void* y, const void* pooled, const void* dpooled, const uint8_t* argmax,
+                                         const float* gamma, const float* beta, const float* save_mean,
+                                         const float* save_invstd, float* dgamma, float* dbeta, const float* sums, int slots,
+                                         int N, int H, int W, int C, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && pooled && dpooled && argmax && gamma && beta && save_mean && save_invstd && dgamma && dbeta && sums);
+    PRIMIA_REQUIRE(N > 0 && H > 0 && W > 0 && slots >= 1 && bn_shape_ok((long)N * H * W, C, dtype));
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        bn_finalize_pool_kernel<T><<<(C + 15) / 16, 16 * kFinSlices, 0, (hipStream_t)stream>>>(
+            sums, slots, C, dbeta, dgamma, gamma, beta, save_mean, save_invstd, (const T*)pooled, (const T*)dpooled, argmax,
+            (const T*)y, N, H, W, pool_out(H), pool_out(W));
+        return launch_status();
+    });
 }
 
 }  // extern "C"

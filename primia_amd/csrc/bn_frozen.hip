@@ -189,13 +189,10 @@ static int bn_frozen_bwd_dispatch(const void* y, const void* z, const uint8_t* m
     // (blockIdx.y carries the sample)
     PRIMIA_REQUIRE(N > 0 && N <= PRIMIA_BATCH_MAX && HW > 0 && bn_shape_ok((long)N * HW, C, dtype));
     if (workspace_bytes < primia_bn_frozen_workspace_bytes(N, HW, C)) return PRIMIA_ERR_WORKSPACE;
-    if (dtype == PRIMIA_F32)
-        return bn_frozen_bwd_impl<float, MODE>(y, z, mask, dz, dy, g_out, gamma, beta, running_mean, running_var, eps,
-                                               ps_dgamma, ps_dbeta, N, HW, C, (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return bn_frozen_bwd_impl<bf16, MODE>(y, z, mask, dz, dy, g_out, gamma, beta, running_mean, running_var, eps,
-                                              ps_dgamma, ps_dbeta, N, HW, C, (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
+    return with_dtype(dtype, [&](auto tag) {
+        return bn_frozen_bwd_impl<decltype(tag), MODE>(y, z, mask, dz, dy, g_out, gamma, beta, running_mean, running_var, eps,
+                                                       ps_dgamma, ps_dbeta, N, HW, C, (float*)workspace, st);
+    });
 }
 
 }  // namespace primia

@@ -136,12 +136,37 @@ __device__ __forceinline__ float round_to<bf16>(float v) {
     return bf16_to_f32(f32_to_bf16(v));
 }
 
-// [M, C] tensors the BatchNorm kernels take: whole 16-byte chunks per row, a row's chunks divide the 256-thread block,
-// per-channel tables of 512 entries
-static inline bool bn_shape_ok(long M, int C, int dtype) {
-    const int ch = dtype == PRIMIA_F32 ? 4 : 8;
-    return M > 0 && C > 0 && C <= 512 && C % ch == 0 && 256 % (C / ch) == 0;
+// The element type behind a dtype code, handed to `f` as a value (float{} or bf16{}): `using T = decltype(tag)`.  Any
+// other code is PRIMIA_ERR_ARG and `f` does not run — nothing has been launched.
+template <typename F>
+static inline int with_dtype(int dtype, F&& f) {
+    if (dtype == PRIMIA_F32) return f(float{});
+    if (dtype == PRIMIA_BF16) return f(bf16{});
+    return PRIMIA_ERR_ARG;
 }
+
+// [M, C] tensors the BatchNorm kernels take: a known dtype, whole 16-byte chunks per row, a row's chunks divide the
+// 256-thread block, per-channel tables of 512 entries
+static inline bool bn_shape_ok(long M, int C, int dtype) {
+    const int ch = dtype == PRIMIA_F32 ? 4 : dtype == PRIMIA_BF16 ? 8 : 0;  // elements per chunk; 0: not a dtype
+    return ch > 0 && M > 0 && C > 0 && C <= 512 && C % ch == 0 && 256 % (C / ch) == 0;
+}
+
+// ... and [N, HW, C] with G groups, the GroupNorm kernels': channels per group a power of two <= 64 (finalize shuffles)
+static inline bool gn_shape_ok(int N, int HW, int C, int G, int dtype) {
+    const int cpg = (G > 0 && C % G == 0) ? C / G : 0;
+    return N > 0 && HW > 0 && bn_shape_ok(HW, C, dtype) && cpg > 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0;
+}
+
+// blocks of 256 threads for a streaming pass over `nchunks` 16-byte chunks: one chunk per thread up to 2048 blocks, then
+// a grid-stride loop
+static inline int stream_blocks(long nchunks) {
+    long b = (nchunks + 255) / 256;
+    return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
+}
+
+// output extent of max-pool(3, 2, 1)
+static inline int pool_out(int n) { return (n + 2 - 3) / 2 + 1; }
 
 // The stem's BatchNorm seen through ReLU + max-pool: where ReLU was active the pooled value IS the activation, so
 // xhat = (p - beta) / gamma can be read off the pooled tensor (bn.hip PoolScatterFn, gn.hip GnPoolScatterFn,
@@ -196,8 +221,8 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 }
 
 // GroupNorm + ReLU + max-pool(3, 2, 1) apply pass, statistics [N][G] given (kernel: csrc/bn.hip, caller: csrc/gn.hip)
-void launch_gn_relu_pool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
-                             const float* mean, const float* invstd, int N, int H, int W, int C, int G, int dtype,
-                             hipStream_t st);
+int launch_gn_relu_pool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
+                            const float* mean, const float* invstd, int N, int H, int W, int C, int G, int dtype,
+                            hipStream_t st);
 
 }  // namespace primia

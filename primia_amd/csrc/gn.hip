@@ -717,10 +717,6 @@ __global__ __launch_bounds__(256) void dp_noise_acc_kernel(float* __restrict__ g
         g[i] = dp_noise_apply(acc[i] + g[i], noise[i], sigma, inv_b);
 }
 
-static inline int gn_stream_blocks(long nchunks) {
-    long b = (nchunks + 255) / 256;
-    return (int)(b < 2048 ? (b < 1 ? 1 : b) : 2048);
-}
 // (blocks per sample, N): ~2048 blocks of 256 threads over the launch
 static inline dim3 gn_sample_grid(int N, int HW, int cpr) {
     long per = ((long)HW * cpr + 255) / 256;     // blocks that cover one sample once
@@ -736,95 +732,95 @@ static inline dim3 gn_rows_grid(int N, long cps) {
     if (per < 1) per = 1;
     return dim3((unsigned)per, (unsigned)N);
 }
-static inline bool gn_shape_ok(int N, int HW, int C, int G, int dtype) {
-    const int ch = dtype == PRIMIA_F32 ? 4 : 8;
-    const int cpg = (G > 0 && C % G == 0) ? C / G : 0;  // channels per group: a power of two <= 64 (finalize shuffles)
-    return N > 0 && HW > 0 && C > 0 && C <= 512 && cpg > 0 && cpg <= 64 && (cpg & (cpg - 1)) == 0 && C % ch == 0 &&
-           256 % (C / ch) == 0;
-}
-
 // one block per sample (gn_sample_reduce_kernel): the batch fills the chip that way and 2C columns fit the block
 static inline bool gn_sample_blocks(int N, int C, int ch) {
     const int tpr = C / ch;
     return N >= kGnSampleBlockMinN && 2 * C <= 1024 && 1024 % tpr == 0 && 1024 / tpr >= 1024 / (2 * C);
 }
 
+// pixel slabs of one sample in the column reductions
+struct GnSlabs {
+    int rps, nslab;   // rows per slab, slabs
+};
+static inline GnSlabs gn_slabs(int HW) {
+    const int rps = (HW + kGnSlabs - 1) / kGnSlabs;
+    return {rps, (HW + rps - 1) / rps};
+}
+
+// mean / invstd [N][G] of y
 template <typename T>
 static void gn_stats(const void* y, float* mean, float* invstd, int N, int HW, int C, int G, float eps, float* partials,
                      hipStream_t st) {
-    const int rps = (HW + kGnSlabs - 1) / kGnSlabs;
-    const int nslab = (HW + rps - 1) / rps;
+    const GnSlabs s = gn_slabs(HW);
     GnStatsFn<T> f{(const T*)y};
     if (gn_sample_blocks(N, C, Chunk<T>::N)) {
         gn_sample_reduce_kernel<T, GnStatsFn<T>, 0><<<N, 1024, 0, st>>>(f, HW, C, G, (double)HW * (C / G), eps, nullptr,
                                                                         mean, invstd, nullptr, nullptr);
     } else {
-        gn_colreduce2_kernel<T, GnStatsFn<T>><<<dim3(nslab, N), 256, 0, st>>>(f, HW, C, rps, partials);
-        gn_stats_finalize_kernel<<<(N * C + 255) / 256, 256, 0, st>>>(partials, nslab, C, G, (long)HW * (C / G), eps, mean,
+        gn_colreduce2_kernel<T, GnStatsFn<T>><<<dim3(s.nslab, N), 256, 0, st>>>(f, HW, C, s.rps, partials);
+        gn_stats_finalize_kernel<<<(N * C + 255) / 256, 256, 0, st>>>(partials, s.nslab, C, G, (long)HW * (C / G), eps, mean,
                                                                       invstd, N * C);
     }
 }
 
-template <typename T>
-static int gn_fwd_impl(const void* y, const void* res, void* z, const float* gamma, const float* beta, float* mean,
-                       float* invstd, int N, int HW, int C, int G, float eps, int relu, float* partials, hipStream_t st,
-                       uint8_t* mask_out = nullptr) {
-    gn_stats<T>(y, mean, invstd, N, HW, C, G, eps, partials, st);
-    gn_apply_kernel<T><<<gn_sample_grid(N, HW, C / Chunk<T>::N), 256, 0, st>>>((const T*)y, (const T*)res, (T*)z, gamma, beta,
-                                                                               mean, invstd, HW, C, G, relu, mask_out);
-    return launch_status();
-}
-
-template <typename T>
-static int gn_bwd_impl(const void* y, const void* z, const void* dz, void* dy, void* g_out, const float* gamma,
-                       const float* mean, const float* invstd, float* ps_dgamma, float* ps_dbeta, int N, int HW, int C,
-                       int G, int relu, float* partials, hipStream_t st, const float* beta_mask = nullptr,
-                       const uint8_t* mask = nullptr) {
-    const int rps = (HW + kGnSlabs - 1) / kGnSlabs;
-    const int nslab = (HW + rps - 1) / rps;
-    GnBwdFn<T> f{(const T*)y, relu ? (const T*)z : nullptr, (const T*)dz, mean, invstd, G, C / G,
-                 beta_mask ? gamma : nullptr, beta_mask, mask, {}, {}, {}, {}};
-    float* gA = partials + (long)N * nslab * 2 * C;  // group sums live behind the partials
+// The backward reduction over `f`'s HW rows per sample: per-sample dgamma / dbeta rows, and the group sums [N][G] of
+// (g, g * xhat) that the apply pass needs.  They live behind the partials.
+struct GnGroupSums {
+    float *a, *b;
+};
+template <typename T, typename F>
+static GnGroupSums gn_bwd_sums(F f, const float* gamma, float* ps_dgamma, float* ps_dbeta, int N, int HW, int C, int G,
+                               float* partials, hipStream_t st) {
+    const GnSlabs s = gn_slabs(HW);
+    float* gA = partials + (long)N * s.nslab * 2 * C;
     float* gB = gA + (long)N * G;
     if (gn_sample_blocks(N, C, Chunk<T>::N)) {
-        gn_sample_reduce_kernel<T, GnBwdFn<T>, 1><<<N, 1024, 0, st>>>(f, HW, C, G, 0.0, 0.f, gamma, ps_dbeta, ps_dgamma, gA,
-                                                                      gB);
+        gn_sample_reduce_kernel<T, F, 1><<<N, 1024, 0, st>>>(f, HW, C, G, 0.0, 0.f, gamma, ps_dbeta, ps_dgamma, gA, gB);
     } else {
-        gn_colreduce2_kernel<T, GnBwdFn<T>><<<dim3(nslab, N), 256, 0, st>>>(f, HW, C, rps, partials);
-        gn_bwd_finalize_kernel<<<(N * C + 255) / 256, 256, 0, st>>>(partials, nslab, C, G, gamma, ps_dbeta, ps_dgamma, gA,
+        gn_colreduce2_kernel<T, F><<<dim3(s.nslab, N), 256, 0, st>>>(f, HW, C, s.rps, partials);
+        gn_bwd_finalize_kernel<<<(N * C + 255) / 256, 256, 0, st>>>(partials, s.nslab, C, G, gamma, ps_dbeta, ps_dgamma, gA,
                                                                     gB, N * C);
     }
-    gn_bwd_apply_kernel<T><<<gn_sample_grid(N, HW, C / Chunk<T>::N), 256, 0, st>>>(
-        (const T*)y, relu ? (const T*)z : nullptr, (const T*)dz, (T*)dy, (T*)g_out, gamma, beta_mask, mean, invstd, gA, gB,
-        (float)(1.0 / ((double)HW * (C / G))), HW, C, G, mask);
-    return launch_status();
+    return {gA, gB};
 }
 
-template <typename T>
-static int gn_relu_pool_bwd_impl(const void* y, const void* pooled, const void* dpooled, const uint8_t* argmax, void* dy,
-                                 const float* gamma, const float* beta, const float* mean, const float* invstd,
-                                 float* ps_dgamma, float* ps_dbeta, int N, int H, int W, int C, int G, float* partials,
-                                 hipStream_t st) {
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1, HWp = Ho * Wo;
-    const int rps = (HWp + kGnSlabs - 1) / kGnSlabs;
-    const int nslab = (HWp + rps - 1) / rps;
-    GnPoolScatterFn<T> f{(const T*)pooled, (const T*)dpooled, argmax, (const T*)y, mean, invstd, gamma, beta,
-                         H, W, C, Ho, Wo, G, {}, {}, {}, {}, false};
-    float* gA = partials + (long)N * nslab * 2 * C;
-    float* gB = gA + (long)N * G;
-    if (gn_sample_blocks(N, C, Chunk<T>::N)) {
-        gn_sample_reduce_kernel<T, GnPoolScatterFn<T>, 1><<<N, 1024, 0, st>>>(f, HWp, C, G, 0.0, 0.f, gamma, ps_dbeta,
-                                                                              ps_dgamma, gA, gB);
-    } else {
-        gn_colreduce2_kernel<T, GnPoolScatterFn<T>><<<dim3(nslab, N), 256, 0, st>>>(f, HWp, C, rps, partials);
-        gn_bwd_finalize_kernel<<<(N * C + 255) / 256, 256, 0, st>>>(partials, nslab, C, G, gamma, ps_dbeta, ps_dgamma, gA,
-                                                                    gB, N * C);
-    }
-    const long total = (long)N * (H / 2) * (W / 2) * (C / Chunk<T>::N);
-    gn_relu_pool_bwd_apply2x2_kernel<T><<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
-        (const T*)y, (const T*)dpooled, argmax, (T*)dy, gamma, beta, mean, invstd, gA, gB,
-        (float)(1.0 / ((double)H * W * (C / G))), N, H, W, C, G, Ho, Wo);
-    return launch_status();
+// Forward pass (primia_gn_fwd, _fwd_mask): statistics -> apply
+static int gn_fwd(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma, const float* beta,
+                  float* save_mean, float* save_invstd, int N, int HW, int C, int G, float eps, int relu, void* workspace,
+                  int64_t workspace_bytes, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && z && gamma && beta && save_mean && save_invstd && workspace);
+    PRIMIA_REQUIRE(gn_shape_ok(N, HW, C, G, dtype));
+    if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        gn_stats<T>(y, save_mean, save_invstd, N, HW, C, G, eps, (float*)workspace, st);
+        gn_apply_kernel<T><<<gn_sample_grid(N, HW, C / Chunk<T>::N), 256, 0, st>>>(
+            (const T*)y, (const T*)residual, (T*)z, gamma, beta, save_mean, save_invstd, HW, C, G, relu, relu_mask);
+        return launch_status();
+    });
+}
+
+// Backward pass (primia_gn_bwd, _bwd_mask, _relu_bwd): the ReLU mask comes from z, from the mask bytes, or (beta given) is
+// recomputed from y
+static int gn_bwd(const void* y, const void* z, const uint8_t* relu_mask, const void* dz, void* dy, void* g_out,
+                  const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float* ps_dgamma,
+                  float* ps_dbeta, int N, int HW, int C, int G, void* workspace, int64_t workspace_bytes, int dtype,
+                  primia_stream_t stream) {
+    PRIMIA_REQUIRE(y && dz && dy && gamma && save_mean && save_invstd && ps_dgamma && ps_dbeta && workspace);
+    PRIMIA_REQUIRE(gn_shape_ok(N, HW, C, G, dtype));
+    if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        GnBwdFn<T> f{(const T*)y, (const T*)z, (const T*)dz, save_mean, save_invstd, G, C / G, beta ? gamma : nullptr, beta,
+                     relu_mask, {}, {}, {}, {}};
+        const GnGroupSums g = gn_bwd_sums<T>(f, gamma, ps_dgamma, ps_dbeta, N, HW, C, G, (float*)workspace, st);
+        gn_bwd_apply_kernel<T><<<gn_sample_grid(N, HW, C / Chunk<T>::N), 256, 0, st>>>(
+            (const T*)y, (const T*)z, (const T*)dz, (T*)dy, (T*)g_out, gamma, beta, save_mean, save_invstd, g.a, g.b,
+            (float)(1.0 / ((double)HW * (C / G))), HW, C, G, relu_mask);
+        return launch_status();
+    });
 }
 
 }  // namespace primia
@@ -840,84 +836,42 @@ int64_t primia_gn_workspace_bytes(int N, int C, int G) {
 int primia_gn_fwd(const void* y, const void* residual, void* z, const float* gamma, const float* beta,
                   float* save_mean, float* save_invstd, int N, int HW, int C, int G, float eps, int relu,
                   void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && z && gamma && beta && save_mean && save_invstd && workspace);
-    PRIMIA_REQUIRE(gn_shape_ok(N, HW, C, G, dtype));
-    if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return gn_fwd_impl<float>(y, residual, z, gamma, beta, save_mean, save_invstd, N, HW, C, G, eps, relu,
-                                  (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return gn_fwd_impl<bf16>(y, residual, z, gamma, beta, save_mean, save_invstd, N, HW, C, G, eps, relu,
-                                 (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
+    return gn_fwd(y, residual, z, nullptr, gamma, beta, save_mean, save_invstd, N, HW, C, G, eps, relu, workspace,
+                  workspace_bytes, dtype, stream);
+}
+
+int primia_gn_fwd_mask(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
+                       const float* beta, float* save_mean, float* save_invstd, int N, int HW, int C, int G, float eps,
+                       void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
+    PRIMIA_REQUIRE(residual && relu_mask);
+    return gn_fwd(y, residual, z, relu_mask, gamma, beta, save_mean, save_invstd, N, HW, C, G, eps, 1, workspace,
+                  workspace_bytes, dtype, stream);
 }
 
 int primia_gn_bwd(const void* y, const void* z, const void* dz, void* dy, void* g_out, const float* gamma,
                   const float* save_mean, const float* save_invstd, float* ps_dgamma, float* ps_dbeta, int N, int HW,
                   int C, int G, int relu, void* workspace, int64_t workspace_bytes, int dtype,
                   primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && dz && dy && gamma && save_mean && save_invstd && ps_dgamma && ps_dbeta && workspace);
     PRIMIA_REQUIRE(!relu || z);
-    PRIMIA_REQUIRE(gn_shape_ok(N, HW, C, G, dtype));
-    if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return gn_bwd_impl<float>(y, z, dz, dy, g_out, gamma, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C, G,
-                                  relu, (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return gn_bwd_impl<bf16>(y, z, dz, dy, g_out, gamma, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C, G,
-                                 relu, (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
-}
-
-int primia_gn_fwd_mask(const void* y, const void* residual, void* z, uint8_t* relu_mask, const float* gamma,
-                       const float* beta, float* save_mean, float* save_invstd, int N, int HW, int C, int G, float eps,
-                       void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && residual && z && relu_mask && gamma && beta && save_mean && save_invstd && workspace);
-    PRIMIA_REQUIRE(gn_shape_ok(N, HW, C, G, dtype));
-    if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return gn_fwd_impl<float>(y, residual, z, gamma, beta, save_mean, save_invstd, N, HW, C, G, eps, 1,
-                                  (float*)workspace, st, relu_mask);
-    if (dtype == PRIMIA_BF16)
-        return gn_fwd_impl<bf16>(y, residual, z, gamma, beta, save_mean, save_invstd, N, HW, C, G, eps, 1,
-                                 (float*)workspace, st, relu_mask);
-    return PRIMIA_ERR_ARG;
+    return gn_bwd(y, relu ? z : nullptr, nullptr, dz, dy, g_out, gamma, nullptr, save_mean, save_invstd, ps_dgamma, ps_dbeta,
+                  N, HW, C, G, workspace, workspace_bytes, dtype, stream);
 }
 
 int primia_gn_bwd_mask(const void* y, const uint8_t* relu_mask, const void* dz, void* dy, void* g_out,
                        const float* gamma, const float* save_mean, const float* save_invstd, float* ps_dgamma,
                        float* ps_dbeta, int N, int HW, int C, int G, void* workspace, int64_t workspace_bytes, int dtype,
                        primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && relu_mask && dz && dy && gamma && save_mean && save_invstd && ps_dgamma && ps_dbeta && workspace);
-    PRIMIA_REQUIRE(gn_shape_ok(N, HW, C, G, dtype));
-    if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return gn_bwd_impl<float>(y, nullptr, dz, dy, g_out, gamma, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C, G,
-                                  0, (float*)workspace, st, nullptr, relu_mask);
-    if (dtype == PRIMIA_BF16)
-        return gn_bwd_impl<bf16>(y, nullptr, dz, dy, g_out, gamma, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C, G,
-                                 0, (float*)workspace, st, nullptr, relu_mask);
-    return PRIMIA_ERR_ARG;
+    PRIMIA_REQUIRE(relu_mask);
+    return gn_bwd(y, nullptr, relu_mask, dz, dy, g_out, gamma, nullptr, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C,
+                  G, workspace, workspace_bytes, dtype, stream);
 }
 
 int primia_gn_relu_bwd(const void* y, const void* dz, void* dy, const float* gamma, const float* beta,
                        const float* save_mean, const float* save_invstd, float* ps_dgamma, float* ps_dbeta, int N, int HW,
                        int C, int G, void* workspace, int64_t workspace_bytes, int dtype, primia_stream_t stream) {
-    PRIMIA_REQUIRE(y && dz && dy && gamma && beta && save_mean && save_invstd && ps_dgamma && ps_dbeta && workspace);
-    PRIMIA_REQUIRE(gn_shape_ok(N, HW, C, G, dtype));
-    if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return gn_bwd_impl<float>(y, nullptr, dz, dy, nullptr, gamma, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C,
-                                  G, 0, (float*)workspace, st, beta);
-    if (dtype == PRIMIA_BF16)
-        return gn_bwd_impl<bf16>(y, nullptr, dz, dy, nullptr, gamma, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C,
-                                 G, 0, (float*)workspace, st, beta);
-    return PRIMIA_ERR_ARG;
+    PRIMIA_REQUIRE(beta);
+    return gn_bwd(y, nullptr, nullptr, dz, dy, nullptr, gamma, beta, save_mean, save_invstd, ps_dgamma, ps_dbeta, N, HW, C, G,
+                  workspace, workspace_bytes, dtype, stream);
 }
 
 int primia_gn_relu_maxpool_fwd(const void* y, void* pooled, uint8_t* argmax, const float* gamma, const float* beta,
@@ -927,14 +881,10 @@ int primia_gn_relu_maxpool_fwd(const void* y, void* pooled, uint8_t* argmax, con
     PRIMIA_REQUIRE(H > 0 && W > 0 && gn_shape_ok(N, H * W, C, G, dtype));
     if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        gn_stats<float>(y, save_mean, save_invstd, N, H * W, C, G, eps, (float*)workspace, st);
-    else if (dtype == PRIMIA_BF16)
-        gn_stats<bf16>(y, save_mean, save_invstd, N, H * W, C, G, eps, (float*)workspace, st);
-    else
-        return PRIMIA_ERR_ARG;
-    launch_gn_relu_pool_fwd(y, pooled, argmax, gamma, beta, save_mean, save_invstd, N, H, W, C, G, dtype, st);
-    return launch_status();
+    return with_dtype(dtype, [&](auto tag) {
+        gn_stats<decltype(tag)>(y, save_mean, save_invstd, N, H * W, C, G, eps, (float*)workspace, st);
+        return launch_gn_relu_pool_fwd(y, pooled, argmax, gamma, beta, save_mean, save_invstd, N, H, W, C, G, dtype, st);
+    });
 }
 
 int primia_gn_relu_maxpool_bwd(const void* y, const void* pooled, const void* dpooled, const uint8_t* argmax, void* dy,
@@ -947,13 +897,18 @@ int primia_gn_relu_maxpool_bwd(const void* y, const void* pooled, const void* dp
     if (H % 2 || W % 2) return PRIMIA_ERR_UNSUPPORTED;
     if (workspace_bytes < primia_gn_workspace_bytes(N, C, G)) return PRIMIA_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == PRIMIA_F32)
-        return gn_relu_pool_bwd_impl<float>(y, pooled, dpooled, argmax, dy, gamma, beta, save_mean, save_invstd, ps_dgamma,
-                                            ps_dbeta, N, H, W, C, G, (float*)workspace, st);
-    if (dtype == PRIMIA_BF16)
-        return gn_relu_pool_bwd_impl<bf16>(y, pooled, dpooled, argmax, dy, gamma, beta, save_mean, save_invstd, ps_dgamma,
-                                           ps_dbeta, N, H, W, C, G, (float*)workspace, st);
-    return PRIMIA_ERR_ARG;
+    return with_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const int Ho = pool_out(H), Wo = pool_out(W);
+        GnPoolScatterFn<T> f{(const T*)pooled, (const T*)dpooled, argmax, (const T*)y, save_mean, save_invstd, gamma, beta,
+                             H, W, C, Ho, Wo, G, {}, {}, {}, {}, false};
+        const GnGroupSums g = gn_bwd_sums<T>(f, gamma, ps_dgamma, ps_dbeta, N, Ho * Wo, C, G, (float*)workspace, st);
+        const long total = (long)N * (H / 2) * (W / 2) * (C / Chunk<T>::N);
+        gn_relu_pool_bwd_apply2x2_kernel<T><<<(unsigned)((total + 255) / 256), 256, 0, st>>>(
+            (const T*)y, (const T*)dpooled, argmax, (T*)dy, gamma, beta, save_mean, save_invstd, g.a, g.b,
+            (float)(1.0 / ((double)H * W * (C / G))), N, H, W, C, G, Ho, Wo);
+        return launch_status();
+    });
 }
 
 int primia_record_sqnorm(const float* x, int N, int64_t per_sample, int views, double* sq_acc, primia_stream_t stream) {

@@ -46,6 +46,58 @@ def test_bad_arguments_return_error_codes(cuda):
         call("primia_conv2d_dgrad", stem, x, x, x, 0, _lib.PRIMIA_BF16)  # the stem has no data gradient
 
 
+# every normalization entry point that takes a dtype (csrc/bn.hip, csrc/gn.hip, csrc/bn_frozen.hip)
+NORM_ENTRIES = (
+    "primia_bn_fwd_train", "primia_bn_fwd_train_from_sums", "primia_bn_fwd_train_mask", "primia_bn_fwd_train_apply_inline",
+    "primia_bn_fwd_train_pair", "primia_bn_fwd_eval", "primia_bn_fwd_eval_mask", "primia_bn_bwd", "primia_bn_bwd_mask",
+    "primia_bn_bwd_mask_from_sums", "primia_bn_bwd_pair", "primia_bn_relu_bwd", "primia_bn_relu_bwd_from_sums",
+    "primia_bn_relu_maxpool_fwd", "primia_bn_relu_maxpool_fwd_from_sums", "primia_bn_relu_maxpool_bwd",
+    "primia_bn_relu_maxpool_bwd_from_sums",
+    "primia_gn_fwd", "primia_gn_fwd_mask", "primia_gn_bwd", "primia_gn_bwd_mask", "primia_gn_relu_bwd",
+    "primia_gn_relu_maxpool_fwd", "primia_gn_relu_maxpool_bwd",
+    "primia_bn_frozen_bwd", "primia_bn_frozen_bwd_mask", "primia_bn_frozen_relu_bwd",
+)
+# [M = 64, C = 64] rows; as samples N = 2 of HW = 32 = 4 x 8 pixels, G = 32 groups: a shape every entry serves
+NORM_SCALARS = {"M": 64, "C": 64, "N": 2, "HW": 32, "H": 4, "W": 8, "G": 32, "eps": 1e-5, "momentum": 0.1, "relu": 1,
+                "slots": 2, "slots2": 2, "slots_d": 2, "dtype": 7}   # two slots: a finalized sum of fills is no fill
+# activations, gradients, masks, argmax codes, flag words: bytes.  Every other pointer is an fp32 array.
+NORM_BYTE_ARGS = {"y", "y2", "yd", "residual", "z", "dz", "dy", "dy2", "dyd", "g_out", "pooled", "dpooled", "argmax",
+                  "relu_mask", "flags", "workspace"}
+
+
+def test_norm_entries_refuse_an_unknown_dtype_before_touching_anything(cuda):
+    """dtype 7 is PRIMIA_ERR_ARG from every normalization entry, and no kernel ran first: each buffer the call was
+    given (statistics, running statistics, dgamma / dbeta, per-sample rows, z / dy / masks, workspace; the inputs too)
+    still holds its fill.  Arguments are built from the header's parameter names."""
+    import ctypes
+
+    assert set(NORM_ENTRIES) == {n for n, (_, a) in _lib.protos().items()
+                                 if n.startswith(("primia_bn_", "primia_gn_")) and any(an == "dtype" for _, an in a)}
+    ws_bytes = 1 << 20                       # more than any of the workspace queries asks for at this shape
+    failures = []
+    for name in NORM_ENTRIES:
+        bufs, fills, args = {}, {}, []
+        for ctype, an in _lib.protos()[name][1][:-1]:              # (the stream is call()'s)
+            if ctype is not ctypes.c_void_p:
+                args.append(ws_bytes if an == "workspace_bytes" else NORM_SCALARS[an])
+                continue
+            if an in NORM_BYTE_ARGS:
+                fills[an] = torch.full((ws_bytes if an == "workspace" else 64 * 64 * 4,), 0xA5, dtype=torch.uint8, device=cuda)
+            else:
+                fills[an] = torch.full((64 * 64,), -7.25, device=cuda)
+            bufs[an] = fills[an].clone()
+            args.append(bufs[an])
+        try:
+            call(name, *args)
+            failures.append(f"{name}: returned PRIMIA_OK")
+        except PrimiaError as e:
+            if "PRIMIA_ERR_ARG" not in str(e):
+                failures.append(f"{name}: {e}")
+        torch.cuda.synchronize()
+        failures += [f"{name}: wrote {an}" for an in bufs if not torch.equal(bufs[an], fills[an])]
+    assert not failures, "\n".join(failures)
+
+
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 50001])
 def test_dif_ragged_sizes(cuda, n):
     """Comparison counts that are not multiples of the wave / block size; 50001 crosses the
