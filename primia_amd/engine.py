@@ -37,6 +37,15 @@ _NORM_BWD = {"batch": ("primia_bn_relu_bwd", "primia_bn_bwd_mask", "primia_bn_bw
 class _Conv:
     def __init__(self, spec, desc, c_real):
         self.spec, self.desc, self.c_real = spec, desc, c_real
+        # How the layer's batched weight gradient is served — decided once by ResNet18Engine.__init__, read by _issue_wgrad:
+        # "stem" (conv1 on the padded input), "pair" (half of a transition block's conv1 + downsample launch), "group"
+        # (member of a stage's same-shape launch) or "single".  wg_hold, pairs and groups: (key of the hold, launches that
+        # fill it, layers of the network that feed it).  wg_x, conv1 only: its operand, the padded input where one exists.
+        self.wg, self.wg_hold, self.wg_x = "single", None, None
+        # DP-SGD norm pass where the layer's tiles are not kept: (conv1's halo kernel serves it, conv1's operand for it)
+        self.dp_norm = (False, None)
+        # asked of the library at first use (the switches that gate them can be set after construction)
+        self.pair_ok = self.bnsums_slots = self.acc_bnsums_slots = self.pair_bnsums_slots = None
 
 
 class ResNet18Engine:
@@ -148,7 +157,7 @@ class ResNet18Engine:
         # atomics, so that only the front part needs zeroing every step.
         acc_total = 0
         ws_need = {c.spec.name: query("primia_conv_wgrad_ws_bytes", c.desc, self.dt) for c in self.convs.values()}
-        self._stem_ws_bytes = query("primia_stem_conv_wgrad_ws_bytes", N, input_size, input_size)
+        stem_ws = query("primia_stem_conv_wgrad_ws_bytes", N, input_size, input_size)
         for overwriting in (False, True):
             for c in self.convs.values():
                 # (conv1's 64 KiB slab stays in the zeroed part: odd input sizes take its accumulate path)
@@ -172,21 +181,19 @@ class ResNet18Engine:
             if c.spec.name != stem.name:
                 c.w_dgrad = torch.empty(query("primia_conv_wdgrad_elems", c.desc), dtype=dtype, device=dev)
             c.acc = self.dw_acc[c.acc_off:c.acc_off + c.wfwd_n]
+        # ---- how each conv's batched weight gradient is served: decided here, recorded on the _Conv (wg, wg_hold), read by
+        # _issue_wgrad — the plain backward pass and the DP-SGD clipped sums issue through that one method ----
         # a transition block's conv1 + downsample weight gradients as one launch (primia_conv2d_wgrad_pair_ws)
-        self._pair_ws = {}
+        shared_ws = [0]
         for blk in self.spec.blocks:
             if blk.down is not None:
-                self._pair_ws[blk.conv1.name] = query("primia_conv_wgrad_pair_ws_bytes", self.convs[blk.conv1.name].desc,
-                                                      self.convs[blk.down.name].desc, self.dt)
-        # workspace of the atomic-free weight-gradient path (primia_conv2d_wgrad_ws): the layers run one after
-        # the other on one stream, so they share one buffer sized for the largest (38 MB at batch 256)
+                c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
+                shared_ws.append(query("primia_conv_wgrad_pair_ws_bytes", c1.desc, cd.desc, self.dt))
+                if shared_ws[-1] > 0:
+                    c1.wg = cd.wg = "pair"
+                    c1.wg_hold = cd.wg_hold = (blk.prefix, 2, 2)
         # several layers of one shape in ONE weight-gradient launch (primia_conv2d_wgrad_group_ws): the 3x3 / stride-1
         # layers of a stage share a shape; a layer's (x, dy) is held back until its siblings' are ready
-        self._wg_group = {}        # conv name -> (shape key, preferred group size)
-        self._wg_held = {}         # shape key -> [(name, x, dy), ...]
-        self._wg_count = {}        # shape key -> layers of that shape in the network
-        self._wg_seen = {}         # shape key -> layers of that shape this backward pass has reached
-        group_ws = [0]
         if dtype == torch.bfloat16:
             shapes = {}
             for c in self.spec.convs:
@@ -198,12 +205,18 @@ class ResNet18Engine:
                 n = query("primia_conv_wgrad_group_size", d, len(names), self.dt)
                 if n >= 2:
                     for nm in names:
-                        self._wg_group[nm] = (key, n)
-                    self._wg_count[key] = len(names)
-                    group_ws.append(query("primia_conv_wgrad_group_ws_bytes", d, n, self.dt))
-        ws_bytes = max(max(ws_need.values()), self._stem_ws_bytes, max(list(self._pair_ws.values()) + [0]), max(group_ws))
-        self.wgrad_ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev) if ws_bytes > 0 else None
+                        self.convs[nm].wg, self.convs[nm].wg_hold = "group", (key, n, len(names))
+                    shared_ws.append(query("primia_conv_wgrad_group_ws_bytes", d, n, self.dt))
+        self._wg_held = {}         # hold key -> [(name, x, dy), ...] waiting for the launch they share
+        self._wg_seen = {}         # hold key -> layers feeding it that this pass has reached
+        # workspace of the atomic-free weight-gradient path (primia_conv2d_wgrad_ws): the layers run one after
+        # the other on one stream, so they share one buffer sized for the largest (38 MB at batch 256)
+        ws_bytes = max(max(ws_need.values()), stem_ws, max(shared_ws))
+        if ws_bytes <= 0:   # (conv1's generic kernel alone asks for one at every shape the checks above let through)
+            raise _lib.PrimiaError("no weight-gradient workspace: primia_conv_wgrad_ws_bytes answered nothing positive")
+        self.wgrad_ws = torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev)
         self.wgrad_ws_bytes = ws_bytes
+        self._wg_stream, self._wg_pending = None, False      # second stream of wgrad_overlap, created at first use
 
         # ---- activations ------------------------------------------------------------------------
         def act(hw, ch):
@@ -248,10 +261,17 @@ class ResNet18Engine:
         # stem tail bn1 -> relu -> maxpool as ONE fused op in training (z = relu(bn(y)) is never written)
         self.fuse_stem = True
         self.relu_masks = {}         # residual layers: 1-bit ReLU masks for the backward passes (see _bn)
-        # the stem convolutions read the padded input copy; the unpadded one is written only where the halo kernels on the
-        # padded one do not serve the shape
-        self._stem_padded = self.x0p is not None
-        self._x0_valid = not self._stem_padded or (self.per_sample_norm and self._stem_ws_bytes <= 0)
+        # the stem convolutions read the padded input copy where there is one — conv1's weight gradient too — and DP-SGD's
+        # norm pass does where the halo kernel serves the shape (exactly where it asks for a workspace); the unpadded copy
+        # is written only where something reads it
+        c = self.convs[stem.name]
+        halo = self.x0p is not None and stem_ws > 0
+        if self.x0p is not None:
+            c.wg, c.wg_x = "stem", self.x0p
+        else:
+            c.wg_x = self.x0
+        c.dp_norm = (halo, self.x0p if halo else self.x0)
+        self._x0_valid = self.x0p is None or (self.per_sample_norm and not halo)
         self.stat_slots = query("primia_conv_stat_slots")
         for c in self.spec.convs:   # slots the kernel serving this conv writes (per-block partials for layer1's)
             self.convs[c.name].stat_slots = (query("primia_conv_stat_slots_for", self.convs[c.name].desc, self.dt)
@@ -304,6 +324,10 @@ class ResNet18Engine:
         self._stem_fused = self._stem_fused_gn = False
         self._stem_sums, self._stem_slots = None, 0   # bn1's partial sums out of the padded-input stem conv (first use)
         self._pool_sums = None       # (partials, slots) of bn1's backward sums where layer1.0.conv1's data gradient forms them
+        self._stem_bwd_fused_ok = None      # the library's gate for primia_stem_bwd_fused at this shape, asked at first use
+        self._bwd_sum_bufs = {}      # partial tables of the *_bnsums fusions, by producer (see _bwd_sums)
+        # DP-SGD: built at first use — the kept-tile buffers, the argument arrays of the *_many launches
+        self._dp_keep = self._sqnorm_many = self._colsum_many = self._scale_many = None
         self.dp = None  # set by dp_backward: {"wgrads": [...]} defers the weight gradients
         self.feat = torch.empty(N, 512, dtype=torch.float32, device=dev)
         self.dfeat = torch.empty(N, 512, dtype=torch.float32, device=dev)
@@ -533,7 +557,7 @@ class ResNet18Engine:
     def _conv_fwd_pair(self, blk, x, y1, yd):
         """conv1 + downsample of a transition block as one launch; False where the library does not serve the pair."""
         c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
-        if getattr(c1, "pair_ok", None) is None:
+        if c1.pair_ok is None:
             c1.pair_ok = self.fwd_pair and query("primia_conv_fwd_pair_ok", c1.desc, cd.desc, self.dt) == 1
         if not c1.pair_ok:
             return False
@@ -558,7 +582,7 @@ class ResNet18Engine:
         if self._x0_valid:
             call("primia_nchw_to_nhwc", x_nchw, self.x0, N, self.spec.in_channels, S, S, 4, self.dt)
         stem_done = False
-        if self._stem_padded:
+        if self.x0p is not None:
             call("primia_nchw_to_nhwc_padded", x_nchw, self.x0p, N, self.spec.in_channels, S, S, 4, 3, 3,
                  self.x0p_dims[0], self.x0p_dims[1], self.dt)
             c = self.convs["conv1"]
@@ -586,7 +610,7 @@ class ResNet18Engine:
                                and self.spec.pooling == "max" and hw % 2 == 0)
         if stem_done:
             pass
-        elif self._stem_fused and self._stem_padded:     # (bn1's sums came with the padded-input stem conv above)
+        elif self._stem_fused and self.x0p is not None:  # (bn1's sums came with the padded-input stem conv above)
             sm, si = self.save["bn1"]
             call("primia_bn_relu_maxpool_fwd_from_sums", t["stem.y"], t["pool.out"], self.pool_argmax,
                  self.views["bn1.weight"], self.views["bn1.bias"], self.views["bn1.running_mean"],
@@ -748,39 +772,83 @@ class ResNet18Engine:
     # by then every operand comes from HBM, while a stage's group still finds its newest dy in the Infinity Cache — and is
     # not kept: profiles/r03_negative_results.txt)
 
-    def _wgrad_transition(self, blk, x, dy1, dyd):
-        """conv1 and the downsample of a transition block: one launch where the library serves the pair."""
-        c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
-        if self.dp is None and self.wgrad_ws is not None and self._pair_ws.get(blk.conv1.name, 0) > 0:
-            self._on_wgrad_stream(lambda: self._timed(
-                "wgrad", c1, lambda: call("primia_conv2d_wgrad_pair_ws", c1.desc, x, dy1, c1.acc, cd.desc, dyd, cd.acc,
-                                          self.wgrad_ws, self.wgrad_ws_bytes, self.dt), extra_macs=self._macs(cd)), transition=True)
-            return
-        self._wgrad(blk.conv1.name, x, dy1)
-        self._wgrad(blk.down.name, x, dyd)
-
     def _wgrad(self, name, x, dy):
-        c = self.convs[name]
-        if self.dp is not None:  # DP-SGD: weight gradients wait for the per-sample clip factors
+        """The backward pass has reached layer `name`'s dy: issue its weight gradient — under DP-SGD, note the operands
+        for the norm pass and the clipped sums, which issue it once the rows of dy carry the clip factors."""
+        if self.dp is not None:
             self.dp["wgrads"].append((name, x, dy))
             return
-        if self.wgrad_ws is not None and name in self._wg_group:
-            key, n = self._wg_group[name]
-            held = self._wg_held.setdefault(key, [])
-            held.append((name, x, dy))
-            self._wg_seen[key] = self._wg_seen.get(key, 0) + 1
-            # a full group — or the stage's last layer (layer4 at batch 256: groups of 2 for 3 layers): it runs NOW, while its
-            # dy is the newest tensor in the Infinity Cache, not at the end of the backward pass
-            if len(held) == n or (self.wgrad_flush_last and self._wg_seen[key] == self._wg_count.get(key, 0)):
-                self._flush_wgrad_group(key)
-            return
-        if self.wgrad_ws is not None:   # (one workspace: the weight gradients stay in order on whichever stream)
-            self._on_wgrad_stream(lambda: self._timed("wgrad", c, lambda: call(
-                "primia_conv2d_wgrad_ws", c.desc, x, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)))
-            return
-        self._on_wgrad_stream(lambda: self._timed("wgrad", c, lambda: call("primia_conv2d_wgrad", c.desc, x, dy, c.acc,
-                                                                             self.dt)))
+        self._issue_wgrad(name, x, dy)
 
+    # measurement hook (tools/power_idle_ab.py): called after every grouped 3x3 weight-gradient launch; None in every product run
+    after_wgrad_hook = None
+
+    def _issue_wgrad(self, name, x, dy):
+        """THE scheduler of the batched weight gradients, for the plain backward pass and the DP-SGD clipped sums alike: the
+        layer's own launch now, or — half of a transition pair, member of a same-shape group (c.wg_hold, decided by the
+        constructor) — held until the launch it shares is complete.  _finalize_wgrads closes the pass."""
+        c = self.convs[name]
+        if c.wg_hold is None:
+            return self._launch_wgrads([(name, x, dy)])
+        key, fill, feeders = c.wg_hold
+        held = self._wg_held.setdefault(key, [])
+        held.append((name, x, dy))
+        self._wg_seen[key] = self._wg_seen.get(key, 0) + 1
+        # a full launch — or the stage's last layer (layer4 at batch 256: groups of 2 for 3 layers): it runs NOW, while its
+        # dy is the newest tensor in the Infinity Cache, not at the end of the pass
+        if len(held) == fill or (self.wgrad_flush_last and self._wg_seen[key] == feeders):
+            self._flush_wgrads(key)
+
+    def _flush_wgrads(self, key):
+        held = self._wg_held.pop(key)
+        try:
+            self._launch_wgrads(held)
+        finally:
+            if self.after_wgrad_hook is not None and self.convs[held[0][0]].wg == "group":
+                self.after_wgrad_hook()
+
+    def _launch_wgrads(self, held):
+        """One launch for (name, x, dy) triples that share one: a transition block's (conv1, downsample) in the order the
+        backward pass reaches them, two to four layers of one shape — or a layer alone, a group's left-over one included.
+        One workspace: the launches stay in order on whichever stream."""
+        c = self.convs[held[0][0]]
+        ws = (self.wgrad_ws, self.wgrad_ws_bytes)
+        extra = 0
+        if len(held) == 1:
+            (_, x, dy), = held
+            if c.wg == "stem":
+                S = self.spec.input_size
+                fn = lambda: call("primia_stem_conv_wgrad_ws", x, dy, c.acc, *ws, self.N, S, S, self.dt)
+            else:
+                fn = lambda: call("primia_conv2d_wgrad_ws", c.desc, x, dy, c.acc, *ws, self.dt)
+        elif c.wg == "pair":
+            (_, x, dy1), (down, _, dyd) = held
+            cd = self.convs[down]
+            extra = self._macs(cd)
+            fn = lambda: call("primia_conv2d_wgrad_pair_ws", c.desc, x, dy1, c.acc, cd.desc, dyd, cd.acc, *ws, self.dt)
+        else:
+            args = [a for nm, x, dy in held for a in (x, dy, self.convs[nm].acc)] + [None] * (3 * (4 - len(held)))
+            extra = (len(held) - 1) * self._macs(c)
+            fn = lambda: call("primia_conv2d_wgrad_group_ws", c.desc, len(held), *args, *ws, self.dt)
+        self._on_wgrad_stream(lambda: self._timed("wgrad", c, fn, extra_macs=extra), transition=c.wg == "pair")
+
+    def _finalize_wgrads(self):
+        """Closing half of _issue_wgrad: what is still held (groups that never filled: odd layer counts), the second
+        stream, then accumulators -> OIHW gradients."""
+        for key in list(self._wg_held):
+            self._flush_wgrads(key)
+        self._join_wgrad_stream()
+        if self.fuse_sgd_tail and self.dp is None and self._sgd_tail_plan() is not None:
+            # the accumulators stay as they are: sgd_step() turns them into gradients, new weights and new kernel-layout
+            # copies in one pass per tile; anything else that wants the gradients calls materialize_grads()
+            self._grads_pending = True
+            return
+        m = self._many_args()
+        call("primia_conv_wgrad_finalize_many", m["descs"], m["creal"], m["acc"], m["gw"], m["n"])
+
+    # Every batched weight-gradient launch goes through _on_wgrad_stream (from _launch_wgrads; primia_stem_bwd_fused from
+    # backward()), in the plain pass and in DP-SGD's clipped sums alike.  With wgrad_overlap = 0 — every product run — it
+    # runs the launch where it stands.  The option:
     # Weight gradients are leaves of the backward graph (nothing reads them before the finalize) and every layer
     # has its own dy buffer, so they can run on a second stream.  Overlapping them with EVERYTHING was slower
     # (7.70 -> 7.91 ms: wgrad and dgrad tiles evict each other from the CUs).  With `wgrad_overlap` the schedule is
@@ -802,7 +870,7 @@ class ResNet18Engine:
             return fn()
         if not self.wgrad_overlap or self.prof is not None:
             return fn()
-        if getattr(self, "_wg_stream", None) is None:
+        if self._wg_stream is None:
             self._wg_stream = torch.cuda.Stream(device=self.device)
         main = torch.cuda.current_stream()
         self._wg_stream.wait_stream(main)        # dy (and the zeroed accumulators) are ready
@@ -811,7 +879,7 @@ class ResNet18Engine:
         self._wg_pending = True
 
     def _join_wgrad_stream(self):
-        if getattr(self, "_wg_pending", False):
+        if self._wg_pending:
             torch.cuda.current_stream().wait_stream(self._wg_stream)
             self._wg_pending = False
 
@@ -831,21 +899,20 @@ class ResNet18Engine:
 
     def _stem_bwd_fused_wanted(self):
         """The stem's backward tail runs as primia_bn_relu_maxpool_bwd (sums only) + primia_stem_bwd_fused."""
-        if getattr(self, "_stem_bwd_fused_ok", None) is None:     # asked once: the library's own gate for this shape
+        if self._stem_bwd_fused_ok is None:     # asked once: the library's own gate for this shape
             S0 = self.spec.input_size
             self._stem_bwd_fused_ok = query("primia_stem_bwd_fused_ok", self.N, S0, S0, self.dt) == 1
-        return bool(self._stem_fused and self._stem_padded and self.dp is None
-                    and self.wgrad_ws is not None and self._stem_bwd_fused_ok)
+        return bool(self._stem_fused and self.x0p is not None and self.dp is None and self._stem_bwd_fused_ok)
 
     def _dgrad_bnsums_slots(self, name):
         """Rows of the partial table conv `name`'s data gradient writes for the BatchNorm in front of it (0: not served)."""
         c = self.convs[name]
-        if getattr(c, "bnsums_slots", None) is None:      # (a property of the layer: asked once, whatever self.dp is then)
+        if c.bnsums_slots is None:      # (a property of the layer: asked once, whatever self.dp is then)
             c.bnsums_slots = query("primia_conv_dgrad_bnsums_slots", c.desc, self.dt) if self.dtype == torch.bfloat16 else 0
         return c.bnsums_slots if self.dp is None else 0
 
     def _bwd_sums(self, name, slots, channels):
-        tab = self.__dict__.setdefault("_bwd_sum_bufs", {})
+        tab = self._bwd_sum_bufs
         if name not in tab or tab[name].numel() != slots * 2 * channels:
             tab[name] = torch.empty(slots * 2 * channels, dtype=torch.float32, device=self.device)
         return tab[name]
@@ -911,7 +978,7 @@ class ResNet18Engine:
                 mode = 2
             elif prev is None and self._stem_bwd_fused_wanted():
                 mode = 3
-        if mode and getattr(c1, "acc_bnsums_slots", None) is None:
+        if mode and c1.acc_bnsums_slots is None:
             c1.acc_bnsums_slots = query("primia_conv_dgrad_masked_acc_bnsums_slots", c1.desc, self.dt)
         slots = c1.acc_bnsums_slots if mode else 0
         if slots > 0 and mode == 2:
@@ -956,14 +1023,15 @@ class ResNet18Engine:
         c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
         if self.wgrad_overlap == 1:
             self._join_wgrad_stream()
-        self._wgrad_transition(blk, x_in, dy1, dyd)
+        self._wgrad(blk.conv1.name, x_in, dy1)
+        self._wgrad(blk.down.name, x_in, dyd)    # (completes the pair where the library serves one)
         # the paired data gradient also forms the backward sums of the residual BatchNorm in front of the block
         # (primia_conv2d_dgrad_pair_bnsums: conv_s2lh_kernel for 64-channel dx, conv_igemm_kernel's parity-class walk for
         # layer3.0 / layer4.0)
         pslots = 0
         pb2 = bn_name(prev.conv2.name) if prev is not None else None
         if self._fuse_bwd_sums_bf16 and prev is not None and prev.down is None and pb2 in self.relu_masks:
-            if getattr(c1, "pair_bnsums_slots", None) is None:
+            if c1.pair_bnsums_slots is None:
                 c1.pair_bnsums_slots = query("primia_conv_dgrad_pair_bnsums_slots", c1.desc, self.dt)
             pslots = c1.pair_bnsums_slots
         if pslots > 0:
@@ -985,7 +1053,7 @@ class ResNet18Engine:
         self._grads_pending = False      # (accumulators of an earlier pass that nobody consumed are overwritten now)
         self._wg_seen = {}
         self._dout_sums = {}             # block prefix -> (partials, slots): backward sums of its bn2 formed by the producer of dout
-        if self.wgrad_ws is not None and self.dp is None:
+        if self.dp is None:
             # the other layers' accumulators are overwritten — conv1's too where its weight gradient runs on the padded input
             # (primia_stem_bwd_fused ends in an ordered reduce that WRITES the slab): then the step has
             # no fill launch at all (tests: test_weight_gradient_accumulators_are_overwritten poisons the arena between steps)
@@ -1063,63 +1131,9 @@ class ResNet18Engine:
             else:
                 call("primia_avgpool3x3s2_bwd", t["pool.dout"], t["stem.dz"], N, hw, hw, 64, self.dt)
             self._bn_bwd("conv1", t["stem.y"], t["stem.z"], t["stem.dz"], t["stem.dy"], None, True)
-        if self._stem_padded and self.dp is None:
-            c = self.convs["conv1"]
-            S = self.spec.input_size
-            if self.wgrad_ws is not None:
-                self._on_wgrad_stream(lambda: self._timed("wgrad", c, lambda: call(
-                    "primia_stem_conv_wgrad_ws", self.x0p, t["stem.dy"], c.acc, self.wgrad_ws, self.wgrad_ws_bytes, N, S,
-                    S, self.dt)))
-            else:
-                self._on_wgrad_stream(lambda: self._timed("wgrad", c, lambda: call("primia_stem_conv_wgrad", self.x0p,
-                                                                                 t["stem.dy"], c.acc, N, S, S, self.dt)))
-        else:
-            self._wgrad("conv1", self.x0, t["stem.dy"])
+        self._wgrad("conv1", self.convs["conv1"].wg_x, t["stem.dy"])
         if self.dp is None:
             self._finalize_wgrads()
-
-    # measurement hook (tools/power_idle_ab.py): called after every grouped 3x3 weight-gradient launch; None in every product run
-    after_wgrad_hook = None
-
-    def _flush_wgrad_group(self, key):
-        held = self._wg_held.pop(key, [])
-        if self.after_wgrad_hook is not None and held:
-            try:
-                return self._flush_wgrad_group_inner(held)
-            finally:
-                self.after_wgrad_hook()
-        return self._flush_wgrad_group_inner(held)
-
-    def _flush_wgrad_group_inner(self, held):
-        if len(held) >= 2:
-            c = self.convs[held[0][0]]
-            args = []
-            for i in range(4):
-                if i < len(held):
-                    nm, x, dy = held[i]
-                    args += [x, dy, self.convs[nm].acc]
-                else:
-                    args += [None, None, None]
-            self._on_wgrad_stream(lambda: self._timed(
-                "wgrad", c, lambda: call("primia_conv2d_wgrad_group_ws", c.desc, len(held), *args, self.wgrad_ws,
-                                         self.wgrad_ws_bytes, self.dt), extra_macs=(len(held) - 1) * self._macs(c)))
-        else:
-            for nm, x, dy in held:
-                c = self.convs[nm]
-                self._on_wgrad_stream(lambda c=c, x=x, dy=dy: self._timed("wgrad", c, lambda: call(
-                    "primia_conv2d_wgrad_ws", c.desc, x, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)))
-
-    def _finalize_wgrads(self):
-        for key in list(self._wg_held):      # (groups that never filled: odd layer counts)
-            self._flush_wgrad_group(key)
-        self._join_wgrad_stream()
-        if self.fuse_sgd_tail and self.dp is None and self._sgd_tail_plan() is not None:
-            # the accumulators stay as they are: sgd_step() turns them into gradients, new weights and new kernel-layout
-            # copies in one pass per tile; anything else that wants the gradients calls materialize_grads()
-            self._grads_pending = True
-            return
-        m = self._many_args()
-        call("primia_conv_wgrad_finalize_many", m["descs"], m["creal"], m["acc"], m["gw"], m["n"])
 
     # The step's tail — accumulator -> OIHW gradient, SGD on the fp32 master, master -> compute-dtype copies — as ONE
     # pass per weight tile (primia_conv_sgd_step_many: 95 -> ~55 us at batch 256, bit-identical weights and gradients).
@@ -1264,7 +1278,7 @@ class ResNet18Engine:
             call("primia_record_sqnorm", ps_fc, N, nc * 512 + nc, m, sq)
             mark("fc")
             if trace is None:   # all 40 per-slot affine gradients in one launch
-                if getattr(self, "_sqnorm_many", None) is None:
+                if self._sqnorm_many is None:
                     xs = [tt.data_ptr() for pair in self.ps_affine.values() for tt in pair]
                     ws_ = [tt.shape[1] for pair in self.ps_affine.values() for tt in pair]
                     self._sqnorm_many = (torch.tensor(xs, dtype=torch.int64, device=dev),
@@ -1280,30 +1294,7 @@ class ResNet18Engine:
             # The kept-tile forms are per sample: records of several views run the two-pass form on every layer
             kept = self._dp_keep_buffers() if m == 1 else {}
             for name, x, dy in self.dp["wgrads"]:
-                c = self.convs[name]
-                done = False
-                if name in kept:
-                    if name == "conv1":
-                        S = self.spec.input_size
-                        call("primia_stem_conv_wgrad_persample_sqnorm_keep", self.x0p, dy, sq, kept[name],
-                             kept[name].numel() * 4, N, S, S, self.dt)
-                    else:
-                        call("primia_conv2d_wgrad_persample_sqnorm_keep", c.desc, x, dy, sq, kept[name],
-                             kept[name].numel() * 4, self.dt)
-                    mark(name)
-                    continue
-                if name == "conv1" and self._stem_padded:   # halo kernel on the padded input, one block per record
-                    S = self.spec.input_size
-                    try:
-                        call("primia_stem_conv_wgrad_record_sqnorm", self.x0p, dy, sq, N, S, S, m, self.dt)
-                        done = True
-                    except _lib.PrimiaError:
-                        done = False
-                if not done:
-                    if name == "conv1" and not self._x0_valid:
-                        raise _lib.PrimiaError("per-record stem gradient: the padded-input kernel refused a shape it "
-                                               "advertised (primia_stem_conv_wgrad_ws_bytes > 0)")
-                    call("primia_conv2d_wgrad_record_sqnorm", c.desc, x, dy, sq, m, self.dt)
+                self._dp_norm_pass(name, x, dy, sq, kept.get(name), m)
                 mark(name)
             # one clip factor per record (record r's target is slot r * m's), then one per slot for the clipped sums
             clip = torch.empty(R, dtype=torch.float32, device=dev)
@@ -1327,43 +1318,44 @@ class ResNet18Engine:
         return self._dp_tail(sq, clip, adaptive, R, masked, expected_batch, accumulate, logical_batch, max_grad_norm,
                              noise_multiplier, noise, generator)
 
+    def _dp_norm_pass(self, name, x, dy, sq, keep, m):
+        """sq[r] += ||record r's gradient of conv `name`||^2.  Three forms: the one that also keeps every sample's tile
+        (`keep`: the layer's buffer of _dp_keep_buffers), conv1's halo kernel on the padded input — one block per record,
+        where the constructor found the shape served — and the generic record form.  An error of any of them is the
+        caller's: none stands in for another."""
+        c, N, S = self.convs[name], self.N, self.spec.input_size
+        halo, x_stem = c.dp_norm
+        if x_stem is not None:      # conv1: the input copy the form chosen for it reads
+            x = x_stem
+        if keep is not None and name == "conv1":
+            call("primia_stem_conv_wgrad_persample_sqnorm_keep", x, dy, sq, keep, keep.numel() * 4, N, S, S, self.dt)
+        elif keep is not None:
+            call("primia_conv2d_wgrad_persample_sqnorm_keep", c.desc, x, dy, sq, keep, keep.numel() * 4, self.dt)
+        elif halo:
+            call("primia_stem_conv_wgrad_record_sqnorm", x, dy, sq, N, S, S, m, self.dt)
+        else:
+            call("primia_conv2d_wgrad_record_sqnorm", c.desc, x, dy, sq, m, self.dt)
+
     def _dp_clipped_sums(self, clip, ps_fc, kept):
         """grads = sum_n clip[n] g_n over the N slots of a DP-SGD pass (self.dp holds the backward pass's operands): the
         rows of dy scaled and the batched weight gradient, the weighted reduce of the `kept` layers' tiles, the weighted
         column sums of the per-sample affine and fc gradients."""
         N, nc, dev = self.N, self.spec.num_classes, self.device
-        # (a transition block's conv1 + downsample: ONE launch as in plain training, once both dy are scaled)
-        pair_of, pair_wait = {}, {}
-        if self.wgrad_ws is not None:
-            for blk in self.spec.blocks:
-                if (blk.down is not None and self._pair_ws.get(blk.conv1.name, 0) > 0
-                        and blk.conv1.name not in kept and blk.down.name not in kept):
-                    pair_of[blk.conv1.name] = pair_of[blk.down.name] = blk
         # every dy of a layer whose tiles are not kept, scaled by the clip factors in ONE launch (a dozen tensors)
         to_scale = [dy for name, _, dy in self.dp["wgrads"] if name not in kept]
         many = 0 < len(to_scale) <= 16
         if many:
             key = tuple(tt.data_ptr() for tt in to_scale)
-            if getattr(self, "_scale_many", (None,))[0] != key:
+            if self._scale_many is None or self._scale_many[0] != key:
                 import ctypes
 
                 self._scale_many = (key, (ctypes.c_void_p * len(key))(*key),
                                     (ctypes.c_int64 * len(key))(*[tt.numel() // N for tt in to_scale]))
             call("primia_scale_rows_many", self._scale_many[1], self._scale_many[2], len(key), clip, N, self.dt)
+        self._wg_seen = {}
         for name, x, dy in self.dp["wgrads"]:
-            c = self.convs[name]
-            if name in pair_of:
-                blk = pair_of[name]
-                if not many:
-                    call("primia_scale_rows", dy, clip, N, dy.numel() // N, self.dt)
-                got = pair_wait.setdefault(blk.prefix, {})
-                got[name] = (x, dy)
-                if len(got) == 2:
-                    c1, cd = self.convs[blk.conv1.name], self.convs[blk.down.name]
-                    call("primia_conv2d_wgrad_pair_ws", c1.desc, got[blk.conv1.name][0], got[blk.conv1.name][1], c1.acc,
-                         cd.desc, got[blk.down.name][1], cd.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)
-                continue
             if name in kept:
+                c = self.convs[name]
                 if name == "conv1":
                     call("primia_stem_conv_wgrad_clipped_sum", kept[name], clip, c.acc, N)
                 else:
@@ -1371,26 +1363,13 @@ class ResNet18Engine:
                 continue
             if not many:
                 call("primia_scale_rows", dy, clip, N, dy.numel() // N, self.dt)
-            # the clipped SUM is an ordinary batched weight gradient: atomic-free kernels, and for the stem the
-            # halo kernel on the padded input (118 us instead of 444 us for the per-tap one)
-            if self.wgrad_ws is not None and name in self._wg_group:     # same-shape layers: one launch per stage
-                key, n = self._wg_group[name]
-                held = self._wg_held.setdefault(key, [])
-                held.append((name, x, dy))
-                if len(held) == n:
-                    self._flush_wgrad_group(key)
-                continue
-            if self.wgrad_ws is None:
-                call("primia_conv2d_wgrad", c.desc, x, dy, c.acc, self.dt)
-            elif name == "conv1" and self._stem_padded:
-                S = self.spec.input_size
-                call("primia_stem_conv_wgrad_ws", self.x0p, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, N, S, S,
-                     self.dt)
-            else:
-                call("primia_conv2d_wgrad_ws", c.desc, x, dy, c.acc, self.wgrad_ws, self.wgrad_ws_bytes, self.dt)
+            # the clipped SUM is an ordinary batched weight gradient, issued as the plain backward pass issues it: atomic-free
+            # kernels, pairs and groups once their last dy is scaled, and for the stem the halo kernel on the padded input
+            # (118 us instead of 444 us for the per-tap one)
+            self._issue_wgrad(name, x, dy)
         self._finalize_wgrads()
         # clipped sums of the per-sample affine gradients: all 40 (dgamma, dbeta) pairs in ONE launch
-        if getattr(self, "_colsum_many", None) is None:
+        if self._colsum_many is None:
             xs, outs, ws_ = [], [], []
             for b, (psg, psb) in self.ps_affine.items():
                 xs += [psg.data_ptr(), psb.data_ptr()]
@@ -1463,9 +1442,9 @@ class ResNet18Engine:
 
     def _dp_keep_buffers(self):
         """{conv name: fp32 buffer} for the layers whose per-sample tiles the DP-SGD norm pass keeps (built once)."""
-        if getattr(self, "_dp_keep", None) is None:
+        if self._dp_keep is None:
             self._dp_keep = {}
-            if self.dp_keep and self.dtype == torch.bfloat16 and self.wgrad_ws is not None:
+            if self.dp_keep and self.dtype == torch.bfloat16:
                 for c in self.spec.convs:
                     if c.name == "conv1":
                         S = self.spec.input_size

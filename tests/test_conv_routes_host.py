@@ -51,3 +51,13 @@ def test_every_query_answers_as_before_the_route(mint, gold):
     lines = [f"{mint.SETTINGS[s] or 'defaults'} {shp[h]} {'bf16' if mint.DTYPES[d] else 'fp32'} {mint.QUERIES[q]}: "
              f"{got[s, h, d, q]} != {want[s, h, d, q]}" for s, h, d, q in bad[:12].tolist()]
     assert not len(bad), f"{len(bad)} of {want.size} answers changed:\n" + "\n".join(lines)
+
+
+@pytest.mark.parametrize("dt", [_lib.PRIMIA_F32, _lib.PRIMIA_BF16])
+def test_the_stem_always_asks_for_a_weight_gradient_workspace(dt):
+    """conv1 takes the route's stem branch, whose workspace is a product of positive counts: the engine's shared
+    weight-gradient workspace therefore exists at every shape, and the engine has no accumulate-form alternative."""
+    for size in (32, 64, 96, 224):
+        for batch in (1, 4, 256):
+            d = _lib.ConvDesc.make(batch, size, size, 4, 64, 7, 7, 2, 3)
+            assert _lib.query("primia_conv_wgrad_ws_bytes", d, dt) > 0, (batch, size)

@@ -796,6 +796,68 @@ def test_schedule_switches_of_round_6_give_the_same_bits(cuda):
     assert list(root._siblings) == [3, 1, 5]
 
 
+def test_plain_and_dp_passes_issue_the_same_weight_gradient_launches(cuda, monkeypatch):
+    """The plain backward pass and DP-SGD's clipped sums serve every conv's batched weight gradient the same way: with
+    engine.call recorded, one loss_backward and one dp_loss_backward issue the same multiset of weight-gradient launches
+    (entry, descriptor fields, accumulators) — only their order may differ.  bf16, GroupNorm, dp_keep off (every layer
+    takes the two-pass form), batch 4 at 160 x 160: the smallest batch-4 size at which the library's queries give
+    transition pairs AND a same-shape group that does not divide its stage (layer4: groups of 2 for 3 layers) — asserted.
+    With clip factors of exactly 1 (C = 1e12) and no noise the clipped sum is the plain gradient times the batch size, so
+    the step's gradient is the plain one, to the bound tests/test_gpu_dp.py holds a bf16 clipped gradient to against
+    its other form (test_dp_step_with_kept_tiles_matches_the_two_pass_form: 2e-2)."""
+    from primia_amd import _lib, engine as E
+
+    batch, size = 4, 160
+    eng = ResNet18Engine(batch, 3, 3, size, "max", dtype=torch.bfloat16, device=cuda, norm="group", options={"dp_keep": False})
+    pairs, ragged = 0, 0
+    shapes = {}
+    for blk in eng.spec.blocks:
+        if blk.down is not None:
+            pairs += _lib.query("primia_conv_wgrad_pair_ws_bytes", eng.convs[blk.conv1.name].desc,
+                                eng.convs[blk.down.name].desc, eng.dt) > 0
+    for c in eng.spec.convs:
+        d = eng.convs[c.name].desc
+        if d.R == 3 and d.stride == 1 and c.name != "conv1":
+            shapes.setdefault((d.H, d.W, d.C, d.K), []).append(d)
+    for ds in shapes.values():
+        n = _lib.query("primia_conv_wgrad_group_size", ds[0], len(ds), eng.dt)
+        ragged += n >= 2 and len(ds) % n != 0
+    assert pairs >= 1 and ragged >= 1, (pairs, ragged)
+    torch.manual_seed(51)
+    eng.load_state_dict(rs.init_state_dict(eng.spec, "group"))
+    g = torch.Generator().manual_seed(52)
+    x = torch.randn(batch, 3, size, size, generator=g).to(cuda)
+    y = torch.randint(0, 3, (batch,), generator=g).to(cuda)
+    accs = {c.acc.data_ptr(): name for name, c in eng.convs.items()}
+    entries = ("primia_conv2d_wgrad", "primia_conv2d_wgrad_ws", "primia_conv2d_wgrad_pair_ws", "primia_conv2d_wgrad_group_ws",
+               "primia_stem_conv_wgrad", "primia_stem_conv_wgrad_ws", "primia_stem_bwd_fused")
+    log, real = [], E.call
+
+    def recorder(name, *args, **kw):
+        if name in entries:
+            log.append((name, tuple(tuple(getattr(a, f) for f, _ in a._fields_) for a in args if isinstance(a, _lib.ConvDesc)),
+                        tuple(accs[a.data_ptr()] for a in args if isinstance(a, torch.Tensor) and a.data_ptr() in accs)))
+        return real(name, *args, **kw)
+
+    monkeypatch.setattr(E, "call", recorder)
+    eng.forward(x)
+    eng.loss_backward(y)
+    plain_log, plain = sorted(log), eng.grads.clone()
+    del log[:]
+    eng.forward(x)
+    eng.dp_loss_backward(y, 1e12, 0.0, noise=torch.zeros(eng.P, device=cuda))
+    dp_log, dp = sorted(log), eng.grads.clone()
+    assert torch.all(eng.dp_stats["clip"] == 1.0)
+    assert sorted(a for _, _, acc in plain_log for a in acc) == sorted(eng.convs), "every conv's accumulator is written once"
+    names = {e[0] for e in plain_log}
+    assert {"primia_conv2d_wgrad_pair_ws", "primia_conv2d_wgrad_group_ws", "primia_conv2d_wgrad_ws",
+            "primia_stem_conv_wgrad_ws"} <= names, names
+    assert dp_log == plain_log
+    err = ((dp.double() - plain.double()).norm() / plain.double().norm()).item()
+    print(f"DP gradient at clip = 1 against the plain gradient: {err:.3e}")
+    assert err < 2e-2
+
+
 def test_torchlib_models_resnet18_builds_the_engine(cuda):
     """`from torchlib.models import resnet18` with the keyword arguments /root/reference/train.py:259-268 passes (+ the
     batch size the engine needs): the same network, state-dict compatible with the reference's 122 keys."""
