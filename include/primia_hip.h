@@ -878,6 +878,37 @@ int primia_dp_clip_factors_masked(const double* sq, const int64_t* target, float
                                   primia_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DP-SGD with class weights (csrc/dp_weighted.hip, primia_amd/dp_weights.py).  Replaces the reference's PrivacyEngine
+ * wrapped around nn.CrossEntropyLoss(weight=class_weights) (train.py: weight_classes with differentially_private) and
+ * the exact per-class counts of calc_class_weights under it.
+ * ------------------------------------------------------------------------------------------ */
+/* The per-slot loss gradient DP-SGD clips, for padded and full batches alike — replaces nn.CrossEntropyLoss(weight=w,
+ * ignore_index=-1) and its autograd, PER SAMPLE: loss_n = w[y_n] * CE_n, with no division by the batch's weight sum (which
+ * would couple a sample's gradient to the other samples drawn).  A row with target < 0 gets a zero dlogits row and is not
+ * counted; target >= C poisons the row and the loss with NaN as primia_xent_hard does; every other row gets
+ *     dlogits[n][c] = (float)( w[t] * scale * (softmax_c - [c == t]) )        the product in fp64, rounded once
+ * with scale = 1 / views (it stands in for the primia_scale launch that follows primia_xent_hard[_masked]).
+ * loss[0] = sum over valid rows of w[t] * CE_n / number of valid rows, 0 when there is none.  dlogits may be NULL (loss
+ * only).  One block, no atomics: a pure function of its inputs.  PRIMIA_ERR_ARG for a NULL logits / target / class_weight /
+ * loss, scale <= 0 or not finite, N <= 0 or C <= 0. */
+int primia_xent_dp_weighted(const float* logits, const int64_t* target, const float* class_weight, float scale, float* loss,
+                            float* dlogits, int N, int C, primia_stream_t stream);
+/* The one-off release of a client's per-class record counts — replaces the counting loop of calc_class_weights
+ * (torchlib/utils.py), whose exact counts of private records a DP run cannot use for free:
+ *     counts_out[c] = max(0, rint((double)count_c + (double)sigma * (double)z_c))      int64, 0 <= c < C
+ * with count_c = #{i < n : targets[i] == c}; targets outside [0, C) are not counted.  z is fp32 [C] from the caller, NULL
+ * meaning zeros.  A Gaussian mechanism in which one record moves one entry by 1 (dp_accountant.Ledger.add_release); the
+ * clamp and the rounding are post-processing.  One block.  PRIMIA_ERR_ARG for C <= 0 or C > 16, n < 0, sigma < 0 or not
+ * finite, a NULL counts_out, or a NULL targets with n > 0. */
+int primia_dp_class_counts(const int64_t* targets, int64_t n, int C, const float* z, float sigma, int64_t* counts_out,
+                           primia_stream_t stream);
+/* The same with z_c = element c of block (counter ? *counter : 0) + block_offset of primia_dp_noise_add's noise (the same
+ * device function; C <= 16 is one block).  `counter` is read, not advanced: follow with primia_u64_add(counter, 1). */
+int primia_dp_class_counts_chacha(uint64_t k0, uint64_t k1, uint64_t k2, uint64_t k3, uint64_t nonce, const uint64_t* counter,
+                                  uint64_t block_offset, const int64_t* targets, int64_t n, int C, float sigma,
+                                  int64_t* counts_out, primia_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * BatchNorm with FROZEN statistics: DP-SGD fine-tuning from pretrained (BatchNorm) weights.  Every norm layer is the
  * per-channel affine map z = (y - running_mean) * invstd * gamma + beta with invstd = 1 / sqrtf(running_var + eps);
  * gamma and beta train, the running statistics are never written.  A sample's gradient then depends on that sample

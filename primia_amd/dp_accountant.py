@@ -150,19 +150,32 @@ def _rdp(q, sigma, alpha):
     return max(log_a, 0.0) / (alpha - 1.0)
 
 
-def total_rdp(segments, alphas=None):
-    """[sum over segments (q, sigma, steps) of steps * rdp(q, sigma, alpha) for alpha in alphas]."""
+def rdp_release(sigma, sensitivity, alpha):
+    """Renyi divergence of order alpha of ONE Gaussian release (no sampling) of a vector in which one record moves one
+    entry by `sensitivity`, with noise standard deviation sigma per entry: alpha * sensitivity^2 / (2 sigma^2)."""
+    sigma, sensitivity = float(sigma), float(sensitivity)
+    if sigma <= 0.0:
+        return math.inf
+    return alpha * sensitivity ** 2 / (2.0 * sigma ** 2)
+
+
+def total_rdp(segments, alphas=None, releases=()):
+    """[sum over segments (q, sigma, steps) of steps * rdp(q, sigma, alpha), plus the `releases` (sigma, sensitivity) of
+    rdp_release, for alpha in alphas]."""
     alphas = DEFAULT_ALPHAS if alphas is None else alphas
-    return [sum(int(t) * rdp_sampled_gaussian(q, s, a) for q, s, t in segments if int(t) > 0) for a in alphas]
+    out = [sum(int(t) * rdp_sampled_gaussian(q, s, a) for q, s, t in segments if int(t) > 0) for a in alphas]
+    if releases:
+        out = [r + sum(rdp_release(s, d, a) for s, d in releases) for a, r in zip(alphas, out)]
+    return out
 
 
-def epsilon(segments, delta, alphas=None):
+def epsilon(segments, delta, alphas=None, releases=()):
     """(eps, best order) with eps = min over alpha of total RDP + log(1 / delta) / (alpha - 1)."""
     if not 0.0 < delta < 1.0:
         raise ValueError(f"delta {delta} outside (0, 1)")
     alphas = DEFAULT_ALPHAS if alphas is None else alphas
     best = (math.inf, None)
-    for a, r in zip(alphas, total_rdp(segments, alphas)):
+    for a, r in zip(alphas, total_rdp(segments, alphas, releases)):
         e = r + math.log(1.0 / delta) / (a - 1.0)
         if e < best[0]:
             best = (e, a)
@@ -233,6 +246,16 @@ class Ledger:
         self.segments = []          # [[q, sigma, steps], ...]
         self.capacities = []        # the capacity each segment's steps ran at
         self.overflow_events = 0
+        self.releases = []          # [[sigma, sensitivity, what], ...]: one-off Gaussian releases (add_release)
+
+    def add_release(self, sigma, sensitivity=1.0, what="class counts"):
+        """One Gaussian mechanism on a vector in which one record moves one entry by `sensitivity` (a histogram of the
+        client's records: one count), noise standard deviation `sigma` per entry, no sampling: alpha * sensitivity^2 /
+        (2 sigma^2) at every order, added to the segments' RDP in report()."""
+        sigma, sensitivity = float(sigma), float(sensitivity)
+        if not sigma > 0.0 or not sensitivity >= 0.0:
+            raise ValueError(f"add_release: sigma {sigma} must be positive and sensitivity {sensitivity} non-negative")
+        self.releases.append([sigma, sensitivity, str(what)])
 
     def add_steps(self, q, sigma, steps=1):
         """A changed q, sigma or capacity (a resumed run sizes its own) opens a new segment."""
@@ -264,7 +287,9 @@ class Ledger:
     def report(self):
         """{"epsilon", "delta", "alpha", "steps", "capacity", "overflow_events", "within_plan"}: eps at 0.99 * delta; the
         reported delta is the target while the truncation event fits its 1% share, and 0.99 * delta + its cost after."""
-        eps, alpha = epsilon(self.segments, DELTA_SHARE * self.delta, self.alphas) if self.steps else (0.0, None)
+        rel = [(s, d) for s, d, _ in self.releases]
+        eps, alpha = (epsilon(self.segments, DELTA_SHARE * self.delta, self.alphas, rel) if self.steps or rel
+                      else (0.0, None))
         cost = sum(truncation_cost(self.n, q, t, k, eps) for (q, _, t), k in zip(self.segments, self.capacities))
         ok = cost <= (1.0 - DELTA_SHARE) * self.delta
         return {"epsilon": eps, "delta": self.delta if ok else DELTA_SHARE * self.delta + cost, "alpha": alpha,
@@ -275,7 +300,7 @@ class Ledger:
         return {"n": self.n, "capacity": self.capacity, "delta": self.delta, "planned_steps": self.planned_steps,
                 "alphas": list(self.alphas), "segments": [list(s) for s in self.segments],
                 "segment_capacities": list(self.capacities),
-                "overflow_events": int(self.overflow_events)}
+                "overflow_events": int(self.overflow_events), "releases": [list(r) for r in self.releases]}
 
     @classmethod
     def from_state_dict(cls, d):
@@ -283,11 +308,13 @@ class Ledger:
         led.segments = [[float(q), float(s), int(t)] for q, s, t in d["segments"]]
         led.capacities = [int(k) for k in d.get("segment_capacities", [led.capacity] * len(led.segments))]
         led.overflow_events = int(d["overflow_events"])
+        led.releases = [[float(s), float(k), str(w)] for s, k, w in d.get("releases", [])]     # (absent before releases)
         return led
 
     def line(self, name):
         r = self.report()
         q, sigma = (self.segments[-1][0], self.segments[-1][1]) if self.segments else (0.0, 0.0)
+        rel = "".join(f", incl. release of {w} at sigma = {s!r}" for s, _, w in self.releases)
         return (f"[dp] {name}: (epsilon, delta) = ({r['epsilon']:.6g}, {r['delta']:.3g}) at order {r['alpha']}, "
                 f"q = {q!r}, sigma = {sigma!r}, steps = {r['steps']}, capacity = {r['capacity']}, "
-                f"overflow events = {r['overflow_events']}")
+                f"overflow events = {r['overflow_events']}{rel}")

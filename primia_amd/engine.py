@@ -1240,7 +1240,15 @@ class ResNet18Engine:
         every slot gradient below is g_n / m and a record's gradient a plain sum; the norm pass completes each kernel's
         tile over a record's images (primia_conv2d_wgrad_record_sqnorm: the cross terms between views), dp_stats has
         R entries, and each record's clip factor is expanded to its slots for the clipped sums.  The kept-tile forms
-        are per sample: an engine with views > 1 runs the two-pass form on every layer."""
+        are per sample: an engine with views > 1 runs the two-pass form on every layer.
+
+        With `self.class_weight` set (fp32 [classes] on the device; train.py: weight_classes, primia_amd.dp_weights) the
+        loss is the PER-SAMPLE weighted one, loss_n = w[y_n] * CE_n, and g_n above its gradient: w[y_n] times the
+        unweighted one.  There is no division by the batch's weight sum as in the non-DP weighted mean — it would make
+        g_n depend on which other samples were drawn; the normalisation of w is fixed before training (equal class
+        counts give w = 1 and the unweighted step, bit for bit).  primia_xent_dp_weighted forms w[y_n] / views *
+        (softmax - onehot) on masked and full batches alike and stands in for the loss kernel and the scale after it;
+        everything that follows is a function of dlogits.  engine.loss is the mean of w[y_n] * CE_n over the valid slots."""
         masked = expected_batch is not None
         if accumulate not in (None, "first", "more", "last"):
             raise ValueError("dp_loss_backward: accumulate is None, 'first', 'more' or 'last'")
@@ -1255,7 +1263,9 @@ class ResNet18Engine:
         N, nc, dev = self.N, self.spec.num_classes, self.device
         R = N // m      # a sample is a record of one view
         # per-slot loss gradients: softmax - onehot (xent gives them divided by the batch size), over the record's m views
-        if masked:      # softmax - onehot on valid rows, zeros on padded ones; the loss is the mean over the valid rows
+        if self.class_weight is not None:   # w[y_n] / m * (softmax - onehot), zeros on padded rows: one launch, no scale
+            call("primia_xent_dp_weighted", self.logits, target, self.class_weight, 1.0 / m, self.loss, self.dlogits, N, nc)
+        elif masked:    # softmax - onehot on valid rows, zeros on padded ones; the loss is the mean over the valid rows
             call("primia_xent_hard_masked", self.logits, target, self.loss, self.dlogits, N, nc)
             if m > 1:
                 call("primia_scale", self.dlogits, self.dlogits.numel(), 1.0 / m)

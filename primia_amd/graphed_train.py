@@ -36,6 +36,11 @@ rule above, between replayed ones: the accumulator is a plain buffer.
 An adaptive clipping norm (engine.dp_clip, primia_amd.dp_clip.AdaptiveClip) adds its parameters — rate, quantile, the
 count's noise, the range and z_delta — to the key, never the value of C: the clip-factor, noise and update nodes read and
 write C, the counts and the released fraction in device tensors that exist before the capture.
+
+Class weights (engine.class_weight; under DP-SGD the per-sample weighted loss of primia_xent_dp_weighted) enter the key by
+their presence only: the loss node reads the weights from device memory, so new values written INTO the same tensor take
+effect at the next replay without a new capture, and the tensor's pointer is among those _fingerprint compares — another
+tensor captures again.
 """
 import gc
 import warnings

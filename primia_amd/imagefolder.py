@@ -121,7 +121,9 @@ def register(data_per_rep, targets, args, num_classes, seed):
     reps, n = len(data_per_rep), data_per_rep[0].shape[0]
     fed = bool(getattr(args, "train_federated", False))   # vanilla training mixes per batch instead (utils.py:1249-1267)
     mix = fed and bool(getattr(args, "mixup", False))
-    if not fed or not (mix or getattr(args, "weight_classes", False)):
+    # (a differentially private run keeps hard labels: its class weights enter the per-sample loss, engine.dp_loss_backward)
+    weighted = bool(getattr(args, "weight_classes", False)) and not getattr(args, "differentially_private", False)
+    if not fed or not (mix or weighted):
         return torch.cat(data_per_rep), targets.repeat(reps)
     onehot = To_one_hot(num_classes, device=targets.device)(targets)
     gen = torch.Generator().manual_seed(seed + 7919)          # the shuffled DataLoader of utils.py:697-703

@@ -19,7 +19,9 @@ or "graph:adaptive" has one whatever the flag says, so `--modes graph,graph:adap
 loop in one session, and the line then carries each such mode's final C.  --dp_augmult M (train.py's flag, with
 --dp_sampling poisson) gives every record M views: capacity and expected batch are divided by M, so the engine keeps its
 slots and a step does the same kernel work on M times fewer records; a mode with the suffix ":mM" (graph:m4) has M views
-whatever the flag says, so `--modes graph,graph:m4` alternates the two in one session.  --capacity C fixes the capacity (in
+whatever the flag says, so `--modes graph,graph:m4` alternates the two in one session.  A mode with the suffix ":weighted"
+(graph:weighted) sets a class-weight tensor on its DP engine — train.py's weight_classes = yes under DP, the per-sample
+weighted loss of primia_amd.dp_weights — so `--modes graph,graph:weighted` alternates the two.  --capacity C fixes the capacity (in
 slots of the M = 1 loop) instead of deriving it from --planned_steps.  With --dp the line also
 carries the engine's slots and, per mode, the peak of torch.cuda.max_memory_allocated() over what was allocated before that
 mode's engine was built (the batches, the records, an earlier mode's engine), read after the mode's warm-up: the engine,
@@ -103,8 +105,10 @@ def main():
         views_of[m] = int(suffix) if suffix.isdigit() else (a.dp_augmult if a.dp else 1)
         if suffix.isdigit():
             m = base
-        if m not in ("eager", "graph") and not (a.dp and m in ("eager:adaptive", "graph:adaptive")):
-            raise SystemExit(f"mode {m!r}: eager or graph, with --dp also eager:adaptive or graph:adaptive, and :mM")
+        if m not in ("eager", "graph") and not (a.dp and m in ("eager:adaptive", "graph:adaptive", "eager:weighted",
+                                                                 "graph:weighted")):
+            raise SystemExit(f"mode {m!r}: eager or graph, with --dp also eager:adaptive or graph:adaptive, "
+                             "eager:weighted or graph:weighted, and :mM")
     if any(v < 1 or (v > 1 and not poisson) for v in views_of.values()):
         raise SystemExit("--dp_augmult / a :mM mode: at least 1, and only with --dp --dp_sampling poisson")
     runs, peak = {}, {}
@@ -130,6 +134,10 @@ def main():
 
                 eng.dp_clip = AdaptiveClip(dev, sigma_b=a.batch / 20.0)
                 eng.dp_clip.tensors()
+            if ":weighted" in m:    # the per-sample weighted loss; (1349, 2538, 1345): the chest X-ray set's class counts
+                from primia_amd.dp_weights import balanced_weights
+
+                eng.class_weight = balanced_weights(torch.tensor([1349, 2538, 1345])).to(dev).contiguous()
             if poisson:
                 pl = PoissonLoader(records, labels, max(1, a.batch // views), cap_m, DeviceSampler(dev), micro_batches=K,
                                    views=views)
@@ -166,6 +174,8 @@ def main():
         out["dp_clip"] = {m: runs[m][0].dp_clip.value() if runs[m][0].dp_clip is not None else "fixed" for m in modes}
         out.update(dp_micro_batches=K, engine_slots=runs[modes[0]][0].N, peak_bytes_over_held=peak)
         out["dp_augmult"] = views_of
+        out["class_weight"] = {m: runs[m][0].class_weight.tolist() if runs[m][0].class_weight is not None else None
+                               for m in modes}
         if poisson:
             out.update(records=a.records, capacity=capacity, planned_steps=a.planned_steps,
                        overflow_events={m: runs[m][4].pl.sampler.overflow_events() for m in modes})

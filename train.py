@@ -8,7 +8,7 @@ Same command line, INI keys and worker CSV as the reference's train.py (train.py
         [--save_file F] [--training_name N] [--hip_graph] [--dp_noise {torch,chacha}] [--debug_dp_noise_seed N] \
         [--dp_norm {group,frozen}] [--dp_sampling {shuffle,poisson}] [--dp_delta D] [--dp_micro_batches K] \
         [--dp_clip {fixed,adaptive}] [--dp_clip_quantile G] [--dp_clip_lr R] [--dp_clip_sigma S] [--dp_clip_init C] \
-        [--dp_augmult M]
+        [--dp_augmult M] [--dp_weight_sigma S]
 
 Two deployments of the same federated epoch (torchlib/utils.py:936-1233):
 
@@ -39,6 +39,10 @@ after every epoch and travel in the checkpoint (`dp_clip`).
 augmented views — stored walks of a federated client, M passes through the training transform otherwise — averages their
 gradients and clips the average once: the sensitivity, the sampling rate and the reported (epsilon, delta) are those of
 M = 1, the engine holds M times as many slots (combine with --dp_micro_batches).
+`weight_classes = yes` with differentially_private = yes trains on the per-sample weighted loss w[y] * CE
+(primia_amd.dp_weights): every client releases its per-class record counts once with Gaussian noise of
+`--dp_weight_sigma S`, the release is entered in its ledger, and the counts travel in the checkpoint (`dp_class_counts`) so
+that a resumed run does not pay again.  `mixup` stays refused under DP: a mixed sample contains two records.
 
 `main(args, verbose, optuna_trial, cmd_args)` returns the best validation MCC like the reference's.
 """
@@ -74,7 +78,9 @@ class SyntheticLoader:
         g = torch.Generator().manual_seed(seed)
         self.data = [(torch.randn(batch, channels, size, size, generator=g).to(device),
                       torch.randint(0, num_classes, (batch,), generator=g).to(device)) for _ in range(n_batches)]
-        if args is not None and getattr(args, "train_federated", False) and (args.mixup or args.weight_classes):
+        # (a differentially private run keeps hard labels: its class weights enter the per-sample loss, dp_loss_backward)
+        if args is not None and getattr(args, "train_federated", False) and (
+                args.mixup or (args.weight_classes and not getattr(args, "differentially_private", False))):
             from types import SimpleNamespace
 
             from primia_amd.imagefolder import register
@@ -246,6 +252,10 @@ class DPOptions:
     # M of --dp_augmult: every Poisson-sampled record fills M consecutive slots with augmented views whose gradients are
     # averaged and clipped once (engine.dp_loss_backward(views=M)); batches, capacities and the ledger count records
     augmult: int = 1
+    # weight_classes = yes under DP: the per-sample weighted loss (engine.dp_loss_backward) with weights formed from every
+    # client's per-class counts, released once with Gaussian noise of --dp_weight_sigma (primia_amd.dp_weights)
+    weighted: bool = False
+    weight_sigma: float = 20.0
 
     @classmethod
     def from_args(cls, args, cmd_args):
@@ -264,6 +274,15 @@ class DPOptions:
         augmult = int(flag("dp_augmult", 1))
         if augmult < 1:
             raise SystemExit("--dp_augmult {:d}: the views of a record, at least 1".format(augmult))
+        if on and getattr(args, "mixup", False):
+            raise SystemExit("differentially_private = yes cannot be combined with mixup: a mixed sample contains two "
+                             "records, so one record is no longer bounded by one clipped gradient, and under Poisson "
+                             "sampling the pairing itself depends on who was drawn")
+        weighted = on and bool(getattr(args, "weight_classes", False))
+        weight_sigma = float(flag("dp_weight_sigma", cls.weight_sigma))
+        if not weight_sigma > 0.0:
+            raise SystemExit("--dp_weight_sigma {:g}: the standard deviation of the noise on the released class counts "
+                             "must be positive (exact counts of private records are not free)".format(weight_sigma))
         if on and augmult > 1 and sampling != "poisson":
             raise SystemExit("--dp_augmult {:d} needs --dp_sampling poisson: shuffled loaders hand out samples, not records "
                              "with their augmented views".format(augmult))
@@ -305,7 +324,7 @@ class DPOptions:
             clip = dict(params, z_delta=z_delta)
         return cls(on=on, noise=noise, noise_seed=flag("debug_dp_noise_seed", None), norm=norm,
                    poisson=on and sampling == "poisson", delta=float(flag("dp_delta", 1e-5)), micro=micro if on else 1,
-                   sigma=sigma, clip=clip, augmult=augmult if on else 1)
+                   sigma=sigma, clip=clip, augmult=augmult if on else 1, weighted=weighted, weight_sigma=weight_sigma)
 
 
 def micro_batch_size(slots, k, poisson):
@@ -328,13 +347,14 @@ def saved_clip(state):
     return dict(saved)
 
 
-def poisson_plan(name, n, batch_size, epochs, delta, sigma, spent=None):
+def poisson_plan(name, n, batch_size, epochs, delta, sigma, spent=None, releases=()):
     """(q, planned steps, capacity) of a client with n records: q = floor(batch_size * 2^64 / n) / 2^64 — the probability
     the kernel samples with is the one the accountant is given — over epochs * ceil(n / batch_size) steps.  An expected
     batch that is not below the record count (q >= 1) ends the run: that is not a sampled mechanism.
     `spent` (a resumed run): the checkpoint's ledger.  The plan is then its steps plus the `epochs` still to run, and the
     capacity is the one that keeps the truncation event of ALL of them — the earlier steps at the capacities they ran
-    at — within its 1% of delta."""
+    at — within its 1% of delta.  `releases`: the (sigma, sensitivity) of every one-off release the ledger holds or will
+    hold (the class counts of weight_classes): the capacity is sized on the epsilon of the steps PLUS those."""
     from primia_amd import dp_accountant
 
     try:
@@ -344,8 +364,12 @@ def poisson_plan(name, n, batch_size, epochs, delta, sigma, spent=None):
             name, batch_size, n, str(e)))
     ahead = epochs * -(-n // batch_size)
     if spent is None or not spent.steps:
-        return q, ahead, dp_accountant.capacity_for(n, q, ahead, delta, sigma=sigma)
-    eps = dp_accountant.epsilon(spent.segments + [[q, sigma, ahead]], dp_accountant.DELTA_SHARE * delta)[0]
+        if not releases:
+            return q, ahead, dp_accountant.capacity_for(n, q, ahead, delta, sigma=sigma)
+        eps = dp_accountant.epsilon([[q, sigma, ahead]], dp_accountant.DELTA_SHARE * delta, releases=releases)[0]
+        return q, ahead, dp_accountant.capacity_for(n, q, ahead, delta, eps=eps)
+    eps = dp_accountant.epsilon(spent.segments + [[q, sigma, ahead]], dp_accountant.DELTA_SHARE * delta,
+                                releases=releases)[0]
     return q, spent.steps + ahead, dp_accountant.capacity_for(n, q, ahead, delta, eps=eps,
                                                               spent=spent.truncation_mass())
 
@@ -374,10 +398,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         raise NotImplementedError("only resnet-18 is on the accelerated path")
     if world > 1 and not args.train_federated:
         raise SystemExit("several ranks are several federated clients: launch with --train_federated")
-    if args.differentially_private and (args.weight_classes or args.mixup):
-        # the per-sample (DP-SGD) loss gradient takes hard, unweighted labels: say so before any data is registered
-        raise SystemExit("differentially_private = yes cannot be combined with weight_classes / mixup: the per-sample "
-                         "clipped gradients are formed from hard, unweighted targets")
+    # (refuses DP with mixup — the per-sample clipped gradients take hard labels of ONE record — before any data is registered)
+    dp = DPOptions.from_args(args, cmd_args)
     dtype = torch.float32 if os.environ.get("PRIMIA_DTYPE", "bf16") == "f32" else torch.bfloat16
     n_batches = int(os.environ.get("PRIMIA_SYNTHETIC_BATCHES", 8))
     synthetic = args.data_dir in (None, "synthetic")
@@ -388,7 +410,6 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                 args.data_dir))
         from primia_amd import imagefolder
 
-    dp = DPOptions.from_args(args, cmd_args)
     if dp.micro > 1 and not dp.poisson:     # (refused before any data is registered; a Poisson capacity is rounded up)
         m = micro_batch_size(args.batch_size, dp.micro, False)
         if rank == 0:
@@ -411,6 +432,20 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             epochs_ahead = max(0, args.epochs - int(resume_state["epoch"]) + 1)      # (the saved epoch is run again)
     reps = args.repetitions_dataset if "repetitions_dataset" in vars(args) else 1
 
+    def saved_counts(name):
+        """weight_classes under DP: the class counts client `name` released in the resumed checkpoint (`dp_class_counts`),
+        or None.  Counts released at this run's --dp_weight_sigma are used again and not paid for twice; at another sigma
+        the client releases again, and its ledger then holds both."""
+        held = (resume_state or {}).get("dp_class_counts") or {}
+        entry = held.get(name)
+        if entry is None or float(entry["sigma"]) != dp.weight_sigma or len(entry["counts"]) != num_classes:
+            return None
+        if dp.poisson:      # ... and only where the checkpoint's ledger shows that release paid for
+            old = spent.get(name)
+            if old is None or not any(s == dp.weight_sigma for s, _, _ in old.releases):
+                return None
+        return [int(c) for c in entry["counts"]]
+
     augmult_warned = []     # (the warning about repeated stored views is given once)
 
     def poisson_loader(name, base, client):
@@ -427,12 +462,18 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         if old is not None and old.n != n:
             warn("{:s}: the checkpoint counted {:d} records, this run has {:d}; its segments are kept as they are".format(
                 name, old.n, n))
-        _, planned, capacity = poisson_plan(name, n, args.batch_size, epochs_ahead, dp.delta, dp.sigma, spent=old)
+        # the one-off releases the ledger will hold: the checkpoint's, and this run's class counts unless they are reused
+        releases = [(s, k) for s, k, _ in old.releases] if old is not None else []
+        if dp.weighted and saved_counts(name) is None:
+            releases.append((dp.weight_sigma, 1.0))
+        _, planned, capacity = poisson_plan(name, n, args.batch_size, epochs_ahead, dp.delta, dp.sigma, spent=old,
+                                            releases=releases)
         nonce = client if client is not None else 0
         sampler = dps.DeviceSampler(device, nonce=nonce, debug_seed=dp.noise_seed)
         led = privacy[name] = dp_accountant.Ledger(n, capacity, dp.delta, planned)
         if old is not None:     # the ledger goes on counting; a changed q, sigma or capacity opens a new segment
             led.segments, led.capacities, led.overflow_events = old.segments, old.capacities, old.overflow_events
+            led.releases = old.releases
         if dp.micro > 1 and rank == 0:
             print("dp_micro_batches: {:s}'s steps of capacity {:d} run as K = {:d} passes on an engine of M = {:d} "
                   "slots".format(name, capacity, dp.micro, micro_batch_size(capacity, dp.micro, True) * dp.augmult))
@@ -563,7 +604,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         val_mean_std = (m.cpu(), s.cpu())
         optimizer = {w: EngineOptimizer.from_args(model[w], args) for w in mine}
         # train.py:335-342: Cross_entropy_one_hot (soft targets) with mixup or federated weight_classes
-        soft = bool(args.mixup or args.weight_classes)
+        # (a DP run's weight_classes keeps hard labels: the weights enter the per-sample loss)
+        soft = bool(args.mixup or (args.weight_classes and not dp.on))
         loss_fn = {w: SimpleNamespace(soft=soft) for w in mine}
     else:
         workers, mine = [], []
@@ -587,7 +629,49 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
 
     # class weights (train.py:192-195, utils.py:469-513): counted over the training targets of every client — across
     # ranks the per-class counts are summed — and handed to every engine's loss
-    if args.weight_classes:
+    class_counts_released = {}      # DP: {client: {"counts": [...], "sigma": s}}, the checkpoint's `dp_class_counts`
+    if dp.weighted:
+        # Under DP the counts are a release of private data (primia_amd.dp_weights): every client's per-class RECORD counts
+        # are noised on its own stream (or taken from the resumed checkpoint) BEFORE anything is summed, the ledger is
+        # charged once, the noised integers are summed like the exact ones below, and balanced_weights — 1.0 everywhere on
+        # balanced data — is applied once; the per-sample weighted loss is dp_loss_backward's
+        from primia_amd.dp_weights import balanced_weights, noised_counts
+
+        loaders = train_loader if isinstance(train_loader, dict) else {"model": train_loader}
+        engines_by_name = model if isinstance(model, dict) else {"model": model}
+        occ = torch.zeros(num_classes, dtype=torch.int64, device=device)
+        for name in sorted(loaders):
+            counts = saved_counts(name)
+            if counts is None:
+                tl = loaders[name]
+                t = tl.targets
+                if hasattr(tl, "threshold"):        # a Poisson loader: its n records
+                    t = t[:tl.n]
+                elif not hasattr(tl, "images") and args.train_federated and not synthetic:
+                    t = t[:t.shape[0] // int(reps or 1)]        # a registered folder holds repetitions_dataset walks
+                counts = noised_counts(t.to(device), num_classes, dp.weight_sigma,
+                                       engines_by_name[name].dp_noise).tolist()
+                if name in privacy:
+                    privacy[name].add_release(dp.weight_sigma)
+            class_counts_released[name] = {"counts": counts, "sigma": dp.weight_sigma}
+            occ += torch.tensor(counts, dtype=torch.int64, device=device)
+        if world > 1:
+            import torch.distributed as dist
+
+            if masks is not None:
+                occ = fed.masked_sum(occ, masks)
+            else:
+                dist.all_reduce(occ)
+        cw = balanced_weights(occ).to(device).contiguous()      # ONE tensor for every engine
+        for m in engines_by_name.values():
+            m.class_weight = cw
+        if rank == 0:
+            print("dp_weights: released class counts (all clients, noise sigma {:g} per client) = {}, weights = {}".format(
+                dp.weight_sigma, [int(c) for c in occ.tolist()], [round(float(w), 6) for w in cw.tolist()]))
+            if not dp.poisson:
+                print("dp_weights: every client's class counts were released once with Gaussian noise of sigma {:g}; "
+                      "shuffle mode reports no (epsilon, delta)".format(dp.weight_sigma))
+    elif args.weight_classes:
         from primia_amd.datapipe import class_counts, class_weights_from_counts
 
         # counted from the loaders' held targets (no batch is drawn: the augmentation and shuffle streams stay where
@@ -676,6 +760,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
                                        states[name]["quantile"], states[name]["updates"]))
         return states
 
+    # released values: every rank's clients', so that a resumed run uses them again and does not pay twice
+    class_counts_ckpt = all_ranks(class_counts_released) if dp.weighted else None
     objectives, model_paths = [], []
     local_flat = None
     for epoch in range(start_at_epoch, args.epochs + 1):
@@ -685,7 +771,7 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
             w = mine[0]
             avg_loss, _, local_flat, optimizer[w] = fed.federated_epoch(
                 model[w], train_loader[w], args, optimizer[w], group=group, local_flat=local_flat, masks=masks,
-                soft_targets=bool(args.mixup or args.weight_classes))
+                soft_targets=soft)
             local.flat.copy_(local_flat)              # "local_model": the last global average
             for b in local.num_batches_tracked:
                 local.num_batches_tracked[b] = 0
@@ -703,6 +789,8 @@ def main(args, verbose=True, optuna_trial=None, cmd_args=None):
         ckpt_extra = {"dp_privacy": account()} if dp.poisson else {}
         if dp.clip is not None:
             ckpt_extra["dp_clip"] = clip_report()
+        if class_counts_ckpt is not None:
+            ckpt_extra["dp_class_counts"] = class_counts_ckpt
         if epoch % args.test_interval == 0:
             # the checkpoint holds every worker's optimizer state (utils.py:1471-1472): collect them on rank 0.  (One process
             # keeps handing save_model the optimizer OBJECTS, as before: not all_ranks' own world == 1 case, which would
@@ -837,6 +925,11 @@ def build_parser():
                         help="with differentially_private = yes and --dp_sampling poisson: augmentation multiplicity — every "
                              "sampled record contributes the average gradient of M augmented views, clipped once (De et al. "
                              "2022).  The privacy cost is that of M = 1; the engine holds M times as many slots")
+    parser.add_argument("--dp_weight_sigma", type=float, default=20.0, metavar="S",
+                        help="differentially_private = yes with weight_classes = yes: the standard deviation of the Gaussian "
+                             "noise every client adds to its per-class record counts before they are summed into the class "
+                             "weights — a one-off release entered in the client's ledger (at n = 1721, batch 256, 280 steps: "
+                             "epsilon 14.0286 without, 14.0321 with S = 20, 14.0426 with S = 10).  Must be positive")
     parser.add_argument("--dp_micro_batches", type=passes, default=1, metavar="K",
                         help="differentially_private = yes: run every step as K passes of (forward, per-sample clip, "
                              "clipped sum) on an engine of 1 / K of the batch (shuffle: batch_size must be a multiple of K) "
