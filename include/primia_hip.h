@@ -1455,6 +1455,32 @@ int primia_dif_eval_local_n(const int64_t* x1_0, const int64_t* x1_1, int w1, in
                             const uint64_t* s0_0, const uint64_t* s0_1, const uint8_t* cw_bits, const uint64_t* cw_sigma,
                             const uint64_t* cw_s, const int32_t* cw_leaf, int64_t* out0, int64_t* out1, int64_t n, int bits,
                             primia_stream_t stream);
+/* The key generation and evaluation entry points above with the PRG an argument ("FSS keys from a ChaCha20
+ * PRG", defines it; kernels: csrc/fss_chacha.hip).  prg = PRIMIA_PRG_SHA: the reference's SHA-512 / SHA-256 of the seed, i.e. the
+ * entry point without `_prg` (the DIF's `_n` one at `bits`).  prg = PRIMIA_PRG_CHACHA: H / G = the ChaCha20 block keyed by the
+ * seed, 20 rounds, counter 0, one nonce tag per construction; key layout, field sizes and every argument keep their meaning (the
+ * DIF takes the `_n` shapes: x uint64, `bits` levels; the DPF is 32 bits wide).  Keys of one PRG are evaluated with that PRG.
+ * Any other prg, and bits outside [32, 64], is PRIMIA_ERR_ARG before any launch. */
+#define PRIMIA_PRG_SHA 0
+#define PRIMIA_PRG_CHACHA 1
+int primia_dif_keygen_prg(const uint64_t* alpha, const uint64_t* s0_pair, uint8_t* cw_bits, uint64_t* cw_sigma, uint64_t* cw_s,
+                          int32_t* cw_leaf, int64_t n, int bits, int prg, primia_stream_t stream);
+int primia_dif_eval_prg(int b, const uint64_t* x, const uint64_t* s0, const uint8_t* cw_bits, const uint64_t* cw_sigma,
+                        const uint64_t* cw_s, const int32_t* cw_leaf, int64_t* out, int64_t n, int bits, int prg,
+                        primia_stream_t stream);
+int primia_dif_eval_local_prg(const int64_t* x1_0, const int64_t* x1_1, int w1, int start1, const int64_t* x2_0,
+                              const int64_t* x2_1, int w2, int start2, int len, const uint64_t* alpha0, const uint64_t* alpha1,
+                              const uint64_t* s0_0, const uint64_t* s0_1, const uint8_t* cw_bits, const uint64_t* cw_sigma,
+                              const uint64_t* cw_s, const int32_t* cw_leaf, int64_t* out0, int64_t* out1, int64_t n, int bits,
+                              int prg, primia_stream_t stream);
+int primia_dpf_keygen_prg(const uint64_t* alpha, const uint64_t* s0_pair, uint8_t* cw_bits, uint64_t* cw_s, int64_t* cw_n,
+                          int64_t n, int prg, primia_stream_t stream);
+int primia_dpf_eval_prg(int b, const uint32_t* x, const uint64_t* s0, const uint8_t* cw_bits, const uint64_t* cw_s,
+                        const int64_t* cw_n, int64_t* out, int64_t n, int prg, primia_stream_t stream);
+int primia_dpf_eval_local_prg(const int64_t* x1_0, const int64_t* x1_1, int w1, int start1, const int64_t* x2_0,
+                              const int64_t* x2_1, int w2, int start2, int len, const uint64_t* alpha0, const uint64_t* alpha1,
+                              const uint64_t* s0_0, const uint64_t* s0_1, const uint8_t* cw_bits, const uint64_t* cw_s,
+                              const int64_t* cw_n, int64_t* out0, int64_t* out1, int64_t n, int prg, primia_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -220,6 +220,12 @@ if __name__ == "__main__":
                              "|d| / 2^n over the provider's mask, and always beyond 2^(n-1): at 32 bits and 6 fractional "
                              "digits that is every activation above 2147.  Key bytes (60 + 37 n per comparison) and the "
                              "comparison kernels' time grow linearly with n")
+    parser.add_argument("--fss_prg", choices=("sha", "chacha"), default="sha",
+                        help="encrypted inference: the PRG of the comparison and equality keys.  sha (default): the "
+                             "reference's SHA-512 / SHA-256 of the seed, keys a PySyft 0.2.9 party could evaluate; chacha: the "
+                             "ChaCha20 block function keyed by the seed (20 rounds), the same constructions, key bytes and "
+                             "results at about a quarter of the instructions per level (DESIGN.md §4; defined here, not by "
+                             "the reference).  With every other option")
     parser.add_argument("--hip_graph", action="store_true",
                         help="encrypted inference: capture the online phase once as a hipGraph and replay it per image "
                              "(the dealer refills the primitive buffers between images)")
@@ -335,7 +341,8 @@ if __name__ == "__main__":
         warn_of_large_products(sd, images, cmd_args.precision_fractional, pooling)
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
-        form = ProtocolForm(pooling=pooling, reveal=reveal, fss_bits=fss_bits, wide_norm=wide, faithful_trunc=faithful)
+        form = ProtocolForm(pooling=pooling, reveal=reveal, fss_bits=fss_bits, fss_prg=cmd_args.fss_prg, wide_norm=wide,
+                            faithful_trunc=faithful)
         if cmd_args.three_role:
             import torch.distributed as dist
 
@@ -382,8 +389,8 @@ if __name__ == "__main__":
                 model = GraphedSecureInference(shared_sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
                                                seed=cmd_args.debug_dealer_seed, batch=bs, form=form)
             else:
-                ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits), base=10,
-                                    precision_fractional=cmd_args.precision_fractional)
+                ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits, fss_prg=cmd_args.fss_prg),
+                                    base=10, precision_fractional=cmd_args.precision_fractional)
                 model = SecureResNet18(ctx, shared_sd, input_size=size, form=form)
             if reveal in ("confusion", "metrics"):      # an evaluation: the passes return nothing, the matrix is opened after the last
                 model.begin()

@@ -47,18 +47,48 @@ def check_fss_bits(bits):
     return bits
 
 
-def fss_call(name, bits, *args):
+# The PRG of the FSS keys: "sha", the reference's SHA-512 / SHA-256 of the seed and the default, or "chacha", the
+# ChaCha20 block keyed by the seed -- the same constructions, key layout and bytes, about a quarter of the instructions per level.
+# Keys of one PRG are evaluated with that PRG: like the width, it is the dealer's, and public.
+FSS_PRGS = {"sha": 0, "chacha": 1}      # name -> the `prg` argument of the primia_*_prg entry points
+FSS_PRG = "sha"
+_PRG_ENTRY = ("dif_keygen", "dif_eval", "dif_eval_local")      # the DIF entry points a PRG has a form of (the rest hash nothing)
+
+
+def check_fss_prg(prg):
+    if prg not in FSS_PRGS:
+        raise ValueError(f"fss_prg must be one of {' / '.join(map(repr, FSS_PRGS))}, got {prg!r}")
+    return prg
+
+
+def fss_call(name, bits, *args, prg=FSS_PRG):
     """A DIF entry point of the library at width `bits`: the reference's 32-bit one (primia_<name>), or its width-general
-    form (primia_<name>_n, which takes the width last).  The one place where the width selects anything."""
-    if bits == FSS_BITS:
+    form (primia_<name>_n, which takes the width last) -- under another PRG than the reference's, primia_<name>_prg (the width,
+    then the PRG; the entry points that hash nothing take their `_n` form at every width, whose uint64 masked input the
+    PRG's evaluation reads).  The one place where the width or the PRG selects anything."""
+    if prg != FSS_PRG:
+        if name in _PRG_ENTRY:
+            call("primia_" + name + "_prg", *args, bits, FSS_PRGS[prg])
+        else:
+            call("primia_" + name + "_n", *args, bits)
+    elif bits == FSS_BITS:
         call("primia_" + name, *args)
     else:
         call("primia_" + name + "_n", *args, bits)
 
 
-def masked_dtype(bits):
-    """What holds an opened masked input: uint32 words at the reference's width, uint64 words above it."""
-    return torch.int32 if bits == FSS_BITS else I64
+def dpf_call(name, *args, prg=FSS_PRG):
+    """A DPF entry point of the library (always 32 bits wide): primia_<name>, or primia_<name>_prg under another PRG."""
+    if prg != FSS_PRG:
+        call("primia_" + name + "_prg", *args, FSS_PRGS[prg])
+    else:
+        call("primia_" + name, *args)
+
+
+def masked_dtype(bits, prg=FSS_PRG):
+    """What holds an opened masked input of a comparison: uint32 words at the reference's width under the reference's PRG,
+    uint64 words otherwise."""
+    return torch.int32 if bits == FSS_BITS and prg == FSS_PRG else I64
 
 
 def _empty_like(t):
@@ -100,12 +130,13 @@ class Dealer:
     public).  `seed` is for tests, benchmarks and oracle replay only: it derives the key from the seed
     (SHA-256), making the whole stream reproducible — and therefore worthless as a secret."""
 
-    def __init__(self, device, seed=None, fss_bits=FSS_BITS):
+    def __init__(self, device, seed=None, fss_bits=FSS_BITS, fss_prg=FSS_PRG):
         import hashlib
         import os
 
         self.device = torch.device(device)
         self.fss_bits = check_fss_bits(fss_bits)
+        self.fss_prg = check_fss_prg(fss_prg)      # the PRG of every key it generates, comparison or equality
         self.seeded = seed is not None
         raw = os.urandom(40) if seed is None else hashlib.sha256(b"primia-dealer-debug-seed:%d" % int(seed)).digest() + bytes(8)
         self._key = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(4)]
@@ -177,9 +208,9 @@ class Dealer:
         s0 = self.rand64(2, 2, n)
         r = self.rand64(n)
         a0 = torch.empty(n, dtype=I64, device=dev)
-        fss_call("fss_alpha_split", w, alpha, s0, r, a0, n)
+        fss_call("fss_alpha_split", w, alpha, s0, r, a0, n, prg=self.fss_prg)
         bits, cw_sigma, cw_s, leaf = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in dif_key_fields(n, w))
-        fss_call("dif_keygen", w, alpha, s0, bits, cw_sigma, cw_s, leaf, n)
+        fss_call("dif_keygen", w, alpha, s0, bits, cw_sigma, cw_s, leaf, n, prg=self.fss_prg)
         keys = [dict(alpha=[a0, r][b], s0=s0[b], bits=bits, cw_sigma=cw_sigma, cw_s=cw_s, cw_leaf=leaf) for b in range(2)]
         if self.log is not None:
             self.log.append(("dif", n, alpha.cpu().numpy(), s0.cpu().numpy(), r.cpu().numpy()))
@@ -200,7 +231,7 @@ class Dealer:
         a0 = torch.empty(n, dtype=I64, device=dev)
         call("primia_fss_alpha_split", alpha, s0, r, a0, n)
         bits, cw_s, cw_n = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in dpf_key_fields(n))
-        call("primia_dpf_keygen", alpha, s0, bits, cw_s, cw_n, n)
+        dpf_call("dpf_keygen", alpha, s0, bits, cw_s, cw_n, n, prg=self.fss_prg)
         keys = [dict(alpha=[a0, r][b], s0=s0[b], bits=bits, cw_s=cw_s, cw_n=cw_n) for b in range(2)]
         if self.log is not None:
             self.log.append(("dpf", n, alpha.cpu().numpy(), s0.cpu().numpy(), r.cpu().numpy()))
@@ -235,12 +266,13 @@ def dpf_key_fields(n):
 
 class PreloadedDealer:
     """Online phase only: hands out primitives that a Dealer generated earlier (its `tape`), in
-    the same order — the reference's pre-provisioned crypto store (mpc/primitives.py:161-235).  `fss_bits`: the width of
-    the dealer that generated them."""
+    the same order — the reference's pre-provisioned crypto store (mpc/primitives.py:161-235).  `fss_bits`, `fss_prg`: the
+    width and the PRG of the dealer that generated them."""
 
-    def __init__(self, tape, device, fss_bits=FSS_BITS):
+    def __init__(self, tape, device, fss_bits=FSS_BITS, fss_prg=FSS_PRG):
         self.tape, self.pos, self.device = tape, 0, torch.device(device)
         self.fss_bits = check_fss_bits(fss_bits)
+        self.fss_prg = check_fss_prg(fss_prg)
         self.log = None
 
     def _next(self):
@@ -318,6 +350,11 @@ class SecureContext:
     def fss_bits(self):
         """The width of the comparisons, which is the width of the dealer's keys (32 for a dealer that names none)."""
         return getattr(self.dealer, "fss_bits", FSS_BITS)
+
+    @property
+    def fss_prg(self):
+        """The PRG of the comparisons and equality tests, which is the PRG of the dealer's keys ("sha" for one that names none)."""
+        return getattr(self.dealer, "fss_prg", FSS_PRG)
 
     @property
     def _in_process(self):
@@ -572,7 +609,7 @@ class SecureContext:
         k0, k1 = keys
         fss_call("dif_eval_local", w, None if x1 is None else x1[0], None if x1 is None else x1[1], cols1[0], cols1[1],
                  x2[0], x2[1], cols2[0], cols2[1], length, k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"],
-                 k0["cw_sigma"], k0["cw_s"], k0["cw_leaf"], out[0], out[1], n)
+                 k0["cw_sigma"], k0["cw_s"], k0["cw_leaf"], out[0], out[1], n, prg=self.fss_prg)
         self.stats["dif_evals"] += n
         return out
 
@@ -588,17 +625,18 @@ class SecureContext:
         for j in self.parties:  # mask_builder
             r[j] = _empty_like(xr)
             call("primia_fss_mask", x1[j], x2[j], keys[j]["alpha"], r[j], n)
-        masked = torch.empty(n, dtype=masked_dtype(w), device=xr.device)
+        prg = self.fss_prg
+        masked = torch.empty(n, dtype=masked_dtype(w, prg), device=xr.device)
         if self.party is None:
-            fss_call("fss_open", w, r[0], r[1], masked, n)
+            fss_call("fss_open", w, r[0], r[1], masked, n, prg=prg)
         else:  # the parties exchange their masked shares; the sum is taken mod 2^32 (fss.py:158-170; mod 2^fss_bits)
             opened = self.opener.open(r)
-            fss_call("fss_open", w, opened, self._const(0, opened.device, opened.numel()), masked, n)
+            fss_call("fss_open", w, opened, self._const(0, opened.device, opened.numel()), masked, n, prg=prg)
 
         def one(j):  # evaluate
             o = _empty_like(xr)
             k = keys[j]
-            fss_call("dif_eval", w, j, masked, k["s0"], k["bits"], k["cw_sigma"], k["cw_s"], k["cw_leaf"], o, n)
+            fss_call("dif_eval", w, j, masked, k["s0"], k["bits"], k["cw_sigma"], k["cw_s"], k["cw_leaf"], o, n, prg=prg)
             return o
 
         self.stats["dif_evals"] += n
@@ -704,8 +742,9 @@ class SecureContext:
         if self._local:
             out = _pair(shape, ref.device)
             k0, k1 = keys
-            call("primia_dpf_eval_local", x1[0], x1[1], cols1[0], cols1[1], x2[0], x2[1], cols2[0], cols2[1], length,
-                 k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"], k0["cw_s"], k0["cw_n"], out[0], out[1], n)
+            dpf_call("dpf_eval_local", x1[0], x1[1], cols1[0], cols1[1], x2[0], x2[1], cols2[0], cols2[1], length,
+                     k0["alpha"], k1["alpha"], k0["s0"], k1["s0"], k0["bits"], k0["cw_s"], k0["cw_n"], out[0], out[1], n,
+                     prg=self.fss_prg)
             return out
         if (cols1, cols2, length) != ((1, 0), (1, 0), 1):
             x1 = self._cols(x1, n // length, cols1[0], cols1[1], length)
@@ -724,7 +763,7 @@ class SecureContext:
         def one(j):  # evaluate
             o = torch.empty(shape, dtype=I64, device=ref.device)
             k = keys[j]
-            call("primia_dpf_eval", j, masked, k["s0"], k["bits"], k["cw_s"], k["cw_n"], o, n)
+            dpf_call("dpf_eval", j, masked, k["s0"], k["bits"], k["cw_s"], k["cw_n"], o, n, prg=self.fss_prg)
             return o
 
         return self._each(one)
@@ -1513,6 +1552,9 @@ class ProtocolForm:
     fss_bits: the width of the comparisons (see FSS_BITS), the dealer's.  A request list does not depend on it (image_requests
     ignores it); wider keys count in serving_bytes and in the serving form's refusal of a batch that does not fit.
     SecureResNet18 takes the width from its context's dealer, not from here.
+    fss_prg: the PRG of the comparison and equality keys (see FSS_PRGS), the dealer's like the width: "sha", the reference's, or
+    "chacha".  Request lists, key bytes and the words the dealer draws do not depend on it; the parties evaluate with the PRG
+    the keys were generated with, so all three roles must name the same one.
     wide_norm (GroupNorm only): every norm site is `group_norm(wide=True)`, right for any group variance in (0, 30,000) at 3 <=
     precision_fractional <= 6; refused for a BatchNorm or folded network (fold_batch_norm is the remedy there).  The site's
     iteration is `rsqrt_newton`'s, GN_WIDE_STEPS - 1 steps of three triples and a mask with no leading mask: 128 requests per
@@ -1526,11 +1568,28 @@ class ProtocolForm:
     fss_bits: int = FSS_BITS
     wide_norm: bool = False
     faithful_trunc: bool = False
+    # (an init-only keyword kept as an attribute, not a sixth dataclass field: what unpacks a form's fields keeps its five
+    # entries; equality, the hash, the repr and dataclasses.replace carry it all the same)
+    fss_prg: dataclasses.InitVar[str] = FSS_PRG
 
-    def __post_init__(self):
+    def __post_init__(self, fss_prg):
         for name, checked in (("pooling", _check_pooling), ("reveal", _check_reveal), ("fss_bits", check_fss_bits),
                               ("wide_norm", bool), ("faithful_trunc", bool)):
             object.__setattr__(self, name, checked(getattr(self, name)))
+        object.__setattr__(self, "fss_prg", check_fss_prg(fss_prg))
+
+    def _key(self):
+        return dataclasses.astuple(self) + (self.fss_prg,)
+
+    def __eq__(self, other):
+        return other.__class__ is self.__class__ and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        named = [f"{f.name}={getattr(self, f.name)!r}" for f in dataclasses.fields(self)] + [f"fss_prg={self.fss_prg!r}"]
+        return f"ProtocolForm({', '.join(named)})"
 
     @classmethod
     def of(cls, form=None, **options):
@@ -2081,7 +2140,8 @@ class GraphedSecureInference(_FormFields):
     `form` or its fields by keyword: `ProtocolForm`, which says what each `reveal` captures and holds in static buffers."""
 
     refill_graph = True
-    fss_bits = property(lambda self: self.form.fss_bits)      # (this form's own dealers are built at the form's width)
+    fss_bits = property(lambda self: self.form.fss_bits)      # (this form's own dealers are built at the form's width
+    fss_prg = property(lambda self: self.form.fss_prg)        # and with the form's PRG)
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
                  memory_budget=None, *, form=None, **options):
@@ -2104,7 +2164,7 @@ class GraphedSecureInference(_FormFields):
         self.labels = None
         if self.reveal in ACCUMULATING:      # (all-zero one-hot rows: the warm-up images are padding)
             self.labels = torch.zeros(self.batch, int(state_dict["fc.weight"].shape[0]), dtype=I64).to(self.device)
-        self.dealer = Dealer(self.device, seed, self.fss_bits)
+        self.dealer = Dealer(self.device, seed, self.fss_bits, self.fss_prg)
         self.dealer.tape, self.dealer.requests = [], []
         ctx = SecureContext(self.dealer, base, precision_fractional)
         model = SecureResNet18(ctx, state_dict, input_size, blocks, form=form)
@@ -2114,7 +2174,7 @@ class GraphedSecureInference(_FormFields):
         self.dealer.tape = self.dealer.requests = None
         self.stats = dict(ctx.stats)
         self._rehome_tape()                            # per-image random words -> one arena (before any pointer is captured)
-        pre = PreloadedDealer(self.tape, self.device, self.fss_bits)
+        pre = PreloadedDealer(self.tape, self.device, self.fss_bits, self.fss_prg)
         self._ctx = SecureContext(pre, base, precision_fractional)
         self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, form=form)      # re-shares with the same masks
         self._model(self.image, labels=self.labels)    # eager pass over the static buffers: builds the pointer tables
@@ -2132,8 +2192,8 @@ class GraphedSecureInference(_FormFields):
             # rewrites them, and __call__ copies them out.  The tail runs eagerly after the last pass, on a dealer of its
             # own (this form's dealer draws on the device from here on, inside the refill graph)
             self._static_rows = self._model.kept[-1]
-            self._tail_ctx = SecureContext(Dealer(self.device, None if seed is None else seed + 104729, self.fss_bits), base,
-                                           precision_fractional)
+            tail_dealer = Dealer(self.device, None if seed is None else seed + 104729, self.fss_bits, self.fss_prg)
+            self._tail_ctx = SecureContext(tail_dealer, base, precision_fractional)
         # the provider's block counter moves to the device, behind everything the offline pass drew
         self._ctr = torch.tensor([self.dealer._block], dtype=I64).to(self.device)      # (uploaded: no fill kernel)
         self.dealer._block = None                      # (the host counter is dead from here on: rand64 would raise)
@@ -2238,11 +2298,11 @@ class GraphedSecureInference(_FormFields):
             elif op[0] == "dpf":
                 _, m, alpha, s0, r, a0, bits, cw_s, cw_n = op
                 call("primia_fss_alpha_split", alpha, s0, r, a0, m)
-                call("primia_dpf_keygen", alpha, s0, bits, cw_s, cw_n, m)
+                dpf_call("dpf_keygen", alpha, s0, bits, cw_s, cw_n, m, prg=d.fss_prg)
             else:
                 _, m, alpha, s0, r, a0, bits, cw_sigma, cw_s, leaf = op
-                fss_call("fss_alpha_split", d.fss_bits, alpha, s0, r, a0, m)
-                fss_call("dif_keygen", d.fss_bits, alpha, s0, bits, cw_sigma, cw_s, leaf, m)
+                fss_call("fss_alpha_split", d.fss_bits, alpha, s0, r, a0, m, prg=d.fss_prg)
+                fss_call("dif_keygen", d.fss_bits, alpha, s0, bits, cw_sigma, cw_s, leaf, m, prg=d.fss_prg)
         call("primia_u64_add", self._ctr, (n + 7) // 8)
 
     def refill(self):
@@ -2409,9 +2469,10 @@ class PartyDealer:
     (mpc/primitives.py:161-235 keeps the same per-worker store; here nothing is requested — the provider
     follows the public request schedule of the network, see model_requests and image_requests)."""
 
-    def __init__(self, link: PartyLink, fss_bits=FSS_BITS):
+    def __init__(self, link: PartyLink, fss_bits=FSS_BITS, fss_prg=FSS_PRG):
         self.link, self.device, self.j = link, link.device, link.role
-        self.fss_bits = check_fss_bits(fss_bits)      # the provider's width: public, like the request schedule
+        self.fss_bits = check_fss_bits(fss_bits)      # the provider's width and PRG: public, like the request schedule
+        self.fss_prg = check_fss_prg(fss_prg)
         self.log = None
 
     def _mine(self, v):
@@ -2481,7 +2542,7 @@ class DealerService:
 def party_context(link: PartyLink, precision_fractional=16, base=10, *, form=None, **options):
     """SecureContext of the party this rank plays, at the width and with the truncation of the `ProtocolForm`."""
     form = ProtocolForm.of(form, **options)
-    return SecureContext(PartyDealer(link, form.fss_bits), base, precision_fractional,
+    return SecureContext(PartyDealer(link, form.fss_bits, form.fss_prg), base, precision_fractional,
                          opener=DistOpener(link.parties_group, link.role), party=link.role, link=link,
                          faithful_trunc=form.faithful_trunc)
 
@@ -2499,7 +2560,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     passes = (n_images + batch - 1) // batch
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
         image_req = image_requests(arch, input_size, batch, blocks, form=form)
-        svc = DealerService(Dealer(link.device, seed, form.fss_bits), link)
+        svc = DealerService(Dealer(link.device, seed, form.fss_bits, form.fss_prg), link)
         svc.serve(model_requests(arch))
         for _ in range(passes):
             svc.serve(image_req)

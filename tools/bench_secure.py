@@ -19,7 +19,10 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    ROC AUC on its own -- classes * N^2 comparisons at 64 bits -- timed with its dealer and on pre-provisioned
                    primitives, next to the same run's per-image online time
     --fss_bits N:  the width of the comparisons, 32 (default, the reference's) to 64: N levels per key and per evaluation (the
-                   report names it when it is not 32)"""
+                   report names it when it is not 32)
+    --fss_prg chacha: the comparison and equality keys from the ChaCha20 PRG (the report names it; default sha, the reference's)
+    --fss-prg-kernels: fss.le of 2^20 comparisons for both parties and their key generation, under sha and under chacha in
+                   alternation, at 32 and at 64 bits"""
 import argparse, dataclasses, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,7 +31,8 @@ from primia_amd.secure import Dealer, PreloadedDealer, ProtocolForm, SecureConte
 
 def non_default(form):
     """The fields of a ProtocolForm that differ from their defaults, as a dict."""
-    return {f.name: getattr(form, f.name) for f in dataclasses.fields(form) if getattr(form, f.name) != f.default}
+    named = {f.name: getattr(form, f.name) for f in dataclasses.fields(form) if getattr(form, f.name) != f.default}
+    return {**named, **({} if form.fss_prg == ProtocolForm().fss_prg else {"fss_prg": form.fss_prg})}
 
 def main():
     ap = argparse.ArgumentParser()
@@ -56,6 +60,10 @@ def main():
     ap.add_argument("--fss_bits", type=int, default=32,
                     help="the width of the DIF comparisons (32..64): key bytes and DIF kernel time grow linearly with it (the report "
                          "names it when it is not 32)")
+    ap.add_argument("--fss_prg", choices=("sha", "chacha"), default="sha",
+                    help="the PRG of the FSS keys (the report names it when it is chacha)")
+    ap.add_argument("--fss-prg-kernels", action="store_true",
+                    help="time primia_dif_eval_local_prg and primia_dif_keygen_prg alone under both PRGs, alternating, at 32 and 64 bits")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
     ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph replay of the online phase")
     ap.add_argument("--only-fss-roofline", action="store_true",
@@ -117,12 +125,12 @@ def main():
     sd = rs.init_state_dict(rs.resnet18_spec(3, 3, a.size, a.pooling), "group" if a.norm == "group" else "batch")
     if a.norm == "folded":
         sd = fold_batch_norm(sd)
-    form = ProtocolForm(pooling=a.pooling, reveal=a.reveal, fss_bits=a.fss_bits, wide_norm=a.wide_norm,
+    form = ProtocolForm(pooling=a.pooling, reveal=a.reveal, fss_bits=a.fss_bits, fss_prg=a.fss_prg, wide_norm=a.wide_norm,
                         faithful_trunc=a.faithful_trunc)
     # (the report of the default keeps its keys: an option is named only where it differs from the default -- "pooling" for
     # avg only, "norm" for group and folded only -- and in the order the report has always had)
     named = {**non_default(form), **({} if a.norm == "batch" else {"norm": a.norm})}
-    form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits") if k in named}
+    form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits", "fss_prg") if k in named}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
@@ -233,7 +241,7 @@ def main():
             with_dealer = (time.perf_counter() - t0) * 1e3
             rows, classes = passes * B, int(sd["fc.weight"].shape[0])
             comparisons = tail_ctx.stats["dif_evals"] - evals0
-            pre = SecureContext(PreloadedDealer(tail_ctx.dealer.tape, dev, fss_bits=form.fss_bits), 10, a.pf)
+            pre = SecureContext(PreloadedDealer(tail_ctx.dealer.tape, dev, form.fss_bits, form.fss_prg), 10, a.pf)
             for u in gi._model.U:
                 u.zero_()
             t0 = time.perf_counter(); gi._model.finish(ctx=pre); torch.cuda.synchronize()
@@ -256,6 +264,44 @@ def main():
                           "beaver_mul": gi.stats["beaver_mul"], **tail_kw}))
         return
 
+    def fss_prg_kernels():
+        """The comparison kernels alone under both PRGs: 2^20 comparisons, both parties in one launch (x1 = NULL, the ReLU
+        form) and the dealer's key generation, the two PRGs alternating launch by launch in this one process; the median of 7
+        launches each, the spread as (min, max), and the key bytes the evaluation reads per second (25 B per level under
+        chacha, whose kernel reads the low word of cw_sigma only; 29 B under sha)."""
+        from primia_amd._lib import call
+        from primia_amd.secure import dif_key_fields
+        n, reps, rec = 1 << 20, 7, {}
+        for bits in (32, 64):
+            d = Dealer(dev, seed=7, fss_bits=bits)
+            raw = [d.rand64(n), d.rand64(2, 2, n)]
+            x2 = [d.rand64(n), d.rand64(n)]
+            a_sh = [d.rand64(n), d.rand64(n)]
+            out = [torch.empty(n, dtype=torch.int64, device=dev) for _ in range(2)]
+            fields = {prg: [torch.empty(sh, dtype=dt, device=dev) for sh, dt in dif_key_fields(n, bits)] for prg in (0, 1)}
+            keygen = lambda prg: call("primia_dif_keygen_prg", raw[0], raw[1], *fields[prg], n, bits, prg)
+            evalua = lambda prg: call("primia_dif_eval_local_prg", None, None, 1, 0, x2[0], x2[1], 1, 0, 1, a_sh[0], a_sh[1],
+                                      raw[1][0], raw[1][1], *fields[prg], out[0], out[1], n, bits, prg)
+            for name, fn in (("keygen", keygen), ("eval_local", evalua)):
+                times = {0: [], 1: []}
+                for it in range(reps + 2):
+                    for prg in (0, 1):
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(); fn(prg); e1.record(); torch.cuda.synchronize()
+                        if it >= 2:      # (two warm-up launches each)
+                            times[prg].append(e0.elapsed_time(e1))
+                for prg, label in ((0, "sha"), (1, "chacha")):
+                    t = sorted(times[prg])
+                    r = {"median_ms": round(t[len(t) // 2], 3), "min_ms": round(t[0], 3), "max_ms": round(t[-1], 3)}
+                    if name == "eval_local":
+                        r["key_read_GBps"] = round(2 * n * bits * (25 if prg else 29) / (t[len(t) // 2] * 1e-3) / 1e9, 1)
+                    rec[f"{name}_{bits}_{label}"] = r
+        return rec
+
+    if a.fss_prg_kernels:
+        print(json.dumps({"fss_prg_kernels": fss_prg_kernels(), "comparisons": 1 << 20}))
+        return
+
     if a.only_fss_roofline:
         d = Dealer(dev, seed=3)
         for _ in range(3):
@@ -264,12 +310,12 @@ def main():
         return
 
     # warm-up (JIT-free, but first launches / allocator)
-    run(Dealer(dev, seed=0, fss_bits=form.fss_bits))
+    run(Dealer(dev, seed=0, fss_bits=form.fss_bits, fss_prg=form.fss_prg))
     res = []
     for i in range(a.images):
-        d = Dealer(dev, seed=100 + i, fss_bits=form.fss_bits); d.tape = []
+        d = Dealer(dev, seed=100 + i, fss_bits=form.fss_bits, fss_prg=form.fss_prg); d.tape = []
         t_total, out_a, ctx = run(d)
-        t_online, out_b, _ = run(PreloadedDealer(d.tape, dev, fss_bits=form.fss_bits))
+        t_online, out_b, _ = run(PreloadedDealer(d.tape, dev, form.fss_bits, form.fss_prg))
         assert torch.equal(out_a.cpu(), out_b.cpu()), "replayed run must be bit-identical"
         res.append((t_total, t_online))
         del d
@@ -284,7 +330,7 @@ def main():
             from primia_amd.secure import GraphedSecureInference
 
             gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, form=form)
-            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, fss_bits=form.fss_bits), 10, a.pf)
+            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, form.fss_bits, form.fss_prg), 10, a.pf)
             out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, form=form)(img)
             assert torch.equal(gi(img, refill=False).cpu(), out_ref.cpu()), "graph replay must be bit-identical"
             torch.cuda.synchronize(); t0 = time.perf_counter()
