@@ -1389,6 +1389,41 @@ int primia_beaver_combine_matmul(int j, const int64_t* delta, const int64_t* eps
                                  const int64_t* b, const int64_t* c, int64_t* z, int64_t* scratch,
                                  int M, int K, int N, primia_stream_t stream);
 
+/* ---- Convolution-shaped Beaver triples (csrc/ring_conv.hip) ----------------------------------------------
+ * conv2d (nn/functional.py:204-308) is bilinear, so its triple can have the convolution's own shape: a like the input
+ * [B][C][H][W], b like the weights [O][C][R][S], c = conv(a, b) [B][O][Ho][Wo] (zero padded, mod 2^64) -- no im2col operand
+ * is stored, opened or read.  Geometries: R = S with (R, stride) in {(7, 2), (3, 1), (3, 2), (1, 2)}, 0 <= pad < R, any B, C,
+ * O, H, W with Ho, Wo > 0; another (R, S, stride): PRIMIA_ERR_UNSUPPORTED.  Null pointers or a bad geometry: PRIMIA_ERR_ARG,
+ * before anything is launched.  Nothing is allocated; every launch captures into a graph.
+ *   primia_ring_conv2d        out = [out +] conv(x, w): the plain ring convolution (accumulate != 0 adds to out)
+ *   primia_ring_conv2d_split  host query: the number of input-channel slices the launcher gives this geometry (combined
+ *                             with 64-bit atomics; `jobs` = 2 for the two-party form primia_beaver_conv_local launches)
+ *   primia_beaver_combine_conv  spdz_compute (mpc/spdz.py:63-122) of party j in {0,1} on opened delta [B][C][H][W] and eps
+ *                             [O][C][R][S]: z = c + conv(delta, b [+ eps if j == 0]) + conv(a, eps), one launch of the
+ *                             two-product kernel; `scratch` holds O*C*R*S int64 (b + eps, party 0 only; may be null for j = 1)
+ *   primia_beaver_conv_local  both parties hosted in one process: spdz_mask of both operands, both opens (additions), both
+ *                             parties' combines in one grid and each party's truncation of its share by `div` (toward zero,
+ *                             like primia_trunc_div) into NCHW -- primia_beaver_matmul_local + primia_trunc_col2out_2p of
+ *                             the im2col form.  div = 0 leaves the product shares untruncated: the faithful chain
+ *                             (primia_trunc_faithful_col2out_2p in its identity layout) takes them as they are.
+ *                             `scratch`: primia_beaver_conv_local_scratch_elems int64 (delta, eps, b0 + eps)
+ *   primia_triple_conv_c1     the dealer's completion (mpc/beaver.py:7-63): c1 = conv(a0 + a1, b0 + b1) - c0 with the other
+ *                             five shares uniform; `scratch`: B*C*H*W + O*C*R*S int64 */
+int primia_ring_conv2d(const int64_t* x, const int64_t* w, int64_t* out, int B, int C, int H, int W, int O, int R, int S,
+                       int stride, int pad, int accumulate, primia_stream_t stream);
+int primia_ring_conv2d_split(int B, int C, int H, int W, int O, int R, int S, int stride, int pad, int jobs);
+int primia_beaver_combine_conv(int j, const int64_t* delta, const int64_t* eps, const int64_t* a, const int64_t* b,
+                               const int64_t* c, int64_t* z, int64_t* scratch, int B, int C, int H, int W, int O, int R, int S,
+                               int stride, int pad, primia_stream_t stream);
+int64_t primia_beaver_conv_local_scratch_elems(int B, int C, int H, int W, int O, int R, int S);
+int primia_beaver_conv_local(const int64_t* x0, const int64_t* x1, const int64_t* w0, const int64_t* w1, const int64_t* a0,
+                             const int64_t* b0, const int64_t* c0, const int64_t* a1, const int64_t* b1, const int64_t* c1,
+                             int64_t* out0, int64_t* out1, int64_t* scratch, int B, int C, int H, int W, int O, int R, int S,
+                             int stride, int pad, int64_t div, primia_stream_t stream);
+int primia_triple_conv_c1(const int64_t* a0, const int64_t* a1, const int64_t* b0, const int64_t* b1, const int64_t* c0,
+                          int64_t* c1, int64_t* scratch, int B, int C, int H, int W, int O, int R, int S, int stride, int pad,
+                          primia_stream_t stream);
+
 /* ---- Function Secret Sharing (mpc/fss.py), n comparisons, lambda = 127, 32-bit inputs --------
  * Key layout (struct of arrays, comparison index fastest):
  *   s0        uint64 [2][n]        party's initial seed (word 0 has 63 bits)

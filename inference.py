@@ -226,6 +226,14 @@ if __name__ == "__main__":
                              "ChaCha20 block function keyed by the seed (20 rounds), the same constructions, key bytes and "
                              "results at about a quarter of the instructions per level (DESIGN.md §4; defined here, not by "
                              "the reference).  With every other option")
+    parser.add_argument("--conv_triples", action="store_true",
+                        help="encrypted inference: Beaver triples of the convolution's own shape (a like the input, b like the "
+                             "weights, c = conv(a, b)) and a direct convolution kernel over Z_2^64, where the reference (the "
+                             "default) unrolls the input and multiplies matrices.  The parties open the masked input at its "
+                             "own size, not the unrolled operand's (2.2 M words per 224 x 224 image over the 20 convolutions "
+                             "against 14.7 M), a pass holds 200 MB less in primitives per image and writes no im2col operand. "
+                             " The products are the same, the shares differ (other masks); defined here, not by the reference "
+                             "(DESIGN.md §4).  With every other option")
     parser.add_argument("--hip_graph", action="store_true",
                         help="encrypted inference: capture the online phase once as a hipGraph and replay it per image "
                              "(the dealer refills the primitive buffers between images)")
@@ -342,7 +350,7 @@ if __name__ == "__main__":
     if args.encrypted_inference:
         # inference.py:279-286: fix_precision(precision_fractional=16, dtype="long").share(..., protocol="fss")
         form = ProtocolForm(pooling=pooling, reveal=reveal, fss_bits=fss_bits, fss_prg=cmd_args.fss_prg, wide_norm=wide,
-                            faithful_trunc=faithful)
+                            faithful_trunc=faithful, conv_triples=cmd_args.conv_triples)
         if cmd_args.three_role:
             import torch.distributed as dist
 

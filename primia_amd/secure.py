@@ -159,16 +159,18 @@ class Dealer:
         call("primia_ring_sub", v, r, s1, v.numel(), v.numel())
         return [r, s1]
 
-    def triple(self, op, xshape, yshape):
+    def triple(self, op, xshape, yshape, **geom):
+        """op "mul" / "matmul", or "conv" with geom = stride, padding: a of the input's shape [B,C,H,W], b of the weights'
+        [O,C,R,S], c = conv(a, b) [B,O,Ho,Wo]."""
         if self.requests is not None:
-            self.requests.append(("triple", (op, tuple(xshape), tuple(yshape)), {}))
+            self.requests.append(("triple", (op, tuple(xshape), tuple(yshape)), geom))
         # the input shares are drawn directly (a = a0 + a1 with both shares uniform IS the sharing of a uniform a that
         # build_triple produces by drawing a and one share, mpc/beaver.py:7-63): 9 launches per triple instead of 21
         sa = [self.rand64(*xshape), self.rand64(*xshape)]
         sb = [self.rand64(*yshape), self.rand64(*yshape)]
-        c0 = self.rand64(*_triple_c_shape(op, xshape, yshape))
+        c0 = self.rand64(*_triple_c_shape(op, xshape, yshape, **geom))
         c1 = _empty_like(c0)
-        self.triple_c1(op, xshape, yshape, sa[0], sa[1], sb[0], sb[1], c0, c1)
+        self.triple_c1(op, xshape, yshape, sa[0], sa[1], sb[0], sb[1], c0, c1, **geom)
         sc = [c0, c1]
         t = [(sa[j], sb[j], sc[j]) for j in range(2)]
         if self.log is not None:
@@ -177,9 +179,13 @@ class Dealer:
             self.tape.append(t)
         return t
 
-    def triple_c1(self, op, xshape, yshape, a0, a1, b0, b1, c0, c1, scratch=None):
+    def triple_c1(self, op, xshape, yshape, a0, a1, b0, b1, c0, c1, scratch=None, **geom):
         """c1 = (a0 + a1) o (b0 + b1) - c0: the product share that completes a triple whose other five shares are uniform."""
-        if op == "mul":
+        if op == "conv":
+            if scratch is None:
+                scratch = torch.empty(a0.numel() + b0.numel(), dtype=I64, device=self.device)
+            call("primia_triple_conv_c1", a0, a1, b0, b1, c0, c1, scratch, *_conv_geometry(xshape, yshape, **geom))
+        elif op == "mul":
             # element-wise with the smaller operand broadcast over the leading dims
             if a0.numel() >= b0.numel():
                 call("primia_triple_mul_c1", a0, a1, b0, b1, c0, c1, a0.numel(), b0.numel())
@@ -280,7 +286,7 @@ class PreloadedDealer:
         self.pos += 1
         return v
 
-    def triple(self, op, xshape, yshape):
+    def triple(self, op, xshape, yshape, **geom):
         return self._next()
 
     def dif_keys(self, n, bits=None):
@@ -320,14 +326,17 @@ class DistOpener:
 
 
 class SecureContext:
-    def __init__(self, dealer, base=10, precision_fractional=16, opener=None, party=None, link=None, faithful_trunc=False):
+    def __init__(self, dealer, base=10, precision_fractional=16, opener=None, party=None, link=None, faithful_trunc=False,
+                 conv_triples=False):
         """party=None: both parties' shares live in this process (a share is a 2-list).  party=j: this process
         is party j of a distributed run — every 2-list carries only entry j (the other is None), `opener` must
         be a DistOpener and `link` a PartyLink for the owner-to-peer transfer of freshly shared secrets.
         faithful_trunc=True: conv2d, affine_eval and linear truncate their products with `trunc_faithful`, which no mask
-        can make wrap, where the reference's per-share division is off by 2^64 / scale with probability |z| / 2^64."""
+        can make wrap, where the reference's per-share division is off by 2^64 / scale with probability |z| / 2^64.
+        conv_triples=True: conv2d multiplies on a convolution-shaped triple (`ProtocolForm`), with no im2col operand."""
         self.dealer = dealer
         self.faithful_trunc = bool(faithful_trunc)
+        self.conv_triples = bool(conv_triples)
         self.base = base
         self.pf = precision_fractional
         self.scale = base ** precision_fractional
@@ -946,6 +955,8 @@ class SecureContext:
     def conv2d(self, x, w, stride, padding):
         """conv2d (nn/functional.py:204-308): per-share im2col, Beaver matmul + truncation,
         per-share reshape.  x shares [B,C,H,W]; w shares [O,C,R,S]; no bias in ResNet convs."""
+        if self.conv_triples:
+            return self._conv2d_on_conv_triple(x, w, stride, padding)
         B, C, H, W = self._ref(x).shape
         O, _, R, S = self._ref(w).shape
         Ho, Wo = (H + 2 * padding - R) // stride + 1, (W + 2 * padding - S) // stride + 1
@@ -978,6 +989,40 @@ class SecureContext:
             return o
 
         return self._each(one)
+
+    def _conv2d_on_conv_triple(self, x, w, stride, padding):
+        """conv2d under `conv_triples`: the triple ("conv", x's shape, w's shape) has a like the input, b like
+        the weights and c = conv(a, b); the parties open delta = x - a and eps = w - b at the operands' own sizes and combine
+        z_j = conv(delta, b_j + [j = 0] eps) + conv(a_j, eps) + c_j straight into NCHW (csrc/ring_conv.hip), then truncate as
+        the default form does.  No im2col operand, no transposed weight (`_weight_t` is not used).  Both parties here: one
+        entry point (primia_beaver_conv_local; the faithful truncation takes its untruncated product); otherwise the chain,
+        which a three-role run executes -- same dealer requests, same bits."""
+        xr, wr = self._ref(x), self._ref(w)
+        xshape, wshape, dev = tuple(xr.shape), tuple(wr.shape), xr.device
+        geom = _conv_geometry(xshape, wshape, stride, padding)
+        check_conv_triple(*geom[5:8])
+        zshape = _triple_c_shape("conv", xshape, wshape, stride=stride, padding=padding)
+        t = self.dealer.triple("conv", xshape, wshape, stride=stride, padding=padding)
+        self.stats["beaver_matmul"] += 1
+        if self._local:
+            out = _pair(zshape, dev)
+            scratch = torch.empty(_lib.query("primia_beaver_conv_local_scratch_elems", *geom[:7]), dtype=I64, device=dev)
+            call("primia_beaver_conv_local", x[0], x[1], w[0], w[1], *_six(t), out[0], out[1], scratch, *geom,
+                 0 if self.faithful_trunc else int(self.scale))
+            return self.trunc_faithful(out, self.scale) if self.faithful_trunc else out
+        d, e = [None, None], [None, None]
+        for j in self.parties:  # spdz_mask
+            d[j], e[j] = _empty_like(xr), _empty_like(wr)
+            call("primia_beaver_mask", x[j], t[j][0], d[j], xr.numel(), w[j], t[j][1], e[j], wr.numel())
+        delta, eps = self.opener.open(d), self.opener.open(e)
+        scratch = torch.empty(wr.numel(), dtype=I64, device=dev)
+
+        def one(j):  # spdz_compute
+            z = torch.empty(zshape, dtype=I64, device=dev)
+            call("primia_beaver_combine_conv", j, delta, eps, *t[j], z, scratch, *geom)
+            return z
+
+        return self.trunc_product(self._each(one))
 
     _wt_cache_max = 64      # a ResNet-18 has 21 shared weight matrices: room for three models on one context
 
@@ -1562,24 +1607,35 @@ class ProtocolForm:
     faithful_trunc (folded only): the products of conv2d, affine_eval and linear are truncated by `SecureContext.trunc_faithful`
     (SecureResNet18 sets its context's flag), each site requesting the carry triple ("mul", shape, shape) right after its
     product triple, shape that of the product; the Newton norms of the other networks truncate per share and are refused.  Three
-    roles: the parties run the chain (two more opens per site)."""
+    roles: the parties run the chain (two more opens per site).
+    conv_triples: every conv2d multiplies on a triple of the convolution's own shape -- a like the input, b like the weights,
+    c = conv(a, b) in NCHW, requested as ("triple", ("conv", xshape, wshape), {"stride": s, "padding": p}) -- where the
+    reference (and the default) unrolls the input and multiplies matrices.  The parties open x - a at the
+    input's size, not the unrolled operand's: 2,182,656 words per 224 x 224 image over the 20 convolutions against 14,689,024,
+    200,101,888 fewer primitive bytes per image, no im2col operand anywhere.  Every other request, `linear`'s matmul triple
+    included, is as before; a faithful site's carry triple has the product's NCHW shape.  The products run in
+    csrc/ring_conv.hip, which has kernels for a ResNet-18's convolutions -- 7 x 7 / 2, 3 x 3 / 1, 3 x 3 / 2 and 1 x 1 / 2, any
+    padding below the filter size -- and `image_requests` / `SecureResNet18` refuse any other with a ValueError
+    (`check_conv_triple`); shares differ from the default form's (other masks), the opened result is the same product."""
     pooling: str = "max"
     reveal: str = "logits"
     fss_bits: int = FSS_BITS
     wide_norm: bool = False
     faithful_trunc: bool = False
-    # (an init-only keyword kept as an attribute, not a sixth dataclass field: what unpacks a form's fields keeps its five
-    # entries; equality, the hash, the repr and dataclasses.replace carry it all the same)
+    # (init-only keywords kept as attributes, not further dataclass fields: what unpacks a form's fields keeps its five
+    # entries; equality, the hash, the repr and dataclasses.replace carry them all the same)
     fss_prg: dataclasses.InitVar[str] = FSS_PRG
+    conv_triples: dataclasses.InitVar[bool] = False
 
-    def __post_init__(self, fss_prg):
+    def __post_init__(self, fss_prg, conv_triples):
         for name, checked in (("pooling", _check_pooling), ("reveal", _check_reveal), ("fss_bits", check_fss_bits),
                               ("wide_norm", bool), ("faithful_trunc", bool)):
             object.__setattr__(self, name, checked(getattr(self, name)))
         object.__setattr__(self, "fss_prg", check_fss_prg(fss_prg))
+        object.__setattr__(self, "conv_triples", bool(conv_triples))
 
     def _key(self):
-        return dataclasses.astuple(self) + (self.fss_prg,)
+        return dataclasses.astuple(self) + (self.fss_prg, self.conv_triples)
 
     def __eq__(self, other):
         return other.__class__ is self.__class__ and self._key() == other._key()
@@ -1589,6 +1645,8 @@ class ProtocolForm:
 
     def __repr__(self):
         named = [f"{f.name}={getattr(self, f.name)!r}" for f in dataclasses.fields(self)] + [f"fss_prg={self.fss_prg!r}"]
+        if self.conv_triples:      # (named when set: the default form prints as it always has)
+            named.append("conv_triples=True")
         return f"ProtocolForm({', '.join(named)})"
 
     @classmethod
@@ -1678,6 +1736,7 @@ class _FormFields:
     reveal = property(lambda self: self.form.reveal)
     wide_norm = property(lambda self: self.form.wide_norm)
     faithful_trunc = property(lambda self: self.form.faithful_trunc)
+    conv_triples = property(lambda self: self.form.conv_triples)
 
 
 class SecureResNet18(_FormFields):
@@ -1704,16 +1763,20 @@ class SecureResNet18(_FormFields):
         GroupNorm: nothing there is image independent; and with a folded dict: there is no iteration.)
         norm=None: "folded" when the state dict has bn1.scale, "group" when it has no bn1.running_mean, else "batch"; an
         explicit value must agree.
-        `form` or its fields by keyword: `ProtocolForm` (the width is the context's dealer's; a faithful context makes it faithful)."""
+        `form` or its fields by keyword: `ProtocolForm` (the width is the context's dealer's; a faithful context makes it faithful, one with
+        conv_triples set makes it use them)."""
         form = ProtocolForm.of(form, **options)
         self.ctx = ctx
         self.input_size = input_size
         self.batched_newton = batched_newton
         self.norm = norm_of(state_dict.keys(), norm)
         self.blocks = blocks if blocks is not None else _default_blocks()
-        self.form = dataclasses.replace(form, faithful_trunc=True) if ctx.faithful_trunc else form
+        self.form = dataclasses.replace(form, faithful_trunc=form.faithful_trunc or ctx.faithful_trunc,
+                                        conv_triples=form.conv_triples or getattr(ctx, "conv_triples", False))
         self.form.check(self.norm, ctx.base, ctx.pf)
-        ctx.faithful_trunc = self.form.faithful_trunc
+        if self.form.conv_triples:      # (walks the convolutions on the host: an architecture without a kernel is refused here)
+            image_requests(architecture_of(state_dict), input_size, 1, self.blocks, form=self.form)
+        ctx.faithful_trunc, ctx.conv_triples = self.form.faithful_trunc, self.form.conv_triples
         if self.norm == "group":
             for n in _norm_prefixes(state_dict.keys(), self.blocks):
                 c = int(state_dict[n + ".weight"].shape[0])
@@ -1990,8 +2053,13 @@ def image_requests(arch, input_size, batch=1, blocks=None, pooling=..., *, form=
     def conv(name, h, stride, pad):
         o, c, r, _ = arch[name + ".weight"]
         ho = out_hw(h, r, stride, pad)
-        triple("matmul", (B, ho * ho, c * r * r), (c * r * r, o))
-        carry(B, ho * ho, o)
+        if form.conv_triples:
+            check_conv_triple(r, r, stride)
+            req.append(("triple", ("conv", (B, c, h, h), (o, c, r, r)), {"stride": stride, "padding": pad}))
+            carry(B, o, ho, ho)
+        else:
+            triple("matmul", (B, ho * ho, c * r * r), (c * r * r, o))
+            carry(B, ho * ho, o)
         return o, ho
 
     def bn(c, h):
@@ -2085,7 +2153,7 @@ def primitive_bytes(requests, fss_bits=FSS_BITS):
             total += DPF_KEY_BYTES * args[0]
         else:
             op, xs, ys = args
-            total += 16 * (numel(xs) + numel(ys) + numel(_triple_c_shape(op, xs, ys)))
+            total += 16 * (numel(xs) + numel(ys) + numel(_triple_c_shape(op, xs, ys, **kw)))
     return total
 
 
@@ -2260,7 +2328,7 @@ class GraphedSecureInference(_FormFields):
 
         self._ops, max_kn = [], 1
         for i, offs in zip(range(self._n_model, len(self.tape)), plan):
-            kind, args, _ = self.requests[i]
+            kind, args, kw = self.requests[i]
             e = self.tape[i]
             if kind == "const_mask":
                 self.tape[i] = view(offs[0], e)
@@ -2269,8 +2337,8 @@ class GraphedSecureInference(_FormFields):
                 (a0, b0, c0), (a1, b1, c1) = e
                 a0, a1, b0, b1, c0 = (view(o, t) for o, t in zip(offs, (a0, a1, b0, b1, c0)))
                 self.tape[i] = [(a0, b0, c0), (a1, b1, c1)]
-                self._ops.append(("triple", op, xshape, yshape, a0, a1, b0, b1, c0, c1))
-                if op != "mul":      # triple_c1's scratch: a = a0 + a1 [B*L, K] and b = b0 + b1 [K, N]
+                self._ops.append(("triple", op, xshape, yshape, a0, a1, b0, b1, c0, c1, kw))
+                if op != "mul":      # triple_c1's scratch: a = a0 + a1 and b = b0 + b1 (matrices, or a convolution's operands)
                     max_kn = max(max_kn, a0.numel() + b0.numel())
             else:
                 (n,) = args
@@ -2293,8 +2361,8 @@ class GraphedSecureInference(_FormFields):
         call("primia_chacha20_fill_ctr", *d._key, d._nonce, self._ctr, 0, self._arena, n)
         for op in self._ops:
             if op[0] == "triple":
-                _, kind, xshape, yshape, a0, a1, b0, b1, c0, c1 = op
-                d.triple_c1(kind, xshape, yshape, a0, a1, b0, b1, c0, c1, scratch=self._mm_scratch)
+                _, kind, xshape, yshape, a0, a1, b0, b1, c0, c1, geom = op
+                d.triple_c1(kind, xshape, yshape, a0, a1, b0, b1, c0, c1, scratch=self._mm_scratch, **geom)
             elif op[0] == "dpf":
                 _, m, alpha, s0, r, a0, bits, cw_s, cw_n = op
                 call("primia_fss_alpha_split", alpha, s0, r, a0, m)
@@ -2457,7 +2525,25 @@ class PartyLink:
 DPF_CW_NAMES = ("bits", "cw_s", "cw_n")
 
 
-def _triple_c_shape(op, xshape, yshape):
+CONV_TRIPLE_KERNELS = ((7, 2), (3, 1), (3, 2), (1, 2))      # (R = S, stride) of csrc/ring_conv.hip's kernels: a ResNet-18's
+
+
+def check_conv_triple(R, S, stride):
+    """Refuse, before anything is requested or launched, a convolution the direct ring convolution has no kernel for."""
+    if R != S or (R, stride) not in CONV_TRIPLE_KERNELS:
+        raise ValueError(f"conv_triples has no kernel for a {R} x {S} / stride {stride} convolution: it has "
+                         + ", ".join(f"{r} x {r} / {s}" for r, s in CONV_TRIPLE_KERNELS) + " (the default form serves any)")
+
+
+def _conv_geometry(xshape, wshape, stride, padding):
+    """(B, C, H, W, O, R, S, stride, padding) of a convolution-shaped triple: the geometry arguments of the conv entry points."""
+    return (*xshape, wshape[0], wshape[2], wshape[3], stride, padding)
+
+
+def _triple_c_shape(op, xshape, yshape, **geom):
+    if op == "conv":      # x [B,C,H,W], w [O,C,R,S] -> [B,O,Ho,Wo]
+        B, _, H, W, O, R, S, s, p = _conv_geometry(xshape, yshape, **geom)
+        return (B, O, (H + 2 * p - R) // s + 1, (W + 2 * p - S) // s + 1)
     if op == "mul":
         nx = int(torch.Size(xshape).numel())
         return tuple(xshape) if nx >= int(torch.Size(yshape).numel()) else tuple(yshape)
@@ -2480,9 +2566,9 @@ class PartyDealer:
         out[self.j] = v
         return out
 
-    def triple(self, op, xshape, yshape):
+    def triple(self, op, xshape, yshape, **geom):
         f = self.link.from_dealer
-        return self._mine((f(xshape), f(yshape), f(_triple_c_shape(op, xshape, yshape))))
+        return self._mine((f(xshape), f(yshape), f(_triple_c_shape(op, xshape, yshape, **geom))))
 
     def dif_keys(self, n, bits=None):
         f = self.link.from_dealer
@@ -2544,7 +2630,7 @@ def party_context(link: PartyLink, precision_fractional=16, base=10, *, form=Non
     form = ProtocolForm.of(form, **options)
     return SecureContext(PartyDealer(link, form.fss_bits, form.fss_prg), base, precision_fractional,
                          opener=DistOpener(link.parties_group, link.role), party=link.role, link=link,
-                         faithful_trunc=form.faithful_trunc)
+                         faithful_trunc=form.faithful_trunc, conv_triples=form.conv_triples)
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,

@@ -21,6 +21,7 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
     --fss_bits N:  the width of the comparisons, 32 (default, the reference's) to 64: N levels per key and per evaluation (the
                    report names it when it is not 32)
     --fss_prg chacha: the comparison and equality keys from the ChaCha20 PRG (the report names it; default sha, the reference's)
+    --conv_triples: convolution-shaped Beaver triples and the direct ring convolution (the report names it)
     --fss-prg-kernels: fss.le of 2^20 comparisons for both parties and their key generation, under sha and under chacha in
                    alternation, at 32 and at 64 bits"""
 import argparse, dataclasses, json, os, sys, time
@@ -32,7 +33,8 @@ from primia_amd.secure import Dealer, PreloadedDealer, ProtocolForm, SecureConte
 def non_default(form):
     """The fields of a ProtocolForm that differ from their defaults, as a dict."""
     named = {f.name: getattr(form, f.name) for f in dataclasses.fields(form) if getattr(form, f.name) != f.default}
-    return {**named, **({} if form.fss_prg == ProtocolForm().fss_prg else {"fss_prg": form.fss_prg})}
+    return {**named, **({} if form.fss_prg == ProtocolForm().fss_prg else {"fss_prg": form.fss_prg}),
+            **({"conv_triples": True} if form.conv_triples else {})}
 
 def main():
     ap = argparse.ArgumentParser()
@@ -62,6 +64,8 @@ def main():
                          "names it when it is not 32)")
     ap.add_argument("--fss_prg", choices=("sha", "chacha"), default="sha",
                     help="the PRG of the FSS keys (the report names it when it is chacha)")
+    ap.add_argument("--conv_triples", action="store_true",
+                    help="conv2d on triples of the convolution's own shape (the report names it)")
     ap.add_argument("--fss-prg-kernels", action="store_true",
                     help="time primia_dif_eval_local_prg and primia_dif_keygen_prg alone under both PRGs, alternating, at 32 and 64 bits")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
@@ -126,11 +130,11 @@ def main():
     if a.norm == "folded":
         sd = fold_batch_norm(sd)
     form = ProtocolForm(pooling=a.pooling, reveal=a.reveal, fss_bits=a.fss_bits, fss_prg=a.fss_prg, wide_norm=a.wide_norm,
-                        faithful_trunc=a.faithful_trunc)
+                        faithful_trunc=a.faithful_trunc, conv_triples=a.conv_triples)
     # (the report of the default keeps its keys: an option is named only where it differs from the default -- "pooling" for
     # avg only, "norm" for group and folded only -- and in the order the report has always had)
     named = {**non_default(form), **({} if a.norm == "batch" else {"norm": a.norm})}
-    form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits", "fss_prg") if k in named}
+    form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits", "fss_prg", "conv_triples") if k in named}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
