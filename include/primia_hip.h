@@ -48,9 +48,13 @@ int primia_abi_version(void);
 
 /* ---- options -------------------------------------------------------------------------------------------------------
  * The library never reads the environment.  The switches that select between kernels or size a launch, and that a
- * test or a tool still sets, are the eight entries of ONE process-wide table with the defaults the benchmarks run on:
+ * test or a tool still sets, are the nine entries of ONE process-wide table with the defaults the benchmarks run on:
  * primia_set_option("lh2", 0) keeps the wide 3x3 layers on the implicit GEMM, ("s2lh", 7) puts every pass of the
- * transition blocks on conv_s2lh_kernel, ("c64_stages", 3) shortens conv3x3_c64_kernel's ring, ...  The names, defaults
+ * transition blocks on conv_s2lh_kernel, ("c64_stages", 3) shortens conv3x3_c64_kernel's ring, ("ring_mfma", 1) sends the
+ * Z_2^64 matrix products of the encrypted path (primia_ring_matmul, primia_beaver_combine_matmul, primia_triple_matmul_c1,
+ * primia_beaver_matmul_local: every M, K, N > 0) to ring_gemm_mfma_kernel -- signed 8-bit limbs on v_mfma_i32_16x16x64_i8
+ * with exact carry reconstruction, the same bits as the default vector-ALU kernels, same signatures and scratch; it is read
+ * on the host at launch, so a captured graph keeps the kernel it was captured with -- ...  The names, defaults
  * and meanings are listed in primia_amd/csrc/options.h; unknown names return PRIMIA_ERR_ARG.  Options are read when a
  * call dispatches (and by the *_bytes / *_ok / *_kernel_id queries, which therefore must be asked again after a
  * change).  Each entry is read and written atomically (no torn values, callable from any thread), but a SEQUENCE of
@@ -1110,7 +1114,8 @@ int primia_ring_slice_cols(const int64_t* x, int64_t* out, int64_t rows, int64_t
                            int64_t len, primia_stream_t stream);
 
 /* C[M,N] = A[M,K] @ B[K,N]  (+ C if accumulate) mod 2^64 — torch.matmul on LongTensors
- * (mpc/spdz.py:54-59). */
+ * (mpc/spdz.py:54-59).  Launches ring_gemm_kernel (u64 products on the vector ALU) or, under the option ring_mfma,
+ * ring_gemm_mfma_kernel (int8 limbs on the matrix pipe); the bits are the same. */
 int primia_ring_matmul(const int64_t* A, const int64_t* B, int64_t* C, int M, int K, int N,
                        int accumulate, primia_stream_t stream);
 

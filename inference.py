@@ -234,6 +234,12 @@ if __name__ == "__main__":
                              "against 14.7 M), a pass holds 200 MB less in primitives per image and writes no im2col operand. "
                              " The products are the same, the shares differ (other masks); defined here, not by the reference "
                              "(DESIGN.md §4).  With every other option")
+    parser.add_argument("--ring_mfma", action="store_true",
+                        help="encrypted inference: the Z_2^64 matrix products (every Beaver matmul, and the dealer's triples) on "
+                             "the matrix pipe -- signed 8-bit limbs through v_mfma_i32_16x16x64_i8 with exact carry "
+                             "reconstruction -- where the default multiplies 64-bit words on the vector ALU.  The same bits from "
+                             "another kernel: nothing the parties exchange or agree on changes (DESIGN.md §7).  With every other "
+                             "option")
     parser.add_argument("--hip_graph", action="store_true",
                         help="encrypted inference: capture the online phase once as a hipGraph and replay it per image "
                              "(the dealer refills the primitive buffers between images)")
@@ -373,7 +379,7 @@ if __name__ == "__main__":
                                     state_dict=owned,
                                     images=images.to(device) if link.role == 1 else None,   # (this rank's GPU)
                                     seed=cmd_args.debug_dealer_seed, batch=bs,
-                                    precision_fractional=cmd_args.precision_fractional, form=form,
+                                    precision_fractional=cmd_args.precision_fractional, form=form, ring_mfma=cmd_args.ring_mfma,
                                     labels=labels if link.role == 1 and reveal in ("confusion", "metrics") else None)
             dist.barrier()
             dist.destroy_process_group()
@@ -395,10 +401,11 @@ if __name__ == "__main__":
                 from primia_amd.secure import GraphedSecureInference
 
                 model = GraphedSecureInference(shared_sd, device, input_size=size, precision_fractional=cmd_args.precision_fractional,
-                                               seed=cmd_args.debug_dealer_seed, batch=bs, form=form)
+                                               seed=cmd_args.debug_dealer_seed, batch=bs, form=form,
+                                               ring_mfma=cmd_args.ring_mfma)
             else:
                 ctx = SecureContext(Dealer(device, seed=cmd_args.debug_dealer_seed, fss_bits=fss_bits, fss_prg=cmd_args.fss_prg),
-                                    base=10, precision_fractional=cmd_args.precision_fractional)
+                                    base=10, precision_fractional=cmd_args.precision_fractional, ring_mfma=cmd_args.ring_mfma)
                 model = SecureResNet18(ctx, shared_sd, input_size=size, form=form)
             if reveal in ("confusion", "metrics"):      # an evaluation: the passes return nothing, the matrix is opened after the last
                 model.begin()

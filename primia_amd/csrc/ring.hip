@@ -3,6 +3,8 @@
 // (SPDZ) combine step.  Integer work: results are bit-exact by construction (unsigned wrap-around
 // arithmetic on the int64 bit patterns).  Everything except the GEMM is an HBM streaming pass.
 #include "common.h"
+#include "options.h"
+#include "ring_gemm_mfma.h"
 #include "trunc_faithful.h"
 
 namespace primia {
@@ -287,7 +289,8 @@ __global__ __launch_bounds__(64) void newton_local_kernel(const u64* __restrict_
 
 // ---- int64 ring GEMM: C = C0 + A1@B1 + A2@B2 ---------------------------------------------------------
 // 64x64 output tile per 256-thread block, 4x4 outputs per thread, k-step 16 staged through LDS.
-// There is no 64-bit integer MFMA; the products run on the vector ALU (v_mad_u64_u32 chains).
+// There is no 64-bit integer MFMA; the products run on the vector ALU (v_mad_u64_u32 chains).  With the option ring_mfma
+// launch_gemm sends the same sum to ring_gemm_mfma_kernel (ring_gemm_mfma.hip): int8 limbs on the matrix pipe, the same bits.
 struct GemmPair {
     const u64* A;
     const u64* B;
@@ -387,6 +390,10 @@ static int launch_gemm(GemmPair p1, GemmPair p2, const u64* C0, u64* C, int M, i
         if (ksplit > kmax) ksplit = kmax;
         if (ksplit < 1) ksplit = 1;
     }
+    // ring_mfma: slices of whole 64-k steps, none over its accumulators' bound (ksplit rises for K alone, at any tile count)
+    const bool mfma = PRIMIA_OPT(ring_mfma) != 0;
+    int kchunk = 0;
+    if (mfma) ring_mfma_slices(K, p2.A ? 2 : 1, &ksplit, &kchunk);
     if (ksplit > 1) {
         // C = C0 (or zero) before the slices add to it -- by kernels of this library, not hipMemsetAsync / hipMemcpyAsync: as
         // memset NODES of a captured refill graph (GraphedSecureInference) the zeroing of c1 was seen to be lost on replays
@@ -398,6 +405,12 @@ static int launch_gemm(GemmPair p1, GemmPair p2, const u64* C0, u64* C, int M, i
         else if (C0 != C)
             ring_scale_kernel<<<ew_blocks(mn), 256, 0, st>>>(C0, (u64)1, C, mn);
         if (launch_status() != PRIMIA_OK) return PRIMIA_ERR_LAUNCH;
+    }
+    if (mfma) {
+        RingMfmaArgs a{};
+        a.side[0] = RingMfmaSide{p1.A, p1.B, p2.A, p2.B, C0, C};
+        a.M = M, a.K = K, a.N = N, a.ksplit = ksplit, a.kchunk = kchunk;
+        return launch_ring_gemm_mfma(a, 1, st);
     }
     dim3 grid((N + 63) / 64, (M + 63) / 64, ksplit);
     ring_gemm_kernel<<<grid, 256, 0, st>>>(p1, p2, C0, C, M, K, N, ksplit);

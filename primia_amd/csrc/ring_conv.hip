@@ -23,8 +23,9 @@
 // A thread loads one filter row's NW = 3 ES + R input words into registers and reuses them over the S taps of that row: per
 // 16 multiply-adds it issues 4 ds_read_b64 of weights and NW / S of inputs, against 8 in ring_gemm_kernel.
 //
-// Products run on the vector ALU (v_mad_u64_u32 chains): there is no 64-bit integer MFMA, and an 8-bit-limb decomposition
-// onto v_mfma_i32_*_i8 is left to a later change that serves the GEMM too.
+// Products run on the vector ALU (v_mad_u64_u32 chains): there is no 64-bit integer MFMA.  The 8-bit-limb decomposition onto
+// v_mfma_i32_16x16x64_i8 serves the GEMM form (ring_gemm_mfma.hip, option ring_mfma); this kernel can take its staging and
+// matrix loop later.
 //
 // Few tiles (one image in layer3 / layer4: 4 and 1 pixel tiles): the input channels are split over blockIdx.z and the slices
 // combined with 64-bit atomicAdd -- ring addition is associative, so the result is bit-identical whatever the order.  C is

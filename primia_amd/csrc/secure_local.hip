@@ -14,6 +14,8 @@
 // Reference: syft/frameworks/torch/mpc/spdz.py:125-197 (spdz_mul), tensors/interpreters/precision.py:309-316,419-463
 // (FPT mul / matmul + truncation), nn/functional.py:44-75 (batch_norm), :204-308 (conv2d), :460-508 (_pool2d).
 #include "common.h"
+#include "options.h"
+#include "ring_gemm_mfma.h"
 #include "trunc_faithful.h"
 
 namespace primia {
@@ -801,6 +803,15 @@ int primia_beaver_matmul_local(const int64_t* x0, const int64_t* x1, const int64
         const int kmax = (K + 63) / 64;
         if (ksplit > kmax) ksplit = kmax;
         if (ksplit < 1) ksplit = 1;
+    }
+    if (PRIMIA_OPT(ring_mfma)) {      // the same sums on int8 MFMA limbs (ring_gemm_mfma.hip): slices of whole 64-k steps
+        RingMfmaArgs g{};
+        int kchunk = 0;
+        ring_mfma_slices(K, 2, &ksplit, &kchunk);
+        g.side[0] = RingMfmaSide{delta, b0e, U(a0), eps, z.p0, z.p0};
+        g.side[1] = RingMfmaSide{delta, U(b1), U(a1), eps, z.p1, z.p1};
+        g.M = M, g.K = K, g.N = N, g.ksplit = ksplit, g.kchunk = kchunk;
+        return launch_ring_gemm_mfma(g, 2, s);
     }
     const dim3 grid((N + 63) / 64, (M + 63) / 64, 2 * ksplit);
     ring_gemm2_kernel<<<grid, 256, 0, s>>>(delta, eps, b0e, U(b1), U(a0), U(a1), z, M, K, N, ksplit);

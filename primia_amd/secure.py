@@ -327,14 +327,19 @@ class DistOpener:
 
 class SecureContext:
     def __init__(self, dealer, base=10, precision_fractional=16, opener=None, party=None, link=None, faithful_trunc=False,
-                 conv_triples=False):
+                 conv_triples=False, ring_mfma=False):
         """party=None: both parties' shares live in this process (a share is a 2-list).  party=j: this process
         is party j of a distributed run — every 2-list carries only entry j (the other is None), `opener` must
         be a DistOpener and `link` a PartyLink for the owner-to-peer transfer of freshly shared secrets.
         faithful_trunc=True: conv2d, affine_eval and linear truncate their products with `trunc_faithful`, which no mask
         can make wrap, where the reference's per-share division is off by 2^64 / scale with probability |z| / 2^64.
-        conv_triples=True: conv2d multiplies on a convolution-shaped triple (`ProtocolForm`), with no im2col operand."""
+        conv_triples=True: conv2d multiplies on a convolution-shaped triple (`ProtocolForm`), with no im2col operand.
+        ring_mfma=True: the Z_2^64 matrix products run on int8 MFMA limbs (the library's option `ring_mfma`, csrc/ring_gemm_mfma.hip):
+        the same bits from another kernel, so no part of the `ProtocolForm`.  The option is the PROCESS's: the context sets it here
+        and before every pass of a model built on it; a captured graph keeps the kernel it was captured with."""
         self.dealer = dealer
+        self.ring_mfma = bool(ring_mfma)
+        self.apply_options()
         self.faithful_trunc = bool(faithful_trunc)
         self.conv_triples = bool(conv_triples)
         self.base = base
@@ -354,6 +359,10 @@ class SecureContext:
     # The dealer's primitives are requested in exactly the order of the step-by-step chain, results are bit-identical;
     # `local_fused = False` selects the chain (what a three-role run executes, where the opens are messages).
     local_fused = True
+
+    def apply_options(self):
+        """Set the library's process-wide options this context asks for (read on the host when a kernel is launched)."""
+        _lib.set_option("ring_mfma", int(self.ring_mfma))
 
     @property
     def fss_bits(self):
@@ -1756,7 +1765,7 @@ class SecureResNet18(_FormFields):
     running statistics, where the reference's form is accurate only for variances in about [0.05, 16]."""
 
     def __init__(self, ctx: SecureContext, state_dict, input_size=224, blocks=None, batched_newton=True, *, norm=None,
-                 form=None, **options):
+                 form=None, ring_mfma=None, **options):
         """batched_newton=False consumes the provider's primitives in exactly the reference's order (newton(running_var)
         inside every batch_norm call, nn/functional.py:62-69) — the mode the reference-minted fixtures pin; the
         default hoists the image-independent iterations of all BatchNorm layers into one batched vector.  (Ignored with
@@ -1764,7 +1773,7 @@ class SecureResNet18(_FormFields):
         norm=None: "folded" when the state dict has bn1.scale, "group" when it has no bn1.running_mean, else "batch"; an
         explicit value must agree.
         `form` or its fields by keyword: `ProtocolForm` (the width is the context's dealer's; a faithful context makes it faithful, one with
-        conv_triples set makes it use them)."""
+        conv_triples set makes it use them).  ring_mfma: None keeps the context's choice of GEMM kernel, a bool sets it."""
         form = ProtocolForm.of(form, **options)
         self.ctx = ctx
         self.input_size = input_size
@@ -1777,6 +1786,9 @@ class SecureResNet18(_FormFields):
         if self.form.conv_triples:      # (walks the convolutions on the host: an architecture without a kernel is refused here)
             image_requests(architecture_of(state_dict), input_size, 1, self.blocks, form=self.form)
         ctx.faithful_trunc, ctx.conv_triples = self.form.faithful_trunc, self.form.conv_triples
+        if ring_mfma is not None:
+            ctx.ring_mfma = bool(ring_mfma)
+        ctx.apply_options()      # (sharing the model multiplies nothing; every pass sets them again)
         if self.norm == "group":
             for n in _norm_prefixes(state_dict.keys(), self.blocks):
                 c = int(state_dict[n + ".weight"].shape[0])
@@ -1951,6 +1963,7 @@ class SecureResNet18(_FormFields):
         count nowhere); party 0 passes none.  The pass adds into the shared confusion matrix and returns None.
         reveal="metrics": the confusion pass, requests included; its logit and label shares are kept for `finish()`."""
         c = self.ctx
+        c.apply_options()
         if c.party in (None, 1):
             xs = c.share(c.encode(image), owner=1)
         else:
@@ -2212,8 +2225,9 @@ class GraphedSecureInference(_FormFields):
     fss_prg = property(lambda self: self.form.fss_prg)        # and with the form's PRG)
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
-                 memory_budget=None, *, form=None, **options):
+                 memory_budget=None, *, form=None, ring_mfma=False, **options):
         self.form = form = ProtocolForm.of(form, **options)
+        self.ring_mfma = bool(ring_mfma)      # (both graphs are captured with this kernel; the eager refill sets it again)
         self.device = torch.device(device)
         self.batch = int(batch)
         if self.batch < 1:
@@ -2234,7 +2248,7 @@ class GraphedSecureInference(_FormFields):
             self.labels = torch.zeros(self.batch, int(state_dict["fc.weight"].shape[0]), dtype=I64).to(self.device)
         self.dealer = Dealer(self.device, seed, self.fss_bits, self.fss_prg)
         self.dealer.tape, self.dealer.requests = [], []
-        ctx = SecureContext(self.dealer, base, precision_fractional)
+        ctx = SecureContext(self.dealer, base, precision_fractional, ring_mfma=self.ring_mfma)
         model = SecureResNet18(ctx, state_dict, input_size, blocks, form=form)
         self._n_model = len(self.dealer.tape)          # primitives consumed by sharing the model (kept)
         model(self.image, labels=self.labels)          # offline pass: fills the tape, warms every kernel
@@ -2243,7 +2257,7 @@ class GraphedSecureInference(_FormFields):
         self.stats = dict(ctx.stats)
         self._rehome_tape()                            # per-image random words -> one arena (before any pointer is captured)
         pre = PreloadedDealer(self.tape, self.device, self.fss_bits, self.fss_prg)
-        self._ctx = SecureContext(pre, base, precision_fractional)
+        self._ctx = SecureContext(pre, base, precision_fractional, ring_mfma=self.ring_mfma)
         self._model = SecureResNet18(self._ctx, state_dict, input_size, blocks, form=form)      # re-shares with the same masks
         self._model(self.image, labels=self.labels)    # eager pass over the static buffers: builds the pointer tables
         pre.pos, self._ctx._newton_calls = self._n_model, 0
@@ -2261,7 +2275,7 @@ class GraphedSecureInference(_FormFields):
             # own (this form's dealer draws on the device from here on, inside the refill graph)
             self._static_rows = self._model.kept[-1]
             tail_dealer = Dealer(self.device, None if seed is None else seed + 104729, self.fss_bits, self.fss_prg)
-            self._tail_ctx = SecureContext(tail_dealer, base, precision_fractional)
+            self._tail_ctx = SecureContext(tail_dealer, base, precision_fractional, ring_mfma=self.ring_mfma)
         # the provider's block counter moves to the device, behind everything the offline pass drew
         self._ctr = torch.tensor([self.dealer._block], dtype=I64).to(self.device)      # (uploaded: no fill kernel)
         self.dealer._block = None                      # (the host counter is dead from here on: rand64 would raise)
@@ -2358,6 +2372,7 @@ class GraphedSecureInference(_FormFields):
     def _refill_launches(self):
         d = self.dealer
         n = self._arena.numel()
+        self._ctx.apply_options()
         call("primia_chacha20_fill_ctr", *d._key, d._nonce, self._ctr, 0, self._arena, n)
         for op in self._ops:
             if op[0] == "triple":
@@ -2434,13 +2449,15 @@ class PipelinedSecureInference:
     `form` or its fields by keyword: `ProtocolForm`; every slot is built with the one form."""
 
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
-                 batch=1, *, form=None, **options):
+                 batch=1, *, form=None, ring_mfma=False, **options):
         self.form = form = ProtocolForm.of(form, **options)
+        self.ring_mfma = bool(ring_mfma)
         self.device = torch.device(device)
         if form.reveal in ACCUMULATING:
             raise ValueError(f'reveal="{form.reveal}" accumulates in one set of static buffers: use GraphedSecureInference')
         self.slots = [GraphedSecureInference(state_dict, device, input_size, precision_fractional, base,
-                                             None if seed is None else seed + 7919 * k, blocks, batch, form=form)
+                                             None if seed is None else seed + 7919 * k, blocks, batch, form=form,
+                                             ring_mfma=self.ring_mfma)
                       for k in range(slots)]
         self.stats = self.slots[0].stats
         self.dealer_stream = torch.cuda.Stream(device=self.device)
@@ -2625,16 +2642,17 @@ class DealerService:
                 send(v, kw.get("owner"))
 
 
-def party_context(link: PartyLink, precision_fractional=16, base=10, *, form=None, **options):
-    """SecureContext of the party this rank plays, at the width and with the truncation of the `ProtocolForm`."""
+def party_context(link: PartyLink, precision_fractional=16, base=10, *, form=None, ring_mfma=False, **options):
+    """SecureContext of the party this rank plays, at the width and with the truncation of the `ProtocolForm`; `ring_mfma` is
+    this rank's own choice of GEMM kernel (`SecureContext`)."""
     form = ProtocolForm.of(form, **options)
     return SecureContext(PartyDealer(link, form.fss_bits, form.fss_prg), base, precision_fractional,
                          opener=DistOpener(link.parties_group, link.role), party=link.role, link=link,
-                         faithful_trunc=form.faithful_trunc, conv_triples=form.conv_triples)
+                         faithful_trunc=form.faithful_trunc, conv_triples=form.conv_triples, ring_mfma=ring_mfma)
 
 
 def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None, images=None, seed=None, blocks=None,
-                   precision_fractional=16, base=10, batch=1, *, labels=None, form=None, **options):
+                   precision_fractional=16, base=10, batch=1, *, labels=None, form=None, ring_mfma=False, **options):
     """One rank's part of the three-role encrypted inference of inference.py:279-321.
     Party 0 passes `state_dict`, party 1 passes `images` (fp32 [n,3,S,S] on its GPU), the dealer neither;
     all know the architecture, the input size, the `ProtocolForm` (`form`, or its fields by keyword), how many images will be
@@ -2644,6 +2662,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     form = ProtocolForm.of(form, **options)
     form.check(norm_of(arch), base, precision_fractional)
     passes = (n_images + batch - 1) // batch
+    _lib.set_option("ring_mfma", int(bool(ring_mfma)))      # (a rank's own kernel choice; the dealer's triples multiply out on it too)
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
         image_req = image_requests(arch, input_size, batch, blocks, form=form)
         svc = DealerService(Dealer(link.device, seed, form.fss_bits, form.fss_prg), link)
@@ -2653,7 +2672,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
         if form.reveal == METRICS:      # the rank-count tail over every row held, padding rows included
             svc.serve(auc_requests(passes * batch, arch["fc.weight"][0]))
         return None
-    ctx = party_context(link, precision_fractional, base, form=form)
+    ctx = party_context(link, precision_fractional, base, form=form, ring_mfma=ring_mfma)
     if link.role == 0:
         if state_dict is None:
             raise ValueError("party 0 is the model owner: it needs the state dict")

@@ -22,6 +22,7 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    report names it when it is not 32)
     --fss_prg chacha: the comparison and equality keys from the ChaCha20 PRG (the report names it; default sha, the reference's)
     --conv_triples: convolution-shaped Beaver triples and the direct ring convolution (the report names it)
+    --ring_mfma:   the Z_2^64 GEMMs on int8 MFMA limbs (SecureContext(ring_mfma=True); the report names it)
     --fss-prg-kernels: fss.le of 2^20 comparisons for both parties and their key generation, under sha and under chacha in
                    alternation, at 32 and at 64 bits"""
 import argparse, dataclasses, json, os, sys, time
@@ -66,6 +67,8 @@ def main():
                     help="the PRG of the FSS keys (the report names it when it is chacha)")
     ap.add_argument("--conv_triples", action="store_true",
                     help="conv2d on triples of the convolution's own shape (the report names it)")
+    ap.add_argument("--ring_mfma", action="store_true",
+                    help="the Z_2^64 matrix products on int8 MFMA limbs, bit-equal to the default (the report names it)")
     ap.add_argument("--fss-prg-kernels", action="store_true",
                     help="time primia_dif_eval_local_prg and primia_dif_keygen_prg alone under both PRGs, alternating, at 32 and 64 bits")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
@@ -135,11 +138,13 @@ def main():
     # avg only, "norm" for group and folded only -- and in the order the report has always had)
     named = {**non_default(form), **({} if a.norm == "batch" else {"norm": a.norm})}
     form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits", "fss_prg", "conv_triples") if k in named}
+    if a.ring_mfma:      # (no field of the form: the kernel behind the same bits)
+        form_report["ring_mfma"] = True
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
     def run(dealer, share_model=True):
-        ctx = SecureContext(dealer, 10, a.pf)
+        ctx = SecureContext(dealer, 10, a.pf, ring_mfma=a.ring_mfma)
         model = SecureResNet18(ctx, sd, input_size=a.size, form=form)
         torch.cuda.synchronize(); t0 = time.perf_counter()
         out = model(img)
@@ -214,7 +219,8 @@ def main():
         B, reps = a.batch, max(a.images, 3)
         imgs = torch.randn(B, 3, a.size, a.size, generator=g).to(dev)
         free = torch.cuda.mem_get_info(dev)[0]
-        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, form=form)
+        gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, batch=B, form=form,
+                                    ring_mfma=a.ring_mfma)
         # (an evaluation's passes carry the data owner's labels: seeded, one per image)
         lab_kw = {"labels": torch.randint(0, 3, (B,), generator=g)} if a.reveal in ("confusion", "metrics") else {}
         gi(imgs, refill=False, **lab_kw); torch.cuda.synchronize()
@@ -245,7 +251,7 @@ def main():
             with_dealer = (time.perf_counter() - t0) * 1e3
             rows, classes = passes * B, int(sd["fc.weight"].shape[0])
             comparisons = tail_ctx.stats["dif_evals"] - evals0
-            pre = SecureContext(PreloadedDealer(tail_ctx.dealer.tape, dev, form.fss_bits, form.fss_prg), 10, a.pf)
+            pre = SecureContext(PreloadedDealer(tail_ctx.dealer.tape, dev, form.fss_bits, form.fss_prg), 10, a.pf, ring_mfma=a.ring_mfma)
             for u in gi._model.U:
                 u.zero_()
             t0 = time.perf_counter(); gi._model.finish(ctx=pre); torch.cuda.synchronize()
@@ -333,8 +339,9 @@ def main():
         try:
             from primia_amd.secure import GraphedSecureInference
 
-            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, form=form)
-            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, form.fss_bits, form.fss_prg), 10, a.pf)
+            gi = GraphedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=999, form=form,
+                                        ring_mfma=a.ring_mfma)
+            ctx_e = SecureContext(PreloadedDealer(gi.tape, dev, form.fss_bits, form.fss_prg), 10, a.pf, ring_mfma=a.ring_mfma)
             out_ref = SecureResNet18(ctx_e, sd, input_size=a.size, form=form)(img)
             assert torch.equal(gi(img, refill=False).cpu(), out_ref.cpu()), "graph replay must be bit-identical"
             torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -356,7 +363,8 @@ def main():
             # on its own stream while the other replays): wall time per image, every image on fresh primitives
             from primia_amd.secure import PipelinedSecureInference
 
-            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, form=form)
+            pi = PipelinedSecureInference(sd, dev, input_size=a.size, precision_fractional=a.pf, seed=555, form=form,
+                                          ring_mfma=a.ring_mfma)
             for _ in range(2):
                 pi(img)
             torch.cuda.synchronize(); t0 = time.perf_counter()
