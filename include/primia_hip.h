@@ -1402,7 +1402,13 @@ int primia_beaver_combine_matmul(int j, const int64_t* delta, const int64_t* eps
  * before anything is launched.  Nothing is allocated; every launch captures into a graph.
  *   primia_ring_conv2d        out = [out +] conv(x, w): the plain ring convolution (accumulate != 0 adds to out)
  *   primia_ring_conv2d_split  host query: the number of input-channel slices the launcher gives this geometry (combined
- *                             with 64-bit atomics; `jobs` = 2 for the two-party form primia_beaver_conv_local launches)
+ *                             with 64-bit atomics; `jobs` = 2 for the two-party form primia_beaver_conv_local launches),
+ *                             for the kernel primia_ring_conv2d_route names
+ *   primia_ring_conv2d_route  host query: the kernel every entry point below launches for this geometry under the current
+ *                             options -- 0 ring_conv_kernel (u64 products on the vector ALU), 1 ring_conv_mfma_kernel (option
+ *                             ring_mfma: signed 8-bit limbs on v_mfma_i32_16x16x64_i8, csrc/ring_conv_mfma.hip; 3 x 3 / 1,
+ *                             3 x 3 / 2 and 1 x 1 / 2, the same bits) -- or the error the entry points return for it.  The
+ *                             launcher reads the same decision (conv_plan, csrc/ring_conv.hip); conv2d: nn/functional.py:204-308
  *   primia_beaver_combine_conv  spdz_compute (mpc/spdz.py:63-122) of party j in {0,1} on opened delta [B][C][H][W] and eps
  *                             [O][C][R][S]: z = c + conv(delta, b [+ eps if j == 0]) + conv(a, eps), one launch of the
  *                             two-product kernel; `scratch` holds O*C*R*S int64 (b + eps, party 0 only; may be null for j = 1)
@@ -1417,6 +1423,7 @@ int primia_beaver_combine_matmul(int j, const int64_t* delta, const int64_t* eps
 int primia_ring_conv2d(const int64_t* x, const int64_t* w, int64_t* out, int B, int C, int H, int W, int O, int R, int S,
                        int stride, int pad, int accumulate, primia_stream_t stream);
 int primia_ring_conv2d_split(int B, int C, int H, int W, int O, int R, int S, int stride, int pad, int jobs);
+int primia_ring_conv2d_route(int B, int C, int H, int W, int O, int R, int S, int stride, int pad, int jobs);
 int primia_beaver_combine_conv(int j, const int64_t* delta, const int64_t* eps, const int64_t* a, const int64_t* b,
                                const int64_t* c, int64_t* z, int64_t* scratch, int B, int C, int H, int W, int O, int R, int S,
                                int stride, int pad, primia_stream_t stream);

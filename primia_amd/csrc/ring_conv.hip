@@ -23,31 +23,20 @@
 // A thread loads one filter row's NW = 3 ES + R input words into registers and reuses them over the S taps of that row: per
 // 16 multiply-adds it issues 4 ds_read_b64 of weights and NW / S of inputs, against 8 in ring_gemm_kernel.
 //
-// Products run on the vector ALU (v_mad_u64_u32 chains): there is no 64-bit integer MFMA.  The 8-bit-limb decomposition onto
-// v_mfma_i32_16x16x64_i8 serves the GEMM form (ring_gemm_mfma.hip, option ring_mfma); this kernel can take its staging and
-// matrix loop later.
+// Products run on the vector ALU (v_mad_u64_u32 chains): there is no 64-bit integer MFMA.  Under the option ring_mfma the
+// 3 x 3 / 1, 3 x 3 / 2 and 1 x 1 / 2 geometries run ring_conv_mfma_kernel instead (ring_conv_mfma.hip: the 8-bit-limb
+// decomposition of ring_gemm_mfma.hip on v_mfma_i32_16x16x64_i8, same grid, same sums, same bits); the stem's 7 x 7 / 2
+// stays here.  conv_route decides, conv_plan plans either kernel's slices, launch_conv launches what the plan names.
 //
 // Few tiles (one image in layer3 / layer4: 4 and 1 pixel tiles): the input channels are split over blockIdx.z and the slices
 // combined with 64-bit atomicAdd -- ring addition is associative, so the result is bit-identical whatever the order.  C is
 // then initialised with C0 (or zero) by a kernel of this file, never a memset node (see launch_gemm, ring.hip).
 // Nothing is allocated here: scratch is passed in, and every launch captures into a hipGraph.
 #include "common.h"
-#include "trunc_faithful.h"
+#include "options.h"
+#include "ring_conv_mfma.h"
 
 namespace primia {
-
-typedef unsigned long long u64;
-
-struct ConvJob {          // one convolution sum: C = C0 + conv(X1, W1) + conv(X2, W2); X2 / W2 and C0 may be null
-    const u64 *X1, *W1, *X2, *W2, *C0;
-    u64* C;
-};
-
-struct ConvGeom {
-    int B, C, H, W, O, Ho, Wo, pad;
-    int tiles_x, ptiles;      // 8 x 8 pixel tiles per row / per image
-    int csplit, cchunk;       // slices of the input channels, channels per slice (a multiple of the kernel's CC)
-};
 
 template <int R, int STRIDE>
 struct ConvCfg {
@@ -61,14 +50,6 @@ struct ConvCfg {
 };
 
 static inline int conv_cc(int R) { return R >= 5 ? 1 : (R >= 2 ? 4 : 16); }
-
-// a party's truncation of ITS share toward zero (sl_trunc, secure_local.hip), the exact quotient by faith_udiv's multiply
-// instead of a 64-bit division: the epilogue below holds 16 of them
-__device__ __forceinline__ u64 conv_trunc(u64 v, const FaithDiv& f) {
-    const int64_t sv = (int64_t)v;
-    const u64 q = faith_udiv(sv < 0 ? (u64)0 - v : v, f);
-    return sv < 0 ? (u64)0 - q : q;
-}
 
 // gridDim = (B * pixel tiles, ceil(O / 64), jobs * csplit).  f.d > 0 (csplit == 1 only): the sum is truncated toward zero
 // by f.d before it is stored -- a party's truncation of its product share, in the epilogue.
@@ -208,9 +189,18 @@ static inline int conv_blocks(long n) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
+// The kernel a supported geometry runs on: 1, ring_conv_mfma_kernel, under the option ring_mfma for every geometry but the
+// stem's 7 x 7 / 2 (C = 3: a tap's k would be 3 live bytes of 64); 0, ring_conv_kernel.  Read by conv_plan, and through it
+// by launch_conv and the host queries.
+static int conv_route(int R, int stride) {
+    (void)stride;
+    return PRIMIA_OPT(ring_mfma) != 0 && R != 7;
+}
+
 // The geometry a call names, checked before anything is launched: PRIMIA_OK and *g filled, or the error to return.
 // The channel split depends on the block count alone (as launch_gemm's on the tile count): with fewer than 256 blocks the
-// input channels are sliced to reach 512, never below 64 multiply-adds per output and slice, in whole chunks of CC channels.
+// input channels are sliced to reach 512, never below 64 multiply-adds per output and slice, in whole chunks of CC channels
+// (the limb kernel: conv_mfma_slices, whole chunks of 64 under its accumulators' bound).
 static int conv_plan(int B, int C, int H, int W, int O, int R, int S, int stride, int pad, int jobs, ConvGeom* g) {
     PRIMIA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && O > 0 && R > 0 && S > 0 && stride > 0 && pad >= 0 && pad < R &&
                    (jobs == 1 || jobs == 2));
@@ -226,6 +216,11 @@ static int conv_plan(int B, int C, int H, int W, int O, int R, int S, int stride
     PRIMIA_REQUIRE(gx <= 0x7fffffffL && gy <= 65535);
     const int cc = conv_cc(R);
     const long blocks = gx * gy * jobs;
+    g->route = conv_route(R, stride);
+    if (g->route) {
+        conv_mfma_slices(C, R * S, blocks, &g->csplit, &g->cchunk);
+        return PRIMIA_OK;
+    }
     int csplit = 1;
     if (blocks < 256) {
         csplit = (int)((512 + blocks - 1) / blocks);
@@ -251,7 +246,10 @@ static int launch_conv(const ConvJob* jobs, int njobs, const ConvGeom& g, int R,
     const ConvJob& a = jobs[0];
     const ConvJob& b = jobs[njobs - 1];
     const FaithDiv d = g.csplit == 1 ? f : FaithDiv{0, 0, 0, 0};
-    if (R == 7)
+    if (g.route) {
+        const int rc = launch_ring_conv_mfma(a, b, g, R, stride, d, grid, st);
+        if (rc != PRIMIA_OK) return rc;
+    } else if (R == 7)
         ring_conv_kernel<7, 2><<<grid, 256, 0, st>>>(a, b, g, d);
     else if (R == 3 && stride == 1)
         ring_conv_kernel<3, 1><<<grid, 256, 0, st>>>(a, b, g, d);
@@ -279,6 +277,12 @@ int primia_ring_conv2d_split(int B, int C, int H, int W, int O, int R, int S, in
     ConvGeom g;
     const int rc = conv_plan(B, C, H, W, O, R, S, stride, pad, jobs, &g);
     return rc != PRIMIA_OK ? rc : g.csplit;
+}
+
+int primia_ring_conv2d_route(int B, int C, int H, int W, int O, int R, int S, int stride, int pad, int jobs) {
+    ConvGeom g;
+    const int rc = conv_plan(B, C, H, W, O, R, S, stride, pad, jobs, &g);
+    return rc != PRIMIA_OK ? rc : g.route;
 }
 
 int64_t primia_beaver_conv_local_scratch_elems(int B, int C, int H, int W, int O, int R, int S) {

@@ -34,38 +34,10 @@
 
 namespace primia {
 
-typedef int rm_v4i __attribute__((ext_vector_type(4)));
-
 constexpr int kRmPitch = 80;
 constexpr int kRmPlane = 64 * kRmPitch;         // one limb plane of one operand
 constexpr int kRmOperand = 8 * kRmPlane;
 constexpr int kRmLds = 2 * kRmOperand;          // 81,920 B
-
-// 4 x 4 byte transpose: o_i byte r = a_r byte i (up to the fixed order of r that both operands share)
-__device__ __forceinline__ void rm_t4(unsigned a0, unsigned a1, unsigned a2, unsigned a3, unsigned& o0, unsigned& o1,
-                                      unsigned& o2, unsigned& o3) {
-    const unsigned t0 = __builtin_amdgcn_perm(a1, a0, 0x05010400u), t1 = __builtin_amdgcn_perm(a1, a0, 0x07030602u);
-    const unsigned t2 = __builtin_amdgcn_perm(a3, a2, 0x05010400u), t3 = __builtin_amdgcn_perm(a3, a2, 0x07030602u);
-    o0 = __builtin_amdgcn_perm(t2, t0, 0x05040100u);
-    o1 = __builtin_amdgcn_perm(t2, t0, 0x07060302u);
-    o2 = __builtin_amdgcn_perm(t3, t1, 0x05040100u);
-    o3 = __builtin_amdgcn_perm(t3, t1, 0x07060302u);
-}
-
-// 8 words of consecutive k -> 8 pieces, piece i the digits i of the 8 words
-__device__ __forceinline__ void rm_digits(const u64 (&w)[8], uint2 (&pl)[8]) {
-    unsigned lo[8], hi[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const u64 s = (w[r] + 0x8080808080808080ull) ^ 0x8080808080808080ull;
-        lo[r] = (unsigned)s;
-        hi[r] = (unsigned)(s >> 32);
-    }
-    rm_t4(lo[0], lo[1], lo[2], lo[3], pl[0].x, pl[1].x, pl[2].x, pl[3].x);
-    rm_t4(lo[4], lo[5], lo[6], lo[7], pl[0].y, pl[1].y, pl[2].y, pl[3].y);
-    rm_t4(hi[0], hi[1], hi[2], hi[3], pl[4].x, pl[5].x, pl[6].x, pl[7].x);
-    rm_t4(hi[4], hi[5], hi[6], hi[7], pl[4].y, pl[5].y, pl[6].y, pl[7].y);
-}
 
 __global__ __launch_bounds__(256, 2) void ring_gemm_mfma_kernel(RingMfmaArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -142,15 +114,7 @@ __global__ __launch_bounds__(256, 2) void ring_gemm_mfma_kernel(RingMfmaArgs g) 
 #pragma unroll
             for (int j = 0; j < 8; ++j) bq[j] = *(const rm_v4i*)(fb + j * kRmPlane + ni * 16 * kRmPitch);
 #pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const rm_v4i a = *(const rm_v4i*)(fa + i * kRmPlane + mi * 16 * kRmPitch);
-#pragma unroll
-                    for (int j = 0; j + i < 8; ++j)
-                        acc[mi][ni][i + j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bq[j], acc[mi][ni][i + j], 0, 0, 0);
-                }
-            }
+            for (int mi = 0; mi < 2; ++mi) rm_pairs(fa + mi * 16 * kRmPitch, kRmPlane, bq, acc[mi][ni]);
         }
         __syncthreads();
     }
@@ -166,9 +130,7 @@ __global__ __launch_bounds__(256, 2) void ring_gemm_mfma_kernel(RingMfmaArgs g) 
             for (int ni = 0; ni < 2; ++ni) {
                 const int gn = n0 + 32 * wn + 16 * ni + fr;
                 if (gn >= N) continue;
-                u64 v = 0;
-#pragma unroll
-                for (int d = 0; d < 8; ++d) v += (u64)(long long)acc[mi][ni][d][r] << (8 * d);
+                const u64 v = rm_combine(acc[mi][ni], r);
                 const long o = (long)gm * N + gn;
                 if (g.ksplit == 1)
                     sd.C[o] = v + (sd.C0 ? sd.C0[o] : (u64)0);

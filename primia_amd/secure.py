@@ -334,7 +334,8 @@ class SecureContext:
         faithful_trunc=True: conv2d, affine_eval and linear truncate their products with `trunc_faithful`, which no mask
         can make wrap, where the reference's per-share division is off by 2^64 / scale with probability |z| / 2^64.
         conv_triples=True: conv2d multiplies on a convolution-shaped triple (`ProtocolForm`), with no im2col operand.
-        ring_mfma=True: the Z_2^64 matrix products run on int8 MFMA limbs (the library's option `ring_mfma`, csrc/ring_gemm_mfma.hip):
+        ring_mfma=True: the Z_2^64 matrix products, and with conv_triples the direct 3 x 3 and 1 x 1 / 2 convolutions, run on int8 MFMA
+        limbs (the library's option `ring_mfma`, csrc/ring_gemm_mfma.hip, csrc/ring_conv_mfma.hip):
         the same bits from another kernel, so no part of the `ProtocolForm`.  The option is the PROCESS's: the context sets it here
         and before every pass of a model built on it; a captured graph keeps the kernel it was captured with."""
         self.dealer = dealer

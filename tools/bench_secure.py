@@ -22,7 +22,8 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    report names it when it is not 32)
     --fss_prg chacha: the comparison and equality keys from the ChaCha20 PRG (the report names it; default sha, the reference's)
     --conv_triples: convolution-shaped Beaver triples and the direct ring convolution (the report names it)
-    --ring_mfma:   the Z_2^64 GEMMs on int8 MFMA limbs (SecureContext(ring_mfma=True); the report names it)
+    --ring_mfma:   the Z_2^64 GEMMs on int8 MFMA limbs (SecureContext(ring_mfma=True); the report names it); with
+                   --conv_triples the direct convolutions too, and the report's "conv_route" names the kernel per geometry
     --fss-prg-kernels: fss.le of 2^20 comparisons for both parties and their key generation, under sha and under chacha in
                    alternation, at 32 and at 64 bits"""
 import argparse, dataclasses, json, os, sys, time
@@ -140,6 +141,11 @@ def main():
     form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits", "fss_prg", "conv_triples") if k in named}
     if a.ring_mfma:      # (no field of the form: the kernel behind the same bits)
         form_report["ring_mfma"] = True
+    if a.ring_mfma and a.conv_triples:      # the kernel per convolution geometry: 0 vector ALU, 1 int8 MFMA limbs
+        from primia_amd import _lib
+        _lib.set_option("ring_mfma", 1)      # (every context of this run sets it again)
+        form_report["conv_route"] = {f"{r}x{r}/{s}": _lib.query("primia_ring_conv2d_route", 1, c, 56, 56, 64, r, r, s, r // 2, 2)
+                                     for r, s, c in ((7, 2, 3), (3, 1, 64), (3, 2, 64), (1, 2, 64))}
     g = torch.Generator().manual_seed(1)
     img = torch.randn(1, 3, a.size, a.size, generator=g).to(dev)
 
