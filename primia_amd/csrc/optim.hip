@@ -92,14 +92,21 @@ struct AxpyFn {
     float* y;
     const float* x;
     float a;
+    // product rounded first, as torch.  __fmul_rn / __fadd_rn are a plain '*' and '+' to hipcc, which its default contraction
+    // fuses into one fma (1 ulp off): contraction is switched off for the two expressions instead.
+    __device__ __forceinline__ float upd(float y_, float x_) const {
+#pragma clang fp contract(off)
+        const float prod = x_ * a;
+        return y_ + prod;
+    }
     __device__ __forceinline__ void vec(long q) const {
         f32x4 v = ((f32x4*)y)[q];
         const f32x4 u = ((const f32x4*)x)[q];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = __fadd_rn(v[i], __fmul_rn(u[i], a));  // product rounded first, as torch
+        for (int i = 0; i < 4; ++i) v[i] = upd(v[i], u[i]);
         ((f32x4*)y)[q] = v;
     }
-    __device__ __forceinline__ void one(long i) const { y[i] = __fadd_rn(y[i], __fmul_rn(x[i], a)); }
+    __device__ __forceinline__ void one(long i) const { y[i] = upd(y[i], x[i]); }
 };
 
 struct DivFn {
