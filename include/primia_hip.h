@@ -1407,7 +1407,8 @@ int primia_beaver_combine_matmul(int j, const int64_t* delta, const int64_t* eps
  *   primia_ring_conv2d_route  host query: the kernel every entry point below launches for this geometry under the current
  *                             options -- 0 ring_conv_kernel (u64 products on the vector ALU), 1 ring_conv_mfma_kernel (option
  *                             ring_mfma: signed 8-bit limbs on v_mfma_i32_16x16x64_i8, csrc/ring_conv_mfma.hip; 3 x 3 / 1,
- *                             3 x 3 / 2 and 1 x 1 / 2, the same bits) -- or the error the entry points return for it.  The
+ *                             3 x 3 / 2 and 1 x 1 / 2, the same bits) or, from ring_mfma = 2 on, ring_conv_stem_mfma_kernel for
+ *                             7 x 7 / 2 with C <= 4 (csrc/ring_conv_stem_mfma.hip; never sliced: the split is 1) -- or the error the entry points return for it.  The
  *                             launcher reads the same decision (conv_plan, csrc/ring_conv.hip); conv2d: nn/functional.py:204-308
  *   primia_beaver_combine_conv  spdz_compute (mpc/spdz.py:63-122) of party j in {0,1} on opened delta [B][C][H][W] and eps
  *                             [O][C][R][S]: z = c + conv(delta, b [+ eps if j == 0]) + conv(a, eps), one launch of the

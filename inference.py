@@ -234,12 +234,13 @@ if __name__ == "__main__":
                              "against 14.7 M), a pass holds 200 MB less in primitives per image and writes no im2col operand. "
                              " The products are the same, the shares differ (other masks); defined here, not by the reference "
                              "(DESIGN.md §4).  With every other option")
-    parser.add_argument("--ring_mfma", action="store_true",
+    parser.add_argument("--ring_mfma", nargs="?", type=int, const=1, default=0, choices=(0, 1, 2), metavar="LEVEL",
                         help="encrypted inference: the Z_2^64 matrix products (every Beaver matmul, and the dealer's triples) on "
                              "the matrix pipe -- signed 8-bit limbs through v_mfma_i32_16x16x64_i8 with exact carry "
                              "reconstruction -- where the default multiplies 64-bit words on the vector ALU.  The same bits from "
-                             "another kernel: nothing the parties exchange or agree on changes (DESIGN.md §7).  With every other "
-                             "option")
+                             "another kernel: nothing the parties exchange or agree on changes (DESIGN.md §7).  LEVEL 1 (the "
+                             "bare flag): those products, and with --conv_triples the direct 3 x 3 and 1 x 1 / 2 convolutions; "
+                             "LEVEL 2: the 7 x 7 / 2 stem convolution of --conv_triples as well.  With every other option")
     parser.add_argument("--hip_graph", action="store_true",
                         help="encrypted inference: capture the online phase once as a hipGraph and replay it per image "
                              "(the dealer refills the primitive buffers between images)")

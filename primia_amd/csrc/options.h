@@ -12,7 +12,7 @@ namespace primia {
     X(c64_blocks, 512)      /* persistent blocks of conv3x3_c64_kernel (2 per CU) */                                   \
     X(c64_dbg, 0)           /* timing experiments only (results are WRONG when set): conv3x3_c64_kernel's debug bits */           \
     X(c64_stages, 4)        /* ring depth of conv3x3_c64_kernel: 3 | 4 */                                              \
-    X(ring_mfma, 0)         /* 1: the Z_2^64 GEMMs of the encrypted path run ring_gemm_mfma_kernel (int8 limbs on v_mfma_i32_16x16x64_i8, bit-equal); and its direct 3x3 / 1, 3x3 / 2 and 1x1 / 2 convolutions ring_conv_mfma_kernel; 0: ring_gemm_kernel / ring_gemm2_kernel / ring_conv_kernel on the vector ALU.  Read at launch: a captured graph keeps its kernel */ \
+    X(ring_mfma, 0)         /* 1: the Z_2^64 GEMMs of the encrypted path run ring_gemm_mfma_kernel (int8 limbs on v_mfma_i32_16x16x64_i8, bit-equal); and its direct 3x3 / 1, 3x3 / 2 and 1x1 / 2 convolutions ring_conv_mfma_kernel; 2: as 1, and the 7x7 / 2 convolutions of at most 4 input channels (the stem) ring_conv_stem_mfma_kernel; 0: ring_gemm_kernel / ring_gemm2_kernel / ring_conv_kernel on the vector ALU.  Read at launch: a captured graph keeps its kernel */ \
     X(s2lh, 1)             /* transition blocks on conv_s2lh_kernel (parity planes, linear halo), bits: 1 dgrad of <= 64-channel dx, 2 forward, 4 dgrad at every width; 0: implicit GEMM */ \
     X(s2lh_dbg, 0)          /* measurement only (wrong results): 1 no halo DMA after the prologue, 2 no weight DMA, 4 no MFMA, 8 no stores, 16 no write-back, 32 no BN partials, 64 linear halo */
 

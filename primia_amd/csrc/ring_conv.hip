@@ -26,7 +26,8 @@
 // Products run on the vector ALU (v_mad_u64_u32 chains): there is no 64-bit integer MFMA.  Under the option ring_mfma the
 // 3 x 3 / 1, 3 x 3 / 2 and 1 x 1 / 2 geometries run ring_conv_mfma_kernel instead (ring_conv_mfma.hip: the 8-bit-limb
 // decomposition of ring_gemm_mfma.hip on v_mfma_i32_16x16x64_i8, same grid, same sums, same bits); the stem's 7 x 7 / 2
-// stays here.  conv_route decides, conv_plan plans either kernel's slices, launch_conv launches what the plan names.
+// stays here at ring_mfma = 1 and runs ring_conv_stem_mfma_kernel (ring_conv_stem_mfma.hip: taps packed into k, C <= 4) at
+// ring_mfma = 2.  conv_route decides, conv_plan plans either kernel's slices, launch_conv launches what the plan names.
 //
 // Few tiles (one image in layer3 / layer4: 4 and 1 pixel tiles): the input channels are split over blockIdx.z and the slices
 // combined with 64-bit atomicAdd -- ring addition is associative, so the result is bit-identical whatever the order.  C is
@@ -189,18 +190,20 @@ static inline int conv_blocks(long n) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-// The kernel a supported geometry runs on: 1, ring_conv_mfma_kernel, under the option ring_mfma for every geometry but the
-// stem's 7 x 7 / 2 (C = 3: a tap's k would be 3 live bytes of 64); 0, ring_conv_kernel.  Read by conv_plan, and through it
-// by launch_conv and the host queries.
-static int conv_route(int R, int stride) {
-    (void)stride;
-    return PRIMIA_OPT(ring_mfma) != 0 && R != 7;
+// The kernel a supported geometry runs on: 1, the limb kernels -- ring_conv_mfma_kernel under the option ring_mfma for every
+// geometry but 7 x 7 / 2 (a tap's k would be C live bytes of 64), and ring_conv_stem_mfma_kernel for 7 x 7 / 2 with C <= 4
+// from ring_mfma = 2 on (taps packed into k); 0, ring_conv_kernel.  Read by conv_plan, and through it by launch_conv and the
+// host queries.
+static int conv_route(int R, int stride, int C) {
+    const int level = PRIMIA_OPT(ring_mfma);
+    if (R == 7) return level >= 2 && stride == 2 && C <= kCsMaxC;
+    return level != 0;
 }
 
 // The geometry a call names, checked before anything is launched: PRIMIA_OK and *g filled, or the error to return.
 // The channel split depends on the block count alone (as launch_gemm's on the tile count): with fewer than 256 blocks the
 // input channels are sliced to reach 512, never below 64 multiply-adds per output and slice, in whole chunks of CC channels
-// (the limb kernel: conv_mfma_slices, whole chunks of 64 under its accumulators' bound).
+// (the limb kernel: conv_mfma_slices, whole chunks of 64 under its accumulators' bound; its 7 x 7 / 2 form: one slice).
 static int conv_plan(int B, int C, int H, int W, int O, int R, int S, int stride, int pad, int jobs, ConvGeom* g) {
     PRIMIA_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && O > 0 && R > 0 && S > 0 && stride > 0 && pad >= 0 && pad < R &&
                    (jobs == 1 || jobs == 2));
@@ -216,7 +219,11 @@ static int conv_plan(int B, int C, int H, int W, int O, int R, int S, int stride
     PRIMIA_REQUIRE(gx <= 0x7fffffffL && gy <= 65535);
     const int cc = conv_cc(R);
     const long blocks = gx * gy * jobs;
-    g->route = conv_route(R, stride);
+    g->route = conv_route(R, stride, C);
+    if (g->route && R == 7) {      // the thin-channel kernel holds every channel in one k step: never sliced
+        g->csplit = 1, g->cchunk = C;
+        return PRIMIA_OK;
+    }
     if (g->route) {
         conv_mfma_slices(C, R * S, blocks, &g->csplit, &g->cchunk);
         return PRIMIA_OK;

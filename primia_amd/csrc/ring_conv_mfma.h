@@ -1,5 +1,5 @@
-// Ring convolution on int8 MFMA limbs (ring_conv_mfma.hip; DESIGN.md §7, "Ring convolution on int8 MFMA limbs"): what
-// ring_conv.hip -- the planner, the launcher and the vector-ALU kernel -- shares with the limb kernel's file.
+// Ring convolution on int8 MFMA limbs (ring_conv_mfma.hip, ring_conv_stem_mfma.hip; DESIGN.md §7, "Ring convolution on int8
+// MFMA limbs"): what ring_conv.hip -- the planner, the launcher and the vector-ALU kernel -- shares with the limb kernels' files.
 #pragma once
 #include "ring_gemm_mfma.h"
 #include "trunc_faithful.h"
@@ -15,7 +15,8 @@ struct ConvGeom {
     int B, C, H, W, O, Ho, Wo, pad;
     int tiles_x, ptiles;      // 8 x 8 pixel tiles per row / per image
     int csplit, cchunk;       // slices of the input channels, channels per slice (a multiple of the kernel's chunk)
-    int route;                // 0: ring_conv_kernel (vector ALU), 1: ring_conv_mfma_kernel -- conv_route's answer
+    int route;                // 0: ring_conv_kernel (vector ALU), 1: the limb kernels (ring_conv_mfma_kernel, 7 x 7 / 2:
+                              // ring_conv_stem_mfma_kernel) -- conv_route's answer
 };
 
 // a party's truncation of ITS share toward zero (sl_trunc, secure_local.hip), the exact quotient by faith_udiv's multiply
@@ -44,8 +45,12 @@ inline void conv_mfma_slices(int C, int taps, long blocks, int* csplit, int* cch
     *cchunk = per * kCmChunk;
 }
 
-// g.route == 1, (R, stride) in {(3, 1), (3, 2), (1, 2)}; C must hold C0 (or zero) already when g.csplit > 1
+constexpr int kCsMaxC = 4;        // the thin-channel 7 x 7 / 2 kernel: a pixel's channels are the 4 bytes of one dword per limb
+
+// g.route == 1, (R, stride) in {(3, 1), (3, 2), (1, 2), (7, 2)}; C must hold C0 (or zero) already when g.csplit > 1
 int launch_ring_conv_mfma(const ConvJob& a, const ConvJob& b, const ConvGeom& g, int R, int stride, FaithDiv f, dim3 grid,
                           hipStream_t st);
+// 7 x 7 / 2 with g.C <= kCsMaxC and g.csplit == 1 (ring_conv_stem_mfma.hip)
+int launch_ring_conv_stem_mfma(const ConvJob& a, const ConvJob& b, const ConvGeom& g, FaithDiv f, dim3 grid, hipStream_t st);
 
 }  // namespace primia

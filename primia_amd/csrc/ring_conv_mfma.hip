@@ -3,7 +3,8 @@
 //
 //     C = C0 + conv(X1, W1) + conv(X2, W2)   mod 2^64,   X [B][C][H][W], W [O][C][R][S], C [B][O][Ho][Wo], zero padded
 //
-// through v_mfma_i32_16x16x64_i8 on signed 8-bit limbs, for 3 x 3 / 1, 3 x 3 / 2 and 1 x 1 / 2.  The arithmetic is
+// through v_mfma_i32_16x16x64_i8 on signed 8-bit limbs, for 3 x 3 / 1, 3 x 3 / 2 and 1 x 1 / 2 (the thin-channel 7 x 7 / 2 has a k
+// layout of its own, taps and not channels: ring_conv_stem_mfma.hip, ring_mfma = 2).  The arithmetic is
 // ring_gemm_mfma.hip's and its device functions are shared (ring_gemm_mfma.h): rm_digits recodes 8 words into 8 limb pieces,
 // rm_pairs runs the 36 digit pairs of a fragment pair onto 8 diagonal i32 accumulators, rm_combine shifts and adds them once.
 // Integer arithmetic throughout: the result is the bits of ring_conv_kernel.  Builtins only.
@@ -273,6 +274,7 @@ int launch_ring_conv_mfma(const ConvJob& a, const ConvJob& b, const ConvGeom& g,
     if (R == 3 && stride == 1) return launch_cm<3, 1>(a, b, g, f, grid, st);
     if (R == 3 && stride == 2) return launch_cm<3, 2>(a, b, g, f, grid, st);
     if (R == 1 && stride == 2) return launch_cm<1, 2>(a, b, g, f, grid, st);
+    if (R == 7 && stride == 2) return launch_ring_conv_stem_mfma(a, b, g, f, grid, st);
     return PRIMIA_ERR_UNSUPPORTED;
 }
 

@@ -55,6 +55,17 @@ FSS_PRG = "sha"
 _PRG_ENTRY = ("dif_keygen", "dif_eval", "dif_eval_local")      # the DIF entry points a PRG has a form of (the rest hash nothing)
 
 
+# The library's option `ring_mfma` as every constructor and CLI here takes it: False / 0 the vector-ALU kernels, True / 1 the
+# Z_2^64 GEMMs and the direct 3 x 3 and 1 x 1 / 2 convolutions on int8 MFMA limbs, 2 the 7 x 7 / 2 stem convolution as well.
+RING_MFMA_LEVELS = (0, 1, 2)
+
+
+def ring_mfma_level(value):
+    if isinstance(value, (bool, int)) and int(value) in RING_MFMA_LEVELS:
+        return int(value)
+    raise ValueError(f"ring_mfma must be False, True or one of {RING_MFMA_LEVELS}, got {value!r}")
+
+
 def check_fss_prg(prg):
     if prg not in FSS_PRGS:
         raise ValueError(f"fss_prg must be one of {' / '.join(map(repr, FSS_PRGS))}, got {prg!r}")
@@ -334,12 +345,13 @@ class SecureContext:
         faithful_trunc=True: conv2d, affine_eval and linear truncate their products with `trunc_faithful`, which no mask
         can make wrap, where the reference's per-share division is off by 2^64 / scale with probability |z| / 2^64.
         conv_triples=True: conv2d multiplies on a convolution-shaped triple (`ProtocolForm`), with no im2col operand.
-        ring_mfma=True: the Z_2^64 matrix products, and with conv_triples the direct 3 x 3 and 1 x 1 / 2 convolutions, run on int8 MFMA
-        limbs (the library's option `ring_mfma`, csrc/ring_gemm_mfma.hip, csrc/ring_conv_mfma.hip):
+        ring_mfma=True (or 1): the Z_2^64 matrix products, and with conv_triples the direct 3 x 3 and 1 x 1 / 2 convolutions, run on int8 MFMA
+        limbs (the library's option `ring_mfma`, csrc/ring_gemm_mfma.hip, csrc/ring_conv_mfma.hip); ring_mfma=2: the 7 x 7 / 2 stem
+        convolution too (csrc/ring_conv_stem_mfma.hip); anything but False / True / 0 / 1 / 2 is a ValueError (`ring_mfma_level`):
         the same bits from another kernel, so no part of the `ProtocolForm`.  The option is the PROCESS's: the context sets it here
         and before every pass of a model built on it; a captured graph keeps the kernel it was captured with."""
         self.dealer = dealer
-        self.ring_mfma = bool(ring_mfma)
+        self.ring_mfma = ring_mfma_level(ring_mfma)
         self.apply_options()
         self.faithful_trunc = bool(faithful_trunc)
         self.conv_triples = bool(conv_triples)
@@ -363,7 +375,7 @@ class SecureContext:
 
     def apply_options(self):
         """Set the library's process-wide options this context asks for (read on the host when a kernel is launched)."""
-        _lib.set_option("ring_mfma", int(self.ring_mfma))
+        _lib.set_option("ring_mfma", ring_mfma_level(self.ring_mfma))
 
     @property
     def fss_bits(self):
@@ -1774,7 +1786,7 @@ class SecureResNet18(_FormFields):
         norm=None: "folded" when the state dict has bn1.scale, "group" when it has no bn1.running_mean, else "batch"; an
         explicit value must agree.
         `form` or its fields by keyword: `ProtocolForm` (the width is the context's dealer's; a faithful context makes it faithful, one with
-        conv_triples set makes it use them).  ring_mfma: None keeps the context's choice of GEMM kernel, a bool sets it."""
+        conv_triples set makes it use them).  ring_mfma: None keeps the context's choice of kernels, a bool or a level sets it."""
         form = ProtocolForm.of(form, **options)
         self.ctx = ctx
         self.input_size = input_size
@@ -1788,7 +1800,7 @@ class SecureResNet18(_FormFields):
             image_requests(architecture_of(state_dict), input_size, 1, self.blocks, form=self.form)
         ctx.faithful_trunc, ctx.conv_triples = self.form.faithful_trunc, self.form.conv_triples
         if ring_mfma is not None:
-            ctx.ring_mfma = bool(ring_mfma)
+            ctx.ring_mfma = ring_mfma_level(ring_mfma)
         ctx.apply_options()      # (sharing the model multiplies nothing; every pass sets them again)
         if self.norm == "group":
             for n in _norm_prefixes(state_dict.keys(), self.blocks):
@@ -2228,7 +2240,7 @@ class GraphedSecureInference(_FormFields):
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, batch=1,
                  memory_budget=None, *, form=None, ring_mfma=False, **options):
         self.form = form = ProtocolForm.of(form, **options)
-        self.ring_mfma = bool(ring_mfma)      # (both graphs are captured with this kernel; the eager refill sets it again)
+        self.ring_mfma = ring_mfma_level(ring_mfma)      # (both graphs are captured with this kernel; the eager refill sets it again)
         self.device = torch.device(device)
         self.batch = int(batch)
         if self.batch < 1:
@@ -2452,7 +2464,7 @@ class PipelinedSecureInference:
     def __init__(self, state_dict, device, input_size=224, precision_fractional=16, base=10, seed=None, blocks=None, slots=2,
                  batch=1, *, form=None, ring_mfma=False, **options):
         self.form = form = ProtocolForm.of(form, **options)
-        self.ring_mfma = bool(ring_mfma)
+        self.ring_mfma = ring_mfma_level(ring_mfma)
         self.device = torch.device(device)
         if form.reveal in ACCUMULATING:
             raise ValueError(f'reveal="{form.reveal}" accumulates in one set of static buffers: use GraphedSecureInference')
@@ -2663,7 +2675,7 @@ def run_three_role(link: PartyLink, arch, input_size, n_images, state_dict=None,
     form = ProtocolForm.of(form, **options)
     form.check(norm_of(arch), base, precision_fractional)
     passes = (n_images + batch - 1) // batch
-    _lib.set_option("ring_mfma", int(bool(ring_mfma)))      # (a rank's own kernel choice; the dealer's triples multiply out on it too)
+    _lib.set_option("ring_mfma", ring_mfma_level(ring_mfma))      # (a rank's own kernel choice; the dealer's triples multiply out on it too)
     if link.role == "dealer":      # follows the public schedule, derived on the host: this rank runs no layer kernel
         image_req = image_requests(arch, input_size, batch, blocks, form=form)
         svc = DealerService(Dealer(link.device, seed, form.fss_bits, form.fss_prg), link)

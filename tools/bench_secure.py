@@ -22,8 +22,9 @@ ms/image for the online phase (primitives pre-provisioned) and for the dealer (t
                    report names it when it is not 32)
     --fss_prg chacha: the comparison and equality keys from the ChaCha20 PRG (the report names it; default sha, the reference's)
     --conv_triples: convolution-shaped Beaver triples and the direct ring convolution (the report names it)
-    --ring_mfma:   the Z_2^64 GEMMs on int8 MFMA limbs (SecureContext(ring_mfma=True); the report names it); with
-                   --conv_triples the direct convolutions too, and the report's "conv_route" names the kernel per geometry
+    --ring_mfma [LEVEL]: the Z_2^64 GEMMs on int8 MFMA limbs (SecureContext(ring_mfma=LEVEL); the report names it; DESIGN.md §7);
+                   with --conv_triples the direct convolutions too -- LEVEL 1 (the bare flag) all but the 7 x 7 / 2 stem, LEVEL 2 the
+                   stem as well -- and the report's "conv_route" names the kernel per geometry at that level
     --fss-prg-kernels: fss.le of 2^20 comparisons for both parties and their key generation, under sha and under chacha in
                    alternation, at 32 and at 64 bits"""
 import argparse, dataclasses, json, os, sys, time
@@ -68,8 +69,9 @@ def main():
                     help="the PRG of the FSS keys (the report names it when it is chacha)")
     ap.add_argument("--conv_triples", action="store_true",
                     help="conv2d on triples of the convolution's own shape (the report names it)")
-    ap.add_argument("--ring_mfma", action="store_true",
-                    help="the Z_2^64 matrix products on int8 MFMA limbs, bit-equal to the default (the report names it)")
+    ap.add_argument("--ring_mfma", nargs="?", type=int, const=1, default=0, choices=(0, 1, 2), metavar="LEVEL",
+                    help="the Z_2^64 matrix products on int8 MFMA limbs, bit-equal to the default (the report names it); LEVEL 1 "
+                         "(the bare flag) or 2: with --conv_triples the 7 x 7 / 2 stem convolution too")
     ap.add_argument("--fss-prg-kernels", action="store_true",
                     help="time primia_dif_eval_local_prg and primia_dif_keygen_prg alone under both PRGs, alternating, at 32 and 64 bits")
     ap.add_argument("--cpu-sample", action="store_true", help="also time the CPU oracle on a bounded sample")
@@ -140,10 +142,10 @@ def main():
     named = {**non_default(form), **({} if a.norm == "batch" else {"norm": a.norm})}
     form_report = {k: named[k] for k in ("pooling", "norm", "wide_norm", "faithful_trunc", "reveal", "fss_bits", "fss_prg", "conv_triples") if k in named}
     if a.ring_mfma:      # (no field of the form: the kernel behind the same bits)
-        form_report["ring_mfma"] = True
+        form_report["ring_mfma"] = True if a.ring_mfma == 1 else a.ring_mfma
     if a.ring_mfma and a.conv_triples:      # the kernel per convolution geometry: 0 vector ALU, 1 int8 MFMA limbs
         from primia_amd import _lib
-        _lib.set_option("ring_mfma", 1)      # (every context of this run sets it again)
+        _lib.set_option("ring_mfma", a.ring_mfma)      # (every context of this run sets it again)
         form_report["conv_route"] = {f"{r}x{r}/{s}": _lib.query("primia_ring_conv2d_route", 1, c, 56, 56, 64, r, r, s, r // 2, 2)
                                      for r, s, c in ((7, 2, 3), (3, 1, 64), (3, 2, 64), (1, 2, 64))}
     g = torch.Generator().manual_seed(1)
